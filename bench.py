@@ -3,6 +3,7 @@
 (1024 random spheres, 3840x2160, 8 spp, depth 8), strips sharded over N GPUs.
 
     python bench.py --gpus N --steps K --warmup W [--workload c2|c3|c4|c5|mesh] [--strong]
+    python bench.py ... --dump-outputs DIR       (also write the last timed step's output strips to DIR/*.npy)
 
 A "step" is one pass of the hot path over one batch of synthetic input: every rank renders the strips it owns of the
 job.  Default = weak scaling: N frames of the workload at N GPUs, unit (frame f, strip d) goes to rank (f + d) % N.
@@ -86,7 +87,38 @@ def parse_args():
                     help="torch.distributed backend for the barrier / timing reduce (gloo: rehearsal on one GPU)")
     ap.add_argument("--share-device", action="store_true",
                     help="rehearsal only: all ranks use GPU 0 (a one-GPU box cannot run RCCL with 2 ranks)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the RGB8 strips the last timed step rendered to DIR/*.npy (float32; a "
+                         "fixed, seeded sample of the pixels if the whole would exceed 64 MB) so that two builds can be compared")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.frame:
+        ap.error("--dump-outputs writes the timed tile path's output; --frame does not run it")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6          # --dump-outputs: all files of all ranks together
+
+
+def dump_outputs(dirname: str, img, units, rank: int, world: int) -> None:
+    """Write what the last timed step returned to its caller: the rank's output strips, RGB8 as float32, in the order of
+    `units` (frame, strip).  Above the byte budget: the RGB of a sorted sample of flat pixel indices drawn with a fixed
+    seed, stored beside the values, so that the same arguments always select the same pixels."""
+    import numpy as np
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    budget = DUMP_BUDGET_BYTES // world - 4096          # (.npy headers)
+    np.save(d / f"units{tag}.npy", np.asarray(units, dtype=np.float64).reshape(-1, 2))
+    if img.size * 4 <= budget:
+        np.save(d / f"image{tag}.npy", img.astype(np.float32))
+        return
+    pix = img.reshape(-1, 3)
+    k = budget // (3 * 4 + 8)               # float32 RGB + float64 flat pixel index per sampled pixel
+    idx = np.sort(np.random.default_rng(0x5EED).choice(len(pix), size=k, replace=False))
+    np.save(d / f"image_sample{tag}.npy", pix[idx].astype(np.float32))
+    np.save(d / f"image_sample_index{tag}.npy", idx.astype(np.float64))
 
 
 def effective_cpus() -> int:
@@ -330,6 +362,11 @@ def main():
     barrier()
     t1 = time.perf_counter()
     st = scene.collect()
+    if args.dump_outputs:
+        # before the passes below, which render into the same buffer; with --overlap the last step went to its own lane
+        last = out if not args.overlap or (step_no[0] - 1) % len(lanes) == 0 else keep[(step_no[0] - 1) % len(lanes) - 1][0]
+        img = last.cpu().numpy().reshape(len(units), rq0.height // rq0.divisions, rq0.width, 3)
+        dump_outputs(args.dump_outputs, img, units, rank, world)
 
     elapsed = t1 - t0
     segs = float(st.ray_segments)
