@@ -277,6 +277,44 @@ RT_API int rt_scene_render_tiles(rt_scene* scene, const rt_tile_request* reqs, u
                                  uint8_t* const* out_rgb, size_t out_len_each,
                                  float* const* out_f32, rt_tile_stats* stats);
 
+/* ---- progressive rendering: a strip's samples in passes over a running sum ------- */
+/* Replaces the one-shot sample loop of slave main.rs:73-81 (`for _ in 0..sample_count { pix_color += ray_color(..) }`, then
+ * mean, gamma and quantise) with passes that a caller can preview, bound in time, stop or continue.
+ *
+ * A PASS renders samples [sample_begin, sample_end) of the S = req->spp sample image; 0 <= sample_begin < sample_end <= S,
+ * else RT_ERR_BAD_ARG (and nothing is launched).  Every check of the one-pass entry points applies as well.
+ *   - Sample s of a pixel draws from exactly the stream it draws from in one pass: seed + 4 PHI ((y W + x) S + s) (`seed`
+ *     above), S being the JOB's spp, not sample_end - sample_begin.
+ *   - accum: Hs*W*3 floats laid out like out_f32, in/out, the pixels' RAW colour sums (not means).  For sample_begin > 0 each
+ *     pixel's sum starts from accum; for sample_begin == 0 it starts from 0 and accum is not read (it may be uninitialised).
+ *     After the pass accum holds the sum over samples [0, sample_end), added one sample at a time in the order s = 0, 1, ...
+ *     NULL: RT_ERR_BAD_ARG.
+ *   - out_rgb / out_f32 (optional, as for rt_scene_render_tile) receive the preview sqrt(accum / sample_end), quantised as
+ *     main.rs:78-81 does.
+ *   - The f32 sum of a pixel after [0, k) is a prefix of the one-pass sum, so the pass with sample_end == S writes out_rgb and
+ *     out_f32 BIT-IDENTICAL to rt_scene_render_tile of the same request, however [0, S) was split into passes.
+ *   - A preview at sample_end < S is NOT the image of a one-pass render with spp = sample_end: that one draws from other
+ *     streams (its stride is sample_end).
+ *   - Counters cover the pass: primary_rays = Hs*W*(sample_end - sample_begin); the ray_segments of the passes add up to the
+ *     one-pass count.
+ * Scratch and every launch parameter are sized by the samples of the PASS: a job at RT_MAX_SPP in passes of 64 keeps the
+ * sample-unit ring at its 64-sample size.   */
+
+/* Host buffers, synchronous.  accum (Hs*W*3 floats) is uploaded when sample_begin > 0 and always downloaded. */
+RT_API int rt_scene_render_tile_pass(rt_scene* scene, const rt_tile_request* req,
+                                     uint32_t sample_begin, uint32_t sample_end, float* accum,
+                                     uint8_t* out_rgb, size_t out_len,
+                                     float* out_f32, rt_tile_stats* stats);
+
+/* Batched device form: the strips of one frame in a single launch (per 64 strips), asynchronous on hip_stream, under the rules of
+ * rt_scene_render_tiles_device (same frame-level fields, counters accumulate until rt_scene_collect).  d_accum[i] is the
+ * device running sum of strip i (no NULL entry). */
+RT_API int rt_scene_render_tiles_pass_device(rt_scene* scene, const rt_tile_request* reqs, uint32_t n,
+                                             uint32_t sample_begin, uint32_t sample_end,
+                                             void* const* d_accum,
+                                             void* const* d_out_rgb, size_t out_len_each,
+                                             void* const* d_out_f32, void* hip_stream);
+
 /* Wait for all work enqueued on the scene, return accumulated counters / event time
  * since the previous collect, and reset them. */
 RT_API int rt_scene_collect(rt_scene* scene, rt_tile_stats* stats);

@@ -207,6 +207,12 @@ def _bind(path: Path) -> C.CDLL:
     lib.rt_scene_render_tiles.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.POINTER(vp), C.c_size_t,
                                           C.POINTER(vp), C.POINTER(TileStats)]
     lib.rt_scene_render_tiles.restype = C.c_int
+    lib.rt_scene_render_tile_pass.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.c_uint32, f32p, u8p, C.c_size_t, f32p,
+                                              C.POINTER(TileStats)]
+    lib.rt_scene_render_tile_pass.restype = C.c_int
+    lib.rt_scene_render_tiles_pass_device.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp),
+                                                      C.POINTER(vp), C.c_size_t, C.POINTER(vp), vp]
+    lib.rt_scene_render_tiles_pass_device.restype = C.c_int
     lib.rt_scene_collect.argtypes = [vp, C.POINTER(TileStats)]
     lib.rt_scene_collect.restype = C.c_int
     lib.rt_render_frame.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(TileRequest), vp, C.c_uint32,

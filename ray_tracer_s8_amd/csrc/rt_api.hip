@@ -197,6 +197,8 @@ struct rt_scene {
     size_t d_out_cap = 0;
     float* d_outf = nullptr;
     size_t d_outf_cap = 0;
+    float* d_acc = nullptr;             // ... and for the running sums of rt_scene_render_tile_pass
+    size_t d_acc_cap = 0;
     // HIP-event bookkeeping of launches not yet collected
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, free_ev;
     uint64_t primary_rays = 0;
@@ -279,15 +281,28 @@ bool same_frame(const rt_tile_request& a, const rt_tile_request& b) {
 // Caller holds sc->mu and has the device current.
 // d_strip_cost: optional device array of COST_COPIES x MAX_BATCH counters (zeroed by the caller, on `stream`): the kernels add the ray
 // segments of strip i of the batch to [copy][i] (KParams::strip_cost); the caller sums the copies.
+// pass: a progressive pass (rt_scene_render_tile_pass) — samples [begin, end) of the request's spp, the strips' running sums in
+// d_acc[i] (checked by the caller: begin < end <= spp, no NULL entry).  nullptr: all spp samples, no sum carried (one pass).
+struct Pass {
+    uint32_t begin, end;
+    void* const* d_acc;
+};
 int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* const* d_rgb, void* const* d_f32,
-                 hipStream_t stream, unsigned long long* d_strip_cost = nullptr) {
+                 hipStream_t stream, unsigned long long* d_strip_cost = nullptr, const Pass* pass = nullptr) {
     const rt_tile_request* rq = &rqs[0];
     rtk::KParams p;
     std::memset(&p, 0, sizeof p);
     p.W = rq->width;
     p.H = rq->height;
     p.Hs = rq->height / rq->divisions;
-    p.spp = rq->spp;
+    // Everything the launch's work is sized by — slots, magic divisors, queue parts, scratch, primary rays — follows the units per
+    // pixel OF THIS LAUNCH; only the stream stride (spp_all) and the mean's divisor (s_end) see the job's whole sample count.
+    const uint32_t s_begin = pass ? pass->begin : 0u, s_end = pass ? pass->end : rq->spp;
+    p.upp = s_end - s_begin;
+    p.spp_all = rq->spp;
+    p.s_begin = s_begin;
+    p.gap = rq->spp - p.upp;
+    p.acc_out = pass ? 1u : 0u;
     p.depth = rq->max_bounces + 1;
     p.n_sph = sc->n_sph;
     p.n_sph_pad = sc->n_sph_pad;
@@ -454,8 +469,8 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
     fill_camera(rq, p);
     p.t_min = rq->t_min;
     p.t_max = rq->t_max;
-    p.spp_f = (float)rq->spp;
-    p.spp_rcp = (rq->spp & (rq->spp - 1u)) == 0u ? 1.0f / (float)rq->spp : 0.0f;   // a power of two up to 2^31: exact in f32
+    p.spp_f = (float)s_end;
+    p.spp_rcp = (s_end & (s_end - 1u)) == 0u ? 1.0f / (float)s_end : 0.0f;         // a power of two up to 2^31: exact in f32
     p.geom_pk = sc->d_geom_pk;
     p.geom_px = sc->d_geom_px;
     p.geom = sc->d_geom;
@@ -488,10 +503,10 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
     // HBM write traffic (profiles/r01_*).
     p.tiles_x = (p.W + 63u) / 64u;
     p.tiles_per_strip = p.tiles_x * p.Hs;
-    // Sample units (rt_kernel.hip.h): pixel slots per wave, the commit threshold, the division by spp
+    // Sample units (rt_kernel.hip.h): pixel slots per wave, the commit threshold, the division by the units per pixel
     {
-        p.grp = p.spp >= 8u ? 1u : (8u + p.spp - 1u) / p.spp;            // a slot is at least 8 units
-        const uint64_t slot_units = (uint64_t)p.grp * p.spp;
+        p.grp = p.upp >= 8u ? 1u : (8u + p.upp - 1u) / p.upp;            // a slot is at least 8 units
+        const uint64_t slot_units = (uint64_t)p.grp * p.upp;
         p.grp_magic = p.grp > 1u ? (uint32_t)((1ull << 32) / p.grp) + 1u : 0u;
         p.slot_stride = 1u + (uint32_t)slot_units;
         // enough slots for the pixels in flight (64 lanes' units, each pixel open as long as its longest path) plus the complete
@@ -509,8 +524,8 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
                                : (uint32_t)std::min<uint64_t>(rtk::SLOTS_MAX, std::max<uint64_t>(fewest, 384u / slot_units));
         const uint32_t cs = dbg(DBG_COMMIT_SLOTS) > 0 ? (uint32_t)dbg(DBG_COMMIT_SLOTS) : std::max<uint32_t>(1u, p.n_slots / 4u);     // (c3: 4 ... 20 of 32 within 1 %)
         p.commit_slots = std::min<uint32_t>(cs, p.n_slots);
-        // q / d == mulhi(q, floor(2^32 / d) + 1) whenever q * d < 2^32: q < 65 * spp with spp <= RT_MAX_SPP (4096)
-        p.spp_magic = p.spp > 1u ? (uint32_t)((1ull << 32) / p.spp) + 1u : 0u;
+        // q / d == mulhi(q, floor(2^32 / d) + 1) whenever q * d < 2^32: q < 65 * upp with upp <= RT_MAX_SPP (4096)
+        p.spp_magic = p.upp > 1u ? (uint32_t)((1ull << 32) / p.upp) + 1u : 0u;
         p.slotu_magic = (uint32_t)((1ull << 32) / slot_units) + 1u;
     }
     const uint64_t n_tiles = (uint64_t)p.tiles_per_strip * n;
@@ -522,6 +537,7 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
         p.strips[i].seed = rqs[i].seed;
         p.strips[i].rgb = (uint8_t*)d_rgb[i];
         p.strips[i].f32 = d_f32 ? (float*)d_f32[i] : nullptr;
+        p.strips[i].acc = pass ? (float*)pass->d_acc[i] : nullptr;
         p.strips[i].y0 = p.Hs * rqs[i].division_no;
     }
     const uint32_t slot = (uint32_t)sc->pending.size();
@@ -561,9 +577,9 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
     {
         const int forced = dbg(DBG_TAIL_TILES);
         const uint64_t waves = (uint64_t)blocks * waves_per_wg;
-        const bool all_parts = p.tiles_total < 16ull * waves || p.spp > 16u;
+        const bool all_parts = p.tiles_total < 16ull * waves || p.upp > 16u;
         uint64_t conv = std::min<uint64_t>(p.tiles_total, forced >= 0 ? (uint64_t)forced : all_parts ? (uint64_t)p.tiles_total : 2ull * waves);
-        p.sub_shift = p.spp > 32u ? 4u : 2u;
+        p.sub_shift = p.upp > 32u ? 4u : 2u;
         if ((((uint64_t)p.tiles_total - conv) + (conv << p.sub_shift)) > 0x7fffffffull) p.sub_shift = 2u;       // (entry numbers are 31 bits)
         p.tiles_big = p.tiles_total - (uint32_t)conv;
         p.n_tiles = p.tiles_big + ((uint32_t)conv << p.sub_shift);
@@ -588,6 +604,9 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
     rt_scene::Ring* rg = nullptr;
     {
         const size_t ring_bytes = (size_t)blocks * waves_per_wg * p.n_slots * p.slot_stride * 12u;
+        if (dbg(DBG_VERBOSE))
+            fprintf(stderr, "[rt] sample-unit ring %zu B: %u units per pixel, %u slots of %u records per wave\n", ring_bytes, p.upp, p.n_slots,
+                    p.slot_stride);
         for (auto& r : sc->rings)
             if (r.d && r.last == stream) { rg = &r; break; }
         if (!rg)
@@ -632,7 +651,7 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
     HIPCHK(hipEventRecord(rg->done, stream));
     if (p.stack_ovf) HIPCHK(hipEventRecord(sc->ovf_done, stream));
     sc->pending.push_back({ev.a, ev.b});
-    sc->primary_rays += (uint64_t)p.Hs * p.W * p.spp * n;
+    sc->primary_rays += (uint64_t)p.Hs * p.W * p.upp * n;
     return RT_OK;
 }
 
@@ -1280,6 +1299,7 @@ static int rt_scene_destroy_impl(rt_scene* sc) {
     (void)hipFree(sc->d_counters);
     (void)hipFree(sc->d_out);
     (void)hipFree(sc->d_outf);
+    (void)hipFree(sc->d_acc);
     (void)hipFree(sc->d_cost);
     delete sc;
     g_live_scenes.fetch_sub(1);
@@ -1297,9 +1317,20 @@ static int check_batch(const rt_tile_request* rqs, uint32_t n) {
     return RT_OK;
 }
 
+// a progressive pass's own arguments (after check_batch): 0 <= begin < end <= spp, a running sum per strip
+static int check_pass(const rt_tile_request* rqs, uint32_t n, uint32_t begin, uint32_t end, const void* const* acc) {
+    if (begin >= end) return fail(RT_ERR_BAD_ARG, "sample_begin >= sample_end");
+    if (end > rqs[0].spp) return fail(RT_ERR_BAD_ARG, "sample_end > spp");
+    if (!acc) return fail(RT_ERR_BAD_ARG, "accum is NULL");
+    for (uint32_t i = 0; i < n; i++)
+        if (!acc[i]) return fail(RT_ERR_BAD_ARG, "accum[i] is NULL");
+    return RT_OK;
+}
+
+// pass: nullptr, or a progressive pass whose d_acc holds one device sum per request (checked here)
 static int rt_scene_render_tiles_device_impl(rt_scene* sc, const rt_tile_request* rqs, uint32_t n,
                                         void* const* d_out_rgb, size_t out_len_each, void* const* d_out_f32,
-                                        void* hip_stream) {
+                                        void* hip_stream, const Pass* pass = nullptr) {
     if (!sc) return fail(RT_ERR_BAD_ARG, "scene is NULL");
     int rc = check_batch(rqs, n);
     if (rc) return rc;
@@ -1307,12 +1338,15 @@ static int rt_scene_render_tiles_device_impl(rt_scene* sc, const rt_tile_request
     for (uint32_t i = 0; i < n; i++)
         if (!d_out_rgb[i]) return fail(RT_ERR_BAD_ARG, "d_out_rgb[i] is NULL");
     if (out_len_each < rt_tile_bytes(&rqs[0])) return fail(RT_ERR_BUFFER_TOO_SMALL, "out_len < (H/div)*W*3");
+    if (pass && (rc = check_pass(rqs, n, pass->begin, pass->end, pass->d_acc))) return rc;
     std::lock_guard<std::mutex> lk(sc->mu);
     HIPCHK(hipSetDevice(sc->ctx->dev));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream;
     for (uint32_t i0 = 0; i0 < n; i0 += rtk::MAX_BATCH) {
         uint32_t m = std::min<uint32_t>(rtk::MAX_BATCH, n - i0);
-        rc = launch_batch(sc, rqs + i0, m, d_out_rgb + i0, d_out_f32 ? d_out_f32 + i0 : nullptr, st);
+        Pass part = {};
+        if (pass) part = {pass->begin, pass->end, pass->d_acc + i0};
+        rc = launch_batch(sc, rqs + i0, m, d_out_rgb + i0, d_out_f32 ? d_out_f32 + i0 : nullptr, st, nullptr, pass ? &part : nullptr);
         if (rc) return rc;
     }
     return RT_OK;
@@ -1333,9 +1367,11 @@ static int rt_scene_collect_impl(rt_scene* sc, rt_tile_stats* st) {
 }
 
 // strip_cost_out: optional host array of n counters: the ray segments of every strip (frame context)
+// pass: nullptr, or a progressive pass whose d_acc holds one HOST sum (float*) per request: uploaded before the launch when the pass
+// continues one (begin > 0), downloaded with the strips
 static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint8_t* const* out_rgb,
                                  size_t out_len_each, float* const* out_f32, rt_tile_stats* stats,
-                                 unsigned long long* strip_cost_out = nullptr) {
+                                 unsigned long long* strip_cost_out = nullptr, const Pass* pass = nullptr) {
     if (!sc) return fail(RT_ERR_BAD_ARG, "scene is NULL");
     int rc = check_batch(rqs, n);
     if (rc) return rc;
@@ -1344,6 +1380,7 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
         if (!out_rgb[i]) return fail(RT_ERR_BAD_ARG, "out_rgb[i] is NULL");
     const size_t need = rt_tile_bytes(&rqs[0]);
     if (out_len_each < need) return fail(RT_ERR_BUFFER_TOO_SMALL, "out_len < (H/div)*W*3");
+    if (pass && (rc = check_pass(rqs, n, pass->begin, pass->end, pass->d_acc))) return rc;
     bool want_f32 = false;
     if (out_f32)
         for (uint32_t i = 0; i < n; i++) want_f32 |= out_f32[i] != nullptr;
@@ -1367,6 +1404,14 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
         if (e != hipSuccess) return fail(RT_ERR_OOM, "hipMalloc(strips f32) failed");
         sc->d_outf_cap = need * n * sizeof(float);
     }
+    if (pass && sc->d_acc_cap < need * n * sizeof(float)) {
+        (void)hipFree(sc->d_acc);
+        sc->d_acc = nullptr;
+        sc->d_acc_cap = 0;
+        hipError_t e = hipMalloc(&sc->d_acc, need * n * sizeof(float));
+        if (e != hipSuccess) return fail(RT_ERR_OOM, "hipMalloc(running sums) failed");
+        sc->d_acc_cap = need * n * sizeof(float);
+    }
     // per-strip costs: one block of COST_COPIES x MAX_BATCH counters per launch group of the call
     constexpr size_t COST_BLOCK = (size_t)rtk::COST_COPIES * rtk::MAX_BATCH;
     const size_t cost_blocks = strip_cost_out ? (n + rtk::MAX_BATCH - 1) / rtk::MAX_BATCH + 1 : 0;
@@ -1385,10 +1430,11 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
     rc = collect_locked(sc, &prev);
     if (rc) return rc;
     sc->h2d_ms = prev.h2d_ms;
-    std::vector<void*> drgb(n), df32(n);
+    std::vector<void*> drgb(n), df32(n), dacc(pass ? n : 0);
     for (uint32_t i = 0; i < n; i++) {
         drgb[i] = sc->d_out + need * i;
         df32[i] = (want_f32 && out_f32[i]) ? (void*)(sc->d_outf + need * i) : nullptr;
+        if (pass) dacc[i] = sc->d_acc + need * i;
     }
     // Launch groups: the last quarter of the strips goes out as its own launch, so that the D2H copies of the strips
     // before it (copy stream) run under it and only the last group's copies are exposed (d2h_ms = that exposed part).
@@ -1427,10 +1473,15 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
         if (rc) return rc;
         gev.push_back(e);
     }
+    if (pass && pass->begin > 0)            // (a pass from sample 0 reads no sum: the caller's buffer may be uninitialised)
+        for (uint32_t i = 0; i < n; i++)
+            HIPCHK(hipMemcpyAsync(dacc[i], pass->d_acc[i], need * sizeof(float), hipMemcpyHostToDevice, st));
     for (size_t g = 0; g < groups.size(); g++) {
         const uint32_t i0 = groups[g].first, m = groups[g].second;
+        Pass part = {};
+        if (pass) part = {pass->begin, pass->end, dacc.data() + i0};
         rc = launch_batch(sc, rqs + i0, m, drgb.data() + i0, want_f32 ? df32.data() + i0 : nullptr, st,
-                          strip_cost_out ? sc->d_cost + g * COST_BLOCK : nullptr);
+                          strip_cost_out ? sc->d_cost + g * COST_BLOCK : nullptr, pass ? &part : nullptr);
         if (rc) return rc;
         HIPCHK(hipEventRecord(gev[g].a, st));
     }
@@ -1439,6 +1490,7 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
         for (uint32_t i = groups[g].first; i < groups[g].first + groups[g].second; i++) {
             HIPCHK(hipMemcpyAsync(out_rgb[i], drgb[i], need, hipMemcpyDeviceToHost, cs));
             if (df32[i]) HIPCHK(hipMemcpyAsync(out_f32[i], df32[i], need * sizeof(float), hipMemcpyDeviceToHost, cs));
+            if (pass) HIPCHK(hipMemcpyAsync(pass->d_acc[i], dacc[i], need * sizeof(float), hipMemcpyDeviceToHost, cs));
         }
     }
     std::vector<unsigned long long> cost_raw;
@@ -1471,6 +1523,22 @@ static int rt_scene_render_tile_impl(rt_scene* sc, const rt_tile_request* rq, ui
     uint8_t* rgb[1] = {out_rgb};
     float* f32[1] = {out_f32};
     return rt_scene_render_tiles_impl(sc, rq, 1, rgb, out_len, out_f32 ? f32 : nullptr, stats);
+}
+
+static int rt_scene_render_tile_pass_impl(rt_scene* sc, const rt_tile_request* rq, uint32_t begin, uint32_t end, float* accum,
+                                          uint8_t* out_rgb, size_t out_len, float* out_f32, rt_tile_stats* stats) {
+    uint8_t* rgb[1] = {out_rgb};
+    float* f32[1] = {out_f32};
+    void* acc[1] = {accum};
+    const Pass pass = {begin, end, acc};
+    return rt_scene_render_tiles_impl(sc, rq, 1, rgb, out_len, out_f32 ? f32 : nullptr, stats, nullptr, &pass);
+}
+
+static int rt_scene_render_tiles_pass_device_impl(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint32_t begin, uint32_t end,
+                                                  void* const* d_accum, void* const* d_out_rgb, size_t out_len_each,
+                                                  void* const* d_out_f32, void* hip_stream) {
+    const Pass pass = {begin, end, d_accum};
+    return rt_scene_render_tiles_device_impl(sc, rqs, n, d_out_rgb, out_len_each, d_out_f32, hip_stream, &pass);
 }
 
 // ---- Test / tool hooks.  NOT part of rt_tile.h and NOT in the product library: compiled only with -DRT_DEBUG_HOOKS, which
@@ -2039,6 +2107,18 @@ RT_API int rt_scene_collect(rt_scene* sc, rt_tile_stats* st) { return guarded([&
 RT_API int rt_scene_render_tiles(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint8_t* const* out_rgb,
                                  size_t out_len_each, float* const* out_f32, rt_tile_stats* stats) {
     return guarded([&] { return rt_scene_render_tiles_impl(sc, rqs, n, out_rgb, out_len_each, out_f32, stats); });
+}
+RT_API int rt_scene_render_tile_pass(rt_scene* sc, const rt_tile_request* rq, uint32_t sample_begin, uint32_t sample_end, float* accum,
+                                     uint8_t* out_rgb, size_t out_len, float* out_f32, rt_tile_stats* stats) {
+    return guarded([&] { return rt_scene_render_tile_pass_impl(sc, rq, sample_begin, sample_end, accum, out_rgb, out_len, out_f32, stats); });
+}
+RT_API int rt_scene_render_tiles_pass_device(rt_scene* sc, const rt_tile_request* reqs, uint32_t n, uint32_t sample_begin,
+                                             uint32_t sample_end, void* const* d_accum, void* const* d_out_rgb, size_t out_len_each,
+                                             void* const* d_out_f32, void* hip_stream) {
+    return guarded([&] {
+        return rt_scene_render_tiles_pass_device_impl(sc, reqs, n, sample_begin, sample_end, d_accum, d_out_rgb, out_len_each,
+                                                      d_out_f32, hip_stream);
+    });
 }
 RT_API int rt_scene_render_tile(rt_scene* sc, const rt_tile_request* rq, uint8_t* out_rgb, size_t out_len, float* out_f32,
                                 rt_tile_stats* stats) {

@@ -144,13 +144,18 @@ struct StripDesc {
     uint64_t seed;
     uint8_t* rgb;                // [Hs*W*3]
     float* f32;                  // optional [Hs*W*3]
+    float* acc;                  // progressive pass only: [Hs*W*3] raw colour sums, in (KParams::s_begin > 0) and out; else nullptr
     uint32_t y0;                 // first global row of the strip = Hs * division_no
     uint32_t pad;
 };
 
 struct KParams {
     uint32_t W, H, Hs;           // image size, rows per strip
-    uint32_t spp, depth;         // samples per pixel; ray_color entry depth = max_bounces+1
+    uint32_t upp, depth;         // sample units per pixel of this launch (= spp of a one-pass launch); ray_color entry depth = max_bounces+1
+    // Progressive passes (rt_scene_render_tile_pass): the launch renders samples [s_begin, s_begin + upp) of an spp_all-sample image.
+    // Sample s of pixel p draws from stream p * spp_all + s whatever the pass; gap = spp_all - upp.  One-pass launch: s_begin 0, gap 0.
+    uint32_t spp_all, s_begin, gap;
+    uint32_t acc_out;            // 1: store every committed pixel's raw sum to its strip's acc (a progressive pass)
     uint32_t n_sph, n_sph_pad;   // spheres, padded to UNROLL with never-hit dummies
     uint32_t n_tri;
     uint32_t chunk;              // spheres per LDS chunk actually used (multiple of UNROLL)
@@ -172,19 +177,19 @@ struct KParams {
                                  //   of one of the remaining tiles: the launch ends on small pieces (its tail is one piece long)
     uint32_t n_tiles;            // queue entries: tiles_big + ((tiles_total - tiles_big) << sub_shift)
     uint32_t n_slots;            // sample units: pixel slots per wave (<= SLOTS_MAX)
-    uint32_t grp;                //   pixels per slot (1 from 8 spp up; 8 / spp below, so that a slot is at least 8 units)
+    uint32_t grp;                //   pixels per slot (1 from 8 units per pixel up; 8 / upp below, so that a slot is at least 8 units)
     uint32_t grp_magic;          //   floor(2^32 / grp) + 1 (grp > 1)
-    uint32_t slot_stride;        //   12-byte records per slot in the scratch: header + grp x spp
+    uint32_t slot_stride;        //   12-byte records per slot in the scratch: header + grp x upp
     uint32_t commit_slots;       //   a commit is worth its instructions once this many slots are complete
-    uint32_t spp_magic;          //   floor(2^32 / spp) + 1: q / spp == mulhi(q, magic) for q < 65 * spp (spp <= RT_MAX_SPP = 4096); 0 for spp 1
-    uint32_t slotu_magic;        //   floor(2^32 / U) + 1, U = grp * spp the units of a full slot: q / U == mulhi(q, magic) for q < 65 * U
+    uint32_t spp_magic;          //   floor(2^32 / upp) + 1: q / upp == mulhi(q, magic) for q < 65 * upp (upp <= RT_MAX_SPP = 4096); 0 for upp 1
+    uint32_t slotu_magic;        //   floor(2^32 / U) + 1, U = grp * upp the units of a full slot: q / U == mulhi(q, magic) for q < 65 * U
     float* ring;                 //   [waves of the grid][n_slots][slot_stride][3]: slot header (x, row, meta), then (r, g, b) per unit
     float org[3], llc[3], hor[3], ver[3];   // Camera::new (camera.rs:19-47), host-computed
     float lens_radius, focus_distance;
     float u_den, v_den;          // aspect*H_f - 1, H_f - 1 (camera.rs:115-117)
     float t_min, t_max;
-    float spp_f;
-    float spp_rcp;               // 1 / spp when spp is a power of two (then x / spp == x * spp_rcp bit for bit), else 0
+    float spp_f;                 // the mean's divisor: samples summed into a pixel at the end of this launch (s_begin + upp)
+    float spp_rcp;               // 1 / spp_f when that is a power of two (then x / spp_f == x * spp_rcp bit for bit), else 0
     const float4* geom_pk;       // [n_sph_pad/2][2]: (c0x,c1x,c0y,c1y) (c0z,c1z,rr0,rr1)
     const float4* geom_px;       // expanded form: (c0x,c1x,c0y,c1y) (c0z,c1z,w0,w1),
                                  //   w = |c|^2 - rr - 2^-16 (|c|^2 + rr)
@@ -786,7 +791,7 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
     uint32_t freem = all_free;                // the free pixel slots.  The LOWEST free slot is taken first: the slots in use — and with them the
                                               // part of the scratch that L2 has to hold — are the low ones unless a burst of long paths needs more
     uint32_t cur_slot = 0;                    // the open slot: the one the tile's next unit belongs to (unless that unit starts a slot)
-    uint32_t tile_u = 0, tile_units = 0;      // issue tile: its next unit, its units (npix * spp); pixel-major: unit = pixel-in-tile * spp + sample
+    uint32_t tile_u = 0, tile_units = 0;      // issue tile: its next unit, its units (npix * upp); pixel-major: unit = pixel-in-tile * upp + sample - s_begin
     uint32_t tile_x0 = 0, tile_row = 0, tile_yg = 0;   // ... decoded once: first column, row within the strip, GLOBAL row (main.rs:66-68)
     uint32_t tile_meta = STAGE_TILES << 16;   // ... strip in the batch | stage slot << 16 (STAGE_TILES: its pixels are stored directly)
     uint64_t tile_seed = 0;                   // ... SplitMix64 state of its first unit's stream
@@ -865,7 +870,7 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
         row = rem / p.tiles_x;
         x0 = (rem - row * p.tiles_x) << 6;
     };
-    // q / spp for q < 65 * spp (a unit's place in its tile -> its pixel): a multiply-high (spp 1: the unit itself)
+    // q / upp for q < 65 * upp (a unit's place in its tile -> its pixel): a multiply-high (upp 1: the unit itself)
     auto div_spp = [&](uint32_t q) -> uint32_t { return p.spp_magic ? __umulhi(q, p.spp_magic) : q; };
 
     TDECL;
@@ -906,9 +911,17 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                         const uint32_t hx = ring_load(reinterpret_cast<const uint32_t*>(sb) + 0);
                         const uint32_t hrow = ring_load(reinterpret_cast<const uint32_t*>(sb) + 1);
                         const uint32_t hmeta = ring_load(reinterpret_cast<const uint32_t*>(sb) + 2);
-                        const float* r = sb + 3u + g * p.spp * 3u;
+                        const float* r = sb + 3u + g * p.upp * 3u;
                         float sum_r = 0.f, sum_g = 0.f, sum_b = 0.f;
                         cstrip = hmeta & 0xffu;
+                        if (p.s_begin != 0u && g < ((hmeta >> 8) & 0xffu)) {
+                            // a progressive pass continues the pixel's running sum over samples 0 .. s_begin - 1 (rt_tile.h
+                            // rt_scene_render_tile_pass): the same sequential f32 sum as one pass, resumed where the last pass stopped
+                            const float* a = p.strips[cstrip].acc + ((size_t)hrow * p.W + hx + g) * 3;
+                            sum_r = a[0];
+                            sum_g = a[1];
+                            sum_b = a[2];
+                        }
                         {
                             // pix_color += (main.rs:75), s = 0 .. spp - 1; the loads of four samples in flight together
                             uint32_t i = 0;
@@ -917,7 +930,7 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                             auto batch = [&](auto cb_tag) {
                                 constexpr int CB = decltype(cb_tag)::value;
 #pragma clang loop unroll(disable)
-                                for (; i + (uint32_t)CB <= p.spp; i += (uint32_t)CB) {
+                                for (; i + (uint32_t)CB <= p.upp; i += (uint32_t)CB) {
                                     LCOUNT(12);
                                     float c[3 * CB];
 #pragma unroll
@@ -934,7 +947,7 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                             if (RT_COMMIT_BATCH > 4 && !QNODES) batch(std::integral_constant<int, RT_COMMIT_BATCH>{});      // (the 96-register quantised kernels would spill)
                             batch(std::integral_constant<int, 4>{});
 #pragma clang loop unroll(disable)
-                            for (; i < p.spp; i++) {
+                            for (; i < p.upp; i++) {
                                 LCOUNT(12);
                                 const float cr = ring_load(r + 0);
                                 const float cg = ring_load(r + 1);
@@ -963,6 +976,12 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                             const uint32_t sidx = hmeta & 0xffu;
                             stg = (hmeta >> 16) & 0xffu;
                             const size_t oidx = ((size_t)hrow * p.W + hx + g) * 3;          // row within the strip
+                            if (p.acc_out) {                                                    // (progressive pass: the sum over 0 .. s_begin + upp - 1)
+                                float* a = p.strips[sidx].acc;
+                                a[oidx + 0] = sum_r;
+                                a[oidx + 1] = sum_g;
+                                a[oidx + 2] = sum_b;
+                            }
                             if (!CAN_STAGE || stg == STAGE_TILES) {
                                 uint8_t* orgb = p.strips[sidx].rgb;
                                 orgb[oidx + 0] = f32_as_u8(cr_ * 255.999f);
@@ -1100,11 +1119,11 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                     tile_row = uni(tile_row);
                     if (tile_x0 >= p.W) continue;                 // (a quarter beyond the right edge of a ragged tile: nothing in it)
                     tile_yg = uni(p.strips[tstrip].y0 + tile_row);                // main.rs:66-68
-                    // SplitMix64 state of the tile's first stream: seed + 4 PHI * (p * S), p = row * W + x0 the tile's first pixel
-                    tile_seed = p.strips[tstrip].seed + (((uint64_t)tile_yg * p.W + tile_x0) * p.spp) * (4ull * PHI);
+                    // SplitMix64 state of the tile's first stream: seed + 4 PHI * (p * S + s_begin), p = row * W + x0 the tile's first pixel
+                    tile_seed = p.strips[tstrip].seed + (((uint64_t)tile_yg * p.W + tile_x0) * p.spp_all + p.s_begin) * (4ull * PHI);
                     tile_seed = (uint64_t)uni((uint32_t)tile_seed) | ((uint64_t)uni((uint32_t)(tile_seed >> 32)) << 32);
                     const uint32_t npix = min(tw, p.W - tile_x0);
-                    tile_units = uni(npix * p.spp);
+                    tile_units = uni(npix * p.upp);
                     tile_u = 0u;
                     uint32_t tstage = STAGE_TILES;
                     if (staging && npix == 64u) {
@@ -1128,7 +1147,7 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                     tile_meta = uni(tstrip | (tstage << 16));
                 }
                 // ---- The tile's next units, all needy lanes at once: the lane of rank r takes unit tv = tile_u + r.  The tile's units
-                // are cut into slots of U = grp * spp (the last one may be short): unit tv belongs to the tile's slot number tv / U.
+                // are cut into slots of U = grp * upp (the last one may be short): unit tv belongs to the tile's slot number tv / U.
                 // Slots up to the one tile_u - 1 lies in are open already (that one is cur_slot); the others are the lowest free slots in turn,
                 // and the lane that takes a slot's first unit sets the slot up (counter, header).
                 bool got = false;
@@ -1155,7 +1174,7 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                     if (got) {
                         useq = (slot << 24) | unit;
                         if (unit == 0u) {
-                            const uint32_t un = min(U, tile_units - tv);                  // its units; its pixels: un / spp
+                            const uint32_t un = min(U, tile_units - tv);                  // its units; its pixels: un / upp
                             wq.cnt[slot] = un;
                             uint32_t* hdr = reinterpret_cast<uint32_t*>(ring + __umul24(slot, p.slot_stride) * 3u);
                             hdr[0] = tile_x0 + __umul24(k, p.grp);
@@ -1176,10 +1195,12 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                 if (got) {
                     WCOUNT(1);
                     LCOUNT(0);
-                    px = tile_x0 + div_spp(tv);                                   // pixel-major: pixel tv / spp, sample tv % spp
+                    const uint32_t j = div_spp(tv);                               // pixel-major: pixel j = tv / upp, sample s_begin + tv % upp
+                    px = tile_x0 + j;
                     pyg = tile_yg;
-                    // stream p * S + s: the tile's first stream + tv (tile_seed holds that one's SplitMix64 state)
-                    rng = seed_state(tile_seed + (uint64_t)tv * (4ull * PHI));
+                    // stream p * S + s: the tile's first stream + tv + j * (S - upp) (tile_seed holds that one's SplitMix64 state;
+                    // tv + j * gap < 64 S <= 2^18)
+                    rng = seed_state(tile_seed + (uint64_t)(tv + __umul24(j, p.gap)) * (4ull * PHI));
                     have_unit = true;
                     need_ray = true;
                     bounce = false;

@@ -150,6 +150,43 @@ class Scene:
                                                   C.byref(st)), "rt_scene_render_tile")
         return out, outf, st
 
+    def render_tile_pass(self, req: TileRequest, begin: int, end: int, accum: Optional[np.ndarray] = None,
+                         want_f32: bool = False):
+        """One progressive pass: samples [begin, end) of the req.spp-sample strip (rt_scene_render_tile_pass).  `accum` is the
+        strip's running colour sum, a contiguous float32 (Hs, W, 3) array, updated in place; None is allowed for begin == 0 and
+        allocates it.  Returns (rgb, f32 | None, accum, stats): the preview sqrt(sum / end), which at end == req.spp is
+        bit-identical to render_tile(req) however the samples were split into passes."""
+        n = self._lib.rt_tile_bytes(C.byref(req))
+        shape = (req.height // max(req.divisions, 1), req.width, 3)      # (a bad request is refused by the library)
+        if accum is None:
+            if begin != 0:
+                raise ValueError("accum: a pass that starts after sample 0 continues a running sum: pass the one of the last pass")
+            accum = np.empty(shape, np.float32)
+        if accum.dtype != np.float32 or accum.shape != shape or not accum.flags.c_contiguous or not accum.flags.writeable:
+            raise ValueError(f"accum: need a writeable contiguous float32 array of shape {shape}")
+        out = np.empty(n, np.uint8)
+        outf = np.empty(n, np.float32) if want_f32 else None
+        fp = C.POINTER(C.c_float)
+        st = TileStats()
+        _abi.check(self._lib.rt_scene_render_tile_pass(self._h, C.byref(req), begin, end, accum.ctypes.data_as(fp),
+                                                       out.ctypes.data_as(C.POINTER(C.c_uint8)), n,
+                                                       outf.ctypes.data_as(fp) if want_f32 else None, C.byref(st)),
+                   "rt_scene_render_tile_pass")
+        return out, outf, accum, st
+
+    def render_progressive(self, req: TileRequest, pass_spp: int):
+        """Generator: the strip in passes of `pass_spp` samples (the last one may be shorter), yielding (end, rgb, stats) after
+        each until end == req.spp; the last rgb equals render_tile(req).  Stop iterating to stop the job."""
+        if pass_spp < 1:
+            raise ValueError("pass_spp must be at least 1")
+        accum = None
+        begin = 0
+        while begin < req.spp:
+            end = min(begin + pass_spp, req.spp)
+            rgb, _, accum, st = self.render_tile_pass(req, begin, end, accum)
+            yield end, rgb, st
+            begin = end
+
     def render_tile_device(self, req: TileRequest, d_out_ptr: int, out_len: int, d_f32_ptr: int = 0, stream: int = 0):
         _abi.check(self._lib.rt_scene_render_tile_device(self._h, C.byref(req), C.c_void_p(d_out_ptr), out_len,
                                                          C.c_void_p(d_f32_ptr) if d_f32_ptr else None,
@@ -184,6 +221,20 @@ class Scene:
         _abi.check(self._lib.rt_scene_render_tiles_device(self._h, arr, n, po, out_len_each, None,
                                                           C.c_void_p(stream) if stream else None),
                    "rt_scene_render_tiles_device")
+
+    def render_tiles_pass_device(self, reqs: Sequence[TileRequest], begin: int, end: int, d_accum_ptrs: Sequence[int],
+                                 d_out_ptrs: Sequence[int], out_len_each: int, d_f32_ptrs: Optional[Sequence[int]] = None,
+                                 stream: int = 0):
+        """Batched progressive pass, asynchronous, device buffers (rt_scene_render_tiles_pass_device): samples [begin, end) of
+        every strip, d_accum_ptrs[i] the running sum of strip i (Hs*W*3 floats on the device)."""
+        n = len(reqs)
+        arr = (TileRequest * n)(*reqs)
+        pa = (C.c_void_p * n)(*d_accum_ptrs)
+        po = (C.c_void_p * n)(*d_out_ptrs)
+        pf = (C.c_void_p * n)(*d_f32_ptrs) if d_f32_ptrs is not None else None
+        _abi.check(self._lib.rt_scene_render_tiles_pass_device(self._h, arr, n, begin, end, pa, po, out_len_each, pf,
+                                                               C.c_void_p(stream) if stream else None),
+                   "rt_scene_render_tiles_pass_device")
 
     def collect(self) -> TileStats:
         st = TileStats()
