@@ -46,7 +46,8 @@ UNITS = [
 
 
 def _deps() -> list[Path]:
-    return [CSRC / u for u, _ in UNITS] + [CSRC / "rt_kernel.hip.h", CSRC / "rt_cull.h", CSRC / "rt_bvh.h", CSRC / "rt_assign.h", ROOT / "include" / "rt_tile.h",
+    return [CSRC / u for u, _ in UNITS] + [CSRC / "rt_kernel.hip.h", CSRC / "rt_consts.h", CSRC / "rt_plan.h", CSRC / "rt_cull.h", CSRC / "rt_bvh.h",
+                                            CSRC / "rt_assign.h", ROOT / "include" / "rt_tile.h",
                                             Path(__file__)]
 
 

@@ -26,6 +26,7 @@
 #include "rt_assign.h"
 #include "rt_bvh.h"
 #include "rt_kernel.hip.h"
+#include "rt_plan.h"
 #include "rt_tile.h"
 
 namespace {
@@ -122,32 +123,32 @@ bool g_init = false;
 std::vector<DeviceCtx*> g_ctx;
 std::atomic<int> g_live_scenes{0};   // rt_shutdown is refused while any scene is alive (scenes point at their DeviceCtx)
 
-constexpr size_t LDS_LIMIT = 160 * 1024 - 3072;   // dynamic LDS budget; 3 KiB left for the kernels' static LDS (the queue words and
-                                                  // one rtk::WaveQ per wave: 16 + 16 x 160 bytes in the 1024-thread kernel)
-constexpr uint32_t RESIDENT_MAX = rtk::CHUNK;   // spheres kept wholly in LDS
-constexpr uint32_t STREAM_CHUNK = 2048;         // chunk size when streaming through LDS
-constexpr uint32_t STACK_LDS_MAX = 12;          // quantised-node kernel: stack entries per lane in LDS, deeper ones in HBM
-constexpr uint32_t TRAVERSE_MIN_TRIS = 4;       // ... or above this many triangles (tools/crossover_tris.py: the LDS-tree walk wins from 8 triangles up)
-constexpr uint32_t RT_QNODES_MIN_PRIMS = 4096;   // from here up the traversal walks the 32-byte quantised nodes (tools/crossover_q.py)
 constexpr uint32_t REORDER_MIN_PRIMS = 64;      // from here up the primitive records are stored in the tree's depth-first leaf order
-constexpr uint32_t DENSE_SCAN_MAX_PRIMS = 192;       // piles of up to this many spheres at a box density of at least ...
-constexpr float DENSE_SCAN_MIN_DENSITY = 3.0f;       // ... this keep the linear scan (see `traverse`)
-constexpr float LT_CULL_MIN_DENSITY = 2.2f;          // the LDS-resident tree is walked nearer child first, with distance culling, from this box density up
-                                                     // (tests/test_gpu_engine_rules.py: at 1.1 ... 1.8 a helix, a lattice and a colonnade of 700 ... 960
-                                                     // spheres lose 7 ... 17 % to the culled step, piles at 1.8 / 2.7 gain 2 / 38 %)
-constexpr uint32_t TRAVERSE_MIN_PRIMS = 2;      // from this many primitives up the BVH-traversal engine is the default.  (Rounds 1-3: 32, with a density rule below it;
-                                                // with the sample units the LDS-resident tree leads the scan on every scene of tools/small_scene_matrix.py —
-                                                // 2 ... 32 spheres, five families, 1.02 ... 1.36 x — but one pile of 32, and on c2's 16-sphere room by 5 ... 8 %.)
+
+// The launch-path knobs the plan reads, read once per launch
+rtplan::Knobs plan_knobs() {
+    rtplan::Knobs k;
+    k.lds_tree = dbg(DBG_LDS_TREE);
+    k.cull_walk = dbg(DBG_CULL_WALK);
+    k.no_stage = dbg(DBG_NO_STAGE);
+    k.slots = dbg(DBG_SLOTS);
+    k.commit_slots = dbg(DBG_COMMIT_SLOTS);
+    k.force_capped = dbg(DBG_FORCE_CAPPED);
+    k.stack_lds = dbg(DBG_STACK_LDS);
+    k.compact = dbg(DBG_COMPACT);
+    k.refill_eighths = dbg(DBG_REFILL_EIGHTHS);
+    k.tail_tiles = dbg(DBG_TAIL_TILES);
+    return k;
+}
 
 }  // namespace
 
 struct rt_scene {
     DeviceCtx* ctx = nullptr;
-    uint32_t n_sph = 0, n_sph_pad = 0, n_tri = 0;
+    rtplan::SceneShape shape;       // what the engine rules read (rt_plan.h)
     float4* d_geom = nullptr;
     float4* d_geom_pk = nullptr;
     float4* d_geom_px = nullptr;   // expanded-form broad phase records
-    bool expanded = false;         // host heuristic: expanded-form margin small against r^2
     float4* d_mat = nullptr;
     float* d_emis = nullptr;
     float* d_tri = nullptr;
@@ -162,17 +163,8 @@ struct rt_scene {
     float4* d_geom_r = nullptr;    // (cx,cy,cz,radius)
     uint32_t* d_big = nullptr;     // culled walk: spheres root-tested at query start (too large for its slack)
     uint32_t n_big = 0;
-    float r_slack = 0.f;           //   largest radius among the other spheres
-    bool cull_pays = false;        //   host heuristic: the scene is dense enough for the culled walk (build_host_scene)
-    bool inverted_boxes = false;   // a sphere of negative radius: its AABB has lo > hi (sphere.rs:65-72), see launch_batch
     float tri_k = 0.f, tri_diag = 0.f, tri_es = 0.f, tri_e = 0.f;   // culled walk over the exact nodes: maxima over the triangles not in `big`
-    bool xcull_pays = false;       //   host heuristic for scenes with triangles
-    bool tri_ok = false;
-    float cull_density = 0.f;      //   the box density behind it
     rtbvh::QGrid grid;
-    float leaf_density = 0.f;      // sum of primitive box areas / scene box area (node-format heuristic)
-    bool quant_ok = false;         // quantised walk usable and worthwhile (grid step small against the primitives)
-    uint32_t root_ref = 0, bvh_depth = 0, n_internal = 0;
     uint32_t* d_leaf_of = nullptr;
     uint32_t* d_world_rank = nullptr;   // world_index of every primitive when the caller gave one (rt_tile.h "the world's order")
     bool has_order = false;
@@ -222,31 +214,6 @@ int check_request(const rt_tile_request* rq) {
     return RT_OK;
 }
 
-// Camera::new with the slave's arguments (main.rs:42-50 -> camera.rs:19-47)
-void fill_camera(const rt_tile_request* rq, rtk::KParams& p) {
-    const float origin[3] = {0.f, 0.f, 0.f};          // Point3::ZERO
-    const float aspect_ratio = (float)rq->width / (float)rq->height;
-    const float image_height = (float)rq->height;
-    const float vh = 2.0f * std::tan(rq->fov / 2.0f);
-    const float vw = aspect_ratio * vh;
-    const float hor[3] = {vw, 0.f, 0.f}, ver[3] = {0.f, vh, 0.f};
-    const float foc[3] = {0.f, 0.f, rq->focal_length};
-    for (int i = 0; i < 3; i++) {
-        p.org[i] = origin[i];
-        p.hor[i] = hor[i];
-        p.ver[i] = ver[i];
-        // origin - horizontal / 2 - vertical / 2 - (0,0,focal_length)
-        float v = origin[i] - hor[i] / 2.0f;
-        v = v - ver[i] / 2.0f;
-        v = v - foc[i];
-        p.llc[i] = v;
-    }
-    p.lens_radius = rq->aperture / 2.0f;
-    p.focus_distance = rq->focus_distance;
-    p.u_den = aspect_ratio * image_height - 1.0f;      // camera.rs:116
-    p.v_den = image_height - 1.0f;                     // camera.rs:117
-}
-
 struct EvPair {
     hipEvent_t a, b;
 };
@@ -287,190 +254,61 @@ struct Pass {
     uint32_t begin, end;
     void* const* d_acc;
 };
+// The scene's stack-overflow area of the capped-stack kernels, grown to at least `words`.
+int acquire_stack_ovf(rt_scene* sc, size_t words) {
+    if (words > sc->stack_ovf_words) {
+        if (sc->d_stack_ovf) {
+            if (sc->ovf_done) HIPCHK(hipEventSynchronize(sc->ovf_done));   // a launch in flight may still use the old area
+            (void)hipFree(sc->d_stack_ovf);
+            sc->d_stack_ovf = nullptr;
+            sc->stack_ovf_words = 0;
+        }
+        HIPCHK(hipMalloc(&sc->d_stack_ovf, words * sizeof(uint32_t)));
+        sc->stack_ovf_words = words;
+    }
+    return RT_OK;
+}
+
+// The launch's sample-unit ring of at least `bytes`: the one this stream used last, else a free one, else the least recently used
+// (after its last launch).
+int acquire_ring(rt_scene* sc, hipStream_t stream, size_t bytes, rt_scene::Ring*& rg) {
+    rg = nullptr;
+    for (auto& r : sc->rings)
+        if (r.d && r.last == stream) { rg = &r; break; }
+    if (!rg)
+        for (auto& r : sc->rings)
+            if (!r.d) { rg = &r; break; }
+    if (!rg) {
+        rg = &sc->rings[0];
+        for (auto& r : sc->rings)
+            if (r.stamp < rg->stamp) rg = &r;
+    }
+    if (rg->bytes < bytes) {
+        if (rg->d) {
+            if (rg->done) HIPCHK(hipEventSynchronize(rg->done));     // a launch in flight may still use the old area
+            (void)hipFree(rg->d);
+            rg->d = nullptr;
+            rg->bytes = 0;
+        }
+        HIPCHK(hipMalloc(&rg->d, bytes));
+        rg->bytes = bytes;
+    }
+    if (!rg->done) HIPCHK(hipEventCreateWithFlags(&rg->done, hipEventDisableTiming));
+    else if (rg->last != stream) HIPCHK(hipStreamWaitEvent(stream, rg->done, 0));
+    rg->last = stream;
+    rg->stamp = ++sc->ring_clock;
+    return RT_OK;
+}
+
 int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* const* d_rgb, void* const* d_f32,
                  hipStream_t stream, unsigned long long* d_strip_cost = nullptr, const Pass* pass = nullptr) {
-    const rt_tile_request* rq = &rqs[0];
+    const rtplan::Knobs kn = plan_knobs();
+    const rtplan::SceneShape& sh = sc->shape;
     rtk::KParams p;
     std::memset(&p, 0, sizeof p);
-    p.W = rq->width;
-    p.H = rq->height;
-    p.Hs = rq->height / rq->divisions;
-    // Everything the launch's work is sized by — slots, magic divisors, queue parts, scratch, primary rays — follows the units per
-    // pixel OF THIS LAUNCH; only the stream stride (spp_all) and the mean's divisor (s_end) see the job's whole sample count.
-    const uint32_t s_begin = pass ? pass->begin : 0u, s_end = pass ? pass->end : rq->spp;
-    p.upp = s_end - s_begin;
-    p.spp_all = rq->spp;
-    p.s_begin = s_begin;
-    p.gap = rq->spp - p.upp;
-    p.acc_out = pass ? 1u : 0u;
-    p.depth = rq->max_bounces + 1;
-    p.n_sph = sc->n_sph;
-    p.n_sph_pad = sc->n_sph_pad;
-    p.n_tri = sc->n_tri;
-    p.flags = rq->flags;
-    // A sphere of negative radius has an AABB with lo > hi (Sphere::aabb = center -+ radius, sphere.rs:65-72): the reference's
-    // sign-selected slab test rejects such a box for (almost) every ray, while the finite-direction shortcut of the kernels
-    // (min / max of the two plane values, valid for lo <= hi) would enter it.  Such a scene is rendered with the crate's
-    // literal test and the whole box chain throughout (the RT_FLAG_FULL_CHAIN path): slower, and exact.
-    if (sc->inverted_boxes) p.flags |= RT_FLAG_FULL_CHAIN;
-    // Engine choice.  BVH traversal reproduces reference semantics only, needs the tree to fit the traversal
-    // stack, and pays off once the scene is larger than a couple of LDS chunks; RT_FLAG_BVH_TRAVERSE /
-    // RT_FLAG_LINEAR_SCAN force either engine for A/B runs and tests.
-    const uint32_t n_prims = sc->n_sph + sc->n_tri;
-    const bool trav_ok = !(rq->flags & (RT_FLAG_EXACT_SCAN | RT_FLAG_NO_BVH_CULL | RT_FLAG_LINEAR_SCAN)) &&
-                         sc->bvh_depth < (uint32_t)rtk::TRAV_STACK && n_prims > 0;   // LDS stack: (depth + 1) KiB per workgroup
-    // (the linear engines test every triangle's box per segment: meshes switch to the tree much earlier)
-    // (Small PILES of overlapping spheres keep the scan: at a box density of 3 and more a ray meets so many leaf boxes that up
-    // to about 200 spheres the scan's 64 packed instructions per 8 spheres beat any walk — tools/dense_matrix.py, 48 ... 192 spheres at
-    // density 3.3 ... 13: the culled LDS-tree walk of round 4 renders them at 0.67 ... 0.84 of the scan (the plain one: 0.59 ... 0.92), at
-    // 256 it leads by 1.4 ... 1.5 x.  Round 3's two further pile rules — up to 384 spheres at densities 5 ... 12 to the scan, larger or
-    // denser piles to the culled L2 walk although their tree fits LDS — are gone: the culled LDS-tree walk is the best engine in
-    // every cell of tools/dense_mid_matrix.py, by 13 ... 30 %.)
-    const bool dense_pile = sc->n_tri == 0 && n_prims <= DENSE_SCAN_MAX_PRIMS && sc->cull_density >= DENSE_SCAN_MIN_DENSITY;
-    const bool traverse = trav_ok && ((rq->flags & RT_FLAG_BVH_TRAVERSE) || (n_prims >= TRAVERSE_MIN_PRIMS && !dense_pile) ||
-                                      sc->n_tri > TRAVERSE_MIN_TRIS);
-    // node format: from RT_QNODES_MIN_PRIMS primitives up the 32-byte quantised nodes (half the gather footprint, and an
-    // LDS plan that keeps five workgroups per CU whatever the tree's depth): +14 % on sparse fields of every size, +17...29 %
-    // on dense fields of 32 768+ spheres, within 2.5 % either way in between; below it the exact-node kernel's six
-    // waves per SIMD win on the headline scene (c3 +1.5 %).  tools/crossover_q.py, DESIGN.md 4.7
-    // (meshes keep the exact nodes: a quantised walk validates a triangle leaf by walking its box chain — two more gathers
-    // per improving hit — and lost 2...16 % on the generated terrains of 7 200 and 100 352 triangles, tools/heuristics_matrix.py)
-    // LDS-resident tree (engine 4, kernel variant 3): the exact 64-byte nodes of a small scene staged into LDS by one
-    // 1024-thread workgroup per CU, 16-bit references / stack / leaf lists.  RT_FLAG_NO_LDS_TREE forces the
-    // L2-gather kernel (A/B runs, tests).
-    const bool ltree_env = dbg(DBG_LDS_TREE) != 0;
-    bool ltree_fits = false;
-    const size_t lt_lane = ((size_t)rtk::MAXL_LTREE + (size_t)(rq->max_bounces + 1) + (size_t)(sc->bvh_depth + 2)) * sizeof(uint16_t);
-    if (traverse && ltree_env && !(rq->flags & RT_FLAG_NO_LDS_TREE) && sc->n_internal > 0 && n_prims <= 0x7fffu &&
-        ((size_t)sc->n_internal + 2) * rtk::LNODE_DW < 0x8000u) {
-        const size_t fixed = (((size_t)sc->n_internal + 2) * rtk::LNODE_DW + n_prims) * 4 + 16 + lt_lane * rtk::LTREE_BLOCK;   // + node DONE and the NaN field
-        ltree_fits = fixed <= LDS_LIMIT;
-    }
-    // (Below the threshold a DENSE sphere scene whose tree does not fit LDS also takes the quantised nodes, for the culled
-    // walk below: tools/cull_matrix_small.py, 2 000...3 500 overlapping spheres 1.55...1.95 x over the exact-node walk, fields of
-    // box density 1...2 0.87...0.98 — hence the higher bar of 2.5 here.)
-    // (round 4: piles whose tree FITS LDS no longer need a rule — the LDS-resident tree has its own culled walk, below)
-    const bool dense_mid = sc->cull_pays && !(rq->flags & RT_FLAG_NO_CULL_WALK) && !ltree_fits && sc->cull_density >= 2.5f &&
-                           n_prims >= 512;
-    // (... and so does a sphere FIELD between the LDS tree's limit and that threshold: at box densities of 0.15 and more the quantised
-    // walk leads the exact one by 17...24 % there — tools/qnodes_mid_matrix.py, 1200...4000 spheres; flat sheets of small spheres,
-    // 0.03...0.1, are the scenes the exact nodes win by up to 12 %, and clusters fail quant_ok)
-    const bool field_mid = !ltree_fits && sc->n_tri == 0 && n_prims < RT_QNODES_MIN_PRIMS && sc->cull_density >= 0.15f;
-    const bool qnodes = traverse && sc->quant_ok && !(rq->flags & RT_FLAG_EXACT_NODES) &&
-                        ((rq->flags & RT_FLAG_QUANT_NODES) || (n_prims >= RT_QNODES_MIN_PRIMS && sc->n_tri <= sc->n_sph) || dense_mid ||
-                         field_mid);
-    const bool ltree = ltree_fits && !qnodes;
-    // Culled walk (engine 5, kernel variant 5): the quantised walk nearer child first, subtrees beyond the running closest hit
-    // skipped.  Spheres only (the bound is derived from the sphere root test's error terms).
-    // Default where the host heuristic says it pays (cull_pays: DESIGN.md 4.7); RT_FLAG_CULL_WALK / RT_FLAG_NO_CULL_WALK
-    // force it on / off (A/B runs, tests), RT_CULL_WALK=0/1 likewise for a whole process.
-    // (an explicit request flag wins over the process-level knob, the knob over the host rule)
-    const int cull_env = dbg(DBG_CULL_WALK);
-    const bool cull_want = (rq->flags & RT_FLAG_NO_CULL_WALK) ? false : (rq->flags & RT_FLAG_CULL_WALK) ? true
-                           : cull_env >= 0 ? cull_env != 0 : sc->cull_pays;
-    const bool cull = qnodes && cull_want && sc->n_tri == 0 && std::isfinite(sc->r_slack);
-    // ... and over the exact nodes (kernel variant 7): scenes with triangles — the bound of cull_bound_tri — wherever the exact-node
-    // L2 walk is the engine; default where the host heuristic says it pays (xcull_pays), forced by the same flags
-    const bool xcull_want = (rq->flags & RT_FLAG_NO_CULL_WALK) ? false : (rq->flags & RT_FLAG_CULL_WALK) ? true
-                            : cull_env >= 0 ? cull_env != 0 : sc->xcull_pays;
-    const bool xcull = traverse && !qnodes && !ltree && xcull_want && sc->n_tri > 0 && sc->tri_ok && std::isfinite(sc->r_slack) &&
-                       !sc->inverted_boxes;
-    // ... and in the LDS-resident tree (kernel variant 4, engine 7; round 4): the same bound, so the same premises (a finite slack
-    // radius, triangles within the K limit or in the `big` list, no inverted boxes); default from a box density of LT_CULL_MIN_DENSITY
-    // up — below it the rays meet so few leaf boxes that ordering the children costs more than the skipped subtrees save
-    // (tools/dense_matrix.py, tools/dense_mid_matrix.py, tests/test_gpu_engine_rules.py)
-    const bool lt_cull_ok = ltree && !sc->inverted_boxes && std::isfinite(sc->r_slack) && (sc->n_tri == 0 || sc->tri_ok);
-    const bool lt_cull_want = (rq->flags & RT_FLAG_NO_CULL_WALK) ? false : (rq->flags & RT_FLAG_CULL_WALK) ? true
-                              : cull_env >= 0 ? cull_env != 0 : sc->cull_density >= LT_CULL_MIN_DENSITY;
-    const bool ltcull = lt_cull_ok && lt_cull_want;
-    const bool streamed = !traverse && sc->n_sph_pad > RESIDENT_MAX;
-    p.chunk = traverse ? 0 : (streamed ? STREAM_CHUNK : sc->n_sph_pad);
-    p.n_chunks = p.chunk ? (sc->n_sph_pad + p.chunk - 1) / p.chunk : 0;
-    p.path32 = (sc->n_sph + sc->n_tri) > 65536u ? 1u : 0u;
-    size_t geom_bytes = traverse ? 0 : (size_t)(p.chunk ? p.chunk : 1) * sizeof(float4);
-    p.lds_cand_off = (uint32_t)geom_bytes;
-    size_t path_bytes = (size_t)p.depth * rtk::BLOCK * (p.path32 ? 4 : 2);
-    // ---- LDS plan of a traversal launch.  Occupancy is worth more than long leaf lists (c3: 6 workgroups per CU with
-    // 7 slots +1.5 % over 5 with 8; c5: 5 with 5 slots +7.5 % over 4 with 8), and an uncapped stack more than either
-    // (the HBM-overflow test on every push / pop costs 6...10 %).  So: the target number of workgroups per CU follows
-    // from the kernel's registers (five waves per SIMD for both node formats).  The exact-node kernel has 7 slots, fixed; the quantised
-    // kernel's lists shrink from MAXL down to MINL slots to reach its target, and a quantised walk whose whole stack still
-    // does not fit takes the capped-stack kernel.
-    // stack slots per lane: up to bvh_depth pending right children (+ 1 spare); the LDS-tree kernel's branch-free step
-    // adds the DONE sentinel in slot 0 and needs the free slot its unconditional stores land in
-    // output staging (one tile per wave): wherever the LDS plan has room for it
-    const bool want_stage = dbg(DBG_NO_STAGE) == 0 && ((traverse && !ltree) || streamed);     // the kernels it is compiled into (see there)
-    const bool list16 = traverse && !ltree && n_prims <= 65536u;          // 16-bit leaf-list entries: half the LDS
-    const size_t stage_bytes_wg = (size_t)rtk::STAGE_TILES * rtk::STAGE_TILE_BYTES * ((ltree ? rtk::LTREE_BLOCK : rtk::BLOCK) / 64);
-    const uint32_t stack_capped = sc->bvh_depth + 1;
-    const uint32_t stack_need = sc->bvh_depth + (ltree ? 2u : 1u);
-    uint32_t maxl = qnodes ? (uint32_t)rtk::MAXL : (uint32_t)rtk::MAXL_EXACT, stack_lds = stack_need;
-    bool capped = false;
-    if (traverse && qnodes) {
-        const size_t per_wg = (160u * 1024u - 4096u) / 5u - 512u;     // 4 KiB of slack, 464 B static LDS
-        const size_t slot = (size_t)rtk::BLOCK * (list16 ? sizeof(uint16_t) : sizeof(uint32_t));
-        const size_t fixed = path_bytes + (size_t)stack_need * rtk::BLOCK * sizeof(uint32_t) + (want_stage ? stage_bytes_wg : 0);
-        // (DBG_FORCE_CAPPED / DBG_STACK_LDS: tests drive the capped-stack kernel with small trees)
-        const bool force_capped = dbg(DBG_FORCE_CAPPED) != 0;
-        if (!force_capped && fixed + (size_t)rtk::MINL * slot <= per_wg) {
-            maxl = (uint32_t)std::min<size_t>((size_t)rtk::MAXL, (per_wg - fixed) / slot);
-        } else {
-            const uint32_t cap = dbg(DBG_STACK_LDS) > 0 ? (uint32_t)dbg(DBG_STACK_LDS) : STACK_LDS_MAX;
-            capped = stack_capped > cap;
-            stack_lds = capped ? cap : stack_need;
-        }
-    }
-    p.maxl = maxl;
-    p.stack_lds = stack_lds;
-    p.list16 = list16 ? 1u : 0u;
-    size_t cand_bytes = traverse ? (size_t)maxl * rtk::BLOCK * (list16 ? sizeof(uint16_t) : sizeof(uint32_t))
-                                 : (size_t)rtk::MAXC * rtk::BLOCK * sizeof(uint16_t);
-    p.lds_path_off = (uint32_t)(geom_bytes + cand_bytes);
-    const bool expanded = !traverse && sc->expanded && !(rq->flags & RT_FLAG_OC_BROAD_PHASE);
-    p.lds_rr_off = (uint32_t)(geom_bytes + cand_bytes + path_bytes);
-    size_t rr_bytes = expanded ? (size_t)(p.chunk ? p.chunk : 1) * sizeof(float) : 0;
-    p.lds_stack_off = (uint32_t)(geom_bytes + cand_bytes + path_bytes + rr_bytes);
-    size_t stack_bytes = traverse ? (size_t)stack_lds * rtk::BLOCK * sizeof(uint32_t) : 0;
-    size_t lds = geom_bytes + cand_bytes + path_bytes + rr_bytes + stack_bytes;
-    p.n_internal = sc->n_internal;
-    p.lds_node_off = 0;
-    const int bs = ltree ? rtk::LTREE_BLOCK : rtk::BLOCK;
-    if (ltree) {
-        // [nodes][leaf lists u16][path u16][stack u16]
-        size_t off = ((((size_t)sc->n_internal + 2) * rtk::LNODE_DW + n_prims) * 4 + 15) & ~(size_t)15;    // nodes, DONE, NaN field of n_prims + 19 dwords
-        p.lds_cand_off = (uint32_t)off;
-        // leaf-list slots: MAXL_LTREE, and up to MAXL_LTREE_MAX where the tree leaves room (fewer flushes forced by a full list)
-        uint32_t lt_maxl = rtk::MAXL_LTREE;
-        while (lt_maxl < (uint32_t)rtk::MAXL_LTREE_MAX &&
-               off + ((size_t)(lt_maxl + 1) + p.depth + stack_need) * bs * sizeof(uint16_t) <= LDS_LIMIT) lt_maxl++;
-        p.maxl = lt_maxl;
-        off += (size_t)lt_maxl * bs * sizeof(uint16_t);
-        p.lds_path_off = (uint32_t)off;
-        off += (size_t)p.depth * bs * sizeof(uint16_t);
-        p.lds_stack_off = (uint32_t)off;
-        off += (size_t)stack_need * bs * sizeof(uint16_t);
-        lds = off;
-    }
-    // compacted root tests of the exact-node L2 kernel (1 KiB per wave; RT_COMPACT=0 keeps the per-lane flush for A/B runs)
-    p.lds_cmp_off = 0xffffffffu;
-    const bool compact_env = dbg(DBG_COMPACT) != 0;
-    if (traverse && !qnodes && !ltree && compact_env && lds + 1024u * (rtk::BLOCK / 64) + 16 <= LDS_LIMIT) {
-        lds = (lds + 15) & ~(size_t)15;
-        p.lds_cmp_off = (uint32_t)lds;
-        lds += 1024u * (rtk::BLOCK / 64);
-    }
-    p.lds_stage_off = 0xffffffffu;
-    if (want_stage && lds + stage_bytes_wg <= LDS_LIMIT) {
-        lds = (lds + 15) & ~(size_t)15;
-        p.lds_stage_off = (uint32_t)lds;
-        lds += stage_bytes_wg;
-    }
-    if (lds > LDS_LIMIT) return fail(RT_ERR_LIMIT, "LDS budget exceeded (scene chunk + path stack)");
-    fill_camera(rq, p);
-    p.t_min = rq->t_min;
-    p.t_max = rq->t_max;
-    p.spp_f = (float)s_end;
-    p.spp_rcp = (s_end & (s_end - 1u)) == 0u ? 1.0f / (float)s_end : 0.0f;         // a power of two up to 2^31: exact in f32
+    const rtplan::SampleRange smp = pass ? rtplan::SampleRange{pass->begin, pass->end, true} : rtplan::SampleRange{0u, rqs[0].spp, false};
+    rtplan::Plan pl = rtplan::plan_launch(sh, rqs[0], n, smp, kn, p);
+    if (pl.status != RT_OK) return fail(pl.status, pl.error);
     p.geom_pk = sc->d_geom_pk;
     p.geom_px = sc->d_geom_px;
     p.geom = sc->d_geom;
@@ -487,52 +325,15 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
         p.q_step[i] = sc->grid.step[i];
         p.q_rstep[i] = 1.0f / sc->grid.step[i];
     }
-    p.root_ref = sc->root_ref;
-    if (ltree) p.root_ref = (p.root_ref & rtk::LEAF_BIT) ? (0x8000u | (p.root_ref & 0x7fffu)) : rtk::lt_r0(sc->n_internal) + p.root_ref * (uint32_t)rtk::LNODE_DW;
-    {
-        // refill threshold: long walks (large scenes) want finished lanes replaced sooner, short walks amortise the
-        // per-round shading / ray-generation code over more finished lanes (tools/variants_q.sh sweeps)
-        const int forced = dbg(DBG_REFILL_EIGHTHS);
-        p.refill_eighths = forced > 0 ? (uint32_t)forced : (n_prims >= RT_QNODES_MIN_PRIMS ? 4u : 2u);
-    }
     p.leaf_of = sc->d_leaf_of;
     p.world_rank = sc->has_order ? sc->d_world_rank : nullptr;
-    p.n_strips = n;
-    // Tile shape: 64x1 keeps each tile on whole 64-byte lines of the RGB8 strip (64 px * 3 B = 3 lines),
-    // so one CU / one XCD L2 writes every byte of a line; 8x8 tiles split lines across XCDs and doubled the
-    // HBM write traffic (profiles/r01_*).
-    p.tiles_x = (p.W + 63u) / 64u;
-    p.tiles_per_strip = p.tiles_x * p.Hs;
-    // Sample units (rt_kernel.hip.h): pixel slots per wave, the commit threshold, the division by the units per pixel
-    {
-        p.grp = p.upp >= 8u ? 1u : (8u + p.upp - 1u) / p.upp;            // a slot is at least 8 units
-        const uint64_t slot_units = (uint64_t)p.grp * p.upp;
-        p.grp_magic = p.grp > 1u ? (uint32_t)((1ull << 32) / p.grp) + 1u : 0u;
-        p.slot_stride = 1u + (uint32_t)slot_units;
-        // enough slots for the pixels in flight (64 lanes' units, each pixel open as long as its longest path) plus the complete
-        // ones a commit waits for.  The price of every slot is scratch that L2 has to keep between a sample's store and its pixel's
-        // commit; what L2 does not keep goes out to HBM (c3, WRITE_SIZE per 23.7 MiB frame / Mrays/s: 32 slots 135 / 15 580, 24 slots
-        // 88 / 15 330, 20 slots 40 / 15 270, 16 slots 33 / 14 300; c4 at 12 / 16 / 24 slots: 15 615 / 16 070 / 16 220 Mrays/s).  The
-        // rate is what this path is measured by, HBM is idle either way (c3: 20 GB/s of 8 TB/s): 384 units per wave, at most 32 slots
-        // — but never fewer than 16 pixels open while a pixel is at most 256 units: a slot is free again only when its LAST sample is in,
-        // and with the 4 slots the 384 units gave the reference's literal 100 samples per pixel a wave stood still for want of a slot
-        // (the mesh at 100 spp: 4 / 8 / 16 / 32 slots 6 990 / 7 250 / 7 340 / 7 370 Mrays/s); 8 up to 1 024 units, 4 beyond (scratch:
-        // 12 bytes per unit and slot for every wave of the grid)
-        const int forced = dbg(DBG_SLOTS);
-        const uint64_t fewest = slot_units <= 256u ? 16u : slot_units <= 1024u ? 8u : 4u;
-        p.n_slots = forced > 0 ? std::min<uint32_t>((uint32_t)forced, rtk::SLOTS_MAX)
-                               : (uint32_t)std::min<uint64_t>(rtk::SLOTS_MAX, std::max<uint64_t>(fewest, 384u / slot_units));
-        const uint32_t cs = dbg(DBG_COMMIT_SLOTS) > 0 ? (uint32_t)dbg(DBG_COMMIT_SLOTS) : std::max<uint32_t>(1u, p.n_slots / 4u);     // (c3: 4 ... 20 of 32 within 1 %)
-        p.commit_slots = std::min<uint32_t>(cs, p.n_slots);
-        // q / d == mulhi(q, floor(2^32 / d) + 1) whenever q * d < 2^32: q < 65 * upp with upp <= RT_MAX_SPP (4096)
-        p.spp_magic = p.upp > 1u ? (uint32_t)((1ull << 32) / p.upp) + 1u : 0u;
-        p.slotu_magic = (uint32_t)((1ull << 32) / slot_units) + 1u;
-    }
-    const uint64_t n_tiles = (uint64_t)p.tiles_per_strip * n;
-    if (n_tiles > 0x1fffffffull) return fail(RT_ERR_LIMIT, "too many tiles in one launch");
-    p.tiles_total = (uint32_t)n_tiles;
-    p.n_tiles = (uint32_t)n_tiles;             // (queue entries: the split into whole tiles and quarters follows the grid below)
-    p.tiles_big = (uint32_t)n_tiles;
+    p.big = sc->d_big;
+    p.n_big = sc->n_big;
+    p.r_slack = sh.r_slack;
+    p.tri_k = sc->tri_k;
+    p.tri_diag = sc->tri_diag;
+    p.tri_es = sc->tri_es;
+    p.tri_e = sc->tri_e;
     for (uint32_t i = 0; i < n; i++) {
         p.strips[i].seed = rqs[i].seed;
         p.strips[i].rgb = (uint8_t*)d_rgb[i];
@@ -547,95 +348,30 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
     p.strip_cost = dbg(DBG_STRIP_COST) ? d_strip_cost : nullptr;
 
     // persistent grid: as many workgroups as the chip holds at this LDS/VGPR budget
+    const rtk::KernelFn kern = pl.isect < 2 ? rtk::kernel_linear(pl.isect, pl.expanded) : rtk::kernel_traverse(pl.isect, pl.count_steps);
     int per_cu = 0;
-    const bool count_steps = traverse && (rq->flags & RT_FLAG_COUNT_STEPS);
-    const bool cull_run = cull;
-    p.big = sc->d_big;
-    p.n_big = sc->n_big;
-    p.r_slack = sc->r_slack;
-    p.tri_k = sc->tri_k;
-    p.tri_diag = sc->tri_diag;
-    p.tri_es = sc->tri_es;
-    p.tri_e = sc->tri_e;
-    const rtk::KernelFn kern = traverse ? rtk::kernel_traverse(ltree ? (ltcull ? 4 : 3) : qnodes ? (cull_run ? (capped ? 6 : 5) : capped ? 2 : 1) : xcull ? 7 : 0, count_steps) : rtk::kernel_linear(streamed, expanded);
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, bs, lds));
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, pl.block, pl.lds));
     if (per_cu < 1) per_cu = 1;
     if (dbg(DBG_VERBOSE))
         fprintf(stderr, "[rt] engine %d%s  lds %zu B  workgroups/CU %d  leaf slots %u  bvh depth %u  leaf density %.3f  prims %u\n",
-                traverse ? (ltree ? (ltcull ? 7 : 4) : qnodes ? (cull_run ? 5 : 3) : xcull ? 6 : 2) : (streamed ? 1 : 0), capped ? " (capped stack)" : "", lds, per_cu, maxl,
-                sc->bvh_depth, sc->leaf_density, n_prims);
-    uint32_t blocks = (uint32_t)sc->ctx->n_cu * (uint32_t)per_cu;
-    const uint32_t waves_per_wg = (uint32_t)bs / 64u;
-    const uint32_t useful = (p.n_tiles + waves_per_wg - 1) / waves_per_wg;   // a wave needs at least one tile
-    if (blocks > useful) blocks = useful ? useful : 1;
-    // Queue entries.  Whole tiles (64 pixels x spp units) first, and the LAST ones — two tiles per wave of the grid — in parts: quarters
-    // (16 pixels), so that the launch's tail is one short entry long.  Two cases take parts for EVERY tile (round 4, measured on the
-    // 100 352-triangle mesh: 1080p / 4 spp +13 %, 100 spp +19 %): a launch with fewer than 16 tiles per wave — its expensive tiles
-    // (handed out first: the bottom rows) are still being worked on when the cheap ones at the end of the queue have long run out, and
-    // an expensive whole tile is a large share of such a launch — and more than 16 samples per pixel, where a whole tile is thousands of
-    // units; from 33 samples per pixel up the parts are sixteenths (4 pixels).  The price where it is not needed: 1-2 % (c2, c4).
-    {
-        const int forced = dbg(DBG_TAIL_TILES);
-        const uint64_t waves = (uint64_t)blocks * waves_per_wg;
-        const bool all_parts = p.tiles_total < 16ull * waves || p.upp > 16u;
-        uint64_t conv = std::min<uint64_t>(p.tiles_total, forced >= 0 ? (uint64_t)forced : all_parts ? (uint64_t)p.tiles_total : 2ull * waves);
-        p.sub_shift = p.upp > 32u ? 4u : 2u;
-        if ((((uint64_t)p.tiles_total - conv) + (conv << p.sub_shift)) > 0x7fffffffull) p.sub_shift = 2u;       // (entry numbers are 31 bits)
-        p.tiles_big = p.tiles_total - (uint32_t)conv;
-        p.n_tiles = p.tiles_big + ((uint32_t)conv << p.sub_shift);
-    }
-    p.ovf_stride = blocks * (uint32_t)bs;
+                pl.engine, pl.capped ? " (capped stack)" : "", pl.lds, per_cu, pl.maxl_l2, sh.bvh_depth, sh.leaf_density, sh.n_sph + sh.n_tri);
+    rtplan::plan_queue(pl, (uint32_t)sc->ctx->n_cu * (uint32_t)per_cu, kn, p);
     p.stack_ovf = nullptr;
-    if (traverse && capped) {
-        const size_t words = (size_t)(stack_capped - stack_lds) * p.ovf_stride;
-        if (words > sc->stack_ovf_words) {
-            if (sc->d_stack_ovf) {
-                if (sc->ovf_done) HIPCHK(hipEventSynchronize(sc->ovf_done));   // a launch in flight may still use the old area
-                (void)hipFree(sc->d_stack_ovf);
-                sc->d_stack_ovf = nullptr;
-                sc->stack_ovf_words = 0;
-            }
-            HIPCHK(hipMalloc(&sc->d_stack_ovf, words * sizeof(uint32_t)));
-            sc->stack_ovf_words = words;
-        }
+    if (pl.capped) {
+        int rc = acquire_stack_ovf(sc, pl.ovf_words);
+        if (rc) return rc;
         p.stack_ovf = sc->d_stack_ovf;
     }
-    // the launch's ring: the one this stream used last, else a free one, else the least recently used (after its last launch)
+    if (dbg(DBG_VERBOSE))
+        fprintf(stderr, "[rt] sample-unit ring %zu B: %u units per pixel, %u slots of %u records per wave\n", pl.ring_bytes, p.upp, p.n_slots,
+                p.slot_stride);
     rt_scene::Ring* rg = nullptr;
-    {
-        const size_t ring_bytes = (size_t)blocks * waves_per_wg * p.n_slots * p.slot_stride * 12u;
-        if (dbg(DBG_VERBOSE))
-            fprintf(stderr, "[rt] sample-unit ring %zu B: %u units per pixel, %u slots of %u records per wave\n", ring_bytes, p.upp, p.n_slots,
-                    p.slot_stride);
-        for (auto& r : sc->rings)
-            if (r.d && r.last == stream) { rg = &r; break; }
-        if (!rg)
-            for (auto& r : sc->rings)
-                if (!r.d) { rg = &r; break; }
-        if (!rg) {
-            rg = &sc->rings[0];
-            for (auto& r : sc->rings)
-                if (r.stamp < rg->stamp) rg = &r;
-        }
-        if (rg->bytes < ring_bytes) {
-            if (rg->d) {
-                if (rg->done) HIPCHK(hipEventSynchronize(rg->done));     // a launch in flight may still use the old area
-                (void)hipFree(rg->d);
-                rg->d = nullptr;
-                rg->bytes = 0;
-            }
-            HIPCHK(hipMalloc(&rg->d, ring_bytes));
-            rg->bytes = ring_bytes;
-        }
-        if (!rg->done) HIPCHK(hipEventCreateWithFlags(&rg->done, hipEventDisableTiming));
-        else if (rg->last != stream) HIPCHK(hipStreamWaitEvent(stream, rg->done, 0));
-        rg->last = stream;
-        rg->stamp = ++sc->ring_clock;
-        p.ring = rg->d;
-    }
-    dim3 grid(blocks), block(bs);
+    int rc = acquire_ring(sc, stream, pl.ring_bytes, rg);
+    if (rc) return rc;
+    p.ring = rg->d;
+    dim3 grid(pl.blocks), block(pl.block);
     EvPair ev;
-    int rc = get_events(sc, ev);
+    rc = get_events(sc, ev);
     if (rc) return rc;
     if (p.stack_ovf) {
         if (sc->ovf_done) HIPCHK(hipStreamWaitEvent(stream, sc->ovf_done, 0));
@@ -643,9 +379,9 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
     }
     HIPCHK(hipMemsetAsync(p.queue, 0, sizeof(unsigned long long), stream));
     HIPCHK(hipEventRecord(ev.a, stream));
-    sc->last_engine = traverse ? (ltree ? (ltcull ? 7u : 4u) : qnodes ? (cull_run ? 5u : 3u) : xcull ? 6u : 2u) : (streamed ? 1u : 0u);
-    sc->last_form = expanded ? 1u : 0u;
-    hipLaunchKernelGGL(kern, grid, block, lds, stream, p);
+    sc->last_engine = (uint32_t)pl.engine;
+    sc->last_form = pl.expanded ? 1u : 0u;
+    hipLaunchKernelGGL(kern, grid, block, pl.lds, stream, p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ev.b, stream));
     HIPCHK(hipEventRecord(rg->done, stream));
@@ -769,14 +505,10 @@ static int ensure_ctx(DeviceCtx* c) {
     if (c->stream) return RT_OK;
     HIPCHK(hipSetDevice(c->dev));
     HIPCHK(hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->dev));
-    for (int streamed = 0; streamed < 2; streamed++)
-        for (int expanded = 0; expanded < 2; expanded++)
-            HIPCHK(hipFuncSetAttribute((const void*)rtk::kernel_linear(streamed != 0, expanded != 0),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
-    for (int variant = 0; variant < 8; variant++)
-        for (int stats = 0; stats < 2; stats++)
-            HIPCHK(hipFuncSetAttribute((const void*)rtk::kernel_traverse(variant, stats != 0),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
+    for (int isect = 0; isect < rtplan::N_ISECT; isect++)
+        for (int alt = 0; alt < 2; alt++)     // the expanded broad phase (ISECT 0, 1) / the node-visit counting twin (ISECT 2 ... 9)
+            HIPCHK(hipFuncSetAttribute((const void*)(isect < 2 ? rtk::kernel_linear(isect, alt != 0) : rtk::kernel_traverse(isect, alt != 0)),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)rtplan::LDS_LIMIT));
     hipStream_t st = nullptr, cs = nullptr;
     HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     HIPCHK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
@@ -805,22 +537,14 @@ static int rt_scene_destroy_impl(rt_scene* sc);
 // Everything rt_scene_create derives on the host from the primitive lists: the device-layout arrays and the reference's
 // candidate-filter BVH.  rt_render_frame builds it ONCE per job and uploads it to every device.
 struct HostScene {
-    uint32_t ns = 0, nt = 0, n_sph_pad = 0;
+    rtplan::SceneShape shape;        // what the engine rules read (rt_plan.h); the rest is uploaded
     std::vector<float4> geom, geom_pk, geom_px, mat, tri_box, geom_r;
     std::vector<float> emis, tri;
-    bool expanded = false, quant_ok = false;
-    float leaf_density = 0.f, bvh_build_ms = 0.f;
-    uint32_t n_internal = 0;         // internal nodes of the tree (bvh.trav may carry one placeholder)
+    float bvh_build_ms = 0.f;
     rtbvh::FlatBVH bvh;
-    std::vector<uint32_t> big;       // culled walk: spheres far larger than the rest, and ...
+    std::vector<uint32_t> big;       // culled walk: spheres far larger than the rest (shape.r_slack: the largest radius among the others)
     uint32_t n_big = 0;
-    float r_slack = 0.f;             // ... the largest radius among the others
-    bool cull_pays = false;          // enough of the rays hit something for nearer-first + culling to beat the plain walk
-    bool inverted_boxes = false;     // some sphere has a negative radius
     float tri_k = 0.f, tri_diag = 0.f, tri_es = 0.f, tri_e = 0.f;
-    bool xcull_pays = false;         // a scene with triangles that the culled walk over the exact nodes may take, and where it pays
-    bool tri_ok = false;             //   ... may take at all (every triangle has a finite bound or a place in the list)
-    float cull_density = 0.f;        // sum of the other spheres' box areas / area of the box around them
     std::vector<uint32_t> world_rank;   // the caller's world_index (one dummy entry when none came)
     bool has_order = false;
 };
@@ -843,8 +567,9 @@ static int check_world(const rt_sphere* sp, uint32_t ns, const rt_triangle* tr, 
 
 static void build_host_scene(const rt_sphere* sp, uint32_t ns, const rt_triangle* tr, uint32_t nt, const uint32_t* world_index,
                              HostScene& hs) {
-    hs.ns = ns;
-    hs.nt = nt;
+    rtplan::SceneShape& sh = hs.shape;
+    sh.n_sph = ns;
+    sh.n_tri = nt;
     hs.has_order = world_index != nullptr && ns + nt > 0;
     const uint32_t np = ns + nt;
     // the reference's candidate-filter BVH (slave main.rs:60), built once per scene instead of per strip
@@ -878,7 +603,7 @@ static void build_host_scene(const rt_sphere* sp, uint32_t ns, const rt_triangle
     }
     rtbvh::FlatBVH& bvh = hs.bvh;
     hs.bvh_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tb0).count();
-    hs.n_internal = (uint32_t)bvh.trav.size();        // before the placeholders below
+    sh.n_internal = (uint32_t)bvh.trav.size();        // before the placeholders below
     if (bvh.nodes.empty()) bvh.nodes.push_back(rtbvh::FlatNode{{0, 0, 0}, 0xffffffffu, {0, 0, 0}, 0});
     if (bvh.leaf_of.empty()) bvh.leaf_of.push_back(0);
     if (bvh.trav.empty()) bvh.trav.push_back(rtbvh::TravNode{});
@@ -924,14 +649,16 @@ static void build_host_scene(const rt_sphere* sp, uint32_t ns, const rt_triangle
         tr = tr_store.data();
         hs.has_order = true;                 // (ties of the plain linear-scan semantics: by place in `world`, no longer by number)
     }
+    sh.bvh_depth = bvh.depth;
+    sh.root_ref = bvh.root_ref;
     if (hs.has_order) hs.world_rank.assign(wi_store.begin(), wi_store.begin() + np);
     else hs.world_rank.assign(1, 0u);
-    hs.n_sph_pad = (ns + rtk::UNROLL - 1) / rtk::UNROLL * rtk::UNROLL;
+    sh.n_sph_pad = (ns + rtk::UNROLL - 1) / rtk::UNROLL * rtk::UNROLL;
     std::vector<float4>& geom = hs.geom;
     std::vector<float4>& mat = hs.mat;
     std::vector<float>& emis = hs.emis;
     std::vector<float>& tri = hs.tri;
-    geom.assign(hs.n_sph_pad ? hs.n_sph_pad : 1, make_float4(0.f, 0.f, 0.f, 0.f));
+    geom.assign(sh.n_sph_pad ? sh.n_sph_pad : 1, make_float4(0.f, 0.f, 0.f, 0.f));
     mat.assign(np ? np : 1, make_float4(0.f, 0.f, 0.f, 0.f));
     emis.assign(np ? np : 1, 0.f);
     tri.assign((size_t)nt * 9 + 1, 0.f);
@@ -943,11 +670,11 @@ static void build_host_scene(const rt_sphere* sp, uint32_t ns, const rt_triangle
         emis[i] = sp[i].emission;
     }
     // padding spheres can never pass either phase: rr = -inf makes every discriminant -inf
-    for (uint32_t i = ns; i < hs.n_sph_pad; i++) geom[i] = make_float4(0.f, 0.f, 0.f, -INFINITY);
+    for (uint32_t i = ns; i < sh.n_sph_pad; i++) geom[i] = make_float4(0.f, 0.f, 0.f, -INFINITY);
     // pair layout for the packed-FP32 broad phase: (c0x,c1x,c0y,c1y) (c0z,c1z,rr0,rr1)
     std::vector<float4>& geom_pk = hs.geom_pk;
     geom_pk.assign(geom.size(), make_float4(0.f, 0.f, 0.f, 0.f));
-    for (uint32_t i = 0; i + 1 < hs.n_sph_pad; i += 2) {
+    for (uint32_t i = 0; i + 1 < sh.n_sph_pad; i += 2) {
         geom_pk[i] = make_float4(geom[i].x, geom[i + 1].x, geom[i].y, geom[i + 1].y);
         geom_pk[i + 1] = make_float4(geom[i].z, geom[i + 1].z, geom[i].w, geom[i + 1].w);
     }
@@ -964,7 +691,7 @@ static void build_host_scene(const rt_sphere* sp, uint32_t ns, const rt_triangle
         std::vector<float4> px(geom.size());
         std::vector<double> ratio;
         const double K = std::ldexp(1.0, -16);
-        for (uint32_t i = 0; i < hs.n_sph_pad; i++) {
+        for (uint32_t i = 0; i < sh.n_sph_pad; i++) {
             if (i >= ns) {
                 px[i] = make_float4(0.f, 0.f, 0.f, INFINITY);      // w = +inf: t = -inf, never a candidate
                 continue;
@@ -977,7 +704,7 @@ static void build_host_scene(const rt_sphere* sp, uint32_t ns, const rt_triangle
             px[i] = make_float4(sp[i].cx, sp[i].cy, sp[i].cz, wf);
             if (rr > 0) ratio.push_back(K * 2.0 * cc / rr);
         }
-        for (uint32_t i = 0; i + 1 < hs.n_sph_pad; i += 2) {
+        for (uint32_t i = 0; i + 1 < sh.n_sph_pad; i += 2) {
             geom_px[i] = make_float4(px[i].x, px[i + 1].x, px[i].y, px[i + 1].y);
             geom_px[i + 1] = make_float4(px[i].z, px[i + 1].z, px[i].w, px[i + 1].w);
         }
@@ -990,7 +717,7 @@ static void build_host_scene(const rt_sphere* sp, uint32_t ns, const rt_triangle
         }
         for (uint32_t i = 0; i < ns && ok; i++)
             ok = std::isfinite(px[i].x) && std::isfinite(px[i].y) && std::isfinite(px[i].z) && std::isfinite(px[i].w);
-        hs.expanded = ok;
+        sh.expanded = ok;
     }
     hs.tri_box.assign((size_t)nt * 2 + 1, make_float4(0.f, 0.f, 0.f, 0.f));
     for (uint32_t i = 0; i < nt; i++) {
@@ -1013,7 +740,7 @@ static void build_host_scene(const rt_sphere* sp, uint32_t ns, const rt_triangle
             std::nth_element(edge.begin(), edge.begin() + np / 2, edge.end());
             ok = edge[np / 2] >= 8.0f;
         }
-        hs.quant_ok = ok;
+        sh.quant_ok = ok;
         // leaf density = sum of primitive box areas / area of the scene box ~ leaves a random ray reaches; above ~2
         // the walk is bound by the exact leaf tests, where the lighter exact-node kernel (5 waves/SIMD) wins
         double area = 0.0, root = 0.0;
@@ -1031,12 +758,12 @@ static void build_host_scene(const rt_sphere* sp, uint32_t ns, const rt_triangle
             const double ex = (double)hi[0] - lo[0], ey = (double)hi[1] - lo[1], ez = (double)hi[2] - lo[2];
             root = ex * ey + ey * ez + ez * ex;
         }
-        hs.leaf_density = root > 0.0 ? (float)(area / root) : INFINITY;
+        sh.leaf_density = root > 0.0 ? (float)(area / root) : INFINITY;
     }
     hs.geom_r.assign(ns ? ns : 1, make_float4(0.f, 0.f, 0.f, 0.f));
     for (uint32_t i = 0; i < ns; i++) {
         hs.geom_r[i] = make_float4(sp[i].cx, sp[i].cy, sp[i].cz, sp[i].radius);
-        if (sp[i].radius < 0.0f) hs.inverted_boxes = true;
+        if (sp[i].radius < 0.0f) sh.inverted_boxes = true;
     }
     // culled walk: its distance bound carries sqrt(2) * (largest radius) of slack, so the few spheres far larger than the
     // rest (a ground sphere) are listed apart and root-tested at every query start instead
@@ -1061,7 +788,7 @@ static void build_host_scene(const rt_sphere* sp, uint32_t ns, const rt_triangle
             if (!is_big[i] && rad[i] > rs) rs = rad[i];
         hs.big = cand;
         hs.n_big = (uint32_t)cand.size();
-        hs.r_slack = rs;
+        sh.r_slack = rs;
         if (hs.big.empty()) hs.big.push_back(0);
         // Does it pay?  The ratio below is the expected number of (non-big) primitive boxes a random line through their
         // common box meets (Cauchy: box areas add up).  tools/cull_matrix.py, 2560x1440: sparse fields at 0.06...0.35 lose
@@ -1081,8 +808,8 @@ static void build_host_scene(const rt_sphere* sp, uint32_t ns, const rt_triangle
         }
         const double ex = (double)hi[0] - lo[0], ey = (double)hi[1] - lo[1], ez = (double)hi[2] - lo[2];
         const double root = ex * ey + ey * ez + ez * ex, diag = std::sqrt(ex * ex + ey * ey + ez * ez);
-        hs.cull_density = root > 0.0 ? (float)(area / root) : 0.f;
-        hs.cull_pays = nt == 0 && root > 0.0 && std::isfinite(area / root) && area / root >= 0.7 && (double)rs <= 0.05 * diag;
+        sh.cull_density = root > 0.0 ? (float)(area / root) : 0.f;
+        sh.cull_pays = nt == 0 && root > 0.0 && std::isfinite(area / root) && area / root >= 0.7 && (double)rs <= 0.05 * diag;
         // (What the bounds claim — no accepted root of a primitive outside the `big` list enters its box beyond cull_bound /
         // cull_bound_tri of its compared distance — is tested by itself, on 1.8e7 seeded and adversarial (ray, primitive, box)
         // triples incl. K -> 0.25, |det| -> 1e-5, origins at 1e3 and tangent rays: tests/test_cull_lemma.py with the bounds
@@ -1143,10 +870,10 @@ static void build_host_scene(const rt_sphere* sp, uint32_t ns, const rt_triangle
                 for (uint32_t q : bigt) hs.big.push_back(q);
                 hs.n_big = (uint32_t)hs.big.size();
                 if (hs.big.empty()) hs.big.push_back(0);
-                hs.cull_density = (float)dens;
-                hs.xcull_pays = std::isfinite(dens) && dens >= 0.7 && (double)rs <= 0.05 * diag2 && (double)hs.tri_diag <= 0.05 * diag2;
+                sh.cull_density = (float)dens;
+                sh.xcull_pays = std::isfinite(dens) && dens >= 0.7 && (double)rs <= 0.05 * diag2 && (double)hs.tri_diag <= 0.05 * diag2;
             }
-            hs.tri_ok = ok;
+            sh.tri_ok = ok;
         }
     }
 }
@@ -1173,17 +900,9 @@ static int upload_scene(int device, const HostScene& hs, rt_scene** out) {
     } guard{sc};
     const rtbvh::FlatBVH& bvh = hs.bvh;
     sc->ctx = ctx;
-    sc->n_sph = hs.ns;
-    sc->n_tri = hs.nt;
-    sc->n_sph_pad = hs.n_sph_pad;
-    sc->expanded = hs.expanded;
+    sc->shape = hs.shape;
     sc->bvh_build_ms = hs.bvh_build_ms;
-    sc->root_ref = bvh.root_ref;
-    sc->bvh_depth = bvh.depth;
-    sc->n_internal = hs.n_internal;
     sc->grid = bvh.grid;
-    sc->quant_ok = hs.quant_ok;
-    sc->leaf_density = hs.leaf_density;
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess) return fail(RT_ERR_HIP, "hipEventCreate failed");
     if (hipEventCreate(&e1) != hipSuccess) {
@@ -1223,16 +942,10 @@ static int upload_scene(int device, const HostScene& hs, rt_scene** out) {
     SC_UP(d_geom_r, hs.geom_r);
     SC_UP(d_big, hs.big);
     sc->n_big = hs.n_big;
-    sc->r_slack = hs.r_slack;
-    sc->cull_pays = hs.cull_pays;
-    sc->inverted_boxes = hs.inverted_boxes;
     sc->tri_k = hs.tri_k;
     sc->tri_diag = hs.tri_diag;
     sc->tri_es = hs.tri_es;
     sc->tri_e = hs.tri_e;
-    sc->xcull_pays = hs.xcull_pays;
-    sc->tri_ok = hs.tri_ok;
-    sc->cull_density = hs.cull_density;
     SC_CHK(hipMalloc(&sc->d_counters, COUNTER_WORDS * sizeof(unsigned long long)));
     SC_CHK(hipMemsetAsync(sc->d_counters, 0, COUNTER_WORDS * sizeof(unsigned long long), ctx->stream));
     SC_CHK(hipEventRecord(e1, ctx->stream));
@@ -1244,7 +957,7 @@ static int upload_scene(int device, const HostScene& hs, rt_scene** out) {
     (void)hipEventDestroy(e1);
     if (dbg(DBG_VERBOSE))
         fprintf(stderr, "[rt] scene: %u prims  culled walk: %u big spheres, slack radius %g, box density %.3f -> %s  bvh build %.2f ms (host)  uploads %.2f ms  upload total %.2f ms\n",
-                hs.ns + hs.nt, hs.n_big, hs.r_slack, hs.cull_density, hs.cull_pays ? "default" : "off", sc->bvh_build_ms, sc->h2d_ms,
+                hs.shape.n_sph + hs.shape.n_tri, hs.n_big, hs.shape.r_slack, hs.shape.cull_density, hs.shape.cull_pays ? "default" : "off", sc->bvh_build_ms, sc->h2d_ms,
                 std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_create0).count());
     guard.sc = nullptr;
     *out = sc;

@@ -32,14 +32,11 @@
 #include <type_traits>
 #include <stdint.h>
 
+#include "rt_consts.h"
 #include "rt_cull.h"
 
 namespace rtk {
 
-constexpr int BLOCK = 256;       // 4 waves
-#ifndef RT_MAXC
-#define RT_MAXC 16
-#endif
 #ifndef RT_MINWAVES
 #define RT_MINWAVES 4
 #endif
@@ -70,17 +67,7 @@ constexpr int BLOCK = 256;       // 4 waves
 #ifndef RT_MINWAVES_QTRAV       // quantised-node kernels: 96 VGPRs, no spill slots (unbounded they take 97-99 = 4 waves/SIMD)
 #define RT_MINWAVES_QTRAV 5
 #endif
-constexpr int MAXC = RT_MAXC;    // candidate list slots per lane (per chunk)
-constexpr int CHUNK = 2048;      // max spheres per LDS chunk (32 KiB): list entries carry an 8-bit group index
 constexpr int UNROLL = 8;        // broad-phase unroll; chunk sizes are padded to this
-constexpr int MAX_BATCH = 64;    // strips per launch
-constexpr int TRAV_STACK = 64;   // traversal stack entries per lane (host falls back to the linear scan beyond)
-#ifndef RT_MAXL
-#define RT_MAXL 8
-#endif
-#ifndef RT_MINL                 // the host may shrink the leaf lists down to this many slots to fit one more workgroup per CU
-#define RT_MINL 4
-#endif
 #ifndef RT_STEPS_PER_CHECK
 #define RT_STEPS_PER_CHECK 8
 #endif
@@ -90,29 +77,12 @@ constexpr int TRAV_STACK = 64;   // traversal stack entries per lane (host falls
 #ifndef RT_STEPS_PER_CHECK_Q    // quantised-node kernel (large scenes, long walks): c5 +1 % over 8
 #define RT_STEPS_PER_CHECK_Q 16
 #endif
-constexpr int MAXL = RT_MAXL;    // leaf-candidate slots per lane in traversal mode (flushed when full)
-constexpr int MINL = RT_MINL;
-constexpr int MAXL_EXACT = 7;     // exact-node kernel: fixed (see the kernel)
-// bias of the LDS-tree kernel's node references: reference 0x8000 = the dword behind node DONE (see the staging code)
-__host__ __device__ inline uint32_t lt_r0(uint32_t n_internal) { return 0x8000u - (n_internal + 1u) * 19u; }
-constexpr int LNODE_DW = 19;      // LDS-tree kernel: dwords per staged node (see the staging code); odd, so that the
-                                  // nodes start on all 32 banks
 #ifndef RT_LT_PARTIAL           // LDS-tree kernel: lanes with a pending candidate that make a partial root-test round (64: never)
 #define RT_LT_PARTIAL 40
 #endif
 #ifndef RT_LT_EAGER             // culled LDS-tree kernel: lanes with candidates but no hit yet that make a partial root-test round
 #define RT_LT_EAGER 12
 #endif
-#ifndef RT_MAXL_LTREE
-#define RT_MAXL_LTREE 12
-#endif
-constexpr int MAXL_LTREE = RT_MAXL_LTREE;     // LDS-tree kernel (16-bit entries): a block of RT_STEPS_PER_CHECK_LTREE appends always fits;
-constexpr int MAXL_LTREE_MAX = 16;            // the host gives a tree that leaves room up to this many slots (KParams::maxl; c3 14: +0.5 %)
-constexpr uint32_t LEAF_BIT = 0x80000000u;
-// Output staging (north_star: "coalesced HBM stores of the tile"): a wave collects the RGB8 bytes of up to STAGE_SLOTS of
-// its 64x1 tiles in LDS and writes a finished tile as 48 whole dwords = three whole 64-byte lines.  Byte stores of
-// single pixels reached HBM as partial lines: 1.3x (c3) to 13x (c5) write amplification (profiles/r01_*, r02_*).
-constexpr uint32_t STAGE_TILE_BYTES = 192;
 
 // ---- Sample units (round 4).  The unit of work a lane takes is ONE SAMPLE of a pixel.  A wave keeps up to
 // n_slots PIXEL SLOTS; a slot holds a group of `grp` neighbouring pixels of a tile (one pixel from 8 samples per pixel up) = grp x spp
@@ -121,9 +91,7 @@ constexpr uint32_t STAGE_TILE_BYTES = 192;
 // colour goes to its record and counts the slot's LDS counter down.  A slot whose counter has reached zero is COMMITTED — out of
 // order with respect to other slots, which is what keeps a long path from holding back anything but its own pixel: each of its
 // pixels is summed s = 0 .. spp-1 (the f32 sum order of main.rs:73-77), then mean, gamma, quantise — and freed.
-constexpr uint32_t SLOTS_MAX = 32;                // pixel slots per wave
 constexpr uint32_t SLOT_FREE = 0x80000000u;       // counter value of a free slot
-constexpr uint32_t STAGE_TILES = 3;               // output staging: tiles a wave may have open
 struct WaveQ {
     uint32_t cnt[SLOTS_MAX];                     // per slot: bits 0-12 units not yet finished (0: complete, waiting for its commit), bits 13-30 the ray
                                                  //   segments its finished units traced (per-strip cost), bit 31 = SLOT_FREE
@@ -132,8 +100,7 @@ struct WaveQ {
     uint32_t cost_acc[2];
     uint32_t cost_strip[2];
 };
-static_assert(sizeof(WaveQ) == 144, "WaveQ layout (rt_api.hip: LDS_LIMIT leaves 3 KiB of static LDS)");
-constexpr uint32_t COST_COPIES = 16;
+static_assert(sizeof(WaveQ) == 144, "WaveQ layout (rt_plan.h: LDS_LIMIT leaves 3 KiB of static LDS)");
 constexpr uint32_t SLOT_UNIT_BITS = 13;           // units of a slot < 2^13 (spp <= RT_MAX_SPP = 4096), segments of a slot < 2^18 (x 63 bounces)
 struct WaveStage {                               // kernels with output staging only
     int left[STAGE_TILES + 1];                   // pixels of the staged tile not yet committed (< 0: stage slot free)
@@ -2135,15 +2102,11 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
 #undef wst
 }
 
-// The kernels are instantiated in rt_kernels_lin.hip / rt_kernels_trav.hip; the host side (rt_api.hip) gets them here.
+// The kernels are instantiated in rt_kernels_lin.hip / rt_kernels_trav.hip; the host side (rt_api.hip) gets them here by their ISECT
+// (which engine runs which ISECT: the engine table of rt_plan.h).  nullptr for an ISECT the unit does not hold.
 using KernelFn = void (*)(const KParams);
-KernelFn kernel_linear(bool streamed, bool expanded);
+KernelFn kernel_linear(int isect, bool expanded);        // ISECT 0, 1; expanded: the expanded-form broad phase
+KernelFn kernel_traverse(int isect, bool stats);         // ISECT 2 ... 9; stats: the twin that also counts node visits (RT_FLAG_COUNT_STEPS)
 void sqrt_selftest_launch(uint32_t from, unsigned long long n, unsigned long long* d_bad, hipStream_t st);   // rt_kernels_trav.hip
-KernelFn kernel_traverse(int variant, bool stats = false);   // 0: exact nodes, 1: quantised nodes, 2: quantised nodes with the capped LDS stack,
-                                         // 3: exact nodes, whole tree resident in LDS (1024-thread workgroups); 4: the same, nearer child first, distance culling
-                                         // 5: quantised nodes, nearer child first, distance culling (spheres only); 6: the same, capped LDS stack
-                                         // 7: exact nodes, nearer child first, distance culling (spheres and triangles)
-                                         // stats: the variant that also counts node visits (RT_FLAG_COUNT_STEPS)
-constexpr int LTREE_BLOCK = 1024;
 
 }  // namespace rtk

@@ -7,8 +7,11 @@
 #include "rt_kernel.hip.h"
 
 namespace rtk {
-KernelFn kernel_linear(bool streamed, bool expanded) {
-    if (streamed) return expanded ? rt_tile_kernel<1, true> : rt_tile_kernel<1, false>;
-    return expanded ? rt_tile_kernel<0, true> : rt_tile_kernel<0, false>;
+KernelFn kernel_linear(int isect, bool expanded) {
+    switch (isect) {
+        case 1: return expanded ? rt_tile_kernel<1, true> : rt_tile_kernel<1, false>;
+        case 0: return expanded ? rt_tile_kernel<0, true> : rt_tile_kernel<0, false>;
+        default: return nullptr;
+    }
 }
 }  // namespace rtk

@@ -1,0 +1,395 @@
+// rt_plan.h — the plan of one batched launch (rt_api.hip launch_batch): which engine renders it, the LDS layout of its kernel,
+// the camera, the sample units and the split of its queue.  A pure function of the scene's shape, the request and the launch-path
+// knobs: plain C++, no HIP (also built by g++ in the CPU harness tests/host/plan_host.cpp, tests/test_launch_plan.py).
+//
+// The planner writes the kernel parameters it decides into `p`: rtk::KParams in rt_api.hip, a struct with the same scalar fields
+// in the harness.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+
+#include "rt_consts.h"
+#include "rt_tile.h"
+
+namespace rtplan {
+
+constexpr size_t LDS_LIMIT = 160 * 1024 - 3072;   // dynamic LDS budget; 3 KiB left for the kernels' static LDS (the queue words and
+                                                  // one rtk::WaveQ per wave: 16 + 16 x 160 bytes in the 1024-thread kernel)
+constexpr uint32_t RESIDENT_MAX = rtk::CHUNK;   // spheres kept wholly in LDS
+constexpr uint32_t STREAM_CHUNK = 2048;         // chunk size when streaming through LDS
+constexpr uint32_t STACK_LDS_MAX = 12;          // quantised-node kernel: stack entries per lane in LDS, deeper ones in HBM
+constexpr uint32_t RT_QNODES_MIN_PRIMS = 4096;   // from here up the traversal walks the 32-byte quantised nodes (tools/crossover_q.py)
+constexpr uint32_t DENSE_SCAN_MAX_PRIMS = 192;       // piles of up to this many spheres at a box density of at least ...
+constexpr float DENSE_SCAN_MIN_DENSITY = 3.0f;       // ... this keep the linear scan (see `traverse`)
+constexpr float DENSE_MID_MIN_DENSITY = 2.5f;        // dense sphere scenes of at least DENSE_MID_MIN_PRIMS whose tree does not fit LDS
+constexpr uint32_t DENSE_MID_MIN_PRIMS = 512;        //   take the quantised nodes for the culled walk (see `dense_mid`)
+constexpr float FIELD_MID_MIN_DENSITY = 0.15f;       // sphere fields below RT_QNODES_MIN_PRIMS take the quantised nodes from here up (`field_mid`)
+constexpr float LT_CULL_MIN_DENSITY = 2.2f;          // the LDS-resident tree is walked nearer child first, with distance culling, from this box density up
+                                                     // (tests/test_gpu_engine_rules.py: at 1.1 ... 1.8 a helix, a lattice and a colonnade of 700 ... 960
+                                                     // spheres lose 7 ... 17 % to the culled step, piles at 1.8 / 2.7 gain 2 / 38 %)
+constexpr uint32_t TRAVERSE_MIN_PRIMS = 2;      // from this many primitives up the BVH-traversal engine is the default.  (Rounds 1-3: 32, with a density rule below it;
+                                                // with the sample units the LDS-resident tree leads the scan on every scene of tools/small_scene_matrix.py —
+                                                // 2 ... 32 spheres, five families, 1.02 ... 1.36 x — but one pile of 32, and on c2's 16-sphere room by 5 ... 8 %.)
+
+// The scalar facts of a scene the rules read (rt_api.hip build_host_scene computes them).
+struct SceneShape {
+    uint32_t n_sph = 0, n_sph_pad = 0, n_tri = 0;   // spheres (padded to rtk::UNROLL), triangles
+    uint32_t bvh_depth = 0, n_internal = 0;         // the reference BVH: depth, internal nodes
+    uint32_t root_ref = 0;                          //   root reference (LEAF_BIT | prim when the tree is a single leaf)
+    float cull_density = 0.f;      // box density of the primitives outside the culled walks' `big` list
+    bool cull_pays = false;        // host heuristic: the scene is dense enough for the culled walk
+    bool xcull_pays = false;       //   ... the same for scenes with triangles
+    bool quant_ok = false;         // quantised walk usable and worthwhile (grid step small against the primitives)
+    bool tri_ok = false;           // every triangle has a finite culling bound or a place in the `big` list
+    float r_slack = 0.f;           // largest radius among the spheres not in `big`
+    bool inverted_boxes = false;   // a sphere of negative radius: its AABB has lo > hi (sphere.rs:65-72)
+    bool expanded = false;         // expanded-form broad phase: margin small against r^2
+    float leaf_density = 0.f;      // sum of primitive box areas / scene box area
+};
+
+// The launch-path knobs the plan reads (rt_api.hip DebugKnob: RT_LDS_TREE, RT_CULL_WALK, ...); the defaults are the product's.
+struct Knobs {
+    int lds_tree = 1;         // 0: never the LDS-resident tree engine
+    int cull_walk = -1;       // 0 / 1: culled walks off / on wherever they are valid; -1: host rule
+    int no_stage = 0;         // 1: no LDS output staging
+    int slots = 0;            // pixel slots per wave; 0: host rule
+    int commit_slots = 0;     // complete slots a commit waits for; 0: host rule
+    int force_capped = 0;     // 1: quantised walks take the capped-stack kernel
+    int stack_lds = 0;        // capped-stack kernel: stack entries per lane in LDS; 0: STACK_LDS_MAX
+    int compact = 1;          // 0: per-lane root tests in the exact-node L2 kernel
+    int refill_eighths = 0;   // refill threshold of the walks; 0: host rule
+    int tail_tiles = -1;      // tiles at the end of the queue handed out in parts; -1: host rule
+};
+
+// The engines (rt_tile_stats.engine) and the kernels that run them: template argument ISECT of rtk::rt_tile_kernel, that of the
+// capped-stack kernel where the engine has one, and the workgroup size.
+struct Engine {
+    int isect, isect_capped, block;
+};
+constexpr Engine ENGINES[8] = {
+    {0, -1, rtk::BLOCK},         // 0 linear scan, scene resident in LDS
+    {1, -1, rtk::BLOCK},         // 1 linear scan, scene streamed through LDS
+    {2, -1, rtk::BLOCK},         // 2 BVH traversal, exact nodes from L2
+    {3, 4, rtk::BLOCK},          // 3 BVH traversal, quantised nodes
+    {5, -1, rtk::LTREE_BLOCK},   // 4 BVH traversal, exact nodes resident in LDS
+    {7, 8, rtk::BLOCK},          // 5 BVH traversal, quantised nodes, nearer child first with distance culling (spheres only)
+    {9, -1, rtk::BLOCK},         // 6 BVH traversal, exact nodes, nearer child first with distance culling
+    {6, -1, rtk::LTREE_BLOCK},   // 7 BVH traversal, exact nodes resident in LDS, nearer child first with distance culling
+};
+constexpr int N_ISECT = 10;      // ISECT 0, 1: rtk::kernel_linear; 2 ... 9: rtk::kernel_traverse
+
+// Samples [begin, end) of the request's spp; pass: a progressive pass (the strips' running sums are carried).
+struct SampleRange {
+    uint32_t begin, end;
+    bool pass;
+};
+
+struct Plan {
+    int status = RT_OK;          // RT_ERR_LIMIT: a budget is exceeded (`error` says which); nothing else below is meaningful then
+    const char* error = nullptr;
+    int engine = 0;              // rt_tile_stats.engine
+    bool capped = false;         // the quantised walk keeps only p.stack_lds stack entries per lane in LDS
+    int isect = 0;               // the kernel: ENGINES[engine], capped or not
+    int block = rtk::BLOCK;      //   its workgroup size
+    bool expanded = false;       //   linear engines: the expanded-form broad phase (rt_tile_stats.broad_form)
+    bool count_steps = false;    //   traversal engines: the twin that counts node visits
+    size_t lds = 0;              // dynamic LDS bytes
+    uint32_t maxl_l2 = 0;        // leaf slots of an L2 walk (the RT_VERBOSE line's; the LDS tree's own are p.maxl)
+    uint32_t ovf_entries = 0;    // capped stack: entries per thread in the HBM overflow area
+    // plan_queue
+    uint32_t blocks = 0;         // workgroups of the persistent grid
+    size_t ring_bytes = 0;       // sample-unit ring: [waves][n_slots][slot_stride] 12-byte records
+    size_t ovf_words = 0;        // stack overflow area
+};
+
+// An explicit request flag wins over the process-level knob (RT_CULL_WALK), the knob over the host rule.
+inline bool cull_wanted(uint32_t flags, int knob, bool rule) {
+    return (flags & RT_FLAG_NO_CULL_WALK) ? false : (flags & RT_FLAG_CULL_WALK) ? true : knob >= 0 ? knob != 0 : rule;
+}
+
+// Camera::new with the slave's arguments (main.rs:42-50 -> camera.rs:19-47)
+template <class KP>
+void fill_camera(const rt_tile_request& rq, KP& p) {
+    const float origin[3] = {0.f, 0.f, 0.f};          // Point3::ZERO
+    const float aspect_ratio = (float)rq.width / (float)rq.height;
+    const float image_height = (float)rq.height;
+    const float vh = 2.0f * std::tan(rq.fov / 2.0f);
+    const float vw = aspect_ratio * vh;
+    const float hor[3] = {vw, 0.f, 0.f}, ver[3] = {0.f, vh, 0.f};
+    const float foc[3] = {0.f, 0.f, rq.focal_length};
+    for (int i = 0; i < 3; i++) {
+        p.org[i] = origin[i];
+        p.hor[i] = hor[i];
+        p.ver[i] = ver[i];
+        // origin - horizontal / 2 - vertical / 2 - (0,0,focal_length)
+        float v = origin[i] - hor[i] / 2.0f;
+        v = v - ver[i] / 2.0f;
+        v = v - foc[i];
+        p.llc[i] = v;
+    }
+    p.lens_radius = rq.aperture / 2.0f;
+    p.focus_distance = rq.focus_distance;
+    p.u_den = aspect_ratio * image_height - 1.0f;      // camera.rs:116
+    p.v_den = image_height - 1.0f;                     // camera.rs:117
+}
+
+// Everything of a launch of n_strips strips of request rq that does not depend on the device: engine, LDS plan, camera, sample
+// units, tiles.  `p` must come zeroed.
+template <class KP>
+Plan plan_launch(const SceneShape& sh, const rt_tile_request& rq, uint32_t n_strips, const SampleRange& smp, const Knobs& kn, KP& p) {
+    using namespace rtk;
+    Plan pl;
+    p.W = rq.width;
+    p.H = rq.height;
+    p.Hs = rq.height / rq.divisions;
+    // Everything the launch's work is sized by — slots, magic divisors, queue parts, scratch, primary rays — follows the units per
+    // pixel OF THIS LAUNCH; only the stream stride (spp_all) and the mean's divisor (s_end) see the job's whole sample count.
+    const uint32_t s_begin = smp.begin, s_end = smp.end;
+    p.upp = s_end - s_begin;
+    p.spp_all = rq.spp;
+    p.s_begin = s_begin;
+    p.gap = rq.spp - p.upp;
+    p.acc_out = smp.pass ? 1u : 0u;
+    p.depth = rq.max_bounces + 1;
+    p.n_sph = sh.n_sph;
+    p.n_sph_pad = sh.n_sph_pad;
+    p.n_tri = sh.n_tri;
+    p.flags = rq.flags;
+    // A sphere of negative radius has an AABB with lo > hi (Sphere::aabb = center -+ radius, sphere.rs:65-72): the reference's
+    // sign-selected slab test rejects such a box for (almost) every ray, while the finite-direction shortcut of the kernels
+    // (min / max of the two plane values, valid for lo <= hi) would enter it.  Such a scene is rendered with the crate's
+    // literal test and the whole box chain throughout (the RT_FLAG_FULL_CHAIN path): slower, and exact.
+    if (sh.inverted_boxes) p.flags |= RT_FLAG_FULL_CHAIN;
+    const uint32_t fl = rq.flags;
+    // Engine choice.  BVH traversal reproduces reference semantics only, needs the tree to fit the traversal
+    // stack, and pays off once the scene is larger than a couple of LDS chunks; RT_FLAG_BVH_TRAVERSE /
+    // RT_FLAG_LINEAR_SCAN force either engine for A/B runs and tests.
+    const uint32_t n_prims = sh.n_sph + sh.n_tri;
+    const bool trav_ok = !(fl & (RT_FLAG_EXACT_SCAN | RT_FLAG_NO_BVH_CULL | RT_FLAG_LINEAR_SCAN)) &&
+                         sh.bvh_depth < (uint32_t)TRAV_STACK && n_prims > 0;   // LDS stack: (depth + 1) KiB per workgroup
+    // (Small PILES of overlapping spheres keep the scan: at a box density of 3 and more a ray meets so many leaf boxes that up
+    // to about 200 spheres the scan's 64 packed instructions per 8 spheres beat any walk — tools/dense_matrix.py, 48 ... 192 spheres at
+    // density 3.3 ... 13: the culled LDS-tree walk of round 4 renders them at 0.67 ... 0.84 of the scan (the plain one: 0.59 ... 0.92), at
+    // 256 it leads by 1.4 ... 1.5 x.  Round 3's two further pile rules — up to 384 spheres at densities 5 ... 12 to the scan, larger or
+    // denser piles to the culled L2 walk although their tree fits LDS — are gone: the culled LDS-tree walk is the best engine in
+    // every cell of tools/dense_mid_matrix.py, by 13 ... 30 %.)
+    const bool dense_pile = sh.n_tri == 0 && n_prims <= DENSE_SCAN_MAX_PRIMS && sh.cull_density >= DENSE_SCAN_MIN_DENSITY;
+    const bool traverse = trav_ok && ((fl & RT_FLAG_BVH_TRAVERSE) || (n_prims >= TRAVERSE_MIN_PRIMS && !dense_pile));
+    // node format: from RT_QNODES_MIN_PRIMS primitives up the 32-byte quantised nodes (half the gather footprint, and an
+    // LDS plan that keeps five workgroups per CU whatever the tree's depth): +14 % on sparse fields of every size, +17...29 %
+    // on dense fields of 32 768+ spheres, within 2.5 % either way in between; below it the exact-node kernel's six
+    // waves per SIMD win on the headline scene (c3 +1.5 %).  tools/crossover_q.py, DESIGN.md 4.7
+    // (meshes keep the exact nodes: a quantised walk validates a triangle leaf by walking its box chain — two more gathers
+    // per improving hit — and lost 2...16 % on the generated terrains of 7 200 and 100 352 triangles, tools/heuristics_matrix.py)
+    // LDS-resident tree (engines 4 and 7): the exact 64-byte nodes of a small scene staged into LDS by one
+    // 1024-thread workgroup per CU, 16-bit references / stack / leaf lists.  RT_FLAG_NO_LDS_TREE forces the
+    // L2-gather kernel (A/B runs, tests).
+    bool ltree_fits = false;
+    const size_t lt_lane = ((size_t)MAXL_LTREE + (size_t)(rq.max_bounces + 1) + (size_t)(sh.bvh_depth + 2)) * sizeof(uint16_t);
+    if (traverse && kn.lds_tree != 0 && !(fl & RT_FLAG_NO_LDS_TREE) && sh.n_internal > 0 && n_prims <= 0x7fffu &&
+        ((size_t)sh.n_internal + 2) * LNODE_DW < 0x8000u) {
+        const size_t fixed = (((size_t)sh.n_internal + 2) * LNODE_DW + n_prims) * 4 + 16 + lt_lane * LTREE_BLOCK;   // + node DONE and the NaN field
+        ltree_fits = fixed <= LDS_LIMIT;
+    }
+    // (Below the threshold a DENSE sphere scene whose tree does not fit LDS also takes the quantised nodes, for the culled
+    // walk below: tools/cull_matrix_small.py, 2 000...3 500 overlapping spheres 1.55...1.95 x over the exact-node walk, fields of
+    // box density 1...2 0.87...0.98 — hence the higher bar of DENSE_MID_MIN_DENSITY here.)
+    // (round 4: piles whose tree FITS LDS no longer need a rule — the LDS-resident tree has its own culled walk, below)
+    const bool dense_mid = sh.cull_pays && !(fl & RT_FLAG_NO_CULL_WALK) && !ltree_fits && sh.cull_density >= DENSE_MID_MIN_DENSITY &&
+                           n_prims >= DENSE_MID_MIN_PRIMS;
+    // (... and so does a sphere FIELD between the LDS tree's limit and that threshold: at box densities of 0.15 and more the quantised
+    // walk leads the exact one by 17...24 % there — tools/qnodes_mid_matrix.py, 1200...4000 spheres; flat sheets of small spheres,
+    // 0.03...0.1, are the scenes the exact nodes win by up to 12 %, and clusters fail quant_ok)
+    const bool field_mid = !ltree_fits && sh.n_tri == 0 && n_prims < RT_QNODES_MIN_PRIMS && sh.cull_density >= FIELD_MID_MIN_DENSITY;
+    const bool qnodes = traverse && sh.quant_ok && !(fl & RT_FLAG_EXACT_NODES) &&
+                        ((fl & RT_FLAG_QUANT_NODES) || (n_prims >= RT_QNODES_MIN_PRIMS && sh.n_tri <= sh.n_sph) || dense_mid ||
+                         field_mid);
+    const bool ltree = ltree_fits && !qnodes;
+    // Culled walk (engine 5): the quantised walk nearer child first, subtrees beyond the running closest hit
+    // skipped.  Spheres only (the bound is derived from the sphere root test's error terms).
+    // Default where the host heuristic says it pays (cull_pays: DESIGN.md 4.7); RT_FLAG_CULL_WALK / RT_FLAG_NO_CULL_WALK
+    // force it on / off (A/B runs, tests), RT_CULL_WALK=0/1 likewise for a whole process.
+    const bool cull = qnodes && cull_wanted(fl, kn.cull_walk, sh.cull_pays) && sh.n_tri == 0 && std::isfinite(sh.r_slack);
+    // ... and over the exact nodes (engine 6): scenes with triangles — the bound of cull_bound_tri — wherever the exact-node
+    // L2 walk is the engine; default where the host heuristic says it pays (xcull_pays), forced by the same flags
+    const bool xcull = traverse && !qnodes && !ltree && cull_wanted(fl, kn.cull_walk, sh.xcull_pays) && sh.n_tri > 0 && sh.tri_ok &&
+                       std::isfinite(sh.r_slack) && !sh.inverted_boxes;
+    // ... and in the LDS-resident tree (engine 7; round 4): the same bound, so the same premises (a finite slack
+    // radius, triangles within the K limit or in the `big` list, no inverted boxes); default from a box density of LT_CULL_MIN_DENSITY
+    // up — below it the rays meet so few leaf boxes that ordering the children costs more than the skipped subtrees save
+    // (tools/dense_matrix.py, tools/dense_mid_matrix.py, tests/test_gpu_engine_rules.py)
+    const bool lt_cull_ok = ltree && !sh.inverted_boxes && std::isfinite(sh.r_slack) && (sh.n_tri == 0 || sh.tri_ok);
+    const bool ltcull = lt_cull_ok && cull_wanted(fl, kn.cull_walk, sh.cull_density >= LT_CULL_MIN_DENSITY);
+    const bool streamed = !traverse && sh.n_sph_pad > RESIDENT_MAX;
+    pl.engine = traverse ? (ltree ? (ltcull ? 7 : 4) : qnodes ? (cull ? 5 : 3) : xcull ? 6 : 2) : (streamed ? 1 : 0);
+    const int bs = ENGINES[pl.engine].block;
+    p.chunk = traverse ? 0 : (streamed ? STREAM_CHUNK : sh.n_sph_pad);
+    p.n_chunks = p.chunk ? (sh.n_sph_pad + p.chunk - 1) / p.chunk : 0;
+    p.path32 = (sh.n_sph + sh.n_tri) > 65536u ? 1u : 0u;
+    size_t geom_bytes = traverse ? 0 : (size_t)(p.chunk ? p.chunk : 1) * 4 * sizeof(float);   // float4 records
+    p.lds_cand_off = (uint32_t)geom_bytes;
+    size_t path_bytes = (size_t)p.depth * BLOCK * (p.path32 ? 4 : 2);
+    // ---- LDS plan of a traversal launch.  Occupancy is worth more than long leaf lists (c3: 6 workgroups per CU with
+    // 7 slots +1.5 % over 5 with 8; c5: 5 with 5 slots +7.5 % over 4 with 8), and an uncapped stack more than either
+    // (the HBM-overflow test on every push / pop costs 6...10 %).  So: the target number of workgroups per CU follows
+    // from the kernel's registers (five waves per SIMD for both node formats).  The exact-node kernel has 7 slots, fixed; the quantised
+    // kernel's lists shrink from MAXL down to MINL slots to reach its target, and a quantised walk whose whole stack still
+    // does not fit takes the capped-stack kernel.
+    // stack slots per lane: up to bvh_depth pending right children (+ 1 spare); the LDS-tree kernel's branch-free step
+    // adds the DONE sentinel in slot 0 and needs the free slot its unconditional stores land in
+    // output staging (one tile per wave): wherever the LDS plan has room for it
+    const bool want_stage = kn.no_stage == 0 && ((traverse && !ltree) || streamed);     // the kernels it is compiled into (see there)
+    const bool list16 = traverse && !ltree && n_prims <= 65536u;          // 16-bit leaf-list entries: half the LDS
+    const size_t stage_bytes_wg = (size_t)STAGE_TILES * STAGE_TILE_BYTES * (bs / 64);
+    const uint32_t stack_capped = sh.bvh_depth + 1;
+    const uint32_t stack_need = sh.bvh_depth + (ltree ? 2u : 1u);
+    uint32_t maxl = qnodes ? (uint32_t)MAXL : (uint32_t)MAXL_EXACT, stack_lds = stack_need;
+    if (traverse && qnodes) {
+        const size_t per_wg = (160u * 1024u - 4096u) / 5u - 512u;     // 4 KiB of slack, 464 B static LDS
+        const size_t slot = (size_t)BLOCK * (list16 ? sizeof(uint16_t) : sizeof(uint32_t));
+        const size_t fixed = path_bytes + (size_t)stack_need * BLOCK * sizeof(uint32_t) + (want_stage ? stage_bytes_wg : 0);
+        // (force_capped / stack_lds: tests drive the capped-stack kernel with small trees)
+        if (kn.force_capped == 0 && fixed + (size_t)MINL * slot <= per_wg) {
+            maxl = (uint32_t)std::min<size_t>((size_t)MAXL, (per_wg - fixed) / slot);
+        } else {
+            const uint32_t cap = kn.stack_lds > 0 ? (uint32_t)kn.stack_lds : STACK_LDS_MAX;
+            pl.capped = stack_capped > cap;
+            stack_lds = pl.capped ? cap : stack_need;
+        }
+    }
+    p.maxl = maxl;
+    p.stack_lds = stack_lds;
+    p.list16 = list16 ? 1u : 0u;
+    size_t cand_bytes = traverse ? (size_t)maxl * BLOCK * (list16 ? sizeof(uint16_t) : sizeof(uint32_t))
+                                 : (size_t)MAXC * BLOCK * sizeof(uint16_t);
+    p.lds_path_off = (uint32_t)(geom_bytes + cand_bytes);
+    const bool expanded = !traverse && sh.expanded && !(fl & RT_FLAG_OC_BROAD_PHASE);
+    p.lds_rr_off = (uint32_t)(geom_bytes + cand_bytes + path_bytes);
+    size_t rr_bytes = expanded ? (size_t)(p.chunk ? p.chunk : 1) * sizeof(float) : 0;
+    p.lds_stack_off = (uint32_t)(geom_bytes + cand_bytes + path_bytes + rr_bytes);
+    size_t stack_bytes = traverse ? (size_t)stack_lds * BLOCK * sizeof(uint32_t) : 0;
+    size_t lds = geom_bytes + cand_bytes + path_bytes + rr_bytes + stack_bytes;
+    p.n_internal = sh.n_internal;
+    p.lds_node_off = 0;
+    if (ltree) {
+        // [nodes][leaf lists u16][path u16][stack u16]
+        size_t off = ((((size_t)sh.n_internal + 2) * LNODE_DW + n_prims) * 4 + 15) & ~(size_t)15;    // nodes, DONE, NaN field of n_prims + 19 dwords
+        p.lds_cand_off = (uint32_t)off;
+        // leaf-list slots: MAXL_LTREE, and up to MAXL_LTREE_MAX where the tree leaves room (fewer flushes forced by a full list)
+        uint32_t lt_maxl = MAXL_LTREE;
+        while (lt_maxl < (uint32_t)MAXL_LTREE_MAX &&
+               off + ((size_t)(lt_maxl + 1) + p.depth + stack_need) * bs * sizeof(uint16_t) <= LDS_LIMIT) lt_maxl++;
+        p.maxl = lt_maxl;
+        off += (size_t)lt_maxl * bs * sizeof(uint16_t);
+        p.lds_path_off = (uint32_t)off;
+        off += (size_t)p.depth * bs * sizeof(uint16_t);
+        p.lds_stack_off = (uint32_t)off;
+        off += (size_t)stack_need * bs * sizeof(uint16_t);
+        lds = off;
+    }
+    // compacted root tests of the exact-node L2 kernel (1 KiB per wave; RT_COMPACT=0 keeps the per-lane flush for A/B runs)
+    p.lds_cmp_off = 0xffffffffu;
+    if (traverse && !qnodes && !ltree && kn.compact != 0 && lds + 1024u * (BLOCK / 64) + 16 <= LDS_LIMIT) {
+        lds = (lds + 15) & ~(size_t)15;
+        p.lds_cmp_off = (uint32_t)lds;
+        lds += 1024u * (BLOCK / 64);
+    }
+    p.lds_stage_off = 0xffffffffu;
+    if (want_stage && lds + stage_bytes_wg <= LDS_LIMIT) {
+        lds = (lds + 15) & ~(size_t)15;
+        p.lds_stage_off = (uint32_t)lds;
+        lds += stage_bytes_wg;
+    }
+    pl.lds = lds;
+    if (lds > LDS_LIMIT) {
+        pl.status = RT_ERR_LIMIT;
+        pl.error = "LDS budget exceeded (scene chunk + path stack)";
+        return pl;
+    }
+    pl.isect = pl.capped ? ENGINES[pl.engine].isect_capped : ENGINES[pl.engine].isect;
+    pl.block = bs;
+    pl.expanded = expanded;
+    pl.count_steps = traverse && (fl & RT_FLAG_COUNT_STEPS);
+    pl.maxl_l2 = maxl;
+    pl.ovf_entries = pl.capped ? stack_capped - stack_lds : 0u;
+    fill_camera(rq, p);
+    p.t_min = rq.t_min;
+    p.t_max = rq.t_max;
+    p.spp_f = (float)s_end;
+    p.spp_rcp = (s_end & (s_end - 1u)) == 0u ? 1.0f / (float)s_end : 0.0f;         // a power of two up to 2^31: exact in f32
+    p.root_ref = sh.root_ref;
+    if (ltree) p.root_ref = (p.root_ref & LEAF_BIT) ? (0x8000u | (p.root_ref & 0x7fffu)) : lt_r0(sh.n_internal) + p.root_ref * (uint32_t)LNODE_DW;
+    // refill threshold: long walks (large scenes) want finished lanes replaced sooner, short walks amortise the
+    // per-round shading / ray-generation code over more finished lanes (tools/variants_q.sh sweeps)
+    p.refill_eighths = kn.refill_eighths > 0 ? (uint32_t)kn.refill_eighths : (n_prims >= RT_QNODES_MIN_PRIMS ? 4u : 2u);
+    p.n_strips = n_strips;
+    // Tile shape: 64x1 keeps each tile on whole 64-byte lines of the RGB8 strip (64 px * 3 B = 3 lines),
+    // so one CU / one XCD L2 writes every byte of a line; 8x8 tiles split lines across XCDs and doubled the
+    // HBM write traffic (profiles/r01_*).
+    p.tiles_x = (p.W + 63u) / 64u;
+    p.tiles_per_strip = p.tiles_x * p.Hs;
+    // Sample units (rt_kernel.hip.h): pixel slots per wave, the commit threshold, the division by the units per pixel
+    {
+        p.grp = p.upp >= 8u ? 1u : (8u + p.upp - 1u) / p.upp;            // a slot is at least 8 units
+        const uint64_t slot_units = (uint64_t)p.grp * p.upp;
+        p.grp_magic = p.grp > 1u ? (uint32_t)((1ull << 32) / p.grp) + 1u : 0u;
+        p.slot_stride = 1u + (uint32_t)slot_units;
+        // enough slots for the pixels in flight (64 lanes' units, each pixel open as long as its longest path) plus the complete
+        // ones a commit waits for.  The price of every slot is scratch that L2 has to keep between a sample's store and its pixel's
+        // commit; what L2 does not keep goes out to HBM (c3, WRITE_SIZE per 23.7 MiB frame / Mrays/s: 32 slots 135 / 15 580, 24 slots
+        // 88 / 15 330, 20 slots 40 / 15 270, 16 slots 33 / 14 300; c4 at 12 / 16 / 24 slots: 15 615 / 16 070 / 16 220 Mrays/s).  The
+        // rate is what this path is measured by, HBM is idle either way (c3: 20 GB/s of 8 TB/s): 384 units per wave, at most 32 slots
+        // — but never fewer than 16 pixels open while a pixel is at most 256 units: a slot is free again only when its LAST sample is in,
+        // and with the 4 slots the 384 units gave the reference's literal 100 samples per pixel a wave stood still for want of a slot
+        // (the mesh at 100 spp: 4 / 8 / 16 / 32 slots 6 990 / 7 250 / 7 340 / 7 370 Mrays/s); 8 up to 1 024 units, 4 beyond (scratch:
+        // 12 bytes per unit and slot for every wave of the grid)
+        const uint64_t fewest = slot_units <= 256u ? 16u : slot_units <= 1024u ? 8u : 4u;
+        p.n_slots = kn.slots > 0 ? std::min<uint32_t>((uint32_t)kn.slots, SLOTS_MAX)
+                                 : (uint32_t)std::min<uint64_t>(SLOTS_MAX, std::max<uint64_t>(fewest, 384u / slot_units));
+        const uint32_t cs = kn.commit_slots > 0 ? (uint32_t)kn.commit_slots : std::max<uint32_t>(1u, p.n_slots / 4u);     // (c3: 4 ... 20 of 32 within 1 %)
+        p.commit_slots = std::min<uint32_t>(cs, p.n_slots);
+        // q / d == mulhi(q, floor(2^32 / d) + 1) whenever q * d < 2^32: q < 65 * upp with upp <= RT_MAX_SPP (4096)
+        p.spp_magic = p.upp > 1u ? (uint32_t)((1ull << 32) / p.upp) + 1u : 0u;
+        p.slotu_magic = (uint32_t)((1ull << 32) / slot_units) + 1u;
+    }
+    const uint64_t n_tiles = (uint64_t)p.tiles_per_strip * n_strips;
+    if (n_tiles > 0x1fffffffull) {
+        pl.status = RT_ERR_LIMIT;
+        pl.error = "too many tiles in one launch";
+        return pl;
+    }
+    p.tiles_total = (uint32_t)n_tiles;
+    p.n_tiles = (uint32_t)n_tiles;             // (queue entries: the split into whole tiles and parts follows the grid, plan_queue)
+    p.tiles_big = (uint32_t)n_tiles;
+    return pl;
+}
+
+// The persistent grid of the launch — `blocks` workgroups as the chip holds them at the plan's LDS / register budget, fewer when the
+// launch has fewer tiles than waves — its queue entries and the sizes of its scratch.
+template <class KP>
+void plan_queue(Plan& pl, uint32_t blocks, const Knobs& kn, KP& p) {
+    const uint32_t waves_per_wg = (uint32_t)pl.block / 64u;
+    const uint32_t useful = (p.n_tiles + waves_per_wg - 1) / waves_per_wg;   // a wave needs at least one tile
+    if (blocks > useful) blocks = useful ? useful : 1;
+    pl.blocks = blocks;
+    // Queue entries.  Whole tiles (64 pixels x spp units) first, and the LAST ones — two tiles per wave of the grid — in parts: quarters
+    // (16 pixels), so that the launch's tail is one short entry long.  Two cases take parts for EVERY tile (round 4, measured on the
+    // 100 352-triangle mesh: 1080p / 4 spp +13 %, 100 spp +19 %): a launch with fewer than 16 tiles per wave — its expensive tiles
+    // (handed out first: the bottom rows) are still being worked on when the cheap ones at the end of the queue have long run out, and
+    // an expensive whole tile is a large share of such a launch — and more than 16 samples per pixel, where a whole tile is thousands of
+    // units; from 33 samples per pixel up the parts are sixteenths (4 pixels).  The price where it is not needed: 1-2 % (c2, c4).
+    const uint64_t waves = (uint64_t)blocks * waves_per_wg;
+    const bool all_parts = p.tiles_total < 16ull * waves || p.upp > 16u;
+    const uint64_t conv = std::min<uint64_t>(p.tiles_total, kn.tail_tiles >= 0 ? (uint64_t)kn.tail_tiles : all_parts ? (uint64_t)p.tiles_total : 2ull * waves);
+    p.sub_shift = p.upp > 32u ? 4u : 2u;
+    if ((((uint64_t)p.tiles_total - conv) + (conv << p.sub_shift)) > 0x7fffffffull) p.sub_shift = 2u;       // (entry numbers are 31 bits)
+    p.tiles_big = p.tiles_total - (uint32_t)conv;
+    p.n_tiles = p.tiles_big + ((uint32_t)conv << p.sub_shift);
+    p.ovf_stride = blocks * (uint32_t)pl.block;
+    pl.ovf_words = (size_t)pl.ovf_entries * p.ovf_stride;
+    pl.ring_bytes = (size_t)blocks * waves_per_wg * p.n_slots * p.slot_stride * 12u;
+}
+
+}  // namespace rtplan

@@ -1,4 +1,4 @@
-"""The host's engine rules (rt_api.hip launch_batch: which of the seven closest-hit engines renders a scene) on scenes they were NOT
+"""The host's engine rules (csrc/rt_plan.h plan_launch, CPU test tests/test_launch_plan.py: which of the seven closest-hit engines renders a scene) on scenes they were NOT
 tuned on.  Round-3 verdict: the density / size constants were fitted to the generators of tools/*_matrix.py and validated on the same
 generators.  All engines give the same bits (the parity tests), so a wrong rule costs time, never correctness; this test prices it:
 every applicable engine is forced on 26 scenes from other generators and seeds (tests/_rule_scenes.py), five timed launches each,

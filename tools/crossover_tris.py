@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Linear scan vs BVH traversal on triangle meshes of growing size (the constant TRAVERSE_MIN_TRIS in rt_api.hip)."""
+"""Linear scan vs BVH traversal on triangle meshes of growing size (the former constant TRAVERSE_MIN_TRIS: now every mesh of two triangles and more is walked, csrc/rt_plan.h)."""
 import sys
 sys.path.insert(0, ".")
 import numpy as np
