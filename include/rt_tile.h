@@ -42,7 +42,9 @@ extern "C" {
                                   4: the deterministic RNG is one stream per (pixel, SAMPLE) (see `seed` below: same seed,
                                      other images than ABI 3); RT_MAX_SPP; rt_hip_runtime_path(); the frame context assigns
                                      strips by measured cost and reports the balance (rt_frame_stats.balance_*,
-                                     RT_FLAG_FRAME_STATIC) */
+                                     RT_FLAG_FRAME_STATIC)
+                                  (4, additions only: ray queries rt_scene_intersect / rt_scene_intersect_device with
+                                     rt_ray, rt_hit, RT_HIT_NONE, RT_QUERY_*; every earlier type and entry point unchanged) */
 
 /* ---- status codes --------------------------------------------------------------- */
 typedef enum rt_status {
@@ -318,6 +320,51 @@ RT_API int rt_scene_render_tiles_pass_device(rt_scene* scene, const rt_tile_requ
 /* Wait for all work enqueued on the scene, return accumulated counters / event time
  * since the previous collect, and reset them. */
 RT_API int rt_scene_collect(rt_scene* scene, rt_tile_stats* stats);
+
+/* ---- ray queries: closest hit and occlusion for the caller's rays ----------------- */
+/* What `WorldRefList::intersect` (ray-tracer-slave/src/shapes/mod.rs:158-191) returns for one ray after `BVH::traverse`
+ * (bvh_impl.rs:373-398) has picked its candidates, for a batch of rays on a resident scene: picking, shadow and visibility
+ * rays, collision probes, an integrator of the caller's own on this BVH and these root tests.
+ *
+ *   - Ray i is Ray::new(origin, direction) (B/ray.rs:133-143): the direction is normalised by DIVISION by its length, so a
+ *     zero or non-finite direction gives NaN components (and no hit).  A root counts when it lies in the ray's own half-open
+ *     window [t_min, t_max) (shapes/mod.rs:106-129); t_min >= t_max admits nothing, t_max may be +inf.
+ *   - RT_QUERY_CLOSEST: the primitive WorldRefList::intersect picks, with its tie rule (min_by keeps the FIRST minimum of
+ *     |P - origin| over the traversal's candidates, i.e. the earlier depth-first leaf; under RT_FLAG_NO_BVH_CULL the earlier
+ *     position in the world).
+ *       index     the primitive's position in RenderInfo.world: world_index[i] of the scene's rt_scene_create when one was
+ *                 given, else the spheres (0 .. n_spheres - 1) followed by the triangles;
+ *       p*        the hit point o + t d (Ray::at, ray.rs:147-149);
+ *       distance  length(P - o), the value the reference compares (shapes/mod.rs:177-182);
+ *       n*        the normal the reference computes: normalize_or_zero(P - centre) for a sphere (sphere.rs:49-51),
+ *                 normalize_or_zero((a - b) x (a - c)) for a triangle (mesh.rs:163-165).
+ *     A miss: index = RT_HIT_NONE, distance = +inf, every other field 0.
+ *   - RT_QUERY_ANY (occlusion): index != RT_HIT_NONE exactly when the closest query would hit; the walk may stop at the first
+ *     admitted hit, so the index is that of SOME admitted primitive and the other fields are unspecified.
+ *   - flags: the RT_FLAG_* bits of the tile entry points, same meaning.  Default: BVH semantics (a hit counts only if
+ *     BVH::traverse would return the primitive), walked over the exact nodes.  RT_FLAG_NO_BVH_CULL: plain scan in world order.
+ *     RT_FLAG_EXACT_SCAN / RT_FLAG_LINEAR_SCAN: BVH semantics by a scan of every primitive with per-hit validation.
+ *     RT_FLAG_FULL_CHAIN: the crate's literal slab test throughout.  RT_FLAG_BVH_TRAVERSE, RT_FLAG_NO_LDS_TREE: the walk (the
+ *     default).  Flags naming an engine the query path does not have (RT_FLAG_QUANT_NODES, RT_FLAG_EXACT_NODES,
+ *     RT_FLAG_CULL_WALK, RT_FLAG_NO_CULL_WALK, RT_FLAG_COUNT_STEPS, RT_FLAG_OC_BROAD_PHASE, the RT_FLAG_FRAME_* bits) are
+ *     accepted and ignored: every engine gives the same hits.
+ *   - RT_ERR_BAD_ARG, and nothing launched: a NULL scene, rays or hits pointer, n == 0, mode > RT_QUERY_ANY.
+ *   - Counters (rt_tile_stats): primary_rays = ray_segments = n; broad_candidates = exact root tests run; kernel_ms; h2d_ms
+ *     (the rays) and d2h_ms (the hits) of the host form; n_launches; engine = the engine that ran (numbered as
+ *     rt_tile_stats.engine: 1 the scan, 2 the exact-node walk).
+ *  */
+typedef struct rt_ray { float ox, oy, oz, t_min; float dx, dy, dz, t_max; } rt_ray;          /* 32 bytes */
+typedef struct rt_hit { float px, py, pz, distance; float nx, ny, nz; uint32_t index; } rt_hit; /* 32 bytes */
+#define RT_HIT_NONE 0xffffffffu
+enum { RT_QUERY_CLOSEST = 0u, RT_QUERY_ANY = 1u };
+
+/* Host buffers (n rays in, n hits out), synchronous; stats may be NULL. */
+RT_API int rt_scene_intersect(rt_scene* scene, const rt_ray* rays, uint32_t n, uint32_t mode, uint32_t flags,
+                              rt_hit* hits, rt_tile_stats* stats);
+/* Device buffers (n rt_ray, n rt_hit), asynchronous on hip_stream (NULL = the scene's stream); counters and event times
+ * accumulate in the scene until rt_scene_collect(). */
+RT_API int rt_scene_intersect_device(rt_scene* scene, const void* d_rays, uint32_t n, uint32_t mode, uint32_t flags,
+                                     void* d_hits, void* hip_stream);
 
 /* ---- whole frame: replaces controller dispatch + assembly ----------------------- */
 /* (controller main.rs:47-75 `for division_no in 0..divisions` and :109-115 stitch.)

@@ -93,9 +93,29 @@ class FrameStats(C.Structure):
     ]
 
 
+class Ray(C.Structure):
+    """rt_ray: origin and window start, direction (normalised by the library, Ray::new) and window end [t_min, t_max)."""
+    _fields_ = [("ox", C.c_float), ("oy", C.c_float), ("oz", C.c_float), ("t_min", C.c_float),
+                ("dx", C.c_float), ("dy", C.c_float), ("dz", C.c_float), ("t_max", C.c_float)]
+
+
+class Hit(C.Structure):
+    """rt_hit: hit point, |P - o|, the reference's normal, the primitive's position in the world (RT_HIT_NONE: a miss)."""
+    _fields_ = [("px", C.c_float), ("py", C.c_float), ("pz", C.c_float), ("distance", C.c_float),
+                ("nx", C.c_float), ("ny", C.c_float), ("nz", C.c_float), ("index", C.c_uint32)]
+
+
+RT_HIT_NONE = 0xFFFFFFFF
+RT_QUERY_CLOSEST = 0
+RT_QUERY_ANY = 1
+# numpy twins of rt_ray / rt_hit (arrays of them are what Scene.intersect passes and returns)
+RAY_DTYPE = np.dtype([(n, "<f4") for n, _ in Ray._fields_])
+HIT_DTYPE = np.dtype([(n, "<u4" if n == "index" else "<f4") for n, _ in Hit._fields_])
+
 assert C.sizeof(TileRequest) == 64
 assert C.sizeof(TileStats) == 64
 assert C.sizeof(FrameStats) == 232
+assert C.sizeof(Ray) == C.sizeof(Hit) == RAY_DTYPE.itemsize == HIT_DTYPE.itemsize == 32
 
 
 def default_request(**kw) -> TileRequest:
@@ -215,6 +235,10 @@ def _bind(path: Path) -> C.CDLL:
     lib.rt_scene_render_tiles_pass_device.restype = C.c_int
     lib.rt_scene_collect.argtypes = [vp, C.POINTER(TileStats)]
     lib.rt_scene_collect.restype = C.c_int
+    lib.rt_scene_intersect.argtypes = [vp, C.POINTER(Ray), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Hit), C.POINTER(TileStats)]
+    lib.rt_scene_intersect.restype = C.c_int
+    lib.rt_scene_intersect_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
+    lib.rt_scene_intersect_device.restype = C.c_int
     lib.rt_render_frame.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(TileRequest), vp, C.c_uint32,
                                     vp, C.c_uint32, vp, vp, C.c_size_t, C.POINTER(TileStats)]
     lib.rt_render_frame.restype = C.c_int

@@ -37,16 +37,17 @@ HIPCC_FLAGS = [
 
 
 # translation units and the flags each one adds: the host side, the linear-scan kernels, the traversal kernels
-# (SLP-vectorised packed FP32 pairs: linear kernels +3 %, traversal kernels -1.5 %, tools/variants_all.sh)
+# (SLP-vectorised packed FP32 pairs: linear kernels +3 %, traversal kernels -1.5 %, tools/variants_all.sh), the ray-query kernels
 UNITS = [
     ("rt_api.hip", []),
     ("rt_kernels_lin.hip", []),
     ("rt_kernels_trav.hip", ["-fno-slp-vectorize"]),
+    ("rt_kernels_query.hip", ["-fno-slp-vectorize"]),
 ]
 
 
 def _deps() -> list[Path]:
-    return [CSRC / u for u, _ in UNITS] + [CSRC / "rt_kernel.hip.h", CSRC / "rt_consts.h", CSRC / "rt_plan.h", CSRC / "rt_cull.h", CSRC / "rt_bvh.h",
+    return [CSRC / u for u, _ in UNITS] + [CSRC / "rt_kernel.hip.h", CSRC / "rt_query.hip.h", CSRC / "rt_consts.h", CSRC / "rt_plan.h", CSRC / "rt_cull.h", CSRC / "rt_bvh.h",
                                             CSRC / "rt_assign.h", ROOT / "include" / "rt_tile.h",
                                             Path(__file__)]
 
@@ -104,7 +105,7 @@ def _compile(lib_path: Path, flags_path: Path, obj_dir: Path, extra: list[str], 
         objs.append(str(obj))
         cmds.append([hipcc, *common, *flags, "-c", str(CSRC / unit), "-o", str(obj)])
     cmds.append([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(lib_path), *objs])
-    # the three compiles are independent: run them side by side, then link
+    # the compiles are independent: run them side by side, then link
     procs = []
     for cmd in cmds[:-1]:
         if verbose:

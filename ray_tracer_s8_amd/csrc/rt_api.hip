@@ -27,6 +27,7 @@
 #include "rt_bvh.h"
 #include "rt_kernel.hip.h"
 #include "rt_plan.h"
+#include "rt_query.hip.h"
 #include "rt_tile.h"
 
 namespace {
@@ -191,6 +192,9 @@ struct rt_scene {
     size_t d_outf_cap = 0;
     float* d_acc = nullptr;             // ... and for the running sums of rt_scene_render_tile_pass
     size_t d_acc_cap = 0;
+    void* d_rays = nullptr;             // ... and for the rays and hits of rt_scene_intersect
+    void* d_hits = nullptr;
+    size_t d_query_cap = 0;             //   rays (= hits) each buffer holds
     // HIP-event bookkeeping of launches not yet collected
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, free_ev;
     uint64_t primary_rays = 0;
@@ -1013,6 +1017,8 @@ static int rt_scene_destroy_impl(rt_scene* sc) {
     (void)hipFree(sc->d_out);
     (void)hipFree(sc->d_outf);
     (void)hipFree(sc->d_acc);
+    (void)hipFree(sc->d_rays);
+    (void)hipFree(sc->d_hits);
     (void)hipFree(sc->d_cost);
     delete sc;
     g_live_scenes.fetch_sub(1);
@@ -1252,6 +1258,129 @@ static int rt_scene_render_tiles_pass_device_impl(rt_scene* sc, const rt_tile_re
                                                   void* const* d_out_f32, void* hip_stream) {
     const Pass pass = {begin, end, d_accum};
     return rt_scene_render_tiles_device_impl(sc, rqs, n, d_out_rgb, out_len_each, d_out_f32, hip_stream, &pass);
+}
+
+// ---- ray queries (rt_tile.h "ray queries", rt_query.hip.h) ---------------------------------------------------------------------
+static int check_query(rt_scene* sc, const void* rays, uint32_t n, uint32_t mode, const void* hits) {
+    if (!sc) return fail(RT_ERR_BAD_ARG, "scene is NULL");
+    if (!rays || !hits) return fail(RT_ERR_BAD_ARG, "rays or hits is NULL");
+    if (n == 0) return fail(RT_ERR_BAD_ARG, "n == 0");
+    if (mode > RT_QUERY_ANY) return fail(RT_ERR_BAD_ARG, "mode is neither RT_QUERY_CLOSEST nor RT_QUERY_ANY");
+    return RT_OK;
+}
+
+// Enqueue one query launch on `stream` (caller holds sc->mu, device current): persistent waves over the n rays.
+static int launch_query(rt_scene* sc, const void* d_rays, uint32_t n, uint32_t mode, uint32_t flags, void* d_hits, hipStream_t stream) {
+    const rtplan::SceneShape& sh = sc->shape;
+    const rtplan::QueryPlan qp = rtplan::plan_query(sh, flags);
+    const rtk::QueryFn kern = rtk::query_kernel(qp.engine, qp.scan_mode, mode == RT_QUERY_ANY);
+    if (!kern) return fail(RT_ERR_HIP, "no query kernel for this plan");
+    rtk::QParams p;
+    std::memset(&p, 0, sizeof p);
+    p.rays = (const float4*)d_rays;
+    p.hits = (uint4*)d_hits;
+    p.n = n;
+    p.n_sph = sh.n_sph;
+    p.n_tri = sh.n_tri;
+    p.root_ref = sh.root_ref;
+    p.full_chain = qp.full_chain ? 1u : 0u;
+    p.trav = sc->d_trav;
+    p.bvh_nodes = sc->d_bvh;
+    p.leaf_of = sc->d_leaf_of;
+    p.world_rank = sc->has_order ? sc->d_world_rank : nullptr;
+    p.geom_r = sc->d_geom_r;
+    p.tri = sc->d_tri;
+    p.counters = sc->d_counters;
+    if (sc->pending.size() >= QUEUE_SLOTS) return fail(RT_ERR_LIMIT, "too many uncollected launches: call rt_scene_collect()");
+    int per_cu = 0;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, rtplan::QUERY_BLOCK, qp.lds));
+    if (per_cu < 1) per_cu = 1;
+    const uint64_t useful = ((uint64_t)n + rtplan::QUERY_BLOCK - 1) / rtplan::QUERY_BLOCK;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(useful, (uint64_t)sc->ctx->n_cu * (uint32_t)per_cu);
+    if (dbg(DBG_VERBOSE))
+        fprintf(stderr, "[rt] query: engine %d  scan mode %d  %s  lds %zu B  workgroups/CU %d  rays %u\n", qp.engine, qp.scan_mode,
+                mode == RT_QUERY_ANY ? "any" : "closest", qp.lds, per_cu, n);
+    EvPair ev;
+    int rc = get_events(sc, ev);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(ev.a, stream));
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(rtplan::QUERY_BLOCK), qp.lds, stream, p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev.b, stream));
+    sc->pending.push_back({ev.a, ev.b});
+    sc->primary_rays += n;
+    sc->last_engine = (uint32_t)qp.engine;
+    sc->last_form = 0;
+    return RT_OK;
+}
+
+static int rt_scene_intersect_device_impl(rt_scene* sc, const void* d_rays, uint32_t n, uint32_t mode, uint32_t flags, void* d_hits,
+                                          void* hip_stream) {
+    int rc = check_query(sc, d_rays, n, mode, d_hits);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    HIPCHK(hipSetDevice(sc->ctx->dev));
+    return launch_query(sc, d_rays, n, mode, flags, d_hits, hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream);
+}
+
+static int rt_scene_intersect_impl(rt_scene* sc, const rt_ray* rays, uint32_t n, uint32_t mode, uint32_t flags, rt_hit* hits,
+                                   rt_tile_stats* stats) {
+    int rc = check_query(sc, rays, n, mode, hits);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> dl(sc->ctx->mu);
+    std::lock_guard<std::mutex> lk(sc->mu);
+    HIPCHK(hipSetDevice(sc->ctx->dev));
+    hipStream_t st = sc->ctx->stream;
+    const size_t bytes = (size_t)n * sizeof(rt_ray);
+    if (sc->d_query_cap < n) {
+        (void)hipFree(sc->d_rays);
+        (void)hipFree(sc->d_hits);
+        sc->d_rays = sc->d_hits = nullptr;
+        sc->d_query_cap = 0;
+        if (hipMalloc(&sc->d_rays, bytes) != hipSuccess || hipMalloc(&sc->d_hits, n * sizeof(rt_hit)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(RT_ERR_OOM, "hipMalloc(rays / hits) failed");
+        }
+        sc->d_query_cap = n;
+    }
+    // settle anything enqueued earlier so the stats of this call are its own (the scene's upload time stays for the next tile call)
+    rt_tile_stats prev;
+    rc = collect_locked(sc, &prev);
+    if (rc) return rc;
+    EvPair up, down;
+    if ((rc = get_events(sc, up)) || (rc = get_events(sc, down))) return rc;
+    struct EvReturn {
+        rt_scene* sc;
+        EvPair a, b;
+        hipStream_t st;
+        bool ok = false;
+        ~EvReturn() {
+            if (!ok) (void)hipStreamSynchronize(st);       // (an error return waits for what already writes into caller memory)
+            sc->free_ev.push_back({a.a, a.b});
+            sc->free_ev.push_back({b.a, b.b});
+        }
+    } ev_return{sc, up, down, st};
+    HIPCHK(hipEventRecord(up.a, st));
+    HIPCHK(hipMemcpyAsync(sc->d_rays, rays, bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(up.b, st));
+    rc = launch_query(sc, sc->d_rays, n, mode, flags, sc->d_hits, st);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(down.a, st));
+    HIPCHK(hipMemcpyAsync(hits, sc->d_hits, n * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(down.b, st));
+    HIPCHK(hipEventSynchronize(down.b));
+    ev_return.ok = true;
+    float h2d = 0.f, d2h = 0.f;
+    HIPCHK(hipEventElapsedTime(&h2d, up.a, up.b));
+    HIPCHK(hipEventElapsedTime(&d2h, down.a, down.b));
+    rt_tile_stats s;
+    rc = collect_locked(sc, &s);
+    if (rc) return rc;
+    sc->h2d_ms = prev.h2d_ms;
+    s.h2d_ms = h2d;
+    s.d2h_ms = d2h;
+    if (stats) *stats = s;
+    return RT_OK;
 }
 
 // ---- Test / tool hooks.  NOT part of rt_tile.h and NOT in the product library: compiled only with -DRT_DEBUG_HOOKS, which
@@ -1817,6 +1946,14 @@ RT_API int rt_scene_render_tile_device(rt_scene* sc, const rt_tile_request* rq, 
     return guarded([&] { return rt_scene_render_tile_device_impl(sc, rq, d_out_rgb, out_len, d_out_f32, hip_stream); });
 }
 RT_API int rt_scene_collect(rt_scene* sc, rt_tile_stats* st) { return guarded([&] { return rt_scene_collect_impl(sc, st); }); }
+RT_API int rt_scene_intersect(rt_scene* sc, const rt_ray* rays, uint32_t n, uint32_t mode, uint32_t flags, rt_hit* hits,
+                              rt_tile_stats* stats) {
+    return guarded([&] { return rt_scene_intersect_impl(sc, rays, n, mode, flags, hits, stats); });
+}
+RT_API int rt_scene_intersect_device(rt_scene* sc, const void* d_rays, uint32_t n, uint32_t mode, uint32_t flags, void* d_hits,
+                                     void* hip_stream) {
+    return guarded([&] { return rt_scene_intersect_device_impl(sc, d_rays, n, mode, flags, d_hits, hip_stream); });
+}
 RT_API int rt_scene_render_tiles(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint8_t* const* out_rgb,
                                  size_t out_len_each, float* const* out_f32, rt_tile_stats* stats) {
     return guarded([&] { return rt_scene_render_tiles_impl(sc, rqs, n, out_rgb, out_len_each, out_f32, stats); });

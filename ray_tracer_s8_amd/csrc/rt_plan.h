@@ -392,4 +392,33 @@ void plan_queue(Plan& pl, uint32_t blocks, const Knobs& kn, KP& p) {
     pl.ring_bytes = (size_t)blocks * waves_per_wg * p.n_slots * p.slot_stride * 12u;
 }
 
+// ---- Ray queries (rt_scene_intersect*, rt_query.hip.h).  One lane per caller ray, no sample units: the plan is the
+// engine, the semantics of its scan and the slab test — a pure function of the scene's shape and the request flags.
+constexpr int QUERY_BLOCK = 256;   // workgroup size of the query kernels
+
+struct QueryPlan {
+    int engine = 2;           // rt_tile_stats.engine: 2 the exact-node walk, 1 the scan in primitive order
+    int scan_mode = 2;        // engine 1: rtk::consider MODE — 0 plain world order (RT_FLAG_NO_BVH_CULL), 2 BVH semantics, every
+                              //   improving hit validated at once
+    bool full_chain = false;  // the crate's literal slab test and the whole box chain (RT_FLAG_FULL_CHAIN, or inverted sphere boxes)
+    size_t lds = 0;           // dynamic LDS bytes: the walk's per-lane stack
+};
+
+// Default: the walk, which reproduces BVH::traverse's depth-first candidate order (ties to the earlier leaf) for spheres and
+// triangles alike.  The scan where the walk cannot serve: plain linear semantics (RT_FLAG_NO_BVH_CULL), an explicit scan
+// (RT_FLAG_EXACT_SCAN / RT_FLAG_LINEAR_SCAN, BVH semantics), a tree deeper than the stack, an empty world.  Every other flag
+// names an engine the query path does not have and changes nothing (rt_tile.h).
+inline QueryPlan plan_query(const SceneShape& sh, uint32_t flags) {
+    QueryPlan q;
+    const uint32_t n_prims = sh.n_sph + sh.n_tri;
+    const bool no_cull = (flags & RT_FLAG_NO_BVH_CULL) != 0;
+    const bool walk = !no_cull && !(flags & (RT_FLAG_EXACT_SCAN | RT_FLAG_LINEAR_SCAN)) && n_prims > 0 &&
+                      sh.bvh_depth < (uint32_t)rtk::TRAV_STACK;
+    q.engine = walk ? 2 : 1;
+    q.scan_mode = no_cull ? 0 : 2;
+    q.full_chain = (flags & RT_FLAG_FULL_CHAIN) != 0 || sh.inverted_boxes;   // (as plan_launch: the finite-direction test needs lo <= hi)
+    q.lds = walk ? ((size_t)sh.bvh_depth + 1) * QUERY_BLOCK * sizeof(uint32_t) : 0;
+    return q;
+}
+
 }  // namespace rtplan

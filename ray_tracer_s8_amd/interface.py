@@ -236,6 +236,36 @@ class Scene:
                                                                C.c_void_p(stream) if stream else None),
                    "rt_scene_render_tiles_pass_device")
 
+    def intersect(self, origins, directions, t_min=0.001, t_max=1000.0, *, any_hit: bool = False, flags: int = 0):
+        """Ray queries (rt_scene_intersect): the closest hit — or, with any_hit, whether there is one — of each ray
+        Ray::new(origins[i], directions[i]) within [t_min, t_max).  origins / directions: (N, 3); t_min / t_max: scalars or (N,).
+        Returns (hits, stats): a structured array of HIT_DTYPE (index = the primitive's position in the world, RT_HIT_NONE
+        for a miss) and the call's TileStats."""
+        o = np.asarray(origins, np.float32)
+        d = np.asarray(directions, np.float32)
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+            raise ValueError(f"origins and directions: need two (N, 3) arrays, got {o.shape} and {d.shape}")
+        n = len(o)
+        rays = np.empty(n, _abi.RAY_DTYPE)
+        rays["ox"], rays["oy"], rays["oz"] = o[:, 0], o[:, 1], o[:, 2]
+        rays["dx"], rays["dy"], rays["dz"] = d[:, 0], d[:, 1], d[:, 2]
+        rays["t_min"] = np.broadcast_to(np.asarray(t_min, np.float32), (n,))
+        rays["t_max"] = np.broadcast_to(np.asarray(t_max, np.float32), (n,))
+        hits = np.empty(n, _abi.HIT_DTYPE)
+        st = TileStats()
+        _abi.check(self._lib.rt_scene_intersect(self._h, rays.ctypes.data_as(C.POINTER(_abi.Ray)), n,
+                                                _abi.RT_QUERY_ANY if any_hit else _abi.RT_QUERY_CLOSEST, flags,
+                                                hits.ctypes.data_as(C.POINTER(_abi.Hit)), C.byref(st)), "rt_scene_intersect")
+        return hits, st
+
+    def intersect_device(self, d_rays: int, n: int, d_hits: int, *, any_hit: bool = False, flags: int = 0, stream: int = 0):
+        """Ray queries on device buffers (rt_scene_intersect_device): n rt_ray at d_rays, n rt_hit to d_hits (e.g. the
+        data_ptr() of torch tensors), asynchronous on `stream`; counters until collect()."""
+        _abi.check(self._lib.rt_scene_intersect_device(self._h, C.c_void_p(d_rays), n,
+                                                       _abi.RT_QUERY_ANY if any_hit else _abi.RT_QUERY_CLOSEST, flags,
+                                                       C.c_void_p(d_hits), C.c_void_p(stream) if stream else None),
+                   "rt_scene_intersect_device")
+
     def collect(self) -> TileStats:
         st = TileStats()
         _abi.check(self._lib.rt_scene_collect(self._h, C.byref(st)), "rt_scene_collect")
