@@ -44,7 +44,9 @@ extern "C" {
                                      strips by measured cost and reports the balance (rt_frame_stats.balance_*,
                                      RT_FLAG_FRAME_STATIC)
                                   (4, additions only: ray queries rt_scene_intersect / rt_scene_intersect_device with
-                                     rt_ray, rt_hit, RT_HIT_NONE, RT_QUERY_*; every earlier type and entry point unchanged) */
+                                     rt_ray, rt_hit, RT_HIT_NONE, RT_QUERY_*; every earlier type and entry point unchanged)
+                                  (4, additions only: path tracing of caller rays rt_scene_trace / rt_scene_trace_device with
+                                     rt_trace_request, RT_TRACE_RAY_*) */
 
 /* ---- status codes --------------------------------------------------------------- */
 typedef enum rt_status {
@@ -365,6 +367,53 @@ RT_API int rt_scene_intersect(rt_scene* scene, const rt_ray* rays, uint32_t n, u
  * accumulate in the scene until rt_scene_collect(). */
 RT_API int rt_scene_intersect_device(rt_scene* scene, const void* d_rays, uint32_t n, uint32_t mode, uint32_t flags,
                                      void* d_hits, void* hip_stream);
+
+/* ---- path tracing of caller rays: the colour a ray sees ---------------------------- */
+/* The reference's integrator on the caller's rays, for a batch of rays (rt_ray above) on a resident scene: any camera (a placed or
+ * rotated pinhole, orthographic, panoramic, stereo, a custom lens), light probes and irradiance samples, sample scheduling of the
+ * caller's own.
+ *
+ *   - Per sample: sample s of ray i is ray_color(ray_i, max_bounces + 1, rng) (ray-tracer-slave/src/main.rs:108-146): the closest
+ *     hit as rt_scene_intersect finds it; on an emitter em * albedo; on any other hit a UnitSphere draw and the scattered ray
+ *     diffuse + roughness (glossy - diffuse) (main.rs:119-127), which is drawn also when the depth runs out (the reference draws
+ *     before ray_color(.., 0) returns black); no hit: the sky of normalize_or_zero(d).y (main.rs:135-144); the albedos multiplied
+ *     right to left (main.rs:123).  Every segment of the path uses the ray's own window [t_min, t_max), as the tile request's
+ *     window serves every segment of a strip.
+ *   - ray_form RT_TRACE_RAY_NEW: the first ray is Ray::new(o, d) (B/ray.rs:133-143), the direction normalised by division (as
+ *     rt_scene_intersect).  RT_TRACE_RAY_AS_GIVEN: the direction is taken bit for bit, as the value Camera::get_ray
+ *     (camera.rs:109-129) or a bounce hands to ray_color (normalising twice is not idempotent in f32).
+ *   - RNG: rng_state == NULL: sample s of ray i draws from SmallRng::seed_from_u64(seed + 4 * 0x9E3779B97F4A7C15 * (i * spp + s))
+ *     (wrapping u64; the tile's stream per (pixel, sample) with the pixel index replaced by the ray index).  Otherwise rng_state
+ *     holds 4 * n u64, the xoshiro256++ state (s[0..3]) of each ray, read and written back: the ray's spp samples draw one after
+ *     the other from that one stream, and the state after the last draw is stored.
+ *   - out_rgb (3 * n floats, required): the f32 sum of the ray's sample colours, added in the order s = 0, 1, ... starting from
+ *     0 — not the mean, not gamma-corrected (the `accum` of the progressive entry points).  out_segments (n u32, optional): the
+ *     ray's ray_color entries with depth > 0, summed over its samples.
+ *   - flags: as for rt_scene_intersect.  Default: BVH semantics over the exact-node walk; RT_FLAG_NO_BVH_CULL the plain scan;
+ *     RT_FLAG_EXACT_SCAN / RT_FLAG_LINEAR_SCAN the scan with BVH semantics; RT_FLAG_FULL_CHAIN the literal slab test; a tree
+ *     deeper than the walk's stack takes the scan.  The tile-only flags are accepted and ignored.
+ *   - RT_ERR_BAD_ARG, and nothing launched: a NULL scene, request, rays or out_rgb, n == 0, spp == 0, ray_form > 1.
+ *     RT_ERR_LIMIT: spp > RT_MAX_SPP, max_bounces > RT_MAX_BOUNCES.
+ *   - Counters (rt_tile_stats): primary_rays = n * spp; ray_segments = the sum of all segments; broad_candidates = exact root
+ *     tests; kernel_ms; h2d_ms (rays and states) and d2h_ms (colours, segments, states) of the host form; n_launches; engine (as
+ *     for rt_scene_intersect).
+ * No per-scene scratch on the device: launches on different streams may overlap.   */
+typedef struct rt_trace_request {
+    uint32_t spp;               /* samples per ray, 1 .. RT_MAX_SPP                                        */
+    uint32_t max_bounces;       /* 0 .. RT_MAX_BOUNCES; ray_color depth = max_bounces + 1 (as rt_tile_request) */
+    uint64_t seed;              /* the seeded streams, when no RNG states are passed                       */
+    uint32_t flags;             /* RT_FLAG_*, as for rt_scene_intersect                                    */
+    uint32_t ray_form;          /* RT_TRACE_RAY_NEW | RT_TRACE_RAY_AS_GIVEN                                */
+} rt_trace_request;             /* 24 bytes */
+enum { RT_TRACE_RAY_NEW = 0u, RT_TRACE_RAY_AS_GIVEN = 1u };
+
+/* Host buffers, synchronous; rng_state, out_segments and stats may be NULL. */
+RT_API int rt_scene_trace(rt_scene* scene, const rt_trace_request* req, const rt_ray* rays, uint32_t n,
+                          uint64_t* rng_state, float* out_rgb, uint32_t* out_segments, rt_tile_stats* stats);
+/* Device buffers (n rt_ray, 4 n u64 or NULL, 3 n f32, n u32 or NULL), asynchronous on hip_stream (NULL = the scene's stream);
+ * counters and event times accumulate in the scene until rt_scene_collect(). */
+RT_API int rt_scene_trace_device(rt_scene* scene, const rt_trace_request* req, const void* d_rays, uint32_t n,
+                                 void* d_rng_state, void* d_out_rgb, void* d_out_segments, void* hip_stream);
 
 /* ---- whole frame: replaces controller dispatch + assembly ----------------------- */
 /* (controller main.rs:47-75 `for division_no in 0..divisions` and :109-115 stitch.)

@@ -112,10 +112,20 @@ RT_QUERY_ANY = 1
 RAY_DTYPE = np.dtype([(n, "<f4") for n, _ in Ray._fields_])
 HIT_DTYPE = np.dtype([(n, "<u4" if n == "index" else "<f4") for n, _ in Hit._fields_])
 
+class TraceRequest(C.Structure):
+    """rt_trace_request: samples per ray, bounces, seed of the seeded streams, RT_FLAG_* and the form of the first ray."""
+    _fields_ = [("spp", C.c_uint32), ("max_bounces", C.c_uint32), ("seed", C.c_uint64), ("flags", C.c_uint32),
+                ("ray_form", C.c_uint32)]
+
+
+RT_TRACE_RAY_NEW = 0
+RT_TRACE_RAY_AS_GIVEN = 1
+
 assert C.sizeof(TileRequest) == 64
 assert C.sizeof(TileStats) == 64
 assert C.sizeof(FrameStats) == 232
 assert C.sizeof(Ray) == C.sizeof(Hit) == RAY_DTYPE.itemsize == HIT_DTYPE.itemsize == 32
+assert C.sizeof(TraceRequest) == 24
 
 
 def default_request(**kw) -> TileRequest:
@@ -239,6 +249,11 @@ def _bind(path: Path) -> C.CDLL:
     lib.rt_scene_intersect.restype = C.c_int
     lib.rt_scene_intersect_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
     lib.rt_scene_intersect_device.restype = C.c_int
+    lib.rt_scene_trace.argtypes = [vp, C.POINTER(TraceRequest), C.POINTER(Ray), C.c_uint32, C.POINTER(C.c_uint64),
+                                   C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(TileStats)]
+    lib.rt_scene_trace.restype = C.c_int
+    lib.rt_scene_trace_device.argtypes = [vp, C.POINTER(TraceRequest), vp, C.c_uint32, vp, vp, vp, vp]
+    lib.rt_scene_trace_device.restype = C.c_int
     lib.rt_render_frame.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(TileRequest), vp, C.c_uint32,
                                     vp, C.c_uint32, vp, vp, C.c_size_t, C.POINTER(TileStats)]
     lib.rt_render_frame.restype = C.c_int

@@ -28,6 +28,7 @@
 #include "rt_kernel.hip.h"
 #include "rt_plan.h"
 #include "rt_query.hip.h"
+#include "rt_trace.hip.h"
 #include "rt_tile.h"
 
 namespace {
@@ -195,6 +196,8 @@ struct rt_scene {
     void* d_rays = nullptr;             // ... and for the rays and hits of rt_scene_intersect
     void* d_hits = nullptr;
     size_t d_query_cap = 0;             //   rays (= hits) each buffer holds
+    char* d_trace = nullptr;            // ... and for rt_scene_trace: rays, RNG states, colours, segments (80 bytes a ray)
+    size_t d_trace_cap = 0;             //   rays it holds
     // HIP-event bookkeeping of launches not yet collected
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, free_ev;
     uint64_t primary_rays = 0;
@@ -1019,6 +1022,7 @@ static int rt_scene_destroy_impl(rt_scene* sc) {
     (void)hipFree(sc->d_acc);
     (void)hipFree(sc->d_rays);
     (void)hipFree(sc->d_hits);
+    (void)hipFree(sc->d_trace);
     (void)hipFree(sc->d_cost);
     delete sc;
     g_live_scenes.fetch_sub(1);
@@ -1367,6 +1371,152 @@ static int rt_scene_intersect_impl(rt_scene* sc, const rt_ray* rays, uint32_t n,
     if (rc) return rc;
     HIPCHK(hipEventRecord(down.a, st));
     HIPCHK(hipMemcpyAsync(hits, sc->d_hits, n * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(down.b, st));
+    HIPCHK(hipEventSynchronize(down.b));
+    ev_return.ok = true;
+    float h2d = 0.f, d2h = 0.f;
+    HIPCHK(hipEventElapsedTime(&h2d, up.a, up.b));
+    HIPCHK(hipEventElapsedTime(&d2h, down.a, down.b));
+    rt_tile_stats s;
+    rc = collect_locked(sc, &s);
+    if (rc) return rc;
+    sc->h2d_ms = prev.h2d_ms;
+    s.h2d_ms = h2d;
+    s.d2h_ms = d2h;
+    if (stats) *stats = s;
+    return RT_OK;
+}
+
+// ---- path tracing of caller rays (rt_tile.h "path tracing of caller rays", rt_trace.hip.h) ---------------------------------------
+static int check_trace(rt_scene* sc, const rt_trace_request* rq, const void* rays, uint32_t n, const void* rgb) {
+    if (!sc) return fail(RT_ERR_BAD_ARG, "scene is NULL");
+    if (!rq) return fail(RT_ERR_BAD_ARG, "request is NULL");
+    if (!rays || !rgb) return fail(RT_ERR_BAD_ARG, "rays or out_rgb is NULL");
+    if (n == 0) return fail(RT_ERR_BAD_ARG, "n == 0");
+    if (rq->spp == 0) return fail(RT_ERR_BAD_ARG, "spp == 0");
+    if (rq->ray_form > RT_TRACE_RAY_AS_GIVEN) return fail(RT_ERR_BAD_ARG, "ray_form is neither RT_TRACE_RAY_NEW nor RT_TRACE_RAY_AS_GIVEN");
+    if (rq->spp > RT_MAX_SPP) return fail(RT_ERR_LIMIT, "spp > RT_MAX_SPP");
+    if (rq->max_bounces > RT_MAX_BOUNCES) return fail(RT_ERR_LIMIT, "max_bounces > RT_MAX_BOUNCES");
+    return RT_OK;
+}
+
+// Enqueue one trace launch on `stream` (caller holds sc->mu, device current): persistent waves over the n rays.
+static int launch_trace(rt_scene* sc, const rt_trace_request* rq, const void* d_rays, uint32_t n, void* d_state, void* d_rgb,
+                        void* d_segs, hipStream_t stream) {
+    const rtplan::SceneShape& sh = sc->shape;
+    const rtplan::TracePlan tp = rtplan::plan_trace(sh, rq->flags, rq->max_bounces);
+    const rtk::TraceFn kern = rtk::trace_kernel(tp.engine, tp.scan_mode);
+    if (!kern) return fail(RT_ERR_HIP, "no trace kernel for this plan");
+    rtk::TParams p;
+    std::memset(&p, 0, sizeof p);
+    p.rays = (const float4*)d_rays;
+    p.rgb = (float*)d_rgb;
+    p.segments = (uint32_t*)d_segs;
+    p.rng_state = (uint64_t*)d_state;
+    p.n = n;
+    p.seed = rq->seed;
+    p.spp = rq->spp;
+    p.depth = rq->max_bounces + 1;
+    p.as_given = rq->ray_form == RT_TRACE_RAY_AS_GIVEN ? 1u : 0u;
+    p.path32 = tp.path32 ? 1u : 0u;
+    p.lds_path_off = (uint32_t)tp.lds_path_off;
+    p.n_sph = sh.n_sph;
+    p.n_tri = sh.n_tri;
+    p.root_ref = sh.root_ref;
+    p.full_chain = tp.full_chain ? 1u : 0u;
+    p.trav = sc->d_trav;
+    p.bvh_nodes = sc->d_bvh;
+    p.leaf_of = sc->d_leaf_of;
+    p.world_rank = sc->has_order ? sc->d_world_rank : nullptr;
+    p.geom_r = sc->d_geom_r;
+    p.tri = sc->d_tri;
+    p.mat = sc->d_mat;
+    p.emis = sc->d_emis;
+    p.counters = sc->d_counters;
+    if (sc->pending.size() >= QUEUE_SLOTS) return fail(RT_ERR_LIMIT, "too many uncollected launches: call rt_scene_collect()");
+    int per_cu = 0;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, (int)tp.block, tp.lds));
+    if (per_cu < 1) per_cu = 1;
+    const uint64_t useful = ((uint64_t)n + tp.block - 1) / tp.block;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(useful, (uint64_t)sc->ctx->n_cu * (uint32_t)per_cu);
+    if (dbg(DBG_VERBOSE))
+        fprintf(stderr, "[rt] trace: engine %d  scan mode %d  block %u  lds %zu B (path %s)  workgroups/CU %d  rays %u  spp %u  bounces %u\n",
+                tp.engine, tp.scan_mode, tp.block, tp.lds, tp.path32 ? "u32" : "u16", per_cu, n, rq->spp, rq->max_bounces);
+    EvPair ev;
+    int rc = get_events(sc, ev);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(ev.a, stream));
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(tp.block), tp.lds, stream, p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev.b, stream));
+    sc->pending.push_back({ev.a, ev.b});
+    sc->primary_rays += (uint64_t)n * rq->spp;
+    sc->last_engine = (uint32_t)tp.engine;
+    sc->last_form = 0;
+    return RT_OK;
+}
+
+static int rt_scene_trace_device_impl(rt_scene* sc, const rt_trace_request* rq, const void* d_rays, uint32_t n, void* d_state,
+                                      void* d_rgb, void* d_segs, void* hip_stream) {
+    int rc = check_trace(sc, rq, d_rays, n, d_rgb);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    HIPCHK(hipSetDevice(sc->ctx->dev));
+    return launch_trace(sc, rq, d_rays, n, d_state, d_rgb, d_segs, hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream);
+}
+
+static int rt_scene_trace_impl(rt_scene* sc, const rt_trace_request* rq, const rt_ray* rays, uint32_t n, uint64_t* rng_state,
+                               float* rgb, uint32_t* segs, rt_tile_stats* stats) {
+    int rc = check_trace(sc, rq, rays, n, rgb);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> dl(sc->ctx->mu);
+    std::lock_guard<std::mutex> lk(sc->mu);
+    HIPCHK(hipSetDevice(sc->ctx->dev));
+    hipStream_t st = sc->ctx->stream;
+    // one device buffer: rays (32 B), states (32 B), colours (12 B), segments (4 B) per ray
+    const size_t ray_b = (size_t)n * sizeof(rt_ray), state_b = (size_t)n * 4 * sizeof(uint64_t), rgb_b = (size_t)n * 3 * sizeof(float),
+                 seg_b = (size_t)n * sizeof(uint32_t);
+    if (sc->d_trace_cap < n) {
+        (void)hipFree(sc->d_trace);
+        sc->d_trace = nullptr;
+        sc->d_trace_cap = 0;
+        if (hipMalloc(&sc->d_trace, ray_b + state_b + rgb_b + seg_b) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(RT_ERR_OOM, "hipMalloc(trace buffers) failed");
+        }
+        sc->d_trace_cap = n;
+    }
+    char* const d_rays = sc->d_trace;
+    char* const d_state = d_rays + ray_b;
+    char* const d_rgb = d_state + state_b;
+    char* const d_segs = d_rgb + rgb_b;
+    // settle anything enqueued earlier so the stats of this call are its own (the scene's upload time stays for the next tile call)
+    rt_tile_stats prev;
+    rc = collect_locked(sc, &prev);
+    if (rc) return rc;
+    EvPair up, down;
+    if ((rc = get_events(sc, up)) || (rc = get_events(sc, down))) return rc;
+    struct EvReturn {
+        rt_scene* sc;
+        EvPair a, b;
+        hipStream_t st;
+        bool ok = false;
+        ~EvReturn() {
+            if (!ok) (void)hipStreamSynchronize(st);       // (an error return waits for what already writes into caller memory)
+            sc->free_ev.push_back({a.a, a.b});
+            sc->free_ev.push_back({b.a, b.b});
+        }
+    } ev_return{sc, up, down, st};
+    HIPCHK(hipEventRecord(up.a, st));
+    HIPCHK(hipMemcpyAsync(d_rays, rays, ray_b, hipMemcpyHostToDevice, st));
+    if (rng_state) HIPCHK(hipMemcpyAsync(d_state, rng_state, state_b, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(up.b, st));
+    rc = launch_trace(sc, rq, d_rays, n, rng_state ? d_state : nullptr, d_rgb, segs ? d_segs : nullptr, st);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(down.a, st));
+    HIPCHK(hipMemcpyAsync(rgb, d_rgb, rgb_b, hipMemcpyDeviceToHost, st));
+    if (segs) HIPCHK(hipMemcpyAsync(segs, d_segs, seg_b, hipMemcpyDeviceToHost, st));
+    if (rng_state) HIPCHK(hipMemcpyAsync(rng_state, d_state, state_b, hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(down.b, st));
     HIPCHK(hipEventSynchronize(down.b));
     ev_return.ok = true;
@@ -1953,6 +2103,14 @@ RT_API int rt_scene_intersect(rt_scene* sc, const rt_ray* rays, uint32_t n, uint
 RT_API int rt_scene_intersect_device(rt_scene* sc, const void* d_rays, uint32_t n, uint32_t mode, uint32_t flags, void* d_hits,
                                      void* hip_stream) {
     return guarded([&] { return rt_scene_intersect_device_impl(sc, d_rays, n, mode, flags, d_hits, hip_stream); });
+}
+RT_API int rt_scene_trace(rt_scene* sc, const rt_trace_request* rq, const rt_ray* rays, uint32_t n, uint64_t* rng_state, float* out_rgb,
+                          uint32_t* out_segments, rt_tile_stats* stats) {
+    return guarded([&] { return rt_scene_trace_impl(sc, rq, rays, n, rng_state, out_rgb, out_segments, stats); });
+}
+RT_API int rt_scene_trace_device(rt_scene* sc, const rt_trace_request* rq, const void* d_rays, uint32_t n, void* d_rng_state,
+                                 void* d_out_rgb, void* d_out_segments, void* hip_stream) {
+    return guarded([&] { return rt_scene_trace_device_impl(sc, rq, d_rays, n, d_rng_state, d_out_rgb, d_out_segments, hip_stream); });
 }
 RT_API int rt_scene_render_tiles(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint8_t* const* out_rgb,
                                  size_t out_len_each, float* const* out_f32, rt_tile_stats* stats) {

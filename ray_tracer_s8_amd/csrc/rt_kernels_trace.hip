@@ -1,0 +1,13 @@
+// Device code of path tracing of caller rays (rt_trace.hip.h): ray_color over the query path's exact-node walk (engine 2) or its scan in
+// primitive order (engine 1, plain or BVH semantics).  Its own translation unit: the tile and query kernels' code objects are untouched
+// by it.
+#include "rt_trace.hip.h"
+
+namespace rtk {
+TraceFn trace_kernel(int engine, int scan_mode) {
+    if (engine == 2) return rt_trace_kernel<2, 2>;
+    if (engine == 1 && scan_mode == 0) return rt_trace_kernel<1, 0>;
+    if (engine == 1 && scan_mode == 2) return rt_trace_kernel<1, 2>;
+    return nullptr;
+}
+}  // namespace rtk

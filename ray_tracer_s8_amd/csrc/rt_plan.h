@@ -421,4 +421,39 @@ inline QueryPlan plan_query(const SceneShape& sh, uint32_t flags) {
     return q;
 }
 
+// ---- Path tracing of caller rays (rt_scene_trace*, rt_trace.hip.h).  One lane per caller ray, its samples and bounces
+// in a loop: the engine is the query path's, the plan adds the path stack and the workgroup size.
+constexpr uint32_t TRACE_LDS_CU = 160 * 1024;   // LDS of one CU: the trace kernels have no static LDS
+constexpr uint32_t TRACE_BLOCKS[] = {256, 128, 64};   // workgroup sizes, largest first
+
+struct TracePlan {
+    int engine = 2;           // as QueryPlan
+    int scan_mode = 2;
+    bool full_chain = false;
+    uint32_t block = 256;     // workgroup size: the largest of TRACE_BLOCKS at which two workgroups share a CU's LDS (64 otherwise)
+    bool path32 = false;      // path stack entries are u32 (more than 65 536 primitives, as the tile's path32), else u16
+    size_t lds_path_off = 0;  // byte offset of the path stack: behind the walk's (bvh depth + 1) x block u32 entries (engine 2)
+    size_t lds = 0;           // dynamic LDS bytes: walk stack + (max_bounces + 1) path entries per lane
+};
+
+// max_bounces <= RT_MAX_BOUNCES (checked by the caller).  The largest case, a 62-bounce trace over a tree of depth TRAV_STACK - 1,
+// needs (64 + 63) x 4 bytes a lane: 127 KiB at 256 lanes, so it takes 128-lane workgroups (63.5 KiB, two per CU).
+inline TracePlan plan_trace(const SceneShape& sh, uint32_t flags, uint32_t max_bounces) {
+    const QueryPlan q = plan_query(sh, flags);
+    TracePlan t;
+    t.engine = q.engine;
+    t.scan_mode = q.scan_mode;
+    t.full_chain = q.full_chain;
+    t.path32 = (sh.n_sph + sh.n_tri) > 65536u;
+    const size_t stack_lane = q.engine == 2 ? ((size_t)sh.bvh_depth + 1) * sizeof(uint32_t) : 0;
+    const size_t path_lane = ((size_t)max_bounces + 1) * (t.path32 ? 4 : 2);
+    for (uint32_t b : TRACE_BLOCKS) {
+        t.block = b;
+        if (2 * (stack_lane + path_lane) * b <= TRACE_LDS_CU) break;
+    }
+    t.lds_path_off = stack_lane * t.block;
+    t.lds = (stack_lane + path_lane) * t.block;
+    return t;
+}
+
 }  // namespace rtplan

@@ -36,13 +36,74 @@ struct QParams {
     unsigned long long* counters;   // [0] rays (ray_segments), [1] exact root tests (broad_candidates)
 };
 
-// The reference's exact root test of primitive `prim` (sphere.rs:42-47 / mesh.rs:109-161 -> shapes/mod.rs:106-129)
-__device__ __forceinline__ bool query_root(const QParams& p, uint32_t prim, V3 o, V3 d, float t_min, float t_max, float& t) {
+// The reference's exact root test of primitive `prim` (sphere.rs:42-47 / mesh.rs:109-161 -> shapes/mod.rs:106-129).  P: QParams or any
+// parameter block with the same scene fields (rt_trace.hip.h TParams).
+template <class P>
+__device__ __forceinline__ bool query_root(const P& p, uint32_t prim, V3 o, V3 d, float t_min, float t_max, float& t) {
     if (prim < p.n_sph) {
         const float4 g = at32(p.geom_r, prim);
         return exact_sphere(o, 2.0f * d, mk(g.x, g.y, g.z), g.w * g.w, t_min, t_max, t);    // (2f32 * ray.direction), radius.powi(2)
     }
     return exact_triangle(o, d, p.tri + 9 * (size_t)(prim - p.n_sph), t_min, t_max, t);
+}
+
+// The closest hit of one ray (ENGINE 2: the walk; 1: the scan with consider<MODE>; ANY: stop at the first admitted hit).  stack: the
+// per-lane walk stack, entry e of lane `tid` at stack[e * stride + tid] ((bvh depth + 1) entries); n_tests counts the exact root tests.
+template <int ENGINE, int MODE, bool ANY, class P>
+__device__ __forceinline__ Hit closest_hit(const P& p, V3 o, V3 d, float t_min, float t_max, const RayAux& aux, uint32_t* stack,
+                                           uint32_t tid, uint32_t stride, unsigned long long& n_tests) {
+    Hit h{-1, 0.f, 0.f};
+    if (ENGINE == 2) {
+        uint32_t ref = p.root_ref, sp = 0;
+        for (;;) {
+            if (ref & LEAF_BIT) {
+                const uint32_t prim = ref & ~LEAF_BIT;
+                float t;
+                n_tests++;
+                if (query_root(p, prim, o, d, t_min, t_max, t)) {
+                    const V3 pt = o + t * d;             // Ray::at, then |P - o| (consider)
+                    const float dist = vlength(pt - o);
+                    if (h.idx < 0 || h.dist > dist) {    // depth-first order: the first minimum wins
+                        h.idx = (int)prim;
+                        h.dist = dist;
+                        h.t = t;
+                    }
+                    if (ANY) break;
+                }
+                if (sp == 0) break;
+                ref = stack[--sp * stride + tid];
+                continue;
+            }
+            // Ray::intersects_aabb (ray.rs:174-194) on both child boxes (TravNode: (l_lo, left) (l_hi, right) (r_lo, -) (r_hi, -))
+            const float4* nd = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(p.trav) + ((size_t)ref << 6));
+            const float4 n0 = nd[0], n1 = nd[1], n2 = nd[2], n3 = nd[3];
+            const bool hl = aux.finite ? intersects_aabb_finite(o, aux, n0, n1) : intersects_aabb(o, aux, n0, n1);
+            const bool hr = aux.finite ? intersects_aabb_finite(o, aux, n2, n3) : intersects_aabb(o, aux, n2, n3);
+            const uint32_t cl = __float_as_uint(n0.w), cr = __float_as_uint(n1.w);
+            if (hl && hr) stack[sp++ * stride + tid] = cr;   // the right subtree after the whole left one
+            if (hl || hr) {
+                ref = hl ? cl : cr;
+            } else {
+                if (sp == 0) break;
+                ref = stack[--sp * stride + tid];
+            }
+        }
+    } else {
+        const uint32_t n_prims = p.n_sph + p.n_tri;
+        for (uint32_t prim = 0; prim < n_prims; prim++) {
+            float t;
+            n_tests++;
+            if (!query_root(p, prim, o, d, t_min, t_max, t)) continue;
+            if (MODE == 0) {
+                if (p.world_rank) consider<1>(h, (int)prim, o, d, t, aux, p.bvh_nodes, p.world_rank);
+                else consider<0>(h, (int)prim, o, d, t, aux, p.bvh_nodes, p.leaf_of);
+            } else {
+                consider<2>(h, (int)prim, o, d, t, aux, p.bvh_nodes, p.leaf_of);
+            }
+            if (ANY && h.idx >= 0) break;
+        }
+    }
+    return h;
 }
 
 // ENGINE 2: the walk; 1: the scan with consider<MODE>.  ANY: stop at the first admitted hit.
@@ -57,58 +118,8 @@ __global__ __launch_bounds__(256) void rt_query_kernel(const QParams p) {
         const V3 d = normalize(mk(r1.x, r1.y, r1.z));    // Ray::new: glam normalize, a division by the length
         const float t_min = r0.w, t_max = r1.w;
         const RayAux aux = ray_aux(d, p.full_chain != 0);
-        Hit h{-1, 0.f, 0.f};
         n_rays++;
-        if (ENGINE == 2) {
-            uint32_t ref = p.root_ref, sp = 0;
-            for (;;) {
-                if (ref & LEAF_BIT) {
-                    const uint32_t prim = ref & ~LEAF_BIT;
-                    float t;
-                    n_tests++;
-                    if (query_root(p, prim, o, d, t_min, t_max, t)) {
-                        const V3 pt = o + t * d;             // Ray::at, then |P - o| (consider)
-                        const float dist = vlength(pt - o);
-                        if (h.idx < 0 || h.dist > dist) {    // depth-first order: the first minimum wins
-                            h.idx = (int)prim;
-                            h.dist = dist;
-                            h.t = t;
-                        }
-                        if (ANY) break;
-                    }
-                    if (sp == 0) break;
-                    ref = qstack[--sp * 256u + tid];
-                    continue;
-                }
-                // Ray::intersects_aabb (ray.rs:174-194) on both child boxes (TravNode: (l_lo, left) (l_hi, right) (r_lo, -) (r_hi, -))
-                const float4* nd = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(p.trav) + ((size_t)ref << 6));
-                const float4 n0 = nd[0], n1 = nd[1], n2 = nd[2], n3 = nd[3];
-                const bool hl = aux.finite ? intersects_aabb_finite(o, aux, n0, n1) : intersects_aabb(o, aux, n0, n1);
-                const bool hr = aux.finite ? intersects_aabb_finite(o, aux, n2, n3) : intersects_aabb(o, aux, n2, n3);
-                const uint32_t cl = __float_as_uint(n0.w), cr = __float_as_uint(n1.w);
-                if (hl && hr) qstack[sp++ * 256u + tid] = cr;   // the right subtree after the whole left one
-                if (hl || hr) {
-                    ref = hl ? cl : cr;
-                } else {
-                    if (sp == 0) break;
-                    ref = qstack[--sp * 256u + tid];
-                }
-            }
-        } else {
-            const uint32_t n_prims = p.n_sph + p.n_tri;
-            for (uint32_t prim = 0; prim < n_prims; prim++) {
-                float t;
-                n_tests++;
-                if (!query_root(p, prim, o, d, t_min, t_max, t)) continue;
-                if (MODE == 0) {
-                    if (p.world_rank) consider<1>(h, (int)prim, o, d, t, aux, p.bvh_nodes, p.world_rank);
-                    else consider<0>(h, (int)prim, o, d, t, aux, p.bvh_nodes, p.leaf_of);
-                } else {
-                    consider<2>(h, (int)prim, o, d, t, aux, p.bvh_nodes, p.leaf_of);
-                }
-                if (ANY && h.idx >= 0) break;
-            }
-        }
+        const Hit h = closest_hit<ENGINE, MODE, ANY>(p, o, d, t_min, t_max, aux, qstack, tid, 256u, n_tests);
         // the hit record (shapes/mod.rs:184-190): P, |P - o|, the normal of sphere.rs:49-51 / mesh.rs:163-165, the world position
         uint4 w0 = make_uint4(0u, 0u, 0u, __float_as_uint(__builtin_inff())), w1 = make_uint4(0u, 0u, 0u, RT_HIT_NONE);
         if (h.idx >= 0) {

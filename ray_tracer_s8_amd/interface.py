@@ -266,6 +266,52 @@ class Scene:
                                                        C.c_void_p(d_hits), C.c_void_p(stream) if stream else None),
                    "rt_scene_intersect_device")
 
+    def trace(self, origins, directions, t_min=0.001, t_max=1000.0, *, spp: int = 1, max_bounces: int = 10, seed: int = 0,
+              rng_state=None, as_given: bool = False, flags: int = 0):
+        """Path tracing of caller rays (rt_scene_trace): for each ray, the f32 sum of `spp` samples of the reference's
+        ray_color(ray, max_bounces + 1, rng) within [t_min, t_max).  origins / directions: (N, 3); t_min / t_max: scalars or (N,).
+        as_given: take the directions bit for bit (RT_TRACE_RAY_AS_GIVEN) instead of Ray::new's normalisation.  rng_state: None
+        for the seeded streams of `seed`, else (N, 4) uint64 xoshiro256++ states, one stream per ray.
+        Returns (rgb_sum (N, 3) float32, segments (N,) uint32, stats), and the written-back states (N, 4) when rng_state is given."""
+        o = np.asarray(origins, np.float32)
+        d = np.asarray(directions, np.float32)
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+            raise ValueError(f"origins and directions: need two (N, 3) arrays, got {o.shape} and {d.shape}")
+        n = len(o)
+        rays = np.empty(n, _abi.RAY_DTYPE)
+        rays["ox"], rays["oy"], rays["oz"] = o[:, 0], o[:, 1], o[:, 2]
+        rays["dx"], rays["dy"], rays["dz"] = d[:, 0], d[:, 1], d[:, 2]
+        rays["t_min"] = np.broadcast_to(np.asarray(t_min, np.float32), (n,))
+        rays["t_max"] = np.broadcast_to(np.asarray(t_max, np.float32), (n,))
+        state = None
+        if rng_state is not None:
+            state = np.array(rng_state, np.uint64, order="C")
+            if state.shape != (n, 4):
+                raise ValueError(f"rng_state: need an (N, 4) uint64 array, got {state.shape}")
+        rq = _abi.TraceRequest(spp, max_bounces, seed & 0xFFFFFFFFFFFFFFFF, flags,
+                               _abi.RT_TRACE_RAY_AS_GIVEN if as_given else _abi.RT_TRACE_RAY_NEW)
+        rgb = np.empty((n, 3), np.float32)
+        segs = np.empty(n, np.uint32)
+        st = TileStats()
+        _abi.check(self._lib.rt_scene_trace(self._h, C.byref(rq), rays.ctypes.data_as(C.POINTER(_abi.Ray)), n,
+                                            state.ctypes.data_as(C.POINTER(C.c_uint64)) if state is not None else None,
+                                            rgb.ctypes.data_as(C.POINTER(C.c_float)), segs.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                            C.byref(st)), "rt_scene_trace")
+        if state is not None:
+            return rgb, segs, st, state
+        return rgb, segs, st
+
+    def trace_device(self, d_rays: int, n: int, d_rgb: int, *, d_segments: int = 0, d_rng_state: int = 0, spp: int = 1,
+                     max_bounces: int = 10, seed: int = 0, as_given: bool = False, flags: int = 0, stream: int = 0):
+        """Path tracing on device buffers (rt_scene_trace_device): n rt_ray at d_rays, 3 n float32 sums to d_rgb, optionally
+        n uint32 segments to d_segments and 4 n uint64 states at d_rng_state (read and written back) — e.g. the data_ptr() of
+        torch tensors; asynchronous on `stream`, counters until collect()."""
+        rq = _abi.TraceRequest(spp, max_bounces, seed & 0xFFFFFFFFFFFFFFFF, flags,
+                               _abi.RT_TRACE_RAY_AS_GIVEN if as_given else _abi.RT_TRACE_RAY_NEW)
+        vp = lambda ptr: C.c_void_p(ptr) if ptr else None
+        _abi.check(self._lib.rt_scene_trace_device(self._h, C.byref(rq), vp(d_rays), n, vp(d_rng_state), vp(d_rgb), vp(d_segments),
+                                                   vp(stream)), "rt_scene_trace_device")
+
     def collect(self) -> TileStats:
         st = TileStats()
         _abi.check(self._lib.rt_scene_collect(self._h, C.byref(st)), "rt_scene_collect")
