@@ -46,7 +46,9 @@ extern "C" {
                                   (4, additions only: ray queries rt_scene_intersect / rt_scene_intersect_device with
                                      rt_ray, rt_hit, RT_HIT_NONE, RT_QUERY_*; every earlier type and entry point unchanged)
                                   (4, additions only: path tracing of caller rays rt_scene_trace / rt_scene_trace_device with
-                                     rt_trace_request, RT_TRACE_RAY_*) */
+                                     rt_trace_request, RT_TRACE_RAY_*)
+                                  (4, additions only: feature buffers of a strip rt_scene_render_aov /
+                                     rt_scene_render_aovs_device with rt_aov_planes) */
 
 /* ---- status codes --------------------------------------------------------------- */
 typedef enum rt_status {
@@ -414,6 +416,60 @@ RT_API int rt_scene_trace(rt_scene* scene, const rt_trace_request* req, const rt
  * counters and event times accumulate in the scene until rt_scene_collect(). */
 RT_API int rt_scene_trace_device(rt_scene* scene, const rt_trace_request* req, const void* d_rays, uint32_t n,
                                  void* d_rng_state, void* d_out_rgb, void* d_out_segments, void* hip_stream);
+
+/* ---- feature buffers (AOVs) of a strip: what the camera rays of the beauty image first hit ---- */
+/* Per-pixel feature buffers for a denoiser, edge-aware filters, picking and compositing, ALIGNED with the beauty image: they
+ * come from the very camera rays (sub-pixel and lens samples) whose colours the tile entry points average, so the planes after
+ * samples [0, e) line up with the progressive preview after [0, e).
+ *
+ *   - Samples: a call covers samples s in [sample_begin, sample_end) of the S = req->spp sample job, with the rules and checks of
+ *     rt_scene_render_tile_pass.  The camera ray of sample s of the pixel at global row y, column x is exactly the ray the tile
+ *     kernel traces first for that sample: Camera::get_ray (camera.rs:109-129) drawing from
+ *     SmallRng::seed_from_u64(seed + 4 * 0x9E3779B97F4A7C15 * ((y W + x) S + s)) (wrapping u64): the UnitDisc rejection pair,
+ *     then the u and v jitter draws; the direction that results is used as given (no second normalisation).
+ *   - The sample's first hit is the closest hit in [req->t_min, req->t_max) as rt_scene_intersect finds it, with its tie rule
+ *     and its RT_FLAG_* semantics: BVH semantics over the exact-node walk by default; the plain scan under RT_FLAG_NO_BVH_CULL;
+ *     the scan with BVH semantics under RT_FLAG_EXACT_SCAN / RT_FLAG_LINEAR_SCAN; RT_FLAG_FULL_CHAIN the literal slab test.
+ *     Tile-only flags are accepted and ignored.
+ *   - Planes (Hs*W pixels laid out like out_f32; a NULL plane is not computed):
+ *       albedo  Hs*W*3 floats: the f32 sum over the call's samples of the first hit's albedo (p_albedo_at, whether or not the
+ *               primitive emits); a miss adds the sky colour ray_color returns for that ray (main.rs:135-144);
+ *       normal  Hs*W*3 floats: the sum of the normal at the first hit, the value of rt_hit.n* (not flipped toward the ray);
+ *       depth   Hs*W floats: the sum of |P - o| (rt_hit.distance; o is the lens point);
+ *       hits    Hs*W u32: the number of samples whose camera ray hit something;
+ *       index   Hs*W u32: the world position (rt_hit.index) hit by sample 0 of the pixel, or RT_HIT_NONE.  Written only by a
+ *               call with sample_begin == 0, left untouched by the others.
+ *   - Sums: a sum starts at +0.0f when sample_begin == 0, else from the plane's current contents (hits likewise, as a u32).
+ *     Each contributing sample is added with one f32 addition in the order s = sample_begin, sample_begin + 1, ...  A miss adds
+ *     nothing to normal and depth (no addition at all: a -0.0 survives).  So the planes after any cut of [0, k) into calls are
+ *     bit-identical to one call over [0, k), and strips of one frame stitch to the planes of a single strip (the streams are
+ *     per global pixel).  Means after [0, e): albedo / e, normal normalised, depth / hits.
+ *   - RT_ERR_BAD_ARG, and nothing launched: a NULL scene, request or planes; every plane NULL; sample_begin >= sample_end or
+ *     sample_end > spp; every check of the tile entry points; in the device form, requests that differ in a frame-level field
+ *     (as rt_scene_render_tiles_device) or entries with different sets of non-NULL planes.  RT_ERR_LIMIT: spp > RT_MAX_SPP.
+ *   - Counters (rt_tile_stats): primary_rays = ray_segments = Hs*W*(sample_end - sample_begin) per strip; broad_candidates =
+ *     exact root tests; engine as for rt_scene_intersect (2 the walk, 1 the scan); kernel_ms; n_launches; h2d_ms (planes
+ *     uploaded) and d2h_ms (planes downloaded) of the host form.
+ * No per-scene scratch on the device: launches on different streams may overlap.  The beauty launch does not write these planes
+ * (a separate pass re-traces the first segment of each sample; callers bound its cost by taking the planes over fewer samples
+ * than the beauty).   */
+typedef struct rt_aov_planes {
+    float*    albedo;           /* Hs*W*3 */
+    float*    normal;           /* Hs*W*3 */
+    float*    depth;            /* Hs*W   */
+    uint32_t* hits;             /* Hs*W   */
+    uint32_t* index;            /* Hs*W   */
+} rt_aov_planes;                /* 40 bytes */
+
+/* Host buffers, synchronous: the non-NULL planes are uploaded when sample_begin > 0 and always downloaded; stats may be NULL. */
+RT_API int rt_scene_render_aov(rt_scene* scene, const rt_tile_request* req, uint32_t sample_begin, uint32_t sample_end,
+                               const rt_aov_planes* planes, rt_tile_stats* stats);
+/* Batched device form: n strips of one frame, one launch per 64 strips, asynchronous on hip_stream (NULL = the scene's stream),
+ * counters and event times accumulating until rt_scene_collect().  d_planes: n entries of device pointers, every entry with
+ * the same set of non-NULL planes. */
+RT_API int rt_scene_render_aovs_device(rt_scene* scene, const rt_tile_request* reqs, uint32_t n,
+                                       uint32_t sample_begin, uint32_t sample_end,
+                                       const rt_aov_planes* d_planes, void* hip_stream);
 
 /* ---- whole frame: replaces controller dispatch + assembly ----------------------- */
 /* (controller main.rs:47-75 `for division_no in 0..divisions` and :109-115 stitch.)

@@ -121,11 +121,21 @@ class TraceRequest(C.Structure):
 RT_TRACE_RAY_NEW = 0
 RT_TRACE_RAY_AS_GIVEN = 1
 
+
+class AovPlanes(C.Structure):
+    """rt_aov_planes: the feature buffers of a strip (host or device pointers); a NULL plane is not computed."""
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("hits", C.c_void_p),
+                ("index", C.c_void_p)]
+
+
+AOV_PLANES = ("albedo", "normal", "depth", "hits", "index")
+
 assert C.sizeof(TileRequest) == 64
 assert C.sizeof(TileStats) == 64
 assert C.sizeof(FrameStats) == 232
 assert C.sizeof(Ray) == C.sizeof(Hit) == RAY_DTYPE.itemsize == HIT_DTYPE.itemsize == 32
 assert C.sizeof(TraceRequest) == 24
+assert C.sizeof(AovPlanes) == 40
 
 
 def default_request(**kw) -> TileRequest:
@@ -254,6 +264,12 @@ def _bind(path: Path) -> C.CDLL:
     lib.rt_scene_trace.restype = C.c_int
     lib.rt_scene_trace_device.argtypes = [vp, C.POINTER(TraceRequest), vp, C.c_uint32, vp, vp, vp, vp]
     lib.rt_scene_trace_device.restype = C.c_int
+    lib.rt_scene_render_aov.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.c_uint32, C.POINTER(AovPlanes),
+                                        C.POINTER(TileStats)]
+    lib.rt_scene_render_aov.restype = C.c_int
+    lib.rt_scene_render_aovs_device.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.c_uint32, C.c_uint32,
+                                                C.POINTER(AovPlanes), vp]
+    lib.rt_scene_render_aovs_device.restype = C.c_int
     lib.rt_render_frame.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(TileRequest), vp, C.c_uint32,
                                     vp, C.c_uint32, vp, vp, C.c_size_t, C.POINTER(TileStats)]
     lib.rt_render_frame.restype = C.c_int

@@ -29,6 +29,7 @@
 #include "rt_plan.h"
 #include "rt_query.hip.h"
 #include "rt_trace.hip.h"
+#include "rt_aov.hip.h"
 #include "rt_tile.h"
 
 namespace {
@@ -198,6 +199,8 @@ struct rt_scene {
     size_t d_query_cap = 0;             //   rays (= hits) each buffer holds
     char* d_trace = nullptr;            // ... and for rt_scene_trace: rays, RNG states, colours, segments (80 bytes a ray)
     size_t d_trace_cap = 0;             //   rays it holds
+    char* d_aov = nullptr;              // ... and for the planes of rt_scene_render_aov (36 bytes a pixel)
+    size_t d_aov_cap = 0;               //   bytes
     // HIP-event bookkeeping of launches not yet collected
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, free_ev;
     uint64_t primary_rays = 0;
@@ -1023,6 +1026,7 @@ static int rt_scene_destroy_impl(rt_scene* sc) {
     (void)hipFree(sc->d_rays);
     (void)hipFree(sc->d_hits);
     (void)hipFree(sc->d_trace);
+    (void)hipFree(sc->d_aov);
     (void)hipFree(sc->d_cost);
     delete sc;
     g_live_scenes.fetch_sub(1);
@@ -1517,6 +1521,192 @@ static int rt_scene_trace_impl(rt_scene* sc, const rt_trace_request* rq, const r
     HIPCHK(hipMemcpyAsync(rgb, d_rgb, rgb_b, hipMemcpyDeviceToHost, st));
     if (segs) HIPCHK(hipMemcpyAsync(segs, d_segs, seg_b, hipMemcpyDeviceToHost, st));
     if (rng_state) HIPCHK(hipMemcpyAsync(rng_state, d_state, state_b, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(down.b, st));
+    HIPCHK(hipEventSynchronize(down.b));
+    ev_return.ok = true;
+    float h2d = 0.f, d2h = 0.f;
+    HIPCHK(hipEventElapsedTime(&h2d, up.a, up.b));
+    HIPCHK(hipEventElapsedTime(&d2h, down.a, down.b));
+    rt_tile_stats s;
+    rc = collect_locked(sc, &s);
+    if (rc) return rc;
+    sc->h2d_ms = prev.h2d_ms;
+    s.h2d_ms = h2d;
+    s.d2h_ms = d2h;
+    if (stats) *stats = s;
+    return RT_OK;
+}
+
+// ---- feature buffers of a strip (rt_tile.h "feature buffers", rt_aov.hip.h) -----------------------------------------------------
+static uint32_t aov_mask(const rt_aov_planes& pl) {
+    return (pl.albedo ? rtk::AOV_ALBEDO : 0u) | (pl.normal ? rtk::AOV_NORMAL : 0u) | (pl.depth ? rtk::AOV_DEPTH : 0u) |
+           (pl.hits ? rtk::AOV_HITS : 0u) | (pl.index ? rtk::AOV_INDEX : 0u);
+}
+
+// The requests and planes of an AOV call (a batch of strips of one frame); *mask: the AOV_* bits of the planes every entry has.
+static int check_aov(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint32_t begin, uint32_t end, const rt_aov_planes* planes,
+                     uint32_t* mask) {
+    if (!sc) return fail(RT_ERR_BAD_ARG, "scene is NULL");
+    int rc = check_batch(rqs, n);
+    if (rc) return rc;
+    if (begin >= end) return fail(RT_ERR_BAD_ARG, "sample_begin >= sample_end");
+    if (end > rqs[0].spp) return fail(RT_ERR_BAD_ARG, "sample_end > spp");
+    if (!planes) return fail(RT_ERR_BAD_ARG, "planes is NULL");
+    *mask = aov_mask(planes[0]);
+    if (*mask == 0) return fail(RT_ERR_BAD_ARG, "every plane is NULL");
+    for (uint32_t i = 1; i < n; i++)
+        if (aov_mask(planes[i]) != *mask) return fail(RT_ERR_BAD_ARG, "the entries of d_planes differ in their set of planes");
+    return RT_OK;
+}
+
+// Enqueue the AOV launches of n strips (one per MAX_BATCH strips) on `stream` (caller holds sc->mu, device current): persistent waves
+// over (strip, pixel).
+static int launch_aov(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint32_t begin, uint32_t end, const rt_aov_planes* d_planes,
+                      uint32_t mask, hipStream_t stream) {
+    const rtplan::SceneShape& sh = sc->shape;
+    const rtplan::QueryPlan qp = rtplan::plan_query(sh, rqs[0].flags);
+    const rtk::AovFn kern = rtk::aov_kernel(qp.engine, qp.scan_mode);
+    if (!kern) return fail(RT_ERR_HIP, "no AOV kernel for this plan");
+    const rt_tile_request& rq = rqs[0];
+    const uint32_t hs = rq.height / rq.divisions;
+    rtk::AParams p;
+    std::memset(&p, 0, sizeof p);
+    rtplan::fill_camera(rq, p);
+    p.t_min = rq.t_min;
+    p.t_max = rq.t_max;
+    p.W = rq.width;
+    p.H = rq.height;
+    p.npix = hs * rq.width;
+    p.spp_all = rq.spp;
+    p.s_begin = begin;
+    p.s_end = end;
+    p.planes = mask;
+    p.n_sph = sh.n_sph;
+    p.n_tri = sh.n_tri;
+    p.root_ref = sh.root_ref;
+    p.full_chain = qp.full_chain ? 1u : 0u;
+    p.trav = sc->d_trav;
+    p.bvh_nodes = sc->d_bvh;
+    p.leaf_of = sc->d_leaf_of;
+    p.world_rank = sc->has_order ? sc->d_world_rank : nullptr;
+    p.geom_r = sc->d_geom_r;
+    p.tri = sc->d_tri;
+    p.mat = sc->d_mat;
+    p.counters = sc->d_counters;
+    int per_cu = 0;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, rtplan::QUERY_BLOCK, qp.lds));
+    if (per_cu < 1) per_cu = 1;
+    for (uint32_t i0 = 0; i0 < n; i0 += rtk::MAX_BATCH) {
+        const uint32_t m = std::min<uint32_t>(rtk::MAX_BATCH, n - i0);
+        p.n_strips = m;
+        for (uint32_t i = 0; i < m; i++) {
+            const rt_aov_planes& pl = d_planes[i0 + i];
+            rtk::AovStrip& sd = p.strips[i];
+            sd.seed = rqs[i0 + i].seed;
+            sd.albedo = pl.albedo;
+            sd.normal = pl.normal;
+            sd.depth = pl.depth;
+            sd.hits = pl.hits;
+            sd.index = pl.index;
+            sd.y0 = hs * rqs[i0 + i].division_no;
+        }
+        if (sc->pending.size() >= QUEUE_SLOTS) return fail(RT_ERR_LIMIT, "too many uncollected launches: call rt_scene_collect()");
+        const uint64_t useful = ((uint64_t)p.npix * m + rtplan::QUERY_BLOCK - 1) / rtplan::QUERY_BLOCK;
+        const uint32_t blocks = (uint32_t)std::min<uint64_t>(useful, (uint64_t)sc->ctx->n_cu * (uint32_t)per_cu);
+        if (dbg(DBG_VERBOSE))
+            fprintf(stderr, "[rt] aov: engine %d  scan mode %d  lds %zu B  workgroups/CU %d  strips %u  pixels %u  samples [%u, %u)  planes %#x\n",
+                    qp.engine, qp.scan_mode, qp.lds, per_cu, m, p.npix, begin, end, mask);
+        EvPair ev;
+        int rc = get_events(sc, ev);
+        if (rc) return rc;
+        HIPCHK(hipEventRecord(ev.a, stream));
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(rtplan::QUERY_BLOCK), qp.lds, stream, p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev.b, stream));
+        sc->pending.push_back({ev.a, ev.b});
+        sc->primary_rays += (uint64_t)p.npix * (end - begin) * m;
+        sc->last_engine = (uint32_t)qp.engine;
+        sc->last_form = 0;
+    }
+    return RT_OK;
+}
+
+static int rt_scene_render_aovs_device_impl(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint32_t begin, uint32_t end,
+                                            const rt_aov_planes* d_planes, void* hip_stream) {
+    uint32_t mask = 0;
+    int rc = check_aov(sc, rqs, n, begin, end, d_planes, &mask);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    HIPCHK(hipSetDevice(sc->ctx->dev));
+    return launch_aov(sc, rqs, n, begin, end, d_planes, mask, hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream);
+}
+
+static int rt_scene_render_aov_impl(rt_scene* sc, const rt_tile_request* rq, uint32_t begin, uint32_t end, const rt_aov_planes* planes,
+                                    rt_tile_stats* stats) {
+    uint32_t mask = 0;
+    int rc = check_aov(sc, rq, 1, begin, end, planes, &mask);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> dl(sc->ctx->mu);
+    std::lock_guard<std::mutex> lk(sc->mu);
+    HIPCHK(hipSetDevice(sc->ctx->dev));
+    hipStream_t st = sc->ctx->stream;
+    // one device buffer: albedo and normal (12 B), depth, hits and index (4 B) per pixel
+    const size_t npix = (size_t)(rq->height / rq->divisions) * rq->width;
+    const size_t v3_b = npix * 3 * sizeof(float), s_b = npix * sizeof(uint32_t);
+    if (sc->d_aov_cap < 2 * v3_b + 3 * s_b) {
+        (void)hipFree(sc->d_aov);
+        sc->d_aov = nullptr;
+        sc->d_aov_cap = 0;
+        if (hipMalloc(&sc->d_aov, 2 * v3_b + 3 * s_b) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(RT_ERR_OOM, "hipMalloc(AOV planes) failed");
+        }
+        sc->d_aov_cap = 2 * v3_b + 3 * s_b;
+    }
+    // the device planes the caller asked for, and their sizes
+    struct Plane {
+        void* host;
+        char* dev;
+        size_t bytes;
+    };
+    const Plane pl[5] = {{planes->albedo, sc->d_aov, v3_b},
+                         {planes->normal, sc->d_aov + v3_b, v3_b},
+                         {planes->depth, sc->d_aov + 2 * v3_b, s_b},
+                         {planes->hits, sc->d_aov + 2 * v3_b + s_b, s_b},
+                         {planes->index, sc->d_aov + 2 * v3_b + 2 * s_b, s_b}};
+    rt_aov_planes dp = {};
+    dp.albedo = planes->albedo ? (float*)pl[0].dev : nullptr;
+    dp.normal = planes->normal ? (float*)pl[1].dev : nullptr;
+    dp.depth = planes->depth ? (float*)pl[2].dev : nullptr;
+    dp.hits = planes->hits ? (uint32_t*)pl[3].dev : nullptr;
+    dp.index = planes->index ? (uint32_t*)pl[4].dev : nullptr;
+    // settle anything enqueued earlier so the stats of this call are its own (the scene's upload time stays for the next tile call)
+    rt_tile_stats prev;
+    rc = collect_locked(sc, &prev);
+    if (rc) return rc;
+    EvPair up, down;
+    if ((rc = get_events(sc, up)) || (rc = get_events(sc, down))) return rc;
+    struct EvReturn {
+        rt_scene* sc;
+        EvPair a, b;
+        hipStream_t st;
+        bool ok = false;
+        ~EvReturn() {
+            if (!ok) (void)hipStreamSynchronize(st);       // (an error return waits for what already writes into caller memory)
+            sc->free_ev.push_back({a.a, a.b});
+            sc->free_ev.push_back({b.a, b.b});
+        }
+    } ev_return{sc, up, down, st};
+    HIPCHK(hipEventRecord(up.a, st));
+    if (begin > 0)          // (a call from sample 0 reads no plane: the caller's buffers may be uninitialised)
+        for (const Plane& q : pl)
+            if (q.host) HIPCHK(hipMemcpyAsync(q.dev, q.host, q.bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(up.b, st));
+    rc = launch_aov(sc, rq, 1, begin, end, &dp, mask, st);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(down.a, st));
+    for (const Plane& q : pl)
+        if (q.host) HIPCHK(hipMemcpyAsync(q.host, q.dev, q.bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(down.b, st));
     HIPCHK(hipEventSynchronize(down.b));
     ev_return.ok = true;
@@ -2111,6 +2301,14 @@ RT_API int rt_scene_trace(rt_scene* sc, const rt_trace_request* rq, const rt_ray
 RT_API int rt_scene_trace_device(rt_scene* sc, const rt_trace_request* rq, const void* d_rays, uint32_t n, void* d_rng_state,
                                  void* d_out_rgb, void* d_out_segments, void* hip_stream) {
     return guarded([&] { return rt_scene_trace_device_impl(sc, rq, d_rays, n, d_rng_state, d_out_rgb, d_out_segments, hip_stream); });
+}
+RT_API int rt_scene_render_aov(rt_scene* sc, const rt_tile_request* rq, uint32_t sample_begin, uint32_t sample_end,
+                               const rt_aov_planes* planes, rt_tile_stats* stats) {
+    return guarded([&] { return rt_scene_render_aov_impl(sc, rq, sample_begin, sample_end, planes, stats); });
+}
+RT_API int rt_scene_render_aovs_device(rt_scene* sc, const rt_tile_request* reqs, uint32_t n, uint32_t sample_begin,
+                                       uint32_t sample_end, const rt_aov_planes* d_planes, void* hip_stream) {
+    return guarded([&] { return rt_scene_render_aovs_device_impl(sc, reqs, n, sample_begin, sample_end, d_planes, hip_stream); });
 }
 RT_API int rt_scene_render_tiles(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint8_t* const* out_rgb,
                                  size_t out_len_each, float* const* out_f32, rt_tile_stats* stats) {

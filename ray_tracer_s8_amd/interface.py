@@ -312,6 +312,49 @@ class Scene:
         _abi.check(self._lib.rt_scene_trace_device(self._h, C.byref(rq), vp(d_rays), n, vp(d_rng_state), vp(d_rgb), vp(d_segments),
                                                    vp(stream)), "rt_scene_trace_device")
 
+    def render_aov(self, req: TileRequest, begin: int = 0, end: Optional[int] = None, *,
+                   planes: Sequence[str] = _abi.AOV_PLANES, out: Optional[dict] = None):
+        """Feature buffers of a strip (rt_scene_render_aov): over samples [begin, end) of the req.spp-sample job (end None:
+        req.spp), the per-pixel sums of what the tile's own camera rays first hit — albedo (Hs, W, 3) float32 (the sky colour
+        on a miss), normal (Hs, W, 3) float32, depth (Hs, W) float32, hits (Hs, W) uint32 — and index (Hs, W) uint32, the world
+        position hit by sample 0 (RT_HIT_NONE: a miss; written only when begin == 0).  `out`: the dict of planes of an earlier
+        call, updated in place, which carries the sums across calls (required when begin > 0, like render_tile_pass's accum).
+        Returns (planes dict, stats); aov_means() turns the sums into means."""
+        end = req.spp if end is None else end
+        names = tuple(planes)
+        bad = [n for n in names if n not in _abi.AOV_PLANES]
+        if bad or not names:
+            raise ValueError(f"planes: a non-empty subset of {_abi.AOV_PLANES}, got {names}")
+        hs = req.height // max(req.divisions, 1)                          # (a bad request is refused by the library)
+        shapes = {"albedo": ((hs, req.width, 3), np.float32), "normal": ((hs, req.width, 3), np.float32),
+                  "depth": ((hs, req.width), np.float32), "hits": ((hs, req.width), np.uint32), "index": ((hs, req.width), np.uint32)}
+        if out is None:
+            if begin != 0:
+                raise ValueError("out: a call that starts after sample 0 continues the sums: pass the planes of the last call")
+            out = {n: np.empty(*shapes[n]) for n in names}
+        for n in names:
+            a = out.get(n)
+            shape, dt = shapes[n]
+            if a is None or a.dtype != dt or a.shape != shape or not a.flags.c_contiguous or not a.flags.writeable:
+                raise ValueError(f"out[{n!r}]: need a writeable contiguous {np.dtype(dt).name} array of shape {shape}")
+        pl = _abi.AovPlanes(*[out[n].ctypes.data if n in names else None for n in _abi.AOV_PLANES])
+        st = TileStats()
+        _abi.check(self._lib.rt_scene_render_aov(self._h, C.byref(req), begin, end, C.byref(pl), C.byref(st)),
+                   "rt_scene_render_aov")
+        return {n: out[n] for n in names}, st
+
+    def render_aovs_device(self, reqs: Sequence[TileRequest], begin: int, end: int, d_planes: Sequence[dict], stream: int = 0):
+        """Feature buffers of n strips of one frame on device buffers (rt_scene_render_aovs_device), asynchronous on `stream`,
+        counters until collect().  d_planes[i]: {plane name: device pointer} of strip i (e.g. torch tensors' data_ptr()); every
+        entry names the same planes."""
+        n = len(reqs)
+        if len(d_planes) != n:
+            raise ValueError("d_planes: one entry per request")
+        arr = (TileRequest * n)(*reqs)
+        pl = (_abi.AovPlanes * n)(*[_abi.AovPlanes(*[d.get(k) or None for k in _abi.AOV_PLANES]) for d in d_planes])
+        _abi.check(self._lib.rt_scene_render_aovs_device(self._h, arr, n, begin, end, pl, C.c_void_p(stream) if stream else None),
+                   "rt_scene_render_aovs_device")
+
     def collect(self) -> TileStats:
         st = TileStats()
         _abi.check(self._lib.rt_scene_collect(self._h, C.byref(st)), "rt_scene_collect")
@@ -392,6 +435,31 @@ class Controller:
     def close(self):
         for s in self.slaves:
             s.close()
+
+
+def aov_means(planes: dict, n_samples: int) -> dict:
+    """Means of the feature-buffer sums of Scene.render_aov after samples [0, n_samples): albedo / n_samples, the normal
+    normalised (zero where no sample hit), depth / hits (zero where no sample hit).  hits and index are passed through."""
+    out = {}
+    hits = planes.get("hits")
+    if "albedo" in planes:
+        out["albedo"] = (planes["albedo"] / np.float32(n_samples)).astype(np.float32)
+    if "normal" in planes:
+        nrm = planes["normal"]
+        ln = np.sqrt((nrm.astype(np.float32) ** 2).sum(-1, keepdims=True))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["normal"] = np.where(ln > 0, nrm / ln, np.float32(0)).astype(np.float32)
+        if hits is not None:
+            out["normal"][hits == 0] = 0
+    if "depth" in planes:
+        if hits is None:
+            raise ValueError("depth means need the hits plane")
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["depth"] = np.where(hits > 0, planes["depth"] / np.maximum(hits, 1).astype(np.float32), np.float32(0)).astype(np.float32)
+    for k in ("hits", "index"):
+        if k in planes:
+            out[k] = planes[k]
+    return out
 
 
 class FrameContext:
