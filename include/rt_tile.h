@@ -48,7 +48,9 @@ extern "C" {
                                   (4, additions only: path tracing of caller rays rt_scene_trace / rt_scene_trace_device with
                                      rt_trace_request, RT_TRACE_RAY_*)
                                   (4, additions only: feature buffers of a strip rt_scene_render_aov /
-                                     rt_scene_render_aovs_device with rt_aov_planes) */
+                                     rt_scene_render_aovs_device with rt_aov_planes)
+                                  (4, additions only: the edge-avoiding a-trous denoiser rt_scene_denoise /
+                                     rt_scene_denoise_device with rt_denoise_request, RT_DENOISE_MAX_ITERATIONS) */
 
 /* ---- status codes --------------------------------------------------------------- */
 typedef enum rt_status {
@@ -470,6 +472,77 @@ RT_API int rt_scene_render_aov(rt_scene* scene, const rt_tile_request* req, uint
 RT_API int rt_scene_render_aovs_device(rt_scene* scene, const rt_tile_request* reqs, uint32_t n,
                                        uint32_t sample_begin, uint32_t sample_end,
                                        const rt_aov_planes* d_planes, void* hip_stream);
+
+/* ---- denoiser: edge-avoiding a-trous wavelet filter guided by the feature buffers ---- */
+/* Dammertz et al. 2010: a 5x5 B3-spline kernel dilated by 2^i at iteration i, with edge stopping on colour, normal and depth and
+ * optional albedo demodulation, over the progressive accum of a frame's strips and their rt_aov_planes.  Every operation below is
+ * one IEEE f32 rounding in the order written (no fused multiply-add, correctly rounded division and sqrt, no exp), so the result
+ * is reproducible bit for bit off the GPU.
+ *
+ *   - Image: reqs[0..n) are strips of one frame with consecutive division_no, ascending, that agree on every frame-level field
+ *     (the check of rt_scene_render_tiles_device).  Their union, stacked top to bottom, is the image P: W columns, R = n*Hs rows.
+ *     The top and bottom rows of P are image borders: strips denoised in separate calls show seams; n = divisions denoises the
+ *     whole frame.  The strip count is not limited to 64.  No scene data is read: the world is irrelevant.
+ *   - Inputs per pixel (finite and non-negative, as the renderer writes them; otherwise the result is unspecified):
+ *       c = C / e per channel, C = accum[i] (Hs*W*3 floats laid out like out_f32), e = color_samples;
+ *       albedo given: a = A / k (k = aov_samples), d = a + albedo_eps, r0 = c / d; without albedo r0 = c;
+ *       normal given: L = sqrt((Nx*Nx + Ny*Ny) + Nz*Nz), n = L > 0 ? (Nx/L, Ny/L, Nz/L) : 0;
+ *       depth given (requires hits): z = hits > 0 ? D / (float)hits : 0, and q = z > 0 ? 1 / z : 0;
+ *       hits given: g = hits > 0, else g = 1.  index is ignored.
+ *   - Iteration i = 0 .. I-1, step s = 2^i, kc_0 = k_color, kc_{i+1} = kc_i * color_step_scale:
+ *       taps (dy, dx) in {-2..2}^2, dy outer, dx inner, both ascending; tap pixel q = p + s*(dx, dy);
+ *       a tap is skipped if q lies outside P or g_q != g_p;
+ *       the centre tap (0, 0) has t = 1; any other tap:
+ *         D = r_q - r_p per channel, x = ((Dr*Dr + Dg*Dg) + Db*Db) * kc_i;
+ *         normal given, unless n_p and n_q are both 0: dot = (np_x*nq_x + np_y*nq_y) + np_z*nq_z, x = x + (1 - dot) * k_normal;
+ *         depth given: x = x + (|z_q - z_p| * q_p) * k_depth;
+ *         t = 1 - x if that is > 0, else +0 (Tukey's biweight: compact support, an exact 0 across a strong edge);
+ *       w = H[dy]*H[dx] * (t*t), H = (1/16, 1/4, 3/8, 1/4, 1/16), the dyadic product first;
+ *       Sw += w, Sc += w * r_q from +0.0 in tap order; r_{i+1} = Sc / Sw per channel (Sw >= 9/64: the centre tap).
+ *   - Outputs, each optional (at least one), laid out like out_f32 per strip: m = albedo ? r_I * d : r_I, the linear mean;
+ *       out_linear  m (Hs*W*3 floats);
+ *       out_f32     sqrt(m) (Hs*W*3 floats: post-gamma, pre-quantise, as the tile's out_f32);
+ *       out_rgb     the tile's quantisation of sqrt(m) * 255.999f (Hs*W*3 bytes, out_len_each >= rt_tile_bytes).
+ *     So with iterations == 0 and no albedo, out_f32 and out_rgb are the progressive pass's preview after [0, e), bit for bit.
+ *     Outputs must not overlap inputs.
+ *   - RT_ERR_BAD_ARG, and nothing launched: a NULL scene, request, dreq, accum (or entry) or planes (an entry whose every plane is
+ *     NULL is allowed: plain colour a-trous); no output; depth without hits; a field of dreq out of range; strips that are not
+ *     consecutive or differ in a frame-level field; entries with different sets of non-NULL planes or outputs; in the device
+ *     form scratch_bytes < rt_denoise_scratch_bytes(W, R) or a NULL d_scratch.  RT_ERR_BUFFER_TOO_SMALL: out_len_each <
+ *     rt_tile_bytes.  RT_ERR_LIMIT: color_samples or aov_samples > RT_MAX_SPP.
+ *   - Counters (rt_tile_stats): kernel_ms, n_launches, h2d_ms (inputs uploaded) and d2h_ms (outputs downloaded) of the host form;
+ *     the ray counters add 0; engine reports 0 (no closest-hit engine runs).
+ *  */
+#define RT_DENOISE_MAX_ITERATIONS 8u
+typedef struct rt_denoise_request {
+    uint32_t color_samples;     /* e: accum holds samples [0, e)                                   1 .. RT_MAX_SPP          */
+    uint32_t aov_samples;       /* k: the albedo plane holds samples [0, k)              1 .. RT_MAX_SPP (when albedo given) */
+    uint32_t iterations;        /* I: 0 .. RT_DENOISE_MAX_ITERATIONS                                                        */
+    uint32_t flags;             /* must be 0                                                                                 */
+    float k_color;              /* >= 0, finite                                                                              */
+    float color_step_scale;     /* > 0, finite: k_color of iteration i+1 = (that of i) * this                               */
+    float k_normal;             /* >= 0, finite                                                                              */
+    float k_depth;              /* >= 0, finite                                                                              */
+    float albedo_eps;           /* > 0, finite                                                                               */
+    uint32_t reserved;          /* must be 0                                                                                 */
+} rt_denoise_request;           /* 40 bytes */
+
+/* The defaults; color_samples and aov_samples are set to 1: the caller sets both. */
+RT_API void rt_denoise_request_defaults(rt_denoise_request* r);
+/* Device scratch of rt_scene_denoise_device for an image of width x rows pixels (any iteration count and set of planes). */
+RT_API size_t rt_denoise_scratch_bytes(uint32_t width, uint32_t rows);
+/* Host buffers, synchronous: accum[i], planes[i] and the outputs are host pointers of strip i; stats may be NULL. */
+RT_API int rt_scene_denoise(rt_scene* scene, const rt_tile_request* reqs, uint32_t n, const rt_denoise_request* dreq,
+                            const float* const* accum, const rt_aov_planes* planes,
+                            uint8_t* const* out_rgb, size_t out_len_each, float* const* out_f32, float* const* out_linear,
+                            rt_tile_stats* stats);
+/* Device buffers, asynchronous on hip_stream (NULL = the scene's stream), counters until rt_scene_collect(); the scratch is the
+ * caller's (no per-scene device scratch: calls on different streams with separate scratch may overlap).  out_rgb, out_f32 and
+ * out_linear: NULL or n device pointers. */
+RT_API int rt_scene_denoise_device(rt_scene* scene, const rt_tile_request* reqs, uint32_t n, const rt_denoise_request* dreq,
+                                   const void* const* d_accum, const rt_aov_planes* d_planes,
+                                   void* const* d_out_rgb, size_t out_len_each, void* const* d_out_f32,
+                                   void* const* d_out_linear, void* d_scratch, size_t scratch_bytes, void* hip_stream);
 
 /* ---- whole frame: replaces controller dispatch + assembly ----------------------- */
 /* (controller main.rs:47-75 `for division_no in 0..divisions` and :109-115 stitch.)

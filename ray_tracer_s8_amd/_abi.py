@@ -130,12 +130,30 @@ class AovPlanes(C.Structure):
 
 AOV_PLANES = ("albedo", "normal", "depth", "hits", "index")
 
+RT_DENOISE_MAX_ITERATIONS = 8
+
+
+class DenoiseRequest(C.Structure):
+    """rt_denoise_request: the a-trous denoiser's parameters (rt_tile.h "denoiser"); DenoiseRequest.defaults() for the library's."""
+    _fields_ = [("color_samples", C.c_uint32), ("aov_samples", C.c_uint32), ("iterations", C.c_uint32), ("flags", C.c_uint32),
+                ("k_color", C.c_float), ("color_step_scale", C.c_float), ("k_normal", C.c_float), ("k_depth", C.c_float),
+                ("albedo_eps", C.c_float), ("reserved", C.c_uint32)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "DenoiseRequest":
+        r = cls()
+        load().rt_denoise_request_defaults(C.byref(r))
+        for k, v in kw.items():
+            setattr(r, k, v)
+        return r
+
 assert C.sizeof(TileRequest) == 64
 assert C.sizeof(TileStats) == 64
 assert C.sizeof(FrameStats) == 232
 assert C.sizeof(Ray) == C.sizeof(Hit) == RAY_DTYPE.itemsize == HIT_DTYPE.itemsize == 32
 assert C.sizeof(TraceRequest) == 24
 assert C.sizeof(AovPlanes) == 40
+assert C.sizeof(DenoiseRequest) == 40
 
 
 def default_request(**kw) -> TileRequest:
@@ -270,6 +288,18 @@ def _bind(path: Path) -> C.CDLL:
     lib.rt_scene_render_aovs_device.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.c_uint32, C.c_uint32,
                                                 C.POINTER(AovPlanes), vp]
     lib.rt_scene_render_aovs_device.restype = C.c_int
+    lib.rt_denoise_request_defaults.argtypes = [C.POINTER(DenoiseRequest)]
+    lib.rt_denoise_request_defaults.restype = None
+    lib.rt_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
+    lib.rt_denoise_scratch_bytes.restype = C.c_size_t
+    lib.rt_scene_denoise.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.POINTER(DenoiseRequest), C.POINTER(vp),
+                                     C.POINTER(AovPlanes), C.POINTER(vp), C.c_size_t, C.POINTER(vp), C.POINTER(vp),
+                                     C.POINTER(TileStats)]
+    lib.rt_scene_denoise.restype = C.c_int
+    lib.rt_scene_denoise_device.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.POINTER(DenoiseRequest), C.POINTER(vp),
+                                            C.POINTER(AovPlanes), C.POINTER(vp), C.c_size_t, C.POINTER(vp), C.POINTER(vp), vp,
+                                            C.c_size_t, vp]
+    lib.rt_scene_denoise_device.restype = C.c_int
     lib.rt_render_frame.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(TileRequest), vp, C.c_uint32,
                                     vp, C.c_uint32, vp, vp, C.c_size_t, C.POINTER(TileStats)]
     lib.rt_render_frame.restype = C.c_int

@@ -30,6 +30,7 @@
 #include "rt_query.hip.h"
 #include "rt_trace.hip.h"
 #include "rt_aov.hip.h"
+#include "rt_denoise.hip.h"
 #include "rt_tile.h"
 
 namespace {
@@ -102,12 +103,14 @@ enum DebugKnob {
     DBG_REORDER,           // RT_REORDER         0: primitive records stay in the caller's order (A/B)          (default 1)
     DBG_TAIL_TILES,        // RT_TAIL_TILES      tiles at the end of a launch's queue handed out in quarters; -1: host rule (default -1)
     DBG_STRIP_COST,        // RT_STRIP_COST      0: the kernels do not count per-strip ray segments for the frame context (A/B)   (default 1)
+    DBG_DENOISE_LDS_STEP,  // RT_DENOISE_LDS_STEP denoiser: largest step staged in LDS (0: none); -1: rtplan::DN_LDS_MAX_STEP    (default -1)
     DBG_N
 };
 std::atomic<int> g_dbg[DBG_N];
 const struct { const char* env; int def; } g_dbg_spec[DBG_N] = {
     {"RT_LDS_TREE", 1}, {"RT_CULL_WALK", -1}, {"RT_NO_STAGE", 0}, {"RT_SLOTS", 0}, {"RT_FORCE_CAPPED", 0},
-    {"RT_STACK_LDS", 0}, {"RT_COMPACT", 1}, {"RT_REFILL_EIGHTHS", 0}, {"RT_COMMIT_SLOTS", 0}, {"RT_VERBOSE", 0}, {"RT_REORDER", 1}, {"RT_TAIL_TILES", -1}, {"RT_STRIP_COST", 1}};
+    {"RT_STACK_LDS", 0}, {"RT_COMPACT", 1}, {"RT_REFILL_EIGHTHS", 0}, {"RT_COMMIT_SLOTS", 0}, {"RT_VERBOSE", 0}, {"RT_REORDER", 1}, {"RT_TAIL_TILES", -1}, {"RT_STRIP_COST", 1},
+    {"RT_DENOISE_LDS_STEP", -1}};
 std::once_flag g_dbg_once;
 void dbg_load_env() {
     std::call_once(g_dbg_once, [] {
@@ -201,6 +204,8 @@ struct rt_scene {
     size_t d_trace_cap = 0;             //   rays it holds
     char* d_aov = nullptr;              // ... and for the planes of rt_scene_render_aov (36 bytes a pixel)
     size_t d_aov_cap = 0;               //   bytes
+    char* d_dn = nullptr;               // ... and for rt_scene_denoise: the filter's scratch, the strips' inputs and outputs
+    size_t d_dn_cap = 0;                //   bytes
     // HIP-event bookkeeping of launches not yet collected
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, free_ev;
     uint64_t primary_rays = 0;
@@ -1027,6 +1032,7 @@ static int rt_scene_destroy_impl(rt_scene* sc) {
     (void)hipFree(sc->d_hits);
     (void)hipFree(sc->d_trace);
     (void)hipFree(sc->d_aov);
+    (void)hipFree(sc->d_dn);
     (void)hipFree(sc->d_cost);
     delete sc;
     g_live_scenes.fetch_sub(1);
@@ -1723,6 +1729,291 @@ static int rt_scene_render_aov_impl(rt_scene* sc, const rt_tile_request* rq, uin
     return RT_OK;
 }
 
+// ---- the a-trous denoiser (rt_tile.h "denoiser", rt_denoise.hip.h, rt_denoise_math.h) -------------------------------------------------
+static uint32_t dn_mask(const rt_aov_planes& pl) {           // (the index plane is ignored)
+    return (pl.albedo ? rtdn::P_ALBEDO : 0u) | (pl.normal ? rtdn::P_NORMAL : 0u) | (pl.depth ? rtdn::P_DEPTH : 0u) |
+           (pl.hits ? rtdn::P_HITS : 0u);
+}
+
+// An optional output array: NULL, or n non-NULL entries.
+static int check_out_array(const void* const* a, uint32_t n, const char* what) {
+    if (!a) return RT_OK;
+    for (uint32_t i = 0; i < n; i++)
+        if (!a[i]) return fail(RT_ERR_BAD_ARG, std::string(what) + "[i] is NULL in a non-NULL array");
+    return RT_OK;
+}
+
+// Every check of rt_tile.h "denoiser" but the device scratch; *mask: the rtdn::P_* of the planes every entry has.
+static int check_denoise(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, const rt_denoise_request* dq, const void* const* acc,
+                         const rt_aov_planes* planes, const void* const* rgb, size_t out_len, const void* const* f32,
+                         const void* const* lin, uint32_t* mask) {
+    if (!sc) return fail(RT_ERR_BAD_ARG, "scene is NULL");
+    int rc = check_batch(rqs, n);
+    if (rc) return rc;
+    for (uint32_t i = 1; i < n; i++)
+        if (rqs[i].division_no != rqs[0].division_no + i) return fail(RT_ERR_BAD_ARG, "strips must have consecutive division_no, ascending");
+    if (!dq) return fail(RT_ERR_BAD_ARG, "denoise request is NULL");
+    if (!acc) return fail(RT_ERR_BAD_ARG, "accum is NULL");
+    for (uint32_t i = 0; i < n; i++)
+        if (!acc[i]) return fail(RT_ERR_BAD_ARG, "accum[i] is NULL");
+    if (!planes) return fail(RT_ERR_BAD_ARG, "planes is NULL");
+    *mask = dn_mask(planes[0]);
+    for (uint32_t i = 1; i < n; i++)
+        if (dn_mask(planes[i]) != *mask) return fail(RT_ERR_BAD_ARG, "the entries of planes differ in their set of planes");
+    if ((*mask & rtdn::P_DEPTH) && !(*mask & rtdn::P_HITS)) return fail(RT_ERR_BAD_ARG, "the depth plane needs the hits plane");
+    if (!rgb && !f32 && !lin) return fail(RT_ERR_BAD_ARG, "no output");
+    if ((rc = check_out_array(rgb, n, "out_rgb")) || (rc = check_out_array(f32, n, "out_f32")) ||
+        (rc = check_out_array(lin, n, "out_linear")))
+        return rc;
+    const bool albedo = (*mask & rtdn::P_ALBEDO) != 0;
+    if (dq->color_samples == 0 || (albedo && dq->aov_samples == 0)) return fail(RT_ERR_BAD_ARG, "color_samples and aov_samples must be >= 1");
+    if (dq->color_samples > RT_MAX_SPP || (albedo && dq->aov_samples > RT_MAX_SPP))
+        return fail(RT_ERR_LIMIT, "color_samples or aov_samples > RT_MAX_SPP");
+    if (dq->iterations > RT_DENOISE_MAX_ITERATIONS) return fail(RT_ERR_BAD_ARG, "iterations > RT_DENOISE_MAX_ITERATIONS");
+    if (dq->flags != 0 || dq->reserved != 0) return fail(RT_ERR_BAD_ARG, "flags and reserved must be 0");
+    auto fin = [](float v) { return std::isfinite(v); };
+    if (!fin(dq->k_color) || !(dq->k_color >= 0.f) || !fin(dq->k_normal) || !(dq->k_normal >= 0.f) || !fin(dq->k_depth) ||
+        !(dq->k_depth >= 0.f))
+        return fail(RT_ERR_BAD_ARG, "k_color, k_normal and k_depth must be finite and >= 0");
+    if (!fin(dq->color_step_scale) || !(dq->color_step_scale > 0.f) || !fin(dq->albedo_eps) || !(dq->albedo_eps > 0.f))
+        return fail(RT_ERR_BAD_ARG, "color_step_scale and albedo_eps must be finite and > 0");
+    if (rgb && out_len < rt_tile_bytes(&rqs[0])) return fail(RT_ERR_BUFFER_TOO_SMALL, "out_len_each < (H/div)*W*3");
+    const uint64_t rows = (uint64_t)(rqs[0].height / rqs[0].divisions) * n;
+    if (rows > rqs[0].height) return fail(RT_ERR_BAD_ARG, "more strips than the frame has");
+    if (rows >= (1u << 30) || rqs[0].width >= (1u << 30)) return fail(RT_ERR_LIMIT, "image of 2^30 rows or columns");   // (taps in int)
+    return RT_OK;
+}
+
+static uint32_t dn_lds_max_step() {
+    const int k = dbg(DBG_DENOISE_LDS_STEP);
+    return k < 0 ? rtplan::DN_LDS_MAX_STEP : (uint32_t)k;
+}
+
+// Enqueue the launches of one denoise call on `stream` (caller holds sc->mu, device current, arguments checked): the entry kernel
+// per band of DN_BAND strips, one step kernel per iteration over the whole image but the last, the last per band (or, with no
+// iteration, the output kernel per band).  One event pair per launch.
+static int launch_denoise(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, const rt_denoise_request& dq, uint32_t mask,
+                          const void* const* acc, const rt_aov_planes* planes, void* const* rgb, void* const* f32, void* const* lin,
+                          char* scratch, hipStream_t stream) {
+    const rt_tile_request& rq = rqs[0];
+    const uint32_t W = rq.width, Hs = rq.height / rq.divisions, R = Hs * n;
+    const bool guided = (mask & (rtdn::P_NORMAL | rtdn::P_DEPTH | rtdn::P_HITS)) != 0;
+    const rtplan::DenoisePlan pl = rtplan::plan_denoise(W, R, dq.iterations, guided, dn_lds_max_step());
+    rtk::DnParams p;
+    std::memset(&p, 0, sizeof p);
+    p.W = W;
+    p.R = R;
+    p.Hs = Hs;
+    p.planes = mask;
+    p.e_f = (float)dq.color_samples;
+    p.k_f = (float)dq.aov_samples;
+    p.eps = dq.albedo_eps;
+    p.kn = dq.k_normal;
+    p.kd = dq.k_depth;
+    p.guide = (float4*)(scratch + pl.off_guide);
+    float4* buf[2] = {(float4*)(scratch + pl.off_color[0]), (float4*)(scratch + pl.off_color[1])};
+    const uint32_t persist = (uint32_t)sc->ctx->n_cu * 8u;           // grid cap of the grid-stride kernels: 8 workgroups of 256 a CU
+    auto launch = [&](rtk::DnFn kern, uint32_t blocks, size_t lds) -> int {
+        if (sc->pending.size() >= QUEUE_SLOTS) return fail(RT_ERR_LIMIT, "too many uncollected launches: call rt_scene_collect()");
+        EvPair ev;
+        int rc = get_events(sc, ev);
+        if (rc) return rc;
+        HIPCHK(hipEventRecord(ev.a, stream));
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(rtplan::DN_BLOCK), lds, stream, p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev.b, stream));
+        sc->pending.push_back({ev.a, ev.b});
+        return RT_OK;
+    };
+    // the band of strips [b0, b0 + m): its rows and its per-strip pointers
+    auto band = [&](uint32_t b0, uint32_t m) {
+        p.row0 = b0 * Hs;
+        p.rows = m * Hs;
+        p.n_strips = m;
+        for (uint32_t i = 0; i < m; i++) {
+            rtk::DnStrip& sd = p.strips[i];
+            const rt_aov_planes& q = planes[b0 + i];
+            sd.accum = (const float*)acc[b0 + i];
+            sd.albedo = q.albedo;
+            sd.normal = q.normal;
+            sd.depth = q.depth;
+            sd.hits = q.hits;
+            sd.rgb = rgb ? (uint8_t*)rgb[b0 + i] : nullptr;
+            sd.f32 = f32 ? (float*)f32[b0 + i] : nullptr;
+            sd.lin = lin ? (float*)lin[b0 + i] : nullptr;
+        }
+    };
+    auto grid_stride = [&](uint64_t pixels) { return (uint32_t)std::min<uint64_t>((pixels + 255) / 256, persist); };
+    auto tiles = [&](uint32_t rows) { return pl.tiles_x * ((rows + rtplan::DN_TILE_Y - 1) / rtplan::DN_TILE_Y); };
+    int rc;
+    p.dst = buf[0];
+    for (uint32_t b0 = 0; b0 < n; b0 += rtk::DN_BAND) {
+        band(b0, std::min<uint32_t>(rtk::DN_BAND, n - b0));
+        if ((rc = launch(rtk::dn_entry_kernel(), grid_stride((uint64_t)p.rows * W), 0))) return rc;
+    }
+    uint32_t cur = 0;
+    float kc = dq.k_color;
+    for (uint32_t i = 0; i < dq.iterations; i++) {
+        p.s = pl.step[i];
+        p.kc = kc;
+        p.src = buf[cur];
+        p.dst = buf[cur ^ 1u];
+        const bool last = i + 1 == dq.iterations;
+        const rtk::DnFn kern = rtk::dn_step_kernel(pl.lds[i] != 0, last);
+        if (!last) {
+            p.row0 = 0;
+            p.rows = R;
+            p.n_strips = 0;
+            if ((rc = launch(kern, tiles(R), pl.lds[i]))) return rc;
+        } else {
+            for (uint32_t b0 = 0; b0 < n; b0 += rtk::DN_BAND) {
+                band(b0, std::min<uint32_t>(rtk::DN_BAND, n - b0));
+                if ((rc = launch(kern, tiles(p.rows), pl.lds[i]))) return rc;
+            }
+        }
+        if (dbg(DBG_VERBOSE))
+            fprintf(stderr, "[rt] denoise: iteration %u  step %u  lds %zu B  workgroups/CU %u  image %u x %u  planes %#x\n", i, p.s,
+                    pl.lds[i], pl.wg_per_cu[i], W, R, mask);
+        cur ^= 1u;
+        kc = kc * dq.color_step_scale;
+    }
+    if (dq.iterations == 0) {
+        p.src = buf[0];
+        for (uint32_t b0 = 0; b0 < n; b0 += rtk::DN_BAND) {
+            band(b0, std::min<uint32_t>(rtk::DN_BAND, n - b0));
+            if ((rc = launch(rtk::dn_output_kernel(), grid_stride((uint64_t)p.rows * W), 0))) return rc;
+        }
+    }
+    sc->last_engine = 0;
+    sc->last_form = 0;
+    return RT_OK;
+}
+
+static int rt_scene_denoise_device_impl(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, const rt_denoise_request* dq,
+                                        const void* const* d_acc, const rt_aov_planes* d_planes, void* const* d_rgb, size_t out_len,
+                                        void* const* d_f32, void* const* d_lin, void* d_scratch, size_t scratch_bytes,
+                                        void* hip_stream) {
+    uint32_t mask = 0;
+    int rc = check_denoise(sc, rqs, n, dq, d_acc, d_planes, (const void* const*)d_rgb, out_len, (const void* const*)d_f32,
+                           (const void* const*)d_lin, &mask);
+    if (rc) return rc;
+    const uint32_t R = rqs[0].height / rqs[0].divisions * n;
+    if (!d_scratch) return fail(RT_ERR_BAD_ARG, "d_scratch is NULL");
+    if (scratch_bytes < rtplan::plan_denoise(rqs[0].width, R, 0, false).scratch_bytes)
+        return fail(RT_ERR_BAD_ARG, "scratch_bytes < rt_denoise_scratch_bytes(W, R)");
+    std::lock_guard<std::mutex> lk(sc->mu);
+    HIPCHK(hipSetDevice(sc->ctx->dev));
+    return launch_denoise(sc, rqs, n, *dq, mask, d_acc, d_planes, d_rgb, d_f32, d_lin, (char*)d_scratch,
+                          hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream);
+}
+
+static int rt_scene_denoise_impl(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, const rt_denoise_request* dq,
+                                 const float* const* acc, const rt_aov_planes* planes, uint8_t* const* rgb, size_t out_len,
+                                 float* const* f32, float* const* lin, rt_tile_stats* stats) {
+    uint32_t mask = 0;
+    int rc = check_denoise(sc, rqs, n, dq, (const void* const*)acc, planes, (const void* const*)rgb, out_len,
+                           (const void* const*)f32, (const void* const*)lin, &mask);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> dl(sc->ctx->mu);
+    std::lock_guard<std::mutex> lk(sc->mu);
+    HIPCHK(hipSetDevice(sc->ctx->dev));
+    hipStream_t st = sc->ctx->stream;
+    // one device buffer: the scratch, then per strip its inputs and outputs, each region 256-B aligned
+    const size_t npix = (size_t)(rqs[0].height / rqs[0].divisions) * rqs[0].width;
+    const size_t v3 = npix * 3 * sizeof(float), s1 = npix * sizeof(uint32_t), u8 = npix * 3;
+    const size_t scratch = rtplan::plan_denoise(rqs[0].width, (uint32_t)(npix / rqs[0].width) * n, 0, false).scratch_bytes;
+    struct Region {
+        const void* host_in;     // uploaded
+        void* host_out;          // downloaded
+        size_t bytes;
+        size_t off;
+    };
+    std::vector<Region> regs;
+    std::vector<const void*> d_acc(n);
+    std::vector<rt_aov_planes> d_pl(n);
+    std::vector<void*> d_rgb(n), d_f32(n), d_lin(n);
+    size_t top = rtplan::dn_align(scratch);
+    auto add = [&](const void* in, void* out, size_t bytes) {
+        regs.push_back({in, out, bytes, top});
+        top += rtplan::dn_align(bytes);
+        return regs.size() - 1;
+    };
+    std::vector<size_t> ia(n), ip(n * 4), io(n * 3);
+    for (uint32_t i = 0; i < n; i++) {
+        ia[i] = add(acc[i], nullptr, v3);
+        ip[i * 4 + 0] = planes[i].albedo ? add(planes[i].albedo, nullptr, v3) : SIZE_MAX;
+        ip[i * 4 + 1] = planes[i].normal ? add(planes[i].normal, nullptr, v3) : SIZE_MAX;
+        ip[i * 4 + 2] = planes[i].depth ? add(planes[i].depth, nullptr, s1) : SIZE_MAX;
+        ip[i * 4 + 3] = planes[i].hits ? add(planes[i].hits, nullptr, s1) : SIZE_MAX;
+        io[i * 3 + 0] = rgb ? add(nullptr, rgb[i], u8) : SIZE_MAX;
+        io[i * 3 + 1] = f32 ? add(nullptr, f32[i], v3) : SIZE_MAX;
+        io[i * 3 + 2] = lin ? add(nullptr, lin[i], v3) : SIZE_MAX;
+    }
+    if (sc->d_dn_cap < top) {
+        (void)hipFree(sc->d_dn);
+        sc->d_dn = nullptr;
+        sc->d_dn_cap = 0;
+        if (hipMalloc(&sc->d_dn, top) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(RT_ERR_OOM, "hipMalloc(denoise staging) failed");
+        }
+        sc->d_dn_cap = top;
+    }
+    auto dev = [&](size_t r) -> void* { return r == SIZE_MAX ? nullptr : sc->d_dn + regs[r].off; };
+    for (uint32_t i = 0; i < n; i++) {
+        d_acc[i] = dev(ia[i]);
+        d_pl[i] = {};
+        d_pl[i].albedo = (float*)dev(ip[i * 4 + 0]);
+        d_pl[i].normal = (float*)dev(ip[i * 4 + 1]);
+        d_pl[i].depth = (float*)dev(ip[i * 4 + 2]);
+        d_pl[i].hits = (uint32_t*)dev(ip[i * 4 + 3]);
+        d_rgb[i] = dev(io[i * 3 + 0]);
+        d_f32[i] = dev(io[i * 3 + 1]);
+        d_lin[i] = dev(io[i * 3 + 2]);
+    }
+    // settle anything enqueued earlier so the stats of this call are its own (the scene's upload time stays for the next tile call)
+    rt_tile_stats prev;
+    rc = collect_locked(sc, &prev);
+    if (rc) return rc;
+    EvPair up, down;
+    if ((rc = get_events(sc, up)) || (rc = get_events(sc, down))) return rc;
+    struct EvReturn {
+        rt_scene* sc;
+        EvPair a, b;
+        hipStream_t st;
+        bool ok = false;
+        ~EvReturn() {
+            if (!ok) (void)hipStreamSynchronize(st);       // (an error return waits for what already writes into caller memory)
+            sc->free_ev.push_back({a.a, a.b});
+            sc->free_ev.push_back({b.a, b.b});
+        }
+    } ev_return{sc, up, down, st};
+    HIPCHK(hipEventRecord(up.a, st));
+    for (const Region& r : regs)
+        if (r.host_in) HIPCHK(hipMemcpyAsync(sc->d_dn + r.off, r.host_in, r.bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(up.b, st));
+    rc = launch_denoise(sc, rqs, n, *dq, mask, d_acc.data(), d_pl.data(), rgb ? d_rgb.data() : nullptr, f32 ? d_f32.data() : nullptr,
+                        lin ? d_lin.data() : nullptr, sc->d_dn, st);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(down.a, st));
+    for (const Region& r : regs)
+        if (r.host_out) HIPCHK(hipMemcpyAsync(r.host_out, sc->d_dn + r.off, r.bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(down.b, st));
+    HIPCHK(hipEventSynchronize(down.b));
+    ev_return.ok = true;
+    float h2d = 0.f, d2h = 0.f;
+    HIPCHK(hipEventElapsedTime(&h2d, up.a, up.b));
+    HIPCHK(hipEventElapsedTime(&d2h, down.a, down.b));
+    rt_tile_stats s;
+    rc = collect_locked(sc, &s);
+    if (rc) return rc;
+    sc->h2d_ms = prev.h2d_ms;
+    s.h2d_ms = h2d;
+    s.d2h_ms = d2h;
+    if (stats) *stats = s;
+    return RT_OK;
+}
+
 // ---- Test / tool hooks.  NOT part of rt_tile.h and NOT in the product library: compiled only with -DRT_DEBUG_HOOKS, which
 // build.py adds for lib/librt_s8_dbg.so (tests) and tools add to their instrumented variants.  tests/test_abi.py checks that
 // librt_s8.so exports exactly the functions rt_tile.h declares.
@@ -2309,6 +2600,37 @@ RT_API int rt_scene_render_aov(rt_scene* sc, const rt_tile_request* rq, uint32_t
 RT_API int rt_scene_render_aovs_device(rt_scene* sc, const rt_tile_request* reqs, uint32_t n, uint32_t sample_begin,
                                        uint32_t sample_end, const rt_aov_planes* d_planes, void* hip_stream) {
     return guarded([&] { return rt_scene_render_aovs_device_impl(sc, reqs, n, sample_begin, sample_end, d_planes, hip_stream); });
+}
+RT_API void rt_denoise_request_defaults(rt_denoise_request* r) {
+    if (!r) return;
+    std::memset(r, 0, sizeof *r);
+    r->color_samples = 1;
+    r->aov_samples = 1;
+    r->iterations = 5;
+    r->k_color = 0.01f;            // (chosen on the quality test's c2 and quad_room inputs)
+    r->color_step_scale = 4.0f;
+    r->k_normal = 1.0f;
+    r->k_depth = 4.0f;
+    r->albedo_eps = 0.00390625f;
+}
+RT_API size_t rt_denoise_scratch_bytes(uint32_t width, uint32_t rows) {
+    return rtplan::plan_denoise(width, rows, 0, false).scratch_bytes;
+}
+RT_API int rt_scene_denoise(rt_scene* sc, const rt_tile_request* reqs, uint32_t n, const rt_denoise_request* dreq,
+                            const float* const* accum, const rt_aov_planes* planes, uint8_t* const* out_rgb, size_t out_len_each,
+                            float* const* out_f32, float* const* out_linear, rt_tile_stats* stats) {
+    return guarded([&] {
+        return rt_scene_denoise_impl(sc, reqs, n, dreq, accum, planes, out_rgb, out_len_each, out_f32, out_linear, stats);
+    });
+}
+RT_API int rt_scene_denoise_device(rt_scene* sc, const rt_tile_request* reqs, uint32_t n, const rt_denoise_request* dreq,
+                                   const void* const* d_accum, const rt_aov_planes* d_planes, void* const* d_out_rgb,
+                                   size_t out_len_each, void* const* d_out_f32, void* const* d_out_linear, void* d_scratch,
+                                   size_t scratch_bytes, void* hip_stream) {
+    return guarded([&] {
+        return rt_scene_denoise_device_impl(sc, reqs, n, dreq, d_accum, d_planes, d_out_rgb, out_len_each, d_out_f32, d_out_linear,
+                                            d_scratch, scratch_bytes, hip_stream);
+    });
 }
 RT_API int rt_scene_render_tiles(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint8_t* const* out_rgb,
                                  size_t out_len_each, float* const* out_f32, rt_tile_stats* stats) {

@@ -456,4 +456,58 @@ inline TracePlan plan_trace(const SceneShape& sh, uint32_t flags, uint32_t max_b
     return t;
 }
 
+// ---- The a-trous denoiser (rt_scene_denoise*, rt_denoise.hip.h).  One lane per pixel of the W x R image P in 64 x 4
+// tiles of 256 lanes; the iterations ping-pong two colour buffers in the caller's scratch, next to one guide buffer.  Steps up to
+// lds_max_step stage their tile's (64 + 4s) x (4 + 4s) window of colours (and guides) in LDS; larger steps gather through L2.
+constexpr uint32_t DN_TILE_X = 64, DN_TILE_Y = 4, DN_BLOCK = DN_TILE_X * DN_TILE_Y;
+constexpr uint32_t DN_MAX_ITER = 8;              // RT_DENOISE_MAX_ITERATIONS
+constexpr uint32_t DN_LDS_MAX_STEP = 2;          // default: steps 1 and 2 through LDS (tools/denoise_bench.py --lds-step)
+constexpr size_t DN_LDS_CU = 160 * 1024;         // LDS of one CU: the denoiser kernels have no static LDS
+constexpr uint32_t DN_WG_PER_CU_MAX = 8;         // 2048 lanes of a CU / DN_BLOCK
+constexpr size_t DN_REC = 16;                    // bytes of a colour or guide record (float4)
+constexpr size_t DN_ALIGN = 256;
+
+struct DenoisePlan {
+    uint64_t npix = 0;            // W * R
+    uint32_t tiles_x = 0;         // tiles per row band; the launches' grids are tiles_x x (row band height / DN_TILE_Y) workgroups
+    size_t off_guide = 0;         // byte offsets in the scratch: the guide records, the two colour buffers
+    size_t off_color[2] = {0, 0};
+    size_t scratch_bytes = 0;     // rt_denoise_scratch_bytes: independent of the iteration count and the planes
+    uint32_t step[DN_MAX_ITER] = {};       // per iteration: the step s
+    size_t lds[DN_MAX_ITER] = {};          // per iteration: dynamic LDS bytes of its window, 0: gather through L2
+    uint32_t wg_per_cu[DN_MAX_ITER] = {};  // per iteration: workgroups a CU holds by its LDS (at most DN_WG_PER_CU_MAX)
+};
+
+inline size_t dn_align(size_t b) { return (b + DN_ALIGN - 1) / DN_ALIGN * DN_ALIGN; }
+
+// The LDS window of step s: (64 + 4s) x (4 + 4s) records of colour, and as many of guide when the call has one.
+inline size_t dn_window_bytes(uint32_t s, bool guided) {
+    return (size_t)(DN_TILE_X + 4 * s) * (DN_TILE_Y + 4 * s) * DN_REC * (guided ? 2 : 1);
+}
+
+// W, R >= 1 with W * R < 2^31 (the tile ABI's largest frame; checked by the caller), iterations <= DN_MAX_ITER.  lds_max_step: the
+// largest step staged in LDS (0: none; a window that does not fit DN_LDS_CU gathers through L2 whatever it says).
+inline DenoisePlan plan_denoise(uint32_t W, uint32_t R, uint32_t iterations, bool guided, uint32_t lds_max_step = DN_LDS_MAX_STEP) {
+    DenoisePlan p;
+    p.npix = (uint64_t)W * R;
+    p.tiles_x = (W + DN_TILE_X - 1) / DN_TILE_X;
+    const size_t buf = dn_align((size_t)p.npix * DN_REC);
+    p.off_guide = 0;
+    p.off_color[0] = buf;
+    p.off_color[1] = 2 * buf;
+    p.scratch_bytes = 3 * buf;
+    for (uint32_t i = 0; i < iterations && i < DN_MAX_ITER; i++) {
+        const uint32_t s = 1u << i;
+        p.step[i] = s;
+        const size_t b = dn_window_bytes(s, guided);
+        if (s <= lds_max_step && b <= DN_LDS_CU) {
+            p.lds[i] = b;
+            p.wg_per_cu[i] = (uint32_t)std::min<size_t>(DN_WG_PER_CU_MAX, DN_LDS_CU / b);
+        } else {
+            p.wg_per_cu[i] = DN_WG_PER_CU_MAX;
+        }
+    }
+    return p;
+}
+
 }  // namespace rtplan

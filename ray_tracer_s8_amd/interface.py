@@ -19,7 +19,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _abi
-from ._abi import FrameStats, TileRequest, TileStats, default_request
+from ._abi import DenoiseRequest, FrameStats, TileRequest, TileStats, default_request
 from .dispatch import assemble, strips_for_worker
 
 
@@ -355,6 +355,90 @@ class Scene:
         _abi.check(self._lib.rt_scene_render_aovs_device(self._h, arr, n, begin, end, pl, C.c_void_p(stream) if stream else None),
                    "rt_scene_render_aovs_device")
 
+    def denoise(self, reqs, accum, planes, color_samples: int, aov_samples: int = 1, dreq: Optional[DenoiseRequest] = None,
+                outputs: Sequence[str] = ("rgb", "f32")):
+        """The a-trous denoiser on host buffers (rt_scene_denoise).  reqs: one request or n strips of one frame with consecutive
+        division_no; accum: the strips' progressive sums after [0, color_samples) ((Hs, W, 3) float32 each); planes: the strips'
+        feature-buffer dicts of render_aov (summed over [0, aov_samples); 'index' ignored, any other plane optional, the same set
+        for every strip); dreq: DenoiseRequest (None: the defaults), whose sample counts are set from the arguments; outputs: a
+        non-empty subset of ("rgb", "linear", "f32").  Returns ({output: array}, stats) for one request, ([{...} per strip],
+        stats) for a sequence."""
+        single = isinstance(reqs, TileRequest)
+        reqs = [reqs] if single else list(reqs)
+        accum = [accum] if single else list(accum)
+        planes = [planes] if single else list(planes)
+        n = len(reqs)
+        if len(accum) != n or len(planes) != n:
+            raise ValueError("accum and planes: one entry per request")
+        outs = tuple(outputs)
+        if not outs or any(o not in DENOISE_OUTPUTS for o in outs):
+            raise ValueError(f"outputs: a non-empty subset of {DENOISE_OUTPUTS}, got {outs}")
+        dq = DenoiseRequest.defaults() if dreq is None else DenoiseRequest.from_buffer_copy(dreq)
+        dq.color_samples, dq.aov_samples = color_samples, aov_samples
+        hs = reqs[0].height // max(reqs[0].divisions, 1)
+        shape = (hs, reqs[0].width, 3)
+        acc = [np.ascontiguousarray(a, np.float32) for a in accum]
+        if any(a.shape != shape for a in acc):
+            raise ValueError(f"accum: need arrays of shape {shape}")
+        want = {"albedo": np.float32, "normal": np.float32, "depth": np.float32, "hits": np.uint32}
+        keep = []
+        pl = (_abi.AovPlanes * n)()
+        for i, d in enumerate(planes):
+            ptrs = []
+            for k in _abi.AOV_PLANES:
+                a = (d or {}).get(k)
+                if a is None or k == "index":
+                    ptrs.append(None)
+                    continue
+                a = np.ascontiguousarray(a, want[k])
+                keep.append(a)
+                ptrs.append(a.ctypes.data)
+            pl[i] = _abi.AovPlanes(*ptrs)
+        res = [{} for _ in range(n)]
+        arrays = {}
+        for o in DENOISE_OUTPUTS:
+            if o in outs:
+                for r in res:
+                    r[o] = np.empty(shape, np.uint8 if o == "rgb" else np.float32)
+                arrays[o] = (C.c_void_p * n)(*[r[o].ctypes.data for r in res])
+            else:
+                arrays[o] = None
+        arr = (TileRequest * n)(*reqs)
+        acc_p = (C.c_void_p * n)(*[a.ctypes.data for a in acc])
+        st = TileStats()
+        _abi.check(self._lib.rt_scene_denoise(self._h, arr, n, C.byref(dq), acc_p, pl, arrays["rgb"], shape[0] * shape[1] * 3,
+                                              arrays["f32"], arrays["linear"], C.byref(st)), "rt_scene_denoise")
+        return (res[0] if single else res), st
+
+    def denoise_device(self, reqs: Sequence[TileRequest], dreq: DenoiseRequest, d_accum: Sequence[int], d_planes: Sequence[dict],
+                       d_scratch: int, scratch_bytes: int, *, d_rgb: Optional[Sequence[int]] = None,
+                       d_f32: Optional[Sequence[int]] = None, d_linear: Optional[Sequence[int]] = None, out_len_each: int = 0,
+                       stream: int = 0):
+        """The denoiser on device buffers (rt_scene_denoise_device), asynchronous on `stream`, counters until collect().  d_accum:
+        one device pointer per strip; d_planes[i]: {plane name: device pointer} of strip i (e.g. torch tensors' data_ptr()), the
+        same names for every strip; d_scratch: >= denoise_scratch_bytes(W, n * Hs) bytes; d_rgb / d_f32 / d_linear: None or one
+        device pointer per strip (out_len_each: 0 means Hs * W * 3)."""
+        reqs = list(reqs)
+        n = len(reqs)
+        if len(d_accum) != n or len(d_planes) != n:
+            raise ValueError("d_accum and d_planes: one entry per request")
+        arr = (TileRequest * n)(*reqs)
+        pl = (_abi.AovPlanes * n)(*[_abi.AovPlanes(*[d.get(k) or None for k in _abi.AOV_PLANES]) for d in d_planes])
+
+        def ptrs(a):
+            if a is None:
+                return None
+            if len(a) != n:
+                raise ValueError("output arrays: one device pointer per request")
+            return (C.c_void_p * n)(*[p or None for p in a])
+
+        if not out_len_each:
+            out_len_each = (reqs[0].height // max(reqs[0].divisions, 1)) * reqs[0].width * 3
+        _abi.check(self._lib.rt_scene_denoise_device(self._h, arr, n, C.byref(dreq), (C.c_void_p * n)(*[p or None for p in d_accum]),
+                                                     pl, ptrs(d_rgb), out_len_each, ptrs(d_f32), ptrs(d_linear),
+                                                     C.c_void_p(d_scratch) if d_scratch else None, scratch_bytes,
+                                                     C.c_void_p(stream) if stream else None), "rt_scene_denoise_device")
+
     def collect(self) -> TileStats:
         st = TileStats()
         _abi.check(self._lib.rt_scene_collect(self._h, C.byref(st)), "rt_scene_collect")
@@ -460,6 +544,14 @@ def aov_means(planes: dict, n_samples: int) -> dict:
         if k in planes:
             out[k] = planes[k]
     return out
+
+
+DENOISE_OUTPUTS = ("rgb", "linear", "f32")
+
+
+def denoise_scratch_bytes(width: int, rows: int) -> int:
+    """Device scratch rt_scene_denoise_device needs for an image of width x rows pixels (rt_denoise_scratch_bytes)."""
+    return int(_abi.load().rt_denoise_scratch_bytes(width, rows))
 
 
 class FrameContext:
