@@ -33,7 +33,7 @@ struct AovStrip {
     uint32_t pad;
 };
 
-struct AParams {
+struct AParams : SceneRefs {
     float org[3], llc[3], hor[3], ver[3];   // Camera::new (camera.rs:19-47), host-computed by rtplan::fill_camera
     float lens_radius, focus_distance;
     float u_den, v_den;          // aspect*H_f - 1, H_f - 1 (camera.rs:115-117)
@@ -44,18 +44,7 @@ struct AParams {
     uint32_t s_begin, s_end;     // the samples of this launch
     uint32_t n_strips;
     uint32_t planes;             // AOV_* bits of the planes computed
-    // the scene, as rt_query.hip.h QParams names it (closest_hit, query_root)
-    uint32_t n_sph, n_tri;
-    uint32_t root_ref;
-    uint32_t full_chain;
-    const float4* trav;
-    const float4* bvh_nodes;
-    const uint32_t* leaf_of;
-    const uint32_t* world_rank;
-    const float4* geom_r;        // [n_sph] (cx, cy, cz, radius)
-    const float* tri;            // [9 n_tri]
     const float4* mat;           // [n_sph + n_tri] (albedo r, g, b, roughness)
-    unsigned long long* counters;   // [0] camera rays (ray_segments), [1] exact root tests (broad_candidates)
     AovStrip strips[MAX_BATCH];
 };
 static_assert(sizeof(AParams) <= 4096, "AParams must fit the kernel argument segment");

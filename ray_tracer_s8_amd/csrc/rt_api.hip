@@ -76,6 +76,29 @@ int guarded(F&& body) noexcept {
                                         std::to_string(__LINE__) + ")");                              \
     } while (0)
 
+// A device staging buffer that grows on demand and never shrinks.  Its owner has the device current and no work in flight on the
+// old area when it grows.
+struct DevBuf {
+    char* d = nullptr;
+    size_t cap = 0;   // bytes
+    int reserve(size_t bytes, const char* what) {
+        if (cap >= bytes) return RT_OK;
+        release();
+        if (hipMalloc(&d, bytes) != hipSuccess) {
+            d = nullptr;
+            (void)hipGetLastError();   // (the failure is reported here: it must not stick to the next HIP call)
+            return fail(RT_ERR_OOM, std::string("hipMalloc(") + what + ") failed");
+        }
+        cap = bytes;
+        return RT_OK;
+    }
+    void release() {
+        (void)hipFree(d);
+        d = nullptr;
+        cap = 0;
+    }
+};
+
 struct DeviceCtx {
     int dev = -1;
     hipStream_t stream = nullptr;
@@ -188,24 +211,11 @@ struct rt_scene {
     };
     Ring rings[4];
     uint64_t ring_clock = 0;
-    unsigned long long* d_cost = nullptr;       // per-strip ray segments of the host-buffer batched call (frame context)
-    size_t d_cost_cap = 0;
-    // staging for the host-buffer entry point (grown on demand)
-    uint8_t* d_out = nullptr;
-    size_t d_out_cap = 0;
-    float* d_outf = nullptr;
-    size_t d_outf_cap = 0;
-    float* d_acc = nullptr;             // ... and for the running sums of rt_scene_render_tile_pass
-    size_t d_acc_cap = 0;
-    void* d_rays = nullptr;             // ... and for the rays and hits of rt_scene_intersect
-    void* d_hits = nullptr;
-    size_t d_query_cap = 0;             //   rays (= hits) each buffer holds
-    char* d_trace = nullptr;            // ... and for rt_scene_trace: rays, RNG states, colours, segments (80 bytes a ray)
-    size_t d_trace_cap = 0;             //   rays it holds
-    char* d_aov = nullptr;              // ... and for the planes of rt_scene_render_aov (36 bytes a pixel)
-    size_t d_aov_cap = 0;               //   bytes
-    char* d_dn = nullptr;               // ... and for rt_scene_denoise: the filter's scratch, the strips' inputs and outputs
-    size_t d_dn_cap = 0;                //   bytes
+    // staging of the host-buffer entry points (grown on demand): the strips' bytes, their f32 twins, the running sums of
+    // rt_scene_render_tile_pass and the per-strip ray segments of the batched call (frame context); the rays and hits of
+    // rt_scene_intersect; rays, RNG states, colours and segments of rt_scene_trace (80 bytes a ray); the planes of rt_scene_render_aov
+    // (36 bytes a pixel); the filter's scratch and the strips' inputs and outputs of rt_scene_denoise
+    DevBuf d_out, d_outf, d_acc, d_cost, d_query, d_trace, d_aov, d_dn;
     // HIP-event bookkeeping of launches not yet collected
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, free_ev;
     uint64_t primary_rays = 0;
@@ -251,6 +261,55 @@ constexpr uint32_t COUNTER_WORDS = 4 + QUEUE_SLOTS + 16 * 8192;      // (+ one b
 #else
 constexpr uint32_t COUNTER_WORDS = 4 + QUEUE_SLOTS;
 #endif
+
+int check_slot(const rt_scene* sc) {
+    if (sc->pending.size() >= QUEUE_SLOTS) return fail(RT_ERR_LIMIT, "too many uncollected launches: call rt_scene_collect()");
+    return RT_OK;
+}
+
+// Enqueue one kernel launch on `stream`, between a pair of events that collect_locked times it by.  Every launch_* goes through
+// here.  Caller holds sc->mu and has the device current.
+template <class P>
+int enqueue(rt_scene* sc, hipStream_t stream, void (*kern)(const P), uint32_t blocks, uint32_t block, size_t lds, const P& p) {
+    EvPair ev;
+    int rc;
+    if ((rc = check_slot(sc)) || (rc = get_events(sc, ev))) return rc;
+    HIPCHK(hipEventRecord(ev.a, stream));
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(block), lds, stream, p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev.b, stream));
+    sc->pending.push_back({ev.a, ev.b});
+    return RT_OK;
+}
+
+// The grid of a persistent kernel: as many workgroups as the chip holds at this block size and dynamic LDS (per_cu of them a
+// CU, at least one), and no more than it takes to give each of the `items` a lane.
+struct Grid {
+    uint32_t blocks = 0;
+    int per_cu = 0;
+};
+template <class P>
+int persistent_blocks(const rt_scene* sc, void (*kern)(const P), uint32_t block, size_t lds, uint64_t items, Grid& g) {
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&g.per_cu, kern, (int)block, lds));
+    if (g.per_cu < 1) g.per_cu = 1;
+    g.blocks = (uint32_t)std::min<uint64_t>((items + block - 1) / block, (uint64_t)sc->ctx->n_cu * (uint32_t)g.per_cu);
+    return RT_OK;
+}
+
+// The scene as the first-hit kernels read it (rt_query.hip.h SceneRefs), into their parameter block.
+void scene_refs(const rt_scene* sc, bool full_chain, rtk::SceneRefs& r) {
+    r.n_sph = sc->shape.n_sph;
+    r.n_tri = sc->shape.n_tri;
+    r.root_ref = sc->shape.root_ref;
+    r.full_chain = full_chain ? 1u : 0u;
+    r.trav = sc->d_trav;
+    r.bvh_nodes = sc->d_bvh;
+    r.leaf_of = sc->d_leaf_of;
+    r.world_rank = sc->has_order ? sc->d_world_rank : nullptr;
+    r.geom_r = sc->d_geom_r;
+    r.tri = sc->d_tri;
+    r.counters = sc->d_counters;
+}
 
 bool same_frame(const rt_tile_request& a, const rt_tile_request& b) {
     return a.width == b.width && a.height == b.height && a.divisions == b.divisions && a.spp == b.spp &&
@@ -356,10 +415,10 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
         p.strips[i].acc = pass ? (float*)pass->d_acc[i] : nullptr;
         p.strips[i].y0 = p.Hs * rqs[i].division_no;
     }
-    const uint32_t slot = (uint32_t)sc->pending.size();
-    if (slot >= QUEUE_SLOTS) return fail(RT_ERR_LIMIT, "too many uncollected launches: call rt_scene_collect()");
+    int rc = check_slot(sc);               // (here already: the slot is the launch's queue head)
+    if (rc) return rc;
     p.counters = sc->d_counters;
-    p.queue = sc->d_counters + 4 + slot;
+    p.queue = sc->d_counters + 4 + sc->pending.size();
     p.strip_cost = dbg(DBG_STRIP_COST) ? d_strip_cost : nullptr;
 
     // persistent grid: as many workgroups as the chip holds at this LDS/VGPR budget
@@ -373,35 +432,25 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
     rtplan::plan_queue(pl, (uint32_t)sc->ctx->n_cu * (uint32_t)per_cu, kn, p);
     p.stack_ovf = nullptr;
     if (pl.capped) {
-        int rc = acquire_stack_ovf(sc, pl.ovf_words);
-        if (rc) return rc;
+        if ((rc = acquire_stack_ovf(sc, pl.ovf_words))) return rc;
         p.stack_ovf = sc->d_stack_ovf;
     }
     if (dbg(DBG_VERBOSE))
         fprintf(stderr, "[rt] sample-unit ring %zu B: %u units per pixel, %u slots of %u records per wave\n", pl.ring_bytes, p.upp, p.n_slots,
                 p.slot_stride);
     rt_scene::Ring* rg = nullptr;
-    int rc = acquire_ring(sc, stream, pl.ring_bytes, rg);
-    if (rc) return rc;
+    if ((rc = acquire_ring(sc, stream, pl.ring_bytes, rg))) return rc;
     p.ring = rg->d;
-    dim3 grid(pl.blocks), block(pl.block);
-    EvPair ev;
-    rc = get_events(sc, ev);
-    if (rc) return rc;
     if (p.stack_ovf) {
         if (sc->ovf_done) HIPCHK(hipStreamWaitEvent(stream, sc->ovf_done, 0));
         else HIPCHK(hipEventCreateWithFlags(&sc->ovf_done, hipEventDisableTiming));
     }
     HIPCHK(hipMemsetAsync(p.queue, 0, sizeof(unsigned long long), stream));
-    HIPCHK(hipEventRecord(ev.a, stream));
     sc->last_engine = (uint32_t)pl.engine;
     sc->last_form = pl.expanded ? 1u : 0u;
-    hipLaunchKernelGGL(kern, grid, block, pl.lds, stream, p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev.b, stream));
+    if ((rc = enqueue(sc, stream, kern, pl.blocks, pl.block, pl.lds, p))) return rc;
     HIPCHK(hipEventRecord(rg->done, stream));
     if (p.stack_ovf) HIPCHK(hipEventRecord(sc->ovf_done, stream));
-    sc->pending.push_back({ev.a, ev.b});
     sc->primary_rays += (uint64_t)p.Hs * p.W * p.upp * n;
     return RT_OK;
 }
@@ -438,6 +487,58 @@ int collect_locked(rt_scene* sc, rt_tile_stats* st) {
     sc->h2d_ms = 0.f;
     return RT_OK;
 }
+
+// The skeleton of a synchronous host-buffer call on the scene's stream: uploads, the call's launches, downloads, each phase
+// timed; the stats are the call's own.  Made under sc->ctx->mu and sc->mu with the device current.  The entry point checks its
+// arguments and reserves its staging, then: begin(), upload, uploads_done(), launch_*, kernels_done(), download, finish().
+// However it returns, the events go back to the scene, the scene's upload time stays for the next tile call, and an error return
+// waits for the stream: what is already enqueued writes into caller memory.
+struct StagedCall {
+    rt_scene* const sc;
+    const hipStream_t st;
+    const float scene_h2d_ms;
+    EvPair up{nullptr, nullptr}, down{nullptr, nullptr};
+    bool finished = false;
+    explicit StagedCall(rt_scene* s) : sc(s), st(s->ctx->stream), scene_h2d_ms(s->h2d_ms) {}
+    StagedCall(const StagedCall&) = delete;
+    ~StagedCall() {
+        if (!finished) (void)hipStreamSynchronize(st);
+        if (up.b) sc->free_ev.push_back({up.a, up.b});
+        if (down.b) sc->free_ev.push_back({down.a, down.b});
+        sc->h2d_ms = scene_h2d_ms;
+    }
+    // settles anything enqueued earlier; the upload phase begins
+    int begin() {
+        int rc;
+        if ((rc = collect_locked(sc, nullptr)) || (rc = get_events(sc, up)) || (rc = get_events(sc, down))) return rc;
+        HIPCHK(hipEventRecord(up.a, st));
+        return RT_OK;
+    }
+    int uploads_done() {
+        HIPCHK(hipEventRecord(up.b, st));
+        return RT_OK;
+    }
+    int kernels_done() {
+        HIPCHK(hipEventRecord(down.a, st));
+        return RT_OK;
+    }
+    // waits for the downloads; *stats (optional): the call's launches, with its upload and download times
+    int finish(rt_tile_stats* stats) {
+        HIPCHK(hipEventRecord(down.b, st));
+        HIPCHK(hipEventSynchronize(down.b));
+        finished = true;
+        rt_tile_stats s;
+        float h2d = 0.f, d2h = 0.f;
+        HIPCHK(hipEventElapsedTime(&h2d, up.a, up.b));
+        HIPCHK(hipEventElapsedTime(&d2h, down.a, down.b));
+        int rc = collect_locked(sc, &s);
+        if (rc) return rc;
+        s.h2d_ms = h2d;
+        s.d2h_ms = d2h;
+        if (stats) *stats = s;
+        return RT_OK;
+    }
+};
 
 }  // namespace
 
@@ -1025,15 +1126,7 @@ static int rt_scene_destroy_impl(rt_scene* sc) {
     (void)hipFree(sc->d_leaf_of);
     (void)hipFree(sc->d_world_rank);
     (void)hipFree(sc->d_counters);
-    (void)hipFree(sc->d_out);
-    (void)hipFree(sc->d_outf);
-    (void)hipFree(sc->d_acc);
-    (void)hipFree(sc->d_rays);
-    (void)hipFree(sc->d_hits);
-    (void)hipFree(sc->d_trace);
-    (void)hipFree(sc->d_aov);
-    (void)hipFree(sc->d_dn);
-    (void)hipFree(sc->d_cost);
+    for (DevBuf* b : {&sc->d_out, &sc->d_outf, &sc->d_acc, &sc->d_cost, &sc->d_query, &sc->d_trace, &sc->d_aov, &sc->d_dn}) b->release();
     delete sc;
     g_live_scenes.fetch_sub(1);
     return RT_OK;
@@ -1050,14 +1143,25 @@ static int check_batch(const rt_tile_request* rqs, uint32_t n) {
     return RT_OK;
 }
 
-// a progressive pass's own arguments (after check_batch): 0 <= begin < end <= spp, a running sum per strip
-static int check_pass(const rt_tile_request* rqs, uint32_t n, uint32_t begin, uint32_t end, const void* const* acc) {
+// a sample range of a request: 0 <= begin < end <= spp
+static int check_samples(uint32_t begin, uint32_t end, uint32_t spp) {
     if (begin >= end) return fail(RT_ERR_BAD_ARG, "sample_begin >= sample_end");
-    if (end > rqs[0].spp) return fail(RT_ERR_BAD_ARG, "sample_end > spp");
-    if (!acc) return fail(RT_ERR_BAD_ARG, "accum is NULL");
-    for (uint32_t i = 0; i < n; i++)
-        if (!acc[i]) return fail(RT_ERR_BAD_ARG, "accum[i] is NULL");
+    if (end > spp) return fail(RT_ERR_BAD_ARG, "sample_end > spp");
     return RT_OK;
+}
+
+// a required array of n non-NULL entries
+static int check_array(const void* const* a, uint32_t n, const char* what) {
+    if (!a) return fail(RT_ERR_BAD_ARG, std::string(what) + " is NULL");
+    for (uint32_t i = 0; i < n; i++)
+        if (!a[i]) return fail(RT_ERR_BAD_ARG, std::string(what) + "[i] is NULL");
+    return RT_OK;
+}
+
+// a progressive pass's own arguments (after check_batch): its sample range, a running sum per strip
+static int check_pass(const rt_tile_request* rqs, uint32_t n, const Pass& pass) {
+    int rc = check_samples(pass.begin, pass.end, rqs[0].spp);
+    return rc ? rc : check_array(pass.d_acc, n, "accum");
 }
 
 // pass: nullptr, or a progressive pass whose d_acc holds one device sum per request (checked here)
@@ -1067,11 +1171,9 @@ static int rt_scene_render_tiles_device_impl(rt_scene* sc, const rt_tile_request
     if (!sc) return fail(RT_ERR_BAD_ARG, "scene is NULL");
     int rc = check_batch(rqs, n);
     if (rc) return rc;
-    if (!d_out_rgb) return fail(RT_ERR_BAD_ARG, "d_out_rgb is NULL");
-    for (uint32_t i = 0; i < n; i++)
-        if (!d_out_rgb[i]) return fail(RT_ERR_BAD_ARG, "d_out_rgb[i] is NULL");
+    if ((rc = check_array(d_out_rgb, n, "d_out_rgb"))) return rc;
     if (out_len_each < rt_tile_bytes(&rqs[0])) return fail(RT_ERR_BUFFER_TOO_SMALL, "out_len < (H/div)*W*3");
-    if (pass && (rc = check_pass(rqs, n, pass->begin, pass->end, pass->d_acc))) return rc;
+    if (pass && (rc = check_pass(rqs, n, *pass))) return rc;
     std::lock_guard<std::mutex> lk(sc->mu);
     HIPCHK(hipSetDevice(sc->ctx->dev));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream;
@@ -1108,12 +1210,10 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
     if (!sc) return fail(RT_ERR_BAD_ARG, "scene is NULL");
     int rc = check_batch(rqs, n);
     if (rc) return rc;
-    if (!out_rgb) return fail(RT_ERR_BAD_ARG, "out_rgb is NULL");
-    for (uint32_t i = 0; i < n; i++)
-        if (!out_rgb[i]) return fail(RT_ERR_BAD_ARG, "out_rgb[i] is NULL");
+    if ((rc = check_array((const void* const*)out_rgb, n, "out_rgb"))) return rc;
     const size_t need = rt_tile_bytes(&rqs[0]);
     if (out_len_each < need) return fail(RT_ERR_BUFFER_TOO_SMALL, "out_len < (H/div)*W*3");
-    if (pass && (rc = check_pass(rqs, n, pass->begin, pass->end, pass->d_acc))) return rc;
+    if (pass && (rc = check_pass(rqs, n, *pass))) return rc;
     bool want_f32 = false;
     if (out_f32)
         for (uint32_t i = 0; i < n; i++) want_f32 |= out_f32[i] != nullptr;
@@ -1121,42 +1221,18 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
     std::lock_guard<std::mutex> lk(sc->mu);
     HIPCHK(hipSetDevice(sc->ctx->dev));
     hipStream_t st = sc->ctx->stream;
-    if (sc->d_out_cap < need * n) {
-        (void)hipFree(sc->d_out);
-        sc->d_out = nullptr;
-        sc->d_out_cap = 0;
-        hipError_t e = hipMalloc(&sc->d_out, need * n);
-        if (e != hipSuccess) return fail(RT_ERR_OOM, "hipMalloc(strips) failed");
-        sc->d_out_cap = need * n;
-    }
-    if (want_f32 && sc->d_outf_cap < need * n * sizeof(float)) {
-        (void)hipFree(sc->d_outf);
-        sc->d_outf = nullptr;
-        sc->d_outf_cap = 0;
-        hipError_t e = hipMalloc(&sc->d_outf, need * n * sizeof(float));
-        if (e != hipSuccess) return fail(RT_ERR_OOM, "hipMalloc(strips f32) failed");
-        sc->d_outf_cap = need * n * sizeof(float);
-    }
-    if (pass && sc->d_acc_cap < need * n * sizeof(float)) {
-        (void)hipFree(sc->d_acc);
-        sc->d_acc = nullptr;
-        sc->d_acc_cap = 0;
-        hipError_t e = hipMalloc(&sc->d_acc, need * n * sizeof(float));
-        if (e != hipSuccess) return fail(RT_ERR_OOM, "hipMalloc(running sums) failed");
-        sc->d_acc_cap = need * n * sizeof(float);
-    }
+    if ((rc = sc->d_out.reserve(need * n, "strips")) || (want_f32 && (rc = sc->d_outf.reserve(need * n * sizeof(float), "strips f32"))) ||
+        (pass && (rc = sc->d_acc.reserve(need * n * sizeof(float), "running sums"))))
+        return rc;
     // per-strip costs: one block of COST_COPIES x MAX_BATCH counters per launch group of the call
     constexpr size_t COST_BLOCK = (size_t)rtk::COST_COPIES * rtk::MAX_BATCH;
     const size_t cost_blocks = strip_cost_out ? (n + rtk::MAX_BATCH - 1) / rtk::MAX_BATCH + 1 : 0;
+    unsigned long long* d_cost = nullptr;
     if (strip_cost_out) {
-        if (sc->d_cost_cap < cost_blocks * COST_BLOCK) {
-            (void)hipFree(sc->d_cost);
-            sc->d_cost = nullptr;
-            sc->d_cost_cap = 0;
-            if (hipMalloc(&sc->d_cost, cost_blocks * COST_BLOCK * sizeof(unsigned long long)) != hipSuccess) return fail(RT_ERR_OOM, "hipMalloc(strip costs) failed");
-            sc->d_cost_cap = cost_blocks * COST_BLOCK;
-        }
-        HIPCHK(hipMemsetAsync(sc->d_cost, 0, cost_blocks * COST_BLOCK * sizeof(unsigned long long), st));
+        const size_t cost_b = cost_blocks * COST_BLOCK * sizeof(unsigned long long);
+        if ((rc = sc->d_cost.reserve(cost_b, "strip costs"))) return rc;
+        d_cost = (unsigned long long*)sc->d_cost.d;
+        HIPCHK(hipMemsetAsync(d_cost, 0, cost_b, st));
     }
     // settle anything enqueued earlier so the stats of this call are its own
     rt_tile_stats prev;
@@ -1165,9 +1241,9 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
     sc->h2d_ms = prev.h2d_ms;
     std::vector<void*> drgb(n), df32(n), dacc(pass ? n : 0);
     for (uint32_t i = 0; i < n; i++) {
-        drgb[i] = sc->d_out + need * i;
-        df32[i] = (want_f32 && out_f32[i]) ? (void*)(sc->d_outf + need * i) : nullptr;
-        if (pass) dacc[i] = sc->d_acc + need * i;
+        drgb[i] = sc->d_out.d + need * i;
+        df32[i] = (want_f32 && out_f32[i]) ? sc->d_outf.d + need * i * sizeof(float) : nullptr;
+        if (pass) dacc[i] = sc->d_acc.d + need * i * sizeof(float);
     }
     // Launch groups: the last quarter of the strips goes out as its own launch, so that the D2H copies of the strips
     // before it (copy stream) run under it and only the last group's copies are exposed (d2h_ms = that exposed part).
@@ -1214,7 +1290,7 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
         Pass part = {};
         if (pass) part = {pass->begin, pass->end, dacc.data() + i0};
         rc = launch_batch(sc, rqs + i0, m, drgb.data() + i0, want_f32 ? df32.data() + i0 : nullptr, st,
-                          strip_cost_out ? sc->d_cost + g * COST_BLOCK : nullptr, pass ? &part : nullptr);
+                          d_cost ? d_cost + g * COST_BLOCK : nullptr, pass ? &part : nullptr);
         if (rc) return rc;
         HIPCHK(hipEventRecord(gev[g].a, st));
     }
@@ -1229,7 +1305,7 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
     std::vector<unsigned long long> cost_raw;
     if (strip_cost_out) {
         cost_raw.resize(groups.size() * COST_BLOCK);
-        HIPCHK(hipMemcpyAsync(cost_raw.data(), sc->d_cost, cost_raw.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
+        HIPCHK(hipMemcpyAsync(cost_raw.data(), d_cost, cost_raw.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
     }
     HIPCHK(hipEventRecord(gev.back().b, cs));
     HIPCHK(hipEventSynchronize(gev.back().b));
@@ -1285,8 +1361,7 @@ static int check_query(rt_scene* sc, const void* rays, uint32_t n, uint32_t mode
 
 // Enqueue one query launch on `stream` (caller holds sc->mu, device current): persistent waves over the n rays.
 static int launch_query(rt_scene* sc, const void* d_rays, uint32_t n, uint32_t mode, uint32_t flags, void* d_hits, hipStream_t stream) {
-    const rtplan::SceneShape& sh = sc->shape;
-    const rtplan::QueryPlan qp = rtplan::plan_query(sh, flags);
+    const rtplan::QueryPlan qp = rtplan::plan_query(sc->shape, flags);
     const rtk::QueryFn kern = rtk::query_kernel(qp.engine, qp.scan_mode, mode == RT_QUERY_ANY);
     if (!kern) return fail(RT_ERR_HIP, "no query kernel for this plan");
     rtk::QParams p;
@@ -1294,34 +1369,14 @@ static int launch_query(rt_scene* sc, const void* d_rays, uint32_t n, uint32_t m
     p.rays = (const float4*)d_rays;
     p.hits = (uint4*)d_hits;
     p.n = n;
-    p.n_sph = sh.n_sph;
-    p.n_tri = sh.n_tri;
-    p.root_ref = sh.root_ref;
-    p.full_chain = qp.full_chain ? 1u : 0u;
-    p.trav = sc->d_trav;
-    p.bvh_nodes = sc->d_bvh;
-    p.leaf_of = sc->d_leaf_of;
-    p.world_rank = sc->has_order ? sc->d_world_rank : nullptr;
-    p.geom_r = sc->d_geom_r;
-    p.tri = sc->d_tri;
-    p.counters = sc->d_counters;
-    if (sc->pending.size() >= QUEUE_SLOTS) return fail(RT_ERR_LIMIT, "too many uncollected launches: call rt_scene_collect()");
-    int per_cu = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, rtplan::QUERY_BLOCK, qp.lds));
-    if (per_cu < 1) per_cu = 1;
-    const uint64_t useful = ((uint64_t)n + rtplan::QUERY_BLOCK - 1) / rtplan::QUERY_BLOCK;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(useful, (uint64_t)sc->ctx->n_cu * (uint32_t)per_cu);
+    scene_refs(sc, qp.full_chain, p);
+    Grid g;
+    int rc = persistent_blocks(sc, kern, rtplan::QUERY_BLOCK, qp.lds, n, g);
+    if (rc) return rc;
     if (dbg(DBG_VERBOSE))
         fprintf(stderr, "[rt] query: engine %d  scan mode %d  %s  lds %zu B  workgroups/CU %d  rays %u\n", qp.engine, qp.scan_mode,
-                mode == RT_QUERY_ANY ? "any" : "closest", qp.lds, per_cu, n);
-    EvPair ev;
-    int rc = get_events(sc, ev);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(ev.a, stream));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(rtplan::QUERY_BLOCK), qp.lds, stream, p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev.b, stream));
-    sc->pending.push_back({ev.a, ev.b});
+                mode == RT_QUERY_ANY ? "any" : "closest", qp.lds, g.per_cu, n);
+    if ((rc = enqueue(sc, stream, kern, g.blocks, rtplan::QUERY_BLOCK, qp.lds, p))) return rc;
     sc->primary_rays += n;
     sc->last_engine = (uint32_t)qp.engine;
     sc->last_form = 0;
@@ -1344,57 +1399,17 @@ static int rt_scene_intersect_impl(rt_scene* sc, const rt_ray* rays, uint32_t n,
     std::lock_guard<std::mutex> dl(sc->ctx->mu);
     std::lock_guard<std::mutex> lk(sc->mu);
     HIPCHK(hipSetDevice(sc->ctx->dev));
-    hipStream_t st = sc->ctx->stream;
-    const size_t bytes = (size_t)n * sizeof(rt_ray);
-    if (sc->d_query_cap < n) {
-        (void)hipFree(sc->d_rays);
-        (void)hipFree(sc->d_hits);
-        sc->d_rays = sc->d_hits = nullptr;
-        sc->d_query_cap = 0;
-        if (hipMalloc(&sc->d_rays, bytes) != hipSuccess || hipMalloc(&sc->d_hits, n * sizeof(rt_hit)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(RT_ERR_OOM, "hipMalloc(rays / hits) failed");
-        }
-        sc->d_query_cap = n;
-    }
-    // settle anything enqueued earlier so the stats of this call are its own (the scene's upload time stays for the next tile call)
-    rt_tile_stats prev;
-    rc = collect_locked(sc, &prev);
-    if (rc) return rc;
-    EvPair up, down;
-    if ((rc = get_events(sc, up)) || (rc = get_events(sc, down))) return rc;
-    struct EvReturn {
-        rt_scene* sc;
-        EvPair a, b;
-        hipStream_t st;
-        bool ok = false;
-        ~EvReturn() {
-            if (!ok) (void)hipStreamSynchronize(st);       // (an error return waits for what already writes into caller memory)
-            sc->free_ev.push_back({a.a, a.b});
-            sc->free_ev.push_back({b.a, b.b});
-        }
-    } ev_return{sc, up, down, st};
-    HIPCHK(hipEventRecord(up.a, st));
-    HIPCHK(hipMemcpyAsync(sc->d_rays, rays, bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(up.b, st));
-    rc = launch_query(sc, sc->d_rays, n, mode, flags, sc->d_hits, st);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(down.a, st));
-    HIPCHK(hipMemcpyAsync(hits, sc->d_hits, n * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(down.b, st));
-    HIPCHK(hipEventSynchronize(down.b));
-    ev_return.ok = true;
-    float h2d = 0.f, d2h = 0.f;
-    HIPCHK(hipEventElapsedTime(&h2d, up.a, up.b));
-    HIPCHK(hipEventElapsedTime(&d2h, down.a, down.b));
-    rt_tile_stats s;
-    rc = collect_locked(sc, &s);
-    if (rc) return rc;
-    sc->h2d_ms = prev.h2d_ms;
-    s.h2d_ms = h2d;
-    s.d2h_ms = d2h;
-    if (stats) *stats = s;
-    return RT_OK;
+    // one device buffer: the rays, then the hits (32 B each per ray)
+    const size_t ray_b = (size_t)n * sizeof(rt_ray), hit_b = (size_t)n * sizeof(rt_hit);
+    if ((rc = sc->d_query.reserve(ray_b + hit_b, "rays / hits"))) return rc;
+    char* const d_rays = sc->d_query.d;
+    char* const d_hits = d_rays + ray_b;
+    StagedCall call(sc);
+    if ((rc = call.begin())) return rc;
+    HIPCHK(hipMemcpyAsync(d_rays, rays, ray_b, hipMemcpyHostToDevice, call.st));
+    if ((rc = call.uploads_done()) || (rc = launch_query(sc, d_rays, n, mode, flags, d_hits, call.st)) || (rc = call.kernels_done())) return rc;
+    HIPCHK(hipMemcpyAsync(hits, d_hits, hit_b, hipMemcpyDeviceToHost, call.st));
+    return call.finish(stats);
 }
 
 // ---- path tracing of caller rays (rt_tile.h "path tracing of caller rays", rt_trace.hip.h) ---------------------------------------
@@ -1413,8 +1428,7 @@ static int check_trace(rt_scene* sc, const rt_trace_request* rq, const void* ray
 // Enqueue one trace launch on `stream` (caller holds sc->mu, device current): persistent waves over the n rays.
 static int launch_trace(rt_scene* sc, const rt_trace_request* rq, const void* d_rays, uint32_t n, void* d_state, void* d_rgb,
                         void* d_segs, hipStream_t stream) {
-    const rtplan::SceneShape& sh = sc->shape;
-    const rtplan::TracePlan tp = rtplan::plan_trace(sh, rq->flags, rq->max_bounces);
+    const rtplan::TracePlan tp = rtplan::plan_trace(sc->shape, rq->flags, rq->max_bounces);
     const rtk::TraceFn kern = rtk::trace_kernel(tp.engine, tp.scan_mode);
     if (!kern) return fail(RT_ERR_HIP, "no trace kernel for this plan");
     rtk::TParams p;
@@ -1430,36 +1444,16 @@ static int launch_trace(rt_scene* sc, const rt_trace_request* rq, const void* d_
     p.as_given = rq->ray_form == RT_TRACE_RAY_AS_GIVEN ? 1u : 0u;
     p.path32 = tp.path32 ? 1u : 0u;
     p.lds_path_off = (uint32_t)tp.lds_path_off;
-    p.n_sph = sh.n_sph;
-    p.n_tri = sh.n_tri;
-    p.root_ref = sh.root_ref;
-    p.full_chain = tp.full_chain ? 1u : 0u;
-    p.trav = sc->d_trav;
-    p.bvh_nodes = sc->d_bvh;
-    p.leaf_of = sc->d_leaf_of;
-    p.world_rank = sc->has_order ? sc->d_world_rank : nullptr;
-    p.geom_r = sc->d_geom_r;
-    p.tri = sc->d_tri;
+    scene_refs(sc, tp.full_chain, p);
     p.mat = sc->d_mat;
     p.emis = sc->d_emis;
-    p.counters = sc->d_counters;
-    if (sc->pending.size() >= QUEUE_SLOTS) return fail(RT_ERR_LIMIT, "too many uncollected launches: call rt_scene_collect()");
-    int per_cu = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, (int)tp.block, tp.lds));
-    if (per_cu < 1) per_cu = 1;
-    const uint64_t useful = ((uint64_t)n + tp.block - 1) / tp.block;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(useful, (uint64_t)sc->ctx->n_cu * (uint32_t)per_cu);
+    Grid g;
+    int rc = persistent_blocks(sc, kern, tp.block, tp.lds, n, g);
+    if (rc) return rc;
     if (dbg(DBG_VERBOSE))
         fprintf(stderr, "[rt] trace: engine %d  scan mode %d  block %u  lds %zu B (path %s)  workgroups/CU %d  rays %u  spp %u  bounces %u\n",
-                tp.engine, tp.scan_mode, tp.block, tp.lds, tp.path32 ? "u32" : "u16", per_cu, n, rq->spp, rq->max_bounces);
-    EvPair ev;
-    int rc = get_events(sc, ev);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(ev.a, stream));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(tp.block), tp.lds, stream, p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev.b, stream));
-    sc->pending.push_back({ev.a, ev.b});
+                tp.engine, tp.scan_mode, tp.block, tp.lds, tp.path32 ? "u32" : "u16", g.per_cu, n, rq->spp, rq->max_bounces);
+    if ((rc = enqueue(sc, stream, kern, g.blocks, tp.block, tp.lds, p))) return rc;
     sc->primary_rays += (uint64_t)n * rq->spp;
     sc->last_engine = (uint32_t)tp.engine;
     sc->last_form = 0;
@@ -1482,65 +1476,26 @@ static int rt_scene_trace_impl(rt_scene* sc, const rt_trace_request* rq, const r
     std::lock_guard<std::mutex> dl(sc->ctx->mu);
     std::lock_guard<std::mutex> lk(sc->mu);
     HIPCHK(hipSetDevice(sc->ctx->dev));
-    hipStream_t st = sc->ctx->stream;
     // one device buffer: rays (32 B), states (32 B), colours (12 B), segments (4 B) per ray
     const size_t ray_b = (size_t)n * sizeof(rt_ray), state_b = (size_t)n * 4 * sizeof(uint64_t), rgb_b = (size_t)n * 3 * sizeof(float),
                  seg_b = (size_t)n * sizeof(uint32_t);
-    if (sc->d_trace_cap < n) {
-        (void)hipFree(sc->d_trace);
-        sc->d_trace = nullptr;
-        sc->d_trace_cap = 0;
-        if (hipMalloc(&sc->d_trace, ray_b + state_b + rgb_b + seg_b) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(RT_ERR_OOM, "hipMalloc(trace buffers) failed");
-        }
-        sc->d_trace_cap = n;
-    }
-    char* const d_rays = sc->d_trace;
+    if ((rc = sc->d_trace.reserve(ray_b + state_b + rgb_b + seg_b, "trace buffers"))) return rc;
+    char* const d_rays = sc->d_trace.d;
     char* const d_state = d_rays + ray_b;
     char* const d_rgb = d_state + state_b;
     char* const d_segs = d_rgb + rgb_b;
-    // settle anything enqueued earlier so the stats of this call are its own (the scene's upload time stays for the next tile call)
-    rt_tile_stats prev;
-    rc = collect_locked(sc, &prev);
-    if (rc) return rc;
-    EvPair up, down;
-    if ((rc = get_events(sc, up)) || (rc = get_events(sc, down))) return rc;
-    struct EvReturn {
-        rt_scene* sc;
-        EvPair a, b;
-        hipStream_t st;
-        bool ok = false;
-        ~EvReturn() {
-            if (!ok) (void)hipStreamSynchronize(st);       // (an error return waits for what already writes into caller memory)
-            sc->free_ev.push_back({a.a, a.b});
-            sc->free_ev.push_back({b.a, b.b});
-        }
-    } ev_return{sc, up, down, st};
-    HIPCHK(hipEventRecord(up.a, st));
-    HIPCHK(hipMemcpyAsync(d_rays, rays, ray_b, hipMemcpyHostToDevice, st));
-    if (rng_state) HIPCHK(hipMemcpyAsync(d_state, rng_state, state_b, hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(up.b, st));
-    rc = launch_trace(sc, rq, d_rays, n, rng_state ? d_state : nullptr, d_rgb, segs ? d_segs : nullptr, st);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(down.a, st));
-    HIPCHK(hipMemcpyAsync(rgb, d_rgb, rgb_b, hipMemcpyDeviceToHost, st));
-    if (segs) HIPCHK(hipMemcpyAsync(segs, d_segs, seg_b, hipMemcpyDeviceToHost, st));
-    if (rng_state) HIPCHK(hipMemcpyAsync(rng_state, d_state, state_b, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(down.b, st));
-    HIPCHK(hipEventSynchronize(down.b));
-    ev_return.ok = true;
-    float h2d = 0.f, d2h = 0.f;
-    HIPCHK(hipEventElapsedTime(&h2d, up.a, up.b));
-    HIPCHK(hipEventElapsedTime(&d2h, down.a, down.b));
-    rt_tile_stats s;
-    rc = collect_locked(sc, &s);
-    if (rc) return rc;
-    sc->h2d_ms = prev.h2d_ms;
-    s.h2d_ms = h2d;
-    s.d2h_ms = d2h;
-    if (stats) *stats = s;
-    return RT_OK;
+    StagedCall call(sc);
+    if ((rc = call.begin())) return rc;
+    HIPCHK(hipMemcpyAsync(d_rays, rays, ray_b, hipMemcpyHostToDevice, call.st));
+    if (rng_state) HIPCHK(hipMemcpyAsync(d_state, rng_state, state_b, hipMemcpyHostToDevice, call.st));
+    if ((rc = call.uploads_done()) ||
+        (rc = launch_trace(sc, rq, d_rays, n, rng_state ? d_state : nullptr, d_rgb, segs ? d_segs : nullptr, call.st)) ||
+        (rc = call.kernels_done()))
+        return rc;
+    HIPCHK(hipMemcpyAsync(rgb, d_rgb, rgb_b, hipMemcpyDeviceToHost, call.st));
+    if (segs) HIPCHK(hipMemcpyAsync(segs, d_segs, seg_b, hipMemcpyDeviceToHost, call.st));
+    if (rng_state) HIPCHK(hipMemcpyAsync(rng_state, d_state, state_b, hipMemcpyDeviceToHost, call.st));
+    return call.finish(stats);
 }
 
 // ---- feature buffers of a strip (rt_tile.h "feature buffers", rt_aov.hip.h) -----------------------------------------------------
@@ -1555,8 +1510,7 @@ static int check_aov(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint3
     if (!sc) return fail(RT_ERR_BAD_ARG, "scene is NULL");
     int rc = check_batch(rqs, n);
     if (rc) return rc;
-    if (begin >= end) return fail(RT_ERR_BAD_ARG, "sample_begin >= sample_end");
-    if (end > rqs[0].spp) return fail(RT_ERR_BAD_ARG, "sample_end > spp");
+    if ((rc = check_samples(begin, end, rqs[0].spp))) return rc;
     if (!planes) return fail(RT_ERR_BAD_ARG, "planes is NULL");
     *mask = aov_mask(planes[0]);
     if (*mask == 0) return fail(RT_ERR_BAD_ARG, "every plane is NULL");
@@ -1569,8 +1523,7 @@ static int check_aov(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint3
 // over (strip, pixel).
 static int launch_aov(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint32_t begin, uint32_t end, const rt_aov_planes* d_planes,
                       uint32_t mask, hipStream_t stream) {
-    const rtplan::SceneShape& sh = sc->shape;
-    const rtplan::QueryPlan qp = rtplan::plan_query(sh, rqs[0].flags);
+    const rtplan::QueryPlan qp = rtplan::plan_query(sc->shape, rqs[0].flags);
     const rtk::AovFn kern = rtk::aov_kernel(qp.engine, qp.scan_mode);
     if (!kern) return fail(RT_ERR_HIP, "no AOV kernel for this plan");
     const rt_tile_request& rq = rqs[0];
@@ -1587,21 +1540,8 @@ static int launch_aov(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint
     p.s_begin = begin;
     p.s_end = end;
     p.planes = mask;
-    p.n_sph = sh.n_sph;
-    p.n_tri = sh.n_tri;
-    p.root_ref = sh.root_ref;
-    p.full_chain = qp.full_chain ? 1u : 0u;
-    p.trav = sc->d_trav;
-    p.bvh_nodes = sc->d_bvh;
-    p.leaf_of = sc->d_leaf_of;
-    p.world_rank = sc->has_order ? sc->d_world_rank : nullptr;
-    p.geom_r = sc->d_geom_r;
-    p.tri = sc->d_tri;
+    scene_refs(sc, qp.full_chain, p);
     p.mat = sc->d_mat;
-    p.counters = sc->d_counters;
-    int per_cu = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, rtplan::QUERY_BLOCK, qp.lds));
-    if (per_cu < 1) per_cu = 1;
     for (uint32_t i0 = 0; i0 < n; i0 += rtk::MAX_BATCH) {
         const uint32_t m = std::min<uint32_t>(rtk::MAX_BATCH, n - i0);
         p.n_strips = m;
@@ -1616,20 +1556,13 @@ static int launch_aov(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint
             sd.index = pl.index;
             sd.y0 = hs * rqs[i0 + i].division_no;
         }
-        if (sc->pending.size() >= QUEUE_SLOTS) return fail(RT_ERR_LIMIT, "too many uncollected launches: call rt_scene_collect()");
-        const uint64_t useful = ((uint64_t)p.npix * m + rtplan::QUERY_BLOCK - 1) / rtplan::QUERY_BLOCK;
-        const uint32_t blocks = (uint32_t)std::min<uint64_t>(useful, (uint64_t)sc->ctx->n_cu * (uint32_t)per_cu);
+        Grid g;
+        int rc = persistent_blocks(sc, kern, rtplan::QUERY_BLOCK, qp.lds, (uint64_t)p.npix * m, g);
+        if (rc) return rc;
         if (dbg(DBG_VERBOSE))
             fprintf(stderr, "[rt] aov: engine %d  scan mode %d  lds %zu B  workgroups/CU %d  strips %u  pixels %u  samples [%u, %u)  planes %#x\n",
-                    qp.engine, qp.scan_mode, qp.lds, per_cu, m, p.npix, begin, end, mask);
-        EvPair ev;
-        int rc = get_events(sc, ev);
-        if (rc) return rc;
-        HIPCHK(hipEventRecord(ev.a, stream));
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(rtplan::QUERY_BLOCK), qp.lds, stream, p);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev.b, stream));
-        sc->pending.push_back({ev.a, ev.b});
+                    qp.engine, qp.scan_mode, qp.lds, g.per_cu, m, p.npix, begin, end, mask);
+        if ((rc = enqueue(sc, stream, kern, g.blocks, rtplan::QUERY_BLOCK, qp.lds, p))) return rc;
         sc->primary_rays += (uint64_t)p.npix * (end - begin) * m;
         sc->last_engine = (uint32_t)qp.engine;
         sc->last_form = 0;
@@ -1655,78 +1588,37 @@ static int rt_scene_render_aov_impl(rt_scene* sc, const rt_tile_request* rq, uin
     std::lock_guard<std::mutex> dl(sc->ctx->mu);
     std::lock_guard<std::mutex> lk(sc->mu);
     HIPCHK(hipSetDevice(sc->ctx->dev));
-    hipStream_t st = sc->ctx->stream;
     // one device buffer: albedo and normal (12 B), depth, hits and index (4 B) per pixel
     const size_t npix = (size_t)(rq->height / rq->divisions) * rq->width;
     const size_t v3_b = npix * 3 * sizeof(float), s_b = npix * sizeof(uint32_t);
-    if (sc->d_aov_cap < 2 * v3_b + 3 * s_b) {
-        (void)hipFree(sc->d_aov);
-        sc->d_aov = nullptr;
-        sc->d_aov_cap = 0;
-        if (hipMalloc(&sc->d_aov, 2 * v3_b + 3 * s_b) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(RT_ERR_OOM, "hipMalloc(AOV planes) failed");
-        }
-        sc->d_aov_cap = 2 * v3_b + 3 * s_b;
-    }
+    if ((rc = sc->d_aov.reserve(2 * v3_b + 3 * s_b, "AOV planes"))) return rc;
+    char* const d = sc->d_aov.d;
     // the device planes the caller asked for, and their sizes
     struct Plane {
         void* host;
         char* dev;
         size_t bytes;
     };
-    const Plane pl[5] = {{planes->albedo, sc->d_aov, v3_b},
-                         {planes->normal, sc->d_aov + v3_b, v3_b},
-                         {planes->depth, sc->d_aov + 2 * v3_b, s_b},
-                         {planes->hits, sc->d_aov + 2 * v3_b + s_b, s_b},
-                         {planes->index, sc->d_aov + 2 * v3_b + 2 * s_b, s_b}};
+    const Plane pl[5] = {{planes->albedo, d, v3_b},
+                         {planes->normal, d + v3_b, v3_b},
+                         {planes->depth, d + 2 * v3_b, s_b},
+                         {planes->hits, d + 2 * v3_b + s_b, s_b},
+                         {planes->index, d + 2 * v3_b + 2 * s_b, s_b}};
     rt_aov_planes dp = {};
     dp.albedo = planes->albedo ? (float*)pl[0].dev : nullptr;
     dp.normal = planes->normal ? (float*)pl[1].dev : nullptr;
     dp.depth = planes->depth ? (float*)pl[2].dev : nullptr;
     dp.hits = planes->hits ? (uint32_t*)pl[3].dev : nullptr;
     dp.index = planes->index ? (uint32_t*)pl[4].dev : nullptr;
-    // settle anything enqueued earlier so the stats of this call are its own (the scene's upload time stays for the next tile call)
-    rt_tile_stats prev;
-    rc = collect_locked(sc, &prev);
-    if (rc) return rc;
-    EvPair up, down;
-    if ((rc = get_events(sc, up)) || (rc = get_events(sc, down))) return rc;
-    struct EvReturn {
-        rt_scene* sc;
-        EvPair a, b;
-        hipStream_t st;
-        bool ok = false;
-        ~EvReturn() {
-            if (!ok) (void)hipStreamSynchronize(st);       // (an error return waits for what already writes into caller memory)
-            sc->free_ev.push_back({a.a, a.b});
-            sc->free_ev.push_back({b.a, b.b});
-        }
-    } ev_return{sc, up, down, st};
-    HIPCHK(hipEventRecord(up.a, st));
+    StagedCall call(sc);
+    if ((rc = call.begin())) return rc;
     if (begin > 0)          // (a call from sample 0 reads no plane: the caller's buffers may be uninitialised)
         for (const Plane& q : pl)
-            if (q.host) HIPCHK(hipMemcpyAsync(q.dev, q.host, q.bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(up.b, st));
-    rc = launch_aov(sc, rq, 1, begin, end, &dp, mask, st);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(down.a, st));
+            if (q.host) HIPCHK(hipMemcpyAsync(q.dev, q.host, q.bytes, hipMemcpyHostToDevice, call.st));
+    if ((rc = call.uploads_done()) || (rc = launch_aov(sc, rq, 1, begin, end, &dp, mask, call.st)) || (rc = call.kernels_done())) return rc;
     for (const Plane& q : pl)
-        if (q.host) HIPCHK(hipMemcpyAsync(q.host, q.dev, q.bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(down.b, st));
-    HIPCHK(hipEventSynchronize(down.b));
-    ev_return.ok = true;
-    float h2d = 0.f, d2h = 0.f;
-    HIPCHK(hipEventElapsedTime(&h2d, up.a, up.b));
-    HIPCHK(hipEventElapsedTime(&d2h, down.a, down.b));
-    rt_tile_stats s;
-    rc = collect_locked(sc, &s);
-    if (rc) return rc;
-    sc->h2d_ms = prev.h2d_ms;
-    s.h2d_ms = h2d;
-    s.d2h_ms = d2h;
-    if (stats) *stats = s;
-    return RT_OK;
+        if (q.host) HIPCHK(hipMemcpyAsync(q.host, q.dev, q.bytes, hipMemcpyDeviceToHost, call.st));
+    return call.finish(stats);
 }
 
 // ---- the a-trous denoiser (rt_tile.h "denoiser", rt_denoise.hip.h, rt_denoise_math.h) -------------------------------------------------
@@ -1753,9 +1645,7 @@ static int check_denoise(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, c
     for (uint32_t i = 1; i < n; i++)
         if (rqs[i].division_no != rqs[0].division_no + i) return fail(RT_ERR_BAD_ARG, "strips must have consecutive division_no, ascending");
     if (!dq) return fail(RT_ERR_BAD_ARG, "denoise request is NULL");
-    if (!acc) return fail(RT_ERR_BAD_ARG, "accum is NULL");
-    for (uint32_t i = 0; i < n; i++)
-        if (!acc[i]) return fail(RT_ERR_BAD_ARG, "accum[i] is NULL");
+    if ((rc = check_array(acc, n, "accum"))) return rc;
     if (!planes) return fail(RT_ERR_BAD_ARG, "planes is NULL");
     *mask = dn_mask(planes[0]);
     for (uint32_t i = 1; i < n; i++)
@@ -1813,18 +1703,7 @@ static int launch_denoise(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, 
     p.guide = (float4*)(scratch + pl.off_guide);
     float4* buf[2] = {(float4*)(scratch + pl.off_color[0]), (float4*)(scratch + pl.off_color[1])};
     const uint32_t persist = (uint32_t)sc->ctx->n_cu * 8u;           // grid cap of the grid-stride kernels: 8 workgroups of 256 a CU
-    auto launch = [&](rtk::DnFn kern, uint32_t blocks, size_t lds) -> int {
-        if (sc->pending.size() >= QUEUE_SLOTS) return fail(RT_ERR_LIMIT, "too many uncollected launches: call rt_scene_collect()");
-        EvPair ev;
-        int rc = get_events(sc, ev);
-        if (rc) return rc;
-        HIPCHK(hipEventRecord(ev.a, stream));
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(rtplan::DN_BLOCK), lds, stream, p);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev.b, stream));
-        sc->pending.push_back({ev.a, ev.b});
-        return RT_OK;
-    };
+    auto launch = [&](rtk::DnFn kern, uint32_t blocks, size_t lds) { return enqueue(sc, stream, kern, blocks, rtplan::DN_BLOCK, lds, p); };
     // the band of strips [b0, b0 + m): its rows and its per-strip pointers
     auto band = [&](uint32_t b0, uint32_t m) {
         p.row0 = b0 * Hs;
@@ -1917,7 +1796,6 @@ static int rt_scene_denoise_impl(rt_scene* sc, const rt_tile_request* rqs, uint3
     std::lock_guard<std::mutex> dl(sc->ctx->mu);
     std::lock_guard<std::mutex> lk(sc->mu);
     HIPCHK(hipSetDevice(sc->ctx->dev));
-    hipStream_t st = sc->ctx->stream;
     // one device buffer: the scratch, then per strip its inputs and outputs, each region 256-B aligned
     const size_t npix = (size_t)(rqs[0].height / rqs[0].divisions) * rqs[0].width;
     const size_t v3 = npix * 3 * sizeof(float), s1 = npix * sizeof(uint32_t), u8 = npix * 3;
@@ -1949,17 +1827,9 @@ static int rt_scene_denoise_impl(rt_scene* sc, const rt_tile_request* rqs, uint3
         io[i * 3 + 1] = f32 ? add(nullptr, f32[i], v3) : SIZE_MAX;
         io[i * 3 + 2] = lin ? add(nullptr, lin[i], v3) : SIZE_MAX;
     }
-    if (sc->d_dn_cap < top) {
-        (void)hipFree(sc->d_dn);
-        sc->d_dn = nullptr;
-        sc->d_dn_cap = 0;
-        if (hipMalloc(&sc->d_dn, top) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(RT_ERR_OOM, "hipMalloc(denoise staging) failed");
-        }
-        sc->d_dn_cap = top;
-    }
-    auto dev = [&](size_t r) -> void* { return r == SIZE_MAX ? nullptr : sc->d_dn + regs[r].off; };
+    if ((rc = sc->d_dn.reserve(top, "denoise staging"))) return rc;
+    char* const d = sc->d_dn.d;
+    auto dev = [&](size_t r) -> void* { return r == SIZE_MAX ? nullptr : d + regs[r].off; };
     for (uint32_t i = 0; i < n; i++) {
         d_acc[i] = dev(ia[i]);
         d_pl[i] = {};
@@ -1971,47 +1841,18 @@ static int rt_scene_denoise_impl(rt_scene* sc, const rt_tile_request* rqs, uint3
         d_f32[i] = dev(io[i * 3 + 1]);
         d_lin[i] = dev(io[i * 3 + 2]);
     }
-    // settle anything enqueued earlier so the stats of this call are its own (the scene's upload time stays for the next tile call)
-    rt_tile_stats prev;
-    rc = collect_locked(sc, &prev);
-    if (rc) return rc;
-    EvPair up, down;
-    if ((rc = get_events(sc, up)) || (rc = get_events(sc, down))) return rc;
-    struct EvReturn {
-        rt_scene* sc;
-        EvPair a, b;
-        hipStream_t st;
-        bool ok = false;
-        ~EvReturn() {
-            if (!ok) (void)hipStreamSynchronize(st);       // (an error return waits for what already writes into caller memory)
-            sc->free_ev.push_back({a.a, a.b});
-            sc->free_ev.push_back({b.a, b.b});
-        }
-    } ev_return{sc, up, down, st};
-    HIPCHK(hipEventRecord(up.a, st));
+    StagedCall call(sc);
+    if ((rc = call.begin())) return rc;
     for (const Region& r : regs)
-        if (r.host_in) HIPCHK(hipMemcpyAsync(sc->d_dn + r.off, r.host_in, r.bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(up.b, st));
-    rc = launch_denoise(sc, rqs, n, *dq, mask, d_acc.data(), d_pl.data(), rgb ? d_rgb.data() : nullptr, f32 ? d_f32.data() : nullptr,
-                        lin ? d_lin.data() : nullptr, sc->d_dn, st);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(down.a, st));
+        if (r.host_in) HIPCHK(hipMemcpyAsync(d + r.off, r.host_in, r.bytes, hipMemcpyHostToDevice, call.st));
+    if ((rc = call.uploads_done()) ||
+        (rc = launch_denoise(sc, rqs, n, *dq, mask, d_acc.data(), d_pl.data(), rgb ? d_rgb.data() : nullptr, f32 ? d_f32.data() : nullptr,
+                             lin ? d_lin.data() : nullptr, d, call.st)) ||
+        (rc = call.kernels_done()))
+        return rc;
     for (const Region& r : regs)
-        if (r.host_out) HIPCHK(hipMemcpyAsync(r.host_out, sc->d_dn + r.off, r.bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(down.b, st));
-    HIPCHK(hipEventSynchronize(down.b));
-    ev_return.ok = true;
-    float h2d = 0.f, d2h = 0.f;
-    HIPCHK(hipEventElapsedTime(&h2d, up.a, up.b));
-    HIPCHK(hipEventElapsedTime(&d2h, down.a, down.b));
-    rt_tile_stats s;
-    rc = collect_locked(sc, &s);
-    if (rc) return rc;
-    sc->h2d_ms = prev.h2d_ms;
-    s.h2d_ms = h2d;
-    s.d2h_ms = d2h;
-    if (stats) *stats = s;
-    return RT_OK;
+        if (r.host_out) HIPCHK(hipMemcpyAsync(r.host_out, d + r.off, r.bytes, hipMemcpyDeviceToHost, call.st));
+    return call.finish(stats);
 }
 
 // ---- Test / tool hooks.  NOT part of rt_tile.h and NOT in the product library: compiled only with -DRT_DEBUG_HOOKS, which
@@ -2100,8 +1941,7 @@ struct FrameDev {
     std::thread th;
     // strip-queue mode: two strips in flight, each on its own stream with its own device buffer (made on first use)
     hipStream_t qs[2] = {nullptr, nullptr};
-    uint8_t* qd[2] = {nullptr, nullptr};
-    size_t qcap = 0;
+    DevBuf qd[2];
     // result of the last command
     int rc = RT_OK;
     std::string err;
@@ -2185,15 +2025,9 @@ int frame_dev_render(rt_frame_ctx* fc, int w) {
     HIPCHK(hipSetDevice(ctx->dev));
     for (int i = 0; i < 2; i++)
         if (!d.qs[i]) HIPCHK(hipStreamCreateWithFlags(&d.qs[i], hipStreamNonBlocking));
-    if (d.qcap < strip) {
-        for (int i = 0; i < 2; i++) {
-            (void)hipFree(d.qd[i]);
-            d.qd[i] = nullptr;
-        }
-        d.qcap = 0;
-        for (int i = 0; i < 2; i++)
-            if (hipMalloc(&d.qd[i], strip) != hipSuccess) return fail(RT_ERR_OOM, "hipMalloc(strip) failed");
-        d.qcap = strip;
+    for (int i = 0; i < 2; i++) {
+        int rc = d.qd[i].reserve(strip, "strip");
+        if (rc) return rc;
     }
     bool busy[2] = {false, false};
     struct Settle {                       // an error return waits for what is already enqueued (it writes caller memory)
@@ -2214,10 +2048,10 @@ int frame_dev_render(rt_frame_ctx* fc, int w) {
         if (i >= rq0.divisions) break;
         rt_tile_request rq = rq0;
         rq.division_no = rq0.divisions - 1u - i;
-        void* d1[1] = {d.qd[sl]};
+        void* d1[1] = {d.qd[sl].d};
         int r = rt_scene_render_tiles_device_impl(sc, &rq, 1, d1, strip, nullptr, d.qs[sl]);
         if (r) return r;
-        HIPCHK(hipMemcpyAsync(out_rgb + (size_t)rq.division_no * strip, d.qd[sl], strip, hipMemcpyDeviceToHost, d.qs[sl]));
+        HIPCHK(hipMemcpyAsync(out_rgb + (size_t)rq.division_no * strip, d.qd[sl].d, strip, hipMemcpyDeviceToHost, d.qs[sl]));
         busy[sl] = true;
     }
     for (int i = 0; i < 2; i++)
@@ -2241,10 +2075,8 @@ void frame_dev_release(FrameDev& d) {
             (void)hipStreamDestroy(d.qs[i]);
             d.qs[i] = nullptr;
         }
-        (void)hipFree(d.qd[i]);
-        d.qd[i] = nullptr;
+        d.qd[i].release();
     }
-    d.qcap = 0;
 }
 
 // dispatcher thread of entry w: sleeps on the context's condition variable between commands

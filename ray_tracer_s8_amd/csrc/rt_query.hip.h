@@ -20,10 +20,9 @@
 
 namespace rtk {
 
-struct QParams {
-    const float4* rays;          // [2 n]: rt_ray (o, t_min) (d, t_max)
-    uint4* hits;                 // [2 n]: rt_hit (P, distance) (normal, index), as bits
-    uint64_t n;
+// The scene as closest_hit / query_root read it: the base of every parameter block that finds first hits (QParams, rt_trace.hip.h
+// TParams, rt_aov.hip.h AParams).  The host fills it in one place (rt_api.hip scene_refs).
+struct SceneRefs {
     uint32_t n_sph, n_tri;
     uint32_t root_ref;           // root reference (LEAF_BIT | prim when the tree is a single leaf)
     uint32_t full_chain;         // the crate's literal slab test and the whole box chain
@@ -36,8 +35,14 @@ struct QParams {
     unsigned long long* counters;   // [0] rays (ray_segments), [1] exact root tests (broad_candidates)
 };
 
-// The reference's exact root test of primitive `prim` (sphere.rs:42-47 / mesh.rs:109-161 -> shapes/mod.rs:106-129).  P: QParams or any
-// parameter block with the same scene fields (rt_trace.hip.h TParams).
+struct QParams : SceneRefs {
+    const float4* rays;          // [2 n]: rt_ray (o, t_min) (d, t_max)
+    uint4* hits;                 // [2 n]: rt_hit (P, distance) (normal, index), as bits
+    uint64_t n;
+};
+
+// The reference's exact root test of primitive `prim` (sphere.rs:42-47 / mesh.rs:109-161 -> shapes/mod.rs:106-129).  P: a parameter
+// block derived from SceneRefs.
 template <class P>
 __device__ __forceinline__ bool query_root(const P& p, uint32_t prim, V3 o, V3 d, float t_min, float t_max, float& t) {
     if (prim < p.n_sph) {

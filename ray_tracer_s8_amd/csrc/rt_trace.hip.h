@@ -17,7 +17,7 @@
 
 namespace rtk {
 
-struct TParams {
+struct TParams : SceneRefs {
     const float4* rays;          // [2 n]: rt_ray (o, t_min) (d, t_max)
     float* rgb;                  // [3 n]: the f32 sum of the ray's sample colours
     uint32_t* segments;          // [n] ray_color entries with depth > 0, or nullptr
@@ -28,19 +28,8 @@ struct TParams {
     uint32_t as_given;           // 1: the direction is taken bit for bit (RT_TRACE_RAY_AS_GIVEN), 0: Ray::new normalises it
     uint32_t path32;             // 1: path stack entries are u32, 0: u16
     uint32_t lds_path_off;       // byte offset of the path stack in dynamic LDS
-    // the scene, as rt_query.hip.h QParams names it (closest_hit, query_root)
-    uint32_t n_sph, n_tri;
-    uint32_t root_ref;
-    uint32_t full_chain;
-    const float4* trav;
-    const float4* bvh_nodes;
-    const uint32_t* leaf_of;
-    const uint32_t* world_rank;
-    const float4* geom_r;        // [n_sph] (cx, cy, cz, radius)
-    const float* tri;            // [9 n_tri]
     const float4* mat;           // [n_sph + n_tri] (albedo r, g, b, roughness)
     const float* emis;           // [n_sph + n_tri]
-    unsigned long long* counters;   // [0] ray segments, [1] exact root tests (broad_candidates)
 };
 
 // ENGINE 2: the walk; 1: the scan with consider<MODE> (MODE 0 plain linear semantics, 2 BVH semantics).

@@ -111,6 +111,21 @@ def init() -> int:
     return n.value
 
 
+def _pack_rays(origins, directions, t_min, t_max) -> np.ndarray:
+    """The rt_ray array (RAY_DTYPE) of origins / directions (N, 3) and t_min / t_max (scalars or (N,))."""
+    o = np.asarray(origins, np.float32)
+    d = np.asarray(directions, np.float32)
+    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+        raise ValueError(f"origins and directions: need two (N, 3) arrays, got {o.shape} and {d.shape}")
+    n = len(o)
+    rays = np.empty(n, _abi.RAY_DTYPE)
+    rays["ox"], rays["oy"], rays["oz"] = o[:, 0], o[:, 1], o[:, 2]
+    rays["dx"], rays["dy"], rays["dz"] = d[:, 0], d[:, 1], d[:, 2]
+    rays["t_min"] = np.broadcast_to(np.asarray(t_min, np.float32), (n,))
+    rays["t_max"] = np.broadcast_to(np.asarray(t_max, np.float32), (n,))
+    return rays
+
+
 class Scene:
     """rt_scene handle: the world resident in one GPU's HBM."""
 
@@ -241,16 +256,8 @@ class Scene:
         Ray::new(origins[i], directions[i]) within [t_min, t_max).  origins / directions: (N, 3); t_min / t_max: scalars or (N,).
         Returns (hits, stats): a structured array of HIT_DTYPE (index = the primitive's position in the world, RT_HIT_NONE
         for a miss) and the call's TileStats."""
-        o = np.asarray(origins, np.float32)
-        d = np.asarray(directions, np.float32)
-        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
-            raise ValueError(f"origins and directions: need two (N, 3) arrays, got {o.shape} and {d.shape}")
-        n = len(o)
-        rays = np.empty(n, _abi.RAY_DTYPE)
-        rays["ox"], rays["oy"], rays["oz"] = o[:, 0], o[:, 1], o[:, 2]
-        rays["dx"], rays["dy"], rays["dz"] = d[:, 0], d[:, 1], d[:, 2]
-        rays["t_min"] = np.broadcast_to(np.asarray(t_min, np.float32), (n,))
-        rays["t_max"] = np.broadcast_to(np.asarray(t_max, np.float32), (n,))
+        rays = _pack_rays(origins, directions, t_min, t_max)
+        n = len(rays)
         hits = np.empty(n, _abi.HIT_DTYPE)
         st = TileStats()
         _abi.check(self._lib.rt_scene_intersect(self._h, rays.ctypes.data_as(C.POINTER(_abi.Ray)), n,
@@ -273,16 +280,8 @@ class Scene:
         as_given: take the directions bit for bit (RT_TRACE_RAY_AS_GIVEN) instead of Ray::new's normalisation.  rng_state: None
         for the seeded streams of `seed`, else (N, 4) uint64 xoshiro256++ states, one stream per ray.
         Returns (rgb_sum (N, 3) float32, segments (N,) uint32, stats), and the written-back states (N, 4) when rng_state is given."""
-        o = np.asarray(origins, np.float32)
-        d = np.asarray(directions, np.float32)
-        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
-            raise ValueError(f"origins and directions: need two (N, 3) arrays, got {o.shape} and {d.shape}")
-        n = len(o)
-        rays = np.empty(n, _abi.RAY_DTYPE)
-        rays["ox"], rays["oy"], rays["oz"] = o[:, 0], o[:, 1], o[:, 2]
-        rays["dx"], rays["dy"], rays["dz"] = d[:, 0], d[:, 1], d[:, 2]
-        rays["t_min"] = np.broadcast_to(np.asarray(t_min, np.float32), (n,))
-        rays["t_max"] = np.broadcast_to(np.asarray(t_max, np.float32), (n,))
+        rays = _pack_rays(origins, directions, t_min, t_max)
+        n = len(rays)
         state = None
         if rng_state is not None:
             state = np.array(rng_state, np.uint64, order="C")
