@@ -41,6 +41,8 @@ def load() -> C.CDLL:
         _lib.rt_oracle_sample_seed.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]
         _lib.rt_oracle_find_roots_quadratic.restype = C.c_int
         _lib.rt_oracle_find_roots_quadratic.argtypes = [C.c_float, C.c_float, C.c_float, C.c_void_p]
+        _lib.rt_oracle_intersect_batch.restype = C.c_int
+        _lib.rt_oracle_trace_batch.restype = C.c_int
     return _lib
 
 
@@ -160,6 +162,69 @@ def ray_color(spheres, triangles, origin, direction, depth, state4, t_min=0.001,
                                _p(_f3(origin)), _p(_f3(direction)), C.c_uint32(depth), _p(state4), _p(out),
                                C.byref(segs))
     return out, segs.value
+
+
+RAY_DTYPE = np.dtype([("ox", "<f4"), ("oy", "<f4"), ("oz", "<f4"), ("t_min", "<f4"),
+                      ("dx", "<f4"), ("dy", "<f4"), ("dz", "<f4"), ("t_max", "<f4")])      # include/rt_tile.h rt_ray
+HIT_NONE = 0xFFFFFFFF
+
+
+def _batch_args(spheres, triangles, world_index, rays):
+    sph = np.ascontiguousarray(spheres) if spheres is not None and len(spheres) else None
+    tri = np.ascontiguousarray(triangles) if triangles is not None and len(triangles) else None
+    ns, nt = (0 if sph is None else len(sph)), (0 if tri is None else len(tri))
+    wi = None if world_index is None else np.ascontiguousarray(world_index, dtype=np.uint32)
+    if wi is not None and wi.size != ns + nt:
+        raise ValueError("world_index: one entry per primitive")
+    r = np.ascontiguousarray(rays)
+    if r.dtype.itemsize != RAY_DTYPE.itemsize or r.ndim != 1:
+        raise ValueError("rays: a 1-d array of rt_ray records (32 bytes each)")
+    return sph, ns, tri, nt, wi, r
+
+
+def intersect_batch(spheres, triangles, rays, backend=0, world_index=None, ray_as_given=False, nthreads=0):
+    """The closest hit of every ray of `rays` (records of rt_ray layout: the window is the ray's own), the scene and its BVH built
+    once.  backend 0 plain scan, 1 BVH semantics; ray_as_given: the direction is taken bit for bit instead of through Ray::new;
+    world_index as render().  Returns a dict of arrays: hit (bool), index (uint32: the POSITION in the world, HIT_NONE on a
+    miss), point, normal, albedo (n x 3 float32), roughness, emission (float32); the float fields of a miss are 0."""
+    sph, ns, tri, nt, wi, r = _batch_args(spheres, triangles, world_index, rays)
+    n = len(r)
+    hit = np.zeros(n, np.uint8)
+    idx = np.full(n, HIT_NONE, np.uint32)
+    out = np.zeros((n, 11), np.float32)
+    rc = load().rt_oracle_intersect_batch(_p(sph), C.c_uint32(ns), _p(tri), C.c_uint32(nt), _p(wi), C.c_int(backend), _p(r),
+                                          C.c_uint64(n), C.c_int(1 if ray_as_given else 0), C.c_int(nthreads), _p(hit), _p(idx),
+                                          _p(out))
+    if rc != 0:
+        raise ValueError(f"rt_oracle_intersect_batch: bad arguments ({rc})")
+    return {"hit": hit.astype(bool), "index": idx, "point": out[:, 0:3].copy(), "normal": out[:, 3:6].copy(),
+            "albedo": out[:, 6:9].copy(), "roughness": out[:, 9].copy(), "emission": out[:, 10].copy()}
+
+
+def trace_batch(spheres, triangles, rays, spp=1, max_bounces=10, backend=0, world_index=None, ray_as_given=False, seed=None,
+                states=None, nthreads=0):
+    """Per ray the in-order f32 sum of ray_color(ray, max_bounces + 1, rng) over spp samples, the ray's own window on every
+    segment.  Exactly one of `seed` (sample s of ray i draws from seed_from_u64(sample_seed(seed, i, spp, s))) and `states`
+    ((n, 4) uint64: one xoshiro256++ state per ray, advanced through its samples).  Returns (rgb (n, 3) float32, segments (n,)
+    uint64, final states (n, 4) uint64 or None for the seeded form)."""
+    if (seed is None) == (states is None):
+        raise ValueError("exactly one of seed and states")
+    sph, ns, tri, nt, wi, r = _batch_args(spheres, triangles, world_index, rays)
+    n = len(r)
+    st = None
+    if states is not None:
+        st = np.array(states, dtype=np.uint64, order="C")
+        if st.shape != (n, 4):
+            raise ValueError("states: (n, 4) uint64")
+    rgb = np.zeros((n, 3), np.float32)
+    segs = np.zeros(n, np.uint64)
+    rc = load().rt_oracle_trace_batch(_p(sph), C.c_uint32(ns), _p(tri), C.c_uint32(nt), _p(wi), C.c_int(backend), _p(r),
+                                      C.c_uint64(n), C.c_int(1 if ray_as_given else 0), C.c_uint32(spp), C.c_uint32(max_bounces),
+                                      C.c_uint64(0 if seed is None else seed & 0xFFFFFFFFFFFFFFFF), _p(st), C.c_int(nthreads),
+                                      _p(rgb), _p(segs))
+    if rc != 0:
+        raise ValueError(f"rt_oracle_trace_batch: bad arguments ({rc})")
+    return rgb, segs, st
 
 
 def sky(direction):

@@ -47,6 +47,7 @@
 // rounds 1-3), 2 = the reference's own structure — one stream per ROW, consumed pixel after pixel,
 // sample after sample (S/main.rs:69-77) — seeded deterministically per row instead of from entropy.
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -229,8 +230,9 @@ struct Ray {
     V3 origin, direction, inv_direction;
     int sign_x, sign_y, sign_z;
 };
-inline Ray ray_new(V3 origin, V3 direction) {  // B/ray.rs:133-143
-    V3 d = normalize(direction);
+// the fields Ray::new derives from the normalised direction (B/ray.rs:135-142); also the ray of a caller that hands the
+// direction over bit for bit (rt_tile.h RT_TRACE_RAY_AS_GIVEN, the feature buffers' camera rays)
+inline Ray ray_as_given(V3 origin, V3 d) {
     Ray r;
     r.origin = origin;
     r.direction = d;
@@ -240,6 +242,7 @@ inline Ray ray_new(V3 origin, V3 direction) {  // B/ray.rs:133-143
     r.sign_z = d.z < 0.0f;
     return r;
 }
+inline Ray ray_new(V3 origin, V3 direction) { return ray_as_given(origin, normalize(direction)); }  // B/ray.rs:133-143
 inline V3 ray_at(const Ray& r, float t) { return r.origin + t * r.direction; }  // B/ray.rs:147-149
 
 // ---------------------------------------------------------------- bvh::aabb::AABB
@@ -462,10 +465,14 @@ struct Scene {
     // `world: Vec<Object>` (S/lib.rs:11) as the ABI carries it: two typed arrays plus, for every position of the list, the
     // object that stands there (objects are numbered spheres first, then triangles).  Identity when no world_index came.
     std::vector<uint32_t> order;
-    float t_min, t_max;
+    float t_min, t_max;   // the tile request's window (T_MIN / T_MAX, S/shapes/mod.rs:12-13)
     BVH bvh;
     bool use_bvh;
     size_t count() const { return spheres.size() + tris.size(); }
+};
+// [t_min, t_max) of select_t: the strip's for every ray of a tile, the ray's own for a caller ray (rt_tile.h rt_ray)
+struct Window {
+    float t_min, t_max;
 };
 inline V3 sph_center(const rt_sphere& s) { return v3(s.cx, s.cy, s.cz); }
 inline V3 arr3(const float* p) { return v3(p[0], p[1], p[2]); }
@@ -498,8 +505,8 @@ inline Roots triangle_get_roots(const rt_triangle& t, const Ray& ray) {  // S/sh
     return Roots{0, {0.f, 0.f}};
 }
 // S/shapes/mod.rs:106-129; returns false for None
-inline bool select_t(const Scene& sc, const Roots& r, float* t) {
-    auto in_range = [&](float x) { return x >= sc.t_min && x < sc.t_max; };  // (T_MIN..T_MAX).contains
+inline bool select_t(const Window& w, const Roots& r, float* t) {
+    auto in_range = [&](float x) { return x >= w.t_min && x < w.t_max; };  // (T_MIN..T_MAX).contains
     if (r.n == 0) return false;
     if (r.n == 1) {
         if (in_range(r.x[0])) {
@@ -523,11 +530,11 @@ inline bool select_t(const Scene& sc, const Roots& r, float* t) {
     }
     return false;
 }
-inline bool object_hit_point(const Scene& sc, uint32_t idx, const Ray& ray, V3* p) {
+inline bool object_hit_point(const Scene& sc, const Window& w, uint32_t idx, const Ray& ray, V3* p) {
     Roots r = idx < sc.spheres.size() ? sphere_get_roots(sc.spheres[idx], ray)
                                       : triangle_get_roots(sc.tris[idx - sc.spheres.size()], ray);
     float t;
-    if (!select_t(sc, r, &t)) return false;
+    if (!select_t(w, r, &t)) return false;
     *p = ray_at(ray, t);
     return true;
 }
@@ -541,7 +548,7 @@ struct IntersectionTable {  // S/shapes/mod.rs:15-21
 
 // WorldRefList::intersect (S/shapes/mod.rs:158-191) over `cands` (or all objects in index
 // order when cands == nullptr).  min_by keeps the FIRST minimum; partial_cmp(None) -> Less.
-bool intersect(const Scene& sc, const Ray& ray, const std::vector<uint32_t>* cands, IntersectionTable* out) {
+bool intersect(const Scene& sc, const Window& w, const Ray& ray, const std::vector<uint32_t>* cands, IntersectionTable* out) {
     bool have = false;
     uint32_t best = 0;
     V3 best_p{};
@@ -552,7 +559,7 @@ bool intersect(const Scene& sc, const Ray& ray, const std::vector<uint32_t>* can
         // linear back-end walks the list front to back)
         uint32_t idx = sc.order[cands ? (*cands)[k] : (uint32_t)k];
         V3 p;
-        if (!object_hit_point(sc, idx, ray, &p)) continue;
+        if (!object_hit_point(sc, w, idx, ray, &p)) continue;
         float d = length(p - ray.origin);
         if (!have) {
             have = true;
@@ -641,7 +648,16 @@ Ray camera_get_ray(const Camera& c, uint32_t x, uint32_t y, Rng& rng) {  // :109
 struct Ctx {
     const Scene* sc;
     uint64_t segments;
+    Window w;   // serves every segment of the path
 };
+// The closest hit of one ray under the scene's back-end: BVH::traverse's candidates (bvh_impl.rs:436-441) or the whole world.
+// cands: scratch for the candidate list.
+inline bool scene_hit(const Scene& sc, const Window& w, const Ray& ray, std::vector<uint32_t>& cands, IntersectionTable* tb) {
+    if (!sc.use_bvh) return intersect(sc, w, ray, nullptr, tb);
+    cands.clear();
+    if (!sc.bvh.nodes.empty()) bvh_traverse_recursive(sc.bvh.nodes, 0, ray, cands);
+    return intersect(sc, w, ray, &cands, tb);
+}
 inline Color sky(V3 direction) {  // :135-144
     float t = normalize_or_zero(direction).y * 0.5f + 1.0f;
     return t * Color{1.0f, 1.0f, 1.0f} + (1.0f - t) * Color{0.3f, 0.3f, 0.8f};
@@ -651,19 +667,11 @@ Color ray_color(Ctx& cx, const Ray& ray, uint32_t depth, Rng& rng) {
     cx.segments++;
     const Scene& sc = *cx.sc;
     IntersectionTable tb;
-    bool hit;
-    if (sc.use_bvh) {
-        // the reference allocates a fresh Vec per call (bvh_impl.rs:436); a per-thread pool indexed by the
-        // recursion depth gives the same candidate list without the allocator traffic
-        static thread_local std::vector<std::vector<uint32_t>> pool;
-        if (pool.size() <= depth) pool.resize(depth + 1);
-        std::vector<uint32_t>& cands = pool[depth];
-        cands.clear();
-        if (!sc.bvh.nodes.empty()) bvh_traverse_recursive(sc.bvh.nodes, 0, ray, cands);
-        hit = intersect(sc, ray, &cands, &tb);
-    } else {
-        hit = intersect(sc, ray, nullptr, &tb);
-    }
+    // the reference allocates a fresh Vec per call (bvh_impl.rs:436); a per-thread pool indexed by the
+    // recursion depth gives the same candidate list without the allocator traffic
+    static thread_local std::vector<std::vector<uint32_t>> pool;
+    if (pool.size() <= depth) pool.resize(depth + 1);
+    const bool hit = scene_hit(sc, cx.w, ray, pool[depth], &tb);
     if (hit) {
         if (tb.emission > 0.0f) return tb.emission * tb.albedo;
         V3 diffuse_dir = unit_sphere(rng) + tb.normal;
@@ -690,7 +698,7 @@ struct Job {
 void render_span(const Job& job, uint32_t yl, uint32_t x_begin, uint32_t x_end, uint8_t* out_rgb, float* out_f32,
                  uint64_t* segs) {
     const rt_tile_request& rq = job.req;
-    Ctx cx{&job.sc, 0};
+    Ctx cx{&job.sc, 0, Window{job.sc.t_min, job.sc.t_max}};
     const uint32_t W = rq.width, H = rq.height;
     uint32_t yg = job.hs * rq.division_no + yl;  // :66-68
     Rng rng = seed_from_u64(row_seed(rq.seed, yg));   // :69 (rng_mode 2: the caller hands over whole rows)
@@ -742,6 +750,56 @@ Camera make_camera(const rt_tile_request* rq) {  // S/main.rs:42-50
                       rq->fov, rq->focal_length, (float)rq->height);
 }
 
+// include/rt_tile.h "the world's order": every position 0 .. n - 1 exactly once
+bool is_permutation(const uint32_t* world_index, uint32_t n) {
+    std::vector<char> seen(n, 0);
+    for (uint32_t i = 0; i < n; i++) {
+        if (world_index[i] >= n || seen[world_index[i]]) return false;
+        seen[world_index[i]] = 1;
+    }
+    return true;
+}
+
+// fn(first, last) over [0, n) in units of 64 items handed out dynamically to nthreads threads (<= 0: hardware_concurrency).
+// Every item owns its outputs and its RNG stream, so the results do not depend on nthreads.
+template <class Fn>
+void for_units(uint64_t n, int nthreads, Fn fn) {
+    const uint64_t UNIT = 64, n_units = (n + UNIT - 1) / UNIT;
+    int nt_ = nthreads > 0 ? nthreads : (int)std::thread::hardware_concurrency();
+    if (nt_ < 1) nt_ = 1;
+    if ((uint64_t)nt_ > n_units) nt_ = n_units ? (int)n_units : 1;
+    std::atomic<uint64_t> next_unit{0};
+    auto workfn = [&]() {
+        for (;;) {
+            const uint64_t u = next_unit.fetch_add(1);
+            if (u >= n_units) break;
+            fn(u * UNIT, std::min<uint64_t>(n, (u + 1) * UNIT));
+        }
+    };
+    if (nt_ == 1) {
+        workfn();
+        return;
+    }
+    std::vector<std::thread> th;
+    for (int i = 0; i < nt_; i++) th.emplace_back(workfn);
+    for (auto& t : th) t.join();
+}
+
+// The scene of the batch entry points: built once, the BVH included; the rays bring their windows.
+bool batch_scene(Scene& sc, const rt_sphere* sp, uint32_t ns, const rt_triangle* tr, uint32_t nt, int backend,
+                 const uint32_t* world_index) {
+    if ((backend != 0 && backend != 1) || (ns && !sp) || (nt && !tr)) return false;
+    if (world_index && !is_permutation(world_index, ns + nt)) return false;
+    rt_tile_request rq{};
+    sc = make_scene(&rq, sp, ns, tr, nt, backend, world_index);
+    if (sc.use_bvh) build_scene_bvh(sc);
+    return true;
+}
+inline Ray batch_ray(const rt_ray& r, int ray_as_given_) {
+    const V3 o = v3(r.ox, r.oy, r.oz), d = v3(r.dx, r.dy, r.dz);
+    return ray_as_given_ ? ray_as_given(o, d) : ray_new(o, d);
+}
+
 }  // namespace
 
 // =====================================================================================
@@ -764,13 +822,7 @@ __attribute__((visibility("default"))) int rt_oracle_render(const rt_tile_reques
     if (!rq || !out_rgb || rq->width == 0 || rq->height == 0 || rq->divisions == 0 ||
         rq->division_no >= rq->divisions || rq->spp == 0 || rng_mode < 0 || rng_mode > 2)
         return -1;
-    if (world_index) {
-        std::vector<char> seen((size_t)ns + nt, 0);
-        for (uint32_t i = 0; i < ns + nt; i++) {
-            if (world_index[i] >= ns + nt || seen[world_index[i]]) return -2;
-            seen[world_index[i]] = 1;
-        }
-    }
+    if (world_index && !is_permutation(world_index, ns + nt)) return -2;
     Job job;
     job.sc = make_scene(rq, sp, ns, tr, nt, backend, world_index);
     auto t0 = std::chrono::steady_clock::now();
@@ -897,14 +949,8 @@ __attribute__((visibility("default"))) int rt_oracle_intersect(const rt_sphere* 
     if (sc.use_bvh) build_scene_bvh(sc);
     Ray ray = ray_new(arr3(origin), arr3(dir));
     IntersectionTable tb;
-    bool hit;
-    if (sc.use_bvh) {
-        std::vector<uint32_t> cands;
-        if (!sc.bvh.nodes.empty()) bvh_traverse_recursive(sc.bvh.nodes, 0, ray, cands);
-        hit = intersect(sc, ray, &cands, &tb);
-    } else
-        hit = intersect(sc, ray, nullptr, &tb);
-    if (!hit) return 0;
+    std::vector<uint32_t> cands;
+    if (!scene_hit(sc, Window{t_min, t_max}, ray, cands, &tb)) return 0;
     float v[11] = {tb.point.x,  tb.point.y,  tb.point.z,  tb.normal.x,  tb.normal.y, tb.normal.z,
                    tb.albedo.r, tb.albedo.g, tb.albedo.b, tb.roughness, tb.emission};
     std::memcpy(out, v, sizeof v);
@@ -921,7 +967,7 @@ __attribute__((visibility("default"))) void rt_oracle_ray_color(const rt_sphere*
     rq.t_min = t_min;
     rq.t_max = t_max;
     Scene sc = make_scene(&rq, sp, ns, tr, nt, 0);
-    Ctx cx{&sc, 0};
+    Ctx cx{&sc, 0, Window{t_min, t_max}};
     Rng r;
     for (int i = 0; i < 4; i++) r.s[i] = state4[i];
     Ray ray = ray_new(arr3(origin), arr3(dir));
@@ -931,6 +977,75 @@ __attribute__((visibility("default"))) void rt_oracle_ray_color(const rt_sphere*
     out_rgb[2] = c.b;
     for (int i = 0; i < 4; i++) state4[i] = r.s[i];
     if (segments) *segments = cx.segments;
+}
+// ---- batch forms: the scene and (backend 1) its BVH built once, the rays spread over threads ------------------------------------
+// Closest hit of n caller rays (include/rt_tile.h rt_ray: origin, t_min, direction, t_max — the window is the ray's own).
+// backend: 0 plain scan in world order, 1 BVH semantics.  ray_as_given: 0 = Ray::new normalises the direction, 1 = the direction is
+// taken bit for bit.  world_index (may be NULL): include/rt_tile.h "the world's order".
+// Per ray i: hit[i] = 1 / 0; on a hit index[i] = the primitive's POSITION in the world, out[11 i ..] = point(3) normal(3) albedo(3)
+// roughness emission; on a miss index[i] = 0xffffffff and out[11 i ..] is left alone.  Returns 0, -1 bad arguments, -2 world_index.
+__attribute__((visibility("default"))) int rt_oracle_intersect_batch(const rt_sphere* sp, uint32_t ns, const rt_triangle* tr,
+                                                                     uint32_t nt, const uint32_t* world_index, int backend,
+                                                                     const rt_ray* rays, uint64_t n, int ray_as_given_,
+                                                                     int nthreads, uint8_t* hit, uint32_t* index, float* out) {
+    if ((n && (!rays || !hit || !index || !out)) || (ray_as_given_ != 0 && ray_as_given_ != 1)) return -1;
+    if (world_index && !is_permutation(world_index, ns + nt)) return -2;
+    Scene sc;
+    if (!batch_scene(sc, sp, ns, tr, nt, backend, world_index)) return -1;
+    for_units(n, nthreads, [&](uint64_t first, uint64_t last) {
+        std::vector<uint32_t> cands;
+        for (uint64_t i = first; i < last; i++) {
+            const Ray ray = batch_ray(rays[i], ray_as_given_);
+            IntersectionTable tb;
+            if (!scene_hit(sc, Window{rays[i].t_min, rays[i].t_max}, ray, cands, &tb)) {
+                hit[i] = 0;
+                index[i] = 0xffffffffu;
+                continue;
+            }
+            const float v[11] = {tb.point.x,  tb.point.y,  tb.point.z,  tb.normal.x,  tb.normal.y, tb.normal.z,
+                                 tb.albedo.r, tb.albedo.g, tb.albedo.b, tb.roughness, tb.emission};
+            std::memcpy(out + 11 * i, v, sizeof v);
+            hit[i] = 1;
+            index[i] = world_index ? world_index[tb.index] : tb.index;
+        }
+    });
+    return 0;
+}
+// Path tracing of n caller rays (include/rt_tile.h "path tracing of caller rays"): per ray the in-order f32 sum over s = 0 .. spp - 1
+// of ray_color(ray, max_bounces + 1, rng), the ray's own window on every segment.  RNG: state4 == NULL: sample s of ray i draws from
+// seed_from_u64(sample_seed(seed, i, spp, s)); else state4[4 i ..] is ray i's xoshiro256++ state, advanced through its samples and
+// written back.  out_rgb[3 n]; segments[n] (may be NULL): ray_color entries with depth > 0.  Returns as rt_oracle_intersect_batch.
+__attribute__((visibility("default"))) int rt_oracle_trace_batch(const rt_sphere* sp, uint32_t ns, const rt_triangle* tr,
+                                                                 uint32_t nt, const uint32_t* world_index, int backend,
+                                                                 const rt_ray* rays, uint64_t n, int ray_as_given_,
+                                                                 uint32_t spp, uint32_t max_bounces, uint64_t seed,
+                                                                 uint64_t* state4, int nthreads, float* out_rgb,
+                                                                 uint64_t* segments) {
+    if ((n && (!rays || !out_rgb)) || spp == 0 || (ray_as_given_ != 0 && ray_as_given_ != 1)) return -1;
+    if (world_index && !is_permutation(world_index, ns + nt)) return -2;
+    Scene sc;
+    if (!batch_scene(sc, sp, ns, tr, nt, backend, world_index)) return -1;
+    for_units(n, nthreads, [&](uint64_t first, uint64_t last) {
+        for (uint64_t i = first; i < last; i++) {
+            const Ray ray = batch_ray(rays[i], ray_as_given_);
+            Ctx cx{&sc, 0, Window{rays[i].t_min, rays[i].t_max}};
+            Rng rng{};
+            if (state4)
+                for (int k = 0; k < 4; k++) rng.s[k] = state4[4 * i + k];
+            Color sum{0.f, 0.f, 0.f};
+            for (uint32_t s = 0; s < spp; s++) {
+                if (!state4) rng = seed_from_u64(sample_seed(seed, i, spp, s));
+                sum = sum + ray_color(cx, ray, max_bounces + 1, rng);
+            }
+            out_rgb[3 * i] = sum.r;
+            out_rgb[3 * i + 1] = sum.g;
+            out_rgb[3 * i + 2] = sum.b;
+            if (segments) segments[i] = cx.segments;
+            if (state4)
+                for (int k = 0; k < 4; k++) state4[4 * i + k] = rng.s[k];
+        }
+    });
+    return 0;
 }
 __attribute__((visibility("default"))) void rt_oracle_sky(const float* dir, float* out_rgb) {
     Color c = sky(arr3(dir));

@@ -170,10 +170,8 @@ def test_big_cases_covered_plain_and_culled_walks(ndev):
 N_MIXED = int(os.environ.get("RT_FUZZ_MIXED", "8"))
 
 
-@pytest.mark.parametrize("i", range(N_MIXED))
-def test_fuzz_big_mixed_scene(ndev, oracle, i):
-    """Thousands of spheres AND triangles in one scene: more spheres than triangles (the quantised walk validates triangle
-    leaves through their box chain) or more triangles (exact nodes, root tests compacted over mixed primitives)."""
+def _mixed_case(i):
+    """Thousands of spheres AND triangles in one scene; odd cases interleaved at random in `world`, with exact copies."""
     g = np.random.default_rng(9000 + i)
     ns, nt = [(5000, 3000), (2000, 6000), (9000, 500), (300, 4000)][i % 4]
     sph = np.zeros(ns, _abi.SPHERE_DTYPE)
@@ -203,6 +201,14 @@ def test_fuzz_big_mixed_scene(ndev, oracle, i):
             for f in geo:
                 arr[f][k] = arr[f][j]
         wi = gw.permutation(ns + nt).astype(np.uint32)
+    return sph, tri, wi, rq, flags
+
+
+@pytest.mark.parametrize("i", range(N_MIXED))
+def test_fuzz_big_mixed_scene(ndev, oracle, i):
+    """Thousands of spheres AND triangles in one scene: more spheres than triangles (the quantised walk validates triangle
+    leaves through their box chain) or more triangles (exact nodes, root tests compacted over mixed primitives)."""
+    sph, tri, wi, rq, flags = _mixed_case(i)
     ref, ref_f, info = oracle.render(rq, sph, tri, backend=1, want_f32=True, world_index=wi)
     r = rq.copy()
     r.flags = flags
