@@ -544,6 +544,63 @@ RT_API int rt_scene_denoise_device(rt_scene* scene, const rt_tile_request* reqs,
                                    void* const* d_out_rgb, size_t out_len_each, void* const* d_out_f32,
                                    void* const* d_out_linear, void* d_scratch, size_t scratch_bytes, void* hip_stream);
 
+/* ---- placed camera: a pose for the strips' camera rays ------------------------------- */
+/* The reference's Camera sits at Point3::ZERO, looks down -z with y up (main.rs:42-50), and can be moved (Camera::set_origin,
+ * camera.rs:73-83).  An rt_camera places and turns the same pinhole / thin-lens camera: its eye, a point it looks at, a roll
+ * reference.  Field of view, focal length, aperture and focus distance stay the request's.
+ *
+ *   - Scope: the camera belongs to the JOB, like the world (the slave makes one Camera per job, main.rs:42-50): it is set on the
+ *     rt_scene (or the rt_frame_ctx, below), not carried by rt_tile_request.  NULL restores the reference camera.
+ *   - When it is read: when a call is enqueued; it travels by value in the kernel arguments, so work already enqueued keeps the
+ *     camera it was enqueued with.  rt_scene_set_camera must not race with other calls on the same scene.
+ *   - Who reads it: every entry point that generates camera rays: rt_scene_render_tile, _tile_device, _tiles, _tiles_device,
+ *     _tile_pass, _tiles_pass_device, rt_scene_render_aov, _aovs_device, rt_scene_camera_rays*, rt_frame_ctx_render (the context's
+ *     camera).  rt_render_tile and rt_render_frame keep the reference camera; rt_scene_intersect*, rt_scene_trace* and
+ *     rt_scene_denoise* do not depend on it.  The closest-hit engine does not depend on the pose.
+ *   - No camera set (or reset with NULL): exactly the code path and the bytes of a library without placed cameras.
+ *   - Arithmetic of a pose.  Each operation is one IEEE f32 rounding in the order written, no fused multiply-add:
+ *       basis    w = (origin - target) / |origin - target|, division by the length as Ray::new does (ray.rs:133-143), a length being
+ *                sqrt((x*x + y*y) + z*z);  u = c / |c| with c = up x w;  v = w x u;  a cross product component is a*b - c*d with the
+ *                two products rounded separately ((a x b).x = a.y*b.z - a.z*b.y, and cyclic);
+ *       vectors  vh = 2 tan(fov / 2), vw = (W / H) vh, lens_radius = aperture / 2 as Camera::new computes them (camera.rs:19-47);
+ *                hor = vw * u, ver = vh * v, foc = focal_length * w;
+ *                llc[i] = ((origin[i] - hor[i] / 2) - ver[i] / 2) - foc[i];  lens_u = lens_radius * u, lens_v = lens_radius * v;
+ *       sample   the lens offset of Camera::get_ray (camera.rs:109-129) is offset[i] = x1 * lens_u[i] + x2 * lens_v[i] (two products,
+ *                one sum) for the UnitDisc draw (x1, x2); everything else of get_ray is unchanged.
+ *     The reference camera is lens_u = (lens_radius, 0, 0), lens_v = (0, lens_radius, 0) written literally; rt_camera_defaults gives
+ *     the same vectors through the arithmetic above for every positive vw, vh and focal_length.
+ *   - RT_ERR_BAD_ARG, and the previous camera stays: a NULL scene or context; a component that is not finite; |origin - target| or
+ *     |up x w| equal to 0 or not finite (up parallel to the view direction); flags or reserved not 0.
+ *  */
+typedef struct rt_camera {
+    float origin[3];            /* the eye (Camera::origin)                                    */
+    float target[3];            /* a point looked at                                           */
+    float up[3];                /* roll reference                                              */
+    uint32_t flags;             /* must be 0                                                   */
+    uint32_t reserved;          /* must be 0                                                   */
+} rt_camera;                    /* 44 bytes */
+
+/* The reference camera as a pose: origin (0,0,0), target (0,0,-1), up (0,1,0). */
+RT_API void rt_camera_defaults(rt_camera* cam);
+/* cam == NULL: back to the reference camera. */
+RT_API int rt_scene_set_camera(rt_scene* scene, const rt_camera* cam);
+
+/* The camera rays of a strip, for an integrator of the caller's own on rt_scene_trace_device / rt_scene_intersect_device that starts
+ * from exactly the rays the tile kernel traces first, without a host round trip.
+ *   - Samples [sample_begin, sample_end) of the S = req->spp sample job, with the checks of rt_scene_render_tile_pass.  The record of
+ *     sample s of the strip's pixel (row, x) is written at (row*W + x) * (sample_end - sample_begin) + (s - sample_begin).
+ *   - rays: (o, t_min) (d, t_max): o the lens point, d the direction as Camera::get_ray hands it to ray_color (for
+ *     RT_TRACE_RAY_AS_GIVEN), t_min / t_max the request's.
+ *   - rng_state (optional, may be NULL): 4 u64 per record, the xoshiro256++ state after get_ray's draws: what ray_color continues
+ *     from (the rng_state of rt_scene_trace with spp = 1).
+ *   - Counters: primary_rays = records written, kernel_ms, n_launches, d2h_ms (host form); ray_segments adds 0. */
+RT_API int rt_scene_camera_rays(rt_scene* scene, const rt_tile_request* req, uint32_t sample_begin, uint32_t sample_end,
+                                rt_ray* rays, uint64_t* rng_state, rt_tile_stats* stats);
+/* Device buffers (Hs*W*(sample_end - sample_begin) rt_ray; 4 u64 per record or NULL), asynchronous on hip_stream (NULL = the scene's
+ * stream); counters and event times accumulate in the scene until rt_scene_collect(). */
+RT_API int rt_scene_camera_rays_device(rt_scene* scene, const rt_tile_request* req, uint32_t sample_begin, uint32_t sample_end,
+                                       void* d_rays, void* d_rng_state, void* hip_stream);
+
 /* ---- whole frame: replaces controller dispatch + assembly ----------------------- */
 /* (controller main.rs:47-75 `for division_no in 0..divisions` and :109-115 stitch.)
  *
@@ -599,6 +656,10 @@ RT_API int rt_frame_ctx_set_world(rt_frame_ctx* ctx,
                                   const rt_sphere* spheres, uint32_t n_spheres,
                                   const rt_triangle* triangles, uint32_t n_triangles,
                                   const uint32_t* world_index);
+/* The job's camera ("placed camera" above): every later frame of the context is rendered from it; NULL: the reference camera.
+ * A new pose starts from the snake assignment again (the strips' costs were measured from another viewpoint).  Must not race with
+ * rt_frame_ctx_render on the same context. */
+RT_API int rt_frame_ctx_set_camera(rt_frame_ctx* ctx, const rt_camera* cam);
 /* Render one frame of the job into out_rgb (>= H*W*3 bytes).  The context page-locks out_rgb (hipHostRegister) the
  * first time it sees it and keeps the registration until another buffer is passed or the context is destroyed — pass the
  * same buffer for every frame of a job and only the first pays pin_ms.  The caller must not free a buffer the context

@@ -147,7 +147,26 @@ class DenoiseRequest(C.Structure):
             setattr(r, k, v)
         return r
 
+class Camera(C.Structure):
+    """rt_camera: a pose of the strips' camera (rt_tile.h "placed camera") — the eye, a point looked at, a roll reference."""
+    _fields_ = [("origin", C.c_float * 3), ("target", C.c_float * 3), ("up", C.c_float * 3), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+    @classmethod
+    def defaults(cls) -> "Camera":
+        """The reference camera as a pose (rt_camera_defaults): origin 0, target (0, 0, -1), up (0, 1, 0).  Pure Python, like
+        default_request."""
+        return cls.look_at((0.0, 0.0, 0.0), (0.0, 0.0, -1.0))
+
+    @classmethod
+    def look_at(cls, origin, target, up=(0.0, 1.0, 0.0)) -> "Camera":
+        c = cls()
+        c.origin[:], c.target[:], c.up[:] = [float(x) for x in origin], [float(x) for x in target], [float(x) for x in up]
+        return c
+
+
 assert C.sizeof(TileRequest) == 64
+assert C.sizeof(Camera) == 44
 assert C.sizeof(TileStats) == 64
 assert C.sizeof(FrameStats) == 232
 assert C.sizeof(Ray) == C.sizeof(Hit) == RAY_DTYPE.itemsize == HIT_DTYPE.itemsize == 32
@@ -300,6 +319,17 @@ def _bind(path: Path) -> C.CDLL:
                                             C.POINTER(AovPlanes), C.POINTER(vp), C.c_size_t, C.POINTER(vp), C.POINTER(vp), vp,
                                             C.c_size_t, vp]
     lib.rt_scene_denoise_device.restype = C.c_int
+    lib.rt_camera_defaults.argtypes = [C.POINTER(Camera)]
+    lib.rt_camera_defaults.restype = None
+    lib.rt_scene_set_camera.argtypes = [vp, C.POINTER(Camera)]
+    lib.rt_scene_set_camera.restype = C.c_int
+    lib.rt_scene_camera_rays.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.c_uint32, C.POINTER(Ray), C.POINTER(C.c_uint64),
+                                         C.POINTER(TileStats)]
+    lib.rt_scene_camera_rays.restype = C.c_int
+    lib.rt_scene_camera_rays_device.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.c_uint32, vp, vp, vp]
+    lib.rt_scene_camera_rays_device.restype = C.c_int
+    lib.rt_frame_ctx_set_camera.argtypes = [vp, C.POINTER(Camera)]
+    lib.rt_frame_ctx_set_camera.restype = C.c_int
     lib.rt_render_frame.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(TileRequest), vp, C.c_uint32,
                                     vp, C.c_uint32, vp, vp, C.c_size_t, C.POINTER(TileStats)]
     lib.rt_render_frame.restype = C.c_int

@@ -36,6 +36,7 @@ struct AovStrip {
 struct AParams : SceneRefs {
     float org[3], llc[3], hor[3], ver[3];   // Camera::new (camera.rs:19-47), host-computed by rtplan::fill_camera
     float lens_radius, focus_distance;
+    float lens_u[3], lens_v[3];  // the lens disc's axes (as KParams)
     float u_den, v_den;          // aspect*H_f - 1, H_f - 1 (camera.rs:115-117)
     float t_min, t_max;
     uint32_t W, H;               // image size
@@ -102,7 +103,7 @@ __global__ __launch_bounds__(256) void rt_aov_kernel(const AParams p) {
                 sm = x1 * x1 + x2 * x2;
                 if (sm <= 1.0f) break;                                         // UnitDisc
             }
-            const V3 offset = mk(x1 * p.lens_radius, x2 * p.lens_radius, 0.0f);
+            const V3 offset = lens_offset(p, x1, x2);                          // (the reference camera: same `o` bit for bit, see the tile kernel)
             const float u = ((float)px + gen_range_01(rng)) / p.u_den;
             const float v = ((float)(p.H - pyg - 1) + gen_range_01(rng)) / p.v_den;   // camera row, main.rs:71
             const V3 dir0 = normalize_or_zero(llc + u * hor + v * ver - corg);

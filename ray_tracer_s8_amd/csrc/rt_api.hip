@@ -30,6 +30,7 @@
 #include "rt_query.hip.h"
 #include "rt_trace.hip.h"
 #include "rt_aov.hip.h"
+#include "rt_camera.hip.h"
 #include "rt_denoise.hip.h"
 #include "rt_tile.h"
 
@@ -175,6 +176,8 @@ rtplan::Knobs plan_knobs() {
 struct rt_scene {
     DeviceCtx* ctx = nullptr;
     rtplan::SceneShape shape;       // what the engine rules read (rt_plan.h)
+    rtplan::Pose pose;              // the job's placed camera (rt_scene_set_camera); read when a call is enqueued
+    bool has_pose = false;          //   false: the reference camera
     float4* d_geom = nullptr;
     float4* d_geom_pk = nullptr;
     float4* d_geom_px = nullptr;   // expanded-form broad phase records
@@ -214,8 +217,9 @@ struct rt_scene {
     // staging of the host-buffer entry points (grown on demand): the strips' bytes, their f32 twins, the running sums of
     // rt_scene_render_tile_pass and the per-strip ray segments of the batched call (frame context); the rays and hits of
     // rt_scene_intersect; rays, RNG states, colours and segments of rt_scene_trace (80 bytes a ray); the planes of rt_scene_render_aov
-    // (36 bytes a pixel); the filter's scratch and the strips' inputs and outputs of rt_scene_denoise
-    DevBuf d_out, d_outf, d_acc, d_cost, d_query, d_trace, d_aov, d_dn;
+    // (36 bytes a pixel); the filter's scratch and the strips' inputs and outputs of rt_scene_denoise; rays and RNG states of
+    // rt_scene_camera_rays (64 bytes a record)
+    DevBuf d_out, d_outf, d_acc, d_cost, d_query, d_trace, d_aov, d_dn, d_cam;
     // HIP-event bookkeeping of launches not yet collected
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, free_ev;
     uint64_t primary_rays = 0;
@@ -381,7 +385,7 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
     rtk::KParams p;
     std::memset(&p, 0, sizeof p);
     const rtplan::SampleRange smp = pass ? rtplan::SampleRange{pass->begin, pass->end, true} : rtplan::SampleRange{0u, rqs[0].spp, false};
-    rtplan::Plan pl = rtplan::plan_launch(sh, rqs[0], n, smp, kn, p);
+    rtplan::Plan pl = rtplan::plan_launch(sh, rqs[0], n, smp, kn, p, sc->has_pose ? &sc->pose : nullptr);
     if (pl.status != RT_OK) return fail(pl.status, pl.error);
     p.geom_pk = sc->d_geom_pk;
     p.geom_px = sc->d_geom_px;
@@ -1126,7 +1130,7 @@ static int rt_scene_destroy_impl(rt_scene* sc) {
     (void)hipFree(sc->d_leaf_of);
     (void)hipFree(sc->d_world_rank);
     (void)hipFree(sc->d_counters);
-    for (DevBuf* b : {&sc->d_out, &sc->d_outf, &sc->d_acc, &sc->d_cost, &sc->d_query, &sc->d_trace, &sc->d_aov, &sc->d_dn}) b->release();
+    for (DevBuf* b : {&sc->d_out, &sc->d_outf, &sc->d_acc, &sc->d_cost, &sc->d_query, &sc->d_trace, &sc->d_aov, &sc->d_dn, &sc->d_cam}) b->release();
     delete sc;
     g_live_scenes.fetch_sub(1);
     return RT_OK;
@@ -1530,7 +1534,7 @@ static int launch_aov(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint
     const uint32_t hs = rq.height / rq.divisions;
     rtk::AParams p;
     std::memset(&p, 0, sizeof p);
-    rtplan::fill_camera(rq, p);
+    rtplan::fill_camera(rq, sc->has_pose ? &sc->pose : nullptr, p);
     p.t_min = rq.t_min;
     p.t_max = rq.t_max;
     p.W = rq.width;
@@ -1618,6 +1622,105 @@ static int rt_scene_render_aov_impl(rt_scene* sc, const rt_tile_request* rq, uin
     if ((rc = call.uploads_done()) || (rc = launch_aov(sc, rq, 1, begin, end, &dp, mask, call.st)) || (rc = call.kernels_done())) return rc;
     for (const Plane& q : pl)
         if (q.host) HIPCHK(hipMemcpyAsync(q.host, q.dev, q.bytes, hipMemcpyDeviceToHost, call.st));
+    return call.finish(stats);
+}
+
+// ---- placed camera and the camera's rays (rt_tile.h "placed camera", rt_plan.h Pose, rt_camera.hip.h) -----------------------------
+// *ps, *has: the pose of cam, or the reference camera for NULL; untouched on an error.
+static int pose_of(const rt_camera* cam, rtplan::Pose* ps, bool* has) {
+    if (!cam) {
+        *has = false;
+        return RT_OK;
+    }
+    if (!rtplan::make_pose(*cam, *ps))
+        return fail(RT_ERR_BAD_ARG, "camera: a component is not finite, origin == target, up is parallel to the view direction, or flags / "
+                                    "reserved are not 0");
+    *has = true;
+    return RT_OK;
+}
+
+static int rt_scene_set_camera_impl(rt_scene* sc, const rt_camera* cam) {
+    if (!sc) return fail(RT_ERR_BAD_ARG, "scene is NULL");
+    rtplan::Pose ps;
+    bool has = false;
+    int rc = pose_of(cam, &ps, &has);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    if (has) sc->pose = ps;
+    sc->has_pose = has;
+    return RT_OK;
+}
+
+static int check_camera_rays(rt_scene* sc, const rt_tile_request* rq, uint32_t begin, uint32_t end, const void* rays) {
+    if (!sc) return fail(RT_ERR_BAD_ARG, "scene is NULL");
+    int rc = check_batch(rq, 1);
+    if (rc) return rc;
+    if ((rc = check_samples(begin, end, rq->spp))) return rc;
+    if (!rays) return fail(RT_ERR_BAD_ARG, "rays is NULL");
+    return RT_OK;
+}
+
+// Enqueue the camera-ray launch of one strip on `stream` (caller holds sc->mu, device current): persistent waves over the records.
+static int launch_camera_rays(rt_scene* sc, const rt_tile_request& rq, uint32_t begin, uint32_t end, void* d_rays, void* d_state,
+                              hipStream_t stream) {
+    const rtk::CameraFn kern = rtk::camera_rays_kernel(d_state != nullptr);
+    const uint32_t hs = rq.height / rq.divisions;
+    rtk::CParams p;
+    std::memset(&p, 0, sizeof p);
+    rtplan::fill_camera(rq, sc->has_pose ? &sc->pose : nullptr, p);
+    p.t_min = rq.t_min;
+    p.t_max = rq.t_max;
+    p.W = rq.width;
+    p.H = rq.height;
+    p.y0 = hs * rq.division_no;
+    p.spp_all = rq.spp;
+    p.s_begin = begin;
+    p.n_smp = end - begin;
+    p.total = (uint64_t)hs * rq.width * (end - begin);
+    p.seed = rq.seed;
+    p.rays = (float4*)d_rays;
+    p.state = (ulonglong2*)d_state;
+    Grid g;
+    int rc = persistent_blocks(sc, kern, rtplan::QUERY_BLOCK, 0, p.total, g);
+    if (rc) return rc;
+    if (dbg(DBG_VERBOSE))
+        fprintf(stderr, "[rt] camera rays: workgroups/CU %d  records %llu  samples [%u, %u)  states %d\n", g.per_cu,
+                (unsigned long long)p.total, begin, end, d_state ? 1 : 0);
+    if ((rc = enqueue(sc, stream, kern, g.blocks, rtplan::QUERY_BLOCK, 0, p))) return rc;
+    sc->primary_rays += p.total;
+    sc->last_engine = 0;
+    sc->last_form = 0;
+    return RT_OK;
+}
+
+static int rt_scene_camera_rays_device_impl(rt_scene* sc, const rt_tile_request* rq, uint32_t begin, uint32_t end, void* d_rays,
+                                            void* d_state, void* hip_stream) {
+    int rc = check_camera_rays(sc, rq, begin, end, d_rays);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    HIPCHK(hipSetDevice(sc->ctx->dev));
+    return launch_camera_rays(sc, *rq, begin, end, d_rays, d_state, hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream);
+}
+
+static int rt_scene_camera_rays_impl(rt_scene* sc, const rt_tile_request* rq, uint32_t begin, uint32_t end, rt_ray* rays,
+                                     uint64_t* rng_state, rt_tile_stats* stats) {
+    int rc = check_camera_rays(sc, rq, begin, end, rays);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> dl(sc->ctx->mu);
+    std::lock_guard<std::mutex> lk(sc->mu);
+    HIPCHK(hipSetDevice(sc->ctx->dev));
+    // one device buffer: the rays, then the states (32 B each per record)
+    const size_t n = (size_t)(rq->height / rq->divisions) * rq->width * (end - begin);
+    const size_t ray_b = n * sizeof(rt_ray), state_b = rng_state ? n * 4 * sizeof(uint64_t) : 0;
+    if ((rc = sc->d_cam.reserve(ray_b + state_b, "camera rays"))) return rc;
+    char* const d_rays = sc->d_cam.d;
+    char* const d_state = rng_state ? d_rays + ray_b : nullptr;
+    StagedCall call(sc);
+    if ((rc = call.begin()) || (rc = call.uploads_done()) || (rc = launch_camera_rays(sc, *rq, begin, end, d_rays, d_state, call.st)) ||
+        (rc = call.kernels_done()))
+        return rc;
+    HIPCHK(hipMemcpyAsync(rays, d_rays, ray_b, hipMemcpyDeviceToHost, call.st));
+    if (rng_state) HIPCHK(hipMemcpyAsync(rng_state, d_state, state_b, hipMemcpyDeviceToHost, call.st));
     return call.finish(stats);
 }
 
@@ -1973,6 +2076,11 @@ struct rt_frame_ctx {
     uint32_t assignment = 0;
     std::vector<double> strip_cost;
     rt_tile_request cost_rq;            // the frame the costs were measured on
+    rtplan::Pose cost_pose;             //   ... and the camera it was seen from (cost_has_pose false: the reference camera)
+    bool cost_has_pose = false;
+    // the job's camera (rt_frame_ctx_set_camera): handed to every entry's scene at the start of a frame
+    rtplan::Pose pose;
+    bool has_pose = false;
     bool cost_valid = false;
     std::vector<unsigned long long> cost_now;   // filled by the dispatchers during a frame (each writes its own strips' entries)
     // the caller's frame buffer, page-locked once
@@ -1991,6 +2099,11 @@ int frame_dev_render(rt_frame_ctx* fc, int w) {
     std::memset(&d.st, 0, sizeof d.st);
     rt_scene* sc = d.scene;
     if (!sc) return fail(RT_ERR_BAD_ARG, "rt_frame_ctx_render before rt_frame_ctx_set_world");
+    {
+        std::lock_guard<std::mutex> lk(sc->mu);          // the job's camera: this entry's launches of the frame read it
+        sc->pose = fc->pose;
+        sc->has_pose = fc->has_pose;
+    }
     if (!fc->use_queue) {
         // strip k -> entry k % nd (controller main.rs:47-75 fires one request per division; Docker DNS round-robins them
         // over the slaves): all strips of this device go out as one batch (one launch per <= MAX_BATCH strips, the last
@@ -2218,6 +2331,18 @@ int rt_frame_ctx_set_world_impl(rt_frame_ctx* fc, const rt_sphere* sp, uint32_t 
     return RT_OK;
 }
 
+int rt_frame_ctx_set_camera_impl(rt_frame_ctx* fc, const rt_camera* cam) {
+    if (!fc) return fail(RT_ERR_BAD_ARG, "ctx is NULL");
+    rtplan::Pose ps;
+    bool has = false;
+    int rc = pose_of(cam, &ps, &has);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> call(fc->call_mu);
+    if (has) fc->pose = ps;
+    fc->has_pose = has;
+    return RT_OK;
+}
+
 int rt_frame_ctx_render_impl(rt_frame_ctx* fc, const rt_tile_request* rq_in, uint8_t* out_rgb, size_t out_len,
                              rt_frame_stats* stats) {
     if (!fc) return fail(RT_ERR_BAD_ARG, "ctx is NULL");
@@ -2275,13 +2400,15 @@ int rt_frame_ctx_render_impl(rt_frame_ctx* fc, const rt_tile_request* rq_in, uin
     fc->strip = istrip;
     fc->next_strip.store(0);
     // which entry renders which strip (rt_assign.h).  The measured costs hold for the same world and the same frame geometry
-    // (size, strips, samples, depth, camera, t window): the seed changes the paths, not where the expensive rows are.
+    // (size, strips, samples, depth, camera — its knobs and its pose —, t window): the seed changes the paths, not where the
+    // expensive rows are.
     {
         rt_tile_request a = rq0, b = fc->cost_rq;
         a.seed = b.seed = 0;
         a.division_no = b.division_no = 0;
         a.flags = b.flags = 0;
-        const bool usable = fc->cost_valid && same_frame(a, b) && fc->strip_cost.size() == rq0.divisions;
+        const bool same_pose = fc->has_pose == fc->cost_has_pose && (!fc->has_pose || std::memcmp(&fc->pose, &fc->cost_pose, sizeof fc->pose) == 0);
+        const bool usable = fc->cost_valid && same_frame(a, b) && same_pose && fc->strip_cost.size() == rq0.divisions;
         const rtassign::Mode mode = fc->use_queue ? rtassign::QUEUE
                                     : (rq_in->flags & RT_FLAG_FRAME_STATIC) ? rtassign::STATIC_MOD
                                     : usable ? rtassign::BY_COST : rtassign::SNAKE;
@@ -2296,6 +2423,8 @@ int rt_frame_ctx_render_impl(rt_frame_ctx* fc, const rt_tile_request* rq_in, uin
         // the strips' costs as this frame measured them: the next frame of the job is assigned by them
         fc->strip_cost.assign(fc->cost_now.begin(), fc->cost_now.end());
         fc->cost_rq = rq0;
+        fc->cost_pose = fc->pose;
+        fc->cost_has_pose = fc->has_pose;
         fc->cost_valid = true;
     }
     rt_frame_stats fs;
@@ -2433,6 +2562,21 @@ RT_API int rt_scene_render_aovs_device(rt_scene* sc, const rt_tile_request* reqs
                                        uint32_t sample_end, const rt_aov_planes* d_planes, void* hip_stream) {
     return guarded([&] { return rt_scene_render_aovs_device_impl(sc, reqs, n, sample_begin, sample_end, d_planes, hip_stream); });
 }
+RT_API void rt_camera_defaults(rt_camera* cam) {
+    if (!cam) return;
+    std::memset(cam, 0, sizeof *cam);
+    cam->target[2] = -1.0f;           // looking down -z (main.rs:42-50)
+    cam->up[1] = 1.0f;
+}
+RT_API int rt_scene_set_camera(rt_scene* sc, const rt_camera* cam) { return guarded([&] { return rt_scene_set_camera_impl(sc, cam); }); }
+RT_API int rt_scene_camera_rays(rt_scene* sc, const rt_tile_request* rq, uint32_t sample_begin, uint32_t sample_end, rt_ray* rays,
+                                uint64_t* rng_state, rt_tile_stats* stats) {
+    return guarded([&] { return rt_scene_camera_rays_impl(sc, rq, sample_begin, sample_end, rays, rng_state, stats); });
+}
+RT_API int rt_scene_camera_rays_device(rt_scene* sc, const rt_tile_request* rq, uint32_t sample_begin, uint32_t sample_end, void* d_rays,
+                                       void* d_rng_state, void* hip_stream) {
+    return guarded([&] { return rt_scene_camera_rays_device_impl(sc, rq, sample_begin, sample_end, d_rays, d_rng_state, hip_stream); });
+}
 RT_API void rt_denoise_request_defaults(rt_denoise_request* r) {
     if (!r) return;
     std::memset(r, 0, sizeof *r);
@@ -2500,6 +2644,9 @@ RT_API int rt_frame_ctx_create(const int* devices, int n_devices, rt_frame_ctx**
 RT_API int rt_frame_ctx_set_world(rt_frame_ctx* fc, const rt_sphere* sp, uint32_t ns, const rt_triangle* tr, uint32_t nt,
                                   const uint32_t* world_index) {
     return guarded([&] { return rt_frame_ctx_set_world_impl(fc, sp, ns, tr, nt, world_index); });
+}
+RT_API int rt_frame_ctx_set_camera(rt_frame_ctx* fc, const rt_camera* cam) {
+    return guarded([&] { return rt_frame_ctx_set_camera_impl(fc, cam); });
 }
 RT_API int rt_frame_ctx_render(rt_frame_ctx* fc, const rt_tile_request* rq, uint8_t* out_rgb, size_t out_len, rt_frame_stats* stats) {
     return guarded([&] { return rt_frame_ctx_render_impl(fc, rq, out_rgb, out_len, stats); });

@@ -152,7 +152,8 @@ struct KParams {
     uint32_t slotu_magic;        //   floor(2^32 / U) + 1, U = grp * upp the units of a full slot: q / U == mulhi(q, magic) for q < 65 * U
     float* ring;                 //   [waves of the grid][n_slots][slot_stride][3]: slot header (x, row, meta), then (r, g, b) per unit
     float org[3], llc[3], hor[3], ver[3];   // Camera::new (camera.rs:19-47), host-computed
-    float lens_radius, focus_distance;
+    float lens_radius, focus_distance;   // (lens_radius: the planner's own; the kernels read lens_u / lens_v)
+    float lens_u[3], lens_v[3];  // the lens disc's axes: lens_radius u, lens_radius v; the reference camera's (lens_radius, 0, 0), (0, lens_radius, 0)
     float u_den, v_den;          // aspect*H_f - 1, H_f - 1 (camera.rs:115-117)
     float t_min, t_max;
     float spp_f;                 // the mean's divisor: samples summed into a pixel at the end of this launch (s_begin + upp)
@@ -204,6 +205,12 @@ __device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b
 __device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 __device__ __forceinline__ V3 operator*(float s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
 __device__ __forceinline__ V3 operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
+// Camera::get_ray's lens offset for the UnitDisc draw (x1, x2): two products and one sum per component, no FMA.  P: a parameter block
+// with the lens vectors of rtplan::fill_camera (KParams, rt_aov.hip.h AParams, rt_camera.hip.h CParams).
+template <class P>
+__device__ __forceinline__ V3 lens_offset(const P& p, float x1, float x2) {
+    return mk(x1 * p.lens_u[0] + x2 * p.lens_v[0], x1 * p.lens_u[1] + x2 * p.lens_v[1], x1 * p.lens_u[2] + x2 * p.lens_v[2]);
+}
 // sqrtf, correctly rounded as IEEE 754 demands, for less than the compiler's sequence.  That sequence is v_sqrt_f32, two one-ulp
 // residual tests and, around them, a scaling of small operands and a class fix-up: 16 instructions, nine of them in the 4-cycle class
 // (tools/ubench/valu_classes).  Here: v_rsq_f32 and one coupled Newton step — seven fast-class instructions — which gives the
@@ -1211,7 +1218,13 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                 // o is already the hit point P (origin exactly P)
             } else {
                 LCOUNT(4);
-                const V3 offset = mk(x1 * p.lens_radius, x2 * p.lens_radius, 0.0f);
+                // The lens offset x1 lens_u + x2 lens_v of a placed camera (rt_tile.h "placed camera").  For the reference camera, lens_u =
+                // (lr, 0, 0) and lens_v = (0, lr, 0), this is (x1 lr + x2 0, x1 0 + x2 lr, x1 0 + x2 0) where the reference computes
+                // (x1 lr, x2 lr, 0), and `o` below has the same bits either way: x1 and x2 are finite (|x| <= 1), so a product with 0 is +-0,
+                // and a + (+-0) == a bit for bit for every a that is not a zero — an infinity, a NaN (x1 lr with lr infinite or NaN: the
+                // addition passes the quiet NaN the product made through unchanged), a subnormal; where a is a zero only the SIGN of the
+                // sum can differ from a's, and the offset is used once, in o = corg + offset with corg = +0 there: (+0) + (+-0) = +0.
+                const V3 offset = lens_offset(p, x1, x2);
                 const float u = ((float)px + gen_range_01(rng)) / p.u_den;
                 const float v = ((float)(p.H - pyg - 1) + gen_range_01(rng)) / p.v_den;   // camera row, main.rs:71
                 const V3 dir0 = normalize_or_zero(llc + u * hor + v * ver - corg);

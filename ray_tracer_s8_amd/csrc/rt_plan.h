@@ -109,7 +109,56 @@ inline bool cull_wanted(uint32_t flags, int knob, bool rule) {
     return (flags & RT_FLAG_NO_CULL_WALK) ? false : (flags & RT_FLAG_CULL_WALK) ? true : knob >= 0 ? knob != 0 : rule;
 }
 
-// Camera::new with the slave's arguments (main.rs:42-50 -> camera.rs:19-47)
+// ---- A placed camera (rt_camera, rt_tile.h "placed camera").  The pose is validated and turned into its basis once,
+// by rt_scene_set_camera / rt_frame_ctx_set_camera; every launch forms its camera vectors from the basis and the request's knobs.  Each
+// operation below is one f32 rounding in the order written (this header is compiled without contraction on both sides).
+struct Pose {
+    float origin[3];   // the eye
+    float u[3], v[3], w[3];   // right, up, backward (the camera looks down -w)
+};
+
+inline float length3(const float a[3]) { return std::sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]); }
+inline void cross3(const float a[3], const float b[3], float out[3]) {    // the two products of a component rounded separately
+    out[0] = a[1] * b[2] - a[2] * b[1];
+    out[1] = a[2] * b[0] - a[0] * b[2];
+    out[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// w = (origin - target) / |origin - target| (division by the length, as Ray::new), u = c / |c| with c = up x w, v = w x u.
+// false, and `ps` untouched: a component that is not finite, a length that is 0 or not finite, flags or reserved not 0.
+inline bool make_pose(const rt_camera& c, Pose& ps) {
+    if (c.flags != 0 || c.reserved != 0) return false;
+    for (int i = 0; i < 3; i++)
+        if (!std::isfinite(c.origin[i]) || !std::isfinite(c.target[i]) || !std::isfinite(c.up[i])) return false;
+    Pose r;
+    float d[3], x[3];
+    for (int i = 0; i < 3; i++) d[i] = c.origin[i] - c.target[i];
+    const float ld = length3(d);
+    if (!(ld > 0.0f) || !std::isfinite(ld)) return false;
+    for (int i = 0; i < 3; i++) r.w[i] = d[i] / ld;
+    cross3(c.up, r.w, x);
+    const float lx = length3(x);
+    if (!(lx > 0.0f) || !std::isfinite(lx)) return false;
+    for (int i = 0; i < 3; i++) r.u[i] = x[i] / lx;
+    cross3(r.w, r.u, r.v);
+    for (int i = 0; i < 3; i++) r.origin[i] = c.origin[i];
+    ps = r;
+    return true;
+}
+
+// The lens vectors of a parameter block that has them (rtk::KParams, rtk::AParams, rtk::CParams); a block without (the launch-plan
+// harness's) gets none.
+template <class KP>
+auto set_lens(KP& p, const float lu[3], const float lv[3], int) -> decltype((void)p.lens_u[0]) {
+    for (int i = 0; i < 3; i++) {
+        p.lens_u[i] = lu[i];
+        p.lens_v[i] = lv[i];
+    }
+}
+template <class KP>
+void set_lens(KP&, const float*, const float*, long) {}
+
+// Camera::new with the slave's arguments (main.rs:42-50 -> camera.rs:19-47): the reference camera, Point3::ZERO looking down -z
 template <class KP>
 void fill_camera(const rt_tile_request& rq, KP& p) {
     const float origin[3] = {0.f, 0.f, 0.f};          // Point3::ZERO
@@ -130,15 +179,55 @@ void fill_camera(const rt_tile_request& rq, KP& p) {
         p.llc[i] = v;
     }
     p.lens_radius = rq.aperture / 2.0f;
+    // the lens disc's axes, literally (no multiplication: an extreme aperture keeps its bits)
+    const float lens_u[3] = {p.lens_radius, 0.f, 0.f}, lens_v[3] = {0.f, p.lens_radius, 0.f};
+    set_lens(p, lens_u, lens_v, 0);
     p.focus_distance = rq.focus_distance;
     p.u_den = aspect_ratio * image_height - 1.0f;      // camera.rs:116
     p.v_den = image_height - 1.0f;                     // camera.rs:117
 }
 
-// Everything of a launch of n_strips strips of request rq that does not depend on the device: engine, LDS plan, camera, sample
-// units, tiles.  `p` must come zeroed.
+// The same camera placed by a pose (Camera::set_origin, camera.rs:73-83, and a look-at basis): hor = vw u, ver = vh v,
+// foc = focal_length w, llc in fill_camera's order, the lens disc spanned by lens_radius u and lens_radius v.
 template <class KP>
-Plan plan_launch(const SceneShape& sh, const rt_tile_request& rq, uint32_t n_strips, const SampleRange& smp, const Knobs& kn, KP& p) {
+void fill_camera(const rt_tile_request& rq, const Pose& ps, KP& p) {
+    const float aspect_ratio = (float)rq.width / (float)rq.height;
+    const float image_height = (float)rq.height;
+    const float vh = 2.0f * std::tan(rq.fov / 2.0f);
+    const float vw = aspect_ratio * vh;
+    p.lens_radius = rq.aperture / 2.0f;
+    float lens_u[3], lens_v[3];
+    for (int i = 0; i < 3; i++) {
+        const float hor = vw * ps.u[i], ver = vh * ps.v[i], foc = rq.focal_length * ps.w[i];
+        p.org[i] = ps.origin[i];
+        p.hor[i] = hor;
+        p.ver[i] = ver;
+        float v = ps.origin[i] - hor / 2.0f;
+        v = v - ver / 2.0f;
+        v = v - foc;
+        p.llc[i] = v;
+        lens_u[i] = p.lens_radius * ps.u[i];
+        lens_v[i] = p.lens_radius * ps.v[i];
+    }
+    set_lens(p, lens_u, lens_v, 0);
+    p.focus_distance = rq.focus_distance;
+    p.u_den = aspect_ratio * image_height - 1.0f;
+    p.v_den = image_height - 1.0f;
+}
+
+// pose == nullptr: the reference camera, on exactly the code path it had before cameras could be placed
+template <class KP>
+void fill_camera(const rt_tile_request& rq, const Pose* pose, KP& p) {
+    if (pose) fill_camera(rq, *pose, p);
+    else fill_camera(rq, p);
+}
+
+// Everything of a launch of n_strips strips of request rq that does not depend on the device: engine, LDS plan, camera, sample
+// units, tiles.  `p` must come zeroed.  pose: the scene's placed camera, nullptr for the reference camera; nothing but the camera
+// vectors depends on it (the engine least of all).
+template <class KP>
+Plan plan_launch(const SceneShape& sh, const rt_tile_request& rq, uint32_t n_strips, const SampleRange& smp, const Knobs& kn, KP& p,
+                 const Pose* pose = nullptr) {
     using namespace rtk;
     Plan pl;
     p.W = rq.width;
@@ -314,7 +403,7 @@ Plan plan_launch(const SceneShape& sh, const rt_tile_request& rq, uint32_t n_str
     pl.count_steps = traverse && (fl & RT_FLAG_COUNT_STEPS);
     pl.maxl_l2 = maxl;
     pl.ovf_entries = pl.capped ? stack_capped - stack_lds : 0u;
-    fill_camera(rq, p);
+    fill_camera(rq, pose, p);
     p.t_min = rq.t_min;
     p.t_max = rq.t_max;
     p.spp_f = (float)s_end;

@@ -19,7 +19,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _abi
-from ._abi import DenoiseRequest, FrameStats, TileRequest, TileStats, default_request
+from ._abi import Camera, DenoiseRequest, FrameStats, TileRequest, TileStats, default_request
 from .dispatch import assemble, strips_for_worker
 
 
@@ -438,6 +438,34 @@ class Scene:
                                                      C.c_void_p(d_scratch) if d_scratch else None, scratch_bytes,
                                                      C.c_void_p(stream) if stream else None), "rt_scene_denoise_device")
 
+    def set_camera(self, cam: Optional[Camera]):
+        """Place the camera of every later call that generates camera rays (rt_scene_set_camera): tiles, passes, feature buffers,
+        camera_rays.  None: back to the reference camera.  Work already enqueued keeps the camera it was enqueued with."""
+        _abi.check(self._lib.rt_scene_set_camera(self._h, C.byref(cam) if cam is not None else None), "rt_scene_set_camera")
+
+    def camera_rays(self, req: TileRequest, begin: int = 0, end: Optional[int] = None, want_states: bool = True):
+        """The camera rays of a strip (rt_scene_camera_rays): for samples [begin, end) of the req.spp-sample job (end None: req.spp),
+        the ray the tile kernel traces first for each sample of each pixel, record (row W + x) (end - begin) + (s - begin).
+        Returns (rays, states, stats): a RAY_DTYPE array whose directions are to be traced as given, and the (n, 4) uint64
+        xoshiro256++ states after the camera's draws (None unless want_states) — the arguments of trace(..., as_given=True)."""
+        end = req.spp if end is None else end
+        n = (req.height // max(req.divisions, 1)) * req.width * max(end - begin, 0)     # (a bad request is refused by the library)
+        rays = np.empty(n, _abi.RAY_DTYPE)
+        states = np.empty((n, 4), np.uint64) if want_states else None
+        st = TileStats()
+        _abi.check(self._lib.rt_scene_camera_rays(self._h, C.byref(req), begin, end, rays.ctypes.data_as(C.POINTER(_abi.Ray)),
+                                                  states.ctypes.data_as(C.POINTER(C.c_uint64)) if want_states else None,
+                                                  C.byref(st)), "rt_scene_camera_rays")
+        return rays, states, st
+
+    def camera_rays_device(self, req: TileRequest, begin: int, end: int, d_rays: int, d_rng_state: int = 0, stream: int = 0):
+        """The camera rays of a strip on device buffers (rt_scene_camera_rays_device): Hs W (end - begin) rt_ray to d_rays and,
+        optionally, 4 uint64 per record to d_rng_state — e.g. the data_ptr() of torch tensors that trace_device / intersect_device
+        then read; asynchronous on `stream`, counters until collect()."""
+        vp = lambda ptr: C.c_void_p(ptr) if ptr else None
+        _abi.check(self._lib.rt_scene_camera_rays_device(self._h, C.byref(req), begin, end, vp(d_rays), vp(d_rng_state), vp(stream)),
+                   "rt_scene_camera_rays_device")
+
     def collect(self) -> TileStats:
         st = TileStats()
         _abi.check(self._lib.rt_scene_collect(self._h, C.byref(st)), "rt_scene_collect")
@@ -578,6 +606,10 @@ class FrameContext:
         _abi.check(self._lib.rt_frame_ctx_set_world(self._h, _abi.ptr(world.spheres), len(world.spheres),
                                                     _abi.ptr(world.triangles), len(world.triangles),
                                                     _abi.ptr(world.world_index)), "rt_frame_ctx_set_world")
+
+    def set_camera(self, cam: Optional[Camera]):
+        """The job's camera (rt_frame_ctx_set_camera): every later frame is rendered from it; None: the reference camera."""
+        _abi.check(self._lib.rt_frame_ctx_set_camera(self._h, C.byref(cam) if cam is not None else None), "rt_frame_ctx_set_camera")
 
     def render(self, req: TileRequest, out: Optional[np.ndarray] = None):
         """One frame.  `out`: a uint8 array of H*W*3 bytes to write into (the SAME array frame after frame keeps its
