@@ -117,7 +117,7 @@ enum DebugKnob {
     DBG_LDS_TREE = 0,      // RT_LDS_TREE        0: never the LDS-resident tree engine                      (default 1)
     DBG_CULL_WALK,         // RT_CULL_WALK       0 / 1: culled walk off / on wherever it is valid; -1: host rule (default -1)
     DBG_NO_STAGE,          // RT_NO_STAGE        1: no LDS output staging                                   (default 0)
-    DBG_SLOTS,             // RT_SLOTS           sample units: pixel slots per wave (<= 32); 0: host rule                  (default 0)
+    DBG_SLOTS,             // RT_SLOTS           sample units: pixel slots per wave, 1 ... 32 (more: 32); <= 0: host rule    (default 0)
     DBG_FORCE_CAPPED,      // RT_FORCE_CAPPED    1: quantised walks take the capped-stack kernel             (default 0)
     DBG_STACK_LDS,         // RT_STACK_LDS       capped-stack kernel: stack entries per lane in LDS; 0: STACK_LDS_MAX
     DBG_COMPACT,           // RT_COMPACT         0: per-lane root tests in the exact-node L2 kernel          (default 1)
@@ -2425,7 +2425,10 @@ int rt_frame_ctx_render_impl(rt_frame_ctx* fc, const rt_tile_request* rq_in, uin
         fc->cost_rq = rq0;
         fc->cost_pose = fc->pose;
         fc->cost_has_pose = fc->has_pose;
-        fc->cost_valid = true;
+        // (nothing counted — RT_STRIP_COST=0, or a frame without a ray — is no measurement: the next frame is a snake frame again)
+        unsigned long long cost_sum = 0ull;
+        for (unsigned long long c : fc->cost_now) cost_sum += c;
+        fc->cost_valid = dbg(DBG_STRIP_COST) != 0 && cost_sum > 0ull;
     }
     rt_frame_stats fs;
     std::memset(&fs, 0, sizeof fs);

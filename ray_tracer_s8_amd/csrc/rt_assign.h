@@ -23,10 +23,16 @@ namespace rtassign {
 
 enum Mode : uint32_t { STATIC_MOD = 0, SNAKE = 1, BY_COST = 2, QUEUE = 3 };
 
-// owner[k] = entry of strip k.  cost: nullptr, or one non-negative value per strip.
+// owner[k] = entry of strip k.  cost: nullptr, or one non-negative value per strip.  BY_COST over costs that sum to 0 (nothing was
+// measured: the kernels' counting was off) is SNAKE: longest-first would put every strip on entry 0, no load ever being below another.
 inline void assign(uint32_t divisions, uint32_t n_entries, const double* cost, Mode mode, std::vector<uint32_t>& owner) {
     owner.assign(divisions, 0u);
     if (n_entries <= 1u) return;
+    if (mode == BY_COST && cost) {
+        double tot = 0.0;
+        for (uint32_t k = 0; k < divisions; k++) tot += cost[k];
+        if (!(tot > 0.0)) mode = SNAKE;
+    }
     if (mode == STATIC_MOD || (mode == BY_COST && !cost)) {
         for (uint32_t k = 0; k < divisions; k++) owner[k] = k % n_entries;
         return;

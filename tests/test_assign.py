@@ -102,3 +102,18 @@ def test_longest_first_is_deterministic_and_breaks_ties_low(lib):
 def test_by_cost_without_costs_falls_back_to_round_robin(lib):
     owner, _ = assign(lib, 9, 4, None, BY_COST)
     assert owner.tolist() == [k % 4 for k in range(9)]
+
+
+@pytest.mark.parametrize("div,n", [(32, 8), (9, 4), (48, 8), (5, 8)])
+def test_by_cost_with_all_zero_costs_is_the_snake(lib, div, n):
+    """Costs that sum to 0 are no measurement (the kernels' counting was off): longest-first would send every strip to entry 0,
+    because no load is ever below another.  The owners must be the snake's."""
+    snake, _ = assign(lib, div, n, None, SNAKE)
+    owner, mom = assign(lib, div, n, np.zeros(div), BY_COST)
+    assert owner.tolist() == snake.tolist() and mom == 0.0
+    assert len(set(owner.tolist())) == min(div, n)
+    # one strip with a cost is a measurement again: longest-first
+    cost = np.zeros(div)
+    cost[div - 1] = 1.0
+    owner, _ = assign(lib, div, n, cost, BY_COST)
+    assert owner[div - 1] == 0

@@ -157,6 +157,25 @@ def test_plan_boundaries(lib, W, R):
                 assert p["wg"][i] == 8
 
 
+@pytest.mark.parametrize("W,R", [(67, 12), (129, 40)])
+def test_plan_of_every_lds_step_the_gpu_sweep_sets(lib, W, R):
+    """RT_DENOISE_LDS_STEP as tests/test_gpu_knobs.py sweeps it, five iterations: steps up to the knob are staged in LDS wherever the
+    window fits a CU's 160 KiB, larger ones gather through L2; the guided window of step 16 (278 528 bytes) never fits."""
+    lds_cu = int(lib.dn_lds_cu())
+    assert lds_cu == 160 * 1024 and lib.dn_lds_max_step_default() == 2
+    for guided in (False, True):
+        win = [(64 + 4 * s) * (4 + 4 * s) * 16 * (2 if guided else 1) for s in (1, 2, 4, 8, 16)]
+        assert win[4] == (278528 if guided else 139264)
+        for knob in (0, 1, 4, 8, 16):
+            p = _plan(lib, W, R, 5, guided, knob)
+            assert p["step"][:5] == [1, 2, 4, 8, 16]
+            for i, s in enumerate(p["step"][:5]):
+                assert p["lds"][i] == (win[i] if s <= knob and win[i] <= lds_cu else 0), (guided, knob, s)
+        assert _plan(lib, W, R, 5, guided, 16)["lds"][4] == (0 if guided else 139264)
+        assert _plan(lib, W, R, 5, guided, 8)["lds"][:5] == win[:4] + [0]
+        assert not any(_plan(lib, W, R, 5, guided, 0)["lds"])
+
+
 def test_scratch_bytes_of_the_library_match_the_plan(lib):
     from ray_tracer_s8_amd import _abi
     l = _abi.load()

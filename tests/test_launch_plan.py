@@ -11,6 +11,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import _knob_matrix as M
+
 ROOT = Path(__file__).resolve().parents[1]
 CSRC = ROOT / "ray_tracer_s8_amd" / "csrc"
 SRC = ROOT / "tests" / "host" / "plan_host.cpp"
@@ -423,3 +425,61 @@ def test_sixteenths_from_33_spp_and_the_31_bit_limit(lib):
 def test_too_many_tiles(lib):
     assert plan(lib, scene(1), width=64, height=2 ** 29 - 1)["status"] == RT_OK
     assert plan(lib, scene(1), width=64, height=2 ** 29)["status"] == RT_ERR_LIMIT
+
+
+# ---------------------------------------------------------------------------------------------------- the GPU knob matrix
+
+
+@pytest.mark.parametrize("rq_name", list(M.REQUESTS))
+def test_knob_matrix_tuples_stay_inside_the_kernels_domain(lib, rq_name):
+    """Every (request, strips, setting) tests/test_gpu_knobs.py launches (tests/_knob_matrix.py), as the 256-thread kernels and as the
+    1024-thread LDS-tree kernels plan it, on a grid of one workgroup and on a full chip's, the progressive passes included: the
+    slots and the queue stay inside what the kernel supports, the sample units are the ones the matrix says each request
+    reaches, and the queue has whole-tile entries exactly where the matrix claims them (RT_TAIL_TILES 0 and 1)."""
+    slots_max = int(K(lib, "SLOTS_MAX"))
+    w, h, spp, grp, units = M.REQUESTS[rq_name]
+    pw, ph, pspp, passes = M.PASS_JOB
+    launches = [(w, h, spp, n, None) for n in (M.DIVISIONS, 1)]
+    if rq_name == list(M.REQUESTS)[0]:
+        launches += [(pw, ph, pspp, 1, p) for p in passes]
+    seen_big = set()
+    for sh, block in ((scene(1), "BLOCK"), (scene(1000, cull_density=0.1), "LTREE_BLOCK")):
+        for grid in (1, 256 * 8):
+            for (fw, fh, fspp, n_strips, pass_range), setting in ((l, s) for l in launches for s in M.SETTINGS):
+                kn = M.plan_knobs(setting)
+                r = plan(lib, sh, width=fw, height=fh, divisions=M.DIVISIONS, spp=fspp, max_bounces=M.MAX_BOUNCES, n_strips=n_strips,
+                         pass_range=pass_range, grid=grid, **kn)
+                what = (rq_name, n_strips, pass_range, setting, block, grid)
+                assert r["status"] == RT_OK and r["block"] == K(lib, block), what
+                assert 1 <= r["commit_slots"] <= r["n_slots"] <= slots_max, what
+                assert r["n_slots"] == kn.get("slots", r["n_slots"]) and r["commit_slots"] == min(kn.get("commit_slots", r["commit_slots"]), r["n_slots"]), what
+                assert 1 <= r["refill_eighths"] <= 8, what
+                total = r["tiles_total"]
+                assert total == (fw + 63) // 64 * (fh // M.DIVISIONS) * n_strips, what
+                assert r["n_tiles"] == r["tiles_big"] + ((total - r["tiles_big"]) << r["sub_shift"]), what
+                assert r["tiles_big"] == {"none": 0, "all": total, "all_but_one": total - 1}[M.SETTINGS[setting][2]], what
+                assert r["sub_shift"] == (4 if r["upp"] > 32 else 2), what
+                seen_big.add(r["tiles_big"] > 0)
+                if pass_range is None:
+                    assert (r["upp"], r["grp"], r["slot_stride"] - 1) == (spp, grp, units), what
+                else:
+                    assert (r["upp"], r["s_begin"], r["gap"], r["acc_out"]) == (pass_range[1] - pass_range[0], pass_range[0],
+                                                                                 fspp - r["upp"], 1), what
+    assert seen_big == {False, True}
+
+
+def test_knob_matrix_covers_every_kernel_family():
+    """Every setting runs on at least one engine of every kernel family it applies to: the ones every engine takes (slots, commit
+    threshold, queue split, strip costs, the two combined ones) on all seven families, the refill threshold on every walk, output
+    staging on every kernel it is compiled into, the compacted root tests on the exact-node L2 walks."""
+    families = set(M.FAMILY.values())
+    assert len(families) == 7 and set(M.FAMILY) == set(M.ENGINE_KEYS)
+    walks = families - {"resident scan", "streamed scan"}
+    staging = families - {"resident scan", "LDS tree", "LDS tree culled"}
+    for name, (knobs, engines, _) in M.SETTINGS.items():
+        assert set(knobs) <= set(M.PLAN_KNOB) | {"RT_STRIP_COST"}, name
+        want = families
+        if name not in ("starved", "wide"):
+            want = {"L2 exact"} if "RT_COMPACT" in knobs else staging if "RT_NO_STAGE" in knobs else walks if "RT_REFILL_EIGHTHS" in knobs else families
+        assert {M.FAMILY[e] for e in engines} == want, name
+    assert M.settings_for(0)[0] == "default" and M.SLOTS_MIN == 1
