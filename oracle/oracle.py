@@ -227,6 +227,28 @@ def trace_batch(spheres, triangles, rays, spp=1, max_bounces=10, backend=0, worl
     return rgb, segs, st
 
 
+# operand-level batch (rt_oracle_operands_batch): families and 32-bit words per record in / out
+SPHERE, SPHERE_NORM, TRIANGLE, AABB, CHAIN, NORMALIZE, AS_U8, RNG = range(8)
+OPERAND_WORDS = {SPHERE: (12, 2), SPHERE_NORM: (12, 5), TRIANGLE: (17, 2), AABB: (12, 3), CHAIN: (18, 3), NORMALIZE: (3, 7),
+                 AS_U8: (1, 1), RNG: (2, 28)}
+
+
+def operands_batch(family: int, records, nthreads: int = 0):
+    """Record i of `records` ((n, words_in) float32 or uint32, taken bit for bit) through the reference's form of `family`
+    (rt_oracle.cpp rt_oracle_operands_batch lists the layouts); returns (n, words_out) uint32."""
+    wi, wo = OPERAND_WORDS[family]
+    r = np.ascontiguousarray(records)
+    if r.dtype.itemsize != 4 or r.ndim != 2 or r.shape[1] != wi:
+        raise ValueError(f"records: (n, {wi}) 32-bit words")
+    out = np.zeros((len(r), wo), np.uint32)
+    lib = load()
+    lib.rt_oracle_operands_batch.restype = C.c_int
+    rc = lib.rt_oracle_operands_batch(C.c_int(family), _p(r), C.c_uint64(len(r)), C.c_int(nthreads), _p(out))
+    if rc != 0:
+        raise ValueError(f"rt_oracle_operands_batch: bad arguments ({rc})")
+    return out
+
+
 def sky(direction):
     out = np.zeros(3, np.float32)
     load().rt_oracle_sky(_p(_f3(direction)), _p(out))
@@ -258,6 +280,16 @@ def bvh_traverse_boxes(boxes, origin, direction):
     n = load().rt_oracle_bvh_traverse_boxes(_p(b), C.c_uint32(len(b)), _p(_f3(origin)), _p(_f3(direction)), _p(out),
                                             C.c_uint32(len(out)), C.byref(nn))
     return out[:n].tolist(), nn.value
+
+
+def bvh_dump(boxes):
+    """The oracle's tree over raw boxes: (topo (nodes, 4) uint32: leaf, shape index, left, right; child_boxes (nodes, 2, 6) float32)."""
+    b = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 6)
+    cap = max(2 * len(b), 1)
+    topo, cb = np.zeros((cap, 4), np.uint32), np.zeros((cap, 2, 6), np.float32)
+    nn = load().rt_oracle_bvh_dump(_p(b), C.c_uint32(len(b)), _p(topo), _p(cb), C.c_uint32(cap))
+    assert 0 <= nn <= cap
+    return topo[:nn], cb[:nn]
 
 
 def aabb_kat(a6, b6, point):

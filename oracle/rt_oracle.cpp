@@ -1047,6 +1047,100 @@ __attribute__((visibility("default"))) int rt_oracle_trace_batch(const rt_sphere
     });
     return 0;
 }
+// ---- operand-level batch: record i in gives record i out, no scene -----------------------------------------------------------
+// The single-call probes above (sphere / triangle roots + select_t, intersects_aabb, the glam normalisations, `as u8`, seed_from_u64
+// and the draws), one record per call, spread over threads like rt_oracle_intersect_batch.  Records are 32-bit words; the families and
+// their layouts are those of the device unit kernel (ray_tracer_s8_amd/csrc/rt_unit.hip.h), so that a test compares word for word:
+//   0 SPHERE       in 12: o d cen r t_min t_max        out 2: hit, t            the direction taken bit for bit (ray_as_given)
+//   1 SPHERE_NORM  in 12: the same                     out 5: hit, t, Ray::new's direction
+//   2 TRIANGLE     in 17: o d A B C t_min t_max        out 2: hit, t            the direction taken bit for bit
+//   3 AABB         in 12: o d lo hi                    out 3: intersects_aabb, the same again, "every inverse component finite"
+//   4 CHAIN        in 18: o d leaf lo hi outer lo hi   out 3: intersects_aabb(leaf), intersects_aabb(outer), finite as above
+//   5 NORMALIZE    in  3: v                            out 7: normalize(v), try_normalize(v).is_some(), normalize_or_zero(v)
+//   6 AS_U8        in  1: v                            out 1: v as u8
+//   7 RNG          in  2: seed (low, high word)        out 28: seed_from_u64's state (4 x low, high), 4 next_u32, 4 value0_1 draws
+//                                                              ([1,2) mantissa - 1), 4 Uniform(-1,1) draws, the final state
+// t is 0 where hit is 0.  Returns 0, -1 for bad arguments.
+__attribute__((visibility("default"))) int rt_oracle_operands_batch(int family, const uint32_t* in, uint64_t n, int nthreads,
+                                                                    uint32_t* out) {
+    static const int WIN[8] = {12, 12, 17, 12, 18, 3, 1, 2}, WOUT[8] = {2, 5, 2, 3, 3, 7, 1, 28};
+    if (family < 0 || family > 7 || (n && (!in || !out))) return -1;
+    const int wi = WIN[family], wo = WOUT[family];
+    for_units(n, nthreads, [&](uint64_t first, uint64_t last) {
+        for (uint64_t i = first; i < last; i++) {
+            const uint32_t* r = in + i * wi;
+            uint32_t* w = out + i * wo;
+            auto F = [&](int k) { float f; std::memcpy(&f, r + k, 4); return f; };
+            auto V = [&](int k) { return v3(F(k), F(k + 1), F(k + 2)); };
+            auto putf = [&](int k, float f) { std::memcpy(w + k, &f, 4); };
+            auto put3 = [&](int k, V3 v) { putf(k, v.x); putf(k + 1, v.y); putf(k + 2, v.z); };
+            auto finite_inv = [&](const Ray& ray) {
+                return std::isfinite(ray.inv_direction.x) && std::isfinite(ray.inv_direction.y) && std::isfinite(ray.inv_direction.z);
+            };
+            switch (family) {
+                case 0:
+                case 1: {
+                    const Ray ray = family == 1 ? ray_new(V(0), V(3)) : ray_as_given(V(0), V(3));
+                    rt_sphere s{};
+                    s.cx = F(6); s.cy = F(7); s.cz = F(8); s.radius = F(9);
+                    float t = 0.0f;
+                    const bool hit = select_t(Window{F(10), F(11)}, sphere_get_roots(s, ray), &t);
+                    w[0] = hit ? 1u : 0u;
+                    putf(1, hit ? t : 0.0f);
+                    if (family == 1) put3(2, ray.direction);
+                    break;
+                }
+                case 2: {
+                    const Ray ray = ray_as_given(V(0), V(3));
+                    rt_triangle tr{};
+                    for (int k = 0; k < 3; k++) { tr.a[k] = F(6 + k); tr.b[k] = F(9 + k); tr.c[k] = F(12 + k); }
+                    float t = 0.0f;
+                    const bool hit = select_t(Window{F(15), F(16)}, triangle_get_roots(tr, ray), &t);
+                    w[0] = hit ? 1u : 0u;
+                    putf(1, hit ? t : 0.0f);
+                    break;
+                }
+                case 3: {
+                    const Ray ray = ray_as_given(V(0), V(3));
+                    const bool p = intersects_aabb(ray, AABB{V(6), V(9)});
+                    w[0] = w[1] = p ? 1u : 0u;
+                    w[2] = finite_inv(ray) ? 1u : 0u;
+                    break;
+                }
+                case 4: {
+                    const Ray ray = ray_as_given(V(0), V(3));
+                    w[0] = intersects_aabb(ray, AABB{V(6), V(9)}) ? 1u : 0u;
+                    w[1] = intersects_aabb(ray, AABB{V(12), V(15)}) ? 1u : 0u;
+                    w[2] = finite_inv(ray) ? 1u : 0u;
+                    break;
+                }
+                case 5: {
+                    V3 tn;
+                    put3(0, normalize(V(0)));
+                    w[3] = try_normalize(V(0), &tn) ? 1u : 0u;
+                    put3(4, normalize_or_zero(V(0)));
+                    break;
+                }
+                case 6:
+                    w[0] = f32_as_u8(F(0));
+                    break;
+                default: {
+                    Rng g = seed_from_u64((uint64_t)r[0] | ((uint64_t)r[1] << 32));
+                    auto put_state = [&](int k) {
+                        for (int j = 0; j < 4; j++) { w[k + 2 * j] = (uint32_t)g.s[j]; w[k + 2 * j + 1] = (uint32_t)(g.s[j] >> 32); }
+                    };
+                    put_state(0);
+                    for (int j = 0; j < 4; j++) w[8 + j] = next_u32(g);
+                    for (int j = 0; j < 4; j++) putf(12 + j, u01_from_u32(next_u32(g)));
+                    for (int j = 0; j < 4; j++) putf(16 + j, uniform_m1_1(g));
+                    put_state(20);
+                    break;
+                }
+            }
+        }
+    });
+    return 0;
+}
 __attribute__((visibility("default"))) void rt_oracle_sky(const float* dir, float* out_rgb) {
     Color c = sky(arr3(dir));
     out_rgb[0] = c.r;
@@ -1117,6 +1211,28 @@ __attribute__((visibility("default"))) int rt_oracle_ray_intersects_aabb_flipped
     r.direction = v3(-r.direction.x, -r.direction.y, -r.direction.z);
     r.inv_direction = v3(-r.inv_direction.x, -r.inv_direction.y, -r.inv_direction.z);
     return intersects_aabb(r, AABB{v3(box6[0], box6[1], box6[2]), v3(box6[3], box6[4], box6[5])}) ? 1 : 0;
+}
+// The oracle's tree over raw AABBs as arrays, for structural checks (tests/test_bvh_structure.py): node k gives
+// topo[4 k ..] = leaf (0/1), shape index, left child, right child and child_boxes[12 k ..] = left min xyz, max xyz, right min xyz, max xyz
+// (zeros for a leaf).  Returns the number of nodes (at most cap_nodes are written).
+__attribute__((visibility("default"))) int rt_oracle_bvh_dump(const float* boxes, uint32_t n, uint32_t* topo, float* child_boxes,
+                                                              uint32_t cap_nodes) {
+    std::vector<AABB> bs(n);
+    for (uint32_t i = 0; i < n; i++)
+        bs[i] = AABB{v3(boxes[6 * i], boxes[6 * i + 1], boxes[6 * i + 2]), v3(boxes[6 * i + 3], boxes[6 * i + 4], boxes[6 * i + 5])};
+    const BVH b = bvh_build(bs);
+    for (size_t k = 0; k < b.nodes.size() && k < cap_nodes; k++) {
+        const BVHNode& nd = b.nodes[k];
+        topo[4 * k] = nd.leaf ? 1u : 0u;
+        topo[4 * k + 1] = nd.shape_index;
+        topo[4 * k + 2] = nd.child_l;
+        topo[4 * k + 3] = nd.child_r;
+        const AABB z{v3(0.f, 0.f, 0.f), v3(0.f, 0.f, 0.f)};
+        const AABB &l = nd.leaf ? z : nd.child_l_aabb, &r = nd.leaf ? z : nd.child_r_aabb;
+        const float v[12] = {l.mn.x, l.mn.y, l.mn.z, l.mx.x, l.mx.y, l.mx.z, r.mn.x, r.mn.y, r.mn.z, r.mx.x, r.mx.y, r.mx.z};
+        std::memcpy(child_boxes + 12 * k, v, sizeof v);
+    }
+    return (int)b.nodes.size();
 }
 // BVH over raw AABBs (n boxes, 6 floats each: min xyz, max xyz); traverse one ray; returns
 // number of candidate shape indices written to out_idx (DFS leaf order), capacity cap.

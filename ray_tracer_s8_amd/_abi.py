@@ -224,6 +224,8 @@ def load_debug() -> C.CDLL:
         _dbg_lib = _bind(_build.build_debug())
         _dbg_lib.rt_debug_set.argtypes = [C.c_char_p, C.c_int]
         _dbg_lib.rt_debug_set.restype = C.c_int
+        _dbg_lib.rt_debug_unit.argtypes = [C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_void_p, C.c_void_p]
+        _dbg_lib.rt_debug_unit.restype = C.c_int
     return _dbg_lib
 
 

@@ -52,7 +52,7 @@ UNITS = [
 
 
 def _deps() -> list[Path]:
-    return [CSRC / u for u, _ in UNITS] + [CSRC / "rt_kernel.hip.h", CSRC / "rt_query.hip.h", CSRC / "rt_trace.hip.h", CSRC / "rt_aov.hip.h", CSRC / "rt_camera.hip.h", CSRC / "rt_denoise.hip.h", CSRC / "rt_denoise_math.h", CSRC / "rt_consts.h", CSRC / "rt_plan.h", CSRC / "rt_cull.h", CSRC / "rt_bvh.h",
+    return [CSRC / u for u, _ in UNITS] + [CSRC / "rt_kernel.hip.h", CSRC / "rt_unit.hip.h", CSRC / "rt_query.hip.h", CSRC / "rt_trace.hip.h", CSRC / "rt_aov.hip.h", CSRC / "rt_camera.hip.h", CSRC / "rt_denoise.hip.h", CSRC / "rt_denoise_math.h", CSRC / "rt_consts.h", CSRC / "rt_plan.h", CSRC / "rt_cull.h", CSRC / "rt_bvh.h",
                                             CSRC / "rt_assign.h", ROOT / "include" / "rt_tile.h",
                                             Path(__file__)]
 
@@ -60,8 +60,8 @@ def _deps() -> list[Path]:
 FLAGS_PATH = LIB_PATH.with_suffix(".flags")      # the exact compile lines of the library next to it
 
 # The TEST library: the product sources plus -DRT_DEBUG_HOOKS, which compiles the rt_debug_* entry points (launch-path knobs,
-# counter read-back, a throwing body, the sqrt self-test) that tests and tools use.  The product library exports exactly
-# include/rt_tile.h (tests/test_abi.py checks both).
+# counter read-back, a throwing body, the sqrt self-test, the unit kernel of rt_unit.hip.h) that tests and tools use.
+# The product library exports exactly include/rt_tile.h (tests/test_abi.py checks both).
 DEBUG_VARIANT = "dbg"
 DEBUG_FLAGS = ["-DRT_DEBUG_HOOKS"]
 DEBUG_LIB_PATH = LIB_DIR / f"librt_s8_{DEBUG_VARIANT}.so"

@@ -33,6 +33,9 @@
 #include "rt_camera.hip.h"
 #include "rt_denoise.hip.h"
 #include "rt_tile.h"
+#ifdef RT_DEBUG_HOOKS
+#include "rt_unit.hip.h"      // record sizes and launchers of the unit kernel (rt_debug_unit)
+#endif
 
 namespace {
 
@@ -1989,6 +1992,34 @@ extern "C" __attribute__((visibility("default"))) int rt_debug_sqrt_selftest(int
         }
         if (e == hipSuccess) e = hipMemcpy(mismatches, d_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost);
         (void)hipFree(d_bad);
+        if (e != hipSuccess) return fail(RT_ERR_HIP, hipGetErrorString(e));
+        return RT_OK;
+    });
+}
+// debug: the device functions of the closest-hit arithmetic, one lane per record (rt_unit.hip.h: families and record layouts), as
+// translation unit `unit` compiles them (0 lin, 1 trav, 2 query).  in: n records of unit_words_in(family) 32-bit words, out: n records
+// of unit_words_out(family) words; one launch, returns after synchronising.  Tests only; not part of rt_tile.h.
+extern "C" __attribute__((visibility("default"))) int rt_debug_unit(int device, int unit, int family, unsigned long long n,
+                                                                    const void* in, void* out) {
+    return guarded([&]() -> int {
+        if (unit < 0 || unit > 2 || family < 0 || family >= rtk::UNIT_FAMILIES) return fail(RT_ERR_BAD_ARG, "unit / family");
+        if (n == 0) return RT_OK;
+        if (!in || !out || n > (1ull << 24)) return fail(RT_ERR_BAD_ARG, "unit records");
+        const size_t bi = (size_t)n * rtk::unit_words_in(family) * 4, bo = (size_t)n * rtk::unit_words_out(family) * 4;
+        HIPCHK(hipSetDevice(device));
+        uint32_t *d_in = nullptr, *d_out = nullptr;
+        hipError_t e = hipMalloc(&d_in, bi);
+        if (e == hipSuccess) e = hipMalloc(&d_out, bo);
+        if (e == hipSuccess) e = hipMemcpy(d_in, in, bi, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(d_out, 0, bo);
+        if (e == hipSuccess) {
+            (unit == 0 ? rtk::unit_launch_lin : unit == 1 ? rtk::unit_launch_trav : rtk::unit_launch_query)(family, n, d_in, d_out, 0);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemcpy(out, d_out, bo, hipMemcpyDeviceToHost);
+        (void)hipFree(d_in);
+        (void)hipFree(d_out);
         if (e != hipSuccess) return fail(RT_ERR_HIP, hipGetErrorString(e));
         return RT_OK;
     });

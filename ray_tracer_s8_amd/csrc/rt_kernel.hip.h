@@ -409,8 +409,13 @@ __device__ __forceinline__ bool intersects_aabb(V3 o, const RayAux& a, float4 lo
 }
 // The same test for a ray whose inverse direction is finite (RayAux::finite): then inv has the sign of the
 // direction, lo <= hi gives (lo-o)*inv <= (hi-o)*inv for inv > 0 and >= for inv < 0 under monotone rounding, so
-// the sign-selected ray_min / ray_max are the min / max of the two products, no NaN can arise (no 0*inf), and
+// the sign-selected ray_min / ray_max are the min / max of the two products, no 0*inf can arise, and
 // min/max differ from the crate's `if x < y` forms only in the sign of a zero, which no comparison sees.
+// NOT the same for a NaN slab product, which a finite inverse direction still allows (a NaN origin component,
+// inf - inf): the crate's forms keep a NaN that is their second operand (the verdict is then no), fminf / fmaxf
+// always drop it (possibly yes).  No hit depends on that: such an origin makes every sphere's discriminant and
+// every triangle's u NaN, so the extra candidates are misses (tests/test_gpu_operands.py test_both_box_tests;
+// the counter-examples are directed records of tests/_operand_cases.py).
 __device__ __forceinline__ bool intersects_aabb_finite(V3 o, const RayAux& a, float4 lo, float4 hi) {
     const float x0 = (lo.x - o.x) * a.inv.x, x1 = (hi.x - o.x) * a.inv.x;
     const float y0 = (lo.y - o.y) * a.inv.y, y1 = (hi.y - o.y) * a.inv.y;
@@ -438,6 +443,11 @@ __device__ __forceinline__ void slabs_finite(V3 o, const RayAux& a, float4 lo, f
 // sign the slab selection uses; the custom min/max are monotone for non-NaN operands and no 0*inf can
 // occur.  Hence ray_min_a <= ray_min_leaf and ray_max_a >= ray_max_leaf: if the leaf's own box passes,
 // every ancestor passes.  Only when a direction component is +-0 (inv = +-inf) is the chain walked.
+// Premise: no NaN slab product other than from a NaN origin component.  That one falls on the same axis, in the
+// same operand position, for the leaf and for every ancestor, and the crate's min / max treat it alike in both
+// (tests/test_gpu_operands.py test_leaf_box_passing_implies_outer_box_passing has such records).  inf - inf (an
+// infinite origin component against an equal box plane) can differ between leaf and ancestor: there the shortcut
+// may admit a candidate the walked chain rejects, and that candidate misses (see intersects_aabb_finite).
 __device__ __forceinline__ bool bvh_reaches(const float4* __restrict__ nodes, uint32_t node, V3 o, const RayAux& a) {
     const bool finite_inv = a.finite;
     for (;;) {

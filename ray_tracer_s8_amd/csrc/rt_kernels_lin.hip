@@ -15,3 +15,9 @@ KernelFn kernel_linear(int isect, bool expanded) {
     }
 }
 }  // namespace rtk
+
+// the unit kernel of the closest-hit arithmetic as THIS unit compiles it (test library only; tests/test_gpu_operands.py)
+#ifdef RT_DEBUG_HOOKS
+#define RT_UNIT_ID 0
+#include "rt_unit.hip.h"
+#endif

@@ -11,3 +11,9 @@ QueryFn query_kernel(int engine, int scan_mode, bool any) {
     return nullptr;
 }
 }  // namespace rtk
+
+// the unit kernel of the closest-hit arithmetic as THIS unit compiles it (test library only; tests/test_gpu_operands.py)
+#ifdef RT_DEBUG_HOOKS
+#define RT_UNIT_ID 2
+#include "rt_unit.hip.h"
+#endif

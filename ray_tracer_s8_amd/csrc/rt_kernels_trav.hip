@@ -43,3 +43,9 @@ void sqrt_selftest_launch(uint32_t from, unsigned long long n, unsigned long lon
     hipLaunchKernelGGL(sqrt_selftest_kernel, dim3(4096), dim3(256), 0, st, from, n, d_bad);
 }
 }  // namespace rtk
+
+// the unit kernel of the closest-hit arithmetic as THIS unit compiles it (test library only; tests/test_gpu_operands.py)
+#ifdef RT_DEBUG_HOOKS
+#define RT_UNIT_ID 1
+#include "rt_unit.hip.h"
+#endif

@@ -5,6 +5,7 @@
 // over rtbvh::TravNode exactly as the exact-node kernel does.
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "rt_bvh.h"
@@ -164,6 +165,21 @@ int host_bvh_check(const float* boxes, uint32_t n, uint32_t* out) {
             }
     }
     return 0;
+}
+
+// The flat tree as arrays, for the structural checks of tests/test_bvh_structure.py.  flat[8 k ..] = node k's lo xyz, parent (bits),
+// hi xyz, 0; trav[16 k ..] = internal node k as TravNode stores it (l_lo, left, l_hi, right, r_lo, 0, r_hi, 0: references as bits);
+// leaf_of[n]; meta = nodes, internal nodes, root reference, depth.  The caller sizes flat for 2 n - 1 and trav for n - 1 nodes.
+void host_bvh_dump(const float* boxes, uint32_t n, float* flat, float* trav, uint32_t* leaf_of, uint32_t* meta) {
+    const rtbvh::FlatBVH t = rtbvh::build(to_boxes(boxes, n));
+    static_assert(sizeof(rtbvh::FlatNode) == 32 && sizeof(rtbvh::TravNode) == 64, "node layouts");
+    if (!t.nodes.empty()) memcpy(flat, t.nodes.data(), t.nodes.size() * sizeof(rtbvh::FlatNode));
+    if (!t.trav.empty()) memcpy(trav, t.trav.data(), t.trav.size() * sizeof(rtbvh::TravNode));
+    for (uint32_t i = 0; i < n; i++) leaf_of[i] = t.leaf_of[i];
+    meta[0] = (uint32_t)t.nodes.size();
+    meta[1] = (uint32_t)t.trav.size();
+    meta[2] = t.root_ref;
+    meta[3] = t.depth;
 }
 
 // The product's AABB helpers (rt_bvh.h) on raw boxes, for the reference's own doc-test vectors (aabb.rs:453,474,520,565;

@@ -50,7 +50,7 @@ def test_product_library_exports_exactly_the_header():
     dbg = _exported(build.DEBUG_LIB_PATH)
     assert set(declared_functions()) < dbg
     assert {n for n in dbg if n.startswith("rt_debug_")} == {"rt_debug_read_counters", "rt_debug_sqrt_selftest", "rt_debug_set",
-                                                              "rt_debug_throw"}
+                                                              "rt_debug_throw", "rt_debug_unit"}
 
 
 def test_abi_version_is_one_number_everywhere():
