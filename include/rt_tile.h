@@ -419,6 +419,72 @@ RT_API int rt_scene_trace(rt_scene* scene, const rt_trace_request* req, const rt
 RT_API int rt_scene_trace_device(rt_scene* scene, const rt_trace_request* req, const void* d_rays, uint32_t n,
                                  void* d_rng_state, void* d_out_rgb, void* d_out_segments, void* hip_stream);
 
+/* ---- path steps: one ray_color bounce for the caller's rays, with compaction -------- */
+/* ONE entry of ray_color with depth > 0 (ray-tracer-slave/src/main.rs:108-146) as a call of its own: the hit, the shade and the
+ * scatter of one segment of every active ray of a batch, for an integrator of the caller's own between the segments — next-event
+ * estimation with RT_QUERY_ANY shadow rays, Russian roulette, per-bounce feature buffers, path-length filters, throughput clamps,
+ * another sky — on this library's BVH, root tests and shading arithmetic.  The ray and its RNG state are updated in place, and a
+ * device-side list of the rays that scattered comes back: the next step's active list, so that every wave of every step is full
+ * of live rays.  K steps folded by the caller reproduce rt_scene_trace bit for bit (below).
+ *
+ * Per active ray i (rt_ray above); the window [t_min, t_max) is the ray's own and is kept:
+ *   - Closest hit: the hit rt_scene_intersect finds under the same flags.  ray_form RT_TRACE_RAY_NEW: the direction is normalised
+ *     by division first (Ray::new, B/ray.rs:133-143); RT_TRACE_RAY_AS_GIVEN: it is taken bit for bit.  The ray a step writes back
+ *     must be stepped AS_GIVEN (normalising twice is not idempotent in f32).
+ *   - RT_BOUNCE_MISSED: rgb = the sky of normalize_or_zero(d).y (main.rs:135-144).  The ray and the state are unchanged.
+ *   - RT_BOUNCE_EMITTED (emission > 0, main.rs:116-117): rgb = albedo * emission.  The ray and the state are unchanged.
+ *   - RT_BOUNCE_SCATTERED: rgb = the albedo.  One UnitSphere draw is taken from state i (main.rs:119); the scattered direction is
+ *     diffuse + roughness (glossy - diffuse) (main.rs:120-122) through try_normalize with the normal as the fallback (main.rs:126),
+ *     then Ray::new's normalisation; its origin is exactly the hit point P.  The scattered ray is written over ray i, the advanced
+ *     state over state i: operation for operation what rt_scene_trace does between two segments.
+ *   - out_hits (optional): the rt_hit of RT_QUERY_CLOSEST for the INCOMING ray; on a miss the miss record.
+ *   - seed_states = 1: state i = SmallRng::seed_from_u64(seed + 4 * 0x9E3779B97F4A7C15 * i) (wrapping u64: the seeded stream of
+ *     rt_scene_trace at spp = 1) is written over state i of every active ray first, whatever its status, and then stepped.
+ *     rng_state is required either way.
+ *   - Active list: active == NULL steps all n rays; otherwise n_active indices < n.  A ray that is not listed has no byte of its
+ *     ray, state, bounce or hit record touched.  Naming a ray twice is the caller's error.  The host form checks every index and
+ *     returns RT_ERR_BAD_ARG; the device form reads the length from *d_n_active ON THE DEVICE (no host synchronisation between
+ *     steps), steps min(n, *d_n_active) entries and skips an index >= n.  d_active and d_n_active are both NULL (all n rays) or
+ *     both given (n is then the upper bound the launch is sized from).
+ *   - Compaction: next_active (optional, capacity n) receives the indices of the SCATTERED rays and *n_next their number; n_next
+ *     alone counts them.  The library zeroes *n_next on the stream before the launch.  The SET is specified, its order is not (one
+ *     atomic append per wave); every per-ray result lives at the ray's own index, so no result depends on that order.
+ *   - Folding: the reference multiplies the albedos right to left (main.rs:123).  A caller who wants rt_scene_trace's bits keeps
+ *     the rgb of every step and folds a1 * (a2 * (... (ak * term))), term the rgb of the step that MISSED or EMITTED; a ray still
+ *     alive after the caller's last step folds term = 0, as the reference draws and then returns black (main.rs:119, 109-111).
+ *     max_bounces = K - 1 of rt_scene_trace is K steps.
+ *   - flags: as for rt_scene_intersect (a tree deeper than the walk's stack takes the scan; tile-only flags are ignored).
+ *   - RT_ERR_BAD_ARG, and nothing launched: a NULL scene, request, rays, rng_state or out_bounce; n == 0; ray_form > 1;
+ *     seed_states > 1; reserved != 0; next_active without n_next; one of active / n_active without the other; in the host form an
+ *     index >= n or n_active > n.
+ *   - Counters (rt_tile_stats): ray_segments = rays stepped; broad_candidates = exact root tests; primary_rays = 0; kernel_ms;
+ *     h2d_ms (rays, states, the active list) and d2h_ms (rays, states, bounces, hits, the next list and its count) of the host
+ *     form; n_launches; engine (as for rt_scene_intersect).
+ * No per-scene scratch on the device: launches on different streams may overlap.   */
+typedef struct rt_bounce { float r, g, b; uint32_t status; } rt_bounce;                       /* 16 bytes */
+enum { RT_BOUNCE_SCATTERED = 0u, RT_BOUNCE_EMITTED = 1u, RT_BOUNCE_MISSED = 2u };
+typedef struct rt_bounce_request {
+    uint32_t flags;             /* RT_FLAG_*, as for rt_scene_intersect                                    */
+    uint32_t ray_form;          /* RT_TRACE_RAY_NEW | RT_TRACE_RAY_AS_GIVEN                                */
+    uint32_t seed_states;       /* 1: first write state i = seed_from_u64(seed + 4*PHI*i), then step       */
+    uint32_t reserved;          /* 0                                                                       */
+    uint64_t seed;
+} rt_bounce_request;            /* 24 bytes */
+
+/* Host buffers, synchronous: rays (n) and rng_state (4 n u64) are read and written back; out_bounce (n) is required; active
+ * (n_active indices), out_hits (n), next_active (n) with n_next, and stats may be NULL.  Records of rays that are not active come
+ * back as they went in; out_bounce / out_hits entries of such rays are not written. */
+RT_API int rt_scene_bounce(rt_scene* scene, const rt_bounce_request* req, rt_ray* rays, uint32_t n, uint64_t* rng_state,
+                           const uint32_t* active, uint32_t n_active, rt_bounce* out_bounce, rt_hit* out_hits,
+                           uint32_t* next_active, uint32_t* n_next, rt_tile_stats* stats);
+/* Device buffers (n rt_ray, 4 n u64, n_active-capacity u32 list and its u32 length or both NULL, n rt_bounce, n rt_hit or NULL,
+ * n u32 or NULL, one u32 or NULL), asynchronous on hip_stream (NULL = the scene's stream); counters and event times accumulate in
+ * the scene until rt_scene_collect().  Ping-pong two lists: d_next_active / d_n_next of one step are d_active / d_n_active of the
+ * next. */
+RT_API int rt_scene_bounce_device(rt_scene* scene, const rt_bounce_request* req, void* d_rays, uint32_t n, void* d_rng_state,
+                                  const void* d_active, const void* d_n_active, void* d_bounce, void* d_hits,
+                                  void* d_next_active, void* d_n_next, void* hip_stream);
+
 /* ---- feature buffers (AOVs) of a strip: what the camera rays of the beauty image first hit ---- */
 /* Per-pixel feature buffers for a denoiser, edge-aware filters, picking and compositing, ALIGNED with the beauty image: they
  * come from the very camera rays (sub-pixel and lens samples) whose colours the tile entry points average, so the planes after

@@ -122,6 +122,24 @@ RT_TRACE_RAY_NEW = 0
 RT_TRACE_RAY_AS_GIVEN = 1
 
 
+class Bounce(C.Structure):
+    """rt_bounce: the colour factor of one path step (the albedo, albedo * emission or the sky) and its RT_BOUNCE_* status."""
+    _fields_ = [("r", C.c_float), ("g", C.c_float), ("b", C.c_float), ("status", C.c_uint32)]
+
+
+class BounceRequest(C.Structure):
+    """rt_bounce_request: RT_FLAG_*, the form of the incoming rays, whether the states are seeded first, and the seed."""
+    _fields_ = [("flags", C.c_uint32), ("ray_form", C.c_uint32), ("seed_states", C.c_uint32), ("reserved", C.c_uint32),
+                ("seed", C.c_uint64)]
+
+
+RT_BOUNCE_SCATTERED = 0
+RT_BOUNCE_EMITTED = 1
+RT_BOUNCE_MISSED = 2
+# numpy twin of rt_bounce (what Scene.bounce returns)
+BOUNCE_DTYPE = np.dtype([("r", "<f4"), ("g", "<f4"), ("b", "<f4"), ("status", "<u4")])
+
+
 class AovPlanes(C.Structure):
     """rt_aov_planes: the feature buffers of a strip (host or device pointers); a NULL plane is not computed."""
     _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("hits", C.c_void_p),
@@ -171,6 +189,7 @@ assert C.sizeof(TileStats) == 64
 assert C.sizeof(FrameStats) == 232
 assert C.sizeof(Ray) == C.sizeof(Hit) == RAY_DTYPE.itemsize == HIT_DTYPE.itemsize == 32
 assert C.sizeof(TraceRequest) == 24
+assert C.sizeof(BounceRequest) == 24 and C.sizeof(Bounce) == BOUNCE_DTYPE.itemsize == 16
 assert C.sizeof(AovPlanes) == 40
 assert C.sizeof(DenoiseRequest) == 40
 
@@ -303,6 +322,12 @@ def _bind(path: Path) -> C.CDLL:
     lib.rt_scene_trace.restype = C.c_int
     lib.rt_scene_trace_device.argtypes = [vp, C.POINTER(TraceRequest), vp, C.c_uint32, vp, vp, vp, vp]
     lib.rt_scene_trace_device.restype = C.c_int
+    lib.rt_scene_bounce.argtypes = [vp, C.POINTER(BounceRequest), C.POINTER(Ray), C.c_uint32, C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Bounce), C.POINTER(Hit), C.POINTER(C.c_uint32),
+                                    C.POINTER(C.c_uint32), C.POINTER(TileStats)]
+    lib.rt_scene_bounce.restype = C.c_int
+    lib.rt_scene_bounce_device.argtypes = [vp, C.POINTER(BounceRequest), vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rt_scene_bounce_device.restype = C.c_int
     lib.rt_scene_render_aov.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.c_uint32, C.POINTER(AovPlanes),
                                         C.POINTER(TileStats)]
     lib.rt_scene_render_aov.restype = C.c_int

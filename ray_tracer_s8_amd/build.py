@@ -38,13 +38,14 @@ HIPCC_FLAGS = [
 
 # translation units and the flags each one adds: the host side, the linear-scan kernels, the traversal kernels
 # (SLP-vectorised packed FP32 pairs: linear kernels +3 %, traversal kernels -1.5 %, tools/variants_all.sh), the ray-query kernels,
-# the kernels that path-trace caller rays, the kernels of the feature buffers, the kernels of the denoiser, the camera-ray kernel
+# the kernels that path-trace caller rays, the kernels of their single path steps, the kernels of the feature buffers, the kernels of the denoiser, the camera-ray kernel
 UNITS = [
     ("rt_api.hip", []),
     ("rt_kernels_lin.hip", []),
     ("rt_kernels_trav.hip", ["-fno-slp-vectorize"]),
     ("rt_kernels_query.hip", ["-fno-slp-vectorize"]),
     ("rt_kernels_trace.hip", ["-fno-slp-vectorize"]),
+    ("rt_kernels_bounce.hip", ["-fno-slp-vectorize"]),
     ("rt_kernels_aov.hip", ["-fno-slp-vectorize"]),
     ("rt_kernels_denoise.hip", ["-fno-slp-vectorize"]),
     ("rt_kernels_camera.hip", ["-fno-slp-vectorize"]),
@@ -52,7 +53,7 @@ UNITS = [
 
 
 def _deps() -> list[Path]:
-    return [CSRC / u for u, _ in UNITS] + [CSRC / "rt_kernel.hip.h", CSRC / "rt_unit.hip.h", CSRC / "rt_query.hip.h", CSRC / "rt_trace.hip.h", CSRC / "rt_aov.hip.h", CSRC / "rt_camera.hip.h", CSRC / "rt_denoise.hip.h", CSRC / "rt_denoise_math.h", CSRC / "rt_consts.h", CSRC / "rt_plan.h", CSRC / "rt_cull.h", CSRC / "rt_bvh.h",
+    return [CSRC / u for u, _ in UNITS] + [CSRC / "rt_kernel.hip.h", CSRC / "rt_unit.hip.h", CSRC / "rt_query.hip.h", CSRC / "rt_trace.hip.h", CSRC / "rt_bounce.hip.h", CSRC / "rt_aov.hip.h", CSRC / "rt_camera.hip.h", CSRC / "rt_denoise.hip.h", CSRC / "rt_denoise_math.h", CSRC / "rt_consts.h", CSRC / "rt_plan.h", CSRC / "rt_cull.h", CSRC / "rt_bvh.h",
                                             CSRC / "rt_assign.h", ROOT / "include" / "rt_tile.h",
                                             Path(__file__)]
 

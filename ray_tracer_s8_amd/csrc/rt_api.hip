@@ -29,6 +29,7 @@
 #include "rt_plan.h"
 #include "rt_query.hip.h"
 #include "rt_trace.hip.h"
+#include "rt_bounce.hip.h"
 #include "rt_aov.hip.h"
 #include "rt_camera.hip.h"
 #include "rt_denoise.hip.h"
@@ -221,8 +222,9 @@ struct rt_scene {
     // rt_scene_render_tile_pass and the per-strip ray segments of the batched call (frame context); the rays and hits of
     // rt_scene_intersect; rays, RNG states, colours and segments of rt_scene_trace (80 bytes a ray); the planes of rt_scene_render_aov
     // (36 bytes a pixel); the filter's scratch and the strips' inputs and outputs of rt_scene_denoise; rays and RNG states of
-    // rt_scene_camera_rays (64 bytes a record)
-    DevBuf d_out, d_outf, d_acc, d_cost, d_query, d_trace, d_aov, d_dn, d_cam;
+    // rt_scene_camera_rays (64 bytes a record); rays, RNG states, bounces, hits and the two index lists of rt_scene_bounce (120 bytes
+    // a ray)
+    DevBuf d_out, d_outf, d_acc, d_cost, d_query, d_trace, d_aov, d_dn, d_cam, d_bounce;
     // HIP-event bookkeeping of launches not yet collected
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, free_ev;
     uint64_t primary_rays = 0;
@@ -1133,7 +1135,7 @@ static int rt_scene_destroy_impl(rt_scene* sc) {
     (void)hipFree(sc->d_leaf_of);
     (void)hipFree(sc->d_world_rank);
     (void)hipFree(sc->d_counters);
-    for (DevBuf* b : {&sc->d_out, &sc->d_outf, &sc->d_acc, &sc->d_cost, &sc->d_query, &sc->d_trace, &sc->d_aov, &sc->d_dn, &sc->d_cam}) b->release();
+    for (DevBuf* b : {&sc->d_out, &sc->d_outf, &sc->d_acc, &sc->d_cost, &sc->d_query, &sc->d_trace, &sc->d_aov, &sc->d_dn, &sc->d_cam, &sc->d_bounce}) b->release();
     delete sc;
     g_live_scenes.fetch_sub(1);
     return RT_OK;
@@ -1502,6 +1504,126 @@ static int rt_scene_trace_impl(rt_scene* sc, const rt_trace_request* rq, const r
     HIPCHK(hipMemcpyAsync(rgb, d_rgb, rgb_b, hipMemcpyDeviceToHost, call.st));
     if (segs) HIPCHK(hipMemcpyAsync(segs, d_segs, seg_b, hipMemcpyDeviceToHost, call.st));
     if (rng_state) HIPCHK(hipMemcpyAsync(rng_state, d_state, state_b, hipMemcpyDeviceToHost, call.st));
+    return call.finish(stats);
+}
+
+// ---- path steps of caller rays (rt_tile.h "path steps", rt_bounce.hip.h) ----------------------------------------------------------
+static int check_bounce(rt_scene* sc, const rt_bounce_request* rq, const void* rays, uint32_t n, const void* state, const void* active,
+                        const void* n_active, const void* bounce, const void* next_active, const void* n_next) {
+    if (!sc) return fail(RT_ERR_BAD_ARG, "scene is NULL");
+    if (!rq) return fail(RT_ERR_BAD_ARG, "request is NULL");
+    if (!rays || !state || !bounce) return fail(RT_ERR_BAD_ARG, "rays, rng_state or out_bounce is NULL");
+    if (n == 0) return fail(RT_ERR_BAD_ARG, "n == 0");
+    if (rq->ray_form > RT_TRACE_RAY_AS_GIVEN) return fail(RT_ERR_BAD_ARG, "ray_form is neither RT_TRACE_RAY_NEW nor RT_TRACE_RAY_AS_GIVEN");
+    if (rq->seed_states > 1) return fail(RT_ERR_BAD_ARG, "seed_states is neither 0 nor 1");
+    if (rq->reserved != 0) return fail(RT_ERR_BAD_ARG, "reserved must be 0");
+    if (next_active && !n_next) return fail(RT_ERR_BAD_ARG, "next_active without n_next");
+    if ((active != nullptr) != (n_active != nullptr)) return fail(RT_ERR_BAD_ARG, "active and n_active: both or neither");
+    return RT_OK;
+}
+
+// Enqueue one step on `stream` (caller holds sc->mu, device current): *d_n_next zeroed, then persistent waves over the `count` entries
+// of the active list (d_active == nullptr: rays 0 .. count - 1), of which the kernel takes the first *d_n_active when that is given.
+static int launch_bounce(rt_scene* sc, const rt_bounce_request* rq, void* d_rays, uint32_t n, void* d_state, const void* d_active,
+                         uint32_t count, const void* d_n_active, void* d_bounce, void* d_hits, void* d_next, void* d_n_next,
+                         hipStream_t stream) {
+    const rtplan::QueryPlan qp = rtplan::plan_query(sc->shape, rq->flags);
+    const rtk::BounceFn kern = rtk::bounce_kernel(qp.engine, qp.scan_mode);
+    if (!kern) return fail(RT_ERR_HIP, "no bounce kernel for this plan");
+    rtk::BParams p;
+    std::memset(&p, 0, sizeof p);
+    p.rays = (float4*)d_rays;
+    p.rng_state = (uint64_t*)d_state;
+    p.active = (const uint32_t*)d_active;
+    p.n_active = (const uint32_t*)d_n_active;
+    p.bounce = (uint4*)d_bounce;
+    p.hits = (uint4*)d_hits;
+    p.next_active = (uint32_t*)d_next;
+    p.n_next = (uint32_t*)d_n_next;
+    p.n = n;
+    p.count = count;
+    p.seed = rq->seed;
+    p.as_given = rq->ray_form == RT_TRACE_RAY_AS_GIVEN ? 1u : 0u;
+    p.seed_states = rq->seed_states;
+    scene_refs(sc, qp.full_chain, p);
+    p.mat = sc->d_mat;
+    p.emis = sc->d_emis;
+    Grid g;
+    int rc = persistent_blocks(sc, kern, rtplan::QUERY_BLOCK, qp.lds, std::max<uint32_t>(count, 1u), g);
+    if (rc || (rc = check_slot(sc))) return rc;
+    if (dbg(DBG_VERBOSE))
+        fprintf(stderr, "[rt] bounce: engine %d  scan mode %d  lds %zu B  workgroups/CU %d  rays %u  listed %s%u\n", qp.engine, qp.scan_mode,
+                qp.lds, g.per_cu, n, d_n_active ? "<= " : "", count);
+    if (d_n_next) HIPCHK(hipMemsetAsync(d_n_next, 0, sizeof(uint32_t), stream));
+    if ((rc = enqueue(sc, stream, kern, g.blocks, rtplan::QUERY_BLOCK, qp.lds, p))) return rc;
+    sc->last_engine = (uint32_t)qp.engine;
+    sc->last_form = 0;
+    return RT_OK;
+}
+
+static int rt_scene_bounce_device_impl(rt_scene* sc, const rt_bounce_request* rq, void* d_rays, uint32_t n, void* d_state,
+                                       const void* d_active, const void* d_n_active, void* d_bounce, void* d_hits, void* d_next,
+                                       void* d_n_next, void* hip_stream) {
+    int rc = check_bounce(sc, rq, d_rays, n, d_state, d_active, d_n_active, d_bounce, d_next, d_n_next);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    HIPCHK(hipSetDevice(sc->ctx->dev));
+    return launch_bounce(sc, rq, d_rays, n, d_state, d_active, n, d_n_active, d_bounce, d_hits, d_next, d_n_next,
+                         hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream);
+}
+
+static int rt_scene_bounce_impl(rt_scene* sc, const rt_bounce_request* rq, rt_ray* rays, uint32_t n, uint64_t* rng_state,
+                                const uint32_t* active, uint32_t n_active, rt_bounce* bounce, rt_hit* hits, uint32_t* next_active,
+                                uint32_t* n_next, rt_tile_stats* stats) {
+    // (the host form's n_active is a value: the both-or-neither rule is the device form's)
+    int rc = check_bounce(sc, rq, rays, n, rng_state, nullptr, nullptr, bounce, next_active, n_next);
+    if (rc) return rc;
+    if (active) {
+        if (n_active > n) return fail(RT_ERR_BAD_ARG, "n_active > n");
+        for (uint32_t k = 0; k < n_active; k++)
+            if (active[k] >= n) return fail(RT_ERR_BAD_ARG, "active[" + std::to_string(k) + "] >= n");
+    }
+    const uint32_t count = active ? n_active : n;
+    std::lock_guard<std::mutex> dl(sc->ctx->mu);
+    std::lock_guard<std::mutex> lk(sc->mu);
+    HIPCHK(hipSetDevice(sc->ctx->dev));
+    // one device buffer: rays (32 B), states (32 B), hits (32 B), bounces (16 B), the two lists (4 B each) per ray, the next list's length
+    const size_t ray_b = (size_t)n * sizeof(rt_ray), state_b = (size_t)n * 4 * sizeof(uint64_t), hit_b = (size_t)n * sizeof(rt_hit),
+                 bnc_b = (size_t)n * sizeof(rt_bounce), list_b = (size_t)n * sizeof(uint32_t);
+    if ((rc = sc->d_bounce.reserve(ray_b + state_b + hit_b + bnc_b + 2 * list_b + sizeof(uint32_t), "bounce buffers"))) return rc;
+    char* const d_rays = sc->d_bounce.d;
+    char* const d_state = d_rays + ray_b;
+    char* const d_hits = d_state + state_b;
+    char* const d_bnc = d_hits + hit_b;
+    char* const d_active = d_bnc + bnc_b;
+    char* const d_next = d_active + list_b;
+    char* const d_n_next = d_next + list_b;
+    StagedCall call(sc);
+    if ((rc = call.begin())) return rc;
+    HIPCHK(hipMemcpyAsync(d_rays, rays, ray_b, hipMemcpyHostToDevice, call.st));
+    HIPCHK(hipMemcpyAsync(d_state, rng_state, state_b, hipMemcpyHostToDevice, call.st));
+    if (active && count) HIPCHK(hipMemcpyAsync(d_active, active, (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
+    if (active) {
+        // records of rays that are not listed come back as they went in: the caller's bytes are the staging's initial contents
+        HIPCHK(hipMemcpyAsync(d_bnc, bounce, bnc_b, hipMemcpyHostToDevice, call.st));
+        if (hits) HIPCHK(hipMemcpyAsync(d_hits, hits, hit_b, hipMemcpyHostToDevice, call.st));
+    }
+    if ((rc = call.uploads_done()) ||
+        (rc = launch_bounce(sc, rq, d_rays, n, d_state, active ? d_active : nullptr, count, nullptr, d_bnc, hits ? d_hits : nullptr,
+                            next_active ? d_next : nullptr, n_next ? d_n_next : nullptr, call.st)) ||
+        (rc = call.kernels_done()))
+        return rc;
+    HIPCHK(hipMemcpyAsync(rays, d_rays, ray_b, hipMemcpyDeviceToHost, call.st));
+    HIPCHK(hipMemcpyAsync(rng_state, d_state, state_b, hipMemcpyDeviceToHost, call.st));
+    HIPCHK(hipMemcpyAsync(bounce, d_bnc, bnc_b, hipMemcpyDeviceToHost, call.st));
+    if (hits) HIPCHK(hipMemcpyAsync(hits, d_hits, hit_b, hipMemcpyDeviceToHost, call.st));
+    if (n_next) {
+        HIPCHK(hipMemcpyAsync(n_next, d_n_next, sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
+        if (next_active) {                                 // (the list's length is known only now)
+            HIPCHK(hipStreamSynchronize(call.st));
+            if (*n_next) HIPCHK(hipMemcpyAsync(next_active, d_next, (size_t)std::min(*n_next, n) * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
+        }
+    }
     return call.finish(stats);
 }
 
@@ -2587,6 +2709,17 @@ RT_API int rt_scene_trace(rt_scene* sc, const rt_trace_request* rq, const rt_ray
 RT_API int rt_scene_trace_device(rt_scene* sc, const rt_trace_request* rq, const void* d_rays, uint32_t n, void* d_rng_state,
                                  void* d_out_rgb, void* d_out_segments, void* hip_stream) {
     return guarded([&] { return rt_scene_trace_device_impl(sc, rq, d_rays, n, d_rng_state, d_out_rgb, d_out_segments, hip_stream); });
+}
+RT_API int rt_scene_bounce(rt_scene* sc, const rt_bounce_request* rq, rt_ray* rays, uint32_t n, uint64_t* rng_state, const uint32_t* active,
+                           uint32_t n_active, rt_bounce* out_bounce, rt_hit* out_hits, uint32_t* next_active, uint32_t* n_next,
+                           rt_tile_stats* stats) {
+    return guarded([&] { return rt_scene_bounce_impl(sc, rq, rays, n, rng_state, active, n_active, out_bounce, out_hits, next_active, n_next, stats); });
+}
+RT_API int rt_scene_bounce_device(rt_scene* sc, const rt_bounce_request* rq, void* d_rays, uint32_t n, void* d_rng_state, const void* d_active,
+                                  const void* d_n_active, void* d_bounce, void* d_hits, void* d_next_active, void* d_n_next, void* hip_stream) {
+    return guarded([&] {
+        return rt_scene_bounce_device_impl(sc, rq, d_rays, n, d_rng_state, d_active, d_n_active, d_bounce, d_hits, d_next_active, d_n_next, hip_stream);
+    });
 }
 RT_API int rt_scene_render_aov(rt_scene* sc, const rt_tile_request* rq, uint32_t sample_begin, uint32_t sample_end,
                                const rt_aov_planes* planes, rt_tile_stats* stats) {

@@ -1,0 +1,13 @@
+// Device code of the path steps of caller rays (rt_bounce.hip.h): one ray_color entry per active ray over the query path's exact-node
+// walk (engine 2) or its scan in primitive order (engine 1, plain or BVH semantics).  Its own translation unit: the tile, query and
+// trace kernels' code objects are untouched by it.
+#include "rt_bounce.hip.h"
+
+namespace rtk {
+BounceFn bounce_kernel(int engine, int scan_mode) {
+    if (engine == 2) return rt_bounce_kernel<2, 2>;
+    if (engine == 1 && scan_mode == 0) return rt_bounce_kernel<1, 0>;
+    if (engine == 1 && scan_mode == 2) return rt_bounce_kernel<1, 2>;
+    return nullptr;
+}
+}  // namespace rtk

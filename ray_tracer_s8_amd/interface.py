@@ -311,6 +311,66 @@ class Scene:
         _abi.check(self._lib.rt_scene_trace_device(self._h, C.byref(rq), vp(d_rays), n, vp(d_rng_state), vp(d_rgb), vp(d_segments),
                                                    vp(stream)), "rt_scene_trace_device")
 
+    def bounce(self, rays, rng_state, active=None, as_given: bool = False, flags: int = 0, seed: Optional[int] = None,
+               want_hits: bool = False, want_next: bool = False):
+        """One path step of caller rays (rt_scene_bounce): one ray_color entry for each active ray — the closest hit, its shade, and
+        for a ray that scatters the UnitSphere draw from its state and the scattered ray.  rays: (N,) RAY_DTYPE; rng_state: (N, 4)
+        uint64; active: None (all N) or ray indices; as_given: take the directions bit for bit (the rays a step returns must be
+        stepped so); seed: seed state i from seed_from_u64(seed + 4 PHI i) first (rng_state may then be None).  The inputs are not
+        modified.  Returns a dict: `rays` and `states` (the scattered rays and their advanced states written over copies of the
+        inputs), `bounce` (BOUNCE_DTYPE: the step's colour factor and RT_BOUNCE_* status; entries of rays that are not active
+        are zero), `hits` (HIT_DTYPE of the incoming rays) when want_hits, `next` (the indices of the rays that scattered,
+        ascending) when want_next, and `stats`."""
+        r = np.array(rays, _abi.RAY_DTYPE, order="C")
+        if r.ndim != 1:
+            raise ValueError(f"rays: need a 1-d array of RAY_DTYPE records, got shape {r.shape}")
+        n = len(r)
+        if rng_state is None:
+            if seed is None:
+                raise ValueError("rng_state: need (N, 4) uint64 states, or a seed to make them from")
+            state = np.zeros((n, 4), np.uint64)
+        else:
+            state = np.array(rng_state, np.uint64, order="C")
+        if state.shape != (n, 4):
+            raise ValueError(f"rng_state: need an (N, 4) uint64 array, got {state.shape}")
+        act = None if active is None else np.ascontiguousarray(active, np.uint32).reshape(-1)
+        rq = _abi.BounceRequest(flags, _abi.RT_TRACE_RAY_AS_GIVEN if as_given else _abi.RT_TRACE_RAY_NEW,
+                                0 if seed is None else 1, 0, (seed or 0) & 0xFFFFFFFFFFFFFFFF)
+        bnc = np.zeros(n, _abi.BOUNCE_DTYPE)
+        hits = np.zeros(n, _abi.HIT_DTYPE) if want_hits else None
+        nxt = np.zeros(n, np.uint32) if want_next else None
+        n_next = C.c_uint32(0)
+        u32p = C.POINTER(C.c_uint32)
+        st = TileStats()
+        # (an empty list is still a list: ctypes gets a non-NULL pointer to an array of one)
+        act_arg = None if act is None else (act if len(act) else np.zeros(1, np.uint32)).ctypes.data_as(u32p)
+        _abi.check(self._lib.rt_scene_bounce(self._h, C.byref(rq), r.ctypes.data_as(C.POINTER(_abi.Ray)), n,
+                                             state.ctypes.data_as(C.POINTER(C.c_uint64)), act_arg, 0 if act is None else len(act),
+                                             bnc.ctypes.data_as(C.POINTER(_abi.Bounce)),
+                                             hits.ctypes.data_as(C.POINTER(_abi.Hit)) if want_hits else None,
+                                             nxt.ctypes.data_as(u32p) if want_next else None,
+                                             C.byref(n_next) if want_next else None, C.byref(st)), "rt_scene_bounce")
+        out = {"rays": r, "states": state, "bounce": bnc, "stats": st}
+        if want_hits:
+            out["hits"] = hits
+        if want_next:
+            out["next"] = np.sort(nxt[:n_next.value])
+        return out
+
+    def bounce_device(self, d_rays: int, n: int, d_rng_state: int, d_bounce: int, *, d_active: int = 0, d_n_active: int = 0,
+                      d_hits: int = 0, d_next_active: int = 0, d_n_next: int = 0, as_given: bool = False, flags: int = 0,
+                      seed: Optional[int] = None, stream: int = 0):
+        """One path step on device buffers (rt_scene_bounce_device): n rt_ray at d_rays and 4 n uint64 states at d_rng_state, both
+        updated in place; n rt_bounce to d_bounce; optionally n rt_hit to d_hits, the active list d_active with its uint32 length
+        at d_n_active (read on the device), and the list of the rays that scattered to d_next_active with its length to d_n_next —
+        e.g. the data_ptr() of torch tensors; asynchronous on `stream`, counters until collect()."""
+        rq = _abi.BounceRequest(flags, _abi.RT_TRACE_RAY_AS_GIVEN if as_given else _abi.RT_TRACE_RAY_NEW,
+                                0 if seed is None else 1, 0, (seed or 0) & 0xFFFFFFFFFFFFFFFF)
+        vp = lambda ptr: C.c_void_p(ptr) if ptr else None
+        _abi.check(self._lib.rt_scene_bounce_device(self._h, C.byref(rq), vp(d_rays), n, vp(d_rng_state), vp(d_active), vp(d_n_active),
+                                                    vp(d_bounce), vp(d_hits), vp(d_next_active), vp(d_n_next), vp(stream)),
+                   "rt_scene_bounce_device")
+
     def render_aov(self, req: TileRequest, begin: int = 0, end: Optional[int] = None, *,
                    planes: Sequence[str] = _abi.AOV_PLANES, out: Optional[dict] = None):
         """Feature buffers of a strip (rt_scene_render_aov): over samples [begin, end) of the req.spp-sample job (end None:

@@ -1,0 +1,224 @@
+"""The CPU reference for ONE path step (rt_scene_bounce, rt_tile.h "path steps"), from the oracle's batch entry points and float32 numpy
+alone: oracle.intersect_batch gives the closest hit (point, normal, albedo, roughness, emission, world position), oracle.draw the
+UnitSphere draw from the ray's state, oracle.sky the colour of a miss; the scatter is the arithmetic of oracle/restate_np.py
+ray_color (S/main.rs:119-127) on float32 arrays, one IEEE operation per numpy operation: dot as (x x' + y y') + z z', try_normalize as
+v * (1 / length) when that reciprocal is finite and > 0, normalize as a division.  tests/test_bounce_np.py pins it on the CPU: K steps
+folded right to left are oracle.trace_batch.  Also here: the fold, the scenes and rays the CPU and GPU tests share."""
+import numpy as np
+
+from ray_tracer_s8_amd import _abi, scenes
+
+import _ray_cases as R
+
+SCATTERED, EMITTED, MISSED = _abi.RT_BOUNCE_SCATTERED, _abi.RT_BOUNCE_EMITTED, _abi.RT_BOUNCE_MISSED
+NONE = _abi.RT_HIT_NONE
+NO_TRI = np.zeros(0, _abi.TRIANGLE_DTYPE)
+NO_SPH = np.zeros(0, _abi.SPHERE_DTYPE)
+F32 = np.float32
+PHI4 = 4 * 0x9E3779B97F4A7C15
+M64 = (1 << 64) - 1
+
+
+def _dot(a, b):
+    return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
+
+
+def _length(a):
+    return np.sqrt(_dot(a, a))
+
+
+def _normalize(a):                               # glam normalize: a division by the length (B/ray.rs:134)
+    return a / _length(a)[:, None]
+
+
+def _try_normalize(a):
+    rcp = F32(1) / _length(a)
+    return np.isfinite(rcp) & (rcp > 0), a * rcp[:, None]
+
+
+def directions(rays, as_given):
+    """The direction each ray is traced with: bit for bit, or Ray::new's."""
+    d = np.stack([rays["dx"], rays["dy"], rays["dz"]], 1).astype(F32)
+    with np.errstate(all="ignore"):
+        return d if as_given else _normalize(d)
+
+
+def seeded_states(seed, n):
+    from oracle import oracle as orc
+    return np.array([orc.seed_from_u64((seed + PHI4 * i) & M64) for i in range(n)], np.uint64).reshape(n, 4)
+
+
+def step(oracle, sph, tri, rays, states, backend, wi=None, as_given=False, active=None, seed=None):
+    """One step of the rays `active` (None: all).  Returns a dict: rays, states (copies, the scattered rays and their advanced
+    states written over them), bounce (BOUNCE_DTYPE), hits (HIT_DTYPE), touched (bool: the ray was active); bounce and hits
+    entries of rays that are not active are zero."""
+    n = len(rays)
+    act = np.arange(n) if active is None else np.asarray(active, np.int64)
+    out_rays, out_states = rays.copy(), np.array(states, np.uint64)
+    bnc, hits = np.zeros(n, _abi.BOUNCE_DTYPE), np.zeros(n, _abi.HIT_DTYPE)
+    touched = np.zeros(n, bool)
+    touched[act] = True
+    if seed is not None:
+        out_states[act] = seeded_states(seed, n)[act]
+    if not len(act):
+        return dict(rays=out_rays, states=out_states, bounce=bnc, hits=hits, touched=touched)
+    r = np.ascontiguousarray(rays[act])
+    e = oracle.intersect_batch(sph, tri, r, backend=backend, world_index=wi, ray_as_given=as_given)
+    hit = e["hit"]
+    o = np.stack([r["ox"], r["oy"], r["oz"]], 1).astype(F32)
+    d = directions(r, as_given)
+    P, nrm, alb, rough, em = e["point"], e["normal"], e["albedo"], e["roughness"], e["emission"]
+    with np.errstate(all="ignore"):
+        dist = np.where(hit, _length(P - o), F32(np.inf)).astype(F32)
+    h = np.zeros(len(act), _abi.HIT_DTYPE)
+    h["px"], h["py"], h["pz"] = P.T
+    h["nx"], h["ny"], h["nz"] = nrm.T
+    h["distance"], h["index"] = dist, e["index"]
+    hits[act] = h
+    b = np.zeros(len(act), _abi.BOUNCE_DTYPE)
+    emits = hit & (em > 0)
+    scat = hit & ~emits
+    b["status"] = np.where(scat, SCATTERED, np.where(emits, EMITTED, MISSED))
+    rgb = np.where(emits[:, None], alb * em[:, None], alb).astype(F32)
+    for j in np.nonzero(~hit)[0]:
+        rgb[j] = oracle.sky(d[j])                # (the sky of normalize_or_zero(d).y of the direction traced)
+    b["r"], b["g"], b["b"] = rgb.T
+    bnc[act] = b
+    js = np.nonzero(scat)[0]
+    if len(js):
+        us = np.zeros((len(js), 3), F32)
+        for k, j in enumerate(js):
+            st = out_states[act[j]].copy()
+            us[k] = oracle.draw(st, 3)           # UnitSphere (S/main.rs:119): the state advanced in place
+            out_states[act[j]] = st
+        nn, dd, rr = nrm[js], d[js], rough[js]
+        with np.errstate(all="ignore"):
+            diffuse = us + nn
+            glossy = dd - (F32(2) * _dot(dd, nn))[:, None] * nn
+            scatter = diffuse + rr[:, None] * (glossy - diffuse)
+            ok, nd = _try_normalize(scatter)
+            nd = np.where(ok[:, None], nd, nn)
+            d2 = _normalize(nd)                  # Ray::new
+        w = out_rays[act[js]]
+        w["ox"], w["oy"], w["oz"] = P[js].T
+        w["dx"], w["dy"], w["dz"] = d2.T
+        out_rays[act[js]] = w
+    return dict(rays=out_rays, states=out_states, bounce=bnc, hits=hits, touched=touched)
+
+
+def rgb_of(bounce):
+    return np.stack([bounce["r"], bounce["g"], bounce["b"]], 1).astype(F32)
+
+
+def fold(steps):
+    """a1 (a2 (... (ak term))) per ray, right to left (S/main.rs:123).  steps: per step (bounce records, indices stepped).  A ray
+    whose last step scattered folds 0: the reference draws, then ray_color(.., 0) returns black."""
+    n = len(steps[0][0])
+    acc = np.zeros((n, 3), F32)
+    for k in range(len(steps) - 1, -1, -1):
+        bnc, act = steps[k]
+        act = np.asarray(act, np.int64)
+        rgb, status = rgb_of(bnc)[act], bnc["status"][act]
+        with np.errstate(all="ignore"):
+            acc[act] = np.where((status == SCATTERED)[:, None], rgb * acc[act], rgb)
+    return acc
+
+
+def compose(oracle, sph, tri, rays, states, K, backend, wi=None, as_given=False, seed=None):
+    """K steps on the CPU with the active list carried along.  Returns (rgb, final states, rays stepped in all)."""
+    cur_rays, cur_states = rays, states
+    act = np.arange(len(rays))
+    steps, stepped = [], 0
+    for k in range(K):
+        s = step(oracle, sph, tri, cur_rays, cur_states, backend, wi, as_given or k > 0, act, seed if k == 0 else None)
+        steps.append((s["bounce"], act))
+        stepped += len(act)
+        cur_rays, cur_states = s["rays"], s["states"]
+        act = act[s["bounce"]["status"][act] == SCATTERED]
+    return fold(steps), cur_states, stepped
+
+
+def same_bits(a, b):
+    """Elementwise: equal bit for bit, NaN matching NaN."""
+    a, b = np.ascontiguousarray(a, F32), np.ascontiguousarray(b, F32)
+    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
+
+
+def records_equal(a, b, float_fields, int_fields):
+    ok = np.ones(len(a), bool)
+    for f in float_fields:
+        ok &= same_bits(a[f], b[f])
+    for f in int_fields:
+        ok &= a[f] == b[f]
+    return ok
+
+
+RAY_F = ("ox", "oy", "oz", "t_min", "dx", "dy", "dz", "t_max")
+HIT_F = ("px", "py", "pz", "distance", "nx", "ny", "nz")
+BNC_F = ("r", "g", "b")
+
+
+# ---------------------------------------------------------------- scenes and rays shared by the CPU and the GPU tests
+def _with_emitters(a, seed, share=0.08):
+    """Some primitives made emitters, so that every status occurs."""
+    a = a.copy()
+    g = np.random.default_rng(seed)
+    k = g.uniform(size=len(a)) < share
+    k[:: max(1, len(a) // 7)] = True
+    a["emission"] = np.where(k, F32(3.0), a["emission"]).astype(F32)
+    return a
+
+
+def scene(name):
+    """(spheres, triangles, world_index or None): a sphere scene (cornell16: emitters of its own), a triangle scene, and the mixed
+    fuzz scene with a permuted world and duplicates."""
+    if name == "spheres":
+        return scenes.cornell16(), NO_TRI, None
+    if name == "triangles":
+        from test_gpu_query import _world
+        _, tri = _world("terrain")
+        return NO_SPH, _with_emitters(np.ascontiguousarray(tri), 41), None
+    if name == "mixed":
+        sph, tri, wi, _ = R.case_scene("mixed", 1)
+        return _with_emitters(sph, 42), _with_emitters(tri, 43), wi
+    raise KeyError(name)
+
+
+SCENE_NAMES = ("spheres", "triangles", "mixed")
+
+
+def population(oracle, name, n, seed):
+    sph, tri, wi = scene(name)
+    g = np.random.default_rng(seed)
+    rays, _, _ = R.ray_population(oracle, g, sph, tri, n, wi)
+    return sph, tri, wi, rays, R.states(n, seed + 1)
+
+
+def exceptional_case():
+    """Constructed rays for the two exceptional arms of the scatter.
+    (a) A triangle whose normal is 0: its edges are 1e10 long, so (a - b) x (a - c) has components of 1e20 whose squares overflow;
+        the length is inf, its reciprocal 0, and normalize_or_zero gives 0.  With a roughness of 3e38 the scatter direction
+        overflows too, try_normalize fails, the fallback is that zero normal, and Ray::new's division gives NaN.
+    (b) A mirror of roughness 1: diffuse + 1 (glossy - diffuse), the diffuse term cancels (up to rounding).
+    (c) The zero normal with roughness 0: the direction is the UnitSphere draw alone.
+    Returns (spheres, triangles, rays)."""
+    tri = np.zeros(2, _abi.TRIANGLE_DTYPE)
+    L = F32(1e10)
+    for k, rough in enumerate((F32(3e38), F32(0.0))):
+        z = F32(-5.0 - 5.0 * k)
+        tri["a"][k], tri["b"][k], tri["c"][k] = (-L, -L, z), (L, -L, z), (0, L, z)
+        tri["albedo_r"][k], tri["albedo_g"][k], tri["albedo_b"][k] = 0.7, 0.6, 0.5
+        tri["roughness"][k] = rough
+    sph = np.zeros(1, _abi.SPHERE_DTYPE)
+    sph["cx"], sph["cy"], sph["cz"], sph["radius"] = 0.0, 0.0, 20.0, 4.0
+    sph["albedo_r"], sph["albedo_g"], sph["albedo_b"], sph["roughness"] = 0.9, 0.8, 0.7, 1.0
+    g = np.random.default_rng(77)
+    m = 48
+    o = g.uniform(-1, 1, (3 * m, 3)).astype(F32)
+    d = g.normal(size=(3 * m, 3)).astype(F32) * F32(0.2)
+    d[:m, 2] = -1.0                              # towards the first triangle
+    o[m:2 * m, 2] = -7.0                         # between the triangles, towards the second
+    d[m:2 * m, 2] = -1.0
+    d[2 * m:, 2] = 1.0                           # towards the mirror sphere
+    d[2 * m:, :2] *= F32(0.25)
+    return sph, tri, R.make_rays(o, d)
