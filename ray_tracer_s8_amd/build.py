@@ -53,9 +53,9 @@ UNITS = [
 
 
 def _deps() -> list[Path]:
-    return [CSRC / u for u, _ in UNITS] + [CSRC / "rt_kernel.hip.h", CSRC / "rt_unit.hip.h", CSRC / "rt_query.hip.h", CSRC / "rt_trace.hip.h", CSRC / "rt_bounce.hip.h", CSRC / "rt_aov.hip.h", CSRC / "rt_camera.hip.h", CSRC / "rt_denoise.hip.h", CSRC / "rt_denoise_math.h", CSRC / "rt_consts.h", CSRC / "rt_plan.h", CSRC / "rt_cull.h", CSRC / "rt_bvh.h",
-                                            CSRC / "rt_assign.h", ROOT / "include" / "rt_tile.h",
-                                            Path(__file__)]
+    """Everything a library is compiled from: every file under csrc/, subdirectories included (a new header cannot be forgotten; a
+    stray file there costs a rebuild, never a stale library), the C header, this recipe."""
+    return sorted(f for f in CSRC.rglob("*") if f.is_file()) + [ROOT / "include" / "rt_tile.h", Path(__file__)]
 
 
 FLAGS_PATH = LIB_PATH.with_suffix(".flags")      # the exact compile lines of the library next to it

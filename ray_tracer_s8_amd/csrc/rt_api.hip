@@ -305,7 +305,7 @@ int persistent_blocks(const rt_scene* sc, void (*kern)(const P), uint32_t block,
     return RT_OK;
 }
 
-// The scene as the first-hit kernels read it (rt_query.hip.h SceneRefs), into their parameter block.
+// The scene as the first-hit kernels read it (rt_path_steps.hip.h SceneRefs), into their parameter block.
 void scene_refs(const rt_scene* sc, bool full_chain, rtk::SceneRefs& r) {
     r.n_sph = sc->shape.n_sph;
     r.n_tri = sc->shape.n_tri;

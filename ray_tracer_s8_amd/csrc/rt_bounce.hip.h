@@ -2,11 +2,9 @@
 //
 // One lane per ACTIVE caller ray, one ray_color entry with depth > 0 (main.rs:108-146) per lane: the closest hit of the segment, its
 // shade, and — when the ray scatters — the UnitSphere draw from the ray's own RNG state and the scattered ray, written back over the
-// ray and the state.  What rt_trace.hip.h does between two segments of its loop, operation for operation: the closest hit is the query
-// path's (rt_query.hip.h closest_hit: the exact-node walk or the scan), the hit record is the query kernel's, the shade and the
-// scatter are the trace kernel's (the Marsaglia rejection loop, diffuse + roughness (glossy - diffuse), try_normalize falling back to
-// the normal, then Ray::new's normalize; emission em * albedo; the sky of normalize_or_zero(d).y).  The albedo product and the
-// termination rule are the caller's: a step returns the segment's own factor (rt_bounce.rgb) and its status.
+// ray and the state.  What rt_trace.hip.h does between two segments of its loop, through the same shared steps of rt_path_steps.hip.h
+// (closest_hit, hit_normal, hit_record, sky_colour, unit_sphere_pair, scattered_dir); emission is em * albedo.  The albedo product and
+// the termination rule are the caller's: a step returns the segment's own factor (rt_bounce.rgb) and its status.
 //
 // Persistent waves stride over the active list (or over all n rays).  The device form reads the list's length from device memory, so
 // consecutive steps need no host synchronisation.  Compaction: the lanes of a wave that scattered are counted by a ballot, ranked by
@@ -16,7 +14,7 @@
 // LDS per lane (rtplan::plan_query): the walk's stack, (bvh depth + 1) u32 entries (engine 2); entry e of lane tid at [e * 256 + tid].
 // No per-scene scratch: launches on different streams may overlap.
 #pragma once
-#include "rt_query.hip.h"
+#include "rt_path_steps.hip.h"
 
 namespace rtk {
 
@@ -53,44 +51,29 @@ __global__ __launch_bounds__(256) void rt_bounce_kernel(const BParams p) {
         const uint64_t i = p.active ? (uint64_t)p.active[k] : k;
         bool scattered = false;
         if (i < p.n) {                                                                 // (an index beyond the batch touches nothing)
-            const float4 r0 = p.rays[2 * i], r1 = p.rays[2 * i + 1];
-            const V3 o = mk(r0.x, r0.y, r0.z);
-            const V3 dr = mk(r1.x, r1.y, r1.z);
-            const V3 d = p.as_given ? dr : normalize(dr);                              // Ray::new (ray.rs:134), or the direction as handed over
-            const float t_min = r0.w, t_max = r1.w;
+            const CallerRay r = load_caller_ray(p.rays + 2 * i, p.as_given != 0);
+            const V3 o = r.o, d = r.d;
             const RayAux aux = ray_aux(d, p.full_chain != 0);
             n_rays++;
             // ================= one ray_color entry with depth > 0: the closest hit (shapes/mod.rs:158-191) =================
-            const Hit h = closest_hit<ENGINE, MODE, false>(p, o, d, t_min, t_max, aux, bstack, tid, 256u, n_tests);
-            uint4 w0 = make_uint4(0u, 0u, 0u, __float_as_uint(__builtin_inff())), w1 = make_uint4(0u, 0u, 0u, RT_HIT_NONE);
+            const Hit h = closest_hit<ENGINE, MODE, false>(p, o, d, r.t_min, r.t_max, aux, bstack, tid, 256u, n_tests);
+            uint4 w0, w1;
+            hit_none(w0, w1);
             float cr, cg, cb;
             uint32_t status;
             Rng rng;
             if (p.seed_states) rng = seed_state(p.seed + i * (4ull * PHI));
             if (h.idx < 0) {
-                const V3 nn = normalize_or_zero(d);                                    // sky (main.rs:135-144)
-                float t = nn.y * 0.5f + 1.0f;
-                float omt = 1.0f - t;
-                cr = 1.0f * t + 0.3f * omt;
-                cg = 1.0f * t + 0.3f * omt;
-                cb = 1.0f * t + 0.8f * omt;
+                const V3 sky = sky_colour(d);                                          // main.rs:135-144
+                cr = sky.x;
+                cg = sky.y;
+                cb = sky.z;
                 status = RT_BOUNCE_MISSED;
             } else {
                 const uint32_t prim = (uint32_t)h.idx;
-                // the hit record (shapes/mod.rs:184-190), as rt_query_kernel fills it
                 const V3 hp = o + h.t * d;                                             // Ray::at (ray.rs:147-149)
-                V3 nv;
-                if (prim < p.n_sph) {
-                    const float4 g = at32(p.geom_r, prim);
-                    nv = hp - mk(g.x, g.y, g.z);                                       // sphere.rs:49-51
-                } else {
-                    const float* tv = p.tri + 9 * (size_t)(prim - p.n_sph);
-                    const V3 A = mk(tv[0], tv[1], tv[2]), B = mk(tv[3], tv[4], tv[5]), C = mk(tv[6], tv[7], tv[8]);
-                    nv = cross(A - B, A - C);                                          // mesh.rs:163-165
-                }
-                const V3 n = normalize_or_zero(nv);
-                w0 = make_uint4(__float_as_uint(hp.x), __float_as_uint(hp.y), __float_as_uint(hp.z), __float_as_uint(h.dist));
-                w1 = make_uint4(__float_as_uint(n.x), __float_as_uint(n.y), __float_as_uint(n.z), p.world_rank ? p.world_rank[prim] : prim);
+                const V3 n = hit_normal(p, prim, hp);
+                hit_record(p, h, hp, n, w0, w1);                                       // shapes/mod.rs:184-190
                 // ================= shade (main.rs:114-127) =================
                 const float em = at32(p.emis, prim);
                 const float4 ma = at32(p.mat, prim);
@@ -105,39 +88,15 @@ __global__ __launch_bounds__(256) void rt_bounce_kernel(const BParams p) {
                     cb = ma.z;
                     status = RT_BOUNCE_SCATTERED;
                     scattered = true;
-                    if (!p.seed_states) {
-                        const uint64_t* s = p.rng_state + 4 * i;
-                        rng.s0 = s[0];
-                        rng.s1 = s[1];
-                        rng.s2 = s[2];
-                        rng.s3 = s[3];
-                    }
+                    if (!p.seed_states) load_rng(p.rng_state + 4 * i, rng);
                     float x1, x2, sm;
-                    for (;;) {                                                         // UnitSphere, main.rs:119
-                        x1 = uniform_m1_1(rng);
-                        x2 = uniform_m1_1(rng);
-                        sm = x1 * x1 + x2 * x2;
-                        if (!(sm >= 1.0f)) break;
-                    }
-                    const float factor = 2.0f * RT_SQRT(1.0f - sm);
-                    const V3 us = mk(x1 * factor, x2 * factor, 1.0f - 2.0f * sm);
-                    const V3 diffuse_dir = us + n;
-                    const V3 glossy_dir = d - (2.0f * dot(d, n)) * n;                  // main.rs:120-121
-                    const V3 pre = diffuse_dir + ma.w * (glossy_dir - diffuse_dir);    // main.rs:122
-                    V3 xdir;
-                    if (!try_normalize(pre, xdir)) xdir = n;                           // main.rs:126
-                    const V3 d2 = normalize(xdir);                                     // Ray::new (ray.rs:134)
-                    p.rays[2 * i] = make_float4(hp.x, hp.y, hp.z, t_min);              // origin exactly P, the window kept
-                    p.rays[2 * i + 1] = make_float4(d2.x, d2.y, d2.z, t_max);
+                    unit_sphere_pair(rng, x1, x2, sm);                                 // UnitSphere, main.rs:119
+                    const V3 d2 = scattered_dir(d, n, ma.w, x1, x2, sm);
+                    p.rays[2 * i] = make_float4(hp.x, hp.y, hp.z, r.t_min);            // origin exactly P, the window kept
+                    p.rays[2 * i + 1] = make_float4(d2.x, d2.y, d2.z, r.t_max);
                 }
             }
-            if (scattered || p.seed_states) {
-                uint64_t* s = p.rng_state + 4 * i;
-                s[0] = rng.s0;
-                s[1] = rng.s1;
-                s[2] = rng.s2;
-                s[3] = rng.s3;
-            }
+            if (scattered || p.seed_states) store_rng(p.rng_state + 4 * i, rng);
             p.bounce[i] = make_uint4(__float_as_uint(cr), __float_as_uint(cg), __float_as_uint(cb), status);
             if (p.hits) {
                 p.hits[2 * i] = w0;
@@ -158,13 +117,7 @@ __global__ __launch_bounds__(256) void rt_bounce_kernel(const BParams p) {
             }
         }
     }
-    // counters: one atomic per wave
-    n_rays = wave_sum(n_rays);
-    n_tests = wave_sum(n_tests);
-    if ((tid & 63u) == 0) {
-        if (n_rays) atomicAdd(p.counters + 0, n_rays);
-        if (n_tests) atomicAdd(p.counters + 1, n_tests);
-    }
+    flush_counters(p.counters, n_rays, n_tests, tid);
 }
 
 using BounceFn = void (*)(const BParams);

@@ -2,18 +2,16 @@
 //
 // One lane per caller ray: `spp` samples of ray_color(ray, max_bounces + 1, rng) (main.rs:108-146), summed in f32 in sample order.
 // Persistent waves stride over the batch; each lane loops over its samples and, within a sample, over the segments of the path.
-// The closest hit of every segment is the query path's (rt_query.hip.h closest_hit: the exact-node walk or the scan, the same
-// operations as rt_scene_intersect), the shading restates the tile kernel's (rt_kernel.hip.h, "shade" and the scattered ray at the
-// top of its round) with the same operations in the same order: the Marsaglia rejection loop, diffuse + roughness (glossy -
-// diffuse), try_normalize falling back to the normal, then Ray::new's normalize; emission em * albedo; the sky of
-// normalize_or_zero(d).y; the UnitSphere draw of a hit at the last depth; the right-to-left albedo product a1 (a2 (... (ak term))).
-// So a ray the tile renderer traces gives the same bits here.
+// The closest hit of every segment, the normal, the sky and the scattered ray are the shared steps of rt_path_steps.hip.h (closest_hit:
+// the exact-node walk or the scan, the same operations as rt_scene_intersect; hit_normal, sky_colour, unit_sphere_pair, scattered_dir);
+// the kernel's own are emission em * albedo, the UnitSphere draw of a hit at the last depth and the right-to-left albedo product
+// a1 (a2 (... (ak term))).  So a ray the tile renderer traces gives the same bits here.
 //
 // LDS per lane (rtplan::plan_trace): the walk's stack, (bvh depth + 1) u32 entries (engine 2), then the path stack, max_bounces + 1
 // primitive indices (u16 when the scene has at most 65 536 primitives, as the tile's path32 rule).  Entry e of lane tid sits at
 // [e * blockDim.x + tid].  No other per-scene scratch: launches on different streams may overlap.
 #pragma once
-#include "rt_query.hip.h"
+#include "rt_path_steps.hip.h"
 
 namespace rtk {
 
@@ -47,39 +45,27 @@ __global__ __launch_bounds__(256) void rt_trace_kernel(const TParams p) {
     };
     unsigned long long n_segs = 0, n_tests = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * bs + tid; i < p.n; i += (uint64_t)gridDim.x * bs) {
-        const float4 r0 = p.rays[2 * i], r1 = p.rays[2 * i + 1];
-        const V3 o0 = mk(r0.x, r0.y, r0.z);
-        const V3 dr = mk(r1.x, r1.y, r1.z);
-        const V3 d0 = p.as_given ? dr : normalize(dr);         // Ray::new (ray.rs:134), or the direction a camera / bounce hands over
-        const float t_min = r0.w, t_max = r1.w;
+        const CallerRay r = load_caller_ray(p.rays + 2 * i, p.as_given != 0);
         Rng rng;
-        if (p.rng_state) {
-            const uint64_t* s = p.rng_state + 4 * i;
-            rng.s0 = s[0];
-            rng.s1 = s[1];
-            rng.s2 = s[2];
-            rng.s3 = s[3];
-        }
+        if (p.rng_state) load_rng(p.rng_state + 4 * i, rng);
         float sum_r = 0.f, sum_g = 0.f, sum_b = 0.f;
         uint32_t segs = 0;
         for (uint32_t smp = 0; smp < p.spp; smp++) {
             if (!p.rng_state) rng = seed_state(p.seed + (i * p.spp + smp) * (4ull * PHI));
-            V3 o = o0, d = d0;
+            V3 o = r.o, d = r.d;
             uint32_t k = 0, depth_left = p.depth;
             float term_r, term_g, term_b;
             for (;;) {
                 // ================= one ray_color entry with depth > 0: the closest hit (shapes/mod.rs:158-191) =================
                 segs++;
                 const RayAux aux = ray_aux(d, p.full_chain != 0);
-                const Hit h = closest_hit<ENGINE, MODE, false>(p, o, d, t_min, t_max, aux, tlds, tid, bs, n_tests);
+                const Hit h = closest_hit<ENGINE, MODE, false>(p, o, d, r.t_min, r.t_max, aux, tlds, tid, bs, n_tests);
                 // ================= shade (main.rs:114-145) =================
                 if (h.idx < 0) {
-                    const V3 nn = normalize_or_zero(d);                                // sky (main.rs:135-144)
-                    float t = nn.y * 0.5f + 1.0f;
-                    float omt = 1.0f - t;
-                    term_r = 1.0f * t + 0.3f * omt;
-                    term_g = 1.0f * t + 0.3f * omt;
-                    term_b = 1.0f * t + 0.8f * omt;
+                    const V3 sky = sky_colour(d);                                      // main.rs:135-144
+                    term_r = sky.x;
+                    term_g = sky.y;
+                    term_b = sky.z;
                     break;
                 }
                 const float em = at32(p.emis, (uint32_t)h.idx);
@@ -91,40 +77,19 @@ __global__ __launch_bounds__(256) void rt_trace_kernel(const TParams p) {
                     break;
                 }
                 const V3 hp = o + h.t * d;                                             // Ray::at (ray.rs:147-149), as in consider
-                V3 nv;
-                if ((uint32_t)h.idx < p.n_sph) {
-                    const float4 g = at32(p.geom_r, (uint32_t)h.idx);
-                    nv = hp - mk(g.x, g.y, g.z);                                       // sphere.rs:49-51
-                } else {
-                    const float* tv = p.tri + 9 * (size_t)(h.idx - p.n_sph);
-                    V3 A = mk(tv[0], tv[1], tv[2]), B = mk(tv[3], tv[4], tv[5]), C = mk(tv[6], tv[7], tv[8]);
-                    nv = cross(A - B, A - C);                                          // mesh.rs:163-165
-                }
-                const V3 n = normalize_or_zero(nv);
+                const V3 n = hit_normal(p, (uint32_t)h.idx, hp);
                 path_set(k, (uint32_t)h.idx);                                          // the albedo product is applied back to front
                 k++;
                 depth_left--;
                 // the scattered ray (main.rs:119-127) — drawn also when the depth has run out: the reference draws UnitSphere
                 // before ray_color(.., 0) returns black (main.rs:119 then :109-111)
                 float x1, x2, sm;
-                for (;;) {
-                    x1 = uniform_m1_1(rng);
-                    x2 = uniform_m1_1(rng);
-                    sm = x1 * x1 + x2 * x2;
-                    if (!(sm >= 1.0f)) break;
-                }
+                unit_sphere_pair(rng, x1, x2, sm);
                 if (depth_left == 0) {
                     term_r = term_g = term_b = 0.0f;
                     break;
                 }
-                const float factor = 2.0f * RT_SQRT(1.0f - sm);                        // UnitSphere, main.rs:119
-                const V3 us = mk(x1 * factor, x2 * factor, 1.0f - 2.0f * sm);
-                const V3 diffuse_dir = us + n;
-                const V3 glossy_dir = d - (2.0f * dot(d, n)) * n;                      // main.rs:120-121
-                const V3 pre = diffuse_dir + m.w * (glossy_dir - diffuse_dir);         // main.rs:122
-                V3 xdir;
-                if (!try_normalize(pre, xdir)) xdir = n;                               // main.rs:126
-                d = normalize(xdir);                                                   // Ray::new (ray.rs:134)
+                d = scattered_dir(d, n, m.w, x1, x2, sm);
                 o = hp;                                                                // origin exactly P
             }
             // a1 (.) (a2 (.) ( ... (ak (.) terminal))) : right-to-left (main.rs:123)
@@ -143,22 +108,10 @@ __global__ __launch_bounds__(256) void rt_trace_kernel(const TParams p) {
         p.rgb[3 * i + 1] = sum_g;
         p.rgb[3 * i + 2] = sum_b;
         if (p.segments) p.segments[i] = segs;
-        if (p.rng_state) {
-            uint64_t* s = p.rng_state + 4 * i;
-            s[0] = rng.s0;
-            s[1] = rng.s1;
-            s[2] = rng.s2;
-            s[3] = rng.s3;
-        }
+        if (p.rng_state) store_rng(p.rng_state + 4 * i, rng);
         n_segs += segs;
     }
-    // counters: one atomic per wave
-    n_segs = wave_sum(n_segs);
-    n_tests = wave_sum(n_tests);
-    if ((tid & 63u) == 0) {
-        if (n_segs) atomicAdd(p.counters + 0, n_segs);
-        if (n_tests) atomicAdd(p.counters + 1, n_tests);
-    }
+    flush_counters(p.counters, n_segs, n_tests, tid);
 }
 
 using TraceFn = void (*)(const TParams);
