@@ -28,6 +28,7 @@
 #include "rt_kernel.hip.h"
 #include "rt_plan.h"
 #include "rt_query.hip.h"
+#include "rt_scene_host.h"
 #include "rt_trace.hip.h"
 #include "rt_bounce.hip.h"
 #include "rt_aov.hip.h"
@@ -156,8 +157,6 @@ std::mutex g_mu;
 bool g_init = false;
 std::vector<DeviceCtx*> g_ctx;
 std::atomic<int> g_live_scenes{0};   // rt_shutdown is refused while any scene is alive (scenes point at their DeviceCtx)
-
-constexpr uint32_t REORDER_MIN_PRIMS = 64;      // from here up the primitive records are stored in the tree's depth-first leaf order
 
 // The launch-path knobs the plan reads, read once per launch
 rtplan::Knobs plan_knobs() {
@@ -659,348 +658,16 @@ static int rt_shutdown_impl(void) {
 
 static int rt_scene_destroy_impl(rt_scene* sc);
 
-// Everything rt_scene_create derives on the host from the primitive lists: the device-layout arrays and the reference's
-// candidate-filter BVH.  rt_render_frame builds it ONCE per job and uploads it to every device.
-struct HostScene {
-    rtplan::SceneShape shape;        // what the engine rules read (rt_plan.h); the rest is uploaded
-    std::vector<float4> geom, geom_pk, geom_px, mat, tri_box, geom_r;
-    std::vector<float> emis, tri;
-    float bvh_build_ms = 0.f;
-    rtbvh::FlatBVH bvh;
-    std::vector<uint32_t> big;       // culled walk: spheres far larger than the rest (shape.r_slack: the largest radius among the others)
-    uint32_t n_big = 0;
-    float tri_k = 0.f, tri_diag = 0.f, tri_es = 0.f, tri_e = 0.f;
-    std::vector<uint32_t> world_rank;   // the caller's world_index (one dummy entry when none came)
-    bool has_order = false;
-};
+using rtscene::HostScene;
+static_assert(sizeof(rtscene::F4) == sizeof(float4) && alignof(rtscene::F4) == alignof(float4), "HostScene's records are the device's float4");
 
 static int check_world(const rt_sphere* sp, uint32_t ns, const rt_triangle* tr, uint32_t nt, const uint32_t* world_index) {
     if ((ns && !sp) || (nt && !tr)) return fail(RT_ERR_BAD_ARG, "primitive pointer is NULL");
     // the kernels address nodes (64 B), geometry (16 B), materials (16 B) and triangles (36 B) with 32-bit byte offsets
     if ((uint64_t)ns + nt > RT_MAX_PRIMITIVES) return fail(RT_ERR_LIMIT, "too many primitives (RT_MAX_PRIMITIVES)");
-    if (world_index) {                   // positions in RenderInfo.world: every one of 0 .. n - 1 exactly once
-        const uint32_t np = ns + nt;
-        std::vector<bool> seen(np, false);
-        for (uint32_t i = 0; i < np; i++) {
-            if (world_index[i] >= np || seen[world_index[i]])
-                return fail(RT_ERR_BAD_ARG, "world_index is not a permutation of 0 .. n_spheres + n_triangles - 1");
-            seen[world_index[i]] = true;
-        }
-    }
+    if (world_index && !rtscene::world_is_permutation(world_index, ns + nt))
+        return fail(RT_ERR_BAD_ARG, "world_index is not a permutation of 0 .. n_spheres + n_triangles - 1");
     return RT_OK;
-}
-
-static void build_host_scene(const rt_sphere* sp, uint32_t ns, const rt_triangle* tr, uint32_t nt, const uint32_t* world_index,
-                             HostScene& hs) {
-    rtplan::SceneShape& sh = hs.shape;
-    sh.n_sph = ns;
-    sh.n_tri = nt;
-    hs.has_order = world_index != nullptr && ns + nt > 0;
-    const uint32_t np = ns + nt;
-    // the reference's candidate-filter BVH (slave main.rs:60), built once per scene instead of per strip
-    std::vector<rtbvh::Box> boxes(np);
-    for (uint32_t i = 0; i < ns; i++) {              // Sphere::aabb, sphere.rs:65-72
-        const float c[3] = {sp[i].cx, sp[i].cy, sp[i].cz};
-        for (int a = 0; a < 3; a++) {
-            boxes[i].lo[a] = c[a] - sp[i].radius;
-            boxes[i].hi[a] = c[a] + sp[i].radius;
-        }
-    }
-    for (uint32_t i = 0; i < nt; i++) {              // Triangle::aabb, mesh.rs:46-96 (min_by / max_by order a,c,b)
-        for (int a = 0; a < 3; a++) {
-            const float va = tr[i].a[a], vb = tr[i].b[a], vc = tr[i].c[a];
-            const float m1 = va > vc ? vc : va;      // min_by(a, c): a unless a > c
-            boxes[ns + i].lo[a] = m1 > vb ? vb : m1;
-            const float x1 = va > vc ? va : vc;      // max_by(a, c): c unless a > c
-            boxes[ns + i].hi[a] = x1 > vb ? x1 : vb;
-        }
-    }
-    auto tb0 = std::chrono::steady_clock::now();
-    {
-        // BVH::build(&mut req.world) (slave main.rs:60) numbers the shapes by their position in `world`: start the build
-        // from the primitives in that order (rt_bvh.h); ties between equal distances then fall as in the reference
-        std::vector<uint32_t> order;
-        if (hs.has_order) {
-            order.resize(np);
-            for (uint32_t i = 0; i < np; i++) order[world_index[i]] = i;
-        }
-        hs.bvh = rtbvh::build(boxes, hs.has_order ? order.data() : nullptr);
-    }
-    rtbvh::FlatBVH& bvh = hs.bvh;
-    hs.bvh_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tb0).count();
-    sh.n_internal = (uint32_t)bvh.trav.size();        // before the placeholders below
-    if (bvh.nodes.empty()) bvh.nodes.push_back(rtbvh::FlatNode{{0, 0, 0}, 0xffffffffu, {0, 0, 0}, 0});
-    if (bvh.leaf_of.empty()) bvh.leaf_of.push_back(0);
-    if (bvh.trav.empty()) bvh.trav.push_back(rtbvh::TravNode{});
-    if (bvh.travq.empty()) bvh.travq.push_back(rtbvh::QNode{});
-    // ---- Storage order (round 3).  The records the kernels fetch per primitive — sphere (centre, radius), material, emission, triangle
-    // vertices — are laid out in the order in which the tree's depth-first walk meets the leaves, not in the caller's order: the
-    // primitives a ray (and the rays of a wave) touch are then neighbours in memory, four sphere records to a 64-byte line, instead of
-    // scattered over megabytes.  Only the library's INTERNAL primitive numbers change (spheres stay below n_sph, triangles above): leaf
-    // references, leaf ranks, the `big` list and the world positions are renumbered with them, and every rule that looks at a
-    // primitive's place in `world` (distance ties) goes through world_rank, which from here on always exists.
-    std::vector<rt_sphere> sp_store;
-    std::vector<rt_triangle> tr_store;
-    std::vector<uint32_t> wi_store(np ? np : 1, 0u);
-    for (uint32_t i = 0; i < np; i++) wi_store[i] = world_index ? world_index[i] : i;
-    if (np >= REORDER_MIN_PRIMS && dbg(DBG_REORDER) != 0) {
-        std::vector<uint32_t> old_of(np), new_of(np);
-        for (uint32_t i = 0; i < np; i++) old_of[i] = i;
-        std::stable_sort(old_of.begin(), old_of.begin() + ns, [&](uint32_t x, uint32_t y) { return bvh.leaf_of[x] < bvh.leaf_of[y]; });
-        std::stable_sort(old_of.begin() + ns, old_of.end(), [&](uint32_t x, uint32_t y) { return bvh.leaf_of[x] < bvh.leaf_of[y]; });
-        for (uint32_t i = 0; i < np; i++) new_of[old_of[i]] = i;
-        sp_store.resize(ns);
-        tr_store.resize(nt);
-        std::vector<rtbvh::Box> boxes2(np);
-        std::vector<uint32_t> leaf2(np), wi2(np);
-        for (uint32_t i = 0; i < np; i++) {
-            const uint32_t o = old_of[i];
-            if (i < ns) sp_store[i] = sp[o];
-            else tr_store[i - ns] = tr[o - ns];
-            boxes2[i] = boxes[o];
-            leaf2[i] = bvh.leaf_of[o];
-            wi2[i] = wi_store[o];
-        }
-        boxes.swap(boxes2);
-        bvh.leaf_of.swap(leaf2);
-        wi_store.swap(wi2);
-        auto remap = [&](uint32_t& ref) {
-            if (ref & rtbvh::LEAF_BIT) ref = rtbvh::LEAF_BIT | new_of[ref & ~rtbvh::LEAF_BIT];
-        };
-        for (rtbvh::TravNode& t : bvh.trav) { remap(t.left); remap(t.right); }
-        for (rtbvh::QNode& q : bvh.travq) { remap(q.left); remap(q.right); }
-        remap(bvh.root_ref);
-        sp = sp_store.data();
-        tr = tr_store.data();
-        hs.has_order = true;                 // (ties of the plain linear-scan semantics: by place in `world`, no longer by number)
-    }
-    sh.bvh_depth = bvh.depth;
-    sh.root_ref = bvh.root_ref;
-    if (hs.has_order) hs.world_rank.assign(wi_store.begin(), wi_store.begin() + np);
-    else hs.world_rank.assign(1, 0u);
-    sh.n_sph_pad = (ns + rtk::UNROLL - 1) / rtk::UNROLL * rtk::UNROLL;
-    std::vector<float4>& geom = hs.geom;
-    std::vector<float4>& mat = hs.mat;
-    std::vector<float>& emis = hs.emis;
-    std::vector<float>& tri = hs.tri;
-    geom.assign(sh.n_sph_pad ? sh.n_sph_pad : 1, make_float4(0.f, 0.f, 0.f, 0.f));
-    mat.assign(np ? np : 1, make_float4(0.f, 0.f, 0.f, 0.f));
-    emis.assign(np ? np : 1, 0.f);
-    tri.assign((size_t)nt * 9 + 1, 0.f);
-    for (uint32_t i = 0; i < ns; i++) {
-        // rr = radius.powi(2) (sphere.rs:45): one rounded multiply
-        volatile float rr = sp[i].radius * sp[i].radius;
-        geom[i] = make_float4(sp[i].cx, sp[i].cy, sp[i].cz, rr);
-        mat[i] = make_float4(sp[i].albedo_r, sp[i].albedo_g, sp[i].albedo_b, sp[i].roughness);
-        emis[i] = sp[i].emission;
-    }
-    // padding spheres can never pass either phase: rr = -inf makes every discriminant -inf
-    for (uint32_t i = ns; i < sh.n_sph_pad; i++) geom[i] = make_float4(0.f, 0.f, 0.f, -INFINITY);
-    // pair layout for the packed-FP32 broad phase: (c0x,c1x,c0y,c1y) (c0z,c1z,rr0,rr1)
-    std::vector<float4>& geom_pk = hs.geom_pk;
-    geom_pk.assign(geom.size(), make_float4(0.f, 0.f, 0.f, 0.f));
-    for (uint32_t i = 0; i + 1 < sh.n_sph_pad; i += 2) {
-        geom_pk[i] = make_float4(geom[i].x, geom[i + 1].x, geom[i].y, geom[i + 1].y);
-        geom_pk[i + 1] = make_float4(geom[i].z, geom[i + 1].z, geom[i].w, geom[i + 1].w);
-    }
-    for (uint32_t i = 0; i < nt; i++) {
-        std::memcpy(&tri[(size_t)i * 9], tr[i].a, 9 * sizeof(float));
-        mat[ns + i] = make_float4(tr[i].albedo_r, tr[i].albedo_g, tr[i].albedo_b, tr[i].roughness);
-        emis[ns + i] = tr[i].emission;
-    }
-    // expanded-form broad phase records: w = |c|^2 - rr - 2^-16 (|c|^2 + rr), evaluated in
-    // double and rounded DOWN to f32 (conservative).
-    std::vector<float4>& geom_px = hs.geom_px;
-    geom_px.assign(geom.size(), make_float4(0.f, 0.f, 0.f, 0.f));
-    {
-        std::vector<float4> px(geom.size());
-        std::vector<double> ratio;
-        const double K = std::ldexp(1.0, -16);
-        for (uint32_t i = 0; i < sh.n_sph_pad; i++) {
-            if (i >= ns) {
-                px[i] = make_float4(0.f, 0.f, 0.f, INFINITY);      // w = +inf: t = -inf, never a candidate
-                continue;
-            }
-            const double cc = (double)sp[i].cx * sp[i].cx + (double)sp[i].cy * sp[i].cy + (double)sp[i].cz * sp[i].cz;
-            const double rr = (double)geom[i].w;
-            const double w = cc - rr - K * (cc + rr);
-            float wf = (float)w;
-            if ((double)wf > w) wf = std::nextafterf(wf, -INFINITY);
-            px[i] = make_float4(sp[i].cx, sp[i].cy, sp[i].cz, wf);
-            if (rr > 0) ratio.push_back(K * 2.0 * cc / rr);
-        }
-        for (uint32_t i = 0; i + 1 < sh.n_sph_pad; i += 2) {
-            geom_px[i] = make_float4(px[i].x, px[i + 1].x, px[i].y, px[i + 1].y);
-            geom_px[i + 1] = make_float4(px[i].z, px[i + 1].z, px[i].w, px[i + 1].w);
-        }
-        // heuristic: the expanded form's additive margin 2^-16 (|o|^2 + |c|^2 + rr) must stay small against rr
-        // for the typical sphere, otherwise candidate lists blow up (c5-class scenes): then use the oc form.
-        bool ok = !ratio.empty();
-        if (ok) {
-            std::nth_element(ratio.begin(), ratio.begin() + ratio.size() / 2, ratio.end());
-            ok = ratio[ratio.size() / 2] < 0.5;
-        }
-        for (uint32_t i = 0; i < ns && ok; i++)
-            ok = std::isfinite(px[i].x) && std::isfinite(px[i].y) && std::isfinite(px[i].z) && std::isfinite(px[i].w);
-        sh.expanded = ok;
-    }
-    hs.tri_box.assign((size_t)nt * 2 + 1, make_float4(0.f, 0.f, 0.f, 0.f));
-    for (uint32_t i = 0; i < nt; i++) {
-        const rtbvh::Box& b = boxes[ns + i];
-        hs.tri_box[2 * (size_t)i] = make_float4(b.lo[0], b.lo[1], b.lo[2], 0.f);
-        hs.tri_box[2 * (size_t)i + 1] = make_float4(b.hi[0], b.hi[1], b.hi[2], 0.f);
-    }
-    {
-        // worthwhile only if the grid step is small against the primitives (else the rounded boxes admit crowds of
-        // false leaves): median primitive box edge >= 8 steps on every axis
-        bool ok = bvh.grid.ok && np > 1;
-        if (ok) {
-            std::vector<float> edge(np);
-            for (uint32_t i = 0; i < np; i++) {
-                float e = INFINITY;
-                for (int a3 = 0; a3 < 3; a3++)
-                    e = fminf(e, (boxes[i].hi[a3] - boxes[i].lo[a3]) / bvh.grid.step[a3]);
-                edge[i] = e;
-            }
-            std::nth_element(edge.begin(), edge.begin() + np / 2, edge.end());
-            ok = edge[np / 2] >= 8.0f;
-        }
-        sh.quant_ok = ok;
-        // leaf density = sum of primitive box areas / area of the scene box ~ leaves a random ray reaches; above ~2
-        // the walk is bound by the exact leaf tests, where the lighter exact-node kernel (5 waves/SIMD) wins
-        double area = 0.0, root = 0.0;
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (uint32_t i = 0; i < np; i++) {
-            const double ex = (double)boxes[i].hi[0] - boxes[i].lo[0], ey = (double)boxes[i].hi[1] - boxes[i].lo[1],
-                         ez = (double)boxes[i].hi[2] - boxes[i].lo[2];
-            area += ex * ey + ey * ez + ez * ex;
-            for (int a3 = 0; a3 < 3; a3++) {
-                lo[a3] = fminf(lo[a3], boxes[i].lo[a3]);
-                hi[a3] = fmaxf(hi[a3], boxes[i].hi[a3]);
-            }
-        }
-        if (np) {
-            const double ex = (double)hi[0] - lo[0], ey = (double)hi[1] - lo[1], ez = (double)hi[2] - lo[2];
-            root = ex * ey + ey * ez + ez * ex;
-        }
-        sh.leaf_density = root > 0.0 ? (float)(area / root) : INFINITY;
-    }
-    hs.geom_r.assign(ns ? ns : 1, make_float4(0.f, 0.f, 0.f, 0.f));
-    for (uint32_t i = 0; i < ns; i++) {
-        hs.geom_r[i] = make_float4(sp[i].cx, sp[i].cy, sp[i].cz, sp[i].radius);
-        if (sp[i].radius < 0.0f) sh.inverted_boxes = true;
-    }
-    // culled walk: its distance bound carries sqrt(2) * (largest radius) of slack, so the few spheres far larger than the
-    // rest (a ground sphere) are listed apart and root-tested at every query start instead
-    {
-        std::vector<float> rad(ns);
-        for (uint32_t i = 0; i < ns; i++) rad[i] = fabsf(sp[i].radius);
-        float med = 0.f;
-        if (ns) {
-            std::vector<float> tmp(rad);
-            std::nth_element(tmp.begin(), tmp.begin() + ns / 2, tmp.end());
-            med = tmp[ns / 2];
-        }
-        std::vector<uint32_t> cand;
-        for (uint32_t i = 0; i < ns; i++)
-            if (rad[i] > 8.0f * med) cand.push_back(i);
-        std::sort(cand.begin(), cand.end(), [&](uint32_t a, uint32_t b) { return rad[a] > rad[b] || (rad[a] == rad[b] && a < b); });
-        if (cand.size() > 16) cand.resize(16);
-        std::vector<char> is_big(ns ? ns : 1, 0);
-        for (uint32_t i : cand) is_big[i] = 1;
-        float rs = 0.f;
-        for (uint32_t i = 0; i < ns; i++)
-            if (!is_big[i] && rad[i] > rs) rs = rad[i];
-        hs.big = cand;
-        hs.n_big = (uint32_t)cand.size();
-        sh.r_slack = rs;
-        if (hs.big.empty()) hs.big.push_back(0);
-        // Does it pay?  The ratio below is the expected number of (non-big) primitive boxes a random line through their
-        // common box meets (Cauchy: box areas add up).  tools/cull_matrix.py, 2560x1440: sparse fields at 0.06...0.35 lose
-        // 5...7 % to the ordering and the early root tests, c5 at 0.95 gains 12 %, fields / mixed radii / dense overlap at
-        // 2...30 gain 1.35...3.5 x.  And the bound's slack (1.5 r_slack) must be small against the scene.
-        double area = 0.0;
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (uint32_t i = 0; i < ns; i++) {
-            if (is_big[i]) continue;
-            const double e = 2.0 * rad[i];
-            area += 3.0 * e * e;
-            const float c[3] = {sp[i].cx, sp[i].cy, sp[i].cz};
-            for (int a3 = 0; a3 < 3; a3++) {
-                lo[a3] = fminf(lo[a3], c[a3] - rad[i]);
-                hi[a3] = fmaxf(hi[a3], c[a3] + rad[i]);
-            }
-        }
-        const double ex = (double)hi[0] - lo[0], ey = (double)hi[1] - lo[1], ez = (double)hi[2] - lo[2];
-        const double root = ex * ey + ey * ez + ez * ex, diag = std::sqrt(ex * ex + ey * ey + ez * ez);
-        sh.cull_density = root > 0.0 ? (float)(area / root) : 0.f;
-        sh.cull_pays = nt == 0 && root > 0.0 && std::isfinite(area / root) && area / root >= 0.7 && (double)rs <= 0.05 * diag;
-        // (What the bounds claim — no accepted root of a primitive outside the `big` list enters its box beyond cull_bound /
-        // cull_bound_tri of its compared distance — is tested by itself, on 1.8e7 seeded and adversarial (ray, primitive, box)
-        // triples incl. K -> 0.25, |det| -> 1e-5, origins at 1e3 and tangent rays: tests/test_cull_lemma.py with the bounds
-        // of csrc/rt_cull.h; reduced soaks against the oracle: tests/test_gpu_cull_soaks.py.)
-        // Scenes with triangles (culled walk over the EXACT nodes, cull_bound_tri in rt_cull.h): its bound needs every
-        // triangle outside the `big` list to have K = |e1||e2| <= 0.25 (with the reference's |det| >= 1e-5 that keeps the
-        // computed determinant within 1.5 % of the true one) and carries the largest box diagonal as slack, so triangles with
-        // a larger K, or a box diagonal of more than 8 x the median, join the list (16 entries with the spheres; more: no culling).
-        if (nt > 0) {
-            std::vector<float> dg(nt), kk(nt), es(nt), em(nt);
-            for (uint32_t i = 0; i < nt; i++) {
-                double e1 = 0, e2 = 0, e3 = 0, d2 = 0;
-                for (int a3 = 0; a3 < 3; a3++) {
-                    const double ab = (double)tr[i].b[a3] - tr[i].a[a3], ac = (double)tr[i].c[a3] - tr[i].a[a3], bc = (double)tr[i].c[a3] - tr[i].b[a3];
-                    e1 += ab * ab; e2 += ac * ac; e3 += bc * bc;
-                    const double ext = (double)boxes[ns + i].hi[a3] - boxes[ns + i].lo[a3];
-                    d2 += ext * ext;
-                }
-                e1 = std::sqrt(e1); e2 = std::sqrt(e2); e3 = std::sqrt(e3);
-                dg[i] = (float)(std::sqrt(d2) * 1.0001);
-                kk[i] = (float)(e1 * e2 * 1.0001);
-                es[i] = (float)((e1 + e2) * 1.0001);
-                em[i] = (float)(std::max(e1, std::max(e2, e3)) * 1.0001);
-            }
-            std::vector<float> tmp(dg);
-            std::nth_element(tmp.begin(), tmp.begin() + nt / 2, tmp.end());
-            const float med_d = tmp[nt / 2];
-            std::vector<uint32_t> bigt;
-            bool ok = true;
-            for (uint32_t i = 0; i < nt && ok; i++) {
-                const bool fin = std::isfinite(dg[i]) && std::isfinite(kk[i]);
-                if (!fin) ok = false;
-                else if (kk[i] > 0.25f || dg[i] > 8.0f * med_d) bigt.push_back(ns + i);
-                if (bigt.size() + hs.n_big > 16) ok = false;
-            }
-            if (ok) {
-                std::vector<char> isb(nt, 0);
-                for (uint32_t q : bigt) isb[q - ns] = 1;
-                double tarea = 0.0;
-                for (uint32_t i = 0; i < nt; i++) {
-                    if (isb[i]) continue;
-                    hs.tri_k = fmaxf(hs.tri_k, kk[i]);
-                    hs.tri_diag = fmaxf(hs.tri_diag, dg[i]);
-                    hs.tri_es = fmaxf(hs.tri_es, es[i]);
-                    hs.tri_e = fmaxf(hs.tri_e, em[i]);
-                    const rtbvh::Box& b = boxes[ns + i];
-                    const double ex2 = (double)b.hi[0] - b.lo[0], ey2 = (double)b.hi[1] - b.lo[1], ez2 = (double)b.hi[2] - b.lo[2];
-                    tarea += ex2 * ey2 + ey2 * ez2 + ez2 * ex2;
-                    for (int a3 = 0; a3 < 3; a3++) {
-                        lo[a3] = fminf(lo[a3], b.lo[a3]);
-                        hi[a3] = fmaxf(hi[a3], b.hi[a3]);
-                    }
-                }
-                const double fx = (double)hi[0] - lo[0], fy = (double)hi[1] - lo[1], fz = (double)hi[2] - lo[2];
-                const double root2 = fx * fy + fy * fz + fz * fx, diag2 = std::sqrt(fx * fx + fy * fy + fz * fz);
-                const double dens = root2 > 0.0 ? (area + tarea) / root2 : 0.0;
-                if (hs.n_big) hs.big.resize(hs.n_big); else hs.big.clear();
-                for (uint32_t q : bigt) hs.big.push_back(q);
-                hs.n_big = (uint32_t)hs.big.size();
-                if (hs.big.empty()) hs.big.push_back(0);
-                sh.cull_density = (float)dens;
-                sh.xcull_pays = std::isfinite(dens) && dens >= 0.7 && (double)rs <= 0.05 * diag2 && (double)hs.tri_diag <= 0.05 * diag2;
-            }
-            sh.tri_ok = ok;
-        }
-    }
 }
 
 // HostScene -> device: allocate, upload on the device's stream, hand back the handle
@@ -1098,7 +765,7 @@ static int rt_scene_create_impl(int device, const rt_sphere* sp, uint32_t ns, co
     if (!g_init) return fail(RT_ERR_NOT_INITIALIZED, "call rt_init() first");
     if (device < 0 || device >= (int)g_ctx.size()) return fail(RT_ERR_BAD_DEVICE, "bad device ordinal");
     HostScene hs;
-    build_host_scene(sp, ns, tr, nt, world_index, hs);
+    rtscene::build_host_scene(sp, ns, tr, nt, world_index, dbg(DBG_REORDER) != 0, hs);
     return upload_scene(device, hs, out);
 }
 
@@ -2472,7 +2139,7 @@ int rt_frame_ctx_set_world_impl(rt_frame_ctx* fc, const rt_sphere* sp, uint32_t 
     const auto t0 = std::chrono::steady_clock::now();
     // the world's host side once per job (the reference rebuilds the BVH per strip, slave main.rs:60)
     HostScene hs;
-    build_host_scene(sp, ns, tr, nt, world_index, hs);
+    rtscene::build_host_scene(sp, ns, tr, nt, world_index, dbg(DBG_REORDER) != 0, hs);
     fc->hs = &hs;
     fc->have_world = false;
     fc->cost_valid = false;            // another world: the strips' costs are to be measured again

@@ -26,6 +26,7 @@ namespace rtk {
 
 constexpr int BLOCK = 256;       // 4 waves
 constexpr int LTREE_BLOCK = 1024;   // LDS-resident tree kernels: one workgroup of 16 waves per CU
+constexpr int UNROLL = 8;        // broad-phase unroll; chunk sizes are padded to this
 constexpr int MAXC = RT_MAXC;    // candidate list slots per lane (per chunk)
 constexpr int CHUNK = 2048;      // max spheres per LDS chunk (32 KiB): list entries carry an 8-bit group index
 constexpr int MAX_BATCH = 64;    // strips per launch

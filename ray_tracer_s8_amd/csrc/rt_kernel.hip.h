@@ -67,7 +67,6 @@ namespace rtk {
 #ifndef RT_MINWAVES_QTRAV       // quantised-node kernels: 96 VGPRs, no spill slots (unbounded they take 97-99 = 4 waves/SIMD)
 #define RT_MINWAVES_QTRAV 5
 #endif
-constexpr int UNROLL = 8;        // broad-phase unroll; chunk sizes are padded to this
 #ifndef RT_STEPS_PER_CHECK
 #define RT_STEPS_PER_CHECK 8
 #endif

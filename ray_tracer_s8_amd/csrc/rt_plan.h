@@ -33,7 +33,7 @@ constexpr uint32_t TRAVERSE_MIN_PRIMS = 2;      // from this many primitives up 
                                                 // with the sample units the LDS-resident tree leads the scan on every scene of tools/small_scene_matrix.py —
                                                 // 2 ... 32 spheres, five families, 1.02 ... 1.36 x — but one pile of 32, and on c2's 16-sphere room by 5 ... 8 %.)
 
-// The scalar facts of a scene the rules read (rt_api.hip build_host_scene computes them).
+// The scalar facts of a scene the rules read (rt_scene_host.h build_host_scene computes them).
 struct SceneShape {
     uint32_t n_sph = 0, n_sph_pad = 0, n_tri = 0;   // spheres (padded to rtk::UNROLL), triangles
     uint32_t bvh_depth = 0, n_internal = 0;         // the reference BVH: depth, internal nodes

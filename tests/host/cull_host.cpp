@@ -20,6 +20,7 @@
 #include <cstring>
 
 #include "rt_cull.h"
+#include "rt_scene_host.h"
 
 namespace {
 
@@ -288,7 +289,7 @@ void cull_check_spheres(uint64_t seed, uint64_t n, int mode, double slack_factor
 // (|det| between 1 and 30 times the reference's 10^-5 threshold), 3 origins at |o| ~ 10^3, 4 slivers (edges at 10^-3..-1
 // rad) seen from far, 5 = 1 and 2 together (the largest triangles the bound admits, at grazing angles: roots off by per cent).
 // The bound's scene maxima are this triangle's own values, formed as the host forms them
-// (rt_api.hip build_host_scene: in double, times 1.0001, rounded to f32).
+// (rt_scene_host.h tri_box, tri_measures: in double, times 1.0001, rounded to f32).
 void cull_check_triangles(uint64_t seed, uint64_t n, int mode, double* out) {
     Rng g{seed * 0x100000001b3ull + 0x7419ull + (uint64_t)mode};
     Tally ty;
@@ -311,26 +312,14 @@ void cull_check_triangles(uint64_t seed, uint64_t n, int mode, double* out) {
         V3 A = {(float)g.range(-ascale, ascale), (float)g.range(-ascale, ascale), (float)g.range(-ascale, ascale)};
         const V3 B = {(float)(A.x + l1 * u1.x), (float)(A.y + l1 * u1.y), (float)(A.z + l1 * u1.z)};
         const V3 C = {(float)(A.x + l2 * u2.x), (float)(A.y + l2 * u2.y), (float)(A.z + l2 * u2.z)};
-        // the rounded edges as the host and the reference see them
-        double e1 = 0, e2 = 0, e3 = 0, d2 = 0;
-        const float va[3] = {A.x, A.y, A.z}, vb[3] = {B.x, B.y, B.z}, vc[3] = {C.x, C.y, C.z};
-        float lo[3], hi[3];
-        for (int a = 0; a < 3; a++) {
-            const double ab = (double)vb[a] - va[a], ac = (double)vc[a] - va[a], bc = (double)vc[a] - vb[a];
-            e1 += ab * ab;
-            e2 += ac * ac;
-            e3 += bc * bc;
-            lo[a] = fminf(fminf(va[a], vb[a]), vc[a]);       // Triangle::aabb, mesh.rs:46-96
-            hi[a] = fmaxf(fmaxf(va[a], vb[a]), vc[a]);
-            const double ext = (double)hi[a] - lo[a];
-            d2 += ext * ext;
-        }
-        e1 = std::sqrt(e1);
-        e2 = std::sqrt(e2);
-        e3 = std::sqrt(e3);
-        const float kk = (float)(e1 * e2 * 1.0001), dg = (float)(std::sqrt(d2) * 1.0001), es = (float)((e1 + e2) * 1.0001),
-                    em = (float)(std::fmax(e1, std::fmax(e2, e3)) * 1.0001);
-        if (kk > 0.25f) continue;                            // such a triangle is in the `big` list: no claim
+        // the rounded edges as the host and the reference see them: the host's own box and measures
+        rt_triangle tri{};
+        tri.a[0] = A.x; tri.a[1] = A.y; tri.a[2] = A.z;
+        tri.b[0] = B.x; tri.b[1] = B.y; tri.b[2] = B.z;
+        tri.c[0] = C.x; tri.c[1] = C.y; tri.c[2] = C.z;
+        const rtbvh::Box box = rtscene::tri_box(tri);                       // Triangle::aabb, mesh.rs:46-96
+        const rtscene::TriMeasures m = rtscene::tri_measures(tri, box);
+        if (m.kk > 0.25f) continue;                            // such a triangle is in the `big` list: no claim
         // a point of the triangle's plane in or near the triangle, and an origin
         double bu = g.range(-0.05, 1.05), bv = g.range(-0.05, 1.05);
         if (bu + bv > 1.0 && g.u() < 0.9) {
@@ -362,9 +351,9 @@ void cull_check_triangles(uint64_t seed, uint64_t n, int mode, double* out) {
         const float D = compared_distance(o, d, t);
         float le32 = 0;
         double le64 = 0;
-        const bool c32 = entry_f32(o, d, lo, hi, &le32), c64 = entry_f64(o, d, lo, hi, &le64);
-        const float bound = rtk::cull_bound_tri(D, o.x, o.y, o.z, kk, dg, es, em);
-        const double rec[] = {o.x, o.y, o.z, d.x, d.y, d.z, A.x, A.y, A.z, kk, t, D, le32, le64, bound, (double)mode};
+        const bool c32 = entry_f32(o, d, box.lo, box.hi, &le32), c64 = entry_f64(o, d, box.lo, box.hi, &le64);
+        const float bound = rtk::cull_bound_tri(D, o.x, o.y, o.z, m.kk, m.dg, m.es, m.em);
+        const double rec[] = {o.x, o.y, o.z, d.x, d.y, d.z, A.x, A.y, A.z, m.kk, t, D, le32, le64, bound, (double)mode};
         ty.judge(c32, le32, c64, le64, bound, rec, 16);
     }
     ty.out(out);

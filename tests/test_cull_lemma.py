@@ -6,8 +6,8 @@ tests/host/cull_host.cpp evaluates, for single (ray, primitive, box) triples, wi
 accepted enters its own box no later than bound(its compared distance).  >= 10^7 seeded triples: generic, tangent rays,
 far-and-small spheres (the reference's false-root domain), origins at |o| ~ 10^3, rays that start on or inside spheres;
 triangles with K = |e1||e2| up to and at the 0.25 limit, determinants 1..30 times the reference's 10^-5 rejection
-threshold (grazing), slivers, far origins.  The host constants behind `big` lists and K <= 0.25 (rt_api.hip
-build_host_scene) cite this test."""
+threshold (grazing), slivers, far origins.  The host constants behind `big` lists and K <= 0.25 (rt_scene_host.h
+sphere_cull_rule, triangle_cull_rule) cite this test; the triangles' box and maxima are that header's tri_box, tri_measures."""
 import ctypes as C
 import subprocess
 from pathlib import Path
@@ -19,14 +19,15 @@ ROOT = Path(__file__).resolve().parents[1]
 SRC = ROOT / "tests" / "host" / "cull_host.cpp"
 OUT = ROOT / "tests" / "host" / "_build" / "libcull_host.so"
 HDR = ROOT / "ray_tracer_s8_amd" / "csrc" / "rt_cull.h"
+DEPS = [SRC, HDR, HDR.parent / "rt_scene_host.h", HDR.parent / "rt_bvh.h"]
 
 
 @pytest.fixture(scope="module")
 def lib():
     OUT.parent.mkdir(exist_ok=True)
-    if not OUT.exists() or OUT.stat().st_mtime < max(SRC.stat().st_mtime, HDR.stat().st_mtime):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", f"-I{HDR.parent}",
-                        "-o", str(OUT), str(SRC)], check=True)
+    if not OUT.exists() or OUT.stat().st_mtime < max(d.stat().st_mtime for d in DEPS):
+        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-ffp-contract=off", "-fno-fast-math", f"-I{HDR.parent}",
+                        f"-I{ROOT / 'include'}", "-o", str(OUT), str(SRC)], check=True)
     l = C.CDLL(str(OUT))
     l.cull_check_spheres.argtypes = [C.c_uint64, C.c_uint64, C.c_int, C.c_double, C.c_void_p]
     l.cull_check_triangles.argtypes = [C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
