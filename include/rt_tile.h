@@ -50,7 +50,9 @@ extern "C" {
                                   (4, additions only: feature buffers of a strip rt_scene_render_aov /
                                      rt_scene_render_aovs_device with rt_aov_planes)
                                   (4, additions only: the edge-avoiding a-trous denoiser rt_scene_denoise /
-                                     rt_scene_denoise_device with rt_denoise_request, RT_DENOISE_MAX_ITERATIONS) */
+                                     rt_scene_denoise_device with rt_denoise_request, RT_DENOISE_MAX_ITERATIONS)
+                                  (4, additions only: direct lighting of caller rays rt_scene_light_count / rt_scene_direct /
+                                     rt_scene_direct_device with rt_direct_request, rt_direct, RT_DIRECT_*) */
 
 /* ---- status codes --------------------------------------------------------------- */
 typedef enum rt_status {
@@ -484,6 +486,64 @@ RT_API int rt_scene_bounce(rt_scene* scene, const rt_bounce_request* req, rt_ray
 RT_API int rt_scene_bounce_device(rt_scene* scene, const rt_bounce_request* req, void* d_rays, uint32_t n, void* d_rng_state,
                                   const void* d_active, const void* d_n_active, void* d_bounce, void* d_hits,
                                   void* d_next_active, void* d_n_next, void* hip_stream);
+
+/* ---- direct lighting: one light sample per hit of the caller's rays ------------------------- */
+/* Next-event estimation for an integrator built from the path steps above: for every active hit record (the rt_hit a step wrote to
+ * out_hits) the library picks one emitter of the scene, draws a point on it from the ray's own RNG state, traces the shadow ray and
+ * returns the Lambertian direct-light estimate, in one launch, one lane per record, the state advanced in place.  Every operation
+ * below is one IEEE f32 rounding in the order written (no fused multiply-add, correctly rounded division and sqrt); a dot product
+ * a.b is (ax*bx + ay*by) + az*bz; u01 is the f32 in [0, 1) of gen_range(0.0..1.0) on the ray's xoshiro256++ state.
+ *
+ *   - Emitters: the primitives with emission > 0 (a NaN emits nothing), listed in ascending position in RenderInfo.world (the value
+ *     rt_hit.index reports); M = rt_scene_light_count() is their number.  The list is made once by rt_scene_create.
+ *   - Active list: as for rt_scene_bounce*.  active == NULL (device form: d_active and d_n_active both NULL) takes all n records;
+ *     otherwise n_active indices < n.  A record that is not listed has no byte of its state or of its rt_direct touched.  The host
+ *     form checks every index (RT_ERR_BAD_ARG); the device form reads the length from *d_n_active ON THE DEVICE, takes
+ *     min(n, *d_n_active) entries and skips an index >= n: the next_active / n_next of a bounce step are valid arguments as they stand.
+ *   - Skipped records: a listed record with hits[i].index == RT_HIT_NONE gets status RT_DIRECT_SKIPPED, light = RT_HIT_NONE and every
+ *     other field 0; it takes no draw and its state is unchanged.  Otherwise, when M == 0: RT_DIRECT_NO_LIGHTS on the same terms.
+ *   - Draws, all from state i, the advanced state written back for every record that drew:
+ *       u = u01; the emitter is k = min((uint32_t)(u * (float)M), M - 1) of the list;
+ *       a sphere light (centre c, radius r): one UnitSphere draw us = (x1*f, x2*f, 1 - 2*s), s = x1*x1 + x2*x2 the accepted pair of
+ *         Uniform(-1, 1) draws (rejected while s >= 1), f = 2 * sqrt(1 - s): the draw of a scattering hit (main.rs:119);
+ *         L = c + r * us per component, nl = us;
+ *       a triangle light (a, b, c): u1 = u01, u2 = u01; if u1 + u2 > 1 then u1 = 1 - u1 and u2 = 1 - u2;
+ *         L = a + (u1 * (b - a) + u2 * (c - a)) per component; nl = normalize_or_zero((a - b) x (a - c)), the normal rt_hit reports.
+ *   - Geometry: P = hits[i].p*, n = hits[i].n* as given (not flipped: the reference's diffuse lobe is about that normal);
+ *       v = L - P; d2 = (vx*vx + vy*vy) + vz*vz; w = v / sqrt(d2); cs = n.w;
+ *       cl = -(nl.w) for a sphere light, |nl.w| for a triangle light (ray_color returns em * albedo from either side of a triangle).
+ *     If !(cs > 0) or !(cl > 0) or d2 is 0 or not finite: status RT_DIRECT_FACING_AWAY, rgb = 0, light and l* written, no ray traced.
+ *   - Visibility: the shadow ray is Ray::new(P, v) (the direction normalised by division: it is w) in the window
+ *     [req->t_min, req->t_max); its closest hit is found as rt_scene_intersect finds it under req->flags (same engines, a tree
+ *     deeper than the walk's stack takes the scan, tile-only flags are ignored).  RT_DIRECT_LIT exactly when that hit's primitive is
+ *     emitter k; otherwise RT_DIRECT_OCCLUDED with rgb = 0.
+ *   - Estimate (without the surface albedo: the caller multiplies by the rt_bounce.rgb of the step and by its throughput):
+ *       rgb = (albedo_k * emission_k) * W per channel;
+ *       sphere light:   W = ((cs * cl) * ((4 * (r*r)) * (float)M)) / d2      (the pi of the area and of the Lambertian 1/pi cancel);
+ *       triangle light: W = ((cs * cl) * (A * (float)M)) / (PI * d2), A = 0.5 * sqrt(c.c) of c = (a - b) x (a - c), PI the f32 pi.
+ *   - rt_direct: rgb; light = the world position of emitter k; l* = L; status.
+ *   - RT_ERR_BAD_ARG, and nothing launched: a NULL scene, request, hits, rng_state or out; n == 0; reserved != 0; one of active /
+ *     n_active given without the other; in the host form an index >= n or n_active > n.  RT_ERR_LIMIT: M > 2^23.
+ *   - Counters (rt_tile_stats): ray_segments = shadow rays traced; primary_rays = 0; broad_candidates = exact root tests; kernel_ms;
+ *     h2d_ms (hits, states, the list) and d2h_ms (states, samples) of the host form; n_launches; engine (as for rt_scene_intersect).
+ *   - Limits: the estimate equals ray_color's next bounce in expectation only at a hit of roughness 0.  A hit point inside an emissive
+ *     sphere sees that sphere as dark (cl <= 0).  The emitter is picked uniformly, not by power.  A caller who adds the estimate drops
+ *     the RT_BOUNCE_EMITTED term of the FOLLOWING step, or the light is counted twice.
+ * No per-scene scratch on the device: launches on different streams may overlap.   */
+typedef struct rt_direct_request { uint32_t flags; uint32_t reserved; float t_min, t_max; } rt_direct_request; /* 16 bytes */
+typedef struct rt_direct { float r, g, b; uint32_t light; float lx, ly, lz; uint32_t status; } rt_direct;      /* 32 bytes */
+enum { RT_DIRECT_LIT = 0u, RT_DIRECT_OCCLUDED = 1u, RT_DIRECT_FACING_AWAY = 2u, RT_DIRECT_NO_LIGHTS = 3u, RT_DIRECT_SKIPPED = 4u };
+
+/* The number M of emitters of the scene. */
+RT_API int rt_scene_light_count(rt_scene* scene, uint32_t* n_lights);
+/* Host buffers, synchronous: hits (n) are read; rng_state (4 n u64) is read and written back; out (n) is required; active (n_active
+ * indices) and stats may be NULL.  Records that are not listed come back as they went in. */
+RT_API int rt_scene_direct(rt_scene* scene, const rt_direct_request* req, const rt_hit* hits, uint32_t n, uint64_t* rng_state,
+                           const uint32_t* active, uint32_t n_active, rt_direct* out, rt_tile_stats* stats);
+/* Device buffers (n rt_hit, 4 n u64, a u32 list and its u32 length or both NULL, n rt_direct), asynchronous on hip_stream (NULL = the
+ * scene's stream); counters and event times accumulate in the scene until rt_scene_collect(). */
+RT_API int rt_scene_direct_device(rt_scene* scene, const rt_direct_request* req, const void* d_hits, uint32_t n, void* d_rng_state,
+                                  const void* d_active, const void* d_n_active, void* d_out, void* hip_stream);
 
 /* ---- feature buffers (AOVs) of a strip: what the camera rays of the beauty image first hit ---- */
 /* Per-pixel feature buffers for a denoiser, edge-aware filters, picking and compositing, ALIGNED with the beauty image: they

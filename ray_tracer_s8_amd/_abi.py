@@ -140,6 +140,27 @@ RT_BOUNCE_MISSED = 2
 BOUNCE_DTYPE = np.dtype([("r", "<f4"), ("g", "<f4"), ("b", "<f4"), ("status", "<u4")])
 
 
+class DirectRequest(C.Structure):
+    """rt_direct_request: RT_FLAG_* of the shadow rays and their window [t_min, t_max)."""
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("t_min", C.c_float), ("t_max", C.c_float)]
+
+
+class Direct(C.Structure):
+    """rt_direct: one light sample of a hit — the estimate (without the surface albedo), the emitter's position in the world, the
+    point sampled on it and the RT_DIRECT_* status."""
+    _fields_ = [("r", C.c_float), ("g", C.c_float), ("b", C.c_float), ("light", C.c_uint32),
+                ("lx", C.c_float), ("ly", C.c_float), ("lz", C.c_float), ("status", C.c_uint32)]
+
+
+RT_DIRECT_LIT = 0
+RT_DIRECT_OCCLUDED = 1
+RT_DIRECT_FACING_AWAY = 2
+RT_DIRECT_NO_LIGHTS = 3
+RT_DIRECT_SKIPPED = 4
+# numpy twin of rt_direct (what Scene.direct returns)
+DIRECT_DTYPE = np.dtype([(n, "<u4" if n in ("light", "status") else "<f4") for n, _ in Direct._fields_])
+
+
 class AovPlanes(C.Structure):
     """rt_aov_planes: the feature buffers of a strip (host or device pointers); a NULL plane is not computed."""
     _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("hits", C.c_void_p),
@@ -190,6 +211,7 @@ assert C.sizeof(FrameStats) == 232
 assert C.sizeof(Ray) == C.sizeof(Hit) == RAY_DTYPE.itemsize == HIT_DTYPE.itemsize == 32
 assert C.sizeof(TraceRequest) == 24
 assert C.sizeof(BounceRequest) == 24 and C.sizeof(Bounce) == BOUNCE_DTYPE.itemsize == 16
+assert C.sizeof(DirectRequest) == 16 and C.sizeof(Direct) == DIRECT_DTYPE.itemsize == 32
 assert C.sizeof(AovPlanes) == 40
 assert C.sizeof(DenoiseRequest) == 40
 
@@ -328,6 +350,13 @@ def _bind(path: Path) -> C.CDLL:
     lib.rt_scene_bounce.restype = C.c_int
     lib.rt_scene_bounce_device.argtypes = [vp, C.POINTER(BounceRequest), vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.rt_scene_bounce_device.restype = C.c_int
+    lib.rt_scene_light_count.argtypes = [vp, C.POINTER(C.c_uint32)]
+    lib.rt_scene_light_count.restype = C.c_int
+    lib.rt_scene_direct.argtypes = [vp, C.POINTER(DirectRequest), C.POINTER(Hit), C.c_uint32, C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Direct), C.POINTER(TileStats)]
+    lib.rt_scene_direct.restype = C.c_int
+    lib.rt_scene_direct_device.argtypes = [vp, C.POINTER(DirectRequest), vp, C.c_uint32, vp, vp, vp, vp, vp]
+    lib.rt_scene_direct_device.restype = C.c_int
     lib.rt_scene_render_aov.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.c_uint32, C.POINTER(AovPlanes),
                                         C.POINTER(TileStats)]
     lib.rt_scene_render_aov.restype = C.c_int

@@ -31,6 +31,7 @@
 #include "rt_scene_host.h"
 #include "rt_trace.hip.h"
 #include "rt_bounce.hip.h"
+#include "rt_direct.hip.h"
 #include "rt_aov.hip.h"
 #include "rt_camera.hip.h"
 #include "rt_denoise.hip.h"
@@ -179,6 +180,8 @@ rtplan::Knobs plan_knobs() {
 struct rt_scene {
     DeviceCtx* ctx = nullptr;
     rtplan::SceneShape shape;       // what the engine rules read (rt_plan.h)
+    uint32_t n_lights = 0;          // direct lighting: the emitters of the scene (rt_scene_light_count)
+    uint32_t* d_lights = nullptr;   //   their primitive numbers in ascending world position (rtscene::emitter_list)
     rtplan::Pose pose;              // the job's placed camera (rt_scene_set_camera); read when a call is enqueued
     bool has_pose = false;          //   false: the reference camera
     float4* d_geom = nullptr;
@@ -222,8 +225,8 @@ struct rt_scene {
     // rt_scene_intersect; rays, RNG states, colours and segments of rt_scene_trace (80 bytes a ray); the planes of rt_scene_render_aov
     // (36 bytes a pixel); the filter's scratch and the strips' inputs and outputs of rt_scene_denoise; rays and RNG states of
     // rt_scene_camera_rays (64 bytes a record); rays, RNG states, bounces, hits and the two index lists of rt_scene_bounce (120 bytes
-    // a ray)
-    DevBuf d_out, d_outf, d_acc, d_cost, d_query, d_trace, d_aov, d_dn, d_cam, d_bounce;
+    // a ray); hits, RNG states, samples and the index list of rt_scene_direct (100 bytes a record)
+    DevBuf d_out, d_outf, d_acc, d_cost, d_query, d_trace, d_aov, d_dn, d_cam, d_bounce, d_direct;
     // HIP-event bookkeeping of launches not yet collected
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, free_ev;
     uint64_t primary_rays = 0;
@@ -733,6 +736,8 @@ static int upload_scene(int device, const HostScene& hs, rt_scene** out) {
     SC_UP(d_travq, bvh.travq);
     SC_UP(d_geom_r, hs.geom_r);
     SC_UP(d_big, hs.big);
+    SC_UP(d_lights, hs.lights);
+    sc->n_lights = hs.n_lights;
     sc->n_big = hs.n_big;
     sc->tri_k = hs.tri_k;
     sc->tri_diag = hs.tri_diag;
@@ -799,10 +804,11 @@ static int rt_scene_destroy_impl(rt_scene* sc) {
     }
     (void)hipFree(sc->d_geom_r);
     (void)hipFree(sc->d_big);
+    (void)hipFree(sc->d_lights);
     (void)hipFree(sc->d_leaf_of);
     (void)hipFree(sc->d_world_rank);
     (void)hipFree(sc->d_counters);
-    for (DevBuf* b : {&sc->d_out, &sc->d_outf, &sc->d_acc, &sc->d_cost, &sc->d_query, &sc->d_trace, &sc->d_aov, &sc->d_dn, &sc->d_cam, &sc->d_bounce}) b->release();
+    for (DevBuf* b : {&sc->d_out, &sc->d_outf, &sc->d_acc, &sc->d_cost, &sc->d_query, &sc->d_trace, &sc->d_aov, &sc->d_dn, &sc->d_cam, &sc->d_bounce, &sc->d_direct}) b->release();
     delete sc;
     g_live_scenes.fetch_sub(1);
     return RT_OK;
@@ -1291,6 +1297,110 @@ static int rt_scene_bounce_impl(rt_scene* sc, const rt_bounce_request* rq, rt_ra
             if (*n_next) HIPCHK(hipMemcpyAsync(next_active, d_next, (size_t)std::min(*n_next, n) * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
         }
     }
+    return call.finish(stats);
+}
+
+// ---- direct lighting of caller rays (rt_tile.h "direct lighting", rt_direct.hip.h) ------------------------------------------------
+static int check_direct(rt_scene* sc, const rt_direct_request* rq, const void* hits, uint32_t n, const void* state, const void* active,
+                        const void* n_active, const void* out) {
+    if (!sc) return fail(RT_ERR_BAD_ARG, "scene is NULL");
+    if (!rq) return fail(RT_ERR_BAD_ARG, "request is NULL");
+    if (!hits || !state || !out) return fail(RT_ERR_BAD_ARG, "hits, rng_state or out is NULL");
+    if (n == 0) return fail(RT_ERR_BAD_ARG, "n == 0");
+    if (rq->reserved != 0) return fail(RT_ERR_BAD_ARG, "reserved must be 0");
+    if ((active != nullptr) != (n_active != nullptr)) return fail(RT_ERR_BAD_ARG, "active and n_active: both or neither");
+    return RT_OK;
+}
+
+// Enqueue one launch on `stream` (caller holds sc->mu, device current): persistent waves over the `count` entries of the active list
+// (d_active == nullptr: records 0 .. count - 1), of which the kernel takes the first *d_n_active when that is given.
+static int launch_direct(rt_scene* sc, const rt_direct_request* rq, const void* d_hits, uint32_t n, void* d_state, const void* d_active,
+                         uint32_t count, const void* d_n_active, void* d_out, hipStream_t stream) {
+    const rtplan::DirectPlan dp = rtplan::plan_direct(sc->shape, sc->n_lights, rq->flags);
+    if (dp.too_many) return fail(RT_ERR_LIMIT, "more than 2^23 emitters");
+    const rtplan::QueryPlan& qp = dp.query;
+    const rtk::DirectFn kern = rtk::direct_kernel(qp.engine, qp.scan_mode);
+    if (!kern) return fail(RT_ERR_HIP, "no direct-lighting kernel for this plan");
+    rtk::DParams p;
+    std::memset(&p, 0, sizeof p);
+    p.hits = (const uint4*)d_hits;
+    p.rng_state = (uint64_t*)d_state;
+    p.active = (const uint32_t*)d_active;
+    p.n_active = (const uint32_t*)d_n_active;
+    p.out = (uint4*)d_out;
+    p.n = n;
+    p.count = count;
+    scene_refs(sc, qp.full_chain, p);
+    p.mat = sc->d_mat;
+    p.emis = sc->d_emis;
+    p.lights = sc->d_lights;
+    p.n_lights = sc->n_lights;
+    p.t_min = rq->t_min;
+    p.t_max = rq->t_max;
+    Grid g;
+    int rc = persistent_blocks(sc, kern, rtplan::QUERY_BLOCK, qp.lds, std::max<uint32_t>(count, 1u), g);
+    if (rc) return rc;
+    if (dbg(DBG_VERBOSE))
+        fprintf(stderr, "[rt] direct: engine %d  scan mode %d  lds %zu B  workgroups/CU %d  records %u  listed %s%u  lights %u\n", qp.engine,
+                qp.scan_mode, qp.lds, g.per_cu, n, d_n_active ? "<= " : "", count, sc->n_lights);
+    if ((rc = enqueue(sc, stream, kern, g.blocks, rtplan::QUERY_BLOCK, qp.lds, p))) return rc;
+    sc->last_engine = (uint32_t)qp.engine;
+    sc->last_form = 0;
+    return RT_OK;
+}
+
+static int rt_scene_light_count_impl(rt_scene* sc, uint32_t* n_lights) {
+    if (!sc || !n_lights) return fail(RT_ERR_BAD_ARG, "scene or n_lights is NULL");
+    *n_lights = sc->n_lights;
+    return RT_OK;
+}
+
+static int rt_scene_direct_device_impl(rt_scene* sc, const rt_direct_request* rq, const void* d_hits, uint32_t n, void* d_state,
+                                       const void* d_active, const void* d_n_active, void* d_out, void* hip_stream) {
+    int rc = check_direct(sc, rq, d_hits, n, d_state, d_active, d_n_active, d_out);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    HIPCHK(hipSetDevice(sc->ctx->dev));
+    return launch_direct(sc, rq, d_hits, n, d_state, d_active, n, d_n_active, d_out, hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream);
+}
+
+static int rt_scene_direct_impl(rt_scene* sc, const rt_direct_request* rq, const rt_hit* hits, uint32_t n, uint64_t* rng_state,
+                                const uint32_t* active, uint32_t n_active, rt_direct* out, rt_tile_stats* stats) {
+    // (the host form's n_active is a value: the both-or-neither rule is the device form's)
+    int rc = check_direct(sc, rq, hits, n, rng_state, nullptr, nullptr, out);
+    if (rc) return rc;
+    if (active) {
+        if (n_active > n) return fail(RT_ERR_BAD_ARG, "n_active > n");
+        for (uint32_t k = 0; k < n_active; k++)
+            if (active[k] >= n) return fail(RT_ERR_BAD_ARG, "active[" + std::to_string(k) + "] >= n");
+    } else if (n_active != 0) {
+        return fail(RT_ERR_BAD_ARG, "n_active without active");
+    }
+    const uint32_t count = active ? n_active : n;
+    std::lock_guard<std::mutex> dl(sc->ctx->mu);
+    std::lock_guard<std::mutex> lk(sc->mu);
+    HIPCHK(hipSetDevice(sc->ctx->dev));
+    // one device buffer: hits (32 B), states (32 B), samples (32 B) and the list (4 B) per record
+    const size_t hit_b = (size_t)n * sizeof(rt_hit), state_b = (size_t)n * 4 * sizeof(uint64_t), out_b = (size_t)n * sizeof(rt_direct),
+                 list_b = (size_t)n * sizeof(uint32_t);
+    if ((rc = sc->d_direct.reserve(hit_b + state_b + out_b + list_b, "direct-lighting buffers"))) return rc;
+    char* const d_hits = sc->d_direct.d;
+    char* const d_state = d_hits + hit_b;
+    char* const d_out = d_state + state_b;
+    char* const d_active = d_out + out_b;
+    StagedCall call(sc);
+    if ((rc = call.begin())) return rc;
+    HIPCHK(hipMemcpyAsync(d_hits, hits, hit_b, hipMemcpyHostToDevice, call.st));
+    HIPCHK(hipMemcpyAsync(d_state, rng_state, state_b, hipMemcpyHostToDevice, call.st));
+    if (active && count) HIPCHK(hipMemcpyAsync(d_active, active, (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
+    // records that are not listed come back as they went in: the caller's bytes are the staging's initial contents
+    if (active) HIPCHK(hipMemcpyAsync(d_out, out, out_b, hipMemcpyHostToDevice, call.st));
+    if ((rc = call.uploads_done()) ||
+        (rc = launch_direct(sc, rq, d_hits, n, d_state, active ? d_active : nullptr, count, nullptr, d_out, call.st)) ||
+        (rc = call.kernels_done()))
+        return rc;
+    HIPCHK(hipMemcpyAsync(rng_state, d_state, state_b, hipMemcpyDeviceToHost, call.st));
+    HIPCHK(hipMemcpyAsync(out, d_out, out_b, hipMemcpyDeviceToHost, call.st));
     return call.finish(stats);
 }
 
@@ -2376,6 +2486,19 @@ RT_API int rt_scene_trace(rt_scene* sc, const rt_trace_request* rq, const rt_ray
 RT_API int rt_scene_trace_device(rt_scene* sc, const rt_trace_request* rq, const void* d_rays, uint32_t n, void* d_rng_state,
                                  void* d_out_rgb, void* d_out_segments, void* hip_stream) {
     return guarded([&] { return rt_scene_trace_device_impl(sc, rq, d_rays, n, d_rng_state, d_out_rgb, d_out_segments, hip_stream); });
+}
+RT_API int rt_scene_light_count(rt_scene* sc, uint32_t* n_lights) {
+    return guarded([&] { return rt_scene_light_count_impl(sc, n_lights); });
+}
+RT_API int rt_scene_direct(rt_scene* sc, const rt_direct_request* rq, const rt_hit* hits, uint32_t n, uint64_t* rng_state, const uint32_t* active,
+                           uint32_t n_active, rt_direct* out, rt_tile_stats* stats) {
+    return guarded([&] { return rt_scene_direct_impl(sc, rq, hits, n, rng_state, active, n_active, out, stats); });
+}
+RT_API int rt_scene_direct_device(rt_scene* sc, const rt_direct_request* rq, const void* d_hits, uint32_t n, void* d_rng_state, const void* d_active,
+                                  const void* d_n_active, void* d_out, void* hip_stream) {
+    return guarded([&] {
+        return rt_scene_direct_device_impl(sc, rq, d_hits, n, d_rng_state, d_active, d_n_active, d_out, hip_stream);
+    });
 }
 RT_API int rt_scene_bounce(rt_scene* sc, const rt_bounce_request* rq, rt_ray* rays, uint32_t n, uint64_t* rng_state, const uint32_t* active,
                            uint32_t n_active, rt_bounce* out_bounce, rt_hit* out_hits, uint32_t* next_active, uint32_t* n_next,

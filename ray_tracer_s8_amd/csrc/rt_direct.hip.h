@@ -1,0 +1,115 @@
+// rt_direct.hip.h — gfx950 direct lighting of caller rays (rt_scene_direct*, rt_tile.h "direct lighting").
+//
+// One lane per ACTIVE hit record (the rt_hit a path step writes), one light sample per lane: an emitter picked uniformly from the
+// scene's emitter list with one u01 of the ray's own RNG state, a point on it (the UnitSphere draw of the shared path steps for a
+// sphere light, two u01 for a triangle light), the two cosines, the shadow ray through the shared closest_hit, and the Lambertian
+// estimate without the surface albedo.  The arithmetic of the pick, the point, the cosines and the weight is rt_direct_math.h, which the
+// CPU harness runs too; the draws, the normal of a triangle light and the closest hit are the steps of rt_path_steps.hip.h, so the
+// shadow ray's hit is rt_scene_intersect's bit for bit.
+//
+// Persistent waves stride over the active list (or over all n records) exactly as rt_bounce_kernel does; the device form reads the
+// list's length from device memory.  Lanes whose sample faces away trace nothing: the walk runs under one branch that the lanes with
+// a shadow ray enter together.  Nothing is read or written through an index >= n.
+//
+// LDS per lane (rtplan::plan_query): the walk's stack, (bvh depth + 1) u32 entries (engine 2); entry e of lane tid at [e * 256 + tid].
+// No per-scene scratch: launches on different streams may overlap.
+#pragma once
+#include "rt_direct_math.h"
+#include "rt_path_steps.hip.h"
+
+namespace rtk {
+
+struct DParams : SceneRefs {
+    const uint4* hits;           // [2 n]: rt_hit (P, distance) (normal, index), as bits
+    uint64_t* rng_state;         // [4 n] xoshiro256++ state per ray: read, and written back by a record that drew
+    const uint32_t* active;      // [count] record indices < n, or nullptr: records 0 .. count - 1
+    const uint32_t* n_active;    // device word that holds the list's length (the call takes min(count, *n_active)), or nullptr
+    uint4* out;                  // [2 n]: rt_direct (r, g, b, light) (lx, ly, lz, status), as bits
+    uint64_t n;                  // records in the batch: every index is below it
+    uint64_t count;              // upper bound of the entries taken (the grid is sized from it)
+    const float4* mat;           // [n_sph + n_tri] (albedo r, g, b, roughness)
+    const float* emis;           // [n_sph + n_tri]
+    const uint32_t* lights;      // [n_lights] the emitters (library primitive numbers) in ascending world position
+    uint32_t n_lights;           // M <= rtdl::MAX_LIGHTS
+    float t_min, t_max;          // the shadow rays' window
+};
+
+__device__ __forceinline__ rtdl::Vec dvec(V3 a) { return rtdl::Vec{a.x, a.y, a.z}; }
+__device__ __forceinline__ V3 v3of(rtdl::Vec a) { return mk(a.x, a.y, a.z); }
+
+// ENGINE 2: the walk; 1: the scan with consider<MODE> (MODE 0 plain linear semantics, 2 BVH semantics).
+template <int ENGINE, int MODE>
+__global__ __launch_bounds__(256) void rt_direct_kernel(const DParams p) {
+    extern __shared__ uint32_t dstack[];                 // [depth + 1][256] (engine 2)
+    const uint32_t tid = threadIdx.x;
+    uint64_t m = p.count;
+    if (p.n_active) {
+        const uint64_t listed = *p.n_active;
+        m = listed < m ? listed : m;
+    }
+    unsigned long long n_rays = 0, n_tests = 0;
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + tid; k < m; k += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t i = p.active ? (uint64_t)p.active[k] : k;
+        if (i >= p.n) continue;                                                        // (an index beyond the batch touches nothing)
+        const uint4 h0 = p.hits[2 * i], h1 = p.hits[2 * i + 1];
+        if (h1.w == RT_HIT_NONE || p.n_lights == 0) {                                  // no draw, the state unchanged
+            p.out[2 * i] = make_uint4(0u, 0u, 0u, RT_HIT_NONE);
+            p.out[2 * i + 1] = make_uint4(0u, 0u, 0u, h1.w == RT_HIT_NONE ? RT_DIRECT_SKIPPED : RT_DIRECT_NO_LIGHTS);
+            continue;
+        }
+        const V3 P = mk(__uint_as_float(h0.x), __uint_as_float(h0.y), __uint_as_float(h0.z));
+        const V3 n = mk(__uint_as_float(h1.x), __uint_as_float(h1.y), __uint_as_float(h1.z));
+        // ================= the draws: the emitter, then the point on it =================
+        Rng rng;
+        load_rng(p.rng_state + 4 * i, rng);
+        const uint32_t pick = rtdl::pick_light(u01(rng), p.n_lights);
+        const uint32_t prim = p.lights[pick];
+        const bool sphere = prim < p.n_sph;
+        rtdl::Vec L, nl;
+        float size;                                                                    // the radius, or the triangle's area
+        if (sphere) {
+            const float4 g = at32(p.geom_r, prim);
+            float x1, x2, sm;
+            unit_sphere_pair(rng, x1, x2, sm);                                         // UnitSphere, as a scattering hit draws it
+            const float factor = 2.0f * RT_SQRT(1.0f - sm);
+            nl = rtdl::Vec{x1 * factor, x2 * factor, 1.0f - 2.0f * sm};
+            L = rtdl::sphere_point(rtdl::Vec{g.x, g.y, g.z}, g.w, nl);
+            size = g.w;
+        } else {
+            const float* tv = p.tri + 9 * (size_t)(prim - p.n_sph);
+            const rtdl::Vec A{tv[0], tv[1], tv[2]}, B{tv[3], tv[4], tv[5]}, C{tv[6], tv[7], tv[8]};
+            float u1 = u01(rng), u2 = u01(rng);
+            rtdl::fold_pair(u1, u2);
+            L = rtdl::triangle_point(A, B, C, u1, u2);
+            nl = dvec(hit_normal(p, prim, mk(0.f, 0.f, 0.f)));                         // (a triangle's normal does not read the point)
+            size = rtdl::triangle_area(A, B, C);
+        }
+        store_rng(p.rng_state + 4 * i, rng);
+        // ================= the cosines; the shadow ray Ray::new(P, L - P) =================
+        const rtdl::Geometry g = rtdl::light_geometry(dvec(P), dvec(n), L, nl, sphere);
+        uint32_t status = RT_DIRECT_FACING_AWAY;
+        rtdl::Vec rgb{0.0f, 0.0f, 0.0f};
+        if (g.facing) {
+            const V3 d = v3of(g.w);                                                    // v / |v|: Ray::new's division (ray.rs:134)
+            const RayAux aux = ray_aux(d, p.full_chain != 0);
+            n_rays++;
+            const Hit h = closest_hit<ENGINE, MODE, false>(p, P, d, p.t_min, p.t_max, aux, dstack, tid, 256u, n_tests);
+            status = RT_DIRECT_OCCLUDED;
+            if (h.idx == (int)prim) {
+                status = RT_DIRECT_LIT;
+                const float4 ma = at32(p.mat, prim);
+                const float W = sphere ? rtdl::sphere_weight(g.cs, g.cl, size, p.n_lights, g.d2)
+                                       : rtdl::triangle_weight(g.cs, g.cl, size, p.n_lights, g.d2);
+                rgb = rtdl::radiance(rtdl::Vec{ma.x, ma.y, ma.z}, at32(p.emis, prim), W);
+            }
+        }
+        p.out[2 * i] = make_uint4(__float_as_uint(rgb.x), __float_as_uint(rgb.y), __float_as_uint(rgb.z), world_position(p, prim));
+        p.out[2 * i + 1] = make_uint4(__float_as_uint(L.x), __float_as_uint(L.y), __float_as_uint(L.z), status);
+    }
+    flush_counters(p.counters, n_rays, n_tests, tid);
+}
+
+using DirectFn = void (*)(const DParams);
+DirectFn direct_kernel(int engine, int scan_mode);    // rt_kernels_direct.hip; nullptr for a combination that does not exist
+
+}  // namespace rtk

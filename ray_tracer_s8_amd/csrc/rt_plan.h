@@ -510,6 +510,23 @@ inline QueryPlan plan_query(const SceneShape& sh, uint32_t flags) {
     return q;
 }
 
+// ---- Direct lighting of caller rays (rt_scene_direct*, rt_direct.hip.h).  One lane per active hit record; the shadow
+// ray takes the query path's engine, so the plan is the query plan plus the one limit of the emitter pick: M up to 2^23, where
+// every (float)M is exact and u * (float)M truncates to at most M.
+constexpr uint32_t DIRECT_MAX_LIGHTS = 1u << 23;
+
+struct DirectPlan {
+    QueryPlan query;          // engine, scan mode, slab test and LDS of the shadow rays
+    bool too_many = false;    // n_lights > DIRECT_MAX_LIGHTS: RT_ERR_LIMIT, nothing launched
+};
+
+inline DirectPlan plan_direct(const SceneShape& sh, uint32_t n_lights, uint32_t flags) {
+    DirectPlan d;
+    d.query = plan_query(sh, flags);
+    d.too_many = n_lights > DIRECT_MAX_LIGHTS;
+    return d;
+}
+
 // ---- Path tracing of caller rays (rt_scene_trace*, rt_trace.hip.h).  One lane per caller ray, its samples and bounces
 // in a loop: the engine is the query path's, the plan adds the path stack and the workgroup size.
 constexpr uint32_t TRACE_LDS_CU = 160 * 1024;   // LDS of one CU: the trace kernels have no static LDS

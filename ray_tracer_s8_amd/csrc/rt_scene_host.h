@@ -36,6 +36,8 @@ struct HostScene {
     float tri_k = 0.f, tri_diag = 0.f, tri_es = 0.f, tri_e = 0.f;
     std::vector<uint32_t> world_rank;   // the caller's world_index (one dummy entry when none came)
     bool has_order = false;
+    std::vector<uint32_t> lights;       // direct lighting: the emitters, in ascending world position (one dummy entry when none)
+    uint32_t n_lights = 0;
 };
 
 // positions in RenderInfo.world: every one of 0 .. n - 1 exactly once
@@ -397,6 +399,22 @@ inline void triangle_cull_rule(const rt_triangle* tr, uint32_t ns, uint32_t nt, 
     sh.tri_ok = ok;
 }
 
+// The emitter list of direct lighting (rt_scene_direct*, rt_tile.h): the library's numbers of the primitives with emission > 0 (a NaN
+// emits nothing, as `em > 0` in ray_color), in ascending world position — the order of the caller's world, whatever the storage
+// order — so that pick k names the same light for every storage order.  Reads hs.emis and hs.world_rank (pack_records and
+// build_host_scene before it); no launch but rt_direct_kernel reads the list.
+inline void emitter_list(HostScene& hs) {
+    const uint32_t np = hs.shape.n_sph + hs.shape.n_tri;
+    std::vector<uint32_t>& lights = hs.lights;
+    lights.clear();
+    for (uint32_t i = 0; i < np; i++)
+        if (hs.emis[i] > 0.0f) lights.push_back(i);
+    if (hs.has_order)
+        std::sort(lights.begin(), lights.end(), [&](uint32_t x, uint32_t y) { return hs.world_rank[x] < hs.world_rank[y]; });
+    hs.n_lights = (uint32_t)lights.size();
+    if (lights.empty()) lights.push_back(0);
+}
+
 // reorder: false keeps the primitive records in the caller's order (A/B)
 inline void build_host_scene(const rt_sphere* sp, uint32_t ns, const rt_triangle* tr, uint32_t nt, const uint32_t* world_index,
                              bool reorder, HostScene& hs) {
@@ -423,6 +441,7 @@ inline void build_host_scene(const rt_sphere* sp, uint32_t ns, const rt_triangle
     if (hs.has_order) hs.world_rank.assign(wi_store.begin(), wi_store.begin() + np);
     else hs.world_rank.assign(1, 0u);
     pack_records(sp, ns, tr, nt, boxes, hs);
+    emitter_list(hs);
     expanded_records(sp, ns, hs);
     sh.quant_ok = quant_rule(boxes, bvh.grid);
     sh.leaf_density = leaf_density(boxes);

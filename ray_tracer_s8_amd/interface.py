@@ -371,6 +371,49 @@ class Scene:
                                                     vp(d_bounce), vp(d_hits), vp(d_next_active), vp(d_n_next), vp(stream)),
                    "rt_scene_bounce_device")
 
+    @property
+    def n_lights(self) -> int:
+        """The number M of emitters of the scene (rt_scene_light_count): the primitives with emission > 0."""
+        m = C.c_uint32(0)
+        _abi.check(self._lib.rt_scene_light_count(self._h, C.byref(m)), "rt_scene_light_count")
+        return m.value
+
+    def direct(self, hits, rng_state, active=None, t_min: float = 0.001, t_max: float = 1000.0, flags: int = 0):
+        """Direct lighting of caller rays (rt_scene_direct): one light sample for each active hit record — an emitter picked with one
+        u01 of the ray's state, a point on it, the shadow ray within [t_min, t_max) and the Lambertian estimate without the surface
+        albedo.  hits: (N,) HIT_DTYPE, as a path step returns them; rng_state: (N, 4) uint64; active: None (all N) or record
+        indices.  The inputs are not modified.  Returns a dict: `direct` (DIRECT_DTYPE; entries of records that are not active are
+        zero), `states` (the advanced states written over a copy of the input) and `stats`."""
+        h = np.array(hits, _abi.HIT_DTYPE, order="C")
+        if h.ndim != 1:
+            raise ValueError(f"hits: need a 1-d array of HIT_DTYPE records, got shape {h.shape}")
+        n = len(h)
+        if rng_state is None:
+            raise ValueError("rng_state: need (N, 4) uint64 states")
+        state = np.array(rng_state, np.uint64, order="C")
+        if state.shape != (n, 4):
+            raise ValueError(f"rng_state: need an (N, 4) uint64 array, got {state.shape}")
+        act = None if active is None else np.ascontiguousarray(active, np.uint32).reshape(-1)
+        rq = _abi.DirectRequest(flags, 0, t_min, t_max)
+        out = np.zeros(n, _abi.DIRECT_DTYPE)
+        st = TileStats()
+        # (an empty list is still a list: ctypes gets a non-NULL pointer to an array of one)
+        act_arg = None if act is None else (act if len(act) else np.zeros(1, np.uint32)).ctypes.data_as(C.POINTER(C.c_uint32))
+        _abi.check(self._lib.rt_scene_direct(self._h, C.byref(rq), h.ctypes.data_as(C.POINTER(_abi.Hit)), n,
+                                             state.ctypes.data_as(C.POINTER(C.c_uint64)), act_arg, 0 if act is None else len(act),
+                                             out.ctypes.data_as(C.POINTER(_abi.Direct)), C.byref(st)), "rt_scene_direct")
+        return {"direct": out, "states": state, "stats": st}
+
+    def direct_device(self, d_hits: int, n: int, d_rng_state: int, d_out: int, *, d_active: int = 0, d_n_active: int = 0,
+                      t_min: float = 0.001, t_max: float = 1000.0, flags: int = 0, stream: int = 0):
+        """Direct lighting on device buffers (rt_scene_direct_device): n rt_hit at d_hits, 4 n uint64 states at d_rng_state (updated in
+        place), n rt_direct to d_out; optionally the active list d_active with its uint32 length at d_n_active (read on the device:
+        the d_next_active / d_n_next of a bounce step as they stand); asynchronous on `stream`, counters until collect()."""
+        rq = _abi.DirectRequest(flags, 0, t_min, t_max)
+        vp = lambda ptr: C.c_void_p(ptr) if ptr else None
+        _abi.check(self._lib.rt_scene_direct_device(self._h, C.byref(rq), vp(d_hits), n, vp(d_rng_state), vp(d_active), vp(d_n_active),
+                                                    vp(d_out), vp(stream)), "rt_scene_direct_device")
+
     def render_aov(self, req: TileRequest, begin: int = 0, end: Optional[int] = None, *,
                    planes: Sequence[str] = _abi.AOV_PLANES, out: Optional[dict] = None):
         """Feature buffers of a strip (rt_scene_render_aov): over samples [begin, end) of the req.spp-sample job (end None:

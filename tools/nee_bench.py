@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""Direct lighting of caller rays (rt_scene_direct): what one light sample per hit costs next to the path step it follows, and what
+it buys, on the camera rays of a benchmark scene (default c2, cornell16).
+
+  timing    the first path step of all camera rays alone (rt_scene_bounce), and the same step followed by rt_scene_direct on the
+            rays that scattered: HIP-event time of the kernels (rt_tile_stats.kernel_ms), best and median of --runs after --warmup
+            warm-ups;
+  variance  K steps with a light sample after each but the last (the fold of examples/nee_rays.c) against rt_scene_trace with
+            max_bounces = K - 1 on the same rays, one sample per ray each: the mean and the variance of the samples' luminance and
+            the variance ratio at that equal sample count, over all samples and within the pixels' own samples.  (The means agree
+            only where every hit has roughness 0: rt_tile.h.)
+
+    python tools/nee_bench.py [--config c2] [--width 480 --height 270 --spp 4] [--steps 4]
+Prints one JSON line."""
+import argparse
+import json
+import statistics
+import sys
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+import ray_tracer_s8_amd as rt  # noqa: E402
+from ray_tracer_s8_amd import _abi, scenes  # noqa: E402
+
+SCATTERED, EMITTED, MISSED = _abi.RT_BOUNCE_SCATTERED, _abi.RT_BOUNCE_EMITTED, _abi.RT_BOUNCE_MISSED
+
+
+def _rgb(a):
+    return np.stack([a["r"], a["g"], a["b"]], 1).astype(np.float64)
+
+
+def _states(n, seed):
+    g = np.random.default_rng(seed)
+    return g.integers(0, 1 << 63, size=(n, 4), dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+
+
+def nee(sc, rays, states, K):
+    """K steps, a light sample after each but the last; returns the colour per ray and the kernel time of steps and samples."""
+    n = len(rays)
+    T, col = np.ones((n, 3)), np.zeros((n, 3))
+    act, ms_step, ms_direct = None, 0.0, 0.0
+    for k in range(K):
+        s = sc.bounce(rays, states, active=act, as_given=True, want_hits=True, want_next=True)
+        rays, states, ms_step = s["rays"], s["states"], ms_step + s["stats"].kernel_ms
+        idx = np.arange(n) if act is None else act.astype(np.int64)
+        status, rgb = s["bounce"]["status"][idx], _rgb(s["bounce"])[idx]
+        own = (status == MISSED) | ((status == EMITTED) & (k == 0))
+        col[idx[own]] += T[idx[own]] * rgb[own]
+        nxt = s["next"]
+        T[nxt] *= _rgb(s["bounce"])[nxt]
+        if k < K - 1 and len(nxt):
+            d = sc.direct(s["hits"], states, active=nxt)
+            states, ms_direct = d["states"], ms_direct + d["stats"].kernel_ms
+            col[nxt] += T[nxt] * _rgb(d["direct"])[nxt]
+        act = nxt
+        if not len(act):
+            break
+    return col, ms_step, ms_direct
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--config", default="c2")
+    ap.add_argument("--width", type=int, default=480)
+    ap.add_argument("--height", type=int, default=270)
+    ap.add_argument("--spp", type=int, default=4)
+    ap.add_argument("--steps", type=int, default=4)
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    a = ap.parse_args()
+    rt.init()
+    sph, rq = scenes.config(a.config)
+    rq.width, rq.height, rq.divisions, rq.division_no, rq.spp = a.width, a.height, 1, 0, a.spp
+    with rt.Scene(0, rt.World(sph)) as sc:
+        rays, states, _ = sc.camera_rays(rq)
+        n = len(rays)
+        t_step, t_direct = [], []
+        for i in range(a.warmup + a.runs):
+            s = sc.bounce(rays, states, as_given=True, want_hits=True, want_next=True)
+            d = sc.direct(s["hits"], s["states"], active=s["next"])
+            if i >= a.warmup:
+                t_step.append(s["stats"].kernel_ms)
+                t_direct.append(d["stats"].kernel_ms)
+        both = [x + y for x, y in zip(t_step, t_direct)]
+        col, ms_step, ms_direct = nee(sc, rays, _states(n, 1), a.steps)
+        o = np.stack([rays["ox"], rays["oy"], rays["oz"]], 1)
+        dd = np.stack([rays["dx"], rays["dy"], rays["dz"]], 1)
+        ref = sc.trace(o, dd, rays["t_min"], rays["t_max"], spp=1, max_bounces=a.steps - 1, rng_state=_states(n, 2), as_given=True)
+        la, lb = ref[0].astype(np.float64).mean(1), col.mean(1)
+        # the variance within a pixel's spp samples (records (row W + x) spp + s), averaged: the noise without the image's own variance
+        wa, wb = (float(x.reshape(-1, a.spp).var(1, ddof=1).mean()) if a.spp > 1 else float("nan") for x in (la, lb))
+        out = {
+            "config": a.config, "rays": n, "lights": sc.n_lights, "scattered": int(len(s["next"])), "shadow_rays": int(d["stats"].ray_segments),
+            "step_ms": {"best": min(t_step), "median": statistics.median(t_step)},
+            "direct_ms": {"best": min(t_direct), "median": statistics.median(t_direct)},
+            "step_plus_direct_ms": {"best": min(both), "median": statistics.median(both)},
+            "steps": a.steps, "nee_kernel_ms": {"steps": ms_step, "direct": ms_direct}, "trace_kernel_ms": ref[2].kernel_ms,
+            "trace": {"mean": float(la.mean()), "variance": float(la.var(ddof=1))},
+            "nee": {"mean": float(lb.mean()), "variance": float(lb.var(ddof=1))},
+            "variance_ratio": float(la.var(ddof=1) / lb.var(ddof=1)),
+            "within_pixel_variance": {"trace": wa, "nee": wb, "ratio": wa / wb},
+        }
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
