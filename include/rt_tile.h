@@ -52,7 +52,9 @@ extern "C" {
                                   (4, additions only: the edge-avoiding a-trous denoiser rt_scene_denoise /
                                      rt_scene_denoise_device with rt_denoise_request, RT_DENOISE_MAX_ITERATIONS)
                                   (4, additions only: direct lighting of caller rays rt_scene_light_count / rt_scene_direct /
-                                     rt_scene_direct_device with rt_direct_request, rt_direct, RT_DIRECT_*) */
+                                     rt_scene_direct_device with rt_direct_request, rt_direct, RT_DIRECT_*)
+                                  (4, additions only: next-event estimation for caller rays rt_scene_trace_nee /
+                                     rt_scene_trace_nee_device with rt_nee_request, RT_NEE_*) */
 
 /* ---- status codes --------------------------------------------------------------- */
 typedef enum rt_status {
@@ -544,6 +546,72 @@ RT_API int rt_scene_direct(rt_scene* scene, const rt_direct_request* req, const 
  * scene's stream); counters and event times accumulate in the scene until rt_scene_collect(). */
 RT_API int rt_scene_direct_device(rt_scene* scene, const rt_direct_request* req, const void* d_hits, uint32_t n, void* d_rng_state,
                                   const void* d_active, const void* d_n_active, void* d_out, void* hip_stream);
+
+/* ---- next-event estimation: the integrator of the path steps and the light samples, in one kernel -------- */
+/* The integrator a caller composes from rt_scene_bounce* and rt_scene_direct* — a path of at most K = max_bounces + 1 segments with one
+ * light sample after every hit but the last — as ONE launch, one lane per ray, nothing written to memory between the steps.  It also
+ * carries the two rules the composed recipe cannot: it knows each hit's roughness, and in RT_NEE_MIS it combines the light sample and
+ * the bounce by the balance heuristic.  Every operation below is one IEEE f32 rounding in the order written (no fused multiply-add,
+ * correctly rounded division and sqrt); products and sums of colours are per channel.
+ *
+ *   - RNG and sums, as rt_scene_trace: rng_state == NULL: sample s of ray i draws from SmallRng::seed_from_u64(seed +
+ *     4 * 0x9E3779B97F4A7C15 * (i * spp + s)); otherwise rng_state holds the xoshiro256++ state of each ray, read and written back, its
+ *     spp samples drawing one after the other.  out_rgb (3 * n floats) is the f32 sum of the ray's sample colours c, added in the
+ *     order s = 0, 1, ... starting from 0.
+ *   - One sample: T = (1, 1, 1), c = (0, 0, 0), sampled = false.  For k = 0 .. max_bounces one path step exactly as rt_scene_bounce
+ *     specifies it: the closest hit under `flags` in the ray's own window [t_min, t_max); ray_form applies to k = 0, every later
+ *     segment is RT_TRACE_RAY_AS_GIVEN; the same UnitSphere draw and scattered ray.
+ *       RT_BOUNCE_MISSED:     c = c + T * sky (one multiplication, then one addition).  The sample ends.
+ *       RT_BOUNCE_SCATTERED   at primitive j (albedo a, roughness rho, point P and normal n as rt_hit reports them): T = T * a.  If
+ *                             k == max_bounces the sample ends: the scatter draw has been taken, as the reference takes it, and no
+ *                             light sample is.  Otherwise sampled = (rho == 0 && M > 0), M = rt_scene_light_count().  If sampled: one
+ *                             light sample exactly as rt_scene_direct specifies it for the record (P, n, j), from the state as the step
+ *                             left it, with the ray's own window and the request's flags; when a shadow ray is traced it is counted
+ *                             in out_shadow; when the sample is RT_DIRECT_LIT with estimate D and weight W,
+ *                               RT_NEE_LIGHT_ONLY:  c = c + T * D;
+ *                               RT_NEE_MIS:         wl = 1.0f / (1.0f + W);  c = c + T * (D * wl);
+ *                             and no addition for any other status.  If not sampled, no draw is taken.  n is kept for the next step.
+ *       RT_BOUNCE_EMITTED     at emitter j, e = albedo * emission.  If k == 0 or !sampled: c = c + T * e.  Otherwise the light
+ *                             strategy's view of this hit point, from the previous hit's normal n, the segment's unit direction d, this
+ *                             hit's rt_hit normal nh and its rt_hit.distance: cs' = n.d; cl' = -(nh.d) for a sphere, |nh.d| for a
+ *                             triangle; d2' = distance * distance; W' = the W of rt_scene_direct for (cs', cl', the radius or area of
+ *                             j, M, d2').  The point is SAMPLABLE when cs' > 0 and cl' > 0 and d2' > 0 and d2' is finite.
+ *                               not samplable (an emissive sphere hit from inside):  c = c + T * e;
+ *                               samplable, RT_NEE_LIGHT_ONLY:  nothing is added (the light sample of the step before stood for it);
+ *                               samplable, RT_NEE_MIS:         wb = 1.0f - 1.0f / (1.0f + W');  c = c + T * (e * wb).
+ *                             The sample ends.
+ *     W is (cs / pi) / p_light = p_bsdf / p_light, so wl and wb are the balance heuristic's weights, and the area estimator's unbounded
+ *     cs * cl / d2 becomes Le * W / (1 + W) <= Le.
+ *   - RT_NEE_LIGHT_ONLY is, bit for bit, the fold above over rt_scene_bounce and rt_scene_direct called per step.
+ *   - out_segments (n u32, optional): the ray's path segments, summed over its samples; with M == 0 they and the written-back states
+ *     are rt_scene_trace's for the same arguments.  out_shadow (n u32, optional): its shadow rays.
+ *   - flags: as for rt_scene_intersect (a tree deeper than the walk's stack takes the scan; tile-only flags are ignored).
+ *   - RT_ERR_BAD_ARG, and nothing launched: a NULL scene, request, rays or out_rgb; n == 0; spp == 0; ray_form > 1; mode > 1;
+ *     reserved != 0.  RT_ERR_LIMIT: spp > RT_MAX_SPP, max_bounces > RT_MAX_BOUNCES, M > 2^23.
+ *   - Counters (rt_tile_stats): primary_rays = n * spp; ray_segments = path segments + shadow rays; broad_candidates = exact root
+ *     tests; kernel_ms; h2d_ms (rays and states) and d2h_ms (colours, counts, states) of the host form; n_launches = 1; engine (as for
+ *     rt_scene_intersect).
+ *   - Limits: a hit with roughness > 0 takes no light sample (it falls back to the bounce, which is unbiased); the emitter is picked
+ *     uniformly, not by power.
+ * No per-scene scratch on the device: launches on different streams may overlap.   */
+typedef struct rt_nee_request {
+    uint32_t spp;               /* samples per ray, 1 .. RT_MAX_SPP                                        */
+    uint32_t max_bounces;       /* 0 .. RT_MAX_BOUNCES; at most max_bounces + 1 path segments, as rt_scene_trace */
+    uint64_t seed;              /* the seeded streams, when no RNG states are passed                       */
+    uint32_t flags;             /* RT_FLAG_*, as for rt_scene_intersect                                    */
+    uint32_t ray_form;          /* RT_TRACE_RAY_NEW | RT_TRACE_RAY_AS_GIVEN (the first segment only)       */
+    uint32_t mode;              /* RT_NEE_LIGHT_ONLY | RT_NEE_MIS                                          */
+    uint32_t reserved;          /* 0                                                                       */
+} rt_nee_request;               /* 32 bytes */
+enum { RT_NEE_LIGHT_ONLY = 0u, RT_NEE_MIS = 1u };
+
+/* Host buffers, synchronous; rng_state, out_segments, out_shadow and stats may be NULL. */
+RT_API int rt_scene_trace_nee(rt_scene* scene, const rt_nee_request* req, const rt_ray* rays, uint32_t n, uint64_t* rng_state,
+                              float* out_rgb, uint32_t* out_segments, uint32_t* out_shadow, rt_tile_stats* stats);
+/* Device buffers (n rt_ray, 4 n u64 or NULL, 3 n f32, n u32 or NULL, n u32 or NULL), asynchronous on hip_stream (NULL = the scene's
+ * stream); counters and event times accumulate in the scene until rt_scene_collect(). */
+RT_API int rt_scene_trace_nee_device(rt_scene* scene, const rt_nee_request* req, const void* d_rays, uint32_t n, void* d_rng_state,
+                                     void* d_out_rgb, void* d_out_segments, void* d_out_shadow, void* hip_stream);
 
 /* ---- feature buffers (AOVs) of a strip: what the camera rays of the beauty image first hit ---- */
 /* Per-pixel feature buffers for a denoiser, edge-aware filters, picking and compositing, ALIGNED with the beauty image: they

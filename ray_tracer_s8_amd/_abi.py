@@ -161,6 +161,16 @@ RT_DIRECT_SKIPPED = 4
 DIRECT_DTYPE = np.dtype([(n, "<u4" if n in ("light", "status") else "<f4") for n, _ in Direct._fields_])
 
 
+class NeeRequest(C.Structure):
+    """rt_nee_request: rt_trace_request's fields, then the RT_NEE_* mode of the integrator."""
+    _fields_ = [("spp", C.c_uint32), ("max_bounces", C.c_uint32), ("seed", C.c_uint64), ("flags", C.c_uint32),
+                ("ray_form", C.c_uint32), ("mode", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+RT_NEE_LIGHT_ONLY = 0
+RT_NEE_MIS = 1
+
+
 class AovPlanes(C.Structure):
     """rt_aov_planes: the feature buffers of a strip (host or device pointers); a NULL plane is not computed."""
     _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("hits", C.c_void_p),
@@ -212,6 +222,7 @@ assert C.sizeof(Ray) == C.sizeof(Hit) == RAY_DTYPE.itemsize == HIT_DTYPE.itemsiz
 assert C.sizeof(TraceRequest) == 24
 assert C.sizeof(BounceRequest) == 24 and C.sizeof(Bounce) == BOUNCE_DTYPE.itemsize == 16
 assert C.sizeof(DirectRequest) == 16 and C.sizeof(Direct) == DIRECT_DTYPE.itemsize == 32
+assert C.sizeof(NeeRequest) == 32
 assert C.sizeof(AovPlanes) == 40
 assert C.sizeof(DenoiseRequest) == 40
 
@@ -357,6 +368,11 @@ def _bind(path: Path) -> C.CDLL:
     lib.rt_scene_direct.restype = C.c_int
     lib.rt_scene_direct_device.argtypes = [vp, C.POINTER(DirectRequest), vp, C.c_uint32, vp, vp, vp, vp, vp]
     lib.rt_scene_direct_device.restype = C.c_int
+    lib.rt_scene_trace_nee.argtypes = [vp, C.POINTER(NeeRequest), C.POINTER(Ray), C.c_uint32, C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(TileStats)]
+    lib.rt_scene_trace_nee.restype = C.c_int
+    lib.rt_scene_trace_nee_device.argtypes = [vp, C.POINTER(NeeRequest), vp, C.c_uint32, vp, vp, vp, vp, vp]
+    lib.rt_scene_trace_nee_device.restype = C.c_int
     lib.rt_scene_render_aov.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.c_uint32, C.POINTER(AovPlanes),
                                         C.POINTER(TileStats)]
     lib.rt_scene_render_aov.restype = C.c_int

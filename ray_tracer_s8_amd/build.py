@@ -38,7 +38,7 @@ HIPCC_FLAGS = [
 
 # translation units and the flags each one adds: the host side, the linear-scan kernels, the traversal kernels
 # (SLP-vectorised packed FP32 pairs: linear kernels +3 %, traversal kernels -1.5 %, tools/variants_all.sh), the ray-query kernels,
-# the kernels that path-trace caller rays, the kernels of their single path steps, the kernels of their direct lighting, the kernels of the feature buffers, the kernels of the denoiser, the camera-ray kernel
+# the kernels that path-trace caller rays, the kernels of their single path steps, the kernels of their direct lighting, the kernel of their next-event-estimation integrator, the kernels of the feature buffers, the kernels of the denoiser, the camera-ray kernel
 UNITS = [
     ("rt_api.hip", []),
     ("rt_kernels_lin.hip", []),
@@ -47,6 +47,7 @@ UNITS = [
     ("rt_kernels_trace.hip", ["-fno-slp-vectorize"]),
     ("rt_kernels_bounce.hip", ["-fno-slp-vectorize"]),
     ("rt_kernels_direct.hip", ["-fno-slp-vectorize"]),
+    ("rt_kernels_nee.hip", ["-fno-slp-vectorize"]),
     ("rt_kernels_aov.hip", ["-fno-slp-vectorize"]),
     ("rt_kernels_denoise.hip", ["-fno-slp-vectorize"]),
     ("rt_kernels_camera.hip", ["-fno-slp-vectorize"]),

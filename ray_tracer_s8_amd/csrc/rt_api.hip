@@ -32,6 +32,7 @@
 #include "rt_trace.hip.h"
 #include "rt_bounce.hip.h"
 #include "rt_direct.hip.h"
+#include "rt_nee.hip.h"
 #include "rt_aov.hip.h"
 #include "rt_camera.hip.h"
 #include "rt_denoise.hip.h"
@@ -225,8 +226,9 @@ struct rt_scene {
     // rt_scene_intersect; rays, RNG states, colours and segments of rt_scene_trace (80 bytes a ray); the planes of rt_scene_render_aov
     // (36 bytes a pixel); the filter's scratch and the strips' inputs and outputs of rt_scene_denoise; rays and RNG states of
     // rt_scene_camera_rays (64 bytes a record); rays, RNG states, bounces, hits and the two index lists of rt_scene_bounce (120 bytes
-    // a ray); hits, RNG states, samples and the index list of rt_scene_direct (100 bytes a record)
-    DevBuf d_out, d_outf, d_acc, d_cost, d_query, d_trace, d_aov, d_dn, d_cam, d_bounce, d_direct;
+    // a ray); hits, RNG states, samples and the index list of rt_scene_direct (100 bytes a record); rays, RNG states, colours and the two
+    // counts of rt_scene_trace_nee (84 bytes a ray)
+    DevBuf d_out, d_outf, d_acc, d_cost, d_query, d_trace, d_aov, d_dn, d_cam, d_bounce, d_direct, d_nee;
     // HIP-event bookkeeping of launches not yet collected
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, free_ev;
     uint64_t primary_rays = 0;
@@ -808,7 +810,7 @@ static int rt_scene_destroy_impl(rt_scene* sc) {
     (void)hipFree(sc->d_leaf_of);
     (void)hipFree(sc->d_world_rank);
     (void)hipFree(sc->d_counters);
-    for (DevBuf* b : {&sc->d_out, &sc->d_outf, &sc->d_acc, &sc->d_cost, &sc->d_query, &sc->d_trace, &sc->d_aov, &sc->d_dn, &sc->d_cam, &sc->d_bounce, &sc->d_direct}) b->release();
+    for (DevBuf* b : {&sc->d_out, &sc->d_outf, &sc->d_acc, &sc->d_cost, &sc->d_query, &sc->d_trace, &sc->d_aov, &sc->d_dn, &sc->d_cam, &sc->d_bounce, &sc->d_direct, &sc->d_nee}) b->release();
     delete sc;
     g_live_scenes.fetch_sub(1);
     return RT_OK;
@@ -1401,6 +1403,101 @@ static int rt_scene_direct_impl(rt_scene* sc, const rt_direct_request* rq, const
         return rc;
     HIPCHK(hipMemcpyAsync(rng_state, d_state, state_b, hipMemcpyDeviceToHost, call.st));
     HIPCHK(hipMemcpyAsync(out, d_out, out_b, hipMemcpyDeviceToHost, call.st));
+    return call.finish(stats);
+}
+
+// ---- next-event estimation for caller rays (rt_tile.h "next-event estimation", rt_nee.hip.h) ---------------------------------------
+static int check_nee(rt_scene* sc, const rt_nee_request* rq, const void* rays, uint32_t n, const void* rgb) {
+    if (!sc) return fail(RT_ERR_BAD_ARG, "scene is NULL");
+    if (!rq) return fail(RT_ERR_BAD_ARG, "request is NULL");
+    if (!rays || !rgb) return fail(RT_ERR_BAD_ARG, "rays or out_rgb is NULL");
+    if (n == 0) return fail(RT_ERR_BAD_ARG, "n == 0");
+    if (rq->spp == 0) return fail(RT_ERR_BAD_ARG, "spp == 0");
+    if (rq->ray_form > RT_TRACE_RAY_AS_GIVEN) return fail(RT_ERR_BAD_ARG, "ray_form is neither RT_TRACE_RAY_NEW nor RT_TRACE_RAY_AS_GIVEN");
+    if (rq->mode > RT_NEE_MIS) return fail(RT_ERR_BAD_ARG, "mode is neither RT_NEE_LIGHT_ONLY nor RT_NEE_MIS");
+    if (rq->reserved != 0) return fail(RT_ERR_BAD_ARG, "reserved must be 0");
+    if (rq->spp > RT_MAX_SPP) return fail(RT_ERR_LIMIT, "spp > RT_MAX_SPP");
+    if (rq->max_bounces > RT_MAX_BOUNCES) return fail(RT_ERR_LIMIT, "max_bounces > RT_MAX_BOUNCES");
+    if (rtplan::plan_nee(sc->shape, sc->n_lights, rq->flags).too_many) return fail(RT_ERR_LIMIT, "more than 2^23 emitters");
+    return RT_OK;
+}
+
+// Enqueue one launch on `stream` (caller holds sc->mu, device current): persistent waves over the n rays.
+static int launch_nee(rt_scene* sc, const rt_nee_request* rq, const void* d_rays, uint32_t n, void* d_state, void* d_rgb, void* d_segs,
+                      void* d_shadow, hipStream_t stream) {
+    const rtplan::NeePlan np = rtplan::plan_nee(sc->shape, sc->n_lights, rq->flags);
+    const rtplan::QueryPlan& qp = np.query;
+    const rtk::NeeFn kern = rtk::nee_kernel(qp.engine, qp.scan_mode);
+    if (!kern) return fail(RT_ERR_HIP, "no next-event-estimation kernel for this plan");
+    rtk::NParams p;
+    std::memset(&p, 0, sizeof p);
+    p.rays = (const float4*)d_rays;
+    p.rgb = (float*)d_rgb;
+    p.segments = (uint32_t*)d_segs;
+    p.shadow = (uint32_t*)d_shadow;
+    p.rng_state = (uint64_t*)d_state;
+    p.n = n;
+    p.seed = rq->seed;
+    p.spp = rq->spp;
+    p.max_bounces = rq->max_bounces;
+    p.as_given = rq->ray_form == RT_TRACE_RAY_AS_GIVEN ? 1u : 0u;
+    p.mis = rq->mode == RT_NEE_MIS ? 1u : 0u;
+    scene_refs(sc, qp.full_chain, p);
+    p.mat = sc->d_mat;
+    p.emis = sc->d_emis;
+    p.lights = sc->d_lights;
+    p.n_lights = sc->n_lights;
+    Grid g;
+    int rc = persistent_blocks(sc, kern, rtplan::QUERY_BLOCK, qp.lds, n, g);
+    if (rc) return rc;
+    if (dbg(DBG_VERBOSE))
+        fprintf(stderr, "[rt] nee: engine %d  scan mode %d  lds %zu B  workgroups/CU %d  rays %u  spp %u  bounces %u  mode %u  lights %u\n",
+                qp.engine, qp.scan_mode, qp.lds, g.per_cu, n, rq->spp, rq->max_bounces, rq->mode, sc->n_lights);
+    if ((rc = enqueue(sc, stream, kern, g.blocks, rtplan::QUERY_BLOCK, qp.lds, p))) return rc;
+    sc->primary_rays += (uint64_t)n * rq->spp;
+    sc->last_engine = (uint32_t)qp.engine;
+    sc->last_form = 0;
+    return RT_OK;
+}
+
+static int rt_scene_trace_nee_device_impl(rt_scene* sc, const rt_nee_request* rq, const void* d_rays, uint32_t n, void* d_state,
+                                          void* d_rgb, void* d_segs, void* d_shadow, void* hip_stream) {
+    int rc = check_nee(sc, rq, d_rays, n, d_rgb);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    HIPCHK(hipSetDevice(sc->ctx->dev));
+    return launch_nee(sc, rq, d_rays, n, d_state, d_rgb, d_segs, d_shadow, hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream);
+}
+
+static int rt_scene_trace_nee_impl(rt_scene* sc, const rt_nee_request* rq, const rt_ray* rays, uint32_t n, uint64_t* rng_state,
+                                   float* rgb, uint32_t* segs, uint32_t* shadow, rt_tile_stats* stats) {
+    int rc = check_nee(sc, rq, rays, n, rgb);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> dl(sc->ctx->mu);
+    std::lock_guard<std::mutex> lk(sc->mu);
+    HIPCHK(hipSetDevice(sc->ctx->dev));
+    // one device buffer: rays (32 B), states (32 B), colours (12 B), segments (4 B), shadow rays (4 B) per ray
+    const size_t ray_b = (size_t)n * sizeof(rt_ray), state_b = (size_t)n * 4 * sizeof(uint64_t), rgb_b = (size_t)n * 3 * sizeof(float),
+                 cnt_b = (size_t)n * sizeof(uint32_t);
+    if ((rc = sc->d_nee.reserve(ray_b + state_b + rgb_b + 2 * cnt_b, "next-event-estimation buffers"))) return rc;
+    char* const d_rays = sc->d_nee.d;
+    char* const d_state = d_rays + ray_b;
+    char* const d_rgb = d_state + state_b;
+    char* const d_segs = d_rgb + rgb_b;
+    char* const d_shadow = d_segs + cnt_b;
+    StagedCall call(sc);
+    if ((rc = call.begin())) return rc;
+    HIPCHK(hipMemcpyAsync(d_rays, rays, ray_b, hipMemcpyHostToDevice, call.st));
+    if (rng_state) HIPCHK(hipMemcpyAsync(d_state, rng_state, state_b, hipMemcpyHostToDevice, call.st));
+    if ((rc = call.uploads_done()) ||
+        (rc = launch_nee(sc, rq, d_rays, n, rng_state ? d_state : nullptr, d_rgb, segs ? d_segs : nullptr, shadow ? d_shadow : nullptr,
+                         call.st)) ||
+        (rc = call.kernels_done()))
+        return rc;
+    HIPCHK(hipMemcpyAsync(rgb, d_rgb, rgb_b, hipMemcpyDeviceToHost, call.st));
+    if (segs) HIPCHK(hipMemcpyAsync(segs, d_segs, cnt_b, hipMemcpyDeviceToHost, call.st));
+    if (shadow) HIPCHK(hipMemcpyAsync(shadow, d_shadow, cnt_b, hipMemcpyDeviceToHost, call.st));
+    if (rng_state) HIPCHK(hipMemcpyAsync(rng_state, d_state, state_b, hipMemcpyDeviceToHost, call.st));
     return call.finish(stats);
 }
 
@@ -2498,6 +2595,16 @@ RT_API int rt_scene_direct_device(rt_scene* sc, const rt_direct_request* rq, con
                                   const void* d_n_active, void* d_out, void* hip_stream) {
     return guarded([&] {
         return rt_scene_direct_device_impl(sc, rq, d_hits, n, d_rng_state, d_active, d_n_active, d_out, hip_stream);
+    });
+}
+RT_API int rt_scene_trace_nee(rt_scene* sc, const rt_nee_request* rq, const rt_ray* rays, uint32_t n, uint64_t* rng_state, float* out_rgb,
+                              uint32_t* out_segments, uint32_t* out_shadow, rt_tile_stats* stats) {
+    return guarded([&] { return rt_scene_trace_nee_impl(sc, rq, rays, n, rng_state, out_rgb, out_segments, out_shadow, stats); });
+}
+RT_API int rt_scene_trace_nee_device(rt_scene* sc, const rt_nee_request* rq, const void* d_rays, uint32_t n, void* d_rng_state, void* d_out_rgb,
+                                     void* d_out_segments, void* d_out_shadow, void* hip_stream) {
+    return guarded([&] {
+        return rt_scene_trace_nee_device_impl(sc, rq, d_rays, n, d_rng_state, d_out_rgb, d_out_segments, d_out_shadow, hip_stream);
     });
 }
 RT_API int rt_scene_bounce(rt_scene* sc, const rt_bounce_request* rq, rt_ray* rays, uint32_t n, uint64_t* rng_state, const uint32_t* active,

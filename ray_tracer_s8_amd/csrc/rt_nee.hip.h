@@ -1,0 +1,198 @@
+// rt_nee.hip.h — gfx950 next-event-estimation integrator for caller rays (rt_scene_trace_nee*, rt_tile.h "next-event estimation";
+// DESIGN.md 4.18).
+//
+// One lane per caller ray: `spp` samples of a path of at most max_bounces + 1 segments, with one light sample after every hit of
+// roughness 0 but the last, summed in f32 in sample order.  Persistent waves stride over the batch as in rt_trace_kernel.  What the
+// composed loop of rt_scene_bounce and rt_scene_direct writes to memory between its launches — rays, states, hit records, bounce
+// records, samples, lists — stays in registers here, and the fold is FORWARD: the throughput T and the colour c are carried along,
+// so there is no path stack.
+//
+// ONE closest_hit site.  A lane is in one of two phases: its ray (o, d) is a path segment, or it is the shadow ray of the light
+// sample it has just drawn, in which case the scattered direction the path goes on with waits in `nd` (both rays start at the hit
+// point) and the sample's contribution, already weighted, waits in `add`.  Every trip of the loop walks the lane's ray through the
+// one site, whichever kind it is, and then resolves it.  A wave therefore never runs a walk for its path segments with the lanes
+// that have a shadow ray idle, and then another for the shadow rays with the rest idle: lanes in different phases share the walk.
+// A lane whose sample faces away, or whose hit is rough, goes straight on to its next segment.
+//
+// Every step is a shared one, so the bits are those of the composed entry points: closest_hit, hit_normal, sky_colour,
+// unit_sphere_pair, scattered_dir, u01 and the RNG load / store / seed of rt_path_steps.hip.h; the pick, point, fold, area, cosines,
+// weight and radiance of rt_direct_math.h, called in the order rt_direct_kernel calls them; the two MIS weights and the samplable
+// test of rt_nee_math.h.
+//
+// LDS per lane (rtplan::plan_nee): the walk's stack, (bvh depth + 1) u32 entries (engine 2); entry e of lane tid at [e * 256 + tid].
+// No per-scene scratch: launches on different streams may overlap.
+#pragma once
+#include "rt_direct.hip.h"
+#include "rt_nee_math.h"
+
+namespace rtk {
+
+struct NParams : SceneRefs {
+    const float4* rays;          // [2 n]: rt_ray (o, t_min) (d, t_max)
+    float* rgb;                  // [3 n]: the f32 sum of the ray's sample colours
+    uint32_t* segments;          // [n] path segments, or nullptr
+    uint32_t* shadow;            // [n] shadow rays, or nullptr
+    uint64_t* rng_state;         // [4 n] xoshiro256++ state per ray (read and written back), or nullptr: the seeded streams
+    uint64_t n;
+    uint64_t seed;               // rng_state == nullptr: sample s of ray i draws from seed_from_u64(seed + 4 PHI (i spp + s))
+    uint32_t spp, max_bounces;
+    uint32_t as_given;           // 1: the first direction is taken bit for bit (RT_TRACE_RAY_AS_GIVEN), 0: Ray::new normalises it
+    uint32_t mis;                // 1: RT_NEE_MIS, 0: RT_NEE_LIGHT_ONLY
+    const float4* mat;           // [n_sph + n_tri] (albedo r, g, b, roughness)
+    const float* emis;           // [n_sph + n_tri]
+    const uint32_t* lights;      // [n_lights] the emitters (library primitive numbers) in ascending world position
+    uint32_t n_lights;           // M <= rtdl::MAX_LIGHTS
+};
+
+// The size rt_direct_math.h's weights take for primitive `prim`: a sphere's radius, a triangle's area.
+template <class P>
+__device__ __forceinline__ float light_size(const P& p, uint32_t prim) {
+    if (prim < p.n_sph) return at32(p.geom_r, prim).w;
+    const float* tv = p.tri + 9 * (size_t)(prim - p.n_sph);
+    return rtdl::triangle_area(rtdl::Vec{tv[0], tv[1], tv[2]}, rtdl::Vec{tv[3], tv[4], tv[5]}, rtdl::Vec{tv[6], tv[7], tv[8]});
+}
+
+// ENGINE 2: the walk; 1: the scan with consider<MODE> (MODE 0 plain linear semantics, 2 BVH semantics).
+template <int ENGINE, int MODE>
+__global__ __launch_bounds__(256) void rt_nee_kernel(const NParams p) {
+    extern __shared__ uint32_t nstack[];                 // [depth + 1][256] (engine 2)
+    const uint32_t tid = threadIdx.x, bs = blockDim.x;
+    unsigned long long n_rays = 0, n_tests = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * bs + tid; i < p.n; i += (uint64_t)gridDim.x * bs) {
+        const CallerRay r = load_caller_ray(p.rays + 2 * i, p.as_given != 0);
+        Rng rng;
+        if (p.rng_state) load_rng(p.rng_state + 4 * i, rng);
+        float sum_r = 0.f, sum_g = 0.f, sum_b = 0.f;
+        uint32_t segs = 0, shad = 0;
+        for (uint32_t smp = 0; smp < p.spp; smp++) {
+            if (!p.rng_state) rng = seed_state(p.seed + (i * p.spp + smp) * (4ull * PHI));
+            V3 o = r.o, d = r.d;                         // the ray the next trip walks
+            V3 T = mk(1.f, 1.f, 1.f), c = mk(0.f, 0.f, 0.f);
+            V3 n_prev = mk(0.f, 0.f, 0.f);               // the normal of the last hit that scattered
+            V3 nd = mk(0.f, 0.f, 0.f), add = mk(0.f, 0.f, 0.f);   // shadow phase: the path's next direction; the sample's T * D (* wl)
+            uint32_t k = 0, lprim = 0;
+            bool sampled = false, shadow = false;
+            for (;;) {
+                const RayAux aux = ray_aux(d, p.full_chain != 0);
+                const Hit h = closest_hit<ENGINE, MODE, false>(p, o, d, r.t_min, r.t_max, aux, nstack, tid, bs, n_tests);
+                if (shadow) {
+                    // ================= the shadow ray resolved: LIT exactly when it reaches the emitter sampled =================
+                    shad++;
+                    if (h.idx == (int)lprim) {
+                        c.x = c.x + add.x;
+                        c.y = c.y + add.y;
+                        c.z = c.z + add.z;
+                    }
+                    d = nd;                                                            // on with the path, from the same point
+                    shadow = false;
+                    continue;
+                }
+                // ================= one path step, as rt_scene_bounce specifies it =================
+                segs++;
+                if (h.idx < 0) {                                                       // MISSED
+                    const V3 sky = sky_colour(d);
+                    c.x = c.x + T.x * sky.x;
+                    c.y = c.y + T.y * sky.y;
+                    c.z = c.z + T.z * sky.z;
+                    break;
+                }
+                const uint32_t prim = (uint32_t)h.idx;
+                const V3 hp = o + h.t * d;                                             // Ray::at (ray.rs:147-149)
+                const V3 nh = hit_normal(p, prim, hp);
+                const float em = at32(p.emis, prim);
+                const float4 ma = at32(p.mat, prim);
+                if (em > 0.0f) {                                                       // EMITTED
+                    float ex = ma.x * em, ey = ma.y * em, ez = ma.z * em;
+                    bool add_it = true;
+                    if (k != 0 && sampled) {
+                        // the light strategy's view of this point: could the sample of the step before have drawn it?
+                        const bool sphere = prim < p.n_sph;
+                        const rtnee::View v = rtnee::emitter_view(dvec(n_prev), dvec(d), dvec(nh), h.dist, sphere);
+                        if (v.samplable) {
+                            add_it = p.mis != 0;                                       // LIGHT_ONLY: that sample stood for it
+                            if (add_it) {
+                                const float wb = rtnee::bounce_weight(rtnee::view_weight(v, sphere, light_size(p, prim), p.n_lights));
+                                ex = ex * wb;
+                                ey = ey * wb;
+                                ez = ez * wb;
+                            }
+                        }
+                    }
+                    if (add_it) {
+                        c.x = c.x + T.x * ex;
+                        c.y = c.y + T.y * ey;
+                        c.z = c.z + T.z * ez;
+                    }
+                    break;
+                }
+                T.x = T.x * ma.x;                                                      // SCATTERED
+                T.y = T.y * ma.y;
+                T.z = T.z * ma.z;
+                float x1, x2, sm;
+                unit_sphere_pair(rng, x1, x2, sm);                                     // drawn also at the last depth (main.rs:119)
+                if (k == p.max_bounces) break;
+                k++;
+                const V3 dn = scattered_dir(d, nh, ma.w, x1, x2, sm);
+                o = hp;                                                                // origin exactly P, of either ray
+                d = dn;
+                n_prev = nh;
+                sampled = ma.w == 0.0f && p.n_lights > 0;
+                if (!sampled) continue;
+                // ================= one light sample, as rt_scene_direct specifies it for the record (P, n, prim) =================
+                const uint32_t pick = rtdl::pick_light(u01(rng), p.n_lights);
+                const uint32_t lp = p.lights[pick];
+                const bool sphere = lp < p.n_sph;
+                rtdl::Vec L, nl;
+                float size;
+                if (sphere) {
+                    const float4 g = at32(p.geom_r, lp);
+                    float y1, y2, ym;
+                    unit_sphere_pair(rng, y1, y2, ym);
+                    const float factor = 2.0f * RT_SQRT(1.0f - ym);
+                    nl = rtdl::Vec{y1 * factor, y2 * factor, 1.0f - 2.0f * ym};
+                    L = rtdl::sphere_point(rtdl::Vec{g.x, g.y, g.z}, g.w, nl);
+                    size = g.w;
+                } else {
+                    const float* tv = p.tri + 9 * (size_t)(lp - p.n_sph);
+                    const rtdl::Vec A{tv[0], tv[1], tv[2]}, B{tv[3], tv[4], tv[5]}, C{tv[6], tv[7], tv[8]};
+                    float u1 = u01(rng), u2 = u01(rng);
+                    rtdl::fold_pair(u1, u2);
+                    L = rtdl::triangle_point(A, B, C, u1, u2);
+                    nl = dvec(hit_normal(p, lp, mk(0.f, 0.f, 0.f)));
+                    size = rtdl::triangle_area(A, B, C);
+                }
+                const rtdl::Geometry g = rtdl::light_geometry(dvec(hp), dvec(nh), L, nl, sphere);
+                if (!g.facing) continue;                                               // FACING_AWAY: no ray, straight on
+                const float4 la = at32(p.mat, lp);
+                const float W = sphere ? rtdl::sphere_weight(g.cs, g.cl, size, p.n_lights, g.d2)
+                                       : rtdl::triangle_weight(g.cs, g.cl, size, p.n_lights, g.d2);
+                rtdl::Vec D = rtdl::radiance(rtdl::Vec{la.x, la.y, la.z}, at32(p.emis, lp), W);
+                if (p.mis) {
+                    const float wl = rtnee::light_weight(W);
+                    D = rtdl::Vec{D.x * wl, D.y * wl, D.z * wl};
+                }
+                add = mk(T.x * D.x, T.y * D.y, T.z * D.z);                             // added if the shadow ray is LIT
+                lprim = lp;
+                nd = dn;
+                d = v3of(g.w);                                                         // Ray::new(P, L - P)
+                shadow = true;
+            }
+            sum_r = sum_r + c.x;
+            sum_g = sum_g + c.y;
+            sum_b = sum_b + c.z;
+        }
+        p.rgb[3 * i + 0] = sum_r;
+        p.rgb[3 * i + 1] = sum_g;
+        p.rgb[3 * i + 2] = sum_b;
+        if (p.segments) p.segments[i] = segs;
+        if (p.shadow) p.shadow[i] = shad;
+        if (p.rng_state) store_rng(p.rng_state + 4 * i, rng);
+        n_rays += (unsigned long long)segs + shad;
+    }
+    flush_counters(p.counters, n_rays, n_tests, tid);
+}
+
+using NeeFn = void (*)(const NParams);
+NeeFn nee_kernel(int engine, int scan_mode);    // rt_kernels_nee.hip; nullptr for a combination that does not exist
+
+}  // namespace rtk

@@ -1,0 +1,40 @@
+// rt_nee_math.h — what the next-event-estimation integrator adds to the sampling arithmetic of rt_direct_math.h (rt_tile.h "next-event
+// estimation"): the two weights of the balance heuristic and the light strategy's view of a hit point the bounce
+// reached by itself.  Plain C++ that compiles as HIP device code (rt_nee.hip.h) and under g++ -ffp-contract=off
+// (tests/host/nee_host.cpp), so the kernel and the CPU harness run the same lines.  Every operation is one IEEE f32 rounding in the
+// order rt_tile.h writes it.
+#pragma once
+#include "rt_direct_math.h"
+
+namespace rtnee {
+
+// W of a light sample is (cs / pi) / p_light = p_bsdf / p_light, so the balance heuristic's weight of the LIGHT sample,
+// p_light / (p_light + p_bsdf), is 1 / (1 + W): 1 at W = 0, 0 at W = +inf, never NaN for W >= 0.
+RT_HOST_DEVICE float light_weight(float W) { return 1.0f / (1.0f + W); }
+
+// ... and the weight of the BOUNCE that found the emitter, p_bsdf / (p_light + p_bsdf), is 1 - 1 / (1 + W'): 0 at W' = 0, 1 at +inf.
+RT_HOST_DEVICE float bounce_weight(float W) { return 1.0f - 1.0f / (1.0f + W); }
+
+// An emitter hit by the bounce, as the light sample of the hit before would have seen the same point: n the normal of the hit before
+// (as rt_hit reports it), d the unit direction of the segment, nh this hit's rt_hit normal, distance its rt_hit.distance.
+struct View {
+    float cs, cl, d2;   // n . d;  -(nh . d) for a sphere, |nh . d| for a triangle;  distance * distance
+    bool samplable;     // cs > 0 and cl > 0 and d2 finite and not 0: the light sample could have drawn this point (Geometry::facing)
+};
+
+RT_HOST_DEVICE View emitter_view(rtdl::Vec n, rtdl::Vec d, rtdl::Vec nh, float distance, bool sphere) {
+    View v;
+    v.cs = rtdl::dot3(n, d);
+    const float c = rtdl::dot3(nh, d);
+    v.cl = sphere ? -c : __builtin_fabsf(c);
+    v.d2 = distance * distance;
+    v.samplable = v.cs > 0.0f && v.cl > 0.0f && v.d2 > 0.0f && v.d2 < __builtin_inff();
+    return v;
+}
+
+// W' of that point: the weight rt_direct_math.h gives a light sample with this geometry (size: the radius, or the triangle's area)
+RT_HOST_DEVICE float view_weight(const View& v, bool sphere, float size, uint32_t M) {
+    return sphere ? rtdl::sphere_weight(v.cs, v.cl, size, M, v.d2) : rtdl::triangle_weight(v.cs, v.cl, size, M, v.d2);
+}
+
+}  // namespace rtnee

@@ -527,6 +527,13 @@ inline DirectPlan plan_direct(const SceneShape& sh, uint32_t n_lights, uint32_t 
     return d;
 }
 
+// ---- Next-event estimation for caller rays (rt_scene_trace_nee*, rt_nee.hip.h).  One lane per caller ray; path
+// segments and shadow rays take the query path's engine through one closest-hit site, and the fold is forward (no path stack), so
+// the plan is the query plan plus the emitter limit of the pick, as plan_direct.
+using NeePlan = DirectPlan;
+
+inline NeePlan plan_nee(const SceneShape& sh, uint32_t n_lights, uint32_t flags) { return plan_direct(sh, n_lights, flags); }
+
 // ---- Path tracing of caller rays (rt_scene_trace*, rt_trace.hip.h).  One lane per caller ray, its samples and bounces
 // in a loop: the engine is the query path's, the plan adds the path stack and the workgroup size.
 constexpr uint32_t TRACE_LDS_CU = 160 * 1024;   // LDS of one CU: the trace kernels have no static LDS

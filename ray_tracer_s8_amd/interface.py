@@ -414,6 +414,47 @@ class Scene:
         _abi.check(self._lib.rt_scene_direct_device(self._h, C.byref(rq), vp(d_hits), n, vp(d_rng_state), vp(d_active), vp(d_n_active),
                                                     vp(d_out), vp(stream)), "rt_scene_direct_device")
 
+    def trace_nee(self, origins, directions, t_min=0.001, t_max=1000.0, *, spp: int = 1, max_bounces: int = 10, seed: int = 0,
+                  rng_state=None, as_given: bool = False, mode: int = _abi.RT_NEE_MIS, flags: int = 0):
+        """Next-event estimation for caller rays (rt_scene_trace_nee): for each ray, the f32 sum of `spp` samples of a path of at most
+        max_bounces + 1 segments with one light sample after every hit of roughness 0 but the last, in one kernel.  mode:
+        RT_NEE_LIGHT_ONLY (bit for bit the fold of Scene.bounce and Scene.direct) or RT_NEE_MIS (light sample and bounce combined by
+        the balance heuristic).  The other arguments as Scene.trace.
+        Returns (rgb_sum (N, 3) float32, segments (N,) uint32, shadow (N,) uint32, stats), and the written-back states (N, 4) when
+        rng_state is given."""
+        rays = _pack_rays(origins, directions, t_min, t_max)
+        n = len(rays)
+        state = None
+        if rng_state is not None:
+            state = np.array(rng_state, np.uint64, order="C")
+            if state.shape != (n, 4):
+                raise ValueError(f"rng_state: need an (N, 4) uint64 array, got {state.shape}")
+        rq = _abi.NeeRequest(spp, max_bounces, seed & 0xFFFFFFFFFFFFFFFF, flags,
+                             _abi.RT_TRACE_RAY_AS_GIVEN if as_given else _abi.RT_TRACE_RAY_NEW, mode, 0)
+        rgb = np.empty((n, 3), np.float32)
+        segs, shadow = np.empty(n, np.uint32), np.empty(n, np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        st = TileStats()
+        _abi.check(self._lib.rt_scene_trace_nee(self._h, C.byref(rq), rays.ctypes.data_as(C.POINTER(_abi.Ray)), n,
+                                                state.ctypes.data_as(C.POINTER(C.c_uint64)) if state is not None else None,
+                                                rgb.ctypes.data_as(C.POINTER(C.c_float)), segs.ctypes.data_as(u32p),
+                                                shadow.ctypes.data_as(u32p), C.byref(st)), "rt_scene_trace_nee")
+        if state is not None:
+            return rgb, segs, shadow, st, state
+        return rgb, segs, shadow, st
+
+    def trace_nee_device(self, d_rays: int, n: int, d_rgb: int, *, d_segments: int = 0, d_shadow: int = 0, d_rng_state: int = 0,
+                         spp: int = 1, max_bounces: int = 10, seed: int = 0, as_given: bool = False, mode: int = _abi.RT_NEE_MIS,
+                         flags: int = 0, stream: int = 0):
+        """Next-event estimation on device buffers (rt_scene_trace_nee_device): n rt_ray at d_rays, 3 n float32 sums to d_rgb,
+        optionally n uint32 path segments to d_segments, n uint32 shadow rays to d_shadow and 4 n uint64 states at d_rng_state (read
+        and written back) — e.g. the data_ptr() of torch tensors; asynchronous on `stream`, counters until collect()."""
+        rq = _abi.NeeRequest(spp, max_bounces, seed & 0xFFFFFFFFFFFFFFFF, flags,
+                             _abi.RT_TRACE_RAY_AS_GIVEN if as_given else _abi.RT_TRACE_RAY_NEW, mode, 0)
+        vp = lambda ptr: C.c_void_p(ptr) if ptr else None
+        _abi.check(self._lib.rt_scene_trace_nee_device(self._h, C.byref(rq), vp(d_rays), n, vp(d_rng_state), vp(d_rgb), vp(d_segments),
+                                                       vp(d_shadow), vp(stream)), "rt_scene_trace_nee_device")
+
     def render_aov(self, req: TileRequest, begin: int = 0, end: Optional[int] = None, *,
                    planes: Sequence[str] = _abi.AOV_PLANES, out: Optional[dict] = None):
         """Feature buffers of a strip (rt_scene_render_aov): over samples [begin, end) of the req.spp-sample job (end None:

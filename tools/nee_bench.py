@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Direct lighting of caller rays (rt_scene_direct): what one light sample per hit costs next to the path step it follows, and what
+"""Direct lighting of caller rays (rt_scene_direct) and the integrator in one kernel (rt_scene_trace_nee): what one light sample per hit costs next to the path step it follows, and what
 it buys, on the camera rays of a benchmark scene (default c2, cornell16).
 
   timing    the first path step of all camera rays alone (rt_scene_bounce), and the same step followed by rt_scene_direct on the
@@ -9,6 +9,9 @@ it buys, on the camera rays of a benchmark scene (default c2, cornell16).
             max_bounces = K - 1 on the same rays, one sample per ray each: the mean and the variance of the samples' luminance and
             the variance ratio at that equal sample count, over all samples and within the pixels' own samples.  (The means agree
             only where every hit has roughness 0: rt_tile.h.)
+  fused     the integrator in one kernel (rt_scene_trace_nee) in both modes on the same rays, max_bounces = K - 1: HIP-event time of
+            the kernel, best and median of --runs after --warmup warm-ups, beside the composed loop and rt_scene_trace timed the same
+            way, and each mode's mean, variance and variance ratio against rt_scene_trace at that equal sample count.
 
     python tools/nee_bench.py [--config c2] [--width 480 --height 270 --spp 4] [--steps 4]
 Prints one JSON line."""
@@ -26,6 +29,7 @@ import ray_tracer_s8_amd as rt  # noqa: E402
 from ray_tracer_s8_amd import _abi, scenes  # noqa: E402
 
 SCATTERED, EMITTED, MISSED = _abi.RT_BOUNCE_SCATTERED, _abi.RT_BOUNCE_EMITTED, _abi.RT_BOUNCE_MISSED
+MODES = {"light_only": _abi.RT_NEE_LIGHT_ONLY, "mis": _abi.RT_NEE_MIS}
 
 
 def _rgb(a):
@@ -92,6 +96,28 @@ def main():
         la, lb = ref[0].astype(np.float64).mean(1), col.mean(1)
         # the variance within a pixel's spp samples (records (row W + x) spp + s), averaged: the noise without the image's own variance
         wa, wb = (float(x.reshape(-1, a.spp).var(1, ddof=1).mean()) if a.spp > 1 else float("nan") for x in (la, lb))
+        # the composed loop, the one-kernel trace and the fused integrator in both modes, timed alike on the same rays
+        t_loop, t_trace, t_fused = [], [], {m: [] for m in MODES}
+        fused = {}
+        for i in range(a.warmup + a.runs):
+            _, ms_s, ms_d = nee(sc, rays, _states(n, 1), a.steps)
+            tr = sc.trace(o, dd, rays["t_min"], rays["t_max"], spp=1, max_bounces=a.steps - 1, rng_state=_states(n, 2), as_given=True)
+            for name, mode in MODES.items():
+                fused[name] = sc.trace_nee(o, dd, rays["t_min"], rays["t_max"], spp=1, max_bounces=a.steps - 1,
+                                           rng_state=_states(n, 3 + mode), as_given=True, mode=mode)
+            if i >= a.warmup:
+                t_loop.append(ms_s + ms_d)
+                t_trace.append(tr[2].kernel_ms)
+                for name in MODES:
+                    t_fused[name].append(fused[name][3].kernel_ms)
+        best_median = lambda t: {"best": min(t), "median": statistics.median(t)}
+        fused_out = {}
+        for name in MODES:
+            lf = fused[name][0].astype(np.float64).mean(1)
+            wf = float(lf.reshape(-1, a.spp).var(1, ddof=1).mean()) if a.spp > 1 else float("nan")
+            fused_out[name] = {"kernel_ms": best_median(t_fused[name]), "mean": float(lf.mean()), "variance": float(lf.var(ddof=1)),
+                               "variance_ratio": float(la.var(ddof=1) / lf.var(ddof=1)), "within_pixel_variance_ratio": wa / wf,
+                               "segments": int(fused[name][1].sum()), "shadow_rays": int(fused[name][2].sum())}
         out = {
             "config": a.config, "rays": n, "lights": sc.n_lights, "scattered": int(len(s["next"])), "shadow_rays": int(d["stats"].ray_segments),
             "step_ms": {"best": min(t_step), "median": statistics.median(t_step)},
@@ -102,6 +128,7 @@ def main():
             "nee": {"mean": float(lb.mean()), "variance": float(lb.var(ddof=1))},
             "variance_ratio": float(la.var(ddof=1) / lb.var(ddof=1)),
             "within_pixel_variance": {"trace": wa, "nee": wb, "ratio": wa / wb},
+            "composed_loop_ms": best_median(t_loop), "trace_ms": best_median(t_trace), "fused": fused_out,
         }
     print(json.dumps(out))
 
