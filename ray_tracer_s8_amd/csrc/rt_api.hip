@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -222,13 +223,15 @@ struct rt_scene {
     Ring rings[4];
     uint64_t ring_clock = 0;
     // staging of the host-buffer entry points (grown on demand): the strips' bytes, their f32 twins, the running sums of
-    // rt_scene_render_tile_pass and the per-strip ray segments of the batched call (frame context); the rays and hits of
-    // rt_scene_intersect; rays, RNG states, colours and segments of rt_scene_trace (80 bytes a ray); the planes of rt_scene_render_aov
+    // rt_scene_render_tile_pass and the per-strip ray segments of the batched call (frame context); the planes of rt_scene_render_aov
     // (36 bytes a pixel); the filter's scratch and the strips' inputs and outputs of rt_scene_denoise; rays and RNG states of
-    // rt_scene_camera_rays (64 bytes a record); rays, RNG states, bounces, hits and the two index lists of rt_scene_bounce (120 bytes
-    // a ray); hits, RNG states, samples and the index list of rt_scene_direct (100 bytes a record); rays, RNG states, colours and the two
-    // counts of rt_scene_trace_nee (84 bytes a ray)
-    DevBuf d_out, d_outf, d_acc, d_cost, d_query, d_trace, d_aov, d_dn, d_cam, d_bounce, d_direct, d_nee;
+    // rt_scene_camera_rays (64 bytes a record)
+    DevBuf d_out, d_outf, d_acc, d_cost, d_aov, d_dn, d_cam;
+    // ... and ONE buffer for the arrays of the caller-ray calls (rt_scene_intersect, _trace, _bounce, _direct, _trace_nee; Staging).
+    // They can share it: every such call holds ctx->mu and sc->mu from start to end, begins by collecting everything pending, and
+    // waits for its own downloads before it returns, so no two of them are ever in flight; and DevBuf::reserve frees (hipFree)
+    // only when it grows, which is before the call has enqueued anything.
+    DevBuf d_caller;
     // HIP-event bookkeeping of launches not yet collected
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, free_ev;
     uint64_t primary_rays = 0;
@@ -553,6 +556,117 @@ struct StagedCall {
     }
 };
 
+// ---- what the caller-ray calls share (ray queries, path tracing, path steps, direct lighting, next-event estimation) ---------------
+// A call's part of its launch's verbose line; empty, and nothing formatted, unless RT_VERBOSE is on.
+__attribute__((format(printf, 1, 2))) std::string vtext(const char* fmt, ...) {
+    if (!dbg(DBG_VERBOSE)) return {};
+    char buf[256];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return buf;
+}
+
+// The scene's materials, and its emitter list, into a parameter block that has the fields.
+template <class P>
+void material_refs(const rt_scene* sc, P& p) {
+    p.mat = sc->d_mat;
+    p.emis = sc->d_emis;
+}
+template <class P>
+void light_refs(const rt_scene* sc, P& p) {
+    p.lights = sc->d_lights;
+    p.n_lights = sc->n_lights;
+}
+
+// Enqueue one caller-ray launch on `stream` (caller holds sc->mu, device current): persistent waves over `items` in workgroups of
+// `block`, with the plan's engine, slab test and LDS.  Every launch_* of these calls ends here with its own fields filled in; the
+// scene goes into the block here.  what: the kernel's name in the error of a plan that has none; head, tail: the verbose line on
+// either side of the occupancy (vtext); primary: added to the scene's primary rays.  d_zero: a device word zeroed on the stream
+// ahead of the launch (a step's *n_next), left alone when there is no slot for the launch.
+template <class P>
+int launch_rays(rt_scene* sc, const rtplan::QueryPlan& qp, uint32_t block, void (*kern)(const P), const char* what, P& p, uint64_t items,
+                const std::string& head, const std::string& tail, uint64_t primary, hipStream_t stream, void* d_zero = nullptr) {
+    if (!kern) return fail(RT_ERR_HIP, std::string("no ") + what + " kernel for this plan");
+    scene_refs(sc, qp.full_chain, p);
+    Grid g;
+    int rc = persistent_blocks(sc, kern, block, qp.lds, items, g);
+    if (rc || (d_zero && (rc = check_slot(sc)))) return rc;
+    if (dbg(DBG_VERBOSE)) fprintf(stderr, "[rt] %s  workgroups/CU %d  %s\n", head.c_str(), g.per_cu, tail.c_str());
+    if (d_zero) HIPCHK(hipMemsetAsync(d_zero, 0, sizeof(uint32_t), stream));
+    if ((rc = enqueue(sc, stream, kern, g.blocks, block, qp.lds, p))) return rc;
+    sc->primary_rays += primary;
+    sc->last_engine = (uint32_t)qp.engine;
+    sc->last_form = 0;
+    return RT_OK;
+}
+
+// A device form: the scene's lock, the device, the caller's stream or the scene's own, then launch(stream).
+template <class L>
+int device_form(rt_scene* sc, void* hip_stream, L&& launch) {
+    std::lock_guard<std::mutex> lk(sc->mu);
+    HIPCHK(hipSetDevice(sc->ctx->dev));
+    return launch(hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream);
+}
+
+// The prologue of a host form: the device's lock and the scene's for the length of the call, and the device made current.
+struct HostForm {
+    rt_scene* const sc;
+    std::lock_guard<std::mutex> dl, lk;
+    explicit HostForm(rt_scene* s) : sc(s), dl(s->ctx->mu), lk(s->mu) {}
+    int device() const {
+        HIPCHK(hipSetDevice(sc->ctx->dev));
+        return RT_OK;
+    }
+};
+
+// The arrays of a host form, in the order they lie in the scene's one staging buffer (rt_scene::d_caller), each behind the one before.
+// An entry whose host pointer is NULL is an array the caller did not ask for: it is copied neither way and dev() gives nullptr.
+struct Staging {
+    enum : unsigned { UP = 1, DOWN = 2 };
+    struct Entry {
+        const void* host;
+        size_t bytes;
+        unsigned copy;           // UP: uploaded before the launch, DOWN: downloaded after it
+        size_t off;
+    };
+    DevBuf& buf;
+    std::vector<Entry> e;
+    size_t total = 0;
+    Staging(rt_scene* sc, std::initializer_list<Entry> entries) : buf(sc->d_caller), e(entries) {
+        for (Entry& x : e) {
+            x.off = total;
+            total += x.bytes;
+        }
+    }
+    int reserve(const char* what) { return buf.reserve(total, what); }
+    char* dev(int k) const { return e[k].host ? buf.d + e[k].off : nullptr; }
+    // the upload phase of `call`, and its download phase up to finish()
+    int upload(StagedCall& call) const {
+        for (int k = 0; k < (int)e.size(); k++)
+            if (e[k].host && e[k].bytes && (e[k].copy & UP)) HIPCHK(hipMemcpyAsync(dev(k), e[k].host, e[k].bytes, hipMemcpyHostToDevice, call.st));
+        return call.uploads_done();
+    }
+    int download(StagedCall& call) const {
+        int rc = call.kernels_done();
+        if (rc) return rc;
+        for (int k = 0; k < (int)e.size(); k++)
+            if (e[k].host && e[k].bytes && (e[k].copy & DOWN))
+                HIPCHK(hipMemcpyAsync(const_cast<void*>(e[k].host), dev(k), e[k].bytes, hipMemcpyDeviceToHost, call.st));
+        return RT_OK;
+    }
+};
+
+// The active list of a host form: at most n entries, each below n.
+int check_active_list(const uint32_t* active, uint32_t n_active, uint32_t n) {
+    if (!active) return RT_OK;
+    if (n_active > n) return fail(RT_ERR_BAD_ARG, "n_active > n");
+    for (uint32_t k = 0; k < n_active; k++)
+        if (active[k] >= n) return fail(RT_ERR_BAD_ARG, "active[" + std::to_string(k) + "] >= n");
+    return RT_OK;
+}
+
 }  // namespace
 
 // =====================================================================================
@@ -810,7 +924,7 @@ static int rt_scene_destroy_impl(rt_scene* sc) {
     (void)hipFree(sc->d_leaf_of);
     (void)hipFree(sc->d_world_rank);
     (void)hipFree(sc->d_counters);
-    for (DevBuf* b : {&sc->d_out, &sc->d_outf, &sc->d_acc, &sc->d_cost, &sc->d_query, &sc->d_trace, &sc->d_aov, &sc->d_dn, &sc->d_cam, &sc->d_bounce, &sc->d_direct, &sc->d_nee}) b->release();
+    for (DevBuf* b : {&sc->d_out, &sc->d_outf, &sc->d_acc, &sc->d_cost, &sc->d_aov, &sc->d_dn, &sc->d_cam, &sc->d_caller}) b->release();
     delete sc;
     g_live_scenes.fetch_sub(1);
     return RT_OK;
@@ -1046,53 +1160,34 @@ static int check_query(rt_scene* sc, const void* rays, uint32_t n, uint32_t mode
 // Enqueue one query launch on `stream` (caller holds sc->mu, device current): persistent waves over the n rays.
 static int launch_query(rt_scene* sc, const void* d_rays, uint32_t n, uint32_t mode, uint32_t flags, void* d_hits, hipStream_t stream) {
     const rtplan::QueryPlan qp = rtplan::plan_query(sc->shape, flags);
-    const rtk::QueryFn kern = rtk::query_kernel(qp.engine, qp.scan_mode, mode == RT_QUERY_ANY);
-    if (!kern) return fail(RT_ERR_HIP, "no query kernel for this plan");
     rtk::QParams p;
     std::memset(&p, 0, sizeof p);
     p.rays = (const float4*)d_rays;
     p.hits = (uint4*)d_hits;
     p.n = n;
-    scene_refs(sc, qp.full_chain, p);
-    Grid g;
-    int rc = persistent_blocks(sc, kern, rtplan::QUERY_BLOCK, qp.lds, n, g);
-    if (rc) return rc;
-    if (dbg(DBG_VERBOSE))
-        fprintf(stderr, "[rt] query: engine %d  scan mode %d  %s  lds %zu B  workgroups/CU %d  rays %u\n", qp.engine, qp.scan_mode,
-                mode == RT_QUERY_ANY ? "any" : "closest", qp.lds, g.per_cu, n);
-    if ((rc = enqueue(sc, stream, kern, g.blocks, rtplan::QUERY_BLOCK, qp.lds, p))) return rc;
-    sc->primary_rays += n;
-    sc->last_engine = (uint32_t)qp.engine;
-    sc->last_form = 0;
-    return RT_OK;
+    return launch_rays(sc, qp, rtplan::QUERY_BLOCK, rtk::query_kernel(qp.engine, qp.scan_mode, mode == RT_QUERY_ANY), "query", p, n,
+                       vtext("query: engine %d  scan mode %d  %s  lds %zu B", qp.engine, qp.scan_mode,
+                             mode == RT_QUERY_ANY ? "any" : "closest", qp.lds),
+                       vtext("rays %u", n), n, stream);
 }
 
 static int rt_scene_intersect_device_impl(rt_scene* sc, const void* d_rays, uint32_t n, uint32_t mode, uint32_t flags, void* d_hits,
                                           void* hip_stream) {
     int rc = check_query(sc, d_rays, n, mode, d_hits);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(sc->mu);
-    HIPCHK(hipSetDevice(sc->ctx->dev));
-    return launch_query(sc, d_rays, n, mode, flags, d_hits, hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream);
+    return device_form(sc, hip_stream, [&](hipStream_t st) { return launch_query(sc, d_rays, n, mode, flags, d_hits, st); });
 }
 
 static int rt_scene_intersect_impl(rt_scene* sc, const rt_ray* rays, uint32_t n, uint32_t mode, uint32_t flags, rt_hit* hits,
                                    rt_tile_stats* stats) {
     int rc = check_query(sc, rays, n, mode, hits);
     if (rc) return rc;
-    std::lock_guard<std::mutex> dl(sc->ctx->mu);
-    std::lock_guard<std::mutex> lk(sc->mu);
-    HIPCHK(hipSetDevice(sc->ctx->dev));
-    // one device buffer: the rays, then the hits (32 B each per ray)
-    const size_t ray_b = (size_t)n * sizeof(rt_ray), hit_b = (size_t)n * sizeof(rt_hit);
-    if ((rc = sc->d_query.reserve(ray_b + hit_b, "rays / hits"))) return rc;
-    char* const d_rays = sc->d_query.d;
-    char* const d_hits = d_rays + ray_b;
+    HostForm hf(sc);
+    Staging s(sc, {{rays, (size_t)n * sizeof(rt_ray), Staging::UP}, {hits, (size_t)n * sizeof(rt_hit), Staging::DOWN}});
     StagedCall call(sc);
-    if ((rc = call.begin())) return rc;
-    HIPCHK(hipMemcpyAsync(d_rays, rays, ray_b, hipMemcpyHostToDevice, call.st));
-    if ((rc = call.uploads_done()) || (rc = launch_query(sc, d_rays, n, mode, flags, d_hits, call.st)) || (rc = call.kernels_done())) return rc;
-    HIPCHK(hipMemcpyAsync(hits, d_hits, hit_b, hipMemcpyDeviceToHost, call.st));
+    if ((rc = hf.device()) || (rc = s.reserve("rays / hits")) || (rc = call.begin()) || (rc = s.upload(call)) ||
+        (rc = launch_query(sc, s.dev(0), n, mode, flags, s.dev(1), call.st)) || (rc = s.download(call)))
+        return rc;
     return call.finish(stats);
 }
 
@@ -1113,8 +1208,6 @@ static int check_trace(rt_scene* sc, const rt_trace_request* rq, const void* ray
 static int launch_trace(rt_scene* sc, const rt_trace_request* rq, const void* d_rays, uint32_t n, void* d_state, void* d_rgb,
                         void* d_segs, hipStream_t stream) {
     const rtplan::TracePlan tp = rtplan::plan_trace(sc->shape, rq->flags, rq->max_bounces);
-    const rtk::TraceFn kern = rtk::trace_kernel(tp.engine, tp.scan_mode);
-    if (!kern) return fail(RT_ERR_HIP, "no trace kernel for this plan");
     rtk::TParams p;
     std::memset(&p, 0, sizeof p);
     p.rays = (const float4*)d_rays;
@@ -1128,57 +1221,34 @@ static int launch_trace(rt_scene* sc, const rt_trace_request* rq, const void* d_
     p.as_given = rq->ray_form == RT_TRACE_RAY_AS_GIVEN ? 1u : 0u;
     p.path32 = tp.path32 ? 1u : 0u;
     p.lds_path_off = (uint32_t)tp.lds_path_off;
-    scene_refs(sc, tp.full_chain, p);
-    p.mat = sc->d_mat;
-    p.emis = sc->d_emis;
-    Grid g;
-    int rc = persistent_blocks(sc, kern, tp.block, tp.lds, n, g);
-    if (rc) return rc;
-    if (dbg(DBG_VERBOSE))
-        fprintf(stderr, "[rt] trace: engine %d  scan mode %d  block %u  lds %zu B (path %s)  workgroups/CU %d  rays %u  spp %u  bounces %u\n",
-                tp.engine, tp.scan_mode, tp.block, tp.lds, tp.path32 ? "u32" : "u16", g.per_cu, n, rq->spp, rq->max_bounces);
-    if ((rc = enqueue(sc, stream, kern, g.blocks, tp.block, tp.lds, p))) return rc;
-    sc->primary_rays += (uint64_t)n * rq->spp;
-    sc->last_engine = (uint32_t)tp.engine;
-    sc->last_form = 0;
-    return RT_OK;
+    material_refs(sc, p);
+    return launch_rays(sc, rtplan::QueryPlan{tp.engine, tp.scan_mode, tp.full_chain, tp.lds}, tp.block,
+                       rtk::trace_kernel(tp.engine, tp.scan_mode), "trace", p, n,
+                       vtext("trace: engine %d  scan mode %d  block %u  lds %zu B (path %s)", tp.engine, tp.scan_mode, tp.block, tp.lds,
+                             tp.path32 ? "u32" : "u16"),
+                       vtext("rays %u  spp %u  bounces %u", n, rq->spp, rq->max_bounces), (uint64_t)n * rq->spp, stream);
 }
 
 static int rt_scene_trace_device_impl(rt_scene* sc, const rt_trace_request* rq, const void* d_rays, uint32_t n, void* d_state,
                                       void* d_rgb, void* d_segs, void* hip_stream) {
     int rc = check_trace(sc, rq, d_rays, n, d_rgb);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(sc->mu);
-    HIPCHK(hipSetDevice(sc->ctx->dev));
-    return launch_trace(sc, rq, d_rays, n, d_state, d_rgb, d_segs, hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream);
+    return device_form(sc, hip_stream, [&](hipStream_t st) { return launch_trace(sc, rq, d_rays, n, d_state, d_rgb, d_segs, st); });
 }
 
 static int rt_scene_trace_impl(rt_scene* sc, const rt_trace_request* rq, const rt_ray* rays, uint32_t n, uint64_t* rng_state,
                                float* rgb, uint32_t* segs, rt_tile_stats* stats) {
     int rc = check_trace(sc, rq, rays, n, rgb);
     if (rc) return rc;
-    std::lock_guard<std::mutex> dl(sc->ctx->mu);
-    std::lock_guard<std::mutex> lk(sc->mu);
-    HIPCHK(hipSetDevice(sc->ctx->dev));
-    // one device buffer: rays (32 B), states (32 B), colours (12 B), segments (4 B) per ray
-    const size_t ray_b = (size_t)n * sizeof(rt_ray), state_b = (size_t)n * 4 * sizeof(uint64_t), rgb_b = (size_t)n * 3 * sizeof(float),
-                 seg_b = (size_t)n * sizeof(uint32_t);
-    if ((rc = sc->d_trace.reserve(ray_b + state_b + rgb_b + seg_b, "trace buffers"))) return rc;
-    char* const d_rays = sc->d_trace.d;
-    char* const d_state = d_rays + ray_b;
-    char* const d_rgb = d_state + state_b;
-    char* const d_segs = d_rgb + rgb_b;
+    HostForm hf(sc);
+    Staging s(sc, {{rays, (size_t)n * sizeof(rt_ray), Staging::UP},
+                   {rng_state, (size_t)n * 4 * sizeof(uint64_t), Staging::UP | Staging::DOWN},
+                   {rgb, (size_t)n * 3 * sizeof(float), Staging::DOWN},
+                   {segs, (size_t)n * sizeof(uint32_t), Staging::DOWN}});
     StagedCall call(sc);
-    if ((rc = call.begin())) return rc;
-    HIPCHK(hipMemcpyAsync(d_rays, rays, ray_b, hipMemcpyHostToDevice, call.st));
-    if (rng_state) HIPCHK(hipMemcpyAsync(d_state, rng_state, state_b, hipMemcpyHostToDevice, call.st));
-    if ((rc = call.uploads_done()) ||
-        (rc = launch_trace(sc, rq, d_rays, n, rng_state ? d_state : nullptr, d_rgb, segs ? d_segs : nullptr, call.st)) ||
-        (rc = call.kernels_done()))
+    if ((rc = hf.device()) || (rc = s.reserve("trace buffers")) || (rc = call.begin()) || (rc = s.upload(call)) ||
+        (rc = launch_trace(sc, rq, s.dev(0), n, s.dev(1), s.dev(2), s.dev(3), call.st)) || (rc = s.download(call)))
         return rc;
-    HIPCHK(hipMemcpyAsync(rgb, d_rgb, rgb_b, hipMemcpyDeviceToHost, call.st));
-    if (segs) HIPCHK(hipMemcpyAsync(segs, d_segs, seg_b, hipMemcpyDeviceToHost, call.st));
-    if (rng_state) HIPCHK(hipMemcpyAsync(rng_state, d_state, state_b, hipMemcpyDeviceToHost, call.st));
     return call.finish(stats);
 }
 
@@ -1203,8 +1273,6 @@ static int launch_bounce(rt_scene* sc, const rt_bounce_request* rq, void* d_rays
                          uint32_t count, const void* d_n_active, void* d_bounce, void* d_hits, void* d_next, void* d_n_next,
                          hipStream_t stream) {
     const rtplan::QueryPlan qp = rtplan::plan_query(sc->shape, rq->flags);
-    const rtk::BounceFn kern = rtk::bounce_kernel(qp.engine, qp.scan_mode);
-    if (!kern) return fail(RT_ERR_HIP, "no bounce kernel for this plan");
     rtk::BParams p;
     std::memset(&p, 0, sizeof p);
     p.rays = (float4*)d_rays;
@@ -1220,20 +1288,10 @@ static int launch_bounce(rt_scene* sc, const rt_bounce_request* rq, void* d_rays
     p.seed = rq->seed;
     p.as_given = rq->ray_form == RT_TRACE_RAY_AS_GIVEN ? 1u : 0u;
     p.seed_states = rq->seed_states;
-    scene_refs(sc, qp.full_chain, p);
-    p.mat = sc->d_mat;
-    p.emis = sc->d_emis;
-    Grid g;
-    int rc = persistent_blocks(sc, kern, rtplan::QUERY_BLOCK, qp.lds, std::max<uint32_t>(count, 1u), g);
-    if (rc || (rc = check_slot(sc))) return rc;
-    if (dbg(DBG_VERBOSE))
-        fprintf(stderr, "[rt] bounce: engine %d  scan mode %d  lds %zu B  workgroups/CU %d  rays %u  listed %s%u\n", qp.engine, qp.scan_mode,
-                qp.lds, g.per_cu, n, d_n_active ? "<= " : "", count);
-    if (d_n_next) HIPCHK(hipMemsetAsync(d_n_next, 0, sizeof(uint32_t), stream));
-    if ((rc = enqueue(sc, stream, kern, g.blocks, rtplan::QUERY_BLOCK, qp.lds, p))) return rc;
-    sc->last_engine = (uint32_t)qp.engine;
-    sc->last_form = 0;
-    return RT_OK;
+    material_refs(sc, p);
+    return launch_rays(sc, qp, rtplan::QUERY_BLOCK, rtk::bounce_kernel(qp.engine, qp.scan_mode), "bounce", p, std::max<uint32_t>(count, 1u),
+                       vtext("bounce: engine %d  scan mode %d  lds %zu B", qp.engine, qp.scan_mode, qp.lds),
+                       vtext("rays %u  listed %s%u", n, d_n_active ? "<= " : "", count), 0, stream, d_n_next);
 }
 
 static int rt_scene_bounce_device_impl(rt_scene* sc, const rt_bounce_request* rq, void* d_rays, uint32_t n, void* d_state,
@@ -1241,10 +1299,9 @@ static int rt_scene_bounce_device_impl(rt_scene* sc, const rt_bounce_request* rq
                                        void* d_n_next, void* hip_stream) {
     int rc = check_bounce(sc, rq, d_rays, n, d_state, d_active, d_n_active, d_bounce, d_next, d_n_next);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(sc->mu);
-    HIPCHK(hipSetDevice(sc->ctx->dev));
-    return launch_bounce(sc, rq, d_rays, n, d_state, d_active, n, d_n_active, d_bounce, d_hits, d_next, d_n_next,
-                         hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream);
+    return device_form(sc, hip_stream, [&](hipStream_t st) {
+        return launch_bounce(sc, rq, d_rays, n, d_state, d_active, n, d_n_active, d_bounce, d_hits, d_next, d_n_next, st);
+    });
 }
 
 static int rt_scene_bounce_impl(rt_scene* sc, const rt_bounce_request* rq, rt_ray* rays, uint32_t n, uint64_t* rng_state,
@@ -1252,52 +1309,29 @@ static int rt_scene_bounce_impl(rt_scene* sc, const rt_bounce_request* rq, rt_ra
                                 uint32_t* n_next, rt_tile_stats* stats) {
     // (the host form's n_active is a value: the both-or-neither rule is the device form's)
     int rc = check_bounce(sc, rq, rays, n, rng_state, nullptr, nullptr, bounce, next_active, n_next);
-    if (rc) return rc;
-    if (active) {
-        if (n_active > n) return fail(RT_ERR_BAD_ARG, "n_active > n");
-        for (uint32_t k = 0; k < n_active; k++)
-            if (active[k] >= n) return fail(RT_ERR_BAD_ARG, "active[" + std::to_string(k) + "] >= n");
-    }
+    if (rc || (rc = check_active_list(active, n_active, n))) return rc;
     const uint32_t count = active ? n_active : n;
-    std::lock_guard<std::mutex> dl(sc->ctx->mu);
-    std::lock_guard<std::mutex> lk(sc->mu);
-    HIPCHK(hipSetDevice(sc->ctx->dev));
-    // one device buffer: rays (32 B), states (32 B), hits (32 B), bounces (16 B), the two lists (4 B each) per ray, the next list's length
-    const size_t ray_b = (size_t)n * sizeof(rt_ray), state_b = (size_t)n * 4 * sizeof(uint64_t), hit_b = (size_t)n * sizeof(rt_hit),
-                 bnc_b = (size_t)n * sizeof(rt_bounce), list_b = (size_t)n * sizeof(uint32_t);
-    if ((rc = sc->d_bounce.reserve(ray_b + state_b + hit_b + bnc_b + 2 * list_b + sizeof(uint32_t), "bounce buffers"))) return rc;
-    char* const d_rays = sc->d_bounce.d;
-    char* const d_state = d_rays + ray_b;
-    char* const d_hits = d_state + state_b;
-    char* const d_bnc = d_hits + hit_b;
-    char* const d_active = d_bnc + bnc_b;
-    char* const d_next = d_active + list_b;
-    char* const d_n_next = d_next + list_b;
+    HostForm hf(sc);
+    // records of rays that are not listed come back as they went in: the caller's bytes are the staging's initial contents
+    const unsigned listed = active ? Staging::UP : 0;
+    enum { RAYS, STATE, HITS, BOUNCE, ACTIVE, NEXT, N_NEXT };
+    Staging s(sc, {{rays, (size_t)n * sizeof(rt_ray), Staging::UP | Staging::DOWN},
+                   {rng_state, (size_t)n * 4 * sizeof(uint64_t), Staging::UP | Staging::DOWN},
+                   {hits, (size_t)n * sizeof(rt_hit), listed | Staging::DOWN},
+                   {bounce, (size_t)n * sizeof(rt_bounce), listed | Staging::DOWN},
+                   {active, (size_t)count * sizeof(uint32_t), Staging::UP},
+                   {next_active, (size_t)n * sizeof(uint32_t), 0},      // (downloaded below)
+                   {n_next, sizeof(uint32_t), Staging::DOWN}});
     StagedCall call(sc);
-    if ((rc = call.begin())) return rc;
-    HIPCHK(hipMemcpyAsync(d_rays, rays, ray_b, hipMemcpyHostToDevice, call.st));
-    HIPCHK(hipMemcpyAsync(d_state, rng_state, state_b, hipMemcpyHostToDevice, call.st));
-    if (active && count) HIPCHK(hipMemcpyAsync(d_active, active, (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
-    if (active) {
-        // records of rays that are not listed come back as they went in: the caller's bytes are the staging's initial contents
-        HIPCHK(hipMemcpyAsync(d_bnc, bounce, bnc_b, hipMemcpyHostToDevice, call.st));
-        if (hits) HIPCHK(hipMemcpyAsync(d_hits, hits, hit_b, hipMemcpyHostToDevice, call.st));
-    }
-    if ((rc = call.uploads_done()) ||
-        (rc = launch_bounce(sc, rq, d_rays, n, d_state, active ? d_active : nullptr, count, nullptr, d_bnc, hits ? d_hits : nullptr,
-                            next_active ? d_next : nullptr, n_next ? d_n_next : nullptr, call.st)) ||
-        (rc = call.kernels_done()))
+    if ((rc = hf.device()) || (rc = s.reserve("bounce buffers")) || (rc = call.begin()) || (rc = s.upload(call)) ||
+        (rc = launch_bounce(sc, rq, s.dev(RAYS), n, s.dev(STATE), s.dev(ACTIVE), count, nullptr, s.dev(BOUNCE), s.dev(HITS), s.dev(NEXT),
+                            s.dev(N_NEXT), call.st)) ||
+        (rc = s.download(call)))
         return rc;
-    HIPCHK(hipMemcpyAsync(rays, d_rays, ray_b, hipMemcpyDeviceToHost, call.st));
-    HIPCHK(hipMemcpyAsync(rng_state, d_state, state_b, hipMemcpyDeviceToHost, call.st));
-    HIPCHK(hipMemcpyAsync(bounce, d_bnc, bnc_b, hipMemcpyDeviceToHost, call.st));
-    if (hits) HIPCHK(hipMemcpyAsync(hits, d_hits, hit_b, hipMemcpyDeviceToHost, call.st));
-    if (n_next) {
-        HIPCHK(hipMemcpyAsync(n_next, d_n_next, sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
-        if (next_active) {                                 // (the list's length is known only now)
-            HIPCHK(hipStreamSynchronize(call.st));
-            if (*n_next) HIPCHK(hipMemcpyAsync(next_active, d_next, (size_t)std::min(*n_next, n) * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
-        }
+    if (next_active) {                                     // (the list's length is known only now)
+        HIPCHK(hipStreamSynchronize(call.st));
+        const size_t next_b = (size_t)std::min(*n_next, n) * sizeof(uint32_t);
+        if (next_b) HIPCHK(hipMemcpyAsync(next_active, s.dev(NEXT), next_b, hipMemcpyDeviceToHost, call.st));
     }
     return call.finish(stats);
 }
@@ -1321,8 +1355,6 @@ static int launch_direct(rt_scene* sc, const rt_direct_request* rq, const void* 
     const rtplan::DirectPlan dp = rtplan::plan_direct(sc->shape, sc->n_lights, rq->flags);
     if (dp.too_many) return fail(RT_ERR_LIMIT, "more than 2^23 emitters");
     const rtplan::QueryPlan& qp = dp.query;
-    const rtk::DirectFn kern = rtk::direct_kernel(qp.engine, qp.scan_mode);
-    if (!kern) return fail(RT_ERR_HIP, "no direct-lighting kernel for this plan");
     rtk::DParams p;
     std::memset(&p, 0, sizeof p);
     p.hits = (const uint4*)d_hits;
@@ -1332,23 +1364,14 @@ static int launch_direct(rt_scene* sc, const rt_direct_request* rq, const void* 
     p.out = (uint4*)d_out;
     p.n = n;
     p.count = count;
-    scene_refs(sc, qp.full_chain, p);
-    p.mat = sc->d_mat;
-    p.emis = sc->d_emis;
-    p.lights = sc->d_lights;
-    p.n_lights = sc->n_lights;
+    material_refs(sc, p);
+    light_refs(sc, p);
     p.t_min = rq->t_min;
     p.t_max = rq->t_max;
-    Grid g;
-    int rc = persistent_blocks(sc, kern, rtplan::QUERY_BLOCK, qp.lds, std::max<uint32_t>(count, 1u), g);
-    if (rc) return rc;
-    if (dbg(DBG_VERBOSE))
-        fprintf(stderr, "[rt] direct: engine %d  scan mode %d  lds %zu B  workgroups/CU %d  records %u  listed %s%u  lights %u\n", qp.engine,
-                qp.scan_mode, qp.lds, g.per_cu, n, d_n_active ? "<= " : "", count, sc->n_lights);
-    if ((rc = enqueue(sc, stream, kern, g.blocks, rtplan::QUERY_BLOCK, qp.lds, p))) return rc;
-    sc->last_engine = (uint32_t)qp.engine;
-    sc->last_form = 0;
-    return RT_OK;
+    return launch_rays(sc, qp, rtplan::QUERY_BLOCK, rtk::direct_kernel(qp.engine, qp.scan_mode), "direct-lighting", p,
+                       std::max<uint32_t>(count, 1u),
+                       vtext("direct: engine %d  scan mode %d  lds %zu B", qp.engine, qp.scan_mode, qp.lds),
+                       vtext("records %u  listed %s%u  lights %u", n, d_n_active ? "<= " : "", count, sc->n_lights), 0, stream);
 }
 
 static int rt_scene_light_count_impl(rt_scene* sc, uint32_t* n_lights) {
@@ -1361,48 +1384,27 @@ static int rt_scene_direct_device_impl(rt_scene* sc, const rt_direct_request* rq
                                        const void* d_active, const void* d_n_active, void* d_out, void* hip_stream) {
     int rc = check_direct(sc, rq, d_hits, n, d_state, d_active, d_n_active, d_out);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(sc->mu);
-    HIPCHK(hipSetDevice(sc->ctx->dev));
-    return launch_direct(sc, rq, d_hits, n, d_state, d_active, n, d_n_active, d_out, hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream);
+    return device_form(sc, hip_stream,
+                       [&](hipStream_t st) { return launch_direct(sc, rq, d_hits, n, d_state, d_active, n, d_n_active, d_out, st); });
 }
 
 static int rt_scene_direct_impl(rt_scene* sc, const rt_direct_request* rq, const rt_hit* hits, uint32_t n, uint64_t* rng_state,
                                 const uint32_t* active, uint32_t n_active, rt_direct* out, rt_tile_stats* stats) {
     // (the host form's n_active is a value: the both-or-neither rule is the device form's)
     int rc = check_direct(sc, rq, hits, n, rng_state, nullptr, nullptr, out);
-    if (rc) return rc;
-    if (active) {
-        if (n_active > n) return fail(RT_ERR_BAD_ARG, "n_active > n");
-        for (uint32_t k = 0; k < n_active; k++)
-            if (active[k] >= n) return fail(RT_ERR_BAD_ARG, "active[" + std::to_string(k) + "] >= n");
-    } else if (n_active != 0) {
-        return fail(RT_ERR_BAD_ARG, "n_active without active");
-    }
+    if (rc || (rc = check_active_list(active, n_active, n))) return rc;
+    if (!active && n_active != 0) return fail(RT_ERR_BAD_ARG, "n_active without active");
     const uint32_t count = active ? n_active : n;
-    std::lock_guard<std::mutex> dl(sc->ctx->mu);
-    std::lock_guard<std::mutex> lk(sc->mu);
-    HIPCHK(hipSetDevice(sc->ctx->dev));
-    // one device buffer: hits (32 B), states (32 B), samples (32 B) and the list (4 B) per record
-    const size_t hit_b = (size_t)n * sizeof(rt_hit), state_b = (size_t)n * 4 * sizeof(uint64_t), out_b = (size_t)n * sizeof(rt_direct),
-                 list_b = (size_t)n * sizeof(uint32_t);
-    if ((rc = sc->d_direct.reserve(hit_b + state_b + out_b + list_b, "direct-lighting buffers"))) return rc;
-    char* const d_hits = sc->d_direct.d;
-    char* const d_state = d_hits + hit_b;
-    char* const d_out = d_state + state_b;
-    char* const d_active = d_out + out_b;
-    StagedCall call(sc);
-    if ((rc = call.begin())) return rc;
-    HIPCHK(hipMemcpyAsync(d_hits, hits, hit_b, hipMemcpyHostToDevice, call.st));
-    HIPCHK(hipMemcpyAsync(d_state, rng_state, state_b, hipMemcpyHostToDevice, call.st));
-    if (active && count) HIPCHK(hipMemcpyAsync(d_active, active, (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
+    HostForm hf(sc);
     // records that are not listed come back as they went in: the caller's bytes are the staging's initial contents
-    if (active) HIPCHK(hipMemcpyAsync(d_out, out, out_b, hipMemcpyHostToDevice, call.st));
-    if ((rc = call.uploads_done()) ||
-        (rc = launch_direct(sc, rq, d_hits, n, d_state, active ? d_active : nullptr, count, nullptr, d_out, call.st)) ||
-        (rc = call.kernels_done()))
+    Staging s(sc, {{hits, (size_t)n * sizeof(rt_hit), Staging::UP},
+                   {rng_state, (size_t)n * 4 * sizeof(uint64_t), Staging::UP | Staging::DOWN},
+                   {out, (size_t)n * sizeof(rt_direct), (active ? Staging::UP : 0u) | Staging::DOWN},
+                   {active, (size_t)count * sizeof(uint32_t), Staging::UP}});
+    StagedCall call(sc);
+    if ((rc = hf.device()) || (rc = s.reserve("direct-lighting buffers")) || (rc = call.begin()) || (rc = s.upload(call)) ||
+        (rc = launch_direct(sc, rq, s.dev(0), n, s.dev(1), s.dev(3), count, nullptr, s.dev(2), call.st)) || (rc = s.download(call)))
         return rc;
-    HIPCHK(hipMemcpyAsync(rng_state, d_state, state_b, hipMemcpyDeviceToHost, call.st));
-    HIPCHK(hipMemcpyAsync(out, d_out, out_b, hipMemcpyDeviceToHost, call.st));
     return call.finish(stats);
 }
 
@@ -1425,10 +1427,7 @@ static int check_nee(rt_scene* sc, const rt_nee_request* rq, const void* rays, u
 // Enqueue one launch on `stream` (caller holds sc->mu, device current): persistent waves over the n rays.
 static int launch_nee(rt_scene* sc, const rt_nee_request* rq, const void* d_rays, uint32_t n, void* d_state, void* d_rgb, void* d_segs,
                       void* d_shadow, hipStream_t stream) {
-    const rtplan::NeePlan np = rtplan::plan_nee(sc->shape, sc->n_lights, rq->flags);
-    const rtplan::QueryPlan& qp = np.query;
-    const rtk::NeeFn kern = rtk::nee_kernel(qp.engine, qp.scan_mode);
-    if (!kern) return fail(RT_ERR_HIP, "no next-event-estimation kernel for this plan");
+    const rtplan::QueryPlan qp = rtplan::plan_nee(sc->shape, sc->n_lights, rq->flags).query;
     rtk::NParams p;
     std::memset(&p, 0, sizeof p);
     p.rays = (const float4*)d_rays;
@@ -1442,62 +1441,35 @@ static int launch_nee(rt_scene* sc, const rt_nee_request* rq, const void* d_rays
     p.max_bounces = rq->max_bounces;
     p.as_given = rq->ray_form == RT_TRACE_RAY_AS_GIVEN ? 1u : 0u;
     p.mis = rq->mode == RT_NEE_MIS ? 1u : 0u;
-    scene_refs(sc, qp.full_chain, p);
-    p.mat = sc->d_mat;
-    p.emis = sc->d_emis;
-    p.lights = sc->d_lights;
-    p.n_lights = sc->n_lights;
-    Grid g;
-    int rc = persistent_blocks(sc, kern, rtplan::QUERY_BLOCK, qp.lds, n, g);
-    if (rc) return rc;
-    if (dbg(DBG_VERBOSE))
-        fprintf(stderr, "[rt] nee: engine %d  scan mode %d  lds %zu B  workgroups/CU %d  rays %u  spp %u  bounces %u  mode %u  lights %u\n",
-                qp.engine, qp.scan_mode, qp.lds, g.per_cu, n, rq->spp, rq->max_bounces, rq->mode, sc->n_lights);
-    if ((rc = enqueue(sc, stream, kern, g.blocks, rtplan::QUERY_BLOCK, qp.lds, p))) return rc;
-    sc->primary_rays += (uint64_t)n * rq->spp;
-    sc->last_engine = (uint32_t)qp.engine;
-    sc->last_form = 0;
-    return RT_OK;
+    material_refs(sc, p);
+    light_refs(sc, p);
+    return launch_rays(sc, qp, rtplan::QUERY_BLOCK, rtk::nee_kernel(qp.engine, qp.scan_mode), "next-event-estimation", p, n,
+                       vtext("nee: engine %d  scan mode %d  lds %zu B", qp.engine, qp.scan_mode, qp.lds),
+                       vtext("rays %u  spp %u  bounces %u  mode %u  lights %u", n, rq->spp, rq->max_bounces, rq->mode, sc->n_lights),
+                       (uint64_t)n * rq->spp, stream);
 }
 
 static int rt_scene_trace_nee_device_impl(rt_scene* sc, const rt_nee_request* rq, const void* d_rays, uint32_t n, void* d_state,
                                           void* d_rgb, void* d_segs, void* d_shadow, void* hip_stream) {
     int rc = check_nee(sc, rq, d_rays, n, d_rgb);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(sc->mu);
-    HIPCHK(hipSetDevice(sc->ctx->dev));
-    return launch_nee(sc, rq, d_rays, n, d_state, d_rgb, d_segs, d_shadow, hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream);
+    return device_form(sc, hip_stream, [&](hipStream_t st) { return launch_nee(sc, rq, d_rays, n, d_state, d_rgb, d_segs, d_shadow, st); });
 }
 
 static int rt_scene_trace_nee_impl(rt_scene* sc, const rt_nee_request* rq, const rt_ray* rays, uint32_t n, uint64_t* rng_state,
                                    float* rgb, uint32_t* segs, uint32_t* shadow, rt_tile_stats* stats) {
     int rc = check_nee(sc, rq, rays, n, rgb);
     if (rc) return rc;
-    std::lock_guard<std::mutex> dl(sc->ctx->mu);
-    std::lock_guard<std::mutex> lk(sc->mu);
-    HIPCHK(hipSetDevice(sc->ctx->dev));
-    // one device buffer: rays (32 B), states (32 B), colours (12 B), segments (4 B), shadow rays (4 B) per ray
-    const size_t ray_b = (size_t)n * sizeof(rt_ray), state_b = (size_t)n * 4 * sizeof(uint64_t), rgb_b = (size_t)n * 3 * sizeof(float),
-                 cnt_b = (size_t)n * sizeof(uint32_t);
-    if ((rc = sc->d_nee.reserve(ray_b + state_b + rgb_b + 2 * cnt_b, "next-event-estimation buffers"))) return rc;
-    char* const d_rays = sc->d_nee.d;
-    char* const d_state = d_rays + ray_b;
-    char* const d_rgb = d_state + state_b;
-    char* const d_segs = d_rgb + rgb_b;
-    char* const d_shadow = d_segs + cnt_b;
+    HostForm hf(sc);
+    Staging s(sc, {{rays, (size_t)n * sizeof(rt_ray), Staging::UP},
+                   {rng_state, (size_t)n * 4 * sizeof(uint64_t), Staging::UP | Staging::DOWN},
+                   {rgb, (size_t)n * 3 * sizeof(float), Staging::DOWN},
+                   {segs, (size_t)n * sizeof(uint32_t), Staging::DOWN},
+                   {shadow, (size_t)n * sizeof(uint32_t), Staging::DOWN}});
     StagedCall call(sc);
-    if ((rc = call.begin())) return rc;
-    HIPCHK(hipMemcpyAsync(d_rays, rays, ray_b, hipMemcpyHostToDevice, call.st));
-    if (rng_state) HIPCHK(hipMemcpyAsync(d_state, rng_state, state_b, hipMemcpyHostToDevice, call.st));
-    if ((rc = call.uploads_done()) ||
-        (rc = launch_nee(sc, rq, d_rays, n, rng_state ? d_state : nullptr, d_rgb, segs ? d_segs : nullptr, shadow ? d_shadow : nullptr,
-                         call.st)) ||
-        (rc = call.kernels_done()))
+    if ((rc = hf.device()) || (rc = s.reserve("next-event-estimation buffers")) || (rc = call.begin()) || (rc = s.upload(call)) ||
+        (rc = launch_nee(sc, rq, s.dev(0), n, s.dev(1), s.dev(2), s.dev(3), s.dev(4), call.st)) || (rc = s.download(call)))
         return rc;
-    HIPCHK(hipMemcpyAsync(rgb, d_rgb, rgb_b, hipMemcpyDeviceToHost, call.st));
-    if (segs) HIPCHK(hipMemcpyAsync(segs, d_segs, cnt_b, hipMemcpyDeviceToHost, call.st));
-    if (shadow) HIPCHK(hipMemcpyAsync(shadow, d_shadow, cnt_b, hipMemcpyDeviceToHost, call.st));
-    if (rng_state) HIPCHK(hipMemcpyAsync(rng_state, d_state, state_b, hipMemcpyDeviceToHost, call.st));
     return call.finish(stats);
 }
 

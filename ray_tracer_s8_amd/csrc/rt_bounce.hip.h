@@ -41,14 +41,10 @@ template <int ENGINE, int MODE>
 __global__ __launch_bounds__(256) void rt_bounce_kernel(const BParams p) {
     extern __shared__ uint32_t bstack[];                 // [depth + 1][256] (engine 2)
     const uint32_t tid = threadIdx.x;
-    uint64_t m = p.count;
-    if (p.n_active) {
-        const uint64_t listed = *p.n_active;
-        m = listed < m ? listed : m;
-    }
+    const uint64_t m = active_count(p);
     unsigned long long n_rays = 0, n_tests = 0;
     for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + tid; k < m; k += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t i = p.active ? (uint64_t)p.active[k] : k;
+        const uint64_t i = active_index(p, k);
         bool scattered = false;
         if (i < p.n) {                                                                 // (an index beyond the batch touches nothing)
             const CallerRay r = load_caller_ray(p.rays + 2 * i, p.as_given != 0);

@@ -4,8 +4,9 @@
 // scene's emitter list with one u01 of the ray's own RNG state, a point on it (the UnitSphere draw of the shared path steps for a
 // sphere light, two u01 for a triangle light), the two cosines, the shadow ray through the shared closest_hit, and the Lambertian
 // estimate without the surface albedo.  The arithmetic of the pick, the point, the cosines and the weight is rt_direct_math.h, which the
-// CPU harness runs too; the draws, the normal of a triangle light and the closest hit are the steps of rt_path_steps.hip.h, so the
-// shadow ray's hit is rt_scene_intersect's bit for bit.
+// CPU harness runs too; the sample (light_sample, sample_weight: the draws, the point, the normal of a triangle light) and the
+// closest hit are the steps of rt_path_steps.hip.h, so the sample is rt_nee_kernel's and the shadow ray's hit is rt_scene_intersect's
+// bit for bit.
 //
 // Persistent waves stride over the active list (or over all n records) exactly as rt_bounce_kernel does; the device form reads the
 // list's length from device memory.  Lanes whose sample faces away trace nothing: the walk runs under one branch that the lanes with
@@ -14,7 +15,6 @@
 // LDS per lane (rtplan::plan_query): the walk's stack, (bvh depth + 1) u32 entries (engine 2); entry e of lane tid at [e * 256 + tid].
 // No per-scene scratch: launches on different streams may overlap.
 #pragma once
-#include "rt_direct_math.h"
 #include "rt_path_steps.hip.h"
 
 namespace rtk {
@@ -34,22 +34,15 @@ struct DParams : SceneRefs {
     float t_min, t_max;          // the shadow rays' window
 };
 
-__device__ __forceinline__ rtdl::Vec dvec(V3 a) { return rtdl::Vec{a.x, a.y, a.z}; }
-__device__ __forceinline__ V3 v3of(rtdl::Vec a) { return mk(a.x, a.y, a.z); }
-
 // ENGINE 2: the walk; 1: the scan with consider<MODE> (MODE 0 plain linear semantics, 2 BVH semantics).
 template <int ENGINE, int MODE>
 __global__ __launch_bounds__(256) void rt_direct_kernel(const DParams p) {
     extern __shared__ uint32_t dstack[];                 // [depth + 1][256] (engine 2)
     const uint32_t tid = threadIdx.x;
-    uint64_t m = p.count;
-    if (p.n_active) {
-        const uint64_t listed = *p.n_active;
-        m = listed < m ? listed : m;
-    }
+    const uint64_t m = active_count(p);
     unsigned long long n_rays = 0, n_tests = 0;
     for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + tid; k < m; k += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t i = p.active ? (uint64_t)p.active[k] : k;
+        const uint64_t i = active_index(p, k);
         if (i >= p.n) continue;                                                        // (an index beyond the batch touches nothing)
         const uint4 h0 = p.hits[2 * i], h1 = p.hits[2 * i + 1];
         if (h1.w == RT_HIT_NONE || p.n_lights == 0) {                                  // no draw, the state unchanged
@@ -62,31 +55,10 @@ __global__ __launch_bounds__(256) void rt_direct_kernel(const DParams p) {
         // ================= the draws: the emitter, then the point on it =================
         Rng rng;
         load_rng(p.rng_state + 4 * i, rng);
-        const uint32_t pick = rtdl::pick_light(u01(rng), p.n_lights);
-        const uint32_t prim = p.lights[pick];
-        const bool sphere = prim < p.n_sph;
-        rtdl::Vec L, nl;
-        float size;                                                                    // the radius, or the triangle's area
-        if (sphere) {
-            const float4 g = at32(p.geom_r, prim);
-            float x1, x2, sm;
-            unit_sphere_pair(rng, x1, x2, sm);                                         // UnitSphere, as a scattering hit draws it
-            const float factor = 2.0f * RT_SQRT(1.0f - sm);
-            nl = rtdl::Vec{x1 * factor, x2 * factor, 1.0f - 2.0f * sm};
-            L = rtdl::sphere_point(rtdl::Vec{g.x, g.y, g.z}, g.w, nl);
-            size = g.w;
-        } else {
-            const float* tv = p.tri + 9 * (size_t)(prim - p.n_sph);
-            const rtdl::Vec A{tv[0], tv[1], tv[2]}, B{tv[3], tv[4], tv[5]}, C{tv[6], tv[7], tv[8]};
-            float u1 = u01(rng), u2 = u01(rng);
-            rtdl::fold_pair(u1, u2);
-            L = rtdl::triangle_point(A, B, C, u1, u2);
-            nl = dvec(hit_normal(p, prim, mk(0.f, 0.f, 0.f)));                         // (a triangle's normal does not read the point)
-            size = rtdl::triangle_area(A, B, C);
-        }
+        const LightSample ls = light_sample(p, rng);
         store_rng(p.rng_state + 4 * i, rng);
         // ================= the cosines; the shadow ray Ray::new(P, L - P) =================
-        const rtdl::Geometry g = rtdl::light_geometry(dvec(P), dvec(n), L, nl, sphere);
+        const rtdl::Geometry g = rtdl::light_geometry(dvec(P), dvec(n), ls.L, ls.nl, ls.sphere);
         uint32_t status = RT_DIRECT_FACING_AWAY;
         rtdl::Vec rgb{0.0f, 0.0f, 0.0f};
         if (g.facing) {
@@ -95,16 +67,15 @@ __global__ __launch_bounds__(256) void rt_direct_kernel(const DParams p) {
             n_rays++;
             const Hit h = closest_hit<ENGINE, MODE, false>(p, P, d, p.t_min, p.t_max, aux, dstack, tid, 256u, n_tests);
             status = RT_DIRECT_OCCLUDED;
-            if (h.idx == (int)prim) {
+            if (h.idx == (int)ls.prim) {
                 status = RT_DIRECT_LIT;
-                const float4 ma = at32(p.mat, prim);
-                const float W = sphere ? rtdl::sphere_weight(g.cs, g.cl, size, p.n_lights, g.d2)
-                                       : rtdl::triangle_weight(g.cs, g.cl, size, p.n_lights, g.d2);
-                rgb = rtdl::radiance(rtdl::Vec{ma.x, ma.y, ma.z}, at32(p.emis, prim), W);
+                const float4 ma = at32(p.mat, ls.prim);
+                const float W = sample_weight(ls, g, p.n_lights);
+                rgb = rtdl::radiance(rtdl::Vec{ma.x, ma.y, ma.z}, at32(p.emis, ls.prim), W);
             }
         }
-        p.out[2 * i] = make_uint4(__float_as_uint(rgb.x), __float_as_uint(rgb.y), __float_as_uint(rgb.z), world_position(p, prim));
-        p.out[2 * i + 1] = make_uint4(__float_as_uint(L.x), __float_as_uint(L.y), __float_as_uint(L.z), status);
+        p.out[2 * i] = make_uint4(__float_as_uint(rgb.x), __float_as_uint(rgb.y), __float_as_uint(rgb.z), world_position(p, ls.prim));
+        p.out[2 * i + 1] = make_uint4(__float_as_uint(ls.L.x), __float_as_uint(ls.L.y), __float_as_uint(ls.L.z), status);
     }
     flush_counters(p.counters, n_rays, n_tests, tid);
 }

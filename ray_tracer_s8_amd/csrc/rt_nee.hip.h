@@ -15,15 +15,15 @@
 // A lane whose sample faces away, or whose hit is rough, goes straight on to its next segment.
 //
 // Every step is a shared one, so the bits are those of the composed entry points: closest_hit, hit_normal, sky_colour,
-// unit_sphere_pair, scattered_dir, u01 and the RNG load / store / seed of rt_path_steps.hip.h; the pick, point, fold, area, cosines,
-// weight and radiance of rt_direct_math.h, called in the order rt_direct_kernel calls them; the two MIS weights and the samplable
-// test of rt_nee_math.h.
+// unit_sphere_pair, scattered_dir, u01 and the RNG load / store / seed of rt_path_steps.hip.h; the light
+// sample is light_sample, rtdl::light_geometry and sample_weight, the steps rt_direct_kernel calls; the two MIS weights and the
+// samplable test of rt_nee_math.h.
 //
 // LDS per lane (rtplan::plan_nee): the walk's stack, (bvh depth + 1) u32 entries (engine 2); entry e of lane tid at [e * 256 + tid].
 // No per-scene scratch: launches on different streams may overlap.
 #pragma once
-#include "rt_direct.hip.h"
 #include "rt_nee_math.h"
+#include "rt_path_steps.hip.h"
 
 namespace rtk {
 
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void rt_nee_kernel(const NParams p) {
         float sum_r = 0.f, sum_g = 0.f, sum_b = 0.f;
         uint32_t segs = 0, shad = 0;
         for (uint32_t smp = 0; smp < p.spp; smp++) {
-            if (!p.rng_state) rng = seed_state(p.seed + (i * p.spp + smp) * (4ull * PHI));
+            if (!p.rng_state) rng = sample_seed(p, i, smp);
             V3 o = r.o, d = r.d;                         // the ray the next trip walks
             V3 T = mk(1.f, 1.f, 1.f), c = mk(0.f, 0.f, 0.f);
             V3 n_prev = mk(0.f, 0.f, 0.f);               // the normal of the last hit that scattered
@@ -139,40 +139,18 @@ __global__ __launch_bounds__(256) void rt_nee_kernel(const NParams p) {
                 sampled = ma.w == 0.0f && p.n_lights > 0;
                 if (!sampled) continue;
                 // ================= one light sample, as rt_scene_direct specifies it for the record (P, n, prim) =================
-                const uint32_t pick = rtdl::pick_light(u01(rng), p.n_lights);
-                const uint32_t lp = p.lights[pick];
-                const bool sphere = lp < p.n_sph;
-                rtdl::Vec L, nl;
-                float size;
-                if (sphere) {
-                    const float4 g = at32(p.geom_r, lp);
-                    float y1, y2, ym;
-                    unit_sphere_pair(rng, y1, y2, ym);
-                    const float factor = 2.0f * RT_SQRT(1.0f - ym);
-                    nl = rtdl::Vec{y1 * factor, y2 * factor, 1.0f - 2.0f * ym};
-                    L = rtdl::sphere_point(rtdl::Vec{g.x, g.y, g.z}, g.w, nl);
-                    size = g.w;
-                } else {
-                    const float* tv = p.tri + 9 * (size_t)(lp - p.n_sph);
-                    const rtdl::Vec A{tv[0], tv[1], tv[2]}, B{tv[3], tv[4], tv[5]}, C{tv[6], tv[7], tv[8]};
-                    float u1 = u01(rng), u2 = u01(rng);
-                    rtdl::fold_pair(u1, u2);
-                    L = rtdl::triangle_point(A, B, C, u1, u2);
-                    nl = dvec(hit_normal(p, lp, mk(0.f, 0.f, 0.f)));
-                    size = rtdl::triangle_area(A, B, C);
-                }
-                const rtdl::Geometry g = rtdl::light_geometry(dvec(hp), dvec(nh), L, nl, sphere);
+                const LightSample ls = light_sample(p, rng);
+                const rtdl::Geometry g = rtdl::light_geometry(dvec(hp), dvec(nh), ls.L, ls.nl, ls.sphere);
                 if (!g.facing) continue;                                               // FACING_AWAY: no ray, straight on
-                const float4 la = at32(p.mat, lp);
-                const float W = sphere ? rtdl::sphere_weight(g.cs, g.cl, size, p.n_lights, g.d2)
-                                       : rtdl::triangle_weight(g.cs, g.cl, size, p.n_lights, g.d2);
-                rtdl::Vec D = rtdl::radiance(rtdl::Vec{la.x, la.y, la.z}, at32(p.emis, lp), W);
+                const float4 la = at32(p.mat, ls.prim);
+                const float W = sample_weight(ls, g, p.n_lights);
+                rtdl::Vec D = rtdl::radiance(rtdl::Vec{la.x, la.y, la.z}, at32(p.emis, ls.prim), W);
                 if (p.mis) {
                     const float wl = rtnee::light_weight(W);
                     D = rtdl::Vec{D.x * wl, D.y * wl, D.z * wl};
                 }
                 add = mk(T.x * D.x, T.y * D.y, T.z * D.z);                             // added if the shadow ray is LIT
-                lprim = lp;
+                lprim = ls.prim;
                 nd = dn;
                 d = v3of(g.w);                                                         // Ray::new(P, L - P)
                 shadow = true;

@@ -1,12 +1,14 @@
 // rt_path_steps.hip.h — the path steps the caller-ray kernels share (DESIGN.md 1 "Device-side steps").
 //
-// The kernels beside the tile renderer (rt_query.hip.h, rt_trace.hip.h, rt_bounce.hip.h, rt_aov.hip.h, rt_camera.hip.h) each walk a
-// part of the reference's path: the camera ray, the closest hit and its record, the shade, the scattered ray.  Every such part is
-// written ONCE, here, with the operations of the tile kernel (rt_kernel.hip.h) in the same order — so the same bits — and inlined
-// into its callers.  A kernel derives its parameter block from SceneRefs (and CameraRefs), calls the steps and adds only
-// what is its own.  The tile kernel keeps its merged camera / bounce arm and its single shared normalisation (measured divergence
-// optimisations); what it shares with these steps is the device primitives they are made of.
+// The kernels beside the tile renderer (rt_query.hip.h, rt_trace.hip.h, rt_bounce.hip.h, rt_direct.hip.h, rt_nee.hip.h, rt_aov.hip.h,
+// rt_camera.hip.h) each walk a part of the reference's path: the camera ray, the closest hit and its record, the shade, the scattered
+// ray; two of them add a light sample.  Every such part is written ONCE, here, with the operations of the tile kernel
+// (rt_kernel.hip.h) in the same order — so the same bits — and inlined into its callers.  A kernel derives its parameter block from
+// SceneRefs (and CameraRefs), calls the steps and adds only what is its own.  The tile kernel keeps its merged camera / bounce arm
+// and its single shared normalisation (measured divergence optimisations); what it shares with these steps is the device primitives
+// they are made of.
 #pragma once
+#include "rt_direct_math.h"
 #include "rt_kernel.hip.h"
 #include "rt_tile.h"
 
@@ -166,17 +168,67 @@ __device__ __forceinline__ void unit_sphere_pair(Rng& rng, float& x1, float& x2,
     }
 }
 
+// The UnitSphere vector of an accepted pair (main.rs:119): a scattering hit adds it to the normal, a sphere light takes it as the
+// normal of the sampled point.
+__device__ __forceinline__ V3 unit_sphere_vec(float x1, float x2, float sm) {
+    const float factor = 2.0f * RT_SQRT(1.0f - sm);
+    return mk(x1 * factor, x2 * factor, 1.0f - 2.0f * sm);
+}
+
 // ... forms the direction of the scattered ray (main.rs:119-127) from the incoming direction d, the hit's normal n, the material's
 // roughness and the accepted pair.  Its origin is the hit point, exactly.
 __device__ __forceinline__ V3 scattered_dir(V3 d, V3 n, float roughness, float x1, float x2, float sm) {
-    const float factor = 2.0f * RT_SQRT(1.0f - sm);                        // UnitSphere, main.rs:119
-    const V3 us = mk(x1 * factor, x2 * factor, 1.0f - 2.0f * sm);
-    const V3 diffuse_dir = us + n;
+    const V3 diffuse_dir = unit_sphere_vec(x1, x2, sm) + n;
     const V3 glossy_dir = d - (2.0f * dot(d, n)) * n;                      // main.rs:120-121
     const V3 pre = diffuse_dir + roughness * (glossy_dir - diffuse_dir);   // main.rs:122
     V3 xdir;
     if (!try_normalize(pre, xdir)) xdir = n;                               // main.rs:126
     return normalize(xdir);                                                // Ray::new (ray.rs:134)
+}
+
+// ------------------------------------------------------------------ the light sample (rt_tile.h "direct lighting")
+// The arithmetic is rt_direct_math.h, which the CPU harness runs too; the draws, the triangle's normal and the scene are the kernel's.
+__device__ __forceinline__ rtdl::Vec dvec(V3 a) { return rtdl::Vec{a.x, a.y, a.z}; }
+__device__ __forceinline__ V3 v3of(rtdl::Vec a) { return mk(a.x, a.y, a.z); }
+
+struct LightSample {
+    uint32_t prim;               // the emitter picked (library primitive number)
+    bool sphere;
+    rtdl::Vec L, nl;             // the point on it and the emitter's normal there
+    float size;                  // the radius, or the triangle's area
+};
+
+// One light sample drawn from rng (p.n_lights > 0): the emitter picked uniformly with one u01, then a point on it — the UnitSphere draw
+// of a scattering hit for a sphere light, two u01 for a triangle light.  P: a parameter block with lights / n_lights.
+template <class P>
+__device__ __forceinline__ LightSample light_sample(const P& p, Rng& rng) {
+    LightSample s;
+    const uint32_t pick = rtdl::pick_light(u01(rng), p.n_lights);
+    s.prim = p.lights[pick];
+    s.sphere = s.prim < p.n_sph;
+    if (s.sphere) {
+        const float4 g = at32(p.geom_r, s.prim);
+        float x1, x2, sm;
+        unit_sphere_pair(rng, x1, x2, sm);
+        s.nl = dvec(unit_sphere_vec(x1, x2, sm));
+        s.L = rtdl::sphere_point(rtdl::Vec{g.x, g.y, g.z}, g.w, s.nl);
+        s.size = g.w;
+    } else {
+        const float* tv = p.tri + 9 * (size_t)(s.prim - p.n_sph);
+        const rtdl::Vec A{tv[0], tv[1], tv[2]}, B{tv[3], tv[4], tv[5]}, C{tv[6], tv[7], tv[8]};
+        float u1 = u01(rng), u2 = u01(rng);
+        rtdl::fold_pair(u1, u2);
+        s.L = rtdl::triangle_point(A, B, C, u1, u2);
+        s.nl = dvec(hit_normal(p, s.prim, mk(0.f, 0.f, 0.f)));                         // (a triangle's normal does not read the point)
+        s.size = rtdl::triangle_area(A, B, C);
+    }
+    return s;
+}
+
+// W of the sample s seen under the geometry g = rtdl::light_geometry(P, n, s.L, s.nl, s.sphere): radiance(albedo, emission, W) is the
+// estimate, and the MIS weight of the light strategy reads W itself.
+__device__ __forceinline__ float sample_weight(const LightSample& s, const rtdl::Geometry& g, uint32_t n_lights) {
+    return s.sphere ? rtdl::sphere_weight(g.cs, g.cl, s.size, n_lights, g.d2) : rtdl::triangle_weight(g.cs, g.cl, s.size, n_lights, g.d2);
 }
 
 // ------------------------------------------------------------------ the camera ray (Camera::get_ray, camera.rs:109-129)
@@ -240,6 +292,28 @@ __device__ __forceinline__ void store_rng(uint64_t* s, const Rng& rng) {
     s[1] = rng.s1;
     s[2] = rng.s2;
     s[3] = rng.s3;
+}
+
+// The active list of a step (BParams, DParams): the number of entries taken, min(count, *n_active), and the index entry k names.  The
+// kernel guards it with i < p.n itself: an index beyond the batch touches nothing.
+template <class P>
+__device__ __forceinline__ uint64_t active_count(const P& p) {
+    uint64_t m = p.count;
+    if (p.n_active) {
+        const uint64_t listed = *p.n_active;
+        m = listed < m ? listed : m;
+    }
+    return m;
+}
+template <class P>
+__device__ __forceinline__ uint64_t active_index(const P& p, uint64_t k) {
+    return p.active ? (uint64_t)p.active[k] : k;
+}
+
+// The stream of sample smp of ray i in a kernel that sums `spp` seeded samples per caller ray (TParams, NParams without caller states).
+template <class P>
+__device__ __forceinline__ Rng sample_seed(const P& p, uint64_t i, uint32_t smp) {
+    return seed_state(p.seed + (i * p.spp + smp) * (4ull * PHI));
 }
 
 // i -> (q, r) = (i / n, i % n), q < 2^32: a 32-bit division while i fits (every launch of fewer than 2^32 items)

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void rt_trace_kernel(const TParams p) {
         float sum_r = 0.f, sum_g = 0.f, sum_b = 0.f;
         uint32_t segs = 0;
         for (uint32_t smp = 0; smp < p.spp; smp++) {
-            if (!p.rng_state) rng = seed_state(p.seed + (i * p.spp + smp) * (4ull * PHI));
+            if (!p.rng_state) rng = sample_seed(p, i, smp);
             V3 o = r.o, d = r.d;
             uint32_t k = 0, depth_left = p.depth;
             float term_r, term_g, term_b;

@@ -6,7 +6,8 @@
    configurations, every ray in its own window, states included;
 3. without emitters the segments and the written-back states are Scene.trace's;
 4. batch sizes around the wave and workgroup sizes, the device form against the host form, two streams at once and repeated calls,
-   spp = 4 against two calls of spp = 2, the scan engine on a tree deeper than the walk's stack;
+   spp = 4 against two calls of spp = 2, the scan engine on a tree deeper than the walk's stack; host-form calls of all five
+   caller-ray kinds interleaved on one scene, whose staging buffer they share, against each call on a fresh scene;
 5. both modes agree with rt_scene_trace within 5 sigma at 2^16 samples on a roughness-0 room, a room with glossy and mirror surfaces
    and that room inside an emissive sphere — where the composed recipe of examples/nee_rays.c (the control) does not;
 6. both modes have the lower variance for a small bright light;
@@ -280,6 +281,54 @@ def test_two_streams_repeated_calls_and_split_samples(ndev, oracle, dev):
             b = _nee(sc, rays, spp=2, max_bounces=3, rng_state=a["states"], mode=mode)
             assert np.array_equal(four["states"], b["states"])
             assert np.array_equal(four["segments"], a["segments"] + b["segments"]) and np.array_equal(four["shadow"], a["shadow"] + b["shadow"])
+
+
+def _arrays(out):
+    """The arrays of a host-form call's result (a tuple or a dict), the stats left out, as bytes."""
+    vals = out.values() if isinstance(out, dict) else out
+    return [np.ascontiguousarray(v).tobytes() for v in vals if isinstance(v, np.ndarray)]
+
+
+def test_interleaved_host_forms_share_one_staging_buffer(ndev):
+    """The host forms of all five caller-ray calls stage their arrays in ONE buffer of the scene, carved anew by every call.  Calls of
+    all kinds interleaved on one scene, with batch sizes that grow and shrink and optional arrays that come and go, each give the
+    bytes of the same call on a fresh scene of the same world: no stale offset, no missed upload, nothing left over from the call
+    before."""
+    sph, tri = D.lit_room()
+    rays = D.camera_rays(64, 48, 0.3, -0.1)[:3000]
+    n = len(rays)
+    assert n == 3000
+    o, d = R.od(rays)
+    tm, tx = rays["t_min"], rays["t_max"]
+    st = R.states(n, 2900)
+    listed = np.random.default_rng(2901).permutation(n)[:2000].astype(np.uint32)
+    step = {}                                          # the path step's results on the shared scene: the light sample's inputs
+
+    def bounce(sc):
+        out = sc.bounce(rays, st, active=listed, want_hits=True, want_next=True)
+        step.setdefault("out", out)
+        return out
+
+    calls = [
+        ("intersect 1000", lambda sc: sc.intersect(o[:1000], d[:1000], tm[:1000], tx[:1000])),
+        ("trace_nee 64", lambda sc: sc.trace_nee(o[:64], d[:64], tm[:64], tx[:64], spp=2, max_bounces=3, rng_state=st[:64])),
+        ("bounce 3000, listed", bounce),
+        ("direct 3000 on its hits", lambda sc: sc.direct(step["out"]["hits"], step["out"]["states"], active=step["out"]["next"])),
+        ("trace 257", lambda sc: sc.trace(o[:257], d[:257], tm[:257], tx[:257], spp=2, max_bounces=3, rng_state=st[:257])),
+        ("intersect 1000 again", lambda sc: sc.intersect(o[:1000], d[:1000], tm[:1000], tx[:1000])),
+        ("trace_nee 3000, seeded", lambda sc: sc.trace_nee(o, d, tm, tx, spp=1, max_bounces=2, seed=7, mode=LIGHT_ONLY)),
+        ("bounce 65, all, seeded", lambda sc: sc.bounce(rays[:65], None, seed=11)),
+        ("direct 700, all", lambda sc: sc.direct(step["out"]["hits"][:700], st[:700])),
+        ("trace 3000, seeded", lambda sc: sc.trace(o, d, tm, tx, spp=1, max_bounces=2, seed=5)),
+        ("any hit 63", lambda sc: sc.intersect(o[:63], d[:63], tm[:63], tx[:63], any_hit=True)),
+    ]
+    with rt.Scene(0, rt.World(sph, tri)) as sc:
+        assert sc.n_lights == 2
+        shared = [_arrays(call(sc)) for _, call in calls]
+    assert len(step["out"]["next"]) > 100 and len(shared[2]) == 5 and len(shared[3]) == 2
+    for (what, call), got in zip(calls, shared):
+        with rt.Scene(0, rt.World(sph, tri)) as fresh:
+            assert got == _arrays(call(fresh)), what
 
 
 def test_optional_outputs_and_as_given(ndev, oracle):
