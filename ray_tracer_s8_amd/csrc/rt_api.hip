@@ -222,16 +222,14 @@ struct rt_scene {
     };
     Ring rings[4];
     uint64_t ring_clock = 0;
-    // staging of the host-buffer entry points (grown on demand): the strips' bytes, their f32 twins, the running sums of
-    // rt_scene_render_tile_pass and the per-strip ray segments of the batched call (frame context); the planes of rt_scene_render_aov
-    // (36 bytes a pixel); the filter's scratch and the strips' inputs and outputs of rt_scene_denoise; rays and RNG states of
-    // rt_scene_camera_rays (64 bytes a record)
-    DevBuf d_out, d_outf, d_acc, d_cost, d_aov, d_dn, d_cam;
-    // ... and ONE buffer for the arrays of the caller-ray calls (rt_scene_intersect, _trace, _bounce, _direct, _trace_nee; Staging).
-    // They can share it: every such call holds ctx->mu and sc->mu from start to end, begins by collecting everything pending, and
-    // waits for its own downloads before it returns, so no two of them are ever in flight; and DevBuf::reserve frees (hipFree)
-    // only when it grows, which is before the call has enqueued anything.
-    DevBuf d_caller;
+    // staging of the tile host form (grown on demand): the strips' bytes, their f32 twins, the running sums of
+    // rt_scene_render_tile_pass and the per-strip ray segments of the batched call (frame context)
+    DevBuf d_out, d_outf, d_acc, d_cost;
+    // ... and ONE buffer for the arrays of the eight other host forms (rt_scene_intersect, _trace, _bounce, _direct, _trace_nee,
+    // _render_aov, _camera_rays, _denoise; Staging).  They can share it: every such call holds ctx->mu and sc->mu from start to end,
+    // begins by collecting everything pending, and waits for its own downloads before it returns, so no two of them are ever in
+    // flight; and DevBuf::reserve frees (hipFree) only when it grows, which is before the call has enqueued anything.
+    DevBuf d_stage;
     // HIP-event bookkeeping of launches not yet collected
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, free_ev;
     uint64_t primary_rays = 0;
@@ -556,7 +554,8 @@ struct StagedCall {
     }
 };
 
-// ---- what the caller-ray calls share (ray queries, path tracing, path steps, direct lighting, next-event estimation) ---------------
+// ---- what the caller-ray calls (ray queries, path tracing, path steps, direct lighting, next-event estimation) and the strip calls
+// (feature buffers, camera rays, denoiser) share ------------------------------------------------------------------------------------
 // A call's part of its launch's verbose line; empty, and nothing formatted, unless RT_VERBOSE is on.
 __attribute__((format(printf, 1, 2))) std::string vtext(const char* fmt, ...) {
     if (!dbg(DBG_VERBOSE)) return {};
@@ -580,26 +579,48 @@ void light_refs(const rt_scene* sc, P& p) {
     p.n_lights = sc->n_lights;
 }
 
-// Enqueue one caller-ray launch on `stream` (caller holds sc->mu, device current): persistent waves over `items` in workgroups of
-// `block`, with the plan's engine, slab test and LDS.  Every launch_* of these calls ends here with its own fields filled in; the
-// scene goes into the block here.  what: the kernel's name in the error of a plan that has none; head, tail: the verbose line on
-// either side of the occupancy (vtext); primary: added to the scene's primary rays.  d_zero: a device word zeroed on the stream
-// ahead of the launch (a step's *n_next), left alone when there is no slot for the launch.
+// Enqueue one launch of persistent waves over `items` in workgroups of `block` on `stream` (caller holds sc->mu, device current),
+// the block `p` complete.  The launches of the caller-ray calls, the feature buffers and the camera rays all end here.  what: the
+// kernel's name in the error of a plan that has none; head, tail: the verbose line on either side of the occupancy (vtext; head up to
+// and with its separator); primary: added to the scene's primary rays.  d_zero: a device word zeroed on the stream ahead of the
+// launch (a step's *n_next), left alone when there is no slot for the launch.
+template <class P>
+int launch_persistent(rt_scene* sc, int engine, size_t lds, uint32_t block, void (*kern)(const P), const char* what, const P& p,
+                      uint64_t items, const std::string& head, const std::string& tail, uint64_t primary, hipStream_t stream,
+                      void* d_zero = nullptr) {
+    if (!kern) return fail(RT_ERR_HIP, std::string("no ") + what + " kernel for this plan");
+    Grid g;
+    int rc = persistent_blocks(sc, kern, block, lds, items, g);
+    if (rc || (d_zero && (rc = check_slot(sc)))) return rc;
+    if (dbg(DBG_VERBOSE)) fprintf(stderr, "[rt] %sworkgroups/CU %d  %s\n", head.c_str(), g.per_cu, tail.c_str());
+    if (d_zero) HIPCHK(hipMemsetAsync(d_zero, 0, sizeof(uint32_t), stream));
+    if ((rc = enqueue(sc, stream, kern, g.blocks, block, lds, p))) return rc;
+    sc->primary_rays += primary;
+    sc->last_engine = (uint32_t)engine;
+    sc->last_form = 0;
+    return RT_OK;
+}
+
+// One caller-ray launch: the scene goes into the block (with the plan's slab test), then launch_persistent with the plan's engine
+// and LDS.  Every launch_* of these calls ends here with its own fields filled in.
 template <class P>
 int launch_rays(rt_scene* sc, const rtplan::QueryPlan& qp, uint32_t block, void (*kern)(const P), const char* what, P& p, uint64_t items,
                 const std::string& head, const std::string& tail, uint64_t primary, hipStream_t stream, void* d_zero = nullptr) {
-    if (!kern) return fail(RT_ERR_HIP, std::string("no ") + what + " kernel for this plan");
     scene_refs(sc, qp.full_chain, p);
-    Grid g;
-    int rc = persistent_blocks(sc, kern, block, qp.lds, items, g);
-    if (rc || (d_zero && (rc = check_slot(sc)))) return rc;
-    if (dbg(DBG_VERBOSE)) fprintf(stderr, "[rt] %s  workgroups/CU %d  %s\n", head.c_str(), g.per_cu, tail.c_str());
-    if (d_zero) HIPCHK(hipMemsetAsync(d_zero, 0, sizeof(uint32_t), stream));
-    if ((rc = enqueue(sc, stream, kern, g.blocks, block, qp.lds, p))) return rc;
-    sc->primary_rays += primary;
-    sc->last_engine = (uint32_t)qp.engine;
-    sc->last_form = 0;
-    return RT_OK;
+    return launch_persistent(sc, qp.engine, qp.lds, block, kern, what, p, items, head, tail, primary, stream, d_zero);
+}
+
+// The frame of a strip call into a parameter block that has the fields (AParams, CParams): the scene's camera, the request's ray
+// interval and image size, the job's sample count and the call's first sample.
+template <class P>
+void frame_refs(const rt_scene* sc, const rt_tile_request& rq, uint32_t begin, P& p) {
+    rtplan::fill_camera(rq, sc->has_pose ? &sc->pose : nullptr, p);
+    p.t_min = rq.t_min;
+    p.t_max = rq.t_max;
+    p.W = rq.width;
+    p.H = rq.height;
+    p.spp_all = rq.spp;
+    p.s_begin = begin;
 }
 
 // A device form: the scene's lock, the device, the caller's stream or the scene's own, then launch(stream).
@@ -621,27 +642,18 @@ struct HostForm {
     }
 };
 
-// The arrays of a host form, in the order they lie in the scene's one staging buffer (rt_scene::d_caller), each behind the one before.
-// An entry whose host pointer is NULL is an array the caller did not ask for: it is copied neither way and dev() gives nullptr.
+// The arrays of a host form, in the order they lie in the scene's one staging buffer (rt_scene::d_stage), laid out by
+// rtplan::stage_layout.  An entry whose host pointer is NULL is an array the caller did not ask for: it is copied neither way and
+// dev() gives nullptr — unless it is DEVICE, memory of the call's own on the device only.
 struct Staging {
-    enum : unsigned { UP = 1, DOWN = 2 };
-    struct Entry {
-        const void* host;
-        size_t bytes;
-        unsigned copy;           // UP: uploaded before the launch, DOWN: downloaded after it
-        size_t off;
-    };
+    enum : unsigned { UP = rtplan::STAGE_UP, DOWN = rtplan::STAGE_DOWN, DEVICE = rtplan::STAGE_DEVICE };
+    using Entry = rtplan::StageEntry;     // {host, bytes, copy}
     DevBuf& buf;
     std::vector<Entry> e;
-    size_t total = 0;
-    Staging(rt_scene* sc, std::initializer_list<Entry> entries) : buf(sc->d_caller), e(entries) {
-        for (Entry& x : e) {
-            x.off = total;
-            total += x.bytes;
-        }
-    }
+    const size_t total;
+    Staging(rt_scene* sc, std::vector<Entry> entries) : buf(sc->d_stage), e(std::move(entries)), total(rtplan::stage_layout(e.data(), e.size())) {}
     int reserve(const char* what) { return buf.reserve(total, what); }
-    char* dev(int k) const { return e[k].host ? buf.d + e[k].off : nullptr; }
+    char* dev(size_t k) const { return e[k].present() ? buf.d + e[k].off : nullptr; }    // (after reserve)
     // the upload phase of `call`, and its download phase up to finish()
     int upload(StagedCall& call) const {
         for (int k = 0; k < (int)e.size(); k++)
@@ -924,7 +936,7 @@ static int rt_scene_destroy_impl(rt_scene* sc) {
     (void)hipFree(sc->d_leaf_of);
     (void)hipFree(sc->d_world_rank);
     (void)hipFree(sc->d_counters);
-    for (DevBuf* b : {&sc->d_out, &sc->d_outf, &sc->d_acc, &sc->d_cost, &sc->d_aov, &sc->d_dn, &sc->d_cam, &sc->d_caller}) b->release();
+    for (DevBuf* b : {&sc->d_out, &sc->d_outf, &sc->d_acc, &sc->d_cost, &sc->d_stage}) b->release();
     delete sc;
     g_live_scenes.fetch_sub(1);
     return RT_OK;
@@ -972,17 +984,16 @@ static int rt_scene_render_tiles_device_impl(rt_scene* sc, const rt_tile_request
     if ((rc = check_array(d_out_rgb, n, "d_out_rgb"))) return rc;
     if (out_len_each < rt_tile_bytes(&rqs[0])) return fail(RT_ERR_BUFFER_TOO_SMALL, "out_len < (H/div)*W*3");
     if (pass && (rc = check_pass(rqs, n, *pass))) return rc;
-    std::lock_guard<std::mutex> lk(sc->mu);
-    HIPCHK(hipSetDevice(sc->ctx->dev));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream;
-    for (uint32_t i0 = 0; i0 < n; i0 += rtk::MAX_BATCH) {
-        uint32_t m = std::min<uint32_t>(rtk::MAX_BATCH, n - i0);
-        Pass part = {};
-        if (pass) part = {pass->begin, pass->end, pass->d_acc + i0};
-        rc = launch_batch(sc, rqs + i0, m, d_out_rgb + i0, d_out_f32 ? d_out_f32 + i0 : nullptr, st, nullptr, pass ? &part : nullptr);
-        if (rc) return rc;
-    }
-    return RT_OK;
+    return device_form(sc, hip_stream, [&](hipStream_t st) -> int {
+        for (uint32_t i0 = 0; i0 < n; i0 += rtk::MAX_BATCH) {
+            uint32_t m = std::min<uint32_t>(rtk::MAX_BATCH, n - i0);
+            Pass part = {};
+            if (pass) part = {pass->begin, pass->end, pass->d_acc + i0};
+            int rc = launch_batch(sc, rqs + i0, m, d_out_rgb + i0, d_out_f32 ? d_out_f32 + i0 : nullptr, st, nullptr, pass ? &part : nullptr);
+            if (rc) return rc;
+        }
+        return RT_OK;
+    });
 }
 
 static int rt_scene_render_tile_device_impl(rt_scene* sc, const rt_tile_request* rq, void* d_out_rgb, size_t out_len,
@@ -1015,11 +1026,9 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
     bool want_f32 = false;
     if (out_f32)
         for (uint32_t i = 0; i < n; i++) want_f32 |= out_f32[i] != nullptr;
-    std::lock_guard<std::mutex> dl(sc->ctx->mu);
-    std::lock_guard<std::mutex> lk(sc->mu);
-    HIPCHK(hipSetDevice(sc->ctx->dev));
+    HostForm hf(sc);
     hipStream_t st = sc->ctx->stream;
-    if ((rc = sc->d_out.reserve(need * n, "strips")) || (want_f32 && (rc = sc->d_outf.reserve(need * n * sizeof(float), "strips f32"))) ||
+    if ((rc = hf.device()) || (rc = sc->d_out.reserve(need * n, "strips")) || (want_f32 && (rc = sc->d_outf.reserve(need * n * sizeof(float), "strips f32"))) ||
         (pass && (rc = sc->d_acc.reserve(need * n * sizeof(float), "running sums"))))
         return rc;
     // per-strip costs: one block of COST_COPIES x MAX_BATCH counters per launch group of the call
@@ -1166,7 +1175,7 @@ static int launch_query(rt_scene* sc, const void* d_rays, uint32_t n, uint32_t m
     p.hits = (uint4*)d_hits;
     p.n = n;
     return launch_rays(sc, qp, rtplan::QUERY_BLOCK, rtk::query_kernel(qp.engine, qp.scan_mode, mode == RT_QUERY_ANY), "query", p, n,
-                       vtext("query: engine %d  scan mode %d  %s  lds %zu B", qp.engine, qp.scan_mode,
+                       vtext("query: engine %d  scan mode %d  %s  lds %zu B  ", qp.engine, qp.scan_mode,
                              mode == RT_QUERY_ANY ? "any" : "closest", qp.lds),
                        vtext("rays %u", n), n, stream);
 }
@@ -1224,7 +1233,7 @@ static int launch_trace(rt_scene* sc, const rt_trace_request* rq, const void* d_
     material_refs(sc, p);
     return launch_rays(sc, rtplan::QueryPlan{tp.engine, tp.scan_mode, tp.full_chain, tp.lds}, tp.block,
                        rtk::trace_kernel(tp.engine, tp.scan_mode), "trace", p, n,
-                       vtext("trace: engine %d  scan mode %d  block %u  lds %zu B (path %s)", tp.engine, tp.scan_mode, tp.block, tp.lds,
+                       vtext("trace: engine %d  scan mode %d  block %u  lds %zu B (path %s)  ", tp.engine, tp.scan_mode, tp.block, tp.lds,
                              tp.path32 ? "u32" : "u16"),
                        vtext("rays %u  spp %u  bounces %u", n, rq->spp, rq->max_bounces), (uint64_t)n * rq->spp, stream);
 }
@@ -1290,7 +1299,7 @@ static int launch_bounce(rt_scene* sc, const rt_bounce_request* rq, void* d_rays
     p.seed_states = rq->seed_states;
     material_refs(sc, p);
     return launch_rays(sc, qp, rtplan::QUERY_BLOCK, rtk::bounce_kernel(qp.engine, qp.scan_mode), "bounce", p, std::max<uint32_t>(count, 1u),
-                       vtext("bounce: engine %d  scan mode %d  lds %zu B", qp.engine, qp.scan_mode, qp.lds),
+                       vtext("bounce: engine %d  scan mode %d  lds %zu B  ", qp.engine, qp.scan_mode, qp.lds),
                        vtext("rays %u  listed %s%u", n, d_n_active ? "<= " : "", count), 0, stream, d_n_next);
 }
 
@@ -1370,7 +1379,7 @@ static int launch_direct(rt_scene* sc, const rt_direct_request* rq, const void* 
     p.t_max = rq->t_max;
     return launch_rays(sc, qp, rtplan::QUERY_BLOCK, rtk::direct_kernel(qp.engine, qp.scan_mode), "direct-lighting", p,
                        std::max<uint32_t>(count, 1u),
-                       vtext("direct: engine %d  scan mode %d  lds %zu B", qp.engine, qp.scan_mode, qp.lds),
+                       vtext("direct: engine %d  scan mode %d  lds %zu B  ", qp.engine, qp.scan_mode, qp.lds),
                        vtext("records %u  listed %s%u  lights %u", n, d_n_active ? "<= " : "", count, sc->n_lights), 0, stream);
 }
 
@@ -1444,7 +1453,7 @@ static int launch_nee(rt_scene* sc, const rt_nee_request* rq, const void* d_rays
     material_refs(sc, p);
     light_refs(sc, p);
     return launch_rays(sc, qp, rtplan::QUERY_BLOCK, rtk::nee_kernel(qp.engine, qp.scan_mode), "next-event-estimation", p, n,
-                       vtext("nee: engine %d  scan mode %d  lds %zu B", qp.engine, qp.scan_mode, qp.lds),
+                       vtext("nee: engine %d  scan mode %d  lds %zu B  ", qp.engine, qp.scan_mode, qp.lds),
                        vtext("rays %u  spp %u  bounces %u  mode %u  lights %u", n, rq->spp, rq->max_bounces, rq->mode, sc->n_lights),
                        (uint64_t)n * rq->spp, stream);
 }
@@ -1479,6 +1488,15 @@ static uint32_t aov_mask(const rt_aov_planes& pl) {
            (pl.hits ? rtk::AOV_HITS : 0u) | (pl.index ? rtk::AOV_INDEX : 0u);
 }
 
+// Every entry of a call's plane array has the set of planes of entry 0 (*mask, by mask_of); name: the array's in the error text.
+static int check_plane_sets(const rt_aov_planes* planes, uint32_t n, uint32_t (*mask_of)(const rt_aov_planes&), const char* name,
+                            uint32_t* mask) {
+    *mask = mask_of(planes[0]);
+    for (uint32_t i = 1; i < n; i++)
+        if (mask_of(planes[i]) != *mask) return fail(RT_ERR_BAD_ARG, std::string("the entries of ") + name + " differ in their set of planes");
+    return RT_OK;
+}
+
 // The requests and planes of an AOV call (a batch of strips of one frame); *mask: the AOV_* bits of the planes every entry has.
 static int check_aov(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint32_t begin, uint32_t end, const rt_aov_planes* planes,
                      uint32_t* mask) {
@@ -1487,11 +1505,8 @@ static int check_aov(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint3
     if (rc) return rc;
     if ((rc = check_samples(begin, end, rqs[0].spp))) return rc;
     if (!planes) return fail(RT_ERR_BAD_ARG, "planes is NULL");
-    *mask = aov_mask(planes[0]);
-    if (*mask == 0) return fail(RT_ERR_BAD_ARG, "every plane is NULL");
-    for (uint32_t i = 1; i < n; i++)
-        if (aov_mask(planes[i]) != *mask) return fail(RT_ERR_BAD_ARG, "the entries of d_planes differ in their set of planes");
-    return RT_OK;
+    if (aov_mask(planes[0]) == 0) return fail(RT_ERR_BAD_ARG, "every plane is NULL");
+    return check_plane_sets(planes, n, aov_mask, "d_planes", mask);
 }
 
 // Enqueue the AOV launches of n strips (one per MAX_BATCH strips) on `stream` (caller holds sc->mu, device current): persistent waves
@@ -1499,20 +1514,12 @@ static int check_aov(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint3
 static int launch_aov(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint32_t begin, uint32_t end, const rt_aov_planes* d_planes,
                       uint32_t mask, hipStream_t stream) {
     const rtplan::QueryPlan qp = rtplan::plan_query(sc->shape, rqs[0].flags);
-    const rtk::AovFn kern = rtk::aov_kernel(qp.engine, qp.scan_mode);
-    if (!kern) return fail(RT_ERR_HIP, "no AOV kernel for this plan");
     const rt_tile_request& rq = rqs[0];
     const uint32_t hs = rq.height / rq.divisions;
     rtk::AParams p;
     std::memset(&p, 0, sizeof p);
-    rtplan::fill_camera(rq, sc->has_pose ? &sc->pose : nullptr, p);
-    p.t_min = rq.t_min;
-    p.t_max = rq.t_max;
-    p.W = rq.width;
-    p.H = rq.height;
+    frame_refs(sc, rq, begin, p);
     p.npix = hs * rq.width;
-    p.spp_all = rq.spp;
-    p.s_begin = begin;
     p.s_end = end;
     p.planes = mask;
     scene_refs(sc, qp.full_chain, p);
@@ -1531,16 +1538,11 @@ static int launch_aov(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint
             sd.index = pl.index;
             sd.y0 = hs * rqs[i0 + i].division_no;
         }
-        Grid g;
-        int rc = persistent_blocks(sc, kern, rtplan::QUERY_BLOCK, qp.lds, (uint64_t)p.npix * m, g);
+        int rc = launch_persistent(sc, qp.engine, qp.lds, rtplan::QUERY_BLOCK, rtk::aov_kernel(qp.engine, qp.scan_mode), "AOV", p,
+                                   (uint64_t)p.npix * m, vtext("aov: engine %d  scan mode %d  lds %zu B  ", qp.engine, qp.scan_mode, qp.lds),
+                                   vtext("strips %u  pixels %u  samples [%u, %u)  planes %#x", m, p.npix, begin, end, mask),
+                                   (uint64_t)p.npix * (end - begin) * m, stream);
         if (rc) return rc;
-        if (dbg(DBG_VERBOSE))
-            fprintf(stderr, "[rt] aov: engine %d  scan mode %d  lds %zu B  workgroups/CU %d  strips %u  pixels %u  samples [%u, %u)  planes %#x\n",
-                    qp.engine, qp.scan_mode, qp.lds, g.per_cu, m, p.npix, begin, end, mask);
-        if ((rc = enqueue(sc, stream, kern, g.blocks, rtplan::QUERY_BLOCK, qp.lds, p))) return rc;
-        sc->primary_rays += (uint64_t)p.npix * (end - begin) * m;
-        sc->last_engine = (uint32_t)qp.engine;
-        sc->last_form = 0;
     }
     return RT_OK;
 }
@@ -1550,9 +1552,7 @@ static int rt_scene_render_aovs_device_impl(rt_scene* sc, const rt_tile_request*
     uint32_t mask = 0;
     int rc = check_aov(sc, rqs, n, begin, end, d_planes, &mask);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(sc->mu);
-    HIPCHK(hipSetDevice(sc->ctx->dev));
-    return launch_aov(sc, rqs, n, begin, end, d_planes, mask, hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream);
+    return device_form(sc, hip_stream, [&](hipStream_t st) { return launch_aov(sc, rqs, n, begin, end, d_planes, mask, st); });
 }
 
 static int rt_scene_render_aov_impl(rt_scene* sc, const rt_tile_request* rq, uint32_t begin, uint32_t end, const rt_aov_planes* planes,
@@ -1560,39 +1560,22 @@ static int rt_scene_render_aov_impl(rt_scene* sc, const rt_tile_request* rq, uin
     uint32_t mask = 0;
     int rc = check_aov(sc, rq, 1, begin, end, planes, &mask);
     if (rc) return rc;
-    std::lock_guard<std::mutex> dl(sc->ctx->mu);
-    std::lock_guard<std::mutex> lk(sc->mu);
-    HIPCHK(hipSetDevice(sc->ctx->dev));
-    // one device buffer: albedo and normal (12 B), depth, hits and index (4 B) per pixel
+    HostForm hf(sc);
+    // albedo and normal (12 B), depth, hits and index (4 B) per pixel; a call from sample 0 reads no plane (the caller's buffers may be
+    // uninitialised), a later one adds to what it is given
     const size_t npix = (size_t)(rq->height / rq->divisions) * rq->width;
     const size_t v3_b = npix * 3 * sizeof(float), s_b = npix * sizeof(uint32_t);
-    if ((rc = sc->d_aov.reserve(2 * v3_b + 3 * s_b, "AOV planes"))) return rc;
-    char* const d = sc->d_aov.d;
-    // the device planes the caller asked for, and their sizes
-    struct Plane {
-        void* host;
-        char* dev;
-        size_t bytes;
-    };
-    const Plane pl[5] = {{planes->albedo, d, v3_b},
-                         {planes->normal, d + v3_b, v3_b},
-                         {planes->depth, d + 2 * v3_b, s_b},
-                         {planes->hits, d + 2 * v3_b + s_b, s_b},
-                         {planes->index, d + 2 * v3_b + 2 * s_b, s_b}};
-    rt_aov_planes dp = {};
-    dp.albedo = planes->albedo ? (float*)pl[0].dev : nullptr;
-    dp.normal = planes->normal ? (float*)pl[1].dev : nullptr;
-    dp.depth = planes->depth ? (float*)pl[2].dev : nullptr;
-    dp.hits = planes->hits ? (uint32_t*)pl[3].dev : nullptr;
-    dp.index = planes->index ? (uint32_t*)pl[4].dev : nullptr;
+    const unsigned copy = (begin > 0 ? Staging::UP : 0u) | Staging::DOWN;
+    Staging s(sc, {{planes->albedo, v3_b, copy}, {planes->normal, v3_b, copy}, {planes->depth, s_b, copy}, {planes->hits, s_b, copy},
+                   {planes->index, s_b, copy}});
     StagedCall call(sc);
-    if ((rc = call.begin())) return rc;
-    if (begin > 0)          // (a call from sample 0 reads no plane: the caller's buffers may be uninitialised)
-        for (const Plane& q : pl)
-            if (q.host) HIPCHK(hipMemcpyAsync(q.dev, q.host, q.bytes, hipMemcpyHostToDevice, call.st));
-    if ((rc = call.uploads_done()) || (rc = launch_aov(sc, rq, 1, begin, end, &dp, mask, call.st)) || (rc = call.kernels_done())) return rc;
-    for (const Plane& q : pl)
-        if (q.host) HIPCHK(hipMemcpyAsync(q.host, q.dev, q.bytes, hipMemcpyDeviceToHost, call.st));
+    auto launch = [&] {
+        const rt_aov_planes dp = {(float*)s.dev(0), (float*)s.dev(1), (float*)s.dev(2), (uint32_t*)s.dev(3), (uint32_t*)s.dev(4)};
+        return launch_aov(sc, rq, 1, begin, end, &dp, mask, call.st);
+    };
+    if ((rc = hf.device()) || (rc = s.reserve("AOV planes")) || (rc = call.begin()) || (rc = s.upload(call)) || (rc = launch()) ||
+        (rc = s.download(call)))
+        return rc;
     return call.finish(stats);
 }
 
@@ -1634,64 +1617,40 @@ static int check_camera_rays(rt_scene* sc, const rt_tile_request* rq, uint32_t b
 // Enqueue the camera-ray launch of one strip on `stream` (caller holds sc->mu, device current): persistent waves over the records.
 static int launch_camera_rays(rt_scene* sc, const rt_tile_request& rq, uint32_t begin, uint32_t end, void* d_rays, void* d_state,
                               hipStream_t stream) {
-    const rtk::CameraFn kern = rtk::camera_rays_kernel(d_state != nullptr);
     const uint32_t hs = rq.height / rq.divisions;
     rtk::CParams p;
     std::memset(&p, 0, sizeof p);
-    rtplan::fill_camera(rq, sc->has_pose ? &sc->pose : nullptr, p);
-    p.t_min = rq.t_min;
-    p.t_max = rq.t_max;
-    p.W = rq.width;
-    p.H = rq.height;
+    frame_refs(sc, rq, begin, p);
     p.y0 = hs * rq.division_no;
-    p.spp_all = rq.spp;
-    p.s_begin = begin;
     p.n_smp = end - begin;
     p.total = (uint64_t)hs * rq.width * (end - begin);
     p.seed = rq.seed;
     p.rays = (float4*)d_rays;
     p.state = (ulonglong2*)d_state;
-    Grid g;
-    int rc = persistent_blocks(sc, kern, rtplan::QUERY_BLOCK, 0, p.total, g);
-    if (rc) return rc;
-    if (dbg(DBG_VERBOSE))
-        fprintf(stderr, "[rt] camera rays: workgroups/CU %d  records %llu  samples [%u, %u)  states %d\n", g.per_cu,
-                (unsigned long long)p.total, begin, end, d_state ? 1 : 0);
-    if ((rc = enqueue(sc, stream, kern, g.blocks, rtplan::QUERY_BLOCK, 0, p))) return rc;
-    sc->primary_rays += p.total;
-    sc->last_engine = 0;
-    sc->last_form = 0;
-    return RT_OK;
+    return launch_persistent(sc, 0, 0, rtplan::QUERY_BLOCK, rtk::camera_rays_kernel(d_state != nullptr), "camera-ray", p, p.total,
+                             vtext("camera rays: "),
+                             vtext("records %llu  samples [%u, %u)  states %d", (unsigned long long)p.total, begin, end, d_state ? 1 : 0),
+                             p.total, stream);
 }
 
 static int rt_scene_camera_rays_device_impl(rt_scene* sc, const rt_tile_request* rq, uint32_t begin, uint32_t end, void* d_rays,
                                             void* d_state, void* hip_stream) {
     int rc = check_camera_rays(sc, rq, begin, end, d_rays);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(sc->mu);
-    HIPCHK(hipSetDevice(sc->ctx->dev));
-    return launch_camera_rays(sc, *rq, begin, end, d_rays, d_state, hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream);
+    return device_form(sc, hip_stream, [&](hipStream_t st) { return launch_camera_rays(sc, *rq, begin, end, d_rays, d_state, st); });
 }
 
 static int rt_scene_camera_rays_impl(rt_scene* sc, const rt_tile_request* rq, uint32_t begin, uint32_t end, rt_ray* rays,
                                      uint64_t* rng_state, rt_tile_stats* stats) {
     int rc = check_camera_rays(sc, rq, begin, end, rays);
     if (rc) return rc;
-    std::lock_guard<std::mutex> dl(sc->ctx->mu);
-    std::lock_guard<std::mutex> lk(sc->mu);
-    HIPCHK(hipSetDevice(sc->ctx->dev));
-    // one device buffer: the rays, then the states (32 B each per record)
+    HostForm hf(sc);
     const size_t n = (size_t)(rq->height / rq->divisions) * rq->width * (end - begin);
-    const size_t ray_b = n * sizeof(rt_ray), state_b = rng_state ? n * 4 * sizeof(uint64_t) : 0;
-    if ((rc = sc->d_cam.reserve(ray_b + state_b, "camera rays"))) return rc;
-    char* const d_rays = sc->d_cam.d;
-    char* const d_state = rng_state ? d_rays + ray_b : nullptr;
+    Staging s(sc, {{rays, n * sizeof(rt_ray), Staging::DOWN}, {rng_state, n * 4 * sizeof(uint64_t), Staging::DOWN}});
     StagedCall call(sc);
-    if ((rc = call.begin()) || (rc = call.uploads_done()) || (rc = launch_camera_rays(sc, *rq, begin, end, d_rays, d_state, call.st)) ||
-        (rc = call.kernels_done()))
+    if ((rc = hf.device()) || (rc = s.reserve("camera rays")) || (rc = call.begin()) || (rc = s.upload(call)) ||
+        (rc = launch_camera_rays(sc, *rq, begin, end, s.dev(0), s.dev(1), call.st)) || (rc = s.download(call)))
         return rc;
-    HIPCHK(hipMemcpyAsync(rays, d_rays, ray_b, hipMemcpyDeviceToHost, call.st));
-    if (rng_state) HIPCHK(hipMemcpyAsync(rng_state, d_state, state_b, hipMemcpyDeviceToHost, call.st));
     return call.finish(stats);
 }
 
@@ -1721,9 +1680,7 @@ static int check_denoise(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, c
     if (!dq) return fail(RT_ERR_BAD_ARG, "denoise request is NULL");
     if ((rc = check_array(acc, n, "accum"))) return rc;
     if (!planes) return fail(RT_ERR_BAD_ARG, "planes is NULL");
-    *mask = dn_mask(planes[0]);
-    for (uint32_t i = 1; i < n; i++)
-        if (dn_mask(planes[i]) != *mask) return fail(RT_ERR_BAD_ARG, "the entries of planes differ in their set of planes");
+    if ((rc = check_plane_sets(planes, n, dn_mask, "planes", mask))) return rc;
     if ((*mask & rtdn::P_DEPTH) && !(*mask & rtdn::P_HITS)) return fail(RT_ERR_BAD_ARG, "the depth plane needs the hits plane");
     if (!rgb && !f32 && !lin) return fail(RT_ERR_BAD_ARG, "no output");
     if ((rc = check_out_array(rgb, n, "out_rgb")) || (rc = check_out_array(f32, n, "out_f32")) ||
@@ -1854,10 +1811,9 @@ static int rt_scene_denoise_device_impl(rt_scene* sc, const rt_tile_request* rqs
     if (!d_scratch) return fail(RT_ERR_BAD_ARG, "d_scratch is NULL");
     if (scratch_bytes < rtplan::plan_denoise(rqs[0].width, R, 0, false).scratch_bytes)
         return fail(RT_ERR_BAD_ARG, "scratch_bytes < rt_denoise_scratch_bytes(W, R)");
-    std::lock_guard<std::mutex> lk(sc->mu);
-    HIPCHK(hipSetDevice(sc->ctx->dev));
-    return launch_denoise(sc, rqs, n, *dq, mask, d_acc, d_planes, d_rgb, d_f32, d_lin, (char*)d_scratch,
-                          hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream);
+    return device_form(sc, hip_stream, [&](hipStream_t st) {
+        return launch_denoise(sc, rqs, n, *dq, mask, d_acc, d_planes, d_rgb, d_f32, d_lin, (char*)d_scratch, st);
+    });
 }
 
 static int rt_scene_denoise_impl(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, const rt_denoise_request* dq,
@@ -1867,65 +1823,29 @@ static int rt_scene_denoise_impl(rt_scene* sc, const rt_tile_request* rqs, uint3
     int rc = check_denoise(sc, rqs, n, dq, (const void* const*)acc, planes, (const void* const*)rgb, out_len,
                            (const void* const*)f32, (const void* const*)lin, &mask);
     if (rc) return rc;
-    std::lock_guard<std::mutex> dl(sc->ctx->mu);
-    std::lock_guard<std::mutex> lk(sc->mu);
-    HIPCHK(hipSetDevice(sc->ctx->dev));
-    // one device buffer: the scratch, then per strip its inputs and outputs, each region 256-B aligned
-    const size_t npix = (size_t)(rqs[0].height / rqs[0].divisions) * rqs[0].width;
-    const size_t v3 = npix * 3 * sizeof(float), s1 = npix * sizeof(uint32_t), u8 = npix * 3;
-    const size_t scratch = rtplan::plan_denoise(rqs[0].width, (uint32_t)(npix / rqs[0].width) * n, 0, false).scratch_bytes;
-    struct Region {
-        const void* host_in;     // uploaded
-        void* host_out;          // downloaded
-        size_t bytes;
-        size_t off;
-    };
-    std::vector<Region> regs;
-    std::vector<const void*> d_acc(n);
-    std::vector<rt_aov_planes> d_pl(n);
-    std::vector<void*> d_rgb(n), d_f32(n), d_lin(n);
-    size_t top = rtplan::dn_align(scratch);
-    auto add = [&](const void* in, void* out, size_t bytes) {
-        regs.push_back({in, out, bytes, top});
-        top += rtplan::dn_align(bytes);
-        return regs.size() - 1;
-    };
-    std::vector<size_t> ia(n), ip(n * 4), io(n * 3);
-    for (uint32_t i = 0; i < n; i++) {
-        ia[i] = add(acc[i], nullptr, v3);
-        ip[i * 4 + 0] = planes[i].albedo ? add(planes[i].albedo, nullptr, v3) : SIZE_MAX;
-        ip[i * 4 + 1] = planes[i].normal ? add(planes[i].normal, nullptr, v3) : SIZE_MAX;
-        ip[i * 4 + 2] = planes[i].depth ? add(planes[i].depth, nullptr, s1) : SIZE_MAX;
-        ip[i * 4 + 3] = planes[i].hits ? add(planes[i].hits, nullptr, s1) : SIZE_MAX;
-        io[i * 3 + 0] = rgb ? add(nullptr, rgb[i], u8) : SIZE_MAX;
-        io[i * 3 + 1] = f32 ? add(nullptr, f32[i], v3) : SIZE_MAX;
-        io[i * 3 + 2] = lin ? add(nullptr, lin[i], v3) : SIZE_MAX;
-    }
-    if ((rc = sc->d_dn.reserve(top, "denoise staging"))) return rc;
-    char* const d = sc->d_dn.d;
-    auto dev = [&](size_t r) -> void* { return r == SIZE_MAX ? nullptr : d + regs[r].off; };
-    for (uint32_t i = 0; i < n; i++) {
-        d_acc[i] = dev(ia[i]);
-        d_pl[i] = {};
-        d_pl[i].albedo = (float*)dev(ip[i * 4 + 0]);
-        d_pl[i].normal = (float*)dev(ip[i * 4 + 1]);
-        d_pl[i].depth = (float*)dev(ip[i * 4 + 2]);
-        d_pl[i].hits = (uint32_t*)dev(ip[i * 4 + 3]);
-        d_rgb[i] = dev(io[i * 3 + 0]);
-        d_f32[i] = dev(io[i * 3 + 1]);
-        d_lin[i] = dev(io[i * 3 + 2]);
-    }
+    HostForm hf(sc);
+    Staging s(sc, rtplan::dn_stage_list(rqs[0], n, acc, planes, rgb, f32, lin));
     StagedCall call(sc);
-    if ((rc = call.begin())) return rc;
-    for (const Region& r : regs)
-        if (r.host_in) HIPCHK(hipMemcpyAsync(d + r.off, r.host_in, r.bytes, hipMemcpyHostToDevice, call.st));
-    if ((rc = call.uploads_done()) ||
-        (rc = launch_denoise(sc, rqs, n, *dq, mask, d_acc.data(), d_pl.data(), rgb ? d_rgb.data() : nullptr, f32 ? d_f32.data() : nullptr,
-                             lin ? d_lin.data() : nullptr, d, call.st)) ||
-        (rc = call.kernels_done()))
+    // the device side of every strip, as the device form takes it
+    auto launch = [&] {
+        std::vector<const void*> d_acc(n);
+        std::vector<rt_aov_planes> d_pl(n);
+        std::vector<void*> d_rgb(n), d_f32(n), d_lin(n);
+        for (uint32_t i = 0; i < n; i++) {
+            auto dev = [&](int k) { return s.dev(1 + (size_t)rtplan::DN_STAGE_STRIP * i + k); };
+            d_acc[i] = dev(rtplan::DN_ACCUM);
+            d_pl[i] = {(float*)dev(rtplan::DN_ALBEDO), (float*)dev(rtplan::DN_NORMAL), (float*)dev(rtplan::DN_DEPTH),
+                       (uint32_t*)dev(rtplan::DN_HITS), nullptr};
+            d_rgb[i] = dev(rtplan::DN_RGB);
+            d_f32[i] = dev(rtplan::DN_F32);
+            d_lin[i] = dev(rtplan::DN_LIN);
+        }
+        return launch_denoise(sc, rqs, n, *dq, mask, d_acc.data(), d_pl.data(), rgb ? d_rgb.data() : nullptr, f32 ? d_f32.data() : nullptr,
+                              lin ? d_lin.data() : nullptr, s.dev(0), call.st);
+    };
+    if ((rc = hf.device()) || (rc = s.reserve("denoise staging")) || (rc = call.begin()) || (rc = s.upload(call)) || (rc = launch()) ||
+        (rc = s.download(call)))
         return rc;
-    for (const Region& r : regs)
-        if (r.host_out) HIPCHK(hipMemcpyAsync(r.host_out, d + r.off, r.bytes, hipMemcpyDeviceToHost, call.st));
     return call.finish(stats);
 }
 

@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #include "rt_consts.h"
 #include "rt_tile.h"
@@ -621,6 +622,50 @@ inline DenoisePlan plan_denoise(uint32_t W, uint32_t R, uint32_t iterations, boo
         }
     }
     return p;
+}
+
+// ---- The staging of a host form (rt_api.hip Staging): the call's arrays in the order they lie in the scene's one staging buffer,
+// each at a multiple of DN_ALIGN behind the one before.  An entry is present when it has a host side or is STAGE_DEVICE (device
+// memory only: the filter's scratch); an absent one, an optional array the caller did not ask for, takes no room.
+enum : unsigned { STAGE_UP = 1, STAGE_DOWN = 2, STAGE_DEVICE = 4 };
+struct StageEntry {
+    const void* host;
+    size_t bytes;
+    unsigned copy;           // STAGE_UP: uploaded before the launch, STAGE_DOWN: downloaded after it
+    size_t off;              // stage_layout's
+    bool present() const { return host || (copy & STAGE_DEVICE); }
+};
+// Sets every entry's offset; returns the bytes the list takes.
+inline size_t stage_layout(StageEntry* e, size_t n) {
+    size_t top = 0;
+    for (size_t k = 0; k < n; k++) {
+        e[k].off = top;
+        if (e[k].present()) top += dn_align(e[k].bytes);
+    }
+    return top;
+}
+
+// The list of rt_scene_denoise: the scratch, then DN_STAGE_STRIP entries per strip (entry k of strip i is 1 + DN_STAGE_STRIP * i + k):
+// its running sum, its guide planes and its outputs.  rgb, f32, lin: NULL or n arrays.
+enum { DN_ACCUM, DN_ALBEDO, DN_NORMAL, DN_DEPTH, DN_HITS, DN_RGB, DN_F32, DN_LIN, DN_STAGE_STRIP };
+inline std::vector<StageEntry> dn_stage_list(const rt_tile_request& rq, uint32_t n, const float* const* acc, const rt_aov_planes* planes,
+                                             uint8_t* const* rgb, float* const* f32, float* const* lin) {
+    const uint32_t Hs = rq.height / rq.divisions;
+    const size_t npix = (size_t)Hs * rq.width, v3 = npix * 3 * sizeof(float), s1 = npix * sizeof(uint32_t), u8 = npix * 3;
+    std::vector<StageEntry> e;
+    e.reserve(1 + (size_t)DN_STAGE_STRIP * n);
+    e.push_back({nullptr, plan_denoise(rq.width, Hs * n, 0, false).scratch_bytes, STAGE_DEVICE, 0});
+    for (uint32_t i = 0; i < n; i++) {
+        e.push_back({acc[i], v3, STAGE_UP, 0});
+        e.push_back({planes[i].albedo, v3, STAGE_UP, 0});
+        e.push_back({planes[i].normal, v3, STAGE_UP, 0});
+        e.push_back({planes[i].depth, s1, STAGE_UP, 0});
+        e.push_back({planes[i].hits, s1, STAGE_UP, 0});
+        e.push_back({rgb ? rgb[i] : nullptr, u8, STAGE_DOWN, 0});
+        e.push_back({f32 ? f32[i] : nullptr, v3, STAGE_DOWN, 0});
+        e.push_back({lin ? lin[i] : nullptr, v3, STAGE_DOWN, 0});
+    }
+    return e;
 }
 
 }  // namespace rtplan

@@ -1,10 +1,12 @@
 // Test harness (CPU only, built by tests/test_launch_plan.py with g++ -ffp-contract=off): the launch plan of csrc/rt_plan.h — the
 // product's plan_launch / plan_queue — on hand-built scene shapes, requests and knobs.  The planner writes the kernel parameters
 // into any struct with rtk::KParams's scalar field names; Params below is that struct, and every value goes back to Python as
-// a double (exact for the u32 and f32 fields), named by plan_field_names().
+// a double (exact for the u32 and f32 fields), named by plan_field_names().  Also the staging layout of the host forms (stage_layout,
+// dn_stage_list), and with -DPLAN_HOST_MAIN a program that runs those (for the sanitizers).
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "rt_plan.h"
 
@@ -127,7 +129,100 @@ double plan_const(const char* name) {
     CONST(FIELD_MID_MIN_DENSITY) CONST(LT_CULL_MIN_DENSITY) CONST(TRAVERSE_MIN_PRIMS) CONST(N_ISECT)
     CONST(BLOCK) CONST(LTREE_BLOCK) CONST(TRAV_STACK) CONST(MAXL) CONST(MINL) CONST(MAXL_EXACT) CONST(MAXL_LTREE)
     CONST(MAXL_LTREE_MAX) CONST(LNODE_DW) CONST(SLOTS_MAX) CONST(STAGE_TILES) CONST(STAGE_TILE_BYTES) CONST(MAXC)
+    CONST(DN_ALIGN)
     return __builtin_nan("");
 }
 
+// The staging layout (rtplan::stage_layout) of n entries of bytes[k]; host[k] != 0: the entry has a host side, device_only[k] != 0: it
+// is STAGE_DEVICE.  off[k], present[k]: what the layout says of entry k; returns the total.
+uint64_t stage_layout(const uint64_t* bytes, const uint8_t* host, const uint8_t* device_only, uint32_t n, uint64_t* off, uint8_t* present) {
+    static const char side = 0;
+    std::vector<rtplan::StageEntry> e(n);
+    for (uint32_t k = 0; k < n; k++)
+        e[k] = {host[k] ? &side : nullptr, (size_t)bytes[k], device_only[k] ? rtplan::STAGE_DEVICE : rtplan::STAGE_UP, ~(size_t)0};
+    const size_t total = rtplan::stage_layout(e.data(), n);
+    for (uint32_t k = 0; k < n; k++) {
+        off[k] = e[k].off;
+        present[k] = e[k].present();
+    }
+    return total;
+}
+
+// The denoiser's list (rtplan::dn_stage_list) for n strips of a width x height frame in `divisions`, laid out.  planes: bit k set: the
+// strips have guide plane k (albedo, normal, depth, hits); outs: bit k set: output k is asked for (rgb, f32, linear).  bytes, off,
+// present: 1 + DN_STAGE_STRIP * n values each; returns the total.
+uint64_t stage_denoise(uint32_t width, uint32_t height, uint32_t divisions, uint32_t n, uint32_t planes, uint32_t outs, uint64_t* bytes,
+                       uint64_t* off, uint8_t* present) {
+    static float side = 0.f;
+    rt_tile_request rq;
+    std::memset(&rq, 0, sizeof rq);
+    rq.width = width;
+    rq.height = height;
+    rq.divisions = divisions;
+    const rt_aov_planes pl = {planes & 1 ? &side : nullptr, planes & 2 ? &side : nullptr, planes & 4 ? &side : nullptr,
+                              planes & 8 ? (uint32_t*)&side : nullptr, nullptr};
+    const std::vector<const float*> acc(n, &side);
+    const std::vector<rt_aov_planes> pls(n, pl);
+    const std::vector<uint8_t*> rgb(n, (uint8_t*)&side);
+    const std::vector<float*> f32(n, &side);
+    std::vector<rtplan::StageEntry> e = rtplan::dn_stage_list(rq, n, acc.data(), pls.data(), outs & 1 ? rgb.data() : nullptr,
+                                                              outs & 2 ? f32.data() : nullptr, outs & 4 ? f32.data() : nullptr);
+    const size_t total = rtplan::stage_layout(e.data(), e.size());
+    for (size_t k = 0; k < e.size(); k++) {
+        bytes[k] = e[k].bytes;
+        off[k] = e[k].off;
+        present[k] = e[k].present();
+    }
+    return total;
+}
+
+int stage_per_strip() { return rtplan::DN_STAGE_STRIP; }
+double stage_scratch_bytes(uint32_t width, uint32_t rows) { return (double)rtplan::plan_denoise(width, rows, 0, false).scratch_bytes; }
+
 }  // extern "C"
+
+#ifdef PLAN_HOST_MAIN
+// The same exports as a program (built with the sanitizers by tests/test_launch_plan.py): seeded lists through stage_layout, the
+// denoiser's lists of 1, 3 and 66 strips with every set of planes and outputs; every present entry aligned, in order, inside the total.
+#include <cstdio>
+namespace {
+bool laid_out(const std::vector<uint64_t>& bytes, const std::vector<uint64_t>& off, const std::vector<uint8_t>& present, uint64_t total) {
+    uint64_t top = 0;
+    for (size_t k = 0; k < bytes.size(); k++) {
+        if (!present[k]) continue;
+        if (off[k] % rtplan::DN_ALIGN || off[k] < top) return false;
+        top = off[k] + bytes[k];
+    }
+    return top <= total;
+}
+}  // namespace
+int main() {
+    uint64_t x = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&] { return (x = x * 6364136223846793005ull + 1442695040888963407ull) >> 33; };
+    for (int round = 0; round < 2000; round++) {
+        const uint32_t n = (uint32_t)(rnd() % 40);
+        std::vector<uint64_t> bytes(n), off(n);
+        std::vector<uint8_t> host(n), dev(n), present(n);
+        for (uint32_t k = 0; k < n; k++) {
+            bytes[k] = rnd() % 3 ? rnd() % 5000 : 0;
+            host[k] = rnd() % 3 != 0;
+            dev[k] = rnd() % 4 == 0;
+        }
+        const uint64_t total = stage_layout(bytes.data(), host.data(), dev.data(), n, off.data(), present.data());
+        for (uint32_t k = 0; k < n; k++)
+            if (present[k] != (host[k] || dev[k])) return std::puts("stage_layout: present"), 1;
+        if (!laid_out(bytes, off, present, total)) return std::puts("stage_layout: layout"), 1;
+    }
+    for (uint32_t n : {1u, 3u, 66u})
+        for (uint32_t planes = 0; planes < 16; planes++)
+            for (uint32_t outs = 1; outs < 8; outs++) {
+                const size_t m = 1 + (size_t)stage_per_strip() * n;
+                std::vector<uint64_t> bytes(m), off(m);
+                std::vector<uint8_t> present(m);
+                const uint64_t total = stage_denoise(40, 132, 66, n, planes, outs, bytes.data(), off.data(), present.data());
+                if (!present[0] || off[0] != 0 || !laid_out(bytes, off, present, total)) return std::puts("stage_denoise: layout"), 1;
+            }
+    std::puts("staging ok");
+    return 0;
+}
+#endif

@@ -8,8 +8,10 @@
 5. argument errors, with nothing launched;
 6. a full-size strip of c3 spot-checked against the oracle;
 7. alignment with the beauty image: pixels whose samples all missed have an albedo sum equal to the progressive accum;
-8. the host forms of the AOV, trace, query and progressive entry points interleaved on one scene, each staging buffer grown
-   in turn: every result repeats."""
+8. the host forms of the AOV, trace, query and progressive entry points interleaved on one scene, the staging grown in turn:
+   every result repeats;
+9. the host forms that share the scene's one staging buffer — AOV, camera rays, denoiser, query, trace — and the tile pass
+   interleaved on one scene, sizes growing and shrinking: each gives the bytes of the same call on a fresh scene."""
 import ctypes as C
 import os
 import subprocess
@@ -398,7 +400,8 @@ def test_sky_pixels_align_with_the_beauty_accum(ndev, scene):
 
 def test_staging_buffers_of_other_entry_points_leave_the_planes_alone(ndev):
     """One scene, the host forms of every entry point that stages through a scene buffer, each grown between two AOV calls: the
-    planes, the traced colours and the hits come out the same bit for bit (each entry point owns its staging buffer)."""
+    planes, the traced colours and the hits come out the same bit for bit (the AOV, trace and query forms carve the scene's one
+    staging buffer anew on every call and leave nothing in flight behind them; the tile pass has buffers of its own)."""
     sph, tri = _scene_world("quad_room")
     g = np.random.default_rng(0x57A6)
     with rt.Scene(0, rt.World(sph, tri)) as sc:
@@ -428,3 +431,68 @@ def test_staging_buffers_of_other_entry_points_leave_the_planes_alone(ndev):
         _assert_planes_equal(sc.render_aov(small)[0], first, "aov after its own buffer grew")
         sc.trace(o, d, spp=1, max_bounces=2, seed=4)
         _assert_planes_equal(sc.render_aov(big)[0], big_planes, "large aov after another trace")
+
+
+def _result_arrays(out):
+    """The arrays of a host-form call's result (tuples, lists and dicts of them), the stats left out, as bytes."""
+    if isinstance(out, np.ndarray):
+        return [np.ascontiguousarray(out).tobytes()]
+    if isinstance(out, dict):
+        out = list(out.values())
+    if isinstance(out, (tuple, list)):
+        return [b for v in out for b in _result_arrays(v)]
+    return []
+
+
+def test_interleaved_strip_host_forms_share_one_staging_buffer(ndev):
+    """The host forms of the feature buffers, the camera rays and the denoiser stage their arrays in the buffer the caller-ray calls
+    use, carved anew by every call.  Calls of all these kinds and a tile pass interleaved on one scene, with staged sizes that grow
+    and shrink, planes and outputs that come and go, and uploads that depend on the sample range, each give the bytes of the same
+    call on a fresh scene of the same world: no stale offset, no missed upload, no wrong copy direction, nothing left over."""
+    sph, tri = _scene_world("quad_room")
+    g = np.random.default_rng(0x57A7)
+    o = g.uniform(-2, 2, size=(1000, 3)).astype(np.float32)
+    d = g.normal(size=(1000, 3)).astype(np.float32)
+    small = _abi.default_request(width=64, height=48, divisions=2, division_no=1, spp=4, max_bounces=6, seed=0x5A11)
+    big = _abi.default_request(width=160, height=96, divisions=2, division_no=0, spp=2, max_bounces=6, seed=0x5B16)
+    strips = [_abi.default_request(width=64, height=48, divisions=4, division_no=k, spp=4, max_bounces=6, seed=0xD0 + k) for k in (1, 2, 3)]
+    # the inputs of the calls that continue or filter something, made once on a scene of their own
+    with rt.Scene(0, rt.World(sph, tri)) as prep:
+        half, _ = prep.render_aov(small, 0, 2)
+        acc = [prep.render_tile_pass(rq, 0, rq.spp)[2] for rq in strips]
+        guides = [prep.render_aov(rq)[0] for rq in strips]
+    two = _abi.DenoiseRequest.defaults(iterations=2)
+    none = _abi.DenoiseRequest.defaults(iterations=0)
+    all_out = ("rgb", "linear", "f32")
+    calls = [
+        ("aov small [0, 2)", lambda sc: sc.render_aov(small, 0, 2)),
+        ("aov small [2, 4) on those planes", lambda sc: sc.render_aov(small, 2, 4, out={k: v.copy() for k, v in half.items()})),
+        ("intersect 1000", lambda sc: sc.intersect(o, d)),
+        ("aov small, depth and hits", lambda sc: sc.render_aov(small, planes=("depth", "hits"))),
+        ("aov big", lambda sc: sc.render_aov(big)),
+        ("trace 257", lambda sc: sc.trace(o[:257], d[:257], spp=2, max_bounces=3, seed=3)),
+        ("camera rays [1, 3), no states", lambda sc: sc.camera_rays(small, 1, 3, want_states=False)),
+        ("denoise 1 strip, all guides, all outputs, 2 iterations", lambda sc: sc.denoise(strips[0], acc[0], guides[0], 4, 4, two, all_out)),
+        ("tile pass", lambda sc: sc.render_tile_pass(big, 0, big.spp)),
+        ("camera rays [1, 4), states", lambda sc: sc.camera_rays(small, 1, 4)),
+        ("denoise 3 strips, no guide, linear, 0 iterations", lambda sc: sc.denoise(strips, acc, [{}] * 3, 4, 4, none, ("linear",))),
+        ("intersect 63", lambda sc: sc.intersect(o[:63], d[:63])),
+        ("denoise 3 strips, all guides, all outputs, 2 iterations", lambda sc: sc.denoise(strips, acc, guides, 4, 4, two, all_out)),
+        ("denoise 1 strip, no guide, linear, 2 iterations", lambda sc: sc.denoise(strips[2], acc[2], {}, 4, 4, two, ("linear",))),
+        ("aov small [0, 2) again", lambda sc: sc.render_aov(small, 0, 2)),
+    ]
+    with rt.Scene(0, rt.World(sph, tri)) as sc:
+        results = [call(sc) for _, call in calls]
+    shared = [_result_arrays(r) for r in results]
+    assert all(len(a) >= 1 for a in shared), [len(a) for a in shared]
+    assert [len(a) for a in shared] == [5, 5, 1, 2, 5, 2, 1, 3, 2, 2, 3, 1, 9, 1, 5]
+    assert shared[0] == _result_arrays(half) and shared[-1] == shared[0]
+    assert shared[1] != shared[0]                                          # the second half added to the first
+    # the filter did something: after 2 iterations the linear colour is not the mean it was given
+    for k, which in ((7, [0]), (12, [0, 1, 2]), (13, [2])):
+        outs = results[k][0] if isinstance(results[k][0], list) else [results[k][0]]
+        for out, i in zip(outs, which):
+            assert np.abs(out["linear"] - acc[i] / np.float32(4)).max() > 1e-3, calls[k][0]
+    for (what, call), got in zip(calls, shared):
+        with rt.Scene(0, rt.World(sph, tri)) as fresh:
+            assert got == _result_arrays(call(fresh)), what

@@ -1,6 +1,6 @@
 """The launch plan (csrc/rt_plan.h, the product's plan_launch / plan_queue through a g++ harness): which engine renders a launch, its
 LDS layout, its sample units and its queue, at the rules' boundaries and as invariants over a seeded grid of scene shapes, requests
-and knobs.  What each engine costs on real scenes is tests/test_gpu_engine_rules.py's business; here: that the rules say what they
+and knobs; and the layout of the host forms' staging buffer (stage_layout, the denoiser's list).  What each engine costs on real scenes is tests/test_gpu_engine_rules.py's business; here: that the rules say what they
 say, on the CPU."""
 import ctypes as C
 import math
@@ -483,3 +483,89 @@ def test_knob_matrix_covers_every_kernel_family():
             want = {"L2 exact"} if "RT_COMPACT" in knobs else staging if "RT_NO_STAGE" in knobs else walks if "RT_REFILL_EIGHTHS" in knobs else families
         assert {M.FAMILY[e] for e in engines} == want, name
     assert M.settings_for(0)[0] == "default" and M.SLOTS_MIN == 1
+
+
+# ---------------------------------------------------------------------------------------------------- staging layout
+ALIGN = 256
+
+
+def _align(b):
+    return (b + ALIGN - 1) // ALIGN * ALIGN
+
+
+def _stage_lib(lib):
+    lib.stage_layout.restype = C.c_uint64
+    lib.stage_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.stage_denoise.restype = C.c_uint64
+    lib.stage_denoise.argtypes = [C.c_uint32] * 6 + [C.c_void_p] * 3
+    lib.stage_scratch_bytes.restype = C.c_double
+    lib.stage_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
+    return lib
+
+
+def _check_layout(nbytes, present, off, total, what):
+    """Every present entry at a multiple of 256, behind the one before it and inside the total; returns the aligned sizes' sum."""
+    top = 0
+    for k in np.nonzero(present)[0]:
+        assert off[k] % ALIGN == 0 and off[k] >= top, (what, k)
+        top = int(off[k]) + int(nbytes[k])
+    assert top <= total, what
+    return sum(_align(int(b)) for b in nbytes[present != 0])
+
+
+def test_staging_layout_of_random_lists(lib):
+    """rtplan::stage_layout against the arithmetic: an entry is present when it has a host side or is device-only, absent ones take no
+    room, present ones lie in list order at multiples of 256 without overlap, zero-byte ones included, and the total covers the last."""
+    _stage_lib(lib)
+    assert K(lib, "DN_ALIGN") == ALIGN
+    g = np.random.default_rng(0x57A6E)
+    for _ in range(300):
+        n = int(g.integers(0, 40))
+        nbytes = np.where(g.random(n) < 0.25, 0, g.integers(0, 5000, n)).astype(np.uint64)
+        host = (g.random(n) < 0.6).astype(np.uint8)
+        dev = (g.random(n) < 0.25).astype(np.uint8)
+        off, present = np.zeros(n, np.uint64), np.zeros(n, np.uint8)
+        total = lib.stage_layout(nbytes.ctypes.data, host.ctypes.data, dev.ctypes.data, n, off.ctypes.data, present.ctypes.data)
+        assert np.array_equal(present != 0, (host | dev) != 0)
+        assert _check_layout(nbytes, present, off, total, (n, nbytes, host, dev)) == total      # ... and no more than that
+        want = np.concatenate([[0], np.cumsum([_align(int(b)) if p else 0 for b, p in zip(nbytes, present)])])
+        assert np.array_equal(off, want[:-1].astype(np.uint64))
+
+
+@pytest.mark.parametrize("n", [1, 3, 66])
+def test_staging_list_of_the_denoiser(lib, n):
+    """rtplan::dn_stage_list for every plane set of tests/test_gpu_denoise.py: the scratch first, at offset 0 and device-only, then per
+    strip the sum, the guide planes it has and the outputs asked for, each aligned; the total holds the scratch and every aligned size."""
+    from test_gpu_denoise import PLANE_SETS
+    _stage_lib(lib)
+    W, Hs = 40, 2
+    per = lib.stage_per_strip()
+    assert per == 8
+    v3, s1, u8 = Hs * W * 12, Hs * W * 4, Hs * W * 3
+    scratch = int(lib.stage_scratch_bytes(W, Hs * n))
+    assert scratch >= 3 * 16 * W * Hs * n
+    order = ("albedo", "normal", "depth", "hits")
+    for names in PLANE_SETS:
+        planes = sum(1 << order.index(k) for k in names)
+        for outs in (1, 4, 7):                                  # rgb only, linear only, all three
+            m = 1 + per * n
+            nbytes, off, present = np.zeros(m, np.uint64), np.zeros(m, np.uint64), np.zeros(m, np.uint8)
+            total = lib.stage_denoise(W, Hs * 66, 66, n, planes, outs, nbytes.ctypes.data, off.ctypes.data, present.ctypes.data)
+            what = (n, names, outs)
+            assert present[0] and off[0] == 0 and nbytes[0] == scratch, what
+            strip = [1] + [1 if k in names else 0 for k in order] + [outs & 1, outs >> 1 & 1, outs >> 2 & 1]
+            assert np.array_equal(present[1:].reshape(n, per), np.tile(np.array(strip, np.uint8), (n, 1))), what
+            assert np.array_equal(nbytes[1:].reshape(n, per), np.tile(np.array([v3, v3, v3, s1, s1, u8, v3, v3], np.uint64), (n, 1))), what
+            aligned = _check_layout(nbytes, present, off, total, what)
+            assert aligned == _align(scratch) + n * sum(_align(b) for b, p in zip([v3, v3, v3, s1, s1, u8, v3, v3], strip) if p), what
+            assert total >= aligned, what
+
+
+def test_staging_harness_under_the_sanitizers(tmp_path):
+    """The harness source once more as a program with its own main, built with -fsanitize=address,undefined: the same lists, run to the
+    end with no report."""
+    exe = tmp_path / "plan_host_san"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-DPLAN_HOST_MAIN", f"-I{CSRC}", f"-I{ROOT / 'include'}", "-o", str(exe), str(SRC)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == "staging ok" and not r.stderr, (r.returncode, r.stdout, r.stderr[-2000:])
