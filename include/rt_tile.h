@@ -54,7 +54,9 @@ extern "C" {
                                   (4, additions only: direct lighting of caller rays rt_scene_light_count / rt_scene_direct /
                                      rt_scene_direct_device with rt_direct_request, rt_direct, RT_DIRECT_*)
                                   (4, additions only: next-event estimation for caller rays rt_scene_trace_nee /
-                                     rt_scene_trace_nee_device with rt_nee_request, RT_NEE_*) */
+                                     rt_scene_trace_nee_device with rt_nee_request, RT_NEE_*)
+                                  (4, additions only: light selection by power RT_FLAG_LIGHTS_BY_POWER for rt_scene_direct* and
+                                     rt_scene_trace_nee*, rt_scene_light_table) */
 
 /* ---- status codes --------------------------------------------------------------- */
 typedef enum rt_status {
@@ -145,7 +147,10 @@ enum {
     RT_FLAG_FRAME_NO_PIN = 1u << 13,
     /* FRAME_STATIC: the plain split strip k -> devices[k % n] (rounds 1-3; A/B runs, tests) instead of the default, which
      * balances the devices by the strips' cost: see "Strip assignment" at rt_frame_ctx below. */
-    RT_FLAG_FRAME_STATIC = 1u << 14
+    RT_FLAG_FRAME_STATIC = 1u << 14,
+    /* Light sampling (rt_scene_direct*, rt_scene_trace_nee* only; every other entry point ignores it): the emitter of a light sample
+     * is picked by power, not uniformly: see "light selection by power" below. */
+    RT_FLAG_LIGHTS_BY_POWER = 1u << 15
 };
 
 typedef struct rt_tile_request {
@@ -529,15 +534,34 @@ RT_API int rt_scene_bounce_device(rt_scene* scene, const rt_bounce_request* req,
  *   - Counters (rt_tile_stats): ray_segments = shadow rays traced; primary_rays = 0; broad_candidates = exact root tests; kernel_ms;
  *     h2d_ms (hits, states, the list) and d2h_ms (states, samples) of the host form; n_launches; engine (as for rt_scene_intersect).
  *   - Limits: the estimate equals ray_color's next bounce in expectation only at a hit of roughness 0.  A hit point inside an emissive
- *     sphere sees that sphere as dark (cl <= 0).  The emitter is picked uniformly, not by power.  A caller who adds the estimate drops
- *     the RT_BOUNCE_EMITTED term of the FOLLOWING step, or the light is counted twice.
- * No per-scene scratch on the device: launches on different streams may overlap.  (DESIGN.md 4.17.) */
+ *     sphere sees that sphere as dark (cl <= 0).  A caller who adds the estimate drops the RT_BOUNCE_EMITTED term of the FOLLOWING
+ *     step, or the light is counted twice.
+ *   - Light selection by power: the emitter above is picked uniformly.  With RT_FLAG_LIGHTS_BY_POWER in req->flags it is picked from
+ *     the scene's light table, made once by rt_scene_create.  For emitter k = 0 .. M - 1 of the list, in its order:
+ *       lum_k = ((ar + ag) + ab) * emission;  area_k = (4 * (r*r)) * PI for a sphere, A + A for a triangle (A as in the estimate: it
+ *       emits from both sides);  q_k = lum_k * area_k, and q_k = 0 if !(q_k > 0) (a NaN, an albedo sum <= 0, radius 0, a degenerate
+ *       triangle);  c_k = c_(k-1) + q_k with c_(-1) = 0;  total = c_(M-1).
+ *     The table is DEGENERATE when !(total > 0 && total < inf) (every q_k zero, an overflowing sum, an infinite q_k): then
+ *     p_k = 1/M, ip_k = (float)M and the pick is the uniform one above, so the flag changes no bit.  Otherwise
+ *       w_k = c_k - c_(k-1);  p_k = 0.5f * (1.0f / (float)M) + 0.5f * (w_k / total);  ip_k = 1.0f / p_k
+ *     — a mixture, half uniform and half by power, that is part of the contract: p_k >= 1/(2M) also for a light whose power the f32
+ *     running sum rounded away, so every emitter is sampled and the weight is bounded.  The pick takes the same single u = u01:
+ *       u < 0.5:   k = min((uint32_t)((u + u) * (float)M), M - 1);
+ *       otherwise: x = ((u - 0.5f) + (u - 0.5f)) * total;  k = the smallest index with x < c_k, or M - 1 when there is none.
+ *     ip_k takes the place of (float)M in W, and nothing else changes:
+ *       sphere light:   W = ((cs * cl) * ((4 * (r*r)) * ip_k)) / d2;      triangle light: W = ((cs * cl) * (A * ip_k)) / (PI * d2).
+ *     rt_scene_light_table() reports every p_k.
+ * No per-scene scratch on the device: launches on different streams may overlap.  (DESIGN.md 4.17, 4.19.) */
 typedef struct rt_direct_request { uint32_t flags; uint32_t reserved; float t_min, t_max; } rt_direct_request; /* 16 bytes */
 typedef struct rt_direct { float r, g, b; uint32_t light; float lx, ly, lz; uint32_t status; } rt_direct;      /* 32 bytes */
 enum { RT_DIRECT_LIT = 0u, RT_DIRECT_OCCLUDED = 1u, RT_DIRECT_FACING_AWAY = 2u, RT_DIRECT_NO_LIGHTS = 3u, RT_DIRECT_SKIPPED = 4u };
 
 /* The number M of emitters of the scene. */
 RT_API int rt_scene_light_count(rt_scene* scene, uint32_t* n_lights);
+/* The emitter list with the probability each emitter is picked with under `flags`: for k < M, out_world_index[k] = the world position
+ * of emitter k (the value rt_direct.light reports) and out_p[k] = p_k of the light table with RT_FLAG_LIGHTS_BY_POWER, 1.0f / (float)M
+ * without it.  Either array may be NULL.  capacity < M or a NULL scene: RT_ERR_BAD_ARG.  Host only: no GPU work, no synchronisation. */
+RT_API int rt_scene_light_table(rt_scene* scene, uint32_t flags, uint32_t* out_world_index, float* out_p, uint32_t capacity);
 /* Host buffers, synchronous: hits (n) are read; rng_state (4 n u64) is read and written back; out (n) is required; active (n_active
  * indices) and stats may be NULL.  Records that are not listed come back as they went in. */
 RT_API int rt_scene_direct(rt_scene* scene, const rt_direct_request* req, const rt_hit* hits, uint32_t n, uint64_t* rng_state,
@@ -591,9 +615,12 @@ RT_API int rt_scene_direct_device(rt_scene* scene, const rt_direct_request* req,
  *   - Counters (rt_tile_stats): primary_rays = n * spp; ray_segments = path segments + shadow rays; broad_candidates = exact root
  *     tests; kernel_ms; h2d_ms (rays and states) and d2h_ms (colours, counts, states) of the host form; n_launches = 1; engine (as for
  *     rt_scene_intersect).
- *   - Limits: a hit with roughness > 0 takes no light sample (it falls back to the bounce, which is unbiased); the emitter is picked
- *     uniformly, not by power.
- * No per-scene scratch on the device: launches on different streams may overlap.  (DESIGN.md 4.18.) */
+ *   - Light selection by power: with RT_FLAG_LIGHTS_BY_POWER in `flags` every light sample is rt_scene_direct's under that flag (the
+ *     pick from the light table, ip_k in W), and in the RT_BOUNCE_EMITTED branch W' takes ip_j of the emitter j that was hit in the
+ *     place of (float)M.  wl and wb are unchanged: W is still p_bsdf / p_light.  RT_NEE_LIGHT_ONLY stays, bit for bit, the fold over
+ *     rt_scene_bounce and rt_scene_direct with the flag.
+ *   - Limits: a hit with roughness > 0 takes no light sample (it falls back to the bounce, which is unbiased).
+ * No per-scene scratch on the device: launches on different streams may overlap.  (DESIGN.md 4.18, 4.19.) */
 typedef struct rt_nee_request {
     uint32_t spp;               /* samples per ray, 1 .. RT_MAX_SPP                                        */
     uint32_t max_bounces;       /* 0 .. RT_MAX_BOUNCES; at most max_bounces + 1 path segments, as rt_scene_trace */

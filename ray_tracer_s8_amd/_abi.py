@@ -40,6 +40,7 @@ RT_FLAG_NO_CULL_WALK = 2048
 RT_FLAG_FRAME_QUEUE = 4096          # frame-level (rt_render_frame / rt_frame_ctx_render): dynamic strip queue
 RT_FLAG_FRAME_NO_PIN = 8192         # frame-level: do not page-lock the caller's frame buffer
 RT_FLAG_FRAME_STATIC = 16384        # frame-level: strip k -> devices[k % n] instead of the cost-balanced assignment
+RT_FLAG_LIGHTS_BY_POWER = 32768     # rt_scene_direct* / rt_scene_trace_nee*: the emitter is picked by power (mixture with uniform)
 RT_MAX_BOUNCES = 62
 RT_MAX_SPP = 4096                 # samples per pixel limit (rt_tile.h)
 
@@ -363,6 +364,8 @@ def _bind(path: Path) -> C.CDLL:
     lib.rt_scene_bounce_device.restype = C.c_int
     lib.rt_scene_light_count.argtypes = [vp, C.POINTER(C.c_uint32)]
     lib.rt_scene_light_count.restype = C.c_int
+    lib.rt_scene_light_table.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_uint32]
+    lib.rt_scene_light_table.restype = C.c_int
     lib.rt_scene_direct.argtypes = [vp, C.POINTER(DirectRequest), C.POINTER(Hit), C.c_uint32, C.POINTER(C.c_uint64),
                                     C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Direct), C.POINTER(TileStats)]
     lib.rt_scene_direct.restype = C.c_int

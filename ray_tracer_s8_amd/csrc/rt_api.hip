@@ -184,6 +184,11 @@ struct rt_scene {
     rtplan::SceneShape shape;       // what the engine rules read (rt_plan.h)
     uint32_t n_lights = 0;          // direct lighting: the emitters of the scene (rt_scene_light_count)
     uint32_t* d_lights = nullptr;   //   their primitive numbers in ascending world position (rtscene::emitter_list)
+    float* d_light_c = nullptr;     // RT_FLAG_LIGHTS_BY_POWER (rtscene::light_table): the running sums of the powers, per emitter
+    float* d_light_ip = nullptr;    //   1 / p of an emitter, by primitive number
+    float light_total = 0.f;        //   the last running sum
+    std::vector<uint32_t> light_world;   // rt_scene_light_table: the world position and the mixture probability of every emitter
+    std::vector<float> light_p;
     rtplan::Pose pose;              // the job's placed camera (rt_scene_set_camera); read when a call is enqueued
     bool has_pose = false;          //   false: the reference camera
     float4* d_geom = nullptr;
@@ -577,7 +582,13 @@ template <class P>
 void light_refs(const rt_scene* sc, P& p) {
     p.lights = sc->d_lights;
     p.n_lights = sc->n_lights;
+    p.table.light_c = sc->d_light_c;
+    p.table.light_ip = sc->d_light_ip;
+    p.table.light_total = sc->light_total;
 }
+
+// RT_FLAG_LIGHTS_BY_POWER picks the kernel instance; it is no business of the plan (rt_plan.h), which never sees an engine in it.
+static bool lights_by_power(uint32_t flags) { return (flags & RT_FLAG_LIGHTS_BY_POWER) != 0; }
 
 // Enqueue one launch of persistent waves over `items` in workgroups of `block` on `stream` (caller holds sc->mu, device current),
 // the block `p` complete.  The launches of the caller-ray calls, the feature buffers and the camera rays all end here.  what: the
@@ -866,6 +877,12 @@ static int upload_scene(int device, const HostScene& hs, rt_scene** out) {
     SC_UP(d_big, hs.big);
     SC_UP(d_lights, hs.lights);
     sc->n_lights = hs.n_lights;
+    SC_UP(d_light_c, hs.light_c);
+    SC_UP(d_light_ip, hs.light_ip_prim);
+    sc->light_total = hs.light_total;
+    sc->light_p.assign(hs.light_p.begin(), hs.light_p.begin() + hs.n_lights);
+    sc->light_world.resize(hs.n_lights);
+    for (uint32_t k = 0; k < hs.n_lights; k++) sc->light_world[k] = hs.has_order ? hs.world_rank[hs.lights[k]] : hs.lights[k];
     sc->n_big = hs.n_big;
     sc->tri_k = hs.tri_k;
     sc->tri_diag = hs.tri_diag;
@@ -933,6 +950,8 @@ static int rt_scene_destroy_impl(rt_scene* sc) {
     (void)hipFree(sc->d_geom_r);
     (void)hipFree(sc->d_big);
     (void)hipFree(sc->d_lights);
+    (void)hipFree(sc->d_light_c);
+    (void)hipFree(sc->d_light_ip);
     (void)hipFree(sc->d_leaf_of);
     (void)hipFree(sc->d_world_rank);
     (void)hipFree(sc->d_counters);
@@ -1377,15 +1396,29 @@ static int launch_direct(rt_scene* sc, const rt_direct_request* rq, const void* 
     light_refs(sc, p);
     p.t_min = rq->t_min;
     p.t_max = rq->t_max;
-    return launch_rays(sc, qp, rtplan::QUERY_BLOCK, rtk::direct_kernel(qp.engine, qp.scan_mode), "direct-lighting", p,
+    return launch_rays(sc, qp, rtplan::QUERY_BLOCK, rtk::direct_kernel(qp.engine, qp.scan_mode, lights_by_power(rq->flags)), "direct-lighting", p,
                        std::max<uint32_t>(count, 1u),
                        vtext("direct: engine %d  scan mode %d  lds %zu B  ", qp.engine, qp.scan_mode, qp.lds),
-                       vtext("records %u  listed %s%u  lights %u", n, d_n_active ? "<= " : "", count, sc->n_lights), 0, stream);
+                       vtext("records %u  listed %s%u  lights %u%s", n, d_n_active ? "<= " : "", count, sc->n_lights,
+                             lights_by_power(rq->flags) ? " by power" : ""),
+                       0, stream);
 }
 
 static int rt_scene_light_count_impl(rt_scene* sc, uint32_t* n_lights) {
     if (!sc || !n_lights) return fail(RT_ERR_BAD_ARG, "scene or n_lights is NULL");
     *n_lights = sc->n_lights;
+    return RT_OK;
+}
+
+// Host-only: the scene's own copy of the table, no device work, no synchronisation.
+static int rt_scene_light_table_impl(rt_scene* sc, uint32_t flags, uint32_t* out_world_index, float* out_p, uint32_t capacity) {
+    if (!sc) return fail(RT_ERR_BAD_ARG, "scene is NULL");
+    const uint32_t M = sc->n_lights;
+    if (capacity < M) return fail(RT_ERR_BAD_ARG, "capacity < rt_scene_light_count()");
+    for (uint32_t k = 0; k < M; k++) {
+        if (out_world_index) out_world_index[k] = sc->light_world[k];
+        if (out_p) out_p[k] = lights_by_power(flags) ? sc->light_p[k] : 1.0f / (float)M;
+    }
     return RT_OK;
 }
 
@@ -1452,9 +1485,10 @@ static int launch_nee(rt_scene* sc, const rt_nee_request* rq, const void* d_rays
     p.mis = rq->mode == RT_NEE_MIS ? 1u : 0u;
     material_refs(sc, p);
     light_refs(sc, p);
-    return launch_rays(sc, qp, rtplan::QUERY_BLOCK, rtk::nee_kernel(qp.engine, qp.scan_mode), "next-event-estimation", p, n,
+    return launch_rays(sc, qp, rtplan::QUERY_BLOCK, rtk::nee_kernel(qp.engine, qp.scan_mode, lights_by_power(rq->flags)), "next-event-estimation", p, n,
                        vtext("nee: engine %d  scan mode %d  lds %zu B  ", qp.engine, qp.scan_mode, qp.lds),
-                       vtext("rays %u  spp %u  bounces %u  mode %u  lights %u", n, rq->spp, rq->max_bounces, rq->mode, sc->n_lights),
+                       vtext("rays %u  spp %u  bounces %u  mode %u  lights %u%s", n, rq->spp, rq->max_bounces, rq->mode, sc->n_lights,
+                             lights_by_power(rq->flags) ? " by power" : ""),
                        (uint64_t)n * rq->spp, stream);
 }
 
@@ -2478,6 +2512,9 @@ RT_API int rt_scene_trace_device(rt_scene* sc, const rt_trace_request* rq, const
 }
 RT_API int rt_scene_light_count(rt_scene* sc, uint32_t* n_lights) {
     return guarded([&] { return rt_scene_light_count_impl(sc, n_lights); });
+}
+RT_API int rt_scene_light_table(rt_scene* sc, uint32_t flags, uint32_t* out_world_index, float* out_p, uint32_t capacity) {
+    return guarded([&] { return rt_scene_light_table_impl(sc, flags, out_world_index, out_p, capacity); });
 }
 RT_API int rt_scene_direct(rt_scene* sc, const rt_direct_request* rq, const rt_hit* hits, uint32_t n, uint64_t* rng_state, const uint32_t* active,
                            uint32_t n_active, rt_direct* out, rt_tile_stats* stats) {

@@ -1,7 +1,7 @@
 // rt_direct.hip.h — gfx950 direct lighting of caller rays (rt_scene_direct*, rt_tile.h "direct lighting").
 //
-// One lane per ACTIVE hit record (the rt_hit a path step writes), one light sample per lane: an emitter picked uniformly from the
-// scene's emitter list with one u01 of the ray's own RNG state, a point on it (the UnitSphere draw of the shared path steps for a
+// One lane per ACTIVE hit record (the rt_hit a path step writes), one light sample per lane: an emitter picked from the
+// scene's emitter list (uniformly, or by power under RT_FLAG_LIGHTS_BY_POWER) with one u01 of the ray's own RNG state, a point on it (the UnitSphere draw of the shared path steps for a
 // sphere light, two u01 for a triangle light), the two cosines, the shadow ray through the shared closest_hit, and the Lambertian
 // estimate without the surface albedo.  The arithmetic of the pick, the point, the cosines and the weight is rt_direct_math.h, which the
 // CPU harness runs too; the sample (light_sample, sample_weight: the draws, the point, the normal of a triangle light) and the
@@ -32,10 +32,11 @@ struct DParams : SceneRefs {
     const uint32_t* lights;      // [n_lights] the emitters (library primitive numbers) in ascending world position
     uint32_t n_lights;           // M <= rtdl::MAX_LIGHTS
     float t_min, t_max;          // the shadow rays' window
+    LightTableRefs table;        // RT_FLAG_LIGHTS_BY_POWER (PICK_POWER instances only)
 };
 
-// ENGINE 2: the walk; 1: the scan with consider<MODE> (MODE 0 plain linear semantics, 2 BVH semantics).
-template <int ENGINE, int MODE>
+// ENGINE 2: the walk; 1: the scan with consider<MODE> (MODE 0 plain linear semantics, 2 BVH semantics).  PICK: the pick rule.
+template <int ENGINE, int MODE, int PICK>
 __global__ __launch_bounds__(256) void rt_direct_kernel(const DParams p) {
     extern __shared__ uint32_t dstack[];                 // [depth + 1][256] (engine 2)
     const uint32_t tid = threadIdx.x;
@@ -55,7 +56,7 @@ __global__ __launch_bounds__(256) void rt_direct_kernel(const DParams p) {
         // ================= the draws: the emitter, then the point on it =================
         Rng rng;
         load_rng(p.rng_state + 4 * i, rng);
-        const LightSample ls = light_sample(p, rng);
+        const LightSample ls = light_sample<PICK>(p, rng);
         store_rng(p.rng_state + 4 * i, rng);
         // ================= the cosines; the shadow ray Ray::new(P, L - P) =================
         const rtdl::Geometry g = rtdl::light_geometry(dvec(P), dvec(n), ls.L, ls.nl, ls.sphere);
@@ -70,7 +71,7 @@ __global__ __launch_bounds__(256) void rt_direct_kernel(const DParams p) {
             if (h.idx == (int)ls.prim) {
                 status = RT_DIRECT_LIT;
                 const float4 ma = at32(p.mat, ls.prim);
-                const float W = sample_weight(ls, g, p.n_lights);
+                const float W = sample_weight<PICK>(ls, g, p.n_lights);
                 rgb = rtdl::radiance(rtdl::Vec{ma.x, ma.y, ma.z}, at32(p.emis, ls.prim), W);
             }
         }
@@ -81,6 +82,6 @@ __global__ __launch_bounds__(256) void rt_direct_kernel(const DParams p) {
 }
 
 using DirectFn = void (*)(const DParams);
-DirectFn direct_kernel(int engine, int scan_mode);    // rt_kernels_direct.hip; nullptr for a combination that does not exist
+DirectFn direct_kernel(int engine, int scan_mode, bool by_power);    // rt_kernels_direct.hip; nullptr for a combination that does not exist
 
 }  // namespace rtk

@@ -29,6 +29,46 @@ RT_HOST_DEVICE uint32_t pick_light(float u, uint32_t M) {
     return k < M - 1u ? k : M - 1u;
 }
 
+// ---- light selection by power (RT_FLAG_LIGHTS_BY_POWER): the table arithmetic the host runs once per scene
+// (rtscene::light_table) and the pick the kernels run per sample.
+// lum = ((ar + ag) + ab) * emission
+RT_HOST_DEVICE float light_luminance(Vec albedo, float emission) { return ((albedo.x + albedo.y) + albedo.z) * emission; }
+
+// area of a sphere light: (4 (r r)) PI
+RT_HOST_DEVICE float sphere_light_area(float r) { return (4.0f * (r * r)) * PI_F32; }
+
+// q = lum * area, and 0 unless q > 0: a NaN, a zero or negative albedo sum, a zero radius and a degenerate triangle have no power
+RT_HOST_DEVICE float light_power(float lum, float area) {
+    const float q = lum * area;
+    return q > 0.0f ? q : 0.0f;
+}
+
+// The table is degenerate unless its total is positive and finite: then the pick is the uniform one and p_k = 1 / M.
+RT_HOST_DEVICE bool table_degenerate(float total) { return !(total > 0.0f && total < __builtin_inff()); }
+
+// p = 0.5 (1 / (float)M) + 0.5 (w / total): half uniform, half by power, so p >= 1 / (2M) whatever the running sum rounded away
+RT_HOST_DEVICE float mixture_probability(float w, float total, uint32_t M) {
+    return 0.5f * (1.0f / (float)M) + 0.5f * (w / total);
+}
+
+// The pick by power from one u in [0, 1) over the running sums c[0 .. M - 1] (non-decreasing, total = c[M - 1]), 1 <= M <= MAX_LIGHTS.
+// u < 0.5: the uniform pick of u + u (exact).  Otherwise x = ((u - 0.5) + (u - 0.5)) * total (the subtraction and the doubling are
+// exact for a 24-bit u) and k is the smallest index with x < c[k], or M - 1 when there is none: ceil(log2 M) halvings whatever x is,
+// so the lanes of a wave leave the loop together, then one comparison.  A degenerate table takes pick_light(u, M), the undoubled draw.
+RT_HOST_DEVICE uint32_t pick_light_power(float u, uint32_t M, const float* c, float total) {
+    if (table_degenerate(total)) return pick_light(u, M);
+    if (u < 0.5f) return pick_light(u + u, M);
+    const float x = ((u - 0.5f) + (u - 0.5f)) * total;
+    uint32_t base = 0, len = M;
+    while (len > 1u) {                                   // the answer is in [base, base + len]
+        const uint32_t half = len >> 1;
+        if (!(x < c[base + half - 1u])) base += half;
+        len -= half;
+    }
+    const uint32_t k = x < c[base] ? base : base + 1u;
+    return k < M - 1u ? k : M - 1u;
+}
+
 // L = c + r * us, the point of the UnitSphere draw `us` on the sphere (c, r); its outward normal there is us itself
 RT_HOST_DEVICE Vec sphere_point(Vec c, float r, Vec us) { return Vec{c.x + r * us.x, c.y + r * us.y, c.z + r * us.z}; }
 
@@ -85,6 +125,11 @@ RT_HOST_DEVICE float sphere_weight(float cs, float cl, float r, uint32_t M, floa
 RT_HOST_DEVICE float triangle_weight(float cs, float cl, float A, uint32_t M, float d2) {
     return ((cs * cl) * (A * (float)M)) / (PI_F32 * d2);
 }
+
+// ... and with the inverse probability ip of the emitter picked in the place of (float)M (RT_FLAG_LIGHTS_BY_POWER; the uniform pick
+// has ip = (float)M): ((cs cl) ((4 (r r)) ip)) / d2 and ((cs cl) (A ip)) / (PI d2)
+RT_HOST_DEVICE float sphere_weight_ip(float cs, float cl, float r, float ip, float d2) { return ((cs * cl) * ((4.0f * (r * r)) * ip)) / d2; }
+RT_HOST_DEVICE float triangle_weight_ip(float cs, float cl, float A, float ip, float d2) { return ((cs * cl) * (A * ip)) / (PI_F32 * d2); }
 
 // rgb = (albedo * emission) * W per channel
 RT_HOST_DEVICE Vec radiance(Vec albedo, float emission, float W) {

@@ -4,10 +4,16 @@
 #include "rt_direct.hip.h"
 
 namespace rtk {
-DirectFn direct_kernel(int engine, int scan_mode) {
-    if (engine == 2) return rt_direct_kernel<2, 2>;
-    if (engine == 1 && scan_mode == 0) return rt_direct_kernel<1, 0>;
-    if (engine == 1 && scan_mode == 2) return rt_direct_kernel<1, 2>;
+template <int PICK>
+static DirectFn direct_kernel_of(int engine, int scan_mode) {
+    if (engine == 2) return rt_direct_kernel<2, 2, PICK>;
+    if (engine == 1 && scan_mode == 0) return rt_direct_kernel<1, 0, PICK>;
+    if (engine == 1 && scan_mode == 2) return rt_direct_kernel<1, 2, PICK>;
     return nullptr;
+}
+
+// by_power: the instances of RT_FLAG_LIGHTS_BY_POWER; the others are the code they were before the flag existed
+DirectFn direct_kernel(int engine, int scan_mode, bool by_power) {
+    return by_power ? direct_kernel_of<PICK_POWER>(engine, scan_mode) : direct_kernel_of<PICK_UNIFORM>(engine, scan_mode);
 }
 }  // namespace rtk

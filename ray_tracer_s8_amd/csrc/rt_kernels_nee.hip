@@ -5,10 +5,16 @@
 #include "rt_nee.hip.h"
 
 namespace rtk {
-NeeFn nee_kernel(int engine, int scan_mode) {
-    if (engine == 2) return rt_nee_kernel<2, 2>;
-    if (engine == 1 && scan_mode == 0) return rt_nee_kernel<1, 0>;
-    if (engine == 1 && scan_mode == 2) return rt_nee_kernel<1, 2>;
+template <int PICK>
+static NeeFn nee_kernel_of(int engine, int scan_mode) {
+    if (engine == 2) return rt_nee_kernel<2, 2, PICK>;
+    if (engine == 1 && scan_mode == 0) return rt_nee_kernel<1, 0, PICK>;
+    if (engine == 1 && scan_mode == 2) return rt_nee_kernel<1, 2, PICK>;
     return nullptr;
+}
+
+// by_power: the instances of RT_FLAG_LIGHTS_BY_POWER; the others are the code they were before the flag existed
+NeeFn nee_kernel(int engine, int scan_mode, bool by_power) {
+    return by_power ? nee_kernel_of<PICK_POWER>(engine, scan_mode) : nee_kernel_of<PICK_UNIFORM>(engine, scan_mode);
 }
 }  // namespace rtk

@@ -42,6 +42,7 @@ struct NParams : SceneRefs {
     const float* emis;           // [n_sph + n_tri]
     const uint32_t* lights;      // [n_lights] the emitters (library primitive numbers) in ascending world position
     uint32_t n_lights;           // M <= rtdl::MAX_LIGHTS
+    LightTableRefs table;        // RT_FLAG_LIGHTS_BY_POWER (PICK_POWER instances only)
 };
 
 // The size rt_direct_math.h's weights take for primitive `prim`: a sphere's radius, a triangle's area.
@@ -52,8 +53,9 @@ __device__ __forceinline__ float light_size(const P& p, uint32_t prim) {
     return rtdl::triangle_area(rtdl::Vec{tv[0], tv[1], tv[2]}, rtdl::Vec{tv[3], tv[4], tv[5]}, rtdl::Vec{tv[6], tv[7], tv[8]});
 }
 
-// ENGINE 2: the walk; 1: the scan with consider<MODE> (MODE 0 plain linear semantics, 2 BVH semantics).
-template <int ENGINE, int MODE>
+// ENGINE 2: the walk; 1: the scan with consider<MODE> (MODE 0 plain linear semantics, 2 BVH semantics).  PICK: the pick rule, which
+// also decides what stands for (float)M in W and in W' (the inverse probability of the emitter sampled, and of the emitter hit).
+template <int ENGINE, int MODE, int PICK>
 __global__ __launch_bounds__(256) void rt_nee_kernel(const NParams p) {
     extern __shared__ uint32_t nstack[];                 // [depth + 1][256] (engine 2)
     const uint32_t tid = threadIdx.x, bs = blockDim.x;
@@ -111,7 +113,10 @@ __global__ __launch_bounds__(256) void rt_nee_kernel(const NParams p) {
                         if (v.samplable) {
                             add_it = p.mis != 0;                                       // LIGHT_ONLY: that sample stood for it
                             if (add_it) {
-                                const float wb = rtnee::bounce_weight(rtnee::view_weight(v, sphere, light_size(p, prim), p.n_lights));
+                                const float size = light_size(p, prim);
+                                const float Wv = PICK == PICK_POWER ? rtnee::view_weight_ip(v, sphere, size, p.table.light_ip[prim])
+                                                                    : rtnee::view_weight(v, sphere, size, p.n_lights);
+                                const float wb = rtnee::bounce_weight(Wv);
                                 ex = ex * wb;
                                 ey = ey * wb;
                                 ez = ez * wb;
@@ -139,11 +144,11 @@ __global__ __launch_bounds__(256) void rt_nee_kernel(const NParams p) {
                 sampled = ma.w == 0.0f && p.n_lights > 0;
                 if (!sampled) continue;
                 // ================= one light sample, as rt_scene_direct specifies it for the record (P, n, prim) =================
-                const LightSample ls = light_sample(p, rng);
+                const LightSample ls = light_sample<PICK>(p, rng);
                 const rtdl::Geometry g = rtdl::light_geometry(dvec(hp), dvec(nh), ls.L, ls.nl, ls.sphere);
                 if (!g.facing) continue;                                               // FACING_AWAY: no ray, straight on
                 const float4 la = at32(p.mat, ls.prim);
-                const float W = sample_weight(ls, g, p.n_lights);
+                const float W = sample_weight<PICK>(ls, g, p.n_lights);
                 rtdl::Vec D = rtdl::radiance(rtdl::Vec{la.x, la.y, la.z}, at32(p.emis, ls.prim), W);
                 if (p.mis) {
                     const float wl = rtnee::light_weight(W);
@@ -171,6 +176,6 @@ __global__ __launch_bounds__(256) void rt_nee_kernel(const NParams p) {
 }
 
 using NeeFn = void (*)(const NParams);
-NeeFn nee_kernel(int engine, int scan_mode);    // rt_kernels_nee.hip; nullptr for a combination that does not exist
+NeeFn nee_kernel(int engine, int scan_mode, bool by_power);    // rt_kernels_nee.hip; nullptr for a combination that does not exist
 
 }  // namespace rtk

@@ -37,4 +37,9 @@ RT_HOST_DEVICE float view_weight(const View& v, bool sphere, float size, uint32_
     return sphere ? rtdl::sphere_weight(v.cs, v.cl, size, M, v.d2) : rtdl::triangle_weight(v.cs, v.cl, size, M, v.d2);
 }
 
+// ... and under RT_FLAG_LIGHTS_BY_POWER, with the inverse probability ip of the emitter hit
+RT_HOST_DEVICE float view_weight_ip(const View& v, bool sphere, float size, float ip) {
+    return sphere ? rtdl::sphere_weight_ip(v.cs, v.cl, size, ip, v.d2) : rtdl::triangle_weight_ip(v.cs, v.cl, size, ip, v.d2);
+}
+
 }  // namespace rtnee

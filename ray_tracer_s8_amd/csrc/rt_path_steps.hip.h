@@ -196,15 +196,32 @@ struct LightSample {
     bool sphere;
     rtdl::Vec L, nl;             // the point on it and the emitter's normal there
     float size;                  // the radius, or the triangle's area
+    float ip;                    // PICK_POWER: the inverse of the probability the emitter was picked with
 };
 
-// One light sample drawn from rng (p.n_lights > 0): the emitter picked uniformly with one u01, then a point on it — the UnitSphere draw
-// of a scattering hit for a sphere light, two u01 for a triangle light.  P: a parameter block with lights / n_lights.
-template <class P>
+// How the emitter is picked: uniformly, or by the scene's light table under RT_FLAG_LIGHTS_BY_POWER.  A template
+// parameter of the kernels that sample lights, so the instances that run without the flag are the code they were before it existed.
+enum { PICK_UNIFORM = 0, PICK_POWER = 1 };
+
+// The scene's light table (rtscene::light_table), the last fields of a parameter block that samples lights; read by PICK_POWER only.
+struct LightTableRefs {
+    const float* light_c;        // [n_lights] running sums of the emitters' powers, in the list's order
+    const float* light_ip;       // [n_sph + n_tri] by primitive number: 1 / p of an emitter
+    float light_total;           // light_c[n_lights - 1]; not positive and finite: the table is degenerate, the pick uniform
+};
+
+// One light sample drawn from rng (p.n_lights > 0): the emitter picked with one u01 — uniformly, or by power — then a point on it: the
+// UnitSphere draw of a scattering hit for a sphere light, two u01 for a triangle light.  P: a parameter block with lights / n_lights
+// (and, for PICK_POWER, table: LightTableRefs).
+template <int PICK, class P>
 __device__ __forceinline__ LightSample light_sample(const P& p, Rng& rng) {
     LightSample s;
-    const uint32_t pick = rtdl::pick_light(u01(rng), p.n_lights);
+    const float u = u01(rng);
+    uint32_t pick;
+    if (PICK == PICK_POWER) pick = rtdl::pick_light_power(u, p.n_lights, p.table.light_c, p.table.light_total);
+    else pick = rtdl::pick_light(u, p.n_lights);
     s.prim = p.lights[pick];
+    s.ip = PICK == PICK_POWER ? p.table.light_ip[s.prim] : 0.0f;
     s.sphere = s.prim < p.n_sph;
     if (s.sphere) {
         const float4 g = at32(p.geom_r, s.prim);
@@ -226,8 +243,11 @@ __device__ __forceinline__ LightSample light_sample(const P& p, Rng& rng) {
 }
 
 // W of the sample s seen under the geometry g = rtdl::light_geometry(P, n, s.L, s.nl, s.sphere): radiance(albedo, emission, W) is the
-// estimate, and the MIS weight of the light strategy reads W itself.
+// estimate, and the MIS weight of the light strategy reads W itself.  PICK_POWER: s.ip in the place of (float)n_lights.
+template <int PICK>
 __device__ __forceinline__ float sample_weight(const LightSample& s, const rtdl::Geometry& g, uint32_t n_lights) {
+    if (PICK == PICK_POWER)
+        return s.sphere ? rtdl::sphere_weight_ip(g.cs, g.cl, s.size, s.ip, g.d2) : rtdl::triangle_weight_ip(g.cs, g.cl, s.size, s.ip, g.d2);
     return s.sphere ? rtdl::sphere_weight(g.cs, g.cl, s.size, n_lights, g.d2) : rtdl::triangle_weight(g.cs, g.cl, s.size, n_lights, g.d2);
 }
 

@@ -12,6 +12,7 @@
 
 #include "rt_bvh.h"
 #include "rt_consts.h"
+#include "rt_direct_math.h"
 #include "rt_plan.h"
 #include "rt_tile.h"
 
@@ -38,6 +39,12 @@ struct HostScene {
     bool has_order = false;
     std::vector<uint32_t> lights;       // direct lighting: the emitters, in ascending world position (one dummy entry when none)
     uint32_t n_lights = 0;
+    // light selection by power (RT_FLAG_LIGHTS_BY_POWER), per emitter k of `lights`: the running sum of the powers, the
+    // mixture probability and its inverse; light_ip_prim: that inverse by primitive number (0 for a primitive that does not emit), which
+    // the kernels read for the emitter picked and for an emitter a bounce hit.  One dummy entry when there is no emitter.
+    std::vector<float> light_c, light_p, light_ip, light_ip_prim;
+    float light_total = 0.f;
+    bool light_degenerate = true;       // !(total > 0 && total < inf): p = 1 / M, ip = (float)M, the uniform pick
 };
 
 // positions in RenderInfo.world: every one of 0 .. n - 1 exactly once
@@ -415,6 +422,47 @@ inline void emitter_list(HostScene& hs) {
     if (lights.empty()) lights.push_back(0);
 }
 
+// The light table of RT_FLAG_LIGHTS_BY_POWER (rt_tile.h "light selection by power"): per emitter of the list, in its order, the power
+// q = luminance * area (rt_direct_math.h; 0 unless positive), the running f32 sum c, and from the width each emitter has IN that sum
+// the mixture probability p = 0.5 / M + 0.5 w / total with its inverse ip.  One IEEE f32 rounding per operation, as the header writes
+// them.  Reads hs.lights, hs.geom_r, hs.tri, hs.mat and hs.emis (emitter_list and pack_records before it); no launch without the flag
+// reads the table.
+inline void light_table(HostScene& hs) {
+    const uint32_t ns = hs.shape.n_sph, np = ns + hs.shape.n_tri, M = hs.n_lights;
+    hs.light_c.assign(M ? M : 1, 0.f);
+    hs.light_p.assign(M ? M : 1, 0.f);
+    hs.light_ip.assign(M ? M : 1, 0.f);
+    hs.light_ip_prim.assign(np ? np : 1, 0.f);
+    float run = 0.f;
+    for (uint32_t k = 0; k < M; k++) {
+        const uint32_t prim = hs.lights[k];
+        const float lum = rtdl::light_luminance(rtdl::Vec{hs.mat[prim].x, hs.mat[prim].y, hs.mat[prim].z}, hs.emis[prim]);
+        float area;
+        if (prim < ns) {
+            area = rtdl::sphere_light_area(hs.geom_r[prim].w);
+        } else {
+            const float* tv = &hs.tri[(size_t)(prim - ns) * 9];
+            const float A = rtdl::triangle_area(rtdl::Vec{tv[0], tv[1], tv[2]}, rtdl::Vec{tv[3], tv[4], tv[5]}, rtdl::Vec{tv[6], tv[7], tv[8]});
+            area = A + A;                                    // a triangle emits from both sides
+        }
+        run = run + rtdl::light_power(lum, area);
+        hs.light_c[k] = run;
+    }
+    hs.light_total = run;
+    hs.light_degenerate = rtdl::table_degenerate(run);
+    for (uint32_t k = 0; k < M; k++) {
+        if (hs.light_degenerate) {
+            hs.light_p[k] = 1.0f / (float)M;
+            hs.light_ip[k] = (float)M;
+        } else {
+            const float w = hs.light_c[k] - (k ? hs.light_c[k - 1] : 0.0f);
+            hs.light_p[k] = rtdl::mixture_probability(w, run, M);
+            hs.light_ip[k] = 1.0f / hs.light_p[k];
+        }
+        hs.light_ip_prim[hs.lights[k]] = hs.light_ip[k];
+    }
+}
+
 // reorder: false keeps the primitive records in the caller's order (A/B)
 inline void build_host_scene(const rt_sphere* sp, uint32_t ns, const rt_triangle* tr, uint32_t nt, const uint32_t* world_index,
                              bool reorder, HostScene& hs) {
@@ -442,6 +490,7 @@ inline void build_host_scene(const rt_sphere* sp, uint32_t ns, const rt_triangle
     else hs.world_rank.assign(1, 0u);
     pack_records(sp, ns, tr, nt, boxes, hs);
     emitter_list(hs);
+    light_table(hs);
     expanded_records(sp, ns, hs);
     sh.quant_ok = quant_rule(boxes, bvh.grid);
     sh.leaf_density = leaf_density(boxes);

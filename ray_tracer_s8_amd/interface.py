@@ -378,6 +378,16 @@ class Scene:
         _abi.check(self._lib.rt_scene_light_count(self._h, C.byref(m)), "rt_scene_light_count")
         return m.value
 
+    def light_table(self, flags: int = 0):
+        """The emitter list with its selection probabilities (rt_scene_light_table): (world_index (M,) uint32, p (M,) float32) — for
+        emitter k its position in the world (the value rt_direct.light reports) and the probability it is picked with under `flags`:
+        the mixture of the light table with RT_FLAG_LIGHTS_BY_POWER, 1 / M without.  Host only."""
+        m = self.n_lights
+        wi, p = np.zeros(m, np.uint32), np.zeros(m, np.float32)
+        _abi.check(self._lib.rt_scene_light_table(self._h, flags, wi.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                  p.ctypes.data_as(C.POINTER(C.c_float)), m), "rt_scene_light_table")
+        return wi, p
+
     def direct(self, hits, rng_state, active=None, t_min: float = 0.001, t_max: float = 1000.0, flags: int = 0):
         """Direct lighting of caller rays (rt_scene_direct): one light sample for each active hit record — an emitter picked with one
         u01 of the ray's state, a point on it, the shadow ray within [t_min, t_max) and the Lambertian estimate without the surface

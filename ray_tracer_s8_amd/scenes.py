@@ -62,6 +62,33 @@ def cornell16(seed: int = 0xC0A11E16) -> np.ndarray:
     return np.array(s, dtype=SPHERE_DTYPE)
 
 
+def lamp_room(n_dim: int = 32) -> np.ndarray:
+    """A many-light scene (tools/nee_bench.py --config lamps, examples/many_lights.c): a ground sphere and three diffuse spheres, all
+    of roughness 0, under one lamp (emission 6, radius 0.5) and n_dim dim spheres (emission 0.05, radius 0.05) on a ring around it:
+    n_dim + 1 emitters of which one carries nearly all the power."""
+    s = [
+        _sph((0.0, -100.5, -3.0), 100.0, (0.5, 0.6, 0.4)),
+        _sph((-1.2, 0.0, -3.2), 0.5, (0.8, 0.3, 0.3)),
+        _sph((0.0, 0.0, -3.0), 0.5, (0.3, 0.7, 0.4)),
+        _sph((1.2, 0.0, -2.8), 0.5, (0.7, 0.7, 0.2)),
+        _sph((0.2, 2.3, -3.0), 0.5, (1.0, 0.9, 0.7), 0.0, 6.0),
+    ]
+    for i in range(n_dim):
+        a = i * (2.0 * np.pi / n_dim)
+        s.append(_sph((0.2 + 1.6 * np.cos(a), 1.6 + 0.3 * np.sin(3 * a), -3.0 + 1.6 * np.sin(a)), 0.05, (1.0, 0.9, 0.7), 0.0, 0.05))
+    return np.array(s, dtype=SPHERE_DTYPE)
+
+
+def lamp_room_rays(width: int = 64, height: int = 32, fov_scale: float = 0.3, pitch: float = -0.1):
+    """Fixed pinhole rays for lamp_room from the origin down -z, one per pixel centre, pitched down onto the spheres and the ground
+    around them: (origins (N, 3), directions (N, 3)) float32."""
+    ys, xs = np.mgrid[0:height, 0:width]
+    u = ((xs + 0.5) / width * 2 - 1) * fov_scale * width / height
+    v = (1 - (ys + 0.5) / height * 2) * fov_scale + pitch
+    d = np.stack([u, v, -np.ones_like(u)], -1).reshape(-1, 3).astype(np.float32)
+    return np.zeros_like(d), d
+
+
 def _rand_field(n_total: int, seed: int, box, rr, ground):
     g = SplitMix64(seed)
     s = [ground]

@@ -12,8 +12,13 @@ it buys, on the camera rays of a benchmark scene (default c2, cornell16).
   fused     the integrator in one kernel (rt_scene_trace_nee) in both modes on the same rays, max_bounces = K - 1: HIP-event time of
             the kernel, best and median of --runs after --warmup warm-ups, beside the composed loop and rt_scene_trace timed the same
             way, and each mode's mean, variance and variance ratio against rt_scene_trace at that equal sample count.
+  power     (--power) light selection by power, RT_FLAG_LIGHTS_BY_POWER, beside the uniform pick on the same rays and states in the same
+            run: HIP-event time of rt_scene_direct on the first step's hits and of rt_scene_trace_nee in both modes (best and median
+            of --runs after --warmup), the mean and the variance of the samples' luminance, and the variance ratio uniform / by power.
 
-    python tools/nee_bench.py [--config c2] [--width 480 --height 270 --spp 4] [--steps 4]
+--config lamps is the many-light scene scenes.lamp_room() (one lamp, 32 dim emitters) under its fixed pinhole rays.
+
+    python tools/nee_bench.py [--config c2 | lamps] [--width 480 --height 270 --spp 4] [--steps 4] [--power]
 Prints one JSON line."""
 import argparse
 import json
@@ -65,6 +70,47 @@ def nee(sc, rays, states, K):
     return col, ms_step, ms_direct
 
 
+def lamp_rays(width, height, spp):
+    """scenes.lamp_room_rays as rt_ray records with unit directions, spp records per pixel (record pixel * spp + s, as camera_rays)."""
+    o, d = scenes.lamp_room_rays(width, height)
+    d = (d / np.linalg.norm(d.astype(np.float64), axis=1, keepdims=True)).astype(np.float32)
+    r = np.zeros(len(d) * spp, _abi.RAY_DTYPE)
+    o, d = np.repeat(o, spp, 0), np.repeat(d, spp, 0)
+    r["ox"], r["oy"], r["oz"], r["dx"], r["dy"], r["dz"] = o[:, 0], o[:, 1], o[:, 2], d[:, 0], d[:, 1], d[:, 2]
+    r["t_min"], r["t_max"] = 0.001, 1000.0
+    return r
+
+
+def power_block(sc, a, step, rays, o, dd):
+    """The uniform pick and the pick by power side by side: the light samples of the first step's scattered hits, and the integrator
+    in both modes, on the same rays and the same states."""
+    n = len(rays)
+    best_median = lambda t: {"best": min(t), "median": statistics.median(t)}
+    out = {}
+    for name, flags in (("uniform", 0), ("by_power", _abi.RT_FLAG_LIGHTS_BY_POWER)):
+        t_direct, t_fused, fused = [], {m: [] for m in MODES}, {}
+        for i in range(a.warmup + a.runs):
+            d = sc.direct(step["hits"], step["states"], active=step["next"], flags=flags)
+            for m, mode in MODES.items():
+                fused[m] = sc.trace_nee(o, dd, rays["t_min"], rays["t_max"], spp=1, max_bounces=a.steps - 1, rng_state=_states(n, 3 + mode),
+                                        as_given=True, mode=mode, flags=flags)
+            if i >= a.warmup:
+                t_direct.append(d["stats"].kernel_ms)
+                for m in MODES:
+                    t_fused[m].append(fused[m][3].kernel_ms)
+        ld = _rgb(d["direct"])[step["next"]].mean(1)
+        out[name] = {"direct": {"kernel_ms": best_median(t_direct), "mean": float(ld.mean()), "variance": float(ld.var(ddof=1))}}
+        for m in MODES:
+            lf = fused[m][0].astype(np.float64).mean(1)
+            out[name][m] = {"kernel_ms": best_median(t_fused[m]), "mean": float(lf.mean()), "variance": float(lf.var(ddof=1)),
+                            "shadow_rays": int(fused[m][2].sum())}
+    out["variance_ratio_uniform_over_by_power"] = {k: out["uniform"][k]["variance"] / out["by_power"][k]["variance"]
+                                                   for k in ("direct", *MODES)}
+    p = sc.light_table(_abi.RT_FLAG_LIGHTS_BY_POWER)[1]
+    out["p"] = {"min": float(p.min()), "max": float(p.max())} if len(p) else {}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", default="c2")
@@ -74,12 +120,18 @@ def main():
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--power", action="store_true", help="also time and compare RT_FLAG_LIGHTS_BY_POWER against the uniform pick")
     a = ap.parse_args()
     rt.init()
-    sph, rq = scenes.config(a.config)
+    lamps = a.config == "lamps"
+    sph, rq = (scenes.lamp_room(), _abi.default_request()) if lamps else scenes.config(a.config)
     rq.width, rq.height, rq.divisions, rq.division_no, rq.spp = a.width, a.height, 1, 0, a.spp
     with rt.Scene(0, rt.World(sph)) as sc:
-        rays, states, _ = sc.camera_rays(rq)
+        if lamps:
+            rays = lamp_rays(a.width, a.height, a.spp)
+            states = _states(len(rays), 0)
+        else:
+            rays, states, _ = sc.camera_rays(rq)
         n = len(rays)
         t_step, t_direct = [], []
         for i in range(a.warmup + a.runs):
@@ -130,6 +182,8 @@ def main():
             "within_pixel_variance": {"trace": wa, "nee": wb, "ratio": wa / wb},
             "composed_loop_ms": best_median(t_loop), "trace_ms": best_median(t_trace), "fused": fused_out,
         }
+        if a.power:
+            out["power"] = power_block(sc, a, s, rays, o, dd)
     print(json.dumps(out))
 
 
