@@ -56,7 +56,9 @@ extern "C" {
                                   (4, additions only: next-event estimation for caller rays rt_scene_trace_nee /
                                      rt_scene_trace_nee_device with rt_nee_request, RT_NEE_*)
                                   (4, additions only: light selection by power RT_FLAG_LIGHTS_BY_POWER for rt_scene_direct* and
-                                     rt_scene_trace_nee*, rt_scene_light_table) */
+                                     rt_scene_trace_nee*, rt_scene_light_table)
+                                  (4, additions only: cone sampling of sphere lights RT_LIGHTS_AREA / RT_LIGHTS_CONE with
+                                     rt_scene_set_light_sampling / rt_scene_light_sampling) */
 
 /* ---- status codes --------------------------------------------------------------- */
 typedef enum rt_status {
@@ -535,7 +537,8 @@ RT_API int rt_scene_bounce_device(rt_scene* scene, const rt_bounce_request* req,
  *     h2d_ms (hits, states, the list) and d2h_ms (states, samples) of the host form; n_launches; engine (as for rt_scene_intersect).
  *   - Limits: the estimate equals ray_color's next bounce in expectation only at a hit of roughness 0.  A hit point inside an emissive
  *     sphere sees that sphere as dark (cl <= 0).  A caller who adds the estimate drops the RT_BOUNCE_EMITTED term of the FOLLOWING
- *     step, or the light is counted twice.
+ *     step, or the light is counted twice.  The area estimator's cs * cl / d2 has no bound next to a light; for sphere lights that
+ *     limit is lifted under RT_LIGHTS_CONE (below).
  *   - Light selection by power: the emitter above is picked uniformly.  With RT_FLAG_LIGHTS_BY_POWER in req->flags it is picked from
  *     the scene's light table, made once by rt_scene_create.  For emitter k = 0 .. M - 1 of the list, in its order:
  *       lum_k = ((ar + ag) + ab) * emission;  area_k = (4 * (r*r)) * PI for a sphere, A + A for a triangle (A as in the estimate: it
@@ -551,7 +554,35 @@ RT_API int rt_scene_bounce_device(rt_scene* scene, const rt_bounce_request* req,
  *     ip_k takes the place of (float)M in W, and nothing else changes:
  *       sphere light:   W = ((cs * cl) * ((4 * (r*r)) * ip_k)) / d2;      triangle light: W = ((cs * cl) * (A * ip_k)) / (PI * d2).
  *     rt_scene_light_table() reports every p_k.
- * No per-scene scratch on the device: launches on different streams may overlap.  (DESIGN.md 4.17, 4.19.) */
+ *   - Cone sampling of sphere lights: how a sphere light is sampled is a property of the SCENE, like its camera:
+ *     rt_scene_set_light_sampling(scene, RT_LIGHTS_AREA | RT_LIGHTS_CONE).  The default is RT_LIGHTS_AREA, the sample above, every
+ *     byte of every output.  The setting is read when a call is enqueued and only selects the kernel instance: work already enqueued
+ *     keeps the setting it was enqueued with; rt_scene_set_light_sampling must not race with other calls on the same scene.  Only
+ *     rt_scene_direct* and rt_scene_trace_nee* read it; every other call ignores it.  Under RT_LIGHTS_CONE everything not listed
+ *     here is as above — the pick, uniform or by power; the active list; the statuses; the shadow ray's window and flags:
+ *       A triangle light is untouched in every byte.  A sphere light (c, r) takes the same draws: the accepted pair x1, x2 with
+ *       s = x1*x1 + x2*x2, so the state written back never depends on the setting.
+ *       Regime: a = c - P per component; dc2 = a.a; r2 = r*r; q = r2 / dc2.  The sample is a CONE sample when q >= 0x1p-10f && q < 1.0f;
+ *         otherwise it is the area sample above in every field (a NaN, a hit point inside or on the sphere, radius 0, a far small
+ *         light, dc2 equal to 0 or inf).
+ *       Cone: ctm = sqrt(1 - q); omc = q / (1 + ctm) (1 - cos(theta_max) without cancellation); e = s * omc; ct = 1 - e;
+ *         st = sqrt(e * (2 - e)); rs = sqrt(s); cp = s > 0 ? x1 / rs : 0; sp = s > 0 ? x2 / rs : 0.
+ *       Frame about the axis (Duff et al. 2017, branch-free): dc = sqrt(dc2); w = a / dc per component; sg = copysignf(1, w.z);
+ *         A = -1 / (sg + w.z); B = (w.x * w.y) * A; t1 = (1 + (sg * (w.x * w.x)) * A, sg * B, -(sg * w.x));
+ *         t2 = (B, sg + (w.y * w.y) * A, -w.y).
+ *       Direction: ka = st * cp; kb = st * sp; v = (ka * t1 + kb * t2) + ct * w per component.  The shadow ray is Ray::new(P, v); its
+ *         direction wn is v normalised by division, as everywhere.  cs = n.wn; !(cs > 0): RT_DIRECT_FACING_AWAY, no ray traced.  There
+ *         is no cl test: every direction of the cone meets the front of the sphere.
+ *       Visibility: unchanged, RT_DIRECT_LIT exactly when the closest hit is emitter k.
+ *       Weight: W = (cs * (omc + omc)) * ip, ip = (float)M, or ip_k under RT_FLAG_LIGHTS_BY_POWER; rgb = (albedo * emission) * W.
+ *         W is cs * Omega / pi / p_k with Omega the cone's solid angle: W <= 2 * ip always.
+ *       l*: where the direction meets the sphere: h = r2 - dc2 * (st * st); h = h > 0 ? h : 0; ts = dc * ct - sqrt(h);
+ *         L = P + ts * wn per component; written for every status that writes l* above.
+ *     Consequences: the written-back states equal RT_LIGHTS_AREA's; a scene with no sphere emitter gives RT_LIGHTS_AREA's bytes.
+ *     Limit: rounding can push a direction on the very rim of the cone past the sphere; that sample reads RT_DIRECT_OCCLUDED although
+ *     nothing occludes it, which slightly darkens the estimate.  The regime's threshold keeps the share of such samples below 2^-14
+ *     (tests/test_cone_host.py measures it); below the threshold the area sample, which has no such rim, is used.
+ * No per-scene scratch on the device: launches on different streams may overlap.  (DESIGN.md 4.17, 4.19, 4.20.) */
 typedef struct rt_direct_request { uint32_t flags; uint32_t reserved; float t_min, t_max; } rt_direct_request; /* 16 bytes */
 typedef struct rt_direct { float r, g, b; uint32_t light; float lx, ly, lz; uint32_t status; } rt_direct;      /* 32 bytes */
 enum { RT_DIRECT_LIT = 0u, RT_DIRECT_OCCLUDED = 1u, RT_DIRECT_FACING_AWAY = 2u, RT_DIRECT_NO_LIGHTS = 3u, RT_DIRECT_SKIPPED = 4u };
@@ -570,6 +601,12 @@ RT_API int rt_scene_direct(rt_scene* scene, const rt_direct_request* req, const 
  * scene's stream); counters and event times accumulate in the scene until rt_scene_collect(). */
 RT_API int rt_scene_direct_device(rt_scene* scene, const rt_direct_request* req, const void* d_hits, uint32_t n, void* d_rng_state,
                                   const void* d_active, const void* d_n_active, void* d_out, void* hip_stream);
+/* How rt_scene_direct* and rt_scene_trace_nee* sample the scene's sphere lights ("cone sampling of sphere lights" above): over the
+ * whole sphere (the default), or over the cone it subtends from the hit point.  sampling > 1 or a NULL scene: RT_ERR_BAD_ARG.  Host
+ * only: no GPU work, no synchronisation. */
+enum { RT_LIGHTS_AREA = 0u, RT_LIGHTS_CONE = 1u };
+RT_API int rt_scene_set_light_sampling(rt_scene* scene, uint32_t sampling);
+RT_API int rt_scene_light_sampling(rt_scene* scene, uint32_t* out_sampling);
 
 /* ---- next-event estimation: the integrator of the path steps and the light samples, in one kernel -------- */
 /* The integrator a caller composes from rt_scene_bounce* and rt_scene_direct* — a path of at most K = max_bounces + 1 segments with one
@@ -605,7 +642,8 @@ RT_API int rt_scene_direct_device(rt_scene* scene, const rt_direct_request* req,
  *                               samplable, RT_NEE_MIS:         wb = 1.0f - 1.0f / (1.0f + W');  c = c + T * (e * wb).
  *                             The sample ends.
  *     W is (cs / pi) / p_light = p_bsdf / p_light, so wl and wb are the balance heuristic's weights, and the area estimator's unbounded
- *     cs * cl / d2 becomes Le * W / (1 + W) <= Le.
+ *     cs * cl / d2 becomes Le * W / (1 + W) <= Le.  RT_NEE_LIGHT_ONLY keeps the unbounded term; for sphere lights that limit is lifted
+ *     under RT_LIGHTS_CONE (below), where W <= 2 * ip.
  *   - RT_NEE_LIGHT_ONLY is, bit for bit, the fold above over rt_scene_bounce and rt_scene_direct called per step.
  *   - out_segments (n u32, optional): the ray's path segments, summed over its samples; with M == 0 they and the written-back states
  *     are rt_scene_trace's for the same arguments.  out_shadow (n u32, optional): its shadow rays.
@@ -619,8 +657,19 @@ RT_API int rt_scene_direct_device(rt_scene* scene, const rt_direct_request* req,
  *     pick from the light table, ip_k in W), and in the RT_BOUNCE_EMITTED branch W' takes ip_j of the emitter j that was hit in the
  *     place of (float)M.  wl and wb are unchanged: W is still p_bsdf / p_light.  RT_NEE_LIGHT_ONLY stays, bit for bit, the fold over
  *     rt_scene_bounce and rt_scene_direct with the flag.
+ *   - Cone sampling of sphere lights: when the scene's setting is RT_LIGHTS_CONE (rt_scene_set_light_sampling) every light sample is
+ *     rt_scene_direct's under that setting, and the RT_BOUNCE_EMITTED branch, for an emitter j that is a sphere (c_j, r) with k != 0
+ *     and sampled, views the point as the cone sample of the hit before saw it.  With o the segment's origin, which is exactly the
+ *     previous hit point: a' = c_j - o; dc2' = a'.a'; q' = (r*r) / dc2'.  If q' is in the cone regime (q' >= 0x1p-10f && q' < 1.0f):
+ *     cs' = n.d; the point is SAMPLABLE exactly when cs' > 0; omc' = q' / (1 + sqrt(1 - q')); W' = (cs' * (omc' + omc')) * ip_j
+ *     (ip_j = (float)M without RT_FLAG_LIGHTS_BY_POWER).  Otherwise, and for triangles, the view above applies unchanged.  The regime
+ *     depends only on the point and the emitter, so the sample taken at P and the view from o = P speak of the same p_light; wl and
+ *     wb stay the balance heuristic's weights.  RT_NEE_LIGHT_ONLY under RT_LIGHTS_CONE stays, bit for bit, the fold over
+ *     rt_scene_bounce and rt_scene_direct under RT_LIGHTS_CONE.  out_segments and the written-back states equal RT_LIGHTS_AREA's: the
+ *     path never depends on the light sample; out_shadow and the colours differ.  A scene with no sphere emitter gives RT_LIGHTS_AREA's
+ *     bytes.  The rim limit of rt_scene_direct's cone sample applies.
  *   - Limits: a hit with roughness > 0 takes no light sample (it falls back to the bounce, which is unbiased).
- * No per-scene scratch on the device: launches on different streams may overlap.  (DESIGN.md 4.18, 4.19.) */
+ * No per-scene scratch on the device: launches on different streams may overlap.  (DESIGN.md 4.18, 4.19, 4.20.) */
 typedef struct rt_nee_request {
     uint32_t spp;               /* samples per ray, 1 .. RT_MAX_SPP                                        */
     uint32_t max_bounces;       /* 0 .. RT_MAX_BOUNCES; at most max_bounces + 1 path segments, as rt_scene_trace */

@@ -191,6 +191,8 @@ struct rt_scene {
     std::vector<float> light_p;
     rtplan::Pose pose;              // the job's placed camera (rt_scene_set_camera); read when a call is enqueued
     bool has_pose = false;          //   false: the reference camera
+    uint32_t light_sampling = RT_LIGHTS_AREA;   // how a sphere light is sampled (rt_scene_set_light_sampling); read when a direct-lighting
+                                                //   or NEE call is enqueued, where it picks the kernel instance
     float4* d_geom = nullptr;
     float4* d_geom_pk = nullptr;
     float4* d_geom_px = nullptr;   // expanded-form broad phase records
@@ -589,6 +591,8 @@ void light_refs(const rt_scene* sc, P& p) {
 
 // RT_FLAG_LIGHTS_BY_POWER picks the kernel instance; it is no business of the plan (rt_plan.h), which never sees an engine in it.
 static bool lights_by_power(uint32_t flags) { return (flags & RT_FLAG_LIGHTS_BY_POWER) != 0; }
+// ... and so does the scene's light sampling (rt_scene_set_light_sampling)
+static bool lights_cone(const rt_scene* sc) { return sc->light_sampling == RT_LIGHTS_CONE; }
 
 // Enqueue one launch of persistent waves over `items` in workgroups of `block` on `stream` (caller holds sc->mu, device current),
 // the block `p` complete.  The launches of the caller-ray calls, the feature buffers and the camera rays all end here.  what: the
@@ -1396,11 +1400,11 @@ static int launch_direct(rt_scene* sc, const rt_direct_request* rq, const void* 
     light_refs(sc, p);
     p.t_min = rq->t_min;
     p.t_max = rq->t_max;
-    return launch_rays(sc, qp, rtplan::QUERY_BLOCK, rtk::direct_kernel(qp.engine, qp.scan_mode, lights_by_power(rq->flags)), "direct-lighting", p,
+    return launch_rays(sc, qp, rtplan::QUERY_BLOCK, rtk::direct_kernel(qp.engine, qp.scan_mode, lights_by_power(rq->flags), lights_cone(sc)), "direct-lighting", p,
                        std::max<uint32_t>(count, 1u),
                        vtext("direct: engine %d  scan mode %d  lds %zu B  ", qp.engine, qp.scan_mode, qp.lds),
-                       vtext("records %u  listed %s%u  lights %u%s", n, d_n_active ? "<= " : "", count, sc->n_lights,
-                             lights_by_power(rq->flags) ? " by power" : ""),
+                       vtext("records %u  listed %s%u  lights %u%s%s", n, d_n_active ? "<= " : "", count, sc->n_lights,
+                             lights_by_power(rq->flags) ? " by power" : "", lights_cone(sc) ? " cone" : ""),
                        0, stream);
 }
 
@@ -1419,6 +1423,22 @@ static int rt_scene_light_table_impl(rt_scene* sc, uint32_t flags, uint32_t* out
         if (out_world_index) out_world_index[k] = sc->light_world[k];
         if (out_p) out_p[k] = lights_by_power(flags) ? sc->light_p[k] : 1.0f / (float)M;
     }
+    return RT_OK;
+}
+
+// How the scene's sphere lights are sampled by the calls enqueued from now on; work already enqueued keeps its kernel instance.
+static int rt_scene_set_light_sampling_impl(rt_scene* sc, uint32_t sampling) {
+    if (!sc) return fail(RT_ERR_BAD_ARG, "scene is NULL");
+    if (sampling > RT_LIGHTS_CONE) return fail(RT_ERR_BAD_ARG, "sampling is neither RT_LIGHTS_AREA nor RT_LIGHTS_CONE");
+    std::lock_guard<std::mutex> lk(sc->mu);
+    sc->light_sampling = sampling;
+    return RT_OK;
+}
+
+static int rt_scene_light_sampling_impl(rt_scene* sc, uint32_t* out_sampling) {
+    if (!sc || !out_sampling) return fail(RT_ERR_BAD_ARG, "scene or out_sampling is NULL");
+    std::lock_guard<std::mutex> lk(sc->mu);
+    *out_sampling = sc->light_sampling;
     return RT_OK;
 }
 
@@ -1485,10 +1505,10 @@ static int launch_nee(rt_scene* sc, const rt_nee_request* rq, const void* d_rays
     p.mis = rq->mode == RT_NEE_MIS ? 1u : 0u;
     material_refs(sc, p);
     light_refs(sc, p);
-    return launch_rays(sc, qp, rtplan::QUERY_BLOCK, rtk::nee_kernel(qp.engine, qp.scan_mode, lights_by_power(rq->flags)), "next-event-estimation", p, n,
+    return launch_rays(sc, qp, rtplan::QUERY_BLOCK, rtk::nee_kernel(qp.engine, qp.scan_mode, lights_by_power(rq->flags), lights_cone(sc)), "next-event-estimation", p, n,
                        vtext("nee: engine %d  scan mode %d  lds %zu B  ", qp.engine, qp.scan_mode, qp.lds),
-                       vtext("rays %u  spp %u  bounces %u  mode %u  lights %u%s", n, rq->spp, rq->max_bounces, rq->mode, sc->n_lights,
-                             lights_by_power(rq->flags) ? " by power" : ""),
+                       vtext("rays %u  spp %u  bounces %u  mode %u  lights %u%s%s", n, rq->spp, rq->max_bounces, rq->mode, sc->n_lights,
+                             lights_by_power(rq->flags) ? " by power" : "", lights_cone(sc) ? " cone" : ""),
                        (uint64_t)n * rq->spp, stream);
 }
 
@@ -2515,6 +2535,12 @@ RT_API int rt_scene_light_count(rt_scene* sc, uint32_t* n_lights) {
 }
 RT_API int rt_scene_light_table(rt_scene* sc, uint32_t flags, uint32_t* out_world_index, float* out_p, uint32_t capacity) {
     return guarded([&] { return rt_scene_light_table_impl(sc, flags, out_world_index, out_p, capacity); });
+}
+RT_API int rt_scene_set_light_sampling(rt_scene* sc, uint32_t sampling) {
+    return guarded([&] { return rt_scene_set_light_sampling_impl(sc, sampling); });
+}
+RT_API int rt_scene_light_sampling(rt_scene* sc, uint32_t* out_sampling) {
+    return guarded([&] { return rt_scene_light_sampling_impl(sc, out_sampling); });
 }
 RT_API int rt_scene_direct(rt_scene* sc, const rt_direct_request* rq, const rt_hit* hits, uint32_t n, uint64_t* rng_state, const uint32_t* active,
                            uint32_t n_active, rt_direct* out, rt_tile_stats* stats) {

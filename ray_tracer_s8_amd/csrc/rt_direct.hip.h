@@ -35,8 +35,10 @@ struct DParams : SceneRefs {
     LightTableRefs table;        // RT_FLAG_LIGHTS_BY_POWER (PICK_POWER instances only)
 };
 
-// ENGINE 2: the walk; 1: the scan with consider<MODE> (MODE 0 plain linear semantics, 2 BVH semantics).  PICK: the pick rule.
-template <int ENGINE, int MODE, int PICK>
+// ENGINE 2: the walk; 1: the scan with consider<MODE> (MODE 0 plain linear semantics, 2 BVH semantics).  PICK: the pick rule.  SHAPE: how
+// a sphere light is sampled (the scene's rt_scene_set_light_sampling).  A cone sample has its l* — where its direction meets the
+// sphere — formed before the walk, by light_sample, and its W after it from cs, omc and ip.
+template <int ENGINE, int MODE, int PICK, int SHAPE>
 __global__ __launch_bounds__(256) void rt_direct_kernel(const DParams p) {
     extern __shared__ uint32_t dstack[];                 // [depth + 1][256] (engine 2)
     const uint32_t tid = threadIdx.x;
@@ -56,10 +58,10 @@ __global__ __launch_bounds__(256) void rt_direct_kernel(const DParams p) {
         // ================= the draws: the emitter, then the point on it =================
         Rng rng;
         load_rng(p.rng_state + 4 * i, rng);
-        const LightSample ls = light_sample<PICK>(p, rng);
+        const typename SampleOf<SHAPE>::type ls = light_sample<PICK, SHAPE>(p, rng, P, n);
         store_rng(p.rng_state + 4 * i, rng);
         // ================= the cosines; the shadow ray Ray::new(P, L - P) =================
-        const rtdl::Geometry g = rtdl::light_geometry(dvec(P), dvec(n), ls.L, ls.nl, ls.sphere);
+        const rtdl::Geometry g = sample_geometry(ls, P, n);
         uint32_t status = RT_DIRECT_FACING_AWAY;
         rtdl::Vec rgb{0.0f, 0.0f, 0.0f};
         if (g.facing) {
@@ -71,7 +73,7 @@ __global__ __launch_bounds__(256) void rt_direct_kernel(const DParams p) {
             if (h.idx == (int)ls.prim) {
                 status = RT_DIRECT_LIT;
                 const float4 ma = at32(p.mat, ls.prim);
-                const float W = sample_weight<PICK>(ls, g, p.n_lights);
+                const float W = sample_weight<PICK, SHAPE>(ls, g, p.n_lights);
                 rgb = rtdl::radiance(rtdl::Vec{ma.x, ma.y, ma.z}, at32(p.emis, ls.prim), W);
             }
         }
@@ -82,6 +84,7 @@ __global__ __launch_bounds__(256) void rt_direct_kernel(const DParams p) {
 }
 
 using DirectFn = void (*)(const DParams);
-DirectFn direct_kernel(int engine, int scan_mode, bool by_power);    // rt_kernels_direct.hip; nullptr for a combination that does not exist
+// rt_kernels_direct.hip; cone: the scene's setting is RT_LIGHTS_CONE; nullptr for a combination that does not exist
+DirectFn direct_kernel(int engine, int scan_mode, bool by_power, bool cone);
 
 }  // namespace rtk

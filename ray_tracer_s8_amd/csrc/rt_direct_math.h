@@ -131,6 +131,92 @@ RT_HOST_DEVICE float triangle_weight(float cs, float cl, float A, uint32_t M, fl
 RT_HOST_DEVICE float sphere_weight_ip(float cs, float cl, float r, float ip, float d2) { return ((cs * cl) * ((4.0f * (r * r)) * ip)) / d2; }
 RT_HOST_DEVICE float triangle_weight_ip(float cs, float cl, float A, float ip, float d2) { return ((cs * cl) * (A * ip)) / (PI_F32 * d2); }
 
+// ---- cone sampling of sphere lights (RT_LIGHTS_CONE; rt_tile.h "cone sampling of sphere lights"): a direction in the
+// cone the sphere (c, r) subtends from P, from the accepted pair (x1, x2) of the UnitSphere draw and s = x1 x1 + x2 x2 — s is uniform
+// on [0, 1) and (x1, x2) / sqrt(s) a uniform azimuth, so the sample takes no draw of its own and no transcendental function.
+constexpr float CONE_Q_MIN = 0.0009765625f;      // 2^-10: below it (r / dc < 1/32) the area sample, which has no rim, is used
+
+// The sample of a point with q = r2 / dc2 is a cone sample when 2^-10 <= q < 1; a NaN, a point inside or on the sphere, radius 0,
+// dc2 = 0 or inf are not.
+RT_HOST_DEVICE bool cone_regime(float q) { return q >= CONE_Q_MIN && q < 1.0f; }
+
+// The point as the light sees it: a = c - P, dc2 = a.a, r2 = r r, q = r2 / dc2
+struct ConeAxis {
+    Vec a;
+    float dc2, r2, q;
+};
+RT_HOST_DEVICE ConeAxis cone_axis(Vec P, Vec c, float r) {
+    ConeAxis x;
+    x.a = sub3(c, P);
+    x.dc2 = dot3(x.a, x.a);
+    x.r2 = r * r;
+    x.q = x.r2 / x.dc2;
+    return x;
+}
+
+// omc = 1 - cos(theta_max) without cancellation: ctm = sqrt(1 - q); omc = q / (1 + ctm)
+RT_HOST_DEVICE float cone_omc(float q) {
+    const float ctm = __builtin_sqrtf(1.0f - q);
+    return q / (1.0f + ctm);
+}
+
+struct Cone {
+    Vec v;             // the direction, about unit length: the shadow ray is Ray::new(P, v)
+    float omc;         // 1 - cos(theta_max)
+    float dc2, dc;     // a.a and its root
+    float ct, st;      // cosine and sine of the angle to the axis
+};
+
+// In the regime (cone_regime(cone_axis(P, c, r).q)).  The frame about the axis w = a / dc is Duff et al. 2017, branch-free.
+RT_HOST_DEVICE Cone cone_sample(Vec P, Vec c, float r, float x1, float x2, float s) {
+    const ConeAxis ax = cone_axis(P, c, r);
+    Cone k;
+    k.dc2 = ax.dc2;
+    k.omc = cone_omc(ax.q);
+    const float e = s * k.omc;
+    k.ct = 1.0f - e;
+    k.st = __builtin_sqrtf(e * (2.0f - e));
+    const float rs = __builtin_sqrtf(s);
+    const float cp = s > 0.0f ? x1 / rs : 0.0f;
+    const float sp = s > 0.0f ? x2 / rs : 0.0f;
+    k.dc = __builtin_sqrtf(ax.dc2);
+    const Vec w{ax.a.x / k.dc, ax.a.y / k.dc, ax.a.z / k.dc};
+    const float sg = __builtin_copysignf(1.0f, w.z);
+    const float A = -1.0f / (sg + w.z);
+    const float B = (w.x * w.y) * A;
+    const Vec t1{1.0f + (sg * (w.x * w.x)) * A, sg * B, -(sg * w.x)};
+    const Vec t2{B, sg + (w.y * w.y) * A, -w.y};
+    const float ka = k.st * cp, kb = k.st * sp;
+    k.v = Vec{(ka * t1.x + kb * t2.x) + k.ct * w.x, (ka * t1.y + kb * t2.y) + k.ct * w.y, (ka * t1.z + kb * t2.z) + k.ct * w.z};
+    return k;
+}
+
+// The geometry of a cone sample: wn = v / sqrt(v.v) is the direction Ray::new gives the shadow ray, cs = n.wn, and the sample faces the
+// light exactly when cs > 0 — every direction of the cone meets the front of the sphere, so there is no cl (it is set to 1, unread).
+RT_HOST_DEVICE Geometry cone_geometry(Vec n, Vec v) {
+    Geometry g;
+    g.v = v;
+    g.d2 = dot3(v, v);
+    const float len = __builtin_sqrtf(g.d2);
+    g.w = Vec{v.x / len, v.y / len, v.z / len};
+    g.cs = dot3(n, g.w);
+    g.cl = 1.0f;
+    g.facing = g.cs > 0.0f;
+    return g;
+}
+
+// W = (cs (omc + omc)) ip: cs Omega / pi over p_k, Omega = 2 pi omc the cone's solid angle; at most 2 ip.  ip = (float)M for the
+// uniform pick.
+RT_HOST_DEVICE float cone_weight(float cs, float omc, float ip) { return (cs * (omc + omc)) * ip; }
+
+// Where the direction wn meets the sphere: h = r2 - dc2 (st st), clamped at 0; ts = dc ct - sqrt(h); L = P + ts wn
+RT_HOST_DEVICE Vec cone_point(Vec P, Vec wn, float r, const Cone& k) {
+    float h = r * r - k.dc2 * (k.st * k.st);
+    h = h > 0.0f ? h : 0.0f;
+    const float ts = k.dc * k.ct - __builtin_sqrtf(h);
+    return Vec{P.x + ts * wn.x, P.y + ts * wn.y, P.z + ts * wn.z};
+}
+
 // rgb = (albedo * emission) * W per channel
 RT_HOST_DEVICE Vec radiance(Vec albedo, float emission, float W) {
     return Vec{(albedo.x * emission) * W, (albedo.y * emission) * W, (albedo.z * emission) * W};

@@ -55,7 +55,9 @@ __device__ __forceinline__ float light_size(const P& p, uint32_t prim) {
 
 // ENGINE 2: the walk; 1: the scan with consider<MODE> (MODE 0 plain linear semantics, 2 BVH semantics).  PICK: the pick rule, which
 // also decides what stands for (float)M in W and in W' (the inverse probability of the emitter sampled, and of the emitter hit).
-template <int ENGINE, int MODE, int PICK>
+// SHAPE: how a sphere light is sampled (the scene's rt_scene_set_light_sampling); SHAPE_CONE also views an emissive sphere the bounce
+// reached from the segment's origin o — exactly the previous hit point — so that W' speaks of the p_light the sample there had.
+template <int ENGINE, int MODE, int PICK, int SHAPE>
 __global__ __launch_bounds__(256) void rt_nee_kernel(const NParams p) {
     extern __shared__ uint32_t nstack[];                 // [depth + 1][256] (engine 2)
     const uint32_t tid = threadIdx.x, bs = blockDim.x;
@@ -109,8 +111,24 @@ __global__ __launch_bounds__(256) void rt_nee_kernel(const NParams p) {
                     if (k != 0 && sampled) {
                         // the light strategy's view of this point: could the sample of the step before have drawn it?
                         const bool sphere = prim < p.n_sph;
+                        bool cone_view = false;
+                        if (SHAPE == SHAPE_CONE && sphere) {
+                            const float4 g = at32(p.geom_r, prim);
+                            const rtnee::ConeView cv = rtnee::emitter_view_cone(dvec(o), dvec(n_prev), dvec(d), rtdl::Vec{g.x, g.y, g.z}, g.w);
+                            cone_view = cv.in_regime;
+                            if (cv.samplable) {
+                                add_it = p.mis != 0;                                   // LIGHT_ONLY: that sample stood for it
+                                if (add_it) {
+                                    const float wb = rtnee::bounce_weight(
+                                        rtnee::cone_view_weight(cv, PICK == PICK_POWER ? p.table.light_ip[prim] : (float)p.n_lights));
+                                    ex = ex * wb;
+                                    ey = ey * wb;
+                                    ez = ez * wb;
+                                }
+                            }
+                        }
                         const rtnee::View v = rtnee::emitter_view(dvec(n_prev), dvec(d), dvec(nh), h.dist, sphere);
-                        if (v.samplable) {
+                        if (!cone_view && v.samplable) {
                             add_it = p.mis != 0;                                       // LIGHT_ONLY: that sample stood for it
                             if (add_it) {
                                 const float size = light_size(p, prim);
@@ -144,11 +162,11 @@ __global__ __launch_bounds__(256) void rt_nee_kernel(const NParams p) {
                 sampled = ma.w == 0.0f && p.n_lights > 0;
                 if (!sampled) continue;
                 // ================= one light sample, as rt_scene_direct specifies it for the record (P, n, prim) =================
-                const LightSample ls = light_sample<PICK>(p, rng);
-                const rtdl::Geometry g = rtdl::light_geometry(dvec(hp), dvec(nh), ls.L, ls.nl, ls.sphere);
+                const typename SampleOf<SHAPE>::type ls = light_sample<PICK, SHAPE>(p, rng, hp, nh);
+                const rtdl::Geometry g = sample_geometry(ls, hp, nh);
                 if (!g.facing) continue;                                               // FACING_AWAY: no ray, straight on
                 const float4 la = at32(p.mat, ls.prim);
-                const float W = sample_weight<PICK>(ls, g, p.n_lights);
+                const float W = sample_weight<PICK, SHAPE>(ls, g, p.n_lights);
                 rtdl::Vec D = rtdl::radiance(rtdl::Vec{la.x, la.y, la.z}, at32(p.emis, ls.prim), W);
                 if (p.mis) {
                     const float wl = rtnee::light_weight(W);
@@ -176,6 +194,7 @@ __global__ __launch_bounds__(256) void rt_nee_kernel(const NParams p) {
 }
 
 using NeeFn = void (*)(const NParams);
-NeeFn nee_kernel(int engine, int scan_mode, bool by_power);    // rt_kernels_nee.hip; nullptr for a combination that does not exist
+// rt_kernels_nee.hip; cone: the scene's setting is RT_LIGHTS_CONE; nullptr for a combination that does not exist
+NeeFn nee_kernel(int engine, int scan_mode, bool by_power, bool cone);
 
 }  // namespace rtk

@@ -42,4 +42,26 @@ RT_HOST_DEVICE float view_weight_ip(const View& v, bool sphere, float size, floa
     return sphere ? rtdl::sphere_weight_ip(v.cs, v.cl, size, ip, v.d2) : rtdl::triangle_weight_ip(v.cs, v.cl, size, ip, v.d2);
 }
 
+// ---- cone sampling of sphere lights (RT_LIGHTS_CONE): the view of an emissive sphere (c, r) the bounce reached from
+// the point o with the normal n there, d the unit direction of the segment.  The regime depends on o and the sphere alone, so the
+// light sample taken at o and this view speak of the same p_light.  Not in the regime: the caller takes emitter_view above.
+struct ConeView {
+    float cs, omc;      // n . d;  1 - cos(theta_max) of the sphere seen from o
+    bool in_regime;     // rtdl::cone_regime(q') of q' = r2 / dc2'
+    bool samplable;     // in the regime and cs > 0: the cone sample could have drawn this direction
+};
+
+RT_HOST_DEVICE ConeView emitter_view_cone(rtdl::Vec o, rtdl::Vec n, rtdl::Vec d, rtdl::Vec c, float r) {
+    ConeView v;
+    const rtdl::ConeAxis ax = rtdl::cone_axis(o, c, r);
+    v.in_regime = rtdl::cone_regime(ax.q);
+    v.cs = rtdl::dot3(n, d);
+    v.omc = v.in_regime ? rtdl::cone_omc(ax.q) : 0.0f;
+    v.samplable = v.in_regime && v.cs > 0.0f;
+    return v;
+}
+
+// W' of that view: (cs' (omc' + omc')) ip_j, ip = (float)M for the uniform pick
+RT_HOST_DEVICE float cone_view_weight(const ConeView& v, float ip) { return rtdl::cone_weight(v.cs, v.omc, ip); }
+
 }  // namespace rtnee

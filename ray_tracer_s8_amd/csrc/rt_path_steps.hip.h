@@ -210,12 +210,36 @@ struct LightTableRefs {
     float light_total;           // light_c[n_lights - 1]; not positive and finite: the table is degenerate, the pick uniform
 };
 
-// One light sample drawn from rng (p.n_lights > 0): the emitter picked with one u01 — uniformly, or by power — then a point on it: the
+// How a sphere light is sampled: over its whole area, or over the cone it subtends from the hit point when the scene's setting is
+// RT_LIGHTS_CONE (rt_scene_set_light_sampling).  A template parameter beside PICK for the same reason: the SHAPE_AREA
+// instances are the code they were before the setting existed; the regime test exists in the SHAPE_CONE instances only.
+enum { SHAPE_AREA = 0, SHAPE_CONE = 1 };
+
+// The sample of a SHAPE_CONE instance.  Its geometry g is formed inside the arm that drew it — rtdl::cone_geometry of the direction for a
+// sphere light in the cone regime (cone; omc its 1 - cos(theta_max); L where the direction meets the sphere), rtdl::light_geometry of
+// the point otherwise — so that only g, not the operands of both arms, is live where the arms meet.
+struct ConeLightSample : LightSample {
+    bool cone;
+    float omc;
+    rtdl::Geometry g;
+};
+template <int SHAPE>
+struct SampleOf {
+    using type = LightSample;
+};
+template <>
+struct SampleOf<SHAPE_CONE> {
+    using type = ConeLightSample;
+};
+
+// One light sample for the hit point P, drawn from rng (p.n_lights > 0): the emitter picked with one u01 — uniformly, or by power — then a point on it: the
 // UnitSphere draw of a scattering hit for a sphere light, two u01 for a triangle light.  P: a parameter block with lights / n_lights
-// (and, for PICK_POWER, table: LightTableRefs).
-template <int PICK, class P>
-__device__ __forceinline__ LightSample light_sample(const P& p, Rng& rng) {
-    LightSample s;
+// (and, for PICK_POWER, table: LightTableRefs).  SHAPE_CONE takes the same draws — the cone arm reuses the accepted pair — so the state
+// a sample leaves never depends on SHAPE; the hit (hp, n) is read by SHAPE_CONE only.
+template <int PICK, int SHAPE, class P>
+__device__ __forceinline__ typename SampleOf<SHAPE>::type light_sample(const P& p, Rng& rng, V3 hp, V3 n) {
+    typename SampleOf<SHAPE>::type s;
+    if constexpr (SHAPE == SHAPE_CONE) s.cone = false;
     const float u = u01(rng);
     uint32_t pick;
     if (PICK == PICK_POWER) pick = rtdl::pick_light_power(u, p.n_lights, p.table.light_c, p.table.light_total);
@@ -227,6 +251,17 @@ __device__ __forceinline__ LightSample light_sample(const P& p, Rng& rng) {
         const float4 g = at32(p.geom_r, s.prim);
         float x1, x2, sm;
         unit_sphere_pair(rng, x1, x2, sm);
+        if constexpr (SHAPE == SHAPE_CONE) {
+            if (rtdl::cone_regime(rtdl::cone_axis(dvec(hp), rtdl::Vec{g.x, g.y, g.z}, g.w).q)) {
+                const rtdl::Cone cn = rtdl::cone_sample(dvec(hp), rtdl::Vec{g.x, g.y, g.z}, g.w, x1, x2, sm);
+                s.cone = true;
+                s.omc = cn.omc;
+                s.g = rtdl::cone_geometry(dvec(n), cn.v);
+                s.L = rtdl::cone_point(dvec(hp), s.g.w, g.w, cn);
+                s.size = g.w;
+                return s;
+            }
+        }
         s.nl = dvec(unit_sphere_vec(x1, x2, sm));
         s.L = rtdl::sphere_point(rtdl::Vec{g.x, g.y, g.z}, g.w, s.nl);
         s.size = g.w;
@@ -239,13 +274,23 @@ __device__ __forceinline__ LightSample light_sample(const P& p, Rng& rng) {
         s.nl = dvec(hit_normal(p, s.prim, mk(0.f, 0.f, 0.f)));                         // (a triangle's normal does not read the point)
         s.size = rtdl::triangle_area(A, B, C);
     }
+    if constexpr (SHAPE == SHAPE_CONE) s.g = rtdl::light_geometry(dvec(hp), dvec(n), s.L, s.nl, s.sphere);
     return s;
 }
 
-// W of the sample s seen under the geometry g = rtdl::light_geometry(P, n, s.L, s.nl, s.sphere): radiance(albedo, emission, W) is the
-// estimate, and the MIS weight of the light strategy reads W itself.  PICK_POWER: s.ip in the place of (float)n_lights.
-template <int PICK>
-__device__ __forceinline__ float sample_weight(const LightSample& s, const rtdl::Geometry& g, uint32_t n_lights) {
+// The geometry of the sample s at the hit (P, n): rtdl::light_geometry of its point, or rtdl::cone_geometry of its direction.
+__device__ __forceinline__ rtdl::Geometry sample_geometry(const LightSample& s, V3 hp, V3 n) {
+    return rtdl::light_geometry(dvec(hp), dvec(n), s.L, s.nl, s.sphere);
+}
+__device__ __forceinline__ rtdl::Geometry sample_geometry(const ConeLightSample& s, V3, V3) { return s.g; }
+
+// W of the sample s seen under the geometry g = sample_geometry(s, P, n): radiance(albedo, emission, W) is the estimate, and the MIS
+// weight of the light strategy reads W itself.  PICK_POWER: s.ip in the place of (float)n_lights.
+template <int PICK, int SHAPE>
+__device__ __forceinline__ float sample_weight(const typename SampleOf<SHAPE>::type& s, const rtdl::Geometry& g, uint32_t n_lights) {
+    if constexpr (SHAPE == SHAPE_CONE) {
+        if (s.cone) return rtdl::cone_weight(g.cs, s.omc, PICK == PICK_POWER ? s.ip : (float)n_lights);
+    }
     if (PICK == PICK_POWER)
         return s.sphere ? rtdl::sphere_weight_ip(g.cs, g.cl, s.size, s.ip, g.d2) : rtdl::triangle_weight_ip(g.cs, g.cl, s.size, s.ip, g.d2);
     return s.sphere ? rtdl::sphere_weight(g.cs, g.cl, s.size, n_lights, g.d2) : rtdl::triangle_weight(g.cs, g.cl, s.size, n_lights, g.d2);

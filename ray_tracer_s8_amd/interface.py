@@ -388,6 +388,19 @@ class Scene:
                                                   p.ctypes.data_as(C.POINTER(C.c_float)), m), "rt_scene_light_table")
         return wi, p
 
+    def set_light_sampling(self, sampling: int):
+        """How later direct() and trace_nee() calls sample the scene's sphere lights (rt_scene_set_light_sampling): _abi.RT_LIGHTS_AREA,
+        over the whole sphere (the default), or _abi.RT_LIGHTS_CONE, over the cone the sphere subtends from the hit point.  Work already
+        enqueued keeps the setting it was enqueued with; every other call ignores it."""
+        _abi.check(self._lib.rt_scene_set_light_sampling(self._h, sampling), "rt_scene_set_light_sampling")
+
+    @property
+    def light_sampling(self) -> int:
+        """The scene's light sampling (rt_scene_light_sampling): RT_LIGHTS_AREA or RT_LIGHTS_CONE."""
+        v = C.c_uint32(0)
+        _abi.check(self._lib.rt_scene_light_sampling(self._h, C.byref(v)), "rt_scene_light_sampling")
+        return int(v.value)
+
     def direct(self, hits, rng_state, active=None, t_min: float = 0.001, t_max: float = 1000.0, flags: int = 0):
         """Direct lighting of caller rays (rt_scene_direct): one light sample for each active hit record — an emitter picked with one
         u01 of the ray's state, a point on it, the shadow ray within [t_min, t_max) and the Lambertian estimate without the surface

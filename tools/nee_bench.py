@@ -15,10 +15,14 @@ it buys, on the camera rays of a benchmark scene (default c2, cornell16).
   power     (--power) light selection by power, RT_FLAG_LIGHTS_BY_POWER, beside the uniform pick on the same rays and states in the same
             run: HIP-event time of rt_scene_direct on the first step's hits and of rt_scene_trace_nee in both modes (best and median
             of --runs after --warmup), the mean and the variance of the samples' luminance, and the variance ratio uniform / by power.
+  cone      (--cone) cone sampling of sphere lights, RT_LIGHTS_CONE, beside RT_LIGHTS_AREA on the same rays and states in the same run
+            (with --power: both under RT_FLAG_LIGHTS_BY_POWER): HIP-event time of rt_scene_direct on the first step's hits and of
+            rt_scene_trace_nee in both modes (best and median of --runs after --warmup), the mean and the variance of the samples'
+            luminance, the variance ratio area / cone and, per setting, the ratio rt_scene_trace / mode.
 
 --config lamps is the many-light scene scenes.lamp_room() (one lamp, 32 dim emitters) under its fixed pinhole rays.
 
-    python tools/nee_bench.py [--config c2 | lamps] [--width 480 --height 270 --spp 4] [--steps 4] [--power]
+    python tools/nee_bench.py [--config c2 | lamps] [--width 480 --height 270 --spp 4] [--steps 4] [--power] [--cone]
 Prints one JSON line."""
 import argparse
 import json
@@ -111,6 +115,39 @@ def power_block(sc, a, step, rays, o, dd):
     return out
 
 
+def cone_block(sc, a, step, rays, o, dd, trace_var):
+    """RT_LIGHTS_AREA and RT_LIGHTS_CONE side by side: the light samples of the first step's scattered hits, and the integrator in both
+    modes, on the same rays and the same states.  The scene is left at RT_LIGHTS_AREA."""
+    n = len(rays)
+    flags = _abi.RT_FLAG_LIGHTS_BY_POWER if a.power else 0
+    best_median = lambda t: {"best": min(t), "median": statistics.median(t)}
+    out = {"flags": "by_power" if a.power else "uniform"}
+    for name, setting in (("area", _abi.RT_LIGHTS_AREA), ("cone", _abi.RT_LIGHTS_CONE)):
+        sc.set_light_sampling(setting)
+        t_direct, t_fused, fused = [], {m: [] for m in MODES}, {}
+        for i in range(a.warmup + a.runs):
+            d = sc.direct(step["hits"], step["states"], active=step["next"], flags=flags)
+            for m, mode in MODES.items():
+                fused[m] = sc.trace_nee(o, dd, rays["t_min"], rays["t_max"], spp=1, max_bounces=a.steps - 1, rng_state=_states(n, 3 + mode),
+                                        as_given=True, mode=mode, flags=flags)
+            if i >= a.warmup:
+                t_direct.append(d["stats"].kernel_ms)
+                for m in MODES:
+                    t_fused[m].append(fused[m][3].kernel_ms)
+        rec = d["direct"][step["next"]]
+        ld = _rgb(rec).mean(1)
+        out[name] = {"direct": {"kernel_ms": best_median(t_direct), "mean": float(ld.mean()), "variance": float(ld.var(ddof=1)),
+                                "largest": float(ld.max()), "shadow_rays": int(d["stats"].ray_segments),
+                                "facing_away": int((rec["status"] == _abi.RT_DIRECT_FACING_AWAY).sum())}}
+        for m in MODES:
+            lf = fused[m][0].astype(np.float64).mean(1)
+            out[name][m] = {"kernel_ms": best_median(t_fused[m]), "mean": float(lf.mean()), "variance": float(lf.var(ddof=1)),
+                            "variance_ratio_trace_over_mode": trace_var / float(lf.var(ddof=1)), "shadow_rays": int(fused[m][2].sum())}
+    sc.set_light_sampling(_abi.RT_LIGHTS_AREA)
+    out["variance_ratio_area_over_cone"] = {k: out["area"][k]["variance"] / out["cone"][k]["variance"] for k in ("direct", *MODES)}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", default="c2")
@@ -121,6 +158,7 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--power", action="store_true", help="also time and compare RT_FLAG_LIGHTS_BY_POWER against the uniform pick")
+    ap.add_argument("--cone", action="store_true", help="also time and compare RT_LIGHTS_CONE against RT_LIGHTS_AREA (with --power: by power)")
     a = ap.parse_args()
     rt.init()
     lamps = a.config == "lamps"
@@ -184,6 +222,8 @@ def main():
         }
         if a.power:
             out["power"] = power_block(sc, a, s, rays, o, dd)
+        if a.cone:
+            out["cone"] = cone_block(sc, a, s, rays, o, dd, float(la.var(ddof=1)))
     print(json.dumps(out))
 
 
