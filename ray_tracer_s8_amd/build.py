@@ -63,7 +63,8 @@ def _deps() -> list[Path]:
 FLAGS_PATH = LIB_PATH.with_suffix(".flags")      # the exact compile lines of the library next to it
 
 # The TEST library: the product sources plus -DRT_DEBUG_HOOKS, which compiles the rt_debug_* entry points (launch-path knobs,
-# counter read-back, a throwing body, the sqrt self-test, the unit kernel of rt_unit.hip.h) that tests and tools use.
+# counter read-back, a throwing body, the sqrt self-test, the unit kernels of rt_unit.hip.h and rt_unit_sampling.hip.h) that tests
+# and tools use.
 # The product library exports exactly include/rt_tile.h (tests/test_abi.py checks both).
 DEBUG_VARIANT = "dbg"
 DEBUG_FLAGS = ["-DRT_DEBUG_HOOKS"]

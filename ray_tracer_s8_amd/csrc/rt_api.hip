@@ -39,7 +39,7 @@
 #include "rt_denoise.hip.h"
 #include "rt_tile.h"
 #ifdef RT_DEBUG_HOOKS
-#include "rt_unit.hip.h"      // record sizes and launchers of the unit kernel (rt_debug_unit)
+#include "rt_unit.hip.h"      // record sizes and launchers of the unit kernels, rt_unit_sampling.hip.h's too (rt_debug_unit)
 #endif
 
 namespace {
@@ -1938,16 +1938,16 @@ extern "C" __attribute__((visibility("default"))) int rt_debug_sqrt_selftest(int
         return RT_OK;
     });
 }
-// debug: the device functions of the closest-hit arithmetic, one lane per record (rt_unit.hip.h: families and record layouts), as
-// translation unit `unit` compiles them (0 lin, 1 trav, 2 query).  in: n records of unit_words_in(family) 32-bit words, out: n records
-// of unit_words_out(family) words; one launch, returns after synchronising.  Tests only; not part of rt_tile.h.
+// debug: the device functions of the closest-hit arithmetic (rt_unit.hip.h) and of the light-sampling and scatter arithmetic
+// (rt_unit_sampling.hip.h), one lane per record, as translation unit `unit` compiles them; a (unit, family) pair that is not
+// instantiated is RT_ERR_BAD_ARG before any device work.  One launch, returns after synchronising.  Tests only; not in rt_tile.h.
 extern "C" __attribute__((visibility("default"))) int rt_debug_unit(int device, int unit, int family, unsigned long long n,
                                                                     const void* in, void* out) {
     return guarded([&]() -> int {
-        if (unit < 0 || unit > 2 || family < 0 || family >= rtk::UNIT_FAMILIES) return fail(RT_ERR_BAD_ARG, "unit / family");
+        if (!rtk::unit_instantiated(unit, family)) return fail(RT_ERR_BAD_ARG, "unit / family");
         if (n == 0) return RT_OK;
         if (!in || !out || n > (1ull << 24)) return fail(RT_ERR_BAD_ARG, "unit records");
-        const size_t bi = (size_t)n * rtk::unit_words_in(family) * 4, bo = (size_t)n * rtk::unit_words_out(family) * 4;
+        const size_t bi = (size_t)n * rtk::unit_record_in(family) * 4, bo = (size_t)n * rtk::unit_record_out(family) * 4;
         HIPCHK(hipSetDevice(device));
         uint32_t *d_in = nullptr, *d_out = nullptr;
         hipError_t e = hipMalloc(&d_in, bi);
@@ -1955,7 +1955,7 @@ extern "C" __attribute__((visibility("default"))) int rt_debug_unit(int device, 
         if (e == hipSuccess) e = hipMemcpy(d_in, in, bi, hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemset(d_out, 0, bo);
         if (e == hipSuccess) {
-            (unit == 0 ? rtk::unit_launch_lin : unit == 1 ? rtk::unit_launch_trav : rtk::unit_launch_query)(family, n, d_in, d_out, 0);
+            rtk::unit_launch(unit, family, n, d_in, d_out, 0);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipDeviceSynchronize();

@@ -161,7 +161,7 @@ RT_HOST_DEVICE float cone_omc(float q) {
 }
 
 struct Cone {
-    Vec v;             // the direction, about unit length: the shadow ray is Ray::new(P, v)
+    Vec v;             // the direction, |v.v - 1| <= 2^-18 while dc2 >= 2^-130 (w takes on a subnormal dc2's lost bits): Ray::new(P, v)
     float omc;         // 1 - cos(theta_max)
     float dc2, dc;     // a.a and its root
     float ct, st;      // cosine and sine of the angle to the axis

@@ -11,3 +11,10 @@ BounceFn bounce_kernel(int engine, int scan_mode) {
     return nullptr;
 }
 }  // namespace rtk
+
+// the unit kernel of the light-sampling and scatter arithmetic as THIS unit compiles it (test library only;
+// tests/test_gpu_sampling_operands.py)
+#ifdef RT_DEBUG_HOOKS
+#define RT_UNIT_ID 5
+#include "rt_unit_sampling.hip.h"
+#endif

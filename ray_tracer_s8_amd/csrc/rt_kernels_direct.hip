@@ -19,3 +19,10 @@ DirectFn direct_kernel(int engine, int scan_mode, bool by_power, bool cone) {
     return by_power ? direct_kernel_of<PICK_POWER, SHAPE_AREA>(engine, scan_mode) : direct_kernel_of<PICK_UNIFORM, SHAPE_AREA>(engine, scan_mode);
 }
 }  // namespace rtk
+
+// the unit kernel of the light-sampling and scatter arithmetic as THIS unit compiles it (test library only;
+// tests/test_gpu_sampling_operands.py)
+#ifdef RT_DEBUG_HOOKS
+#define RT_UNIT_ID 3
+#include "rt_unit_sampling.hip.h"
+#endif

@@ -20,3 +20,10 @@ NeeFn nee_kernel(int engine, int scan_mode, bool by_power, bool cone) {
     return by_power ? nee_kernel_of<PICK_POWER, SHAPE_AREA>(engine, scan_mode) : nee_kernel_of<PICK_UNIFORM, SHAPE_AREA>(engine, scan_mode);
 }
 }  // namespace rtk
+
+// the unit kernel of the light-sampling and scatter arithmetic as THIS unit compiles it (test library only;
+// tests/test_gpu_sampling_operands.py)
+#ifdef RT_DEBUG_HOOKS
+#define RT_UNIT_ID 4
+#include "rt_unit_sampling.hip.h"
+#endif

@@ -5,7 +5,7 @@
 // the square root they choose (RT_IEEE_SQRT_PLAIN), so each unit that wants checking instantiates the kernel for itself:
 //     #define RT_UNIT_ID <n>      (0 lin, 1 trav, 2 query: rt_debug_unit's `unit` argument)
 //     #include "rt_unit.hip.h"
-// (rt_api.hip includes it without RT_UNIT_ID: the record sizes and the launchers' declarations only.)
+// (rt_api.hip includes it without RT_UNIT_ID: the record sizes and the launchers' declarations only, and the sibling header.)
 // Records are 32-bit words, plain loads and stores.  Words in / out per family (tests/_operand_cases.py holds the same table):
 //   0 SPHERE       in 12: o d cen r t_min t_max                 out 2: hit, t              exact_sphere(o, 2*d, cen, r*r, ...)
 //   1 SPHERE_NORM  in 12: the same                              out 5: hit, t, normalize(d)           the same after Ray::new
@@ -17,6 +17,7 @@
 //   7 RNG          in  2: st (low word, high word)              out 28: seed_state's 4 words (low, high each), 4 next_u32, 4 u01,
 //                                                                       4 uniform_m1_1 (drawn in that order), the final 4 words
 // t is stored as the function leaves it (zero-initialised before the call): it means something only where hit is set.
+// Families 8 .. 15 (units 3 .. 6), the light-sampling and scatter arithmetic, are rt_unit_sampling.hip.h's.
 #pragma once
 #include "rt_kernel.hip.h"
 
@@ -135,3 +136,22 @@ void unit_launch_query
 }
 #endif  // RT_UNIT_ID
 }  // namespace rtk
+
+// rt_api.hip (no RT_UNIT_ID) takes both unit headers through this one: the sibling's record sizes and launchers, and what
+// rt_debug_unit asks of the two together.
+#ifndef RT_UNIT_ID
+#include "rt_unit_sampling.hip.h"
+namespace rtk {
+// units 0 .. 2 carry families 0 .. 7, units 3 .. 6 the families unit_carries names
+inline bool unit_instantiated(int unit, int family) {
+    return (unit >= 0 && unit <= 2 && family >= 0 && family < UNIT_FAMILIES) ||
+           (family >= UNIT_SAMPLING_FIRST && family < UNIT_SAMPLING_END && unit_carries(unit, family));
+}
+inline int unit_record_in(int family) { return family < UNIT_FAMILIES ? unit_words_in(family) : sampling_words_in(family); }
+inline int unit_record_out(int family) { return family < UNIT_FAMILIES ? unit_words_out(family) : sampling_words_out(family); }
+inline void unit_launch(int unit, int family, unsigned long long n, const uint32_t* d_in, uint32_t* d_out, hipStream_t st) {
+    (unit == 0 ? unit_launch_lin : unit == 1 ? unit_launch_trav : unit == 2 ? unit_launch_query : unit == 3 ? unit_launch_direct :
+     unit == 4 ? unit_launch_nee : unit == 5 ? unit_launch_bounce : unit_launch_trace)(family, n, d_in, d_out, st);
+}
+}  // namespace rtk
+#endif

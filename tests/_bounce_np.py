@@ -36,6 +36,35 @@ def _try_normalize(a):
     return np.isfinite(rcp) & (rcp > 0), a * rcp[:, None]
 
 
+def unit_sphere_vec(x1, x2, sm):
+    """The UnitSphere vector of an accepted pair (S/main.rs:119), rows (n, 3): (x1 f, x2 f, 1 - 2 sm), f = 2 sqrt(1 - sm).  `step` does
+    not call it (its vector is oracle.draw's); tests/test_sampling_corpus.py holds it to oracle.draw."""
+    f = F32(2) * np.sqrt(F32(1) - sm)
+    return np.stack([x1 * f, x2 * f, F32(1) - F32(2) * sm], 1).astype(F32)
+
+
+def scatter_dir(us, nn, dd, rr):
+    """The direction of the scattered ray (S/main.rs:119-127) from the UnitSphere draws us, the normals nn, the incoming directions dd
+    (rows (n, 3)) and the roughnesses rr: (direction after Ray::new, try_normalize succeeded)."""
+    diffuse = us + nn
+    glossy = dd - (F32(2) * _dot(dd, nn))[:, None] * nn
+    scatter = diffuse + rr[:, None] * (glossy - diffuse)
+    ok, nd = _try_normalize(scatter)
+    nd = np.where(ok[:, None], nd, nn)
+    return _normalize(nd), ok                    # Ray::new
+
+
+def sky_colour(d):
+    """The sky a ray of direction d sees (S/main.rs:135-144), rows (n, 3): t = normalize_or_zero(d).y 0.5 + 1 and
+    (1 t + 0.3 (1 - t), the same, 1 t + 0.8 (1 - t)).  `step` does not call it (its sky is oracle.sky, the reference's own);
+    tests/test_sampling_corpus.py holds it to oracle.sky."""
+    ok, nd = _try_normalize(d)
+    t = np.where(ok, nd[:, 1], F32(0)) * F32(0.5) + F32(1)
+    omt = F32(1) - t
+    rg = F32(1) * t + F32(0.3) * omt
+    return np.stack([rg, rg, F32(1) * t + F32(0.8) * omt], 1).astype(F32)
+
+
 def directions(rays, as_given):
     """The direction each ray is traced with: bit for bit, or Ray::new's."""
     d = np.stack([rays["dx"], rays["dy"], rays["dz"]], 1).astype(F32)
@@ -93,12 +122,7 @@ def step(oracle, sph, tri, rays, states, backend, wi=None, as_given=False, activ
             out_states[act[j]] = st
         nn, dd, rr = nrm[js], d[js], rough[js]
         with np.errstate(all="ignore"):
-            diffuse = us + nn
-            glossy = dd - (F32(2) * _dot(dd, nn))[:, None] * nn
-            scatter = diffuse + rr[:, None] * (glossy - diffuse)
-            ok, nd = _try_normalize(scatter)
-            nd = np.where(ok[:, None], nd, nn)
-            d2 = _normalize(nd)                  # Ray::new
+            d2, _ = scatter_dir(us, nn, dd, rr)
         w = out_rays[act[js]]
         w["ox"], w["oy"], w["oz"] = P[js].T
         w["dx"], w["dy"], w["dz"] = d2.T

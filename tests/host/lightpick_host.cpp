@@ -73,6 +73,22 @@ __attribute__((visibility("default"))) uint32_t lightpick_counts(uint32_t M, con
     return bad;
 }
 
+// Record i, 20 words (the PICK_POWER records of csrc/rt_unit_sampling.hip.h): [0] u, [1] M (1 .. 16), [2] total, [3] M_big
+// (1 .. 2^23), [4..19] the running sums c.  Out, 2 words: pick_light_power(u, M, c, total) and pick_light(u, M_big); an M or M_big
+// outside its range writes 0, 0.
+__attribute__((visibility("default"))) void lightpick_pick_records(uint32_t n, const uint32_t* in, uint32_t* out) {
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t* r = in + (size_t)i * 20;
+        const uint32_t M = r[1], M_big = r[3];
+        out[2 * i] = out[2 * i + 1] = 0;
+        if (M < 1u || M > 16u || M_big < 1u || M_big > rtdl::MAX_LIGHTS) continue;
+        float c[16];
+        std::memcpy(c, r + 4, sizeof c);
+        out[2 * i] = rtdl::pick_light_power(f_of(r[0]), M, c, f_of(r[2]));
+        out[2 * i + 1] = rtdl::pick_light(f_of(r[0]), M_big);
+    }
+}
+
 // Record i, 6 words: [0] kind (0 sphere, 1 triangle), [1] cs, [2] cl, [3] size, [4] ip, [5] d2.  Out, 2 words: W of
 // sphere_weight_ip / triangle_weight_ip, and W' of rtnee::view_weight_ip for the view (cs, cl, d2).
 __attribute__((visibility("default"))) void lightpick_weights(uint32_t n, const uint32_t* in, uint32_t* out) {
