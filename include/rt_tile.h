@@ -58,7 +58,9 @@ extern "C" {
                                   (4, additions only: light selection by power RT_FLAG_LIGHTS_BY_POWER for rt_scene_direct* and
                                      rt_scene_trace_nee*, rt_scene_light_table)
                                   (4, additions only: cone sampling of sphere lights RT_LIGHTS_AREA / RT_LIGHTS_CONE with
-                                     rt_scene_set_light_sampling / rt_scene_light_sampling) */
+                                     rt_scene_set_light_sampling / rt_scene_light_sampling)
+                                  (4, additions only: light samples at glossy hits RT_GLOSSY_BOUNCE / RT_GLOSSY_MIS with
+                                     rt_scene_set_glossy_sampling / rt_scene_glossy_sampling) */
 
 /* ---- status codes --------------------------------------------------------------- */
 typedef enum rt_status {
@@ -668,8 +670,57 @@ RT_API int rt_scene_light_sampling(rt_scene* scene, uint32_t* out_sampling);
  *     rt_scene_bounce and rt_scene_direct under RT_LIGHTS_CONE.  out_segments and the written-back states equal RT_LIGHTS_AREA's: the
  *     path never depends on the light sample; out_shadow and the colours differ.  A scene with no sphere emitter gives RT_LIGHTS_AREA's
  *     bytes.  The rim limit of rt_scene_direct's cone sample applies.
- *   - Limits: a hit with roughness > 0 takes no light sample (it falls back to the bounce, which is unbiased).
- * No per-scene scratch on the device: launches on different streams may overlap.  (DESIGN.md 4.18, 4.19, 4.20.) */
+ *   - Light samples at glossy hits: whether a hit of roughness rho > 0 takes a light sample is a property of the SCENE:
+ *     rt_scene_set_glossy_sampling(scene, RT_GLOSSY_BOUNCE | RT_GLOSSY_MIS).  The default is RT_GLOSSY_BOUNCE, everything above, every
+ *     byte of every output.  The setting is read when a call is enqueued and only selects the kernel instance: work already enqueued
+ *     keeps the setting it was enqueued with; rt_scene_set_glossy_sampling must not race with other calls on the same scene.  Only
+ *     rt_scene_trace_nee* in mode RT_NEE_MIS reads it: RT_NEE_LIGHT_ONLY (so its fold identity stays), rt_scene_direct* (which has
+ *     neither the roughness nor the incoming direction) and every other call ignore it in every byte.  The light sample alone has
+ *     no finite variance at such a hit (below); under the balance heuristic its term is Le * W / (1 + W) <= Le.
+ *     ray_color scatters along pre = diffuse + rho * (glossy - diffuse) = c + r * us, us uniform on the unit sphere: the direction
+ *     from the origin to a uniform point of the sphere of radius r = 1 - rho about c = r * n + rho * g, g the mirrored direction.
+ *     With b = c.w and kappa = c.c - r*r the density of the unit direction w is p(w) = (b*b + D) / (2 pi r sqrt(D)), D = b*b - kappa,
+ *     for b > 0 and D > 0, else 0 (both intersections contribute, each t*t / |cos|; the origin lies outside the sphere, kappa > 0, at
+ *     every front-face hit with 0 < rho < 1).  cg = pi * p(w) stands where the Lambertian cs stands above.  Under RT_GLOSSY_MIS, in
+ *     mode RT_NEE_MIS, everything not listed here is as above:
+ *       Class of an RT_BOUNCE_SCATTERED hit with k != max_bounces and M > 0: d the segment's direction as the step used it,
+ *         g = d - (2 * (d.n)) * n the glossy_dir the step formed (the same bits), gn = n.g, gg = g.g.
+ *           rho == 0:                          the diffuse sample exactly as above (cs; the lobe formula is not used);
+ *           0 < rho && rho < 1 && gn >= 0:     LOBE-SAMPLED;
+ *           anything else (rho >= 1, rho < 0, a NaN, a back-face hit gn < 0, where the origin may lie inside the sphere): no light
+ *                                              sample and no draw, as above.
+ *       Lobe of a lobe-sampled hit: r = 1 - rho; c = r * n + rho * g per component (two products, one sum);
+ *         kappa = rho * (rho * gg + (r + r) * gn).
+ *       Lobe factor of a unit direction w: b = c.w; D = b * b - kappa; w is IN THE LOBE iff b > 0 && D > 0;
+ *         cg = (b * b + D) / ((r + r) * sqrt(D)).
+ *       Light sample at a lobe-sampled hit: the draws, the pick (uniform or by power), the point or the cone pair and the regime rule
+ *         of the scene's RT_LIGHTS_CONE are rt_scene_direct's, from the state as the step left it.  Every rejection above stays
+ *         (cs > 0, cl > 0, d2 finite and not 0; cs > 0 alone for a cone sample).  One is added: with wn the shadow ray's unit
+ *         direction (v normalised by division) and W the W of rt_scene_direct with cg(wn) in the place of cs —
+ *           area sphere: ((cg * cl) * ((4 * (r_l*r_l)) * ip)) / d2;  triangle: ((cg * cl) * (A * ip)) / (PI * d2);
+ *           cone: (cg * (omc + omc)) * ip;  ip = (float)M, or ip_k under RT_FLAG_LIGHTS_BY_POWER —
+ *         if wn is not in the lobe or !(W < inf), no ray is traced, nothing is added and out_shadow does not count it; the draws
+ *         have been taken.  Otherwise wl = 1.0f / (1.0f + W) and, when the shadow ray is RT_DIRECT_LIT, c = c + T * (D * wl) with
+ *         D = (albedo * emission) * W.
+ *       Lobe factor of the direction the scatter itself took, formed at the lobe-sampled hit from the UnitSphere vector us of its
+ *         scatter draw (the scattered point is X = c + r * us, and this is cg(X / |X|) without the cancellation of b * b - kappa on the
+ *         rim): m = r * (c.us + r); t = sqrt(kappa + (m + m)); cgb = ((kappa + m) * (kappa + m) + m * m) / (((r + r) * |m|) * t);
+ *         that direction is IN THE LOBE iff cgb > 0 (not for m == 0, a NaN, an overflowing scatter).
+ *       RT_BOUNCE_EMITTED after a lobe-sampled hit: the view above, by area or by cone under the same regime rule, with cgb of the
+ *         previous hit in the place of cs' in W'; the point is SAMPLABLE when it is samplable above (cs' = n.d > 0 and the rest)
+ *         and cgb > 0.  W' = inf gives wb = 1, the full term.  Not samplable: c = c + T * e.
+ *     Consequences: a lobe-sampled hit advances the RNG by the light sample's draws, so the segments, the written-back states and
+ *     the colours of a ray that meets such a hit differ from RT_GLOSSY_BOUNCE's; a ray that meets only hits of rho == 0 or
+ *     rho >= 1 (and a scene with M == 0) gives RT_GLOSSY_BOUNCE's bytes.  The estimator stays unbiased: wl and wb are the balance
+ *     heuristic's weights of p_scatter / p_light.
+ *   - Limits: under RT_GLOSSY_BOUNCE a hit with roughness > 0 takes no light sample (it falls back to the bounce, which is unbiased);
+ *     under RT_GLOSSY_MIS that holds for rho >= 1 and for back-face hits.  p(w) has a 1 / sqrt(D) singularity on the rim of the lobe,
+ *     so the light sample alone (Le * W) has a logarithmically divergent variance there: the setting exists for RT_NEE_MIS only.
+ *     Rim: D = b * b - kappa of an f32 direction cancels on the rim, where up to 2^-9 of the scatter's own directions would read
+ *     D <= 0; that is why the bounce's factor is formed from its draw, cgb above, which leaves fewer than 2^-14 of them outside
+ *     the lobe (tests/test_lobe_density.py measures both).  A bounce direction outside the lobe has its emitter
+ *     added in full, and a light sample whose direction rounds to D <= 0 is dropped.
+ * No per-scene scratch on the device: launches on different streams may overlap.  (DESIGN.md 4.18, 4.19, 4.20, 4.21.) */
 typedef struct rt_nee_request {
     uint32_t spp;               /* samples per ray, 1 .. RT_MAX_SPP                                        */
     uint32_t max_bounces;       /* 0 .. RT_MAX_BOUNCES; at most max_bounces + 1 path segments, as rt_scene_trace */
@@ -688,6 +739,12 @@ RT_API int rt_scene_trace_nee(rt_scene* scene, const rt_nee_request* req, const 
  * stream); counters and event times accumulate in the scene until rt_scene_collect(). */
 RT_API int rt_scene_trace_nee_device(rt_scene* scene, const rt_nee_request* req, const void* d_rays, uint32_t n, void* d_rng_state,
                                      void* d_out_rgb, void* d_out_segments, void* d_out_shadow, void* hip_stream);
+/* Whether rt_scene_trace_nee* in mode RT_NEE_MIS takes a light sample at hits of roughness 0 < rho < 1 ("light samples at glossy hits"
+ * above): not (the default: such a hit falls back to the bounce), or weighted by the density of the reference's scatter lobe.
+ * sampling > 1 or a NULL scene: RT_ERR_BAD_ARG.  Host only: no GPU work, no synchronisation. */
+enum { RT_GLOSSY_BOUNCE = 0u, RT_GLOSSY_MIS = 1u };
+RT_API int rt_scene_set_glossy_sampling(rt_scene* scene, uint32_t sampling);
+RT_API int rt_scene_glossy_sampling(rt_scene* scene, uint32_t* out_sampling);
 
 /* ---- feature buffers (AOVs) of a strip: what the camera rays of the beauty image first hit ---- */
 /* Per-pixel feature buffers for a denoiser, edge-aware filters, picking and compositing, ALIGNED with the beauty image: they

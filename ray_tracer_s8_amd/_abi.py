@@ -43,6 +43,8 @@ RT_FLAG_FRAME_STATIC = 16384        # frame-level: strip k -> devices[k % n] ins
 RT_FLAG_LIGHTS_BY_POWER = 32768     # rt_scene_direct* / rt_scene_trace_nee*: the emitter is picked by power (mixture with uniform)
 RT_LIGHTS_AREA = 0                  # rt_scene_set_light_sampling: a sphere light is sampled over its whole area (the default) ...
 RT_LIGHTS_CONE = 1                  # ... or over the cone it subtends from the hit point
+RT_GLOSSY_BOUNCE = 0                # rt_scene_set_glossy_sampling: RT_NEE_MIS takes no light sample at a hit of roughness > 0 (the default) ...
+RT_GLOSSY_MIS = 1                   # ... or one weighted by the density of the reference's scatter lobe, at 0 < roughness < 1
 RT_MAX_BOUNCES = 62
 RT_MAX_SPP = 4096                 # samples per pixel limit (rt_tile.h)
 
@@ -372,6 +374,10 @@ def _bind(path: Path) -> C.CDLL:
     lib.rt_scene_set_light_sampling.restype = C.c_int
     lib.rt_scene_light_sampling.argtypes = [vp, C.POINTER(C.c_uint32)]
     lib.rt_scene_light_sampling.restype = C.c_int
+    lib.rt_scene_set_glossy_sampling.argtypes = [vp, C.c_uint32]
+    lib.rt_scene_set_glossy_sampling.restype = C.c_int
+    lib.rt_scene_glossy_sampling.argtypes = [vp, C.POINTER(C.c_uint32)]
+    lib.rt_scene_glossy_sampling.restype = C.c_int
     lib.rt_scene_direct.argtypes = [vp, C.POINTER(DirectRequest), C.POINTER(Hit), C.c_uint32, C.POINTER(C.c_uint64),
                                     C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Direct), C.POINTER(TileStats)]
     lib.rt_scene_direct.restype = C.c_int

@@ -193,6 +193,8 @@ struct rt_scene {
     bool has_pose = false;          //   false: the reference camera
     uint32_t light_sampling = RT_LIGHTS_AREA;   // how a sphere light is sampled (rt_scene_set_light_sampling); read when a direct-lighting
                                                 //   or NEE call is enqueued, where it picks the kernel instance
+    uint32_t glossy_sampling = RT_GLOSSY_BOUNCE;   // whether RT_NEE_MIS takes light samples at glossy hits (rt_scene_set_glossy_sampling);
+                                                   //   read when an NEE call is enqueued, where it picks the kernel instance
     float4* d_geom = nullptr;
     float4* d_geom_pk = nullptr;
     float4* d_geom_px = nullptr;   // expanded-form broad phase records
@@ -593,6 +595,8 @@ void light_refs(const rt_scene* sc, P& p) {
 static bool lights_by_power(uint32_t flags) { return (flags & RT_FLAG_LIGHTS_BY_POWER) != 0; }
 // ... and so does the scene's light sampling (rt_scene_set_light_sampling)
 static bool lights_cone(const rt_scene* sc) { return sc->light_sampling == RT_LIGHTS_CONE; }
+// ... and its glossy sampling (rt_scene_set_glossy_sampling), which only RT_NEE_MIS reads
+static bool glossy_mis(const rt_scene* sc, const rt_nee_request* rq) { return sc->glossy_sampling == RT_GLOSSY_MIS && rq->mode == RT_NEE_MIS; }
 
 // Enqueue one launch of persistent waves over `items` in workgroups of `block` on `stream` (caller holds sc->mu, device current),
 // the block `p` complete.  The launches of the caller-ray calls, the feature buffers and the camera rays all end here.  what: the
@@ -1442,6 +1446,22 @@ static int rt_scene_light_sampling_impl(rt_scene* sc, uint32_t* out_sampling) {
     return RT_OK;
 }
 
+// Whether RT_NEE_MIS takes light samples at glossy hits, for the calls enqueued from now on.
+static int rt_scene_set_glossy_sampling_impl(rt_scene* sc, uint32_t sampling) {
+    if (!sc) return fail(RT_ERR_BAD_ARG, "scene is NULL");
+    if (sampling > RT_GLOSSY_MIS) return fail(RT_ERR_BAD_ARG, "sampling is neither RT_GLOSSY_BOUNCE nor RT_GLOSSY_MIS");
+    std::lock_guard<std::mutex> lk(sc->mu);
+    sc->glossy_sampling = sampling;
+    return RT_OK;
+}
+
+static int rt_scene_glossy_sampling_impl(rt_scene* sc, uint32_t* out_sampling) {
+    if (!sc || !out_sampling) return fail(RT_ERR_BAD_ARG, "scene or out_sampling is NULL");
+    std::lock_guard<std::mutex> lk(sc->mu);
+    *out_sampling = sc->glossy_sampling;
+    return RT_OK;
+}
+
 static int rt_scene_direct_device_impl(rt_scene* sc, const rt_direct_request* rq, const void* d_hits, uint32_t n, void* d_state,
                                        const void* d_active, const void* d_n_active, void* d_out, void* hip_stream) {
     int rc = check_direct(sc, rq, d_hits, n, d_state, d_active, d_n_active, d_out);
@@ -1505,10 +1525,10 @@ static int launch_nee(rt_scene* sc, const rt_nee_request* rq, const void* d_rays
     p.mis = rq->mode == RT_NEE_MIS ? 1u : 0u;
     material_refs(sc, p);
     light_refs(sc, p);
-    return launch_rays(sc, qp, rtplan::QUERY_BLOCK, rtk::nee_kernel(qp.engine, qp.scan_mode, lights_by_power(rq->flags), lights_cone(sc)), "next-event-estimation", p, n,
+    return launch_rays(sc, qp, rtplan::QUERY_BLOCK, rtk::nee_kernel(qp.engine, qp.scan_mode, lights_by_power(rq->flags), lights_cone(sc), glossy_mis(sc, rq)), "next-event-estimation", p, n,
                        vtext("nee: engine %d  scan mode %d  lds %zu B  ", qp.engine, qp.scan_mode, qp.lds),
-                       vtext("rays %u  spp %u  bounces %u  mode %u  lights %u%s%s", n, rq->spp, rq->max_bounces, rq->mode, sc->n_lights,
-                             lights_by_power(rq->flags) ? " by power" : "", lights_cone(sc) ? " cone" : ""),
+                       vtext("rays %u  spp %u  bounces %u  mode %u  lights %u%s%s%s", n, rq->spp, rq->max_bounces, rq->mode, sc->n_lights,
+                             lights_by_power(rq->flags) ? " by power" : "", lights_cone(sc) ? " cone" : "", glossy_mis(sc, rq) ? " glossy" : ""),
                        (uint64_t)n * rq->spp, stream);
 }
 
@@ -2541,6 +2561,12 @@ RT_API int rt_scene_set_light_sampling(rt_scene* sc, uint32_t sampling) {
 }
 RT_API int rt_scene_light_sampling(rt_scene* sc, uint32_t* out_sampling) {
     return guarded([&] { return rt_scene_light_sampling_impl(sc, out_sampling); });
+}
+RT_API int rt_scene_set_glossy_sampling(rt_scene* sc, uint32_t sampling) {
+    return guarded([&] { return rt_scene_set_glossy_sampling_impl(sc, sampling); });
+}
+RT_API int rt_scene_glossy_sampling(rt_scene* sc, uint32_t* out_sampling) {
+    return guarded([&] { return rt_scene_glossy_sampling_impl(sc, out_sampling); });
 }
 RT_API int rt_scene_direct(rt_scene* sc, const rt_direct_request* rq, const rt_hit* hits, uint32_t n, uint64_t* rng_state, const uint32_t* active,
                            uint32_t n_active, rt_direct* out, rt_tile_stats* stats) {

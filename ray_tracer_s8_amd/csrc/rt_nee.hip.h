@@ -12,16 +12,20 @@
 // point) and the sample's contribution, already weighted, waits in `add`.  Every trip of the loop walks the lane's ray through the
 // one site, whichever kind it is, and then resolves it.  A wave therefore never runs a walk for its path segments with the lanes
 // that have a shadow ray idle, and then another for the shadow rays with the rest idle: lanes in different phases share the walk.
-// A lane whose sample faces away, or whose hit is rough, goes straight on to its next segment.
+// A lane whose sample faces away, or whose hit is rough, goes straight on to its next segment.  In the LOBE instances (the scene's
+// RT_GLOSSY_MIS, mode RT_NEE_MIS only) a hit of roughness 0 < rho < 1 seen from its front takes the light sample too, weighted by the
+// density of the reference's scatter lobe (rt_lobe_math.h), and the lane keeps the lobe factor of the direction the
+// scatter took for the emitter the bounce may reach next.
 //
 // Every step is a shared one, so the bits are those of the composed entry points: closest_hit, hit_normal, sky_colour,
 // unit_sphere_pair, scattered_dir, u01 and the RNG load / store / seed of rt_path_steps.hip.h; the light
 // sample is light_sample, rtdl::light_geometry and sample_weight, the steps rt_direct_kernel calls; the two MIS weights and the
-// samplable test of rt_nee_math.h.
+// samplable test of rt_nee_math.h; the lobe, its factor and the sampled-class rule of rt_lobe_math.h.
 //
 // LDS per lane (rtplan::plan_nee): the walk's stack, (bvh depth + 1) u32 entries (engine 2); entry e of lane tid at [e * 256 + tid].
 // No per-scene scratch: launches on different streams may overlap.
 #pragma once
+#include "rt_lobe_math.h"
 #include "rt_nee_math.h"
 #include "rt_path_steps.hip.h"
 
@@ -57,7 +61,9 @@ __device__ __forceinline__ float light_size(const P& p, uint32_t prim) {
 // also decides what stands for (float)M in W and in W' (the inverse probability of the emitter sampled, and of the emitter hit).
 // SHAPE: how a sphere light is sampled (the scene's rt_scene_set_light_sampling); SHAPE_CONE also views an emissive sphere the bounce
 // reached from the segment's origin o — exactly the previous hit point — so that W' speaks of the p_light the sample there had.
-template <int ENGINE, int MODE, int PICK, int SHAPE>
+// LOBE: 1 under the scene's RT_GLOSSY_MIS in mode RT_NEE_MIS (rt_scene_set_glossy_sampling); the LOBE = 0 instances are the code they
+// were before the setting existed.
+template <int ENGINE, int MODE, int PICK, int SHAPE, int LOBE>
 __global__ __launch_bounds__(256) void rt_nee_kernel(const NParams p) {
     extern __shared__ uint32_t nstack[];                 // [depth + 1][256] (engine 2)
     const uint32_t tid = threadIdx.x, bs = blockDim.x;
@@ -76,6 +82,8 @@ __global__ __launch_bounds__(256) void rt_nee_kernel(const NParams p) {
             V3 nd = mk(0.f, 0.f, 0.f), add = mk(0.f, 0.f, 0.f);   // shadow phase: the path's next direction; the sample's T * D (* wl)
             uint32_t k = 0, lprim = 0;
             bool sampled = false, shadow = false;
+            bool lobed = false;                          // LOBE: the last hit that scattered was lobe-sampled, and this is the lobe factor
+            float cg_prev = 0.f;                         //   of the direction its scatter took (0 or NaN: not in the lobe)
             for (;;) {
                 const RayAux aux = ray_aux(d, p.full_chain != 0);
                 const Hit h = closest_hit<ENGINE, MODE, false>(p, o, d, r.t_min, r.t_max, aux, nstack, tid, bs, n_tests);
@@ -112,10 +120,17 @@ __global__ __launch_bounds__(256) void rt_nee_kernel(const NParams p) {
                         // the light strategy's view of this point: could the sample of the step before have drawn it?
                         const bool sphere = prim < p.n_sph;
                         bool cone_view = false;
+                        const bool in_lobe = cg_prev > 0.0f;                            // LOBE: cg(d) takes the place of cs', and d must be in the lobe
                         if (SHAPE == SHAPE_CONE && sphere) {
                             const float4 g = at32(p.geom_r, prim);
-                            const rtnee::ConeView cv = rtnee::emitter_view_cone(dvec(o), dvec(n_prev), dvec(d), rtdl::Vec{g.x, g.y, g.z}, g.w);
+                            rtnee::ConeView cv = rtnee::emitter_view_cone(dvec(o), dvec(n_prev), dvec(d), rtdl::Vec{g.x, g.y, g.z}, g.w);
                             cone_view = cv.in_regime;
+                            if constexpr (LOBE != 0) {
+                                if (lobed) {
+                                    cv.samplable = cv.samplable && in_lobe;
+                                    cv.cs = cg_prev;
+                                }
+                            }
                             if (cv.samplable) {
                                 add_it = p.mis != 0;                                   // LIGHT_ONLY: that sample stood for it
                                 if (add_it) {
@@ -127,7 +142,13 @@ __global__ __launch_bounds__(256) void rt_nee_kernel(const NParams p) {
                                 }
                             }
                         }
-                        const rtnee::View v = rtnee::emitter_view(dvec(n_prev), dvec(d), dvec(nh), h.dist, sphere);
+                        rtnee::View v = rtnee::emitter_view(dvec(n_prev), dvec(d), dvec(nh), h.dist, sphere);
+                        if constexpr (LOBE != 0) {
+                            if (lobed) {
+                                v.samplable = v.samplable && in_lobe;
+                                v.cs = cg_prev;
+                            }
+                        }
                         if (!cone_view && v.samplable) {
                             add_it = p.mis != 0;                                       // LIGHT_ONLY: that sample stood for it
                             if (add_it) {
@@ -156,17 +177,42 @@ __global__ __launch_bounds__(256) void rt_nee_kernel(const NParams p) {
                 if (k == p.max_bounces) break;
                 k++;
                 const V3 dn = scattered_dir(d, nh, ma.w, x1, x2, sm);
+                rtlobe::Lobe lobe{rtdl::Vec{0.f, 0.f, 0.f}, 0.f, 0.f};
+                if constexpr (LOBE != 0) {
+                    const rtdl::Vec gd = rtlobe::glossy_dir(dvec(d), dvec(nh));        // the glossy_dir scattered_dir formed, the same bits
+                    const uint32_t cls = p.n_lights > 0 ? rtlobe::sampled_class(ma.w, rtdl::dot3(dvec(nh), gd)) : (uint32_t)rtlobe::CLASS_NONE;
+                    sampled = cls != rtlobe::CLASS_NONE;
+                    lobed = cls == rtlobe::CLASS_LOBE;
+                    if (lobed) {
+                        lobe = rtlobe::lobe_of(dvec(nh), gd, ma.w);
+                        cg_prev = rtlobe::lobe_factor_scatter(lobe, dvec(unit_sphere_vec(x1, x2, sm))).cg;   // the us scattered_dir used
+                    }
+                } else {
+                    sampled = ma.w == 0.0f && p.n_lights > 0;
+                }
                 o = hp;                                                                // origin exactly P, of either ray
                 d = dn;
                 n_prev = nh;
-                sampled = ma.w == 0.0f && p.n_lights > 0;
                 if (!sampled) continue;
                 // ================= one light sample, as rt_scene_direct specifies it for the record (P, n, prim) =================
                 const typename SampleOf<SHAPE>::type ls = light_sample<PICK, SHAPE>(p, rng, hp, nh);
                 const rtdl::Geometry g = sample_geometry(ls, hp, nh);
                 if (!g.facing) continue;                                               // FACING_AWAY: no ray, straight on
                 const float4 la = at32(p.mat, ls.prim);
-                const float W = sample_weight<PICK, SHAPE>(ls, g, p.n_lights);
+                float W;
+                if constexpr (LOBE != 0) {
+                    if (lobed) {                                                       // cg(wn) in the place of cs; outside the lobe: no ray
+                        const rtlobe::LobeFactor lfs = rtlobe::lobe_factor(lobe, g.w);
+                        rtdl::Geometry gl = g;
+                        gl.cs = lfs.cg;
+                        W = sample_weight<PICK, SHAPE>(ls, gl, p.n_lights);
+                        if (!rtlobe::lobe_sample_taken(lfs, W)) continue;
+                    } else {
+                        W = sample_weight<PICK, SHAPE>(ls, g, p.n_lights);
+                    }
+                } else {
+                    W = sample_weight<PICK, SHAPE>(ls, g, p.n_lights);
+                }
                 rtdl::Vec D = rtdl::radiance(rtdl::Vec{la.x, la.y, la.z}, at32(p.emis, ls.prim), W);
                 if (p.mis) {
                     const float wl = rtnee::light_weight(W);
@@ -194,7 +240,8 @@ __global__ __launch_bounds__(256) void rt_nee_kernel(const NParams p) {
 }
 
 using NeeFn = void (*)(const NParams);
-// rt_kernels_nee.hip; cone: the scene's setting is RT_LIGHTS_CONE; nullptr for a combination that does not exist
-NeeFn nee_kernel(int engine, int scan_mode, bool by_power, bool cone);
+// rt_kernels_nee.hip; cone: the scene's setting is RT_LIGHTS_CONE; lobe: it is RT_GLOSSY_MIS and the mode RT_NEE_MIS; nullptr for a
+// combination that does not exist
+NeeFn nee_kernel(int engine, int scan_mode, bool by_power, bool cone, bool lobe);
 
 }  // namespace rtk

@@ -17,7 +17,7 @@
 //   7 RNG          in  2: st (low word, high word)              out 28: seed_state's 4 words (low, high each), 4 next_u32, 4 u01,
 //                                                                       4 uniform_m1_1 (drawn in that order), the final 4 words
 // t is stored as the function leaves it (zero-initialised before the call): it means something only where hit is set.
-// Families 8 .. 15 (units 3 .. 6), the light-sampling and scatter arithmetic, are rt_unit_sampling.hip.h's.
+// Families 8 .. 16 (units 3 .. 6), the light-sampling and scatter arithmetic, are rt_unit_sampling.hip.h's.
 #pragma once
 #include "rt_kernel.hip.h"
 

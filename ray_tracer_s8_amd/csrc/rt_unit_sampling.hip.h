@@ -2,7 +2,8 @@
 // #ifdef RT_DEBUG_HOOKS).  The sibling of rt_unit.hip.h for everything that samples a light or scatters a ray: one lane per record
 // calls the functions of rt_direct_math.h, rt_nee_math.h and the device-only shade lines of rt_path_steps.hip.h on the record's
 // operands and stores what they return, so that tests/test_gpu_sampling_operands.py can hold them to the numpy restatements
-// (tests/_sampling_cases.py) operand by operand.  The translation units whose product kernels inline these lines instantiate the
+// (tests/_sampling_cases.py) operand by operand; family 16 calls rt_lobe_math.h for tests/test_gpu_lobe_operands.py
+// (tests/_lobe_cases.py).  The translation units whose product kernels inline these lines instantiate the
 // kernel for themselves, with the families their kernels use:
 //     #define RT_UNIT_ID <n>      (3 direct, 4 nee, 5 bounce, 6 trace: rt_debug_unit's `unit` argument)
 //     #include "rt_unit_sampling.hip.h"
@@ -26,24 +27,28 @@
 //   14 SCATTER     in 10: d, n, roughness, x1, x2, sm               out  7: unit_sphere_vec, scattered_dir, try_normalize fell  5 6
 //                                                                           back to n
 //   15 SKY         in  3: d                                         out  3: sky_colour                                        5 6
+//   16 LOBE        in 16: lobe_host.cpp lobe_records: n, d, rho,    out 20: sampled_class, g, gn, c, r, kappa, b, D, in the      4
+//                         w, W, us, unused                                  lobe, cg, lobe_sample_taken(W); lobe_factor_scatter(us):
+//                                                                           m, t, cg, in the lobe; 0
 #pragma once
+#include "rt_lobe_math.h"
 #include "rt_nee_math.h"
 #include "rt_path_steps.hip.h"
 
 namespace rtk {
-constexpr int UNIT_SAMPLING_FIRST = 8, UNIT_SAMPLING_END = 16;     // families [FIRST, END)
+constexpr int UNIT_SAMPLING_FIRST = 8, UNIT_SAMPLING_END = 17;     // families [FIRST, END)
 constexpr int UNIT_PICK_TABLE = 16;                                // running sums a PICK_POWER record holds
 __host__ __device__ constexpr int sampling_words_in(int family) {
     return family == 8 ? 28 : family == 9 ? 6 : family == 10 ? 4 + UNIT_PICK_TABLE : family == 11 ? 16 : family == 12 ? 14 :
-           family == 13 ? 14 : family == 14 ? 10 : 3;
+           family == 13 ? 14 : family == 14 ? 10 : family == 16 ? 16 : 3;
 }
 __host__ __device__ constexpr int sampling_words_out(int family) {
     return family == 8 ? 16 : family == 9 ? 2 : family == 10 ? 2 : family == 11 ? 20 : family == 12 ? 5 : family == 13 ? 8 :
-           family == 14 ? 7 : 3;
+           family == 14 ? 7 : family == 16 ? 20 : 3;
 }
 // the (unit, family) pairs that are instantiated: rt_debug_unit refuses every other pair before any device work
 __host__ __device__ constexpr bool unit_carries(int unit, int family) {
-    return unit == 3 ? family >= 8 && family <= 11 : unit == 4 ? family >= 8 && family <= 13 :
+    return unit == 3 ? family >= 8 && family <= 11 : unit == 4 ? (family >= 8 && family <= 13) || family == 16 :
            unit == 5 || unit == 6 ? family == 14 || family == 15 : false;
 }
 
@@ -146,6 +151,25 @@ __global__ void __launch_bounds__(256) rt_unit_sampling_kernel(int family, unsig
             put(5, rtnee::bounce_weight(W));
             put(6, rtnee::light_weight(F(13)));
             put(7, rtnee::bounce_weight(F(13)));
+        }
+    }
+    if constexpr (unit_carries(UNIT, 16)) {
+        if (family == 16) {
+            const rtdl::Vec nrm = V(0), g = rtlobe::glossy_dir(V(3), nrm);
+            const float rho = F(6), gn = rtdl::dot3(nrm, g);
+            const rtlobe::Lobe l = rtlobe::lobe_of(nrm, g, rho);
+            const rtlobe::LobeFactor f = rtlobe::lobe_factor(l, V(7));
+            w[0] = rtlobe::sampled_class(rho, gn);
+            put3(1, g);
+            put(4, gn);
+            put3(5, l.c);
+            put(8, l.r), put(9, l.kappa), put(10, f.b), put(11, f.D);
+            w[12] = f.in_lobe ? 1u : 0u;
+            put(13, f.cg);
+            w[14] = rtlobe::lobe_sample_taken(f, F(10)) ? 1u : 0u;
+            const rtlobe::ScatterFactor s = rtlobe::lobe_factor_scatter(l, V(11));
+            put(15, s.m), put(16, s.t), put(17, s.cg);
+            w[18] = s.in_lobe ? 1u : 0u;
         }
     }
     if constexpr (unit_carries(UNIT, 14)) {

@@ -401,6 +401,20 @@ class Scene:
         _abi.check(self._lib.rt_scene_light_sampling(self._h, C.byref(v)), "rt_scene_light_sampling")
         return int(v.value)
 
+    def set_glossy_sampling(self, sampling: int):
+        """Whether later trace_nee() calls in mode RT_NEE_MIS take a light sample at hits of roughness 0 < rho < 1
+        (rt_scene_set_glossy_sampling): _abi.RT_GLOSSY_BOUNCE, no (the default: such a hit falls back to the bounce), or
+        _abi.RT_GLOSSY_MIS, one weighted by the density of the reference's scatter lobe.  Work already enqueued keeps the setting it was
+        enqueued with; RT_NEE_LIGHT_ONLY, direct() and every other call ignore it."""
+        _abi.check(self._lib.rt_scene_set_glossy_sampling(self._h, sampling), "rt_scene_set_glossy_sampling")
+
+    @property
+    def glossy_sampling(self) -> int:
+        """The scene's glossy sampling (rt_scene_glossy_sampling): RT_GLOSSY_BOUNCE or RT_GLOSSY_MIS."""
+        v = C.c_uint32(0)
+        _abi.check(self._lib.rt_scene_glossy_sampling(self._h, C.byref(v)), "rt_scene_glossy_sampling")
+        return int(v.value)
+
     def direct(self, hits, rng_state, active=None, t_min: float = 0.001, t_max: float = 1000.0, flags: int = 0):
         """Direct lighting of caller rays (rt_scene_direct): one light sample for each active hit record — an emitter picked with one
         u01 of the ray's state, a point on it, the shadow ray within [t_min, t_max) and the Lambertian estimate without the surface

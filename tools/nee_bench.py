@@ -19,10 +19,16 @@ it buys, on the camera rays of a benchmark scene (default c2, cornell16).
             (with --power: both under RT_FLAG_LIGHTS_BY_POWER): HIP-event time of rt_scene_direct on the first step's hits and of
             rt_scene_trace_nee in both modes (best and median of --runs after --warmup), the mean and the variance of the samples'
             luminance, the variance ratio area / cone and, per setting, the ratio rt_scene_trace / mode.
+  glossy    (--glossy) light samples at glossy hits, RT_GLOSSY_MIS, beside RT_GLOSSY_BOUNCE in mode RT_NEE_MIS on the same rays and states
+            in the same run (with --power / --cone: under RT_FLAG_LIGHTS_BY_POWER / RT_LIGHTS_CONE), on the config's camera rays and on
+            the glossy room (a ground of roughness 0.5, spheres of roughness 0, 0.5 and 1, a sphere light and a triangle light, under
+            fixed pinhole rays): HIP-event time of rt_scene_trace_nee (best, median and the spread of --runs after --warmup), the mean
+            and the variance of the samples' luminance, the variance ratio bounce / MIS, the time ratio, and the figure of merit
+            (variance x time) bounce / MIS.
 
 --config lamps is the many-light scene scenes.lamp_room() (one lamp, 32 dim emitters) under its fixed pinhole rays.
 
-    python tools/nee_bench.py [--config c2 | lamps] [--width 480 --height 270 --spp 4] [--steps 4] [--power] [--cone]
+    python tools/nee_bench.py [--config c2 | lamps] [--width 480 --height 270 --spp 4] [--steps 4] [--power] [--cone] [--glossy]
 Prints one JSON line."""
 import argparse
 import json
@@ -148,6 +154,70 @@ def cone_block(sc, a, step, rays, o, dd, trace_var):
     return out
 
 
+def glossy_room():
+    """(spheres, triangles): a ground of roughness 0.5, spheres of roughness 0, 0.5 and 1, a sphere light and a triangle light."""
+    sph = np.zeros(5, _abi.SPHERE_DTYPE)
+    sph["cx"], sph["cy"], sph["cz"] = [0.0, -1.2, 0.0, 1.2, 0.2], [-100.5, 0.0, 0.0, 0.0, 2.3], [-3.0, -3.2, -3.0, -2.8, -3.0]
+    sph["radius"] = [100.0, 0.5, 0.5, 0.5, 0.5]
+    sph["albedo_r"], sph["albedo_g"], sph["albedo_b"] = [0.5, 0.8, 0.3, 0.7, 1.0], [0.6, 0.3, 0.7, 0.7, 0.9], [0.4, 0.3, 0.4, 0.2, 0.7]
+    sph["roughness"], sph["emission"] = [0.5, 0.0, 0.5, 1.0, 0.0], [0.0, 0.0, 0.0, 0.0, 6.0]
+    tri = np.zeros(1, _abi.TRIANGLE_DTYPE)
+    tri["a"][0], tri["b"][0], tri["c"][0] = (-2.5, 0.2, -4.5), (-1.5, 1.8, -4.8), (-2.8, 1.5, -3.6)
+    tri["albedo_r"], tri["albedo_g"], tri["albedo_b"], tri["emission"] = 0.6, 0.8, 1.0, 3.0
+    return sph, tri
+
+
+def room_rays(width, height, spp):
+    """Fixed pinhole rays from the origin down -z, pitched down onto the room's spheres, spp records per pixel, unit directions."""
+    ys, xs = np.mgrid[0:height, 0:width]
+    u = ((xs + 0.5) / width * 2 - 1) * 0.3 * width / height
+    v = (1 - (ys + 0.5) / height * 2) * 0.3 - 0.1
+    d = np.stack([u, v, -np.ones_like(u)], -1).reshape(-1, 3)
+    d = np.repeat((d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32), spp, 0)
+    r = np.zeros(len(d), _abi.RAY_DTYPE)
+    r["dx"], r["dy"], r["dz"], r["t_min"], r["t_max"] = d[:, 0], d[:, 1], d[:, 2], 0.001, 1000.0
+    return r
+
+
+def glossy_block(sc, a, rays):
+    """RT_GLOSSY_BOUNCE and RT_GLOSSY_MIS side by side in mode RT_NEE_MIS on the same rays and states, next to rt_scene_trace.  The
+    scene is left at RT_GLOSSY_BOUNCE."""
+    n = len(rays)
+    o = np.stack([rays["ox"], rays["oy"], rays["oz"]], 1)
+    dd = np.stack([rays["dx"], rays["dy"], rays["dz"]], 1)
+    flags = _abi.RT_FLAG_LIGHTS_BY_POWER if a.power else 0
+    sc.set_light_sampling(_abi.RT_LIGHTS_CONE if a.cone else _abi.RT_LIGHTS_AREA)
+    spread = lambda t: {"best": min(t), "median": statistics.median(t), "worst": max(t), "runs": len(t)}
+    t_trace = []
+    for i in range(a.warmup + a.runs):
+        tr = sc.trace(o, dd, rays["t_min"], rays["t_max"], spp=1, max_bounces=a.steps - 1, rng_state=_states(n, 2), as_given=True)
+        if i >= a.warmup:
+            t_trace.append(tr[2].kernel_ms)
+    lt = tr[0].astype(np.float64).mean(1)
+    out = {"rays": n, "lights": sc.n_lights, "flags": "by_power" if a.power else "uniform", "light_sampling": "cone" if a.cone else "area",
+           "trace": {"kernel_ms": spread(t_trace), "mean": float(lt.mean()), "variance": float(lt.var(ddof=1))}}
+    for name, setting in (("bounce", _abi.RT_GLOSSY_BOUNCE), ("mis", _abi.RT_GLOSSY_MIS)):
+        sc.set_glossy_sampling(setting)
+        t = []
+        for i in range(a.warmup + a.runs):
+            got = sc.trace_nee(o, dd, rays["t_min"], rays["t_max"], spp=1, max_bounces=a.steps - 1, rng_state=_states(n, 4), as_given=True,
+                               mode=_abi.RT_NEE_MIS, flags=flags)
+            if i >= a.warmup:
+                t.append(got[3].kernel_ms)
+        lf = got[0].astype(np.float64).mean(1)
+        out[name] = {"kernel_ms": spread(t), "mean": float(lf.mean()), "variance": float(lf.var(ddof=1)),
+                     "standard_error": float(np.sqrt(lf.var(ddof=1) / n)), "largest": float(lf.max()), "segments": int(got[1].sum()),
+                     "shadow_rays": int(got[2].sum()), "variance_ratio_trace_over_this": float(lt.var(ddof=1) / lf.var(ddof=1))}
+    sc.set_glossy_sampling(_abi.RT_GLOSSY_BOUNCE)
+    sc.set_light_sampling(_abi.RT_LIGHTS_AREA)
+    vr = out["bounce"]["variance"] / out["mis"]["variance"]
+    tr_ = out["mis"]["kernel_ms"]["median"] / out["bounce"]["kernel_ms"]["median"]
+    out["variance_ratio_bounce_over_mis"] = vr
+    out["time_ratio_mis_over_bounce"] = tr_
+    out["variance_x_time_bounce_over_mis"] = vr / tr_
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", default="c2")
@@ -159,6 +229,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--power", action="store_true", help="also time and compare RT_FLAG_LIGHTS_BY_POWER against the uniform pick")
     ap.add_argument("--cone", action="store_true", help="also time and compare RT_LIGHTS_CONE against RT_LIGHTS_AREA (with --power: by power)")
+    ap.add_argument("--glossy", action="store_true",
+                    help="also time and compare RT_GLOSSY_MIS against RT_GLOSSY_BOUNCE in mode RT_NEE_MIS, on these rays and on the glossy room")
     a = ap.parse_args()
     rt.init()
     lamps = a.config == "lamps"
@@ -224,6 +296,11 @@ def main():
             out["power"] = power_block(sc, a, s, rays, o, dd)
         if a.cone:
             out["cone"] = cone_block(sc, a, s, rays, o, dd, float(la.var(ddof=1)))
+        if a.glossy:
+            out["glossy"] = {"config": glossy_block(sc, a, rays)}
+    if a.glossy:
+        with rt.Scene(0, rt.World(*glossy_room())) as room:
+            out["glossy"]["room"] = glossy_block(room, a, room_rays(a.width, a.height, a.spp))
     print(json.dumps(out))
 
 
