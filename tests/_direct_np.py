@@ -1,9 +1,8 @@
-"""The CPU reference for direct lighting (rt_scene_direct, rt_tile.h "direct lighting"), from the oracle's entry points and float32 numpy
-alone: oracle.draw gives the u01 and UnitSphere draws from the ray's state, oracle.intersect_batch the closest hit of the shadow ray
-Ray::new(P, L - P); the pick, the point on the light, the cosines and the weight are float32 numpy scalars, one IEEE operation per
-numpy operation in the order the header writes them (a dot product is (x x' + y y') + z z').  tests/test_direct_host.py pins the
-arithmetic against csrc/rt_direct_math.h under g++; tests/test_gpu_direct.py compares the GPU with `direct` bit for bit.  Also here:
-the emitter list, the K-step integrator's fold and the scenes the tests share."""
+"""The arithmetic of direct lighting (rt_scene_direct, rt_tile.h "direct lighting") in float32 numpy: the pick, the point on the light,
+the cosines, the weight and the radiance are float32 numpy scalars, one IEEE operation per numpy operation in the order the header
+writes them (a dot product is (x x' + y y') + z z').  tests/test_direct_host.py pins it against csrc/rt_direct_math.h under g++.  The
+kernel's restatement — the draws, the shadow ray, the record — is tests/_lights_np.py's `direct`.  Also here: the emitter list, the
+K-step integrator's fold and the scenes the tests share."""
 import numpy as np
 
 from ray_tracer_s8_amd import _abi
@@ -107,62 +106,6 @@ def light_fields(kind, rec):
     if kind == "sphere":
         return (v3(rec["cx"], rec["cy"], rec["cz"]), F32(rec["radius"])), alb, F32(rec["emission"])
     return (np.array(rec["a"], F32), np.array(rec["b"], F32), np.array(rec["c"], F32)), alb, F32(rec["emission"])
-
-
-def sample(oracle, state, kind, rec, P, n, M):
-    """One light sample on the emitter (kind, rec) for the hit (P, n), the draws taken from `state` (advanced in place).
-    Returns a dict: L, v, facing, rgb_if_lit."""
-    geo, alb, em = light_fields(kind, rec)
-    sphere = kind == "sphere"
-    if sphere:
-        us = oracle.draw(state, 3).astype(F32)
-        L, nl = sphere_point(geo[0], geo[1], us), us
-    else:
-        u1 = oracle.draw(state, 0)[0]
-        u2 = oracle.draw(state, 0)[0]
-        u1, u2 = fold_pair(u1, u2)
-        L, nl = triangle_point(geo[0], geo[1], geo[2], u1, u2), normalize_or_zero(cross(geo[0] - geo[1], geo[0] - geo[2]))
-    v, d2, w, cs, cl, facing = geometry(P, n, L, nl, sphere)
-    W = sphere_weight(cs, cl, geo[1], M, d2) if sphere else triangle_weight(cs, cl, triangle_area(*geo), M, d2)
-    return dict(L=L, v=v, facing=facing, rgb=radiance(alb, em, W))
-
-
-def direct(oracle, sph, tri, hits, states, backend, wi=None, active=None, t_min=0.001, t_max=1000.0):
-    """One light sample for the records `active` (None: all).  Returns a dict: direct (DIRECT_DTYPE; entries of records that are
-    not active are zero), states (a copy, advanced where a record drew), shadow (bool: a shadow ray was traced)."""
-    n = len(hits)
-    act = np.arange(n) if active is None else np.asarray(active, np.int64)
-    out, out_states = np.zeros(n, _abi.DIRECT_DTYPE), np.array(states, np.uint64)
-    shadow = np.zeros(n, bool)
-    lights = emitters(sph, tri, wi)
-    M = len(lights)
-    pending, rays = [], []
-    for i in act:
-        h = hits[i]
-        if h["index"] == NONE or M == 0:
-            out[i] = (0, 0, 0, NONE, 0, 0, 0, SKIPPED if h["index"] == NONE else NO_LIGHTS)
-            continue
-        st = out_states[i].copy()
-        k = pick(oracle.draw(st, 0)[0], M)
-        pos, kind, rec = lights[k]
-        P, nrm = v3(h["px"], h["py"], h["pz"]), v3(h["nx"], h["ny"], h["nz"])
-        s = sample(oracle, st, kind, rec, P, nrm, M)
-        out_states[i] = st
-        out[i] = (0, 0, 0, pos, s["L"][0], s["L"][1], s["L"][2], FACING_AWAY)
-        if s["facing"]:
-            shadow[i] = True
-            pending.append((i, pos, s["rgb"]))
-            rays.append((P[0], P[1], P[2], t_min, s["v"][0], s["v"][1], s["v"][2], t_max))
-    if pending:
-        r = np.array(rays, _abi.RAY_DTYPE)
-        e = oracle.intersect_batch(sph, tri, r, backend=backend, world_index=wi)
-        for j, (i, pos, rgb) in enumerate(pending):
-            if e["hit"][j] and int(e["index"][j]) == pos:
-                out["r"][i], out["g"][i], out["b"][i] = rgb
-                out["status"][i] = LIT
-            else:
-                out["status"][i] = OCCLUDED
-    return dict(direct=out, states=out_states, shadow=shadow)
 
 
 def rgb_of(d):

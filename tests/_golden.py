@@ -1,4 +1,4 @@
-"""Loader for tests/golden/*.npz: rebuilds (request, scene) for each committed vector."""
+"""Loader for the render vectors among tests/golden/*.npz: rebuilds (request, scene) for each committed vector."""
 from pathlib import Path
 
 import numpy as np
@@ -26,6 +26,8 @@ def load_all():
     out = []
     for f in sorted(GOLDEN.glob("*.npz")):
         z = np.load(f, allow_pickle=False)
+        if "request" not in z.files:                     # a fixture of another kind (light_restatements.npz): not a render vector
+            continue
         rec = z["request"][0]
         rq = _abi.TileRequest()
         for k in rec.dtype.names:

@@ -1,25 +1,18 @@
-"""The CPU reference for light selection by power (RT_FLAG_LIGHTS_BY_POWER, rt_tile.h "light selection by power"), from the oracle's entry
-points and float32 numpy alone, one IEEE operation per numpy operation in the order the header writes them.  Points, geometry,
-radiance, the fold pair, the emitter list and the path step are those of tests/_direct_np.py, tests/_nee_np.py and tests/_bounce_np.py;
-what is restated here is the flag's own: the light table, the pick, the weights with ip in the place of (float)M, and the two driver
-loops (rt_scene_direct, rt_scene_trace_nee) with the pick rule as a parameter — by_power=False is the uniform pick of the two modules.
-tests/test_lightpick_host.py pins the table, the pick and the weights against csrc/rt_scene_host.h and csrc/rt_direct_math.h under g++;
-tests/test_gpu_lightpick.py compares the GPU with `direct` and `nee` bit for bit."""
+"""The arithmetic of light selection by power (RT_FLAG_LIGHTS_BY_POWER, rt_tile.h "light selection by power") in float32 numpy, one
+IEEE operation per numpy operation in the order the header writes them: an emitter's power, and the weights with ip in the place of
+(float)M.  The light table built from the powers and its pick are tests/_lights_np.py's `Table`; tests/test_lightpick_host.py pins
+all three against csrc/rt_scene_host.h and csrc/rt_direct_math.h under g++.  Also here: the scenes with many lights."""
 import numpy as np
 
 from ray_tracer_s8_amd import _abi, scenes
 
 import _bounce_np as B
 import _direct_np as D
-import _nee_np as N
 
 F32 = np.float32
-HALF, ONE = F32(0.5), F32(1)
-BY_POWER = _abi.RT_FLAG_LIGHTS_BY_POWER
-LIGHT_ONLY, MIS, MODES = N.LIGHT_ONLY, N.MIS, N.MODES
 
 
-# ---------------------------------------------------------------- the light table
+# ---------------------------------------------------------------- the power of an emitter, the weights with ip
 def power(kind, rec):
     """q = lum * area of one emitter record, 0 unless q > 0."""
     geo, alb, em = D.light_fields(kind, rec)
@@ -35,46 +28,6 @@ def power(kind, rec):
     return q if q > 0 else F32(0)
 
 
-class Table:
-    """The emitter list (D.emitters: ascending world position) with, per emitter, the running sum c, the probability p and its
-    inverse ip; by_power=False: the uniform table p = 1 / M, ip = (float)M, as is a degenerate one."""
-
-    def __init__(self, sph, tri, wi=None, by_power=True):
-        self.list = D.emitters(sph, tri, wi)
-        M = self.M = len(self.list)
-        self.world_index = np.array([e[0] for e in self.list], np.uint32)
-        self.q = np.array([power(kind, rec) for _, kind, rec in self.list], F32)
-        self.c = np.zeros(M, F32)
-        run = F32(0)
-        with np.errstate(all="ignore"):
-            for k in range(M):
-                run = F32(run + self.q[k])
-                self.c[k] = run
-        self.total = run
-        self.degenerate = not (run > 0 and run < np.inf)
-        self.by_power = by_power and not self.degenerate
-        self.p, self.ip = np.zeros(M, F32), np.zeros(M, F32)
-        for k in range(M):
-            if self.by_power:
-                w = self.c[k] - (self.c[k - 1] if k else F32(0))
-                self.p[k] = HALF * (ONE / F32(M)) + HALF * (w / self.total)
-                self.ip[k] = ONE / self.p[k]
-            else:
-                self.p[k] = ONE / F32(M)
-                self.ip[k] = F32(M)
-        self.ip_at = {int(pos): self.ip[k] for k, pos in enumerate(self.world_index)}      # by world position
-
-    def pick(self, u):
-        """The emitter one u01 picks."""
-        u, M = F32(u), self.M
-        if not self.by_power:
-            return D.pick(u, M)
-        if u < HALF:
-            return D.pick(u + u, M)
-        x = ((u - HALF) + (u - HALF)) * self.total
-        return min(int(np.searchsorted(self.c, x, side="right")), M - 1)   # the smallest k with x < c_k, or M - 1
-
-
 def sphere_weight(cs, cl, r, ip, d2):
     with np.errstate(all="ignore"):
         r = F32(r)
@@ -84,146 +37,6 @@ def sphere_weight(cs, cl, r, ip, d2):
 def triangle_weight(cs, cl, A, ip, d2):
     with np.errstate(all="ignore"):
         return ((cs * cl) * (A * F32(ip))) / (D.PI * d2)
-
-
-def light_sample(oracle, state, table, P, n):
-    """One light sample for the hit (P, n), the draws taken from `state` (advanced in place): the pick from the table, the point as
-    rt_scene_direct draws it, W with the emitter's ip.  Returns (world position, L, v = L - P, facing, D, W)."""
-    k = table.pick(oracle.draw(state, 0)[0])
-    pos, kind, rec = table.list[k]
-    geo, alb, em = D.light_fields(kind, rec)
-    sphere = kind == "sphere"
-    if sphere:
-        us = oracle.draw(state, 3).astype(F32)
-        L, nl = D.sphere_point(geo[0], geo[1], us), us
-    else:
-        u1 = oracle.draw(state, 0)[0]
-        u2 = oracle.draw(state, 0)[0]
-        u1, u2 = D.fold_pair(u1, u2)
-        L, nl = D.triangle_point(geo[0], geo[1], geo[2], u1, u2), D.normalize_or_zero(D.cross(geo[0] - geo[1], geo[0] - geo[2]))
-    v, d2, w, cs, cl, facing = D.geometry(P, n, L, nl, sphere)
-    ip = table.ip[k]
-    W = sphere_weight(cs, cl, geo[1], ip, d2) if sphere else triangle_weight(cs, cl, D.triangle_area(*geo), ip, d2)
-    return pos, L, v, facing, D.radiance(alb, em, W), W
-
-
-# ---------------------------------------------------------------- rt_scene_direct
-def direct(oracle, sph, tri, hits, states, backend, wi=None, active=None, t_min=0.001, t_max=1000.0, by_power=True):
-    """As D.direct, the emitter picked from the table."""
-    n = len(hits)
-    act = np.arange(n) if active is None else np.asarray(active, np.int64)
-    out, out_states = np.zeros(n, _abi.DIRECT_DTYPE), np.array(states, np.uint64)
-    shadow = np.zeros(n, bool)
-    table = Table(sph, tri, wi, by_power)
-    pending, rays = [], []
-    for i in act:
-        h = hits[i]
-        if h["index"] == D.NONE or table.M == 0:
-            out[i] = (0, 0, 0, D.NONE, 0, 0, 0, D.SKIPPED if h["index"] == D.NONE else D.NO_LIGHTS)
-            continue
-        st = out_states[i].copy()
-        P, nrm = D.v3(h["px"], h["py"], h["pz"]), D.v3(h["nx"], h["ny"], h["nz"])
-        pos, L, v, facing, rgb, _ = light_sample(oracle, st, table, P, nrm)
-        out_states[i] = st
-        out[i] = (0, 0, 0, pos, L[0], L[1], L[2], D.FACING_AWAY)
-        if facing:
-            shadow[i] = True
-            pending.append((i, pos, rgb))
-            rays.append((P[0], P[1], P[2], t_min, v[0], v[1], v[2], t_max))
-    if pending:
-        e = oracle.intersect_batch(sph, tri, np.array(rays, _abi.RAY_DTYPE), backend=backend, world_index=wi)
-        for j, (i, pos, rgb) in enumerate(pending):
-            if e["hit"][j] and int(e["index"][j]) == pos:
-                out["r"][i], out["g"][i], out["b"][i] = rgb
-                out["status"][i] = D.LIT
-            else:
-                out["status"][i] = D.OCCLUDED
-    return dict(direct=out, states=out_states, shadow=shadow)
-
-
-# ---------------------------------------------------------------- rt_scene_trace_nee
-def one_sample(oracle, sph, tri, lights, table, rays, states, max_bounces, backend, wi=None, as_given=False):
-    """As N.one_sample: one sample of every ray in both modes, the light sample from the table and W' with ip of the emitter hit."""
-    n = len(rays)
-    T = np.ones((n, 3), F32)
-    c = {m: np.zeros((n, 3), F32) for m in MODES}
-    segs, shadow = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
-    sampled = np.zeros(n, bool)
-    n_prev = np.zeros((n, 3), F32)
-    cur_rays, cur_states = rays, np.array(states, np.uint64)
-    act = np.arange(n)
-    for k in range(max_bounces + 1):
-        if not len(act):
-            break
-        given = as_given or k > 0
-        s = B.step(oracle, sph, tri, cur_rays, cur_states, backend, wi, as_given=given, active=act)
-        d_in = B.directions(np.ascontiguousarray(cur_rays[act]), given)
-        cur_rays, cur_states = s["rays"], s["states"]
-        segs[act] += 1
-        status, rgb, hits = s["bounce"]["status"], B.rgb_of(s["bounce"]), s["hits"]
-        pending, shadow_rays = [], []
-        for a, i in enumerate(act):
-            if status[i] == B.MISSED:
-                N._add(c, i, T[i], {m: rgb[i] for m in MODES})
-            elif status[i] == B.EMITTED:
-                e = rgb[i]
-                term = {m: e for m in MODES}
-                if k != 0 and sampled[i]:
-                    j = int(hits["index"][i])
-                    sphere = bool(lights.sphere[j])
-                    nh = D.v3(hits["nx"][i], hits["ny"][i], hits["nz"][i])
-                    cs, cl, d2, samplable = N.emitter_view(n_prev[i], d_in[a], nh, hits["distance"][i], sphere)
-                    if samplable:
-                        with np.errstate(all="ignore"):
-                            Wv = (sphere_weight if sphere else triangle_weight)(cs, cl, lights.size(j), table.ip_at[j], d2)
-                            term = {LIGHT_ONLY: None, MIS: (e * N.bounce_weight(Wv)).astype(F32)}
-                N._add(c, i, T[i], term)
-            else:
-                with np.errstate(all="ignore"):
-                    T[i] = T[i] * rgb[i]
-                if k == max_bounces:
-                    continue
-                j = int(hits["index"][i])
-                sampled[i] = bool(lights.rough[j] == 0 and table.M > 0)
-                P, nrm = D.v3(hits["px"][i], hits["py"][i], hits["pz"][i]), D.v3(hits["nx"][i], hits["ny"][i], hits["nz"][i])
-                n_prev[i] = nrm
-                if not sampled[i]:
-                    continue
-                st = cur_states[i].copy()
-                pos, _, v, facing, Dv, W = light_sample(oracle, st, table, P, nrm)
-                cur_states[i] = st
-                if facing:
-                    shadow[i] += 1
-                    with np.errstate(all="ignore"):
-                        pending.append((i, pos, {LIGHT_ONLY: Dv, MIS: (Dv * N.light_weight(W)).astype(F32)}))
-                    shadow_rays.append((P[0], P[1], P[2], cur_rays["t_min"][i], v[0], v[1], v[2], cur_rays["t_max"][i]))
-        if pending:
-            e = oracle.intersect_batch(sph, tri, np.array(shadow_rays, _abi.RAY_DTYPE), backend=backend, world_index=wi)
-            for q, (i, pos, term) in enumerate(pending):
-                if e["hit"][q] and int(e["index"][q]) == pos:
-                    N._add(c, i, T[i], term)
-        act = act[status[act] == B.SCATTERED] if k < max_bounces else act[:0]
-    return c, segs, shadow, cur_states
-
-
-def nee(oracle, sph, tri, rays, spp, max_bounces, backend, wi=None, as_given=False, states=None, seed=0, by_power=True):
-    """As N.nee: rt_scene_trace_nee in both modes.  Returns a dict: rgb ({mode: (n, 3) float32 sums}), segments, shadow, states."""
-    n = len(rays)
-    lights, table = N.Lights(sph, tri, wi), Table(sph, tri, wi, by_power)
-    total = {m: np.zeros((n, 3), F32) for m in MODES}
-    segs, shadow = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
-    cur = None if states is None else np.array(states, np.uint64)
-    for s in range(spp):
-        st = N.sample_states(seed, n, spp, s) if states is None else cur
-        c, sg, sh, out_states = one_sample(oracle, sph, tri, lights, table, rays, st, max_bounces, backend, wi, as_given)
-        if states is not None:
-            cur = out_states
-        with np.errstate(all="ignore"):
-            for m in MODES:
-                total[m] = total[m] + c[m]
-        segs += sg
-        shadow += sh
-    return dict(rgb=total, segments=segs, shadow=shadow, states=cur)
 
 
 # ---------------------------------------------------------------- scenes shared by the CPU and the GPU tests

@@ -9,8 +9,8 @@
     samples is within 5 sample standard errors of it, on three geometries;
 (e) the rim share: with the light alone in the scene, the share of cone samples whose shadow ray (oracle.intersect_batch) does not hit
     the emitter is at most 2^-14 at r/dc = 0.9, 0.3, 1/16 and 1/32, 2^19 samples each;
-(f) the restatement's drivers with cone=False are tests/_lightpick_np.py's `direct` and `nee` byte for byte, and with cone=True leave
-    the same states and segments;
+(f) the restatement's drivers (tests/_lights_np.py) with cone=False give the bytes recorded from the drivers of tests/_lightpick_np.py
+    that they replaced (tests/test_light_restatement.py), and with cone=True leave the same states and segments;
 (g) the harness as a stand-alone program under -fsanitize=address,undefined."""
 import ctypes as C
 import subprocess
@@ -23,7 +23,9 @@ import _bounce_np as B
 import _cone_np as CN
 import _direct_np as D
 import _lightpick_np as LP
+import _lights_np as LN
 from ray_tracer_s8_amd import _abi
+from test_light_restatement import recorded
 
 ROOT = Path(__file__).resolve().parents[1]
 CSRC = ROOT / "ray_tracer_s8_amd" / "csrc"
@@ -294,9 +296,9 @@ def test_drivers_without_the_setting_are_the_lightpick_restatement(oracle, name)
     st = R.states(n, 4100)
     step = B.step(oracle, sph, tri, rays, st, 1, wi)
     for by_power in (False, True):
-        a = LP.direct(oracle, sph, tri, step["hits"], step["states"], 1, wi, by_power=by_power)
-        b = CN.direct(oracle, sph, tri, step["hits"], step["states"], 1, wi, by_power=by_power, cone=False)
-        c = CN.direct(oracle, sph, tri, step["hits"], step["states"], 1, wi, by_power=by_power, cone=True)
+        a = recorded(f"direct/_lightpick_np/{name}/p{int(by_power)}c0g0")    # (LP.direct of these hits and states, by_power=by_power)
+        b = LN.direct(oracle, sph, tri, step["hits"], step["states"], 1, wi, by_power=by_power, cone=False)
+        c = LN.direct(oracle, sph, tri, step["hits"], step["states"], 1, wi, by_power=by_power, cone=True)
         assert a["direct"].tobytes() == b["direct"].tobytes() and np.array_equal(a["states"], b["states"])
         assert np.array_equal(a["shadow"], b["shadow"]) and not b["in_cone"].any()
         assert np.array_equal(c["states"], a["states"]) and c["in_cone"].sum() > 20
@@ -304,10 +306,10 @@ def test_drivers_without_the_setting_are_the_lightpick_restatement(oracle, name)
         assert c["direct"][tri_rec].tobytes() == a["direct"][tri_rec].tobytes()
         assert (c["direct"]["status"] == D.FACING_AWAY).sum() < (a["direct"]["status"] == D.FACING_AWAY).sum()
         m = 60
-        x = LP.nee(oracle, sph, tri, rays[:m], 2, 3, 1, wi, states=st[:m], by_power=by_power)
-        y = CN.nee(oracle, sph, tri, rays[:m], 2, 3, 1, wi, states=st[:m], by_power=by_power, cone=False)
-        z = CN.nee(oracle, sph, tri, rays[:m], 2, 3, 1, wi, states=st[:m], by_power=by_power, cone=True)
-        for mode in CN.MODES:
+        x = recorded(f"nee/_lightpick_np/{name}/p{int(by_power)}c0g0")       # (LP.nee of these rays and states, by_power=by_power)
+        y = LN.nee(oracle, sph, tri, rays[:m], 2, 3, 1, wi, states=st[:m], by_power=by_power, cone=False)
+        z = LN.nee(oracle, sph, tri, rays[:m], 2, 3, 1, wi, states=st[:m], by_power=by_power, cone=True)
+        for mode in LN.MODES:
             assert x["rgb"][mode].tobytes() == y["rgb"][mode].tobytes()
         assert np.array_equal(x["segments"], y["segments"]) and np.array_equal(x["shadow"], y["shadow"]) and np.array_equal(x["states"], y["states"])
         assert np.array_equal(z["segments"], x["segments"]) and np.array_equal(z["states"], x["states"])

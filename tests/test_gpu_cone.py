@@ -1,6 +1,6 @@
 """Cone sampling of sphere lights on the GPU (rt_scene_set_light_sampling(RT_LIGHTS_CONE) for rt_scene_direct*, rt_scene_trace_nee*):
-1. both kernels against the CPU restatement tests/_cone_np.py (pinned by tests/test_cone_host.py), bit for bit: every rt_direct field and
-   the states, the NEE colours of both modes, segment and shadow counts and states; on two_lights (M = 2, one sphere and one triangle
+1. both kernels against the CPU restatement tests/_lights_np.py with cone=True (its cone arithmetic pinned by tests/test_cone_host.py,
+   its bytes by tests/test_light_restatement.py), bit for bit: every rt_direct field and the states, the NEE colours of both modes, segment and shadow counts and states; on two_lights (M = 2, one sphere and one triangle
    light), many_lights (M = 33, the radius-0 emitter among them, a permuted world_index), the lamp room and the "regimes" scene (hit
    points inside an emissive sphere, on either side of q = 2^-10, under a light that nearly touches the surface); the four flag sets of
    tests/test_gpu_direct.py each with and without RT_FLAG_LIGHTS_BY_POWER; host and device forms; batches of 1, 63, 64, 65 and 2000;
@@ -29,9 +29,11 @@ import _bounce_np as B
 import _cone_np as CN
 import _direct_np as D
 import _lightpick_np as LP
+import _lights_np as LN
 import _nee_np as N
 from test_gpu_bounce import CONFIGS, FILL, Dev, dev  # noqa: F401  (dev: a fixture of this module too)
-from test_gpu_direct import _gap_and_bound, _room_rays
+from test_gpu_direct import _device_direct, _gap_and_bound, _room_rays
+from test_gpu_lightpick import _assert_direct, _assert_nee
 from test_gpu_nee import _device_nee, _nee, _one_window, _rooms, _same
 
 pytestmark = pytest.mark.gpu
@@ -41,7 +43,7 @@ R = B.R
 F32 = np.float32
 AREA, CONE = _abi.RT_LIGHTS_AREA, _abi.RT_LIGHTS_CONE
 POWER = _abi.RT_FLAG_LIGHTS_BY_POWER
-LIGHT_ONLY, MIS = N.LIGHT_ONLY, N.MIS
+LIGHT_ONLY, MIS = LN.LIGHT_ONLY, LN.MIS
 N_RAYS = 2000
 N_NEE = 300                                      # the rays of the NEE comparisons with the (per-ray Python) restatement
 SIZES = [1, 63, 64, 65, 2000]
@@ -95,7 +97,7 @@ def _ref_direct(oracle, name, cfg, by_power, cone=True):
     key = ("direct", name, cfg, by_power, cone)
     if key not in _REF:
         c, step = _case(oracle, name, flags)
-        _REF[key] = CN.direct(oracle, c["sph"], c["tri"], step["hits"], step["states"], backend, c["wi"], by_power=by_power, cone=cone)
+        _REF[key] = LN.direct(oracle, c["sph"], c["tri"], step["hits"], step["states"], backend, c["wi"], by_power=by_power, cone=cone)
     return _REF[key]
 
 
@@ -104,29 +106,9 @@ def _ref_nee(oracle, name, backend, by_power, cone=True):
     key = ("nee", name, backend, by_power, cone)
     if key not in _REF:
         c, _ = _case(oracle, name)
-        _REF[key] = CN.nee(oracle, c["sph"], c["tri"], c["rays"][:N_NEE], 2, 3, backend, c["wi"], states=c["st0"][:N_NEE],
+        _REF[key] = LN.nee(oracle, c["sph"], c["tri"], c["rays"][:N_NEE], 2, 3, backend, c["wi"], states=c["st0"][:N_NEE],
                            by_power=by_power, cone=cone)
     return _REF[key]
-
-
-def _assert_direct(got_direct, got_states, want, idx, what):
-    ok = D.records_equal(got_direct[idx], want["direct"][idx])
-    assert ok.all(), (what, np.asarray(idx)[~ok][:5], got_direct[idx][~ok][:3], want["direct"][idx][~ok][:3])
-    assert np.array_equal(got_states[idx], want["states"][idx]), (what, "states")
-
-
-def _device_direct(sc, dev, hits, states, n, **kw):
-    d_hits, d_state, d_out = dev.put(hits), dev.put(states), dev.alloc(32 * n, FILL)
-    sc.direct_device(d_hits, n, d_state, d_out, **kw)
-    sc.collect()
-    return dev.get(d_out, _abi.DIRECT_DTYPE, n), dev.get(d_state, np.uint64, 4 * n).reshape(n, 4)
-
-
-def _assert_nee(got, want, mode, n, what):
-    ok = np.all(B.same_bits(got["rgb"], want["rgb"][mode][:n]), 1)
-    assert ok.all(), (what, np.nonzero(~ok)[0][:5], got["rgb"][~ok][:3], want["rgb"][mode][:n][~ok][:3])
-    assert np.array_equal(got["segments"], want["segments"][:n]) and np.array_equal(got["shadow"], want["shadow"][:n]), what
-    assert np.array_equal(got["states"], want["states"][:n]), what
 
 
 # ---------------------------------------------------------------- 1. both kernels against the restatement
@@ -159,7 +141,7 @@ def test_direct_is_bit_exact(ndev, oracle, dev, name, cfg, by_power):
     assert {D.LIT, D.OCCLUDED, D.FACING_AWAY} <= set(status.tolist()), (name, set(status.tolist()))
     assert want["in_cone"].sum() > 50, (name, int(want["in_cone"].sum()))
     if name in ("regimes", "many_lights"):                                 # sphere lights outside the regime too
-        sphere_prims = LP.Table(c["sph"], c["tri"], c["wi"]).list
+        sphere_prims = LN.Table(c["sph"], c["tri"], c["wi"]).list
         is_sphere = {pos for pos, kind, _ in sphere_prims if kind == "sphere"}
         drew_sphere = np.isin(want["direct"]["light"], list(is_sphere)) & ~np.isin(status, (D.SKIPPED, D.NO_LIGHTS))
         assert (drew_sphere & ~want["in_cone"]).sum() > 20, name
@@ -179,7 +161,7 @@ def test_direct_is_bit_exact(ndev, oracle, dev, name, cfg, by_power):
         assert off["direct"][rest].tobytes() == got["direct"][rest].tobytes()
         assert not D.records_equal(off["direct"][want["in_cone"]], got["direct"][want["in_cone"]]).any()
         lit = got["direct"][want["in_cone"] & (status == D.LIT)]
-        ip_max = 1.0 / LP.Table(c["sph"], c["tri"], c["wi"], by_power).p.min()
+        ip_max = 1.0 / LN.Table(c["sph"], c["tri"], c["wi"], by_power).p.min()
     with rt.Scene(0, rt.World(c["sph"], c["tri"], c["wi"])) as fresh:      # a scene that never saw the setting
         base = fresh.direct(step["hits"], step["states"], flags=flags | bit)
     assert base["direct"].tobytes() == off["direct"].tobytes() and np.array_equal(base["states"], off["states"])
@@ -211,7 +193,7 @@ def test_direct_on_the_regimes_threshold(ndev, oracle):
     hits["px"], hits["py"], hits["pz"], hits["nx"], hits["ny"], hits["nz"] = *P.T, *nrm.T
     hits["distance"], hits["index"] = 1.0, 0
     st = R.states(n, 4501)
-    want = CN.direct(oracle, sph, tri, hits, st, 1, None, cone=True)
+    want = LN.direct(oracle, sph, tri, hits, st, 1, None, cone=True)
     q_far = CN.cone_axis(P.T.copy(), np.array(c_far, F32)[:, None], F32(0.25))[3]
     q_near = CN.cone_axis(P.T.copy(), np.array(c_near, F32)[:, None], F32(0.5))[3]
     far_pts, near_pts = np.arange(n) // m % 2 == 0, np.arange(n) // m % 2 == 1
@@ -259,8 +241,8 @@ def test_nee_seeded_streams_and_depths(ndev, oracle, max_bounces):
     c, _ = _case(oracle, "two_lights")
     m = 120
     rays = c["rays"][:m]
-    want = CN.nee(oracle, c["sph"], c["tri"], rays, 3, max_bounces, 1, c["wi"], seed=0xC0DE + max_bounces, cone=True)
-    given = CN.nee(oracle, c["sph"], c["tri"], rays, 1, max_bounces, 1, c["wi"], states=c["st0"][:m], cone=True)
+    want = LN.nee(oracle, c["sph"], c["tri"], rays, 3, max_bounces, 1, c["wi"], seed=0xC0DE + max_bounces, cone=True)
+    given = LN.nee(oracle, c["sph"], c["tri"], rays, 1, max_bounces, 1, c["wi"], states=c["st0"][:m], cone=True)
     with _scene(c) as sc:
         for mode in (LIGHT_ONLY, MIS):
             got = _nee(sc, rays, spp=3, max_bounces=max_bounces, seed=0xC0DE + max_bounces, mode=mode)
@@ -343,7 +325,7 @@ def test_next_list_of_a_bounce_step_goes_straight_in(ndev, oracle, dev):
 # ---------------------------------------------------------------- 2. invariants
 def test_triangle_records_are_the_area_bytes(ndev, oracle):
     c, step = _case(oracle, "many_lights")
-    tri_pos = {pos for pos, kind, _ in LP.Table(c["sph"], c["tri"], c["wi"]).list if kind == "triangle"}
+    tri_pos = {pos for pos, kind, _ in LN.Table(c["sph"], c["tri"], c["wi"]).list if kind == "triangle"}
     with _scene(c) as sc:
         on = sc.direct(step["hits"], step["states"])["direct"]
         sc.set_light_sampling(AREA)
@@ -444,7 +426,7 @@ def test_light_only_is_the_fold_of_bounce_and_direct_under_cone(ndev, oracle, na
     c, _ = _case(oracle, name)
     rays = _one_window(c["rays"])
     n = len(rays)
-    lights = N.Lights(c["sph"], c["tri"], c["wi"])
+    lights = LN.Table(c["sph"], c["tri"], c["wi"])
     with _scene(c) as sc:
         for max_bounces in (1, 3):
             want_c, want_segs, want_shadow, want_states = _cone_fold(sc, lights, rays, c["st0"], max_bounces, flags)

@@ -1,5 +1,6 @@
 """Direct lighting of caller rays on the GPU (rt_scene_direct, rt_scene_direct_device):
-1. parity, bit for bit, with the CPU restatement tests/_direct_np.py (pinned by tests/test_direct_host.py): every field of rt_direct
+1. parity, bit for bit, with the CPU restatement tests/_lights_np.py `direct` (its arithmetic pinned by tests/test_direct_host.py, its
+   bytes by tests/test_light_restatement.py): every field of rt_direct
    and the states, host form and device form, under four configurations, on one diffuse sphere under one emissive sphere (M = 1), the
    sphere, triangle and mixed (permuted world) scenes of tests/_bounce_np.py, a scene without emitters (M = 0) and a tree deeper than
    the walk's stack (the scan fallback); batch sizes around the wave and workgroup sizes;
@@ -23,6 +24,7 @@ from ray_tracer_s8_amd import _abi, scenes
 
 import _bounce_np as B
 import _direct_np as D
+import _lights_np as LN
 from test_direct_surface import bad_arg_calls
 from test_gpu_bounce import CONFIGS, FILL, SCAN, SENTINEL_U32, WALK, Dev, dev  # noqa: F401  (dev: a fixture of this module too)
 
@@ -77,7 +79,7 @@ def _reference(oracle, name, cfg):
     flags, _, backend = CONFIGS[cfg]
     if (name, cfg) not in _REF:
         c, step = _case(oracle, name, flags)
-        _REF[name, cfg] = D.direct(oracle, c["sph"], c["tri"], step["hits"], step["states"], backend, c["wi"])
+        _REF[name, cfg] = LN.direct(oracle, c["sph"], c["tri"], step["hits"], step["states"], backend, c["wi"])
     return _REF[name, cfg]
 
 
@@ -233,7 +235,7 @@ def test_k_step_integrator_equals_the_restatement(ndev, oracle, cfg):
     sph, tri, wi = c["sph"], c["tri"], c["wi"]
     want_rgb, want_states = D.integrate(
         lambda r, s, act, given: B.step(oracle, sph, tri, r, s, backend, wi, as_given=given, active=act),
-        lambda h, s, act: D.direct(oracle, sph, tri, h, s, backend, wi, active=act), rays, st0, 3)
+        lambda h, s, act: LN.direct(oracle, sph, tri, h, s, backend, wi, active=act), rays, st0, 3)
     with rt.Scene(0, rt.World(sph, tri, wi)) as sc:
         got_rgb, got_states = D.integrate(
             lambda r, s, act, given: sc.bounce(r, s, active=act, as_given=given, flags=flags, want_hits=True),

@@ -1,6 +1,6 @@
 """Light selection by power on the GPU (RT_FLAG_LIGHTS_BY_POWER in rt_scene_direct*, rt_scene_trace_nee*; rt_scene_light_table):
-1. both kernels against the CPU restatement tests/_lightpick_np.py (pinned by tests/test_lightpick_host.py), bit for bit: every rt_direct
-   field and the states, the NEE colours of both modes, segment and shadow counts and states; M = 2 (one sphere, one triangle light) and
+1. both kernels against the CPU restatement tests/_lights_np.py with by_power=True (its table, pick and weights pinned by
+   tests/test_lightpick_host.py, its bytes by tests/test_light_restatement.py), bit for bit: every rt_direct field and the states, the NEE colours of both modes, segment and shadow counts and states; M = 2 (one sphere, one triangle light) and
    M = 33 (mixed kinds, an emitter of albedo 0, one of radius 0, emissions over six decades, a permuted world_index); the four flag sets
    of tests/test_gpu_direct.py each with the bit; host and device forms; batches of 1, 63, 64, 65 and 2000 records; active lists; the
    next list of a bounce step passed straight in.  Without the feature the flag changes nothing and these fail;
@@ -25,8 +25,9 @@ from ray_tracer_s8_amd import _abi, scenes
 import _bounce_np as B
 import _direct_np as D
 import _lightpick_np as LP
-import _nee_np as N
+import _lights_np as LN
 from test_gpu_bounce import CONFIGS, FILL, Dev, dev  # noqa: F401  (dev: a fixture of this module too)
+from test_gpu_direct import _assert_equal as _assert_direct, _device_direct, _gap_and_bound, _room_rays
 from test_gpu_nee import _composed_sample, _device_nee, _nee, _one_window, _same
 
 pytestmark = pytest.mark.gpu
@@ -35,7 +36,7 @@ ROOT = Path(__file__).resolve().parent.parent
 R = B.R
 F32 = np.float32
 BIT = _abi.RT_FLAG_LIGHTS_BY_POWER
-LIGHT_ONLY, MIS = N.LIGHT_ONLY, N.MIS
+LIGHT_ONLY, MIS = LN.LIGHT_ONLY, LN.MIS
 N_RAYS = 2000
 N_NEE = 600                                      # the rays of the NEE comparisons with the (per-ray Python) restatement
 SIZES = [1, 63, 64, 65, 2000]
@@ -65,7 +66,8 @@ def _ref_direct(oracle, name, cfg):
     flags, _, backend = CONFIGS[cfg]
     if ("direct", name, cfg) not in _REF:
         c, step = _case(oracle, name, flags)
-        _REF["direct", name, cfg] = LP.direct(oracle, c["sph"], c["tri"], step["hits"], step["states"], backend, c["wi"])
+        _REF["direct", name, cfg] = LN.direct(oracle, c["sph"], c["tri"], step["hits"], step["states"], backend, c["wi"],
+                                               by_power=True)
     return _REF["direct", name, cfg]
 
 
@@ -73,21 +75,9 @@ def _ref_nee(oracle, name, backend):
     """The restatement on the first N_NEE rays of the case, 2 samples from given states, 3 bounces: once per (scene, backend)."""
     if ("nee", name, backend) not in _REF:
         c, _ = _case(oracle, name)
-        _REF["nee", name, backend] = LP.nee(oracle, c["sph"], c["tri"], c["rays"][:N_NEE], 2, 3, backend, c["wi"], states=c["st0"][:N_NEE])
+        _REF["nee", name, backend] = LN.nee(oracle, c["sph"], c["tri"], c["rays"][:N_NEE], 2, 3, backend, c["wi"], states=c["st0"][:N_NEE],
+                                             by_power=True)
     return _REF["nee", name, backend]
-
-
-def _assert_direct(got_direct, got_states, want, idx, what):
-    ok = D.records_equal(got_direct[idx], want["direct"][idx])
-    assert ok.all(), (what, np.asarray(idx)[~ok][:5], got_direct[idx][~ok][:3], want["direct"][idx][~ok][:3])
-    assert np.array_equal(got_states[idx], want["states"][idx]), (what, "states")
-
-
-def _device_direct(sc, dev, hits, states, n, **kw):
-    d_hits, d_state, d_out = dev.put(hits), dev.put(states), dev.alloc(32 * n, FILL)
-    sc.direct_device(d_hits, n, d_state, d_out, **kw)
-    sc.collect()
-    return dev.get(d_out, _abi.DIRECT_DTYPE, n), dev.get(d_state, np.uint64, 4 * n).reshape(n, 4)
 
 
 def _assert_nee(got, want, mode, n, what):
@@ -243,7 +233,7 @@ def test_flag_changes_no_bit_with_one_emitter_or_a_degenerate_table(ndev, oracle
     else:
         sph, tri, wi = _degenerate_scene(which)
         rays = _case(oracle, "many_lights")[0]["rays"]
-        t = LP.Table(sph, tri, wi)
+        t = LN.Table(sph, tri, wi)
         assert t.degenerate and t.M == 33 and np.all(t.ip == F32(33))
         if which == "overflow":
             assert np.all(np.isfinite(t.q))
@@ -272,7 +262,7 @@ def test_light_only_is_the_fold_of_bounce_and_direct_with_the_flag(ndev, oracle,
     c, _ = _case(oracle, "many_lights")
     rays = _one_window(c["rays"])
     n = len(rays)
-    lights = N.Lights(c["sph"], c["tri"], c["wi"])
+    lights = LN.Table(c["sph"], c["tri"], c["wi"])
     with rt.Scene(0, rt.World(c["sph"], c["tri"], c["wi"])) as sc:
         for max_bounces in (1, 3):
             want_c, want_segs, want_shadow, want_states = _composed_sample(sc, lights, rays, c["st0"], max_bounces, flags, False)
@@ -292,7 +282,7 @@ def test_light_only_is_the_fold_of_bounce_and_direct_with_the_flag(ndev, oracle,
 @pytest.mark.parametrize("name", SCENES)
 def test_light_table_equals_the_restatement(ndev, name):
     sph, tri, wi = SCENES[name]()
-    t = LP.Table(sph, tri, wi)
+    t = LN.Table(sph, tri, wi)
     lib = _abi.load()
     with rt.Scene(0, rt.World(sph, tri, wi)) as sc:
         sc.collect()
@@ -333,17 +323,6 @@ def test_lights_are_drawn_with_the_tables_probability(ndev):
 
 
 # ---------------------------------------------------------------- 5. unbiased, and the lower variance
-def _gap_and_bound(x, y):
-    """Per channel: |mean_x - mean_y| and 5 sqrt(var_x / N_x + var_y / N_y), the variances from the samples themselves (the rule of
-    tests/test_gpu_direct.py and tests/test_gpu_nee.py)."""
-    return np.abs(x.mean(0) - y.mean(0)), 5 * np.sqrt(x.var(0, ddof=1) / len(x) + y.var(0, ddof=1) / len(y))
-
-
-def _room_rays():
-    """2^16 ray samples of 2 048 fixed camera rays, pitched down onto the spheres and the ground around them (tests/test_gpu_direct.py)."""
-    return np.tile(D.camera_rays(64, 32, 0.3, -0.1), 32)
-
-
 _EST = {}
 
 

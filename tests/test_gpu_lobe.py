@@ -1,6 +1,6 @@
 """Light samples at glossy hits on the GPU (rt_scene_set_glossy_sampling(RT_GLOSSY_MIS) for rt_scene_trace_nee* in mode RT_NEE_MIS):
-1. the kernel against the CPU restatement tests/_lobe_np.py (pinned by tests/test_lobe_host.py), bit for bit: colours, segment and
-   shadow counts and written-back states on the glossy room of tests/test_gpu_nee.py (a ground of roughness 0.5, spheres of roughness
+1. the kernel against the CPU restatement tests/_lights_np.py with glossy=True (its lobe arithmetic pinned by tests/test_lobe_host.py,
+   its bytes by tests/test_light_restatement.py), bit for bit: colours, segment and shadow counts and written-back states on the glossy room of tests/test_gpu_nee.py (a ground of roughness 0.5, spheres of roughness
    0, 0.5 and 1, one sphere light and one triangle light), 300 rays, 2 samples, 3 bounces, given states; with and without
    RT_FLAG_LIGHTS_BY_POWER, under RT_LIGHTS_AREA and RT_LIGHTS_CONE, the four flag sets of tests/test_gpu_bounce.py; host and device
    forms; batches of 1, 63, 64, 65 and 2000 (the first 300 against the restatement, the rest host == device); the seeded streams at
@@ -27,6 +27,7 @@ from ray_tracer_s8_amd import _abi
 
 import _bounce_np as B
 import _direct_np as D
+import _lights_np as LN
 import _lobe_np as L
 from test_gpu_bounce import CONFIGS, FILL, Dev, dev  # noqa: F401  (dev: a fixture of this module too)
 from test_gpu_direct import _gap_and_bound, _room_rays
@@ -40,7 +41,7 @@ F32 = np.float32
 AREA, CONE = _abi.RT_LIGHTS_AREA, _abi.RT_LIGHTS_CONE
 BOUNCE, GLOSSY = _abi.RT_GLOSSY_BOUNCE, _abi.RT_GLOSSY_MIS
 POWER = _abi.RT_FLAG_LIGHTS_BY_POWER
-LIGHT_ONLY, MIS = L.LIGHT_ONLY, L.MIS
+LIGHT_ONLY, MIS = LN.LIGHT_ONLY, LN.MIS
 N_RAYS = 2000
 N_NEE = 300                                      # the rays compared with the (per-ray Python) restatement
 SIZES = [1, 63, 64, 65, 2000]
@@ -71,7 +72,7 @@ def _ref(oracle, backend, by_power, cone):
     key = (backend, by_power, cone)
     if key not in _REF:
         c = _case(oracle)
-        _REF[key] = L.nee(oracle, c["sph"], c["tri"], c["rays"][:N_NEE], 2, 3, backend, None, states=c["st0"][:N_NEE], by_power=by_power,
+        _REF[key] = LN.nee(oracle, c["sph"], c["tri"], c["rays"][:N_NEE], 2, 3, backend, None, states=c["st0"][:N_NEE], by_power=by_power,
                           cone=cone, glossy=True)
     return _REF[key]
 
@@ -150,8 +151,8 @@ def test_seeded_streams_and_depths(ndev, oracle, max_bounces):
     c = _case(oracle)
     m = 120
     rays = c["rays"][:m]
-    want = L.nee(oracle, c["sph"], c["tri"], rays, 3, max_bounces, 1, None, seed=0x10BE + max_bounces, cone=False, glossy=True)
-    given = L.nee(oracle, c["sph"], c["tri"], rays, 1, max_bounces, 1, None, states=c["st0"][:m], cone=False, glossy=True)
+    want = LN.nee(oracle, c["sph"], c["tri"], rays, 3, max_bounces, 1, None, seed=0x10BE + max_bounces, cone=False, glossy=True)
+    given = LN.nee(oracle, c["sph"], c["tri"], rays, 1, max_bounces, 1, None, states=c["st0"][:m], cone=False, glossy=True)
     with _scene(c["sph"], c["tri"]) as sc:
         got = _nee(sc, rays, spp=3, max_bounces=max_bounces, seed=0x10BE + max_bounces, mode=MIS)
         _assert_mis(got, want, m, (max_bounces, "seeded"))
@@ -168,8 +169,8 @@ def test_ray_as_given_with_non_unit_directions(ndev, oracle, dev):
     for f in ("dx", "dy", "dz"):
         rays[f] = rays[f] * scale
     st0 = R.states(m, 5501)
-    want = L.nee(oracle, c["sph"], c["tri"], rays, 2, 3, 1, None, as_given=True, states=st0, cone=True, glossy=True)
-    unit = L.nee(oracle, c["sph"], c["tri"], rays, 2, 3, 1, None, as_given=False, states=st0, cone=True, glossy=True)
+    want = LN.nee(oracle, c["sph"], c["tri"], rays, 2, 3, 1, None, as_given=True, states=st0, cone=True, glossy=True)
+    unit = LN.nee(oracle, c["sph"], c["tri"], rays, 2, 3, 1, None, as_given=False, states=st0, cone=True, glossy=True)
     assert want["counts"]["lobe"] > 100 and want["rgb"][MIS].tobytes() != unit["rgb"][MIS].tobytes()
     with _scene(c["sph"], c["tri"], lights=CONE) as sc:
         got = _nee(sc, rays, spp=2, max_bounces=3, rng_state=st0, mode=MIS, as_given=True)
@@ -192,7 +193,7 @@ def test_class_boundaries(ndev, oracle, cone):
     on_tri = idx == len(sph)
     nd = B._dot(np.stack([first["hits"]["nx"], first["hits"]["ny"], first["hits"]["nz"]], 1), B.directions(rays, False))
     assert (on_tri & (nd > 0)).sum() >= 20 and (on_tri & (nd < 0)).sum() >= 20          # its back and its front
-    want = L.nee(oracle, sph, tri, rays, 2, 3, 1, None, states=st0, cone=cone, glossy=True)
+    want = LN.nee(oracle, sph, tri, rays, 2, 3, 1, None, states=st0, cone=cone, glossy=True)
     assert min(want["counts"][k] for k in ("none", "diffuse", "lobe")) > 50, want["counts"]
     assert want["counts"]["emitted_after_lobe"] > 50, want["counts"]
     with _scene(sph, tri, lights=CONE if cone else AREA) as sc:

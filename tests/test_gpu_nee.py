@@ -2,8 +2,8 @@
 1. RT_NEE_LIGHT_ONLY equals, bit for bit, the contract's forward fold over the EXISTING entry points — Scene.bounce per step, Scene.direct
    on the scattered hits whose primitive has roughness 0 — colours, segment and shadow-ray counts and final states, for max_bounces 0, 1
    and 3, with given states (spp = 1) and seeded (spp = 3, the per-sample states formed with the oracle's seeding);
-2. both modes equal the CPU restatement tests/_nee_np.py (pinned by tests/test_nee_host.py) bit for bit on six scenes under four
-   configurations, every ray in its own window, states included;
+2. both modes equal the CPU restatement tests/_lights_np.py `nee` (its arithmetic pinned by tests/test_nee_host.py, its bytes by
+   tests/test_light_restatement.py) bit for bit on six scenes under four configurations, every ray in its own window, states included;
 3. without emitters the segments and the written-back states are Scene.trace's;
 4. batch sizes around the wave and workgroup sizes, the device form against the host form, two streams at once and repeated calls,
    spp = 4 against two calls of spp = 2, the scan engine on a tree deeper than the walk's stack; host-form calls of all five
@@ -24,6 +24,7 @@ from ray_tracer_s8_amd import _abi
 
 import _bounce_np as B
 import _direct_np as D
+import _lights_np as LN
 import _nee_np as N
 from test_gpu_bounce import CONFIGS, FILL, SCAN, Dev, dev  # noqa: F401  (dev: a fixture of this module too)
 from test_gpu_direct import SCENES, SIZES, _gap_and_bound, _room_rays, _scene
@@ -127,7 +128,7 @@ def _check_light_only(oracle, name, cfg, max_bounces):
     c = _case(oracle, name)
     rays = _one_window(c["rays"])
     n = len(rays)
-    lights = N.Lights(c["sph"], c["tri"], c["wi"])
+    lights = LN.Table(c["sph"], c["tri"], c["wi"])
     with rt.Scene(0, rt.World(c["sph"], c["tri"], c["wi"])) as sc:
         assert sc.n_lights == lights.M
         # spp = 1, given states
@@ -174,7 +175,7 @@ def _reference(oracle, name, backend):
     """The restatement on the REF rays of the case, 2 samples from given states, 3 bounces: once per (scene, backend)."""
     if (name, backend) not in _REF:
         c = _case(oracle, name)
-        _REF[name, backend] = N.nee(oracle, c["sph"], c["tri"], c["rays"][REF], 2, 3, backend, c["wi"], states=c["st0"][REF])
+        _REF[name, backend] = LN.nee(oracle, c["sph"], c["tri"], c["rays"][REF], 2, 3, backend, c["wi"], states=c["st0"][REF])
     return _REF[name, backend]
 
 
@@ -379,7 +380,7 @@ def _estimates(which, seed):
     n = len(rays)
     assert n == 1 << 16
     o, d = R.od(rays)
-    lights = N.Lights(sph, tri)
+    lights = LN.Table(sph, tri)
     with rt.Scene(0, rt.World(sph, tri)) as sc:
         assert sc.n_lights == lights.M == (3 if which == "enclosed" else 2)
         A = sc.trace(o, d, rays["t_min"], rays["t_max"], spp=1, max_bounces=_MAX_BOUNCES, rng_state=R.states(n, seed))[0]

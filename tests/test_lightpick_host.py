@@ -1,6 +1,6 @@
 """Light selection by power off the GPU, through the g++ harness tests/host/lightpick_host.cpp:
 (a) the light table of the host's scene derivation (csrc/rt_scene_host.h light_table) equals the numpy restatement of rt_tile.h
-    (tests/_lightpick_np.py) bit for bit: M = 1, 2, 3, 7, 33 and 1000, powers over twelve decades, spheres and triangles mixed, with
+    (tests/_lights_np.py Table) bit for bit: M = 1, 2, 3, 7, 33 and 1000, powers over twelve decades, spheres and triangles mixed, with
     and without a world_index, below and above the storage-reorder threshold, emitters without power (albedo 0, radius 0, a degenerate
     triangle, a NaN albedo) and the three degenerate tables (all zero, a sum that overflows, one infinite power), whose ip is (float)M;
 (b) the pick (csrc/rt_direct_math.h pick_light_power) equals the restatement at its ends — u = 0, the largest u below 0.5, 0.5, the
@@ -19,6 +19,7 @@ import pytest
 
 import _direct_np as D
 import _lightpick_np as LP
+import _lights_np as LN
 import _ray_cases as R
 from ray_tracer_s8_amd import _abi
 
@@ -121,7 +122,7 @@ def test_table_equals_the_restatement(lib, M, kind):
         sph, tri, wi = _world(M, 0, extra, kind)
         assert (len(sph) + len(tri) >= REORDER_MIN_PRIMS) == (extra == 80 or M >= 50)
         for w in (None, wi):
-            want = LP.Table(sph, tri, w)
+            want = LN.Table(sph, tri, w)
             assert want.M == M and want.degenerate == (kind != "spread")
             if kind == "overflow":
                 assert np.all(np.isfinite(want.q)) and want.total == np.inf
@@ -164,7 +165,7 @@ class _Sums:
         self.degenerate = not (self.total > 0 and self.total < np.inf)
         self.by_power = not self.degenerate
 
-    pick = LP.Table.pick
+    pick = LN.Table.pick
 
 
 def _edge_draws(t):
@@ -234,7 +235,7 @@ def _count_bound(p):
 @pytest.mark.parametrize("M,kind", TABLES)
 def test_every_u01_picks_by_the_tables_probability(lib, M, kind):
     sph, tri, wi = _world(M, 0, 5, kind)
-    t = LP.Table(sph, tri, wi)
+    t = LN.Table(sph, tri, wi)
     counts = np.zeros(M, np.uint64)
     c = np.ascontiguousarray(t.c)
     bad = lib.lightpick_counts(M, c.ctypes.data, int(np.array([t.total], F32).view(np.uint32)[0]), counts.ctypes.data)

@@ -6,8 +6,8 @@
     cg == cs is NOT asserted at rho = 0: that hit takes the diffuse path and never the lobe formula;
 (c) at every lobe-sampled seeded record kappa >= 0 (the origin lies outside the sphere, or on it) and kappa is within 2^-19 of its terms
     of the header's formula in float64, which is |c|^2 - r^2 up to r^2 (n.n - 1); in the lobe cg > 0 and is no NaN;
-(d) the restatement's driver with glossy=False is tests/_cone_np.py's `nee` byte for byte; with glossy=True on the glossy room it
-    meets every class, drops some lobe samples, and a scene whose roughnesses are 0 and 1 only gives glossy=False's RT_NEE_MIS bytes;
+(d) the restatement's driver (tests/_lights_np.py) with glossy=False gives the bytes recorded from tests/_cone_np.py's `nee` that it
+    replaced (tests/test_light_restatement.py); with glossy=True on the glossy room it meets every class, drops some lobe samples, and a scene whose roughnesses are 0 and 1 only gives glossy=False's RT_NEE_MIS bytes;
 (e) the harness as a stand-alone program under -fsanitize=address,undefined."""
 import ctypes as C
 import subprocess
@@ -17,10 +17,11 @@ import numpy as np
 import pytest
 
 import _bounce_np as B
-import _cone_np as CN
 import _direct_np as D
+import _lights_np as LN
 import _lobe_cases as LC
 import _lobe_np as L
+from test_light_restatement import assert_recorded, scene
 
 ROOT = Path(__file__).resolve().parents[1]
 CSRC = ROOT / "ray_tracer_s8_amd" / "csrc"
@@ -124,24 +125,24 @@ def test_driver_without_the_setting_is_the_cone_restatement_and_with_it_meets_ev
     rays = D.camera_rays(12, 8, 0.6, -0.1)
     n = len(rays)
     st = R.states(n, 1800)
+    held = scene("glossy")["nee"]                                           # the rays of this batch whose results are recorded
     for cone in (False, True):
-        a = CN.nee(oracle, sph, tri, rays, 2, 3, 1, None, states=st, cone=cone)
-        b = L.nee(oracle, sph, tri, rays, 2, 3, 1, None, states=st, cone=cone, glossy=False)
-        for mode in CN.MODES:
-            assert a["rgb"][mode].tobytes() == b["rgb"][mode].tobytes()
-        assert np.array_equal(a["states"], b["states"]) and np.array_equal(a["segments"], b["segments"])
-        z = L.nee(oracle, sph, tri, rays, 2, 3, 1, None, states=st, cone=cone, glossy=True)
+        a = LN.nee(oracle, sph, tri, rays, 2, 3, 1, None, states=st, cone=cone, glossy=False)
+        assert_recorded(a, f"nee/_cone_np/glossy/p0c{int(cone)}g0", held)    # (CN.nee of these rays and states, cone=cone)
+        z = LN.nee(oracle, sph, tri, rays, 2, 3, 1, None, states=st, cone=cone, glossy=True)
+        assert_recorded(z, f"nee/_lobe_np/glossy/p0c{int(cone)}g1", held)
         cnt = z["counts"]
         assert cnt["lobe"] > 20 and cnt["diffuse"] > 5 and cnt["none"] > 5 and cnt["dropped"] > 0, cnt
         assert cnt["dropped"] < cnt["lobe"] and z["shadow"].sum() > a["shadow"].sum()
-        assert not np.array_equal(z["states"], a["states"]) and z["rgb"][L.MIS].tobytes() != a["rgb"][L.MIS].tobytes()
-        assert np.isfinite(z["rgb"][L.MIS]).all()
+        assert not np.array_equal(z["states"], a["states"]) and z["rgb"][LN.MIS].tobytes() != a["rgb"][LN.MIS].tobytes()
+        assert np.isfinite(z["rgb"][LN.MIS]).all()
     # roughnesses 0 and 1 only: no hit is lobe-sampled, RT_GLOSSY_BOUNCE's bytes
     sph2 = sph.copy()
     sph2["roughness"][:4] = [1.0, 0.0, 1.0, 0.0]
-    a = CN.nee(oracle, sph2, tri, rays, 2, 3, 1, None, states=st, cone=False)
-    z = L.nee(oracle, sph2, tri, rays, 2, 3, 1, None, states=st, cone=False, glossy=True)
-    assert z["counts"]["lobe"] == 0 and z["rgb"][L.MIS].tobytes() == a["rgb"][L.MIS].tobytes()
+    a = LN.nee(oracle, sph2, tri, rays, 2, 3, 1, None, states=st, cone=False, glossy=False)
+    assert_recorded(a, "nee/_cone_np/rough01/p0c0g0", held)
+    z = LN.nee(oracle, sph2, tri, rays, 2, 3, 1, None, states=st, cone=False, glossy=True)
+    assert z["counts"]["lobe"] == 0 and z["rgb"][LN.MIS].tobytes() == a["rgb"][LN.MIS].tobytes()
     assert np.array_equal(z["states"], a["states"]) and np.array_equal(z["shadow"], a["shadow"])
 
 
