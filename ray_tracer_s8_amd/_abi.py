@@ -47,6 +47,14 @@ RT_GLOSSY_BOUNCE = 0                # rt_scene_set_glossy_sampling: RT_NEE_MIS t
 RT_GLOSSY_MIS = 1                   # ... or one weighted by the density of the reference's scatter lobe, at 0 < roughness < 1
 RT_MAX_BOUNCES = 62
 RT_MAX_SPP = 4096                 # samples per pixel limit (rt_tile.h)
+RT_MAX_PRIMITIVES = 0x3ffffff     # spheres + triangles of a scene: what the kernels' 32-bit byte offsets can address
+RT_FRAME_STATS_ENTRIES = 16       # rt_frame_stats.entry_segments
+
+
+def _record_dtype(struct) -> np.dtype:
+    """The numpy record dtype with the layout of a ctypes Structure of scalars (arrays of it are what the calls pass and return)."""
+    return np.dtype([(n, np.dtype(t).str) for n, t in struct._fields_])
+
 
 # numpy dtypes with the exact layout of rt_sphere / rt_triangle (no padding)
 SPHERE_DTYPE = np.dtype(
@@ -94,7 +102,7 @@ class FrameStats(C.Structure):
         ("totals", TileStats), ("wall_ms", C.c_float), ("pin_ms", C.c_float), ("scene_ms", C.c_float),
         ("kernel_ms", C.c_float), ("d2h_exposed_ms", C.c_float), ("host_ms", C.c_float),
         ("n_devices", C.c_uint32), ("pinned", C.c_uint32),
-        ("assignment", C.c_uint32), ("balance_max_over_mean", C.c_float), ("entry_segments", C.c_uint64 * 16),
+        ("assignment", C.c_uint32), ("balance_max_over_mean", C.c_float), ("entry_segments", C.c_uint64 * RT_FRAME_STATS_ENTRIES),
     ]
 
 
@@ -114,8 +122,8 @@ RT_HIT_NONE = 0xFFFFFFFF
 RT_QUERY_CLOSEST = 0
 RT_QUERY_ANY = 1
 # numpy twins of rt_ray / rt_hit (arrays of them are what Scene.intersect passes and returns)
-RAY_DTYPE = np.dtype([(n, "<f4") for n, _ in Ray._fields_])
-HIT_DTYPE = np.dtype([(n, "<u4" if n == "index" else "<f4") for n, _ in Hit._fields_])
+RAY_DTYPE = _record_dtype(Ray)
+HIT_DTYPE = _record_dtype(Hit)
 
 class TraceRequest(C.Structure):
     """rt_trace_request: samples per ray, bounces, seed of the seeded streams, RT_FLAG_* and the form of the first ray."""
@@ -142,7 +150,7 @@ RT_BOUNCE_SCATTERED = 0
 RT_BOUNCE_EMITTED = 1
 RT_BOUNCE_MISSED = 2
 # numpy twin of rt_bounce (what Scene.bounce returns)
-BOUNCE_DTYPE = np.dtype([("r", "<f4"), ("g", "<f4"), ("b", "<f4"), ("status", "<u4")])
+BOUNCE_DTYPE = _record_dtype(Bounce)
 
 
 class DirectRequest(C.Structure):
@@ -163,7 +171,7 @@ RT_DIRECT_FACING_AWAY = 2
 RT_DIRECT_NO_LIGHTS = 3
 RT_DIRECT_SKIPPED = 4
 # numpy twin of rt_direct (what Scene.direct returns)
-DIRECT_DTYPE = np.dtype([(n, "<u4" if n in ("light", "status") else "<f4") for n, _ in Direct._fields_])
+DIRECT_DTYPE = _record_dtype(Direct)
 
 
 class NeeRequest(C.Structure):
@@ -231,6 +239,84 @@ assert C.sizeof(NeeRequest) == 32
 assert C.sizeof(AovPlanes) == 40
 assert C.sizeof(DenoiseRequest) == 40
 
+# the structs of rt_tile.h by their C names (rt_sphere and rt_triangle have numpy records only: SPHERE_DTYPE, TRIANGLE_DTYPE)
+STRUCTS = {
+    "rt_tile_request": TileRequest, "rt_tile_stats": TileStats, "rt_frame_stats": FrameStats, "rt_ray": Ray, "rt_hit": Hit,
+    "rt_trace_request": TraceRequest, "rt_bounce": Bounce, "rt_bounce_request": BounceRequest, "rt_direct_request": DirectRequest,
+    "rt_direct": Direct, "rt_nee_request": NeeRequest, "rt_aov_planes": AovPlanes, "rt_denoise_request": DenoiseRequest,
+    "rt_camera": Camera,
+}
+
+
+def _signatures() -> dict:
+    P, vp, i32, u32, sz = C.POINTER, C.c_void_p, C.c_int, C.c_uint32, C.c_size_t
+    vpp, intp, u8p, u32p, u64p, f32p = P(vp), P(i32), P(C.c_uint8), P(u32), P(C.c_uint64), P(C.c_float)
+    req, stats, ray, hit, planes, dreq, cam = P(TileRequest), P(TileStats), P(Ray), P(Hit), P(AovPlanes), P(DenoiseRequest), P(Camera)
+    trq, brq, drq, nrq = P(TraceRequest), P(BounceRequest), P(DirectRequest), P(NeeRequest)
+    return {
+        "rt_init": (i32, [intp]),
+        "rt_shutdown": (None, []),
+        "rt_abi_version": (u32, []),
+        "rt_hip_runtime_path": (sz, [C.c_char_p, sz]),
+        "rt_strerror": (C.c_char_p, [i32]),
+        "rt_last_error": (C.c_char_p, []),
+        "rt_tile_request_defaults": (None, [req]),
+        "rt_tile_bytes": (sz, [req]),
+        "rt_render_tile": (i32, [i32, req, vp, u32, vp, u32, vp, vp, sz, vp, stats]),
+        "rt_scene_create": (i32, [i32, vp, u32, vp, u32, vp, vpp]),
+        "rt_scene_destroy": (None, [vp]),
+        "rt_scene_render_tile": (i32, [vp, req, vp, sz, vp, stats]),
+        "rt_scene_render_tile_device": (i32, [vp, req, vp, sz, vp, vp]),
+        "rt_scene_render_tiles_device": (i32, [vp, req, u32, vpp, sz, vpp, vp]),
+        "rt_scene_render_tiles": (i32, [vp, req, u32, vpp, sz, vpp, stats]),
+        "rt_scene_render_tile_pass": (i32, [vp, req, u32, u32, f32p, u8p, sz, f32p, stats]),
+        "rt_scene_render_tiles_pass_device": (i32, [vp, req, u32, u32, u32, vpp, vpp, sz, vpp, vp]),
+        "rt_scene_collect": (i32, [vp, stats]),
+        "rt_scene_intersect": (i32, [vp, ray, u32, u32, u32, hit, stats]),
+        "rt_scene_intersect_device": (i32, [vp, vp, u32, u32, u32, vp, vp]),
+        "rt_scene_trace": (i32, [vp, trq, ray, u32, u64p, f32p, u32p, stats]),
+        "rt_scene_trace_device": (i32, [vp, trq, vp, u32, vp, vp, vp, vp]),
+        "rt_scene_bounce": (i32, [vp, brq, ray, u32, u64p, u32p, u32, P(Bounce), hit, u32p, u32p, stats]),
+        "rt_scene_bounce_device": (i32, [vp, brq, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "rt_scene_light_count": (i32, [vp, u32p]),
+        "rt_scene_light_table": (i32, [vp, u32, u32p, f32p, u32]),
+        "rt_scene_direct": (i32, [vp, drq, hit, u32, u64p, u32p, u32, P(Direct), stats]),
+        "rt_scene_direct_device": (i32, [vp, drq, vp, u32, vp, vp, vp, vp, vp]),
+        "rt_scene_set_light_sampling": (i32, [vp, u32]),
+        "rt_scene_light_sampling": (i32, [vp, u32p]),
+        "rt_scene_trace_nee": (i32, [vp, nrq, ray, u32, u64p, f32p, u32p, u32p, stats]),
+        "rt_scene_trace_nee_device": (i32, [vp, nrq, vp, u32, vp, vp, vp, vp, vp]),
+        "rt_scene_set_glossy_sampling": (i32, [vp, u32]),
+        "rt_scene_glossy_sampling": (i32, [vp, u32p]),
+        "rt_scene_render_aov": (i32, [vp, req, u32, u32, planes, stats]),
+        "rt_scene_render_aovs_device": (i32, [vp, req, u32, u32, u32, planes, vp]),
+        "rt_denoise_request_defaults": (None, [dreq]),
+        "rt_denoise_scratch_bytes": (sz, [u32, u32]),
+        "rt_scene_denoise": (i32, [vp, req, u32, dreq, vpp, planes, vpp, sz, vpp, vpp, stats]),
+        "rt_scene_denoise_device": (i32, [vp, req, u32, dreq, vpp, planes, vpp, sz, vpp, vpp, vp, sz, vp]),
+        "rt_camera_defaults": (None, [cam]),
+        "rt_scene_set_camera": (i32, [vp, cam]),
+        "rt_scene_camera_rays": (i32, [vp, req, u32, u32, ray, u64p, stats]),
+        "rt_scene_camera_rays_device": (i32, [vp, req, u32, u32, vp, vp, vp]),
+        "rt_frame_ctx_create": (i32, [intp, i32, vpp]),
+        "rt_frame_ctx_set_world": (i32, [vp, vp, u32, vp, u32, vp]),
+        "rt_frame_ctx_set_camera": (i32, [vp, cam]),
+        "rt_frame_ctx_render": (i32, [vp, req, vp, sz, P(FrameStats)]),
+        "rt_frame_ctx_release_buffer": (i32, [vp]),
+        "rt_frame_ctx_destroy": (None, [vp]),
+        "rt_render_frame": (i32, [intp, i32, req, vp, u32, vp, u32, vp, vp, sz, stats]),
+    }
+
+
+# every entry point of rt_tile.h, in the header's order: name -> (restype, argtypes).  _bind applies it to a loaded library; a
+# new entry point is one line here (tests/test_surface.py compares the table with the header, type by type)
+SIGNATURES = _signatures()
+# the rt_debug_* hooks of the test library that load_debug binds on top
+DEBUG_SIGNATURES = {
+    "rt_debug_set": (C.c_int, [C.c_char_p, C.c_int]),
+    "rt_debug_unit": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_void_p, C.c_void_p]),
+}
+
 
 def default_request(**kw) -> TileRequest:
     """Reference literals (slave main.rs:39-51, shapes/mod.rs:12-13, controller main.rs:33-39).
@@ -279,10 +365,7 @@ def load_debug() -> C.CDLL:
     global _dbg_lib
     if _dbg_lib is None:
         _dbg_lib = _bind(_build.build_debug())
-        _dbg_lib.rt_debug_set.argtypes = [C.c_char_p, C.c_int]
-        _dbg_lib.rt_debug_set.restype = C.c_int
-        _dbg_lib.rt_debug_unit.argtypes = [C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_void_p, C.c_void_p]
-        _dbg_lib.rt_debug_unit.restype = C.c_int
+        _apply(_dbg_lib, DEBUG_SIGNATURES)
     return _dbg_lib
 
 
@@ -302,134 +385,23 @@ class debug_library:
         return False
 
 
+def _apply(lib: C.CDLL, table: dict) -> None:
+    for name, (restype, argtypes) in table.items():
+        f = getattr(lib, name)
+        f.restype, f.argtypes = restype, list(argtypes)
+
+
 def _bind(path: Path) -> C.CDLL:
     if not path.exists():
         raise FileNotFoundError(
             f"{path} not found: the HIP extension is required (run `python -m ray_tracer_s8_amd.build`); "
             "there is no CPU fallback")
     lib = C.CDLL(str(path))
-    u8p, f32p, vp = C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.c_void_p
-    lib.rt_init.argtypes = [C.POINTER(C.c_int)]
-    lib.rt_init.restype = C.c_int
-    lib.rt_shutdown.argtypes = []
-    lib.rt_shutdown.restype = None
-    lib.rt_abi_version.argtypes = []
-    lib.rt_abi_version.restype = C.c_uint32
+    _apply(lib, {"rt_abi_version": SIGNATURES["rt_abi_version"]})
     if lib.rt_abi_version() != RT_ABI_VERSION:
         raise RuntimeError(f"{path} has ABI version {lib.rt_abi_version()}, this binding is written for "
                            f"{RT_ABI_VERSION}: rebuild it (python -m ray_tracer_s8_amd.build)")
-    lib.rt_strerror.argtypes = [C.c_int]
-    lib.rt_strerror.restype = C.c_char_p
-    lib.rt_last_error.argtypes = []
-    lib.rt_last_error.restype = C.c_char_p
-    lib.rt_tile_request_defaults.argtypes = [C.POINTER(TileRequest)]
-    lib.rt_tile_request_defaults.restype = None
-    lib.rt_tile_bytes.argtypes = [C.POINTER(TileRequest)]
-    lib.rt_tile_bytes.restype = C.c_size_t
-    lib.rt_render_tile.argtypes = [C.c_int, C.POINTER(TileRequest), vp, C.c_uint32, vp, C.c_uint32, vp,
-                                   vp, C.c_size_t, vp, C.POINTER(TileStats)]
-    lib.rt_render_tile.restype = C.c_int
-    lib.rt_scene_create.argtypes = [C.c_int, vp, C.c_uint32, vp, C.c_uint32, vp, C.POINTER(vp)]
-    lib.rt_scene_create.restype = C.c_int
-    lib.rt_scene_destroy.argtypes = [vp]
-    lib.rt_scene_destroy.restype = None
-    lib.rt_scene_render_tile.argtypes = [vp, C.POINTER(TileRequest), vp, C.c_size_t, vp, C.POINTER(TileStats)]
-    lib.rt_scene_render_tile.restype = C.c_int
-    lib.rt_scene_render_tile_device.argtypes = [vp, C.POINTER(TileRequest), vp, C.c_size_t, vp, vp]
-    lib.rt_scene_render_tile_device.restype = C.c_int
-    lib.rt_scene_render_tiles_device.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.POINTER(vp), C.c_size_t,
-                                                 C.POINTER(vp), vp]
-    lib.rt_scene_render_tiles_device.restype = C.c_int
-    lib.rt_scene_render_tiles.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.POINTER(vp), C.c_size_t,
-                                          C.POINTER(vp), C.POINTER(TileStats)]
-    lib.rt_scene_render_tiles.restype = C.c_int
-    lib.rt_scene_render_tile_pass.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.c_uint32, f32p, u8p, C.c_size_t, f32p,
-                                              C.POINTER(TileStats)]
-    lib.rt_scene_render_tile_pass.restype = C.c_int
-    lib.rt_scene_render_tiles_pass_device.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp),
-                                                      C.POINTER(vp), C.c_size_t, C.POINTER(vp), vp]
-    lib.rt_scene_render_tiles_pass_device.restype = C.c_int
-    lib.rt_scene_collect.argtypes = [vp, C.POINTER(TileStats)]
-    lib.rt_scene_collect.restype = C.c_int
-    lib.rt_scene_intersect.argtypes = [vp, C.POINTER(Ray), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Hit), C.POINTER(TileStats)]
-    lib.rt_scene_intersect.restype = C.c_int
-    lib.rt_scene_intersect_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
-    lib.rt_scene_intersect_device.restype = C.c_int
-    lib.rt_scene_trace.argtypes = [vp, C.POINTER(TraceRequest), C.POINTER(Ray), C.c_uint32, C.POINTER(C.c_uint64),
-                                   C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(TileStats)]
-    lib.rt_scene_trace.restype = C.c_int
-    lib.rt_scene_trace_device.argtypes = [vp, C.POINTER(TraceRequest), vp, C.c_uint32, vp, vp, vp, vp]
-    lib.rt_scene_trace_device.restype = C.c_int
-    lib.rt_scene_bounce.argtypes = [vp, C.POINTER(BounceRequest), C.POINTER(Ray), C.c_uint32, C.POINTER(C.c_uint64),
-                                    C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Bounce), C.POINTER(Hit), C.POINTER(C.c_uint32),
-                                    C.POINTER(C.c_uint32), C.POINTER(TileStats)]
-    lib.rt_scene_bounce.restype = C.c_int
-    lib.rt_scene_bounce_device.argtypes = [vp, C.POINTER(BounceRequest), vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.rt_scene_bounce_device.restype = C.c_int
-    lib.rt_scene_light_count.argtypes = [vp, C.POINTER(C.c_uint32)]
-    lib.rt_scene_light_count.restype = C.c_int
-    lib.rt_scene_light_table.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_uint32]
-    lib.rt_scene_light_table.restype = C.c_int
-    lib.rt_scene_set_light_sampling.argtypes = [vp, C.c_uint32]
-    lib.rt_scene_set_light_sampling.restype = C.c_int
-    lib.rt_scene_light_sampling.argtypes = [vp, C.POINTER(C.c_uint32)]
-    lib.rt_scene_light_sampling.restype = C.c_int
-    lib.rt_scene_set_glossy_sampling.argtypes = [vp, C.c_uint32]
-    lib.rt_scene_set_glossy_sampling.restype = C.c_int
-    lib.rt_scene_glossy_sampling.argtypes = [vp, C.POINTER(C.c_uint32)]
-    lib.rt_scene_glossy_sampling.restype = C.c_int
-    lib.rt_scene_direct.argtypes = [vp, C.POINTER(DirectRequest), C.POINTER(Hit), C.c_uint32, C.POINTER(C.c_uint64),
-                                    C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Direct), C.POINTER(TileStats)]
-    lib.rt_scene_direct.restype = C.c_int
-    lib.rt_scene_direct_device.argtypes = [vp, C.POINTER(DirectRequest), vp, C.c_uint32, vp, vp, vp, vp, vp]
-    lib.rt_scene_direct_device.restype = C.c_int
-    lib.rt_scene_trace_nee.argtypes = [vp, C.POINTER(NeeRequest), C.POINTER(Ray), C.c_uint32, C.POINTER(C.c_uint64),
-                                       C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(TileStats)]
-    lib.rt_scene_trace_nee.restype = C.c_int
-    lib.rt_scene_trace_nee_device.argtypes = [vp, C.POINTER(NeeRequest), vp, C.c_uint32, vp, vp, vp, vp, vp]
-    lib.rt_scene_trace_nee_device.restype = C.c_int
-    lib.rt_scene_render_aov.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.c_uint32, C.POINTER(AovPlanes),
-                                        C.POINTER(TileStats)]
-    lib.rt_scene_render_aov.restype = C.c_int
-    lib.rt_scene_render_aovs_device.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.c_uint32, C.c_uint32,
-                                                C.POINTER(AovPlanes), vp]
-    lib.rt_scene_render_aovs_device.restype = C.c_int
-    lib.rt_denoise_request_defaults.argtypes = [C.POINTER(DenoiseRequest)]
-    lib.rt_denoise_request_defaults.restype = None
-    lib.rt_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
-    lib.rt_denoise_scratch_bytes.restype = C.c_size_t
-    lib.rt_scene_denoise.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.POINTER(DenoiseRequest), C.POINTER(vp),
-                                     C.POINTER(AovPlanes), C.POINTER(vp), C.c_size_t, C.POINTER(vp), C.POINTER(vp),
-                                     C.POINTER(TileStats)]
-    lib.rt_scene_denoise.restype = C.c_int
-    lib.rt_scene_denoise_device.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.POINTER(DenoiseRequest), C.POINTER(vp),
-                                            C.POINTER(AovPlanes), C.POINTER(vp), C.c_size_t, C.POINTER(vp), C.POINTER(vp), vp,
-                                            C.c_size_t, vp]
-    lib.rt_scene_denoise_device.restype = C.c_int
-    lib.rt_camera_defaults.argtypes = [C.POINTER(Camera)]
-    lib.rt_camera_defaults.restype = None
-    lib.rt_scene_set_camera.argtypes = [vp, C.POINTER(Camera)]
-    lib.rt_scene_set_camera.restype = C.c_int
-    lib.rt_scene_camera_rays.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.c_uint32, C.POINTER(Ray), C.POINTER(C.c_uint64),
-                                         C.POINTER(TileStats)]
-    lib.rt_scene_camera_rays.restype = C.c_int
-    lib.rt_scene_camera_rays_device.argtypes = [vp, C.POINTER(TileRequest), C.c_uint32, C.c_uint32, vp, vp, vp]
-    lib.rt_scene_camera_rays_device.restype = C.c_int
-    lib.rt_frame_ctx_set_camera.argtypes = [vp, C.POINTER(Camera)]
-    lib.rt_frame_ctx_set_camera.restype = C.c_int
-    lib.rt_render_frame.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(TileRequest), vp, C.c_uint32,
-                                    vp, C.c_uint32, vp, vp, C.c_size_t, C.POINTER(TileStats)]
-    lib.rt_render_frame.restype = C.c_int
-    lib.rt_frame_ctx_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
-    lib.rt_frame_ctx_create.restype = C.c_int
-    lib.rt_frame_ctx_set_world.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp]
-    lib.rt_frame_ctx_set_world.restype = C.c_int
-    lib.rt_frame_ctx_render.argtypes = [vp, C.POINTER(TileRequest), vp, C.c_size_t, C.POINTER(FrameStats)]
-    lib.rt_frame_ctx_render.restype = C.c_int
-    lib.rt_frame_ctx_release_buffer.argtypes = [vp]
-    lib.rt_frame_ctx_release_buffer.restype = C.c_int
-    lib.rt_frame_ctx_destroy.argtypes = [vp]
-    lib.rt_frame_ctx_destroy.restype = None
+    _apply(lib, SIGNATURES)
     return lib
 
 
@@ -467,11 +439,8 @@ def hip_runtime_path() -> str:
     """The libamdhip64 file the library's HIP calls are bound to (rt_hip_runtime_path).  PyTorch wheels bundle their own
     runtime; whichever of torch / this library is loaded FIRST decides which one this library uses
     (profiles/README.md, "two HIP runtimes in one process")."""
-    lib = load()
-    lib.rt_hip_runtime_path.argtypes = [C.c_char_p, C.c_size_t]
-    lib.rt_hip_runtime_path.restype = C.c_size_t
     buf = C.create_string_buffer(4096)
-    return buf.value.decode() if lib.rt_hip_runtime_path(buf, 4096) else ""
+    return buf.value.decode() if load().rt_hip_runtime_path(buf, 4096) else ""
 
 
 def hip_runtime() -> C.CDLL:

@@ -65,7 +65,7 @@ FLAGS_PATH = LIB_PATH.with_suffix(".flags")      # the exact compile lines of th
 # The TEST library: the product sources plus -DRT_DEBUG_HOOKS, which compiles the rt_debug_* entry points (launch-path knobs,
 # counter read-back, a throwing body, the sqrt self-test, the unit kernels of rt_unit.hip.h and rt_unit_sampling.hip.h) that tests
 # and tools use.
-# The product library exports exactly include/rt_tile.h (tests/test_abi.py checks both).
+# The product library exports exactly include/rt_tile.h (tests/test_surface.py checks both).
 DEBUG_VARIANT = "dbg"
 DEBUG_FLAGS = ["-DRT_DEBUG_HOOKS"]
 DEBUG_LIB_PATH = LIB_DIR / f"librt_s8_{DEBUG_VARIANT}.so"

@@ -111,6 +111,102 @@ def init() -> int:
     return n.value
 
 
+# ---- marshalling, each step once: what the methods below hand to the entry points of _abi.SIGNATURES
+
+def _addr(p: int):
+    """An integer address (a device buffer, a HIP stream) as a pointer argument; 0 is NULL."""
+    return C.c_void_p(p) if p else None
+
+
+def _addr_array(addrs: Optional[Sequence[int]]):
+    """One pointer per strip: the `void* const*` argument of a batch (None: NULL, the optional output is not wanted)."""
+    return None if addrs is None else (C.c_void_p * len(addrs))(*[p or None for p in addrs])
+
+
+_POINTEE = {np.dtype(np.uint8): C.c_uint8, np.dtype(np.uint32): C.c_uint32, np.dtype(np.uint64): C.c_uint64,
+            np.dtype(np.float32): C.c_float, _abi.RAY_DTYPE: _abi.Ray, _abi.HIT_DTYPE: _abi.Hit, _abi.BOUNCE_DTYPE: _abi.Bounce,
+            _abi.DIRECT_DTYPE: _abi.Direct}
+
+
+def _arg(a: Optional[np.ndarray]):
+    """A numpy array as a pointer argument: a pointer to the C type of its dtype, which the typed parameters require and the
+    `void*` ones accept (it keeps the array alive); None is NULL."""
+    return None if a is None else a.ctypes.data_as(C.POINTER(_POINTEE[a.dtype]))
+
+
+def _requests(reqs: Sequence[TileRequest]):
+    """The rt_tile_request array of a batch.  Marshalled afresh on every call (a few dozen structs): a cache keyed on id(reqs)
+    served stale requests to a caller that changed seed or division_no in place."""
+    return (TileRequest * len(reqs))(*reqs)
+
+
+def _strip_shape(req: TileRequest):
+    """(Hs, W) of the request's strip (a bad request is refused by the library)."""
+    return req.height // max(req.divisions, 1), req.width
+
+
+def _states(rng_state, n: int):
+    """The optional (N, 4) uint64 xoshiro256++ states of n rays: None, or a C-ordered copy for the call to advance."""
+    if rng_state is None:
+        return None
+    state = np.array(rng_state, np.uint64, order="C")
+    if state.shape != (n, 4):
+        raise ValueError(f"rng_state: need an (N, 4) uint64 array, got {state.shape}")
+    return state
+
+
+def _states_or_seeded(rng_state, n: int, seed: Optional[int]):
+    """The required form: the copy of _states, or zeroed states for the library to seed when a seed stands in for them."""
+    if rng_state is None and seed is None:
+        raise ValueError("rng_state: need (N, 4) uint64 states, or a seed to make them from")
+    return np.zeros((n, 4), np.uint64) if rng_state is None else _states(rng_state, n)
+
+
+def _active(active):
+    """(active, n_active) arguments of an active list: (NULL, 0) for None, all rays.  An empty list is still a list: the library gets
+    a non-NULL pointer to an array of one."""
+    if active is None:
+        return None, 0
+    act = np.ascontiguousarray(active, np.uint32).reshape(-1)
+    return _arg(act if len(act) else np.zeros(1, np.uint32)), len(act)
+
+
+def _aov_planes(strips: Sequence[dict]):
+    """The rt_aov_planes array of a batch from one {plane name: address} dict per strip; a plane that is missing or 0 is NULL."""
+    return (_abi.AovPlanes * len(strips))(*[_abi.AovPlanes(*[d.get(k) or None for k in _abi.AOV_PLANES]) for d in strips])
+
+
+def _devices(devices: Optional[Sequence[int]]):
+    """(devices, n_devices) arguments: the ordinals as a C int array, or (NULL, 0) for every device."""
+    return (None, 0) if devices is None else ((C.c_int * len(devices))(*devices), len(devices))
+
+
+def _world_args(world: "World"):
+    """spheres, n_spheres, triangles, n_triangles, world_index of a World, in the order every entry point takes them."""
+    return (_abi.ptr(world.spheres), len(world.spheres), _abi.ptr(world.triangles), len(world.triangles),
+            _abi.ptr(world.world_index))
+
+
+def _ray_form(as_given: bool) -> int:
+    return _abi.RT_TRACE_RAY_AS_GIVEN if as_given else _abi.RT_TRACE_RAY_NEW
+
+
+def _trace_request(spp, max_bounces, seed, flags, as_given) -> _abi.TraceRequest:
+    return _abi.TraceRequest(spp, max_bounces, seed & 0xFFFFFFFFFFFFFFFF, flags, _ray_form(as_given))
+
+
+def _bounce_request(flags, as_given, seed) -> _abi.BounceRequest:
+    return _abi.BounceRequest(flags, _ray_form(as_given), 0 if seed is None else 1, 0, (seed or 0) & 0xFFFFFFFFFFFFFFFF)
+
+
+def _direct_request(flags, t_min, t_max) -> _abi.DirectRequest:
+    return _abi.DirectRequest(flags, 0, t_min, t_max)
+
+
+def _nee_request(spp, max_bounces, seed, flags, as_given, mode) -> _abi.NeeRequest:
+    return _abi.NeeRequest(spp, max_bounces, seed & 0xFFFFFFFFFFFFFFFF, flags, _ray_form(as_given), mode, 0)
+
+
 def _pack_rays(origins, directions, t_min, t_max) -> np.ndarray:
     """The rt_ray array (RAY_DTYPE) of origins / directions (N, 3) and t_min / t_max (scalars or (N,))."""
     o = np.asarray(origins, np.float32)
@@ -136,10 +232,7 @@ class Scene:
         self.world = world
         self.device = device
         h = C.c_void_p()
-        _abi.check(self._lib.rt_scene_create(device, _abi.ptr(world.spheres), len(world.spheres),
-                                             _abi.ptr(world.triangles), len(world.triangles),
-                                             _abi.ptr(world.world_index), C.byref(h)),
-                   "rt_scene_create")
+        _abi.check(self._lib.rt_scene_create(device, *_world_args(world), C.byref(h)), "rt_scene_create")
         self._h = h
 
     def close(self):
@@ -160,9 +253,8 @@ class Scene:
         out = np.empty(n, np.uint8)
         outf = np.empty(n, np.float32) if want_f32 else None
         st = TileStats()
-        _abi.check(self._lib.rt_scene_render_tile(self._h, C.byref(req), out.ctypes.data_as(C.c_void_p), n,
-                                                  outf.ctypes.data_as(C.c_void_p) if want_f32 else None,
-                                                  C.byref(st)), "rt_scene_render_tile")
+        _abi.check(self._lib.rt_scene_render_tile(self._h, C.byref(req), _arg(out), n, _arg(outf), C.byref(st)),
+                   "rt_scene_render_tile")
         return out, outf, st
 
     def render_tile_pass(self, req: TileRequest, begin: int, end: int, accum: Optional[np.ndarray] = None,
@@ -172,7 +264,7 @@ class Scene:
         allocates it.  Returns (rgb, f32 | None, accum, stats): the preview sqrt(sum / end), which at end == req.spp is
         bit-identical to render_tile(req) however the samples were split into passes."""
         n = self._lib.rt_tile_bytes(C.byref(req))
-        shape = (req.height // max(req.divisions, 1), req.width, 3)      # (a bad request is refused by the library)
+        shape = (*_strip_shape(req), 3)
         if accum is None:
             if begin != 0:
                 raise ValueError("accum: a pass that starts after sample 0 continues a running sum: pass the one of the last pass")
@@ -181,12 +273,9 @@ class Scene:
             raise ValueError(f"accum: need a writeable contiguous float32 array of shape {shape}")
         out = np.empty(n, np.uint8)
         outf = np.empty(n, np.float32) if want_f32 else None
-        fp = C.POINTER(C.c_float)
         st = TileStats()
-        _abi.check(self._lib.rt_scene_render_tile_pass(self._h, C.byref(req), begin, end, accum.ctypes.data_as(fp),
-                                                       out.ctypes.data_as(C.POINTER(C.c_uint8)), n,
-                                                       outf.ctypes.data_as(fp) if want_f32 else None, C.byref(st)),
-                   "rt_scene_render_tile_pass")
+        _abi.check(self._lib.rt_scene_render_tile_pass(self._h, C.byref(req), begin, end, _arg(accum), _arg(out), n, _arg(outf),
+                                                       C.byref(st)), "rt_scene_render_tile_pass")
         return out, outf, accum, st
 
     def render_progressive(self, req: TileRequest, pass_spp: int):
@@ -203,52 +292,39 @@ class Scene:
             begin = end
 
     def render_tile_device(self, req: TileRequest, d_out_ptr: int, out_len: int, d_f32_ptr: int = 0, stream: int = 0):
-        _abi.check(self._lib.rt_scene_render_tile_device(self._h, C.byref(req), C.c_void_p(d_out_ptr), out_len,
-                                                         C.c_void_p(d_f32_ptr) if d_f32_ptr else None,
-                                                         C.c_void_p(stream) if stream else None),
-                   "rt_scene_render_tile_device")
+        _abi.check(self._lib.rt_scene_render_tile_device(self._h, C.byref(req), _addr(d_out_ptr), out_len, _addr(d_f32_ptr),
+                                                         _addr(stream)), "rt_scene_render_tile_device")
 
     def render_tiles(self, reqs: Sequence[TileRequest], want_f32: bool = False, out=None):
         """Batched: strips of one frame, host buffers out (rt_scene_render_tiles).  `out`: a list of uint8 arrays
         from an earlier call to write into again (a caller that renders frame after frame keeps its pages warm)."""
         n = len(reqs)
         nb = self._lib.rt_tile_bytes(C.byref(reqs[0]))
-        arr = (TileRequest * n)(*reqs)
         if out is not None:
             if len(out) != n or any(o.dtype != np.uint8 or o.size < nb or not o.flags.c_contiguous for o in out):
                 raise ValueError("out: need one contiguous uint8 array of at least rt_tile_bytes per request")
         outs = out if out is not None else [np.empty(nb, np.uint8) for _ in range(n)]
         outf = [np.empty(nb, np.float32) for _ in range(n)] if want_f32 else None
-        po = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-        pf = (C.c_void_p * n)(*[o.ctypes.data for o in outf]) if want_f32 else None
         st = TileStats()
-        _abi.check(self._lib.rt_scene_render_tiles(self._h, arr, n, po, nb, pf, C.byref(st)), "rt_scene_render_tiles")
+        _abi.check(self._lib.rt_scene_render_tiles(self._h, _requests(reqs), n, _addr_array([o.ctypes.data for o in outs]), nb,
+                                                   _addr_array([o.ctypes.data for o in outf]) if want_f32 else None, C.byref(st)),
+                   "rt_scene_render_tiles")
         return outs, outf, st
 
     def render_tiles_device(self, reqs: Sequence[TileRequest], d_out_ptrs: Sequence[int], out_len_each: int,
                             stream: int = 0):
         """Batched, asynchronous, device-resident output (rt_scene_render_tiles_device)."""
-        n = len(reqs)
-        # marshalled afresh on every call (a few dozen structs): a cache keyed on id(reqs) served stale requests to a
-        # caller that changed seed or division_no in place
-        arr = (TileRequest * n)(*reqs)
-        po = (C.c_void_p * n)(*d_out_ptrs)
-        _abi.check(self._lib.rt_scene_render_tiles_device(self._h, arr, n, po, out_len_each, None,
-                                                          C.c_void_p(stream) if stream else None),
-                   "rt_scene_render_tiles_device")
+        _abi.check(self._lib.rt_scene_render_tiles_device(self._h, _requests(reqs), len(reqs), _addr_array(d_out_ptrs), out_len_each,
+                                                          None, _addr(stream)), "rt_scene_render_tiles_device")
 
     def render_tiles_pass_device(self, reqs: Sequence[TileRequest], begin: int, end: int, d_accum_ptrs: Sequence[int],
                                  d_out_ptrs: Sequence[int], out_len_each: int, d_f32_ptrs: Optional[Sequence[int]] = None,
                                  stream: int = 0):
         """Batched progressive pass, asynchronous, device buffers (rt_scene_render_tiles_pass_device): samples [begin, end) of
         every strip, d_accum_ptrs[i] the running sum of strip i (Hs*W*3 floats on the device)."""
-        n = len(reqs)
-        arr = (TileRequest * n)(*reqs)
-        pa = (C.c_void_p * n)(*d_accum_ptrs)
-        po = (C.c_void_p * n)(*d_out_ptrs)
-        pf = (C.c_void_p * n)(*d_f32_ptrs) if d_f32_ptrs is not None else None
-        _abi.check(self._lib.rt_scene_render_tiles_pass_device(self._h, arr, n, begin, end, pa, po, out_len_each, pf,
-                                                               C.c_void_p(stream) if stream else None),
+        _abi.check(self._lib.rt_scene_render_tiles_pass_device(self._h, _requests(reqs), len(reqs), begin, end,
+                                                               _addr_array(d_accum_ptrs), _addr_array(d_out_ptrs), out_len_each,
+                                                               _addr_array(d_f32_ptrs), _addr(stream)),
                    "rt_scene_render_tiles_pass_device")
 
     def intersect(self, origins, directions, t_min=0.001, t_max=1000.0, *, any_hit: bool = False, flags: int = 0):
@@ -260,18 +336,16 @@ class Scene:
         n = len(rays)
         hits = np.empty(n, _abi.HIT_DTYPE)
         st = TileStats()
-        _abi.check(self._lib.rt_scene_intersect(self._h, rays.ctypes.data_as(C.POINTER(_abi.Ray)), n,
-                                                _abi.RT_QUERY_ANY if any_hit else _abi.RT_QUERY_CLOSEST, flags,
-                                                hits.ctypes.data_as(C.POINTER(_abi.Hit)), C.byref(st)), "rt_scene_intersect")
+        _abi.check(self._lib.rt_scene_intersect(self._h, _arg(rays), n, _abi.RT_QUERY_ANY if any_hit else _abi.RT_QUERY_CLOSEST, flags,
+                                                _arg(hits), C.byref(st)), "rt_scene_intersect")
         return hits, st
 
     def intersect_device(self, d_rays: int, n: int, d_hits: int, *, any_hit: bool = False, flags: int = 0, stream: int = 0):
         """Ray queries on device buffers (rt_scene_intersect_device): n rt_ray at d_rays, n rt_hit to d_hits (e.g. the
         data_ptr() of torch tensors), asynchronous on `stream`; counters until collect()."""
-        _abi.check(self._lib.rt_scene_intersect_device(self._h, C.c_void_p(d_rays), n,
+        _abi.check(self._lib.rt_scene_intersect_device(self._h, _addr(d_rays), n,
                                                        _abi.RT_QUERY_ANY if any_hit else _abi.RT_QUERY_CLOSEST, flags,
-                                                       C.c_void_p(d_hits), C.c_void_p(stream) if stream else None),
-                   "rt_scene_intersect_device")
+                                                       _addr(d_hits), _addr(stream)), "rt_scene_intersect_device")
 
     def trace(self, origins, directions, t_min=0.001, t_max=1000.0, *, spp: int = 1, max_bounces: int = 10, seed: int = 0,
               rng_state=None, as_given: bool = False, flags: int = 0):
@@ -282,20 +356,13 @@ class Scene:
         Returns (rgb_sum (N, 3) float32, segments (N,) uint32, stats), and the written-back states (N, 4) when rng_state is given."""
         rays = _pack_rays(origins, directions, t_min, t_max)
         n = len(rays)
-        state = None
-        if rng_state is not None:
-            state = np.array(rng_state, np.uint64, order="C")
-            if state.shape != (n, 4):
-                raise ValueError(f"rng_state: need an (N, 4) uint64 array, got {state.shape}")
-        rq = _abi.TraceRequest(spp, max_bounces, seed & 0xFFFFFFFFFFFFFFFF, flags,
-                               _abi.RT_TRACE_RAY_AS_GIVEN if as_given else _abi.RT_TRACE_RAY_NEW)
+        state = _states(rng_state, n)
+        rq = _trace_request(spp, max_bounces, seed, flags, as_given)
         rgb = np.empty((n, 3), np.float32)
         segs = np.empty(n, np.uint32)
         st = TileStats()
-        _abi.check(self._lib.rt_scene_trace(self._h, C.byref(rq), rays.ctypes.data_as(C.POINTER(_abi.Ray)), n,
-                                            state.ctypes.data_as(C.POINTER(C.c_uint64)) if state is not None else None,
-                                            rgb.ctypes.data_as(C.POINTER(C.c_float)), segs.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                            C.byref(st)), "rt_scene_trace")
+        _abi.check(self._lib.rt_scene_trace(self._h, C.byref(rq), _arg(rays), n, _arg(state), _arg(rgb), _arg(segs), C.byref(st)),
+                   "rt_scene_trace")
         if state is not None:
             return rgb, segs, st, state
         return rgb, segs, st
@@ -305,11 +372,9 @@ class Scene:
         """Path tracing on device buffers (rt_scene_trace_device): n rt_ray at d_rays, 3 n float32 sums to d_rgb, optionally
         n uint32 segments to d_segments and 4 n uint64 states at d_rng_state (read and written back) — e.g. the data_ptr() of
         torch tensors; asynchronous on `stream`, counters until collect()."""
-        rq = _abi.TraceRequest(spp, max_bounces, seed & 0xFFFFFFFFFFFFFFFF, flags,
-                               _abi.RT_TRACE_RAY_AS_GIVEN if as_given else _abi.RT_TRACE_RAY_NEW)
-        vp = lambda ptr: C.c_void_p(ptr) if ptr else None
-        _abi.check(self._lib.rt_scene_trace_device(self._h, C.byref(rq), vp(d_rays), n, vp(d_rng_state), vp(d_rgb), vp(d_segments),
-                                                   vp(stream)), "rt_scene_trace_device")
+        rq = _trace_request(spp, max_bounces, seed, flags, as_given)
+        _abi.check(self._lib.rt_scene_trace_device(self._h, C.byref(rq), _addr(d_rays), n, _addr(d_rng_state), _addr(d_rgb),
+                                                   _addr(d_segments), _addr(stream)), "rt_scene_trace_device")
 
     def bounce(self, rays, rng_state, active=None, as_given: bool = False, flags: int = 0, seed: Optional[int] = None,
                want_hits: bool = False, want_next: bool = False):
@@ -325,31 +390,15 @@ class Scene:
         if r.ndim != 1:
             raise ValueError(f"rays: need a 1-d array of RAY_DTYPE records, got shape {r.shape}")
         n = len(r)
-        if rng_state is None:
-            if seed is None:
-                raise ValueError("rng_state: need (N, 4) uint64 states, or a seed to make them from")
-            state = np.zeros((n, 4), np.uint64)
-        else:
-            state = np.array(rng_state, np.uint64, order="C")
-        if state.shape != (n, 4):
-            raise ValueError(f"rng_state: need an (N, 4) uint64 array, got {state.shape}")
-        act = None if active is None else np.ascontiguousarray(active, np.uint32).reshape(-1)
-        rq = _abi.BounceRequest(flags, _abi.RT_TRACE_RAY_AS_GIVEN if as_given else _abi.RT_TRACE_RAY_NEW,
-                                0 if seed is None else 1, 0, (seed or 0) & 0xFFFFFFFFFFFFFFFF)
+        state = _states_or_seeded(rng_state, n, seed)
+        rq = _bounce_request(flags, as_given, seed)
         bnc = np.zeros(n, _abi.BOUNCE_DTYPE)
         hits = np.zeros(n, _abi.HIT_DTYPE) if want_hits else None
         nxt = np.zeros(n, np.uint32) if want_next else None
         n_next = C.c_uint32(0)
-        u32p = C.POINTER(C.c_uint32)
         st = TileStats()
-        # (an empty list is still a list: ctypes gets a non-NULL pointer to an array of one)
-        act_arg = None if act is None else (act if len(act) else np.zeros(1, np.uint32)).ctypes.data_as(u32p)
-        _abi.check(self._lib.rt_scene_bounce(self._h, C.byref(rq), r.ctypes.data_as(C.POINTER(_abi.Ray)), n,
-                                             state.ctypes.data_as(C.POINTER(C.c_uint64)), act_arg, 0 if act is None else len(act),
-                                             bnc.ctypes.data_as(C.POINTER(_abi.Bounce)),
-                                             hits.ctypes.data_as(C.POINTER(_abi.Hit)) if want_hits else None,
-                                             nxt.ctypes.data_as(u32p) if want_next else None,
-                                             C.byref(n_next) if want_next else None, C.byref(st)), "rt_scene_bounce")
+        _abi.check(self._lib.rt_scene_bounce(self._h, C.byref(rq), _arg(r), n, _arg(state), *_active(active), _arg(bnc), _arg(hits),
+                                             _arg(nxt), C.byref(n_next) if want_next else None, C.byref(st)), "rt_scene_bounce")
         out = {"rays": r, "states": state, "bounce": bnc, "stats": st}
         if want_hits:
             out["hits"] = hits
@@ -364,12 +413,10 @@ class Scene:
         updated in place; n rt_bounce to d_bounce; optionally n rt_hit to d_hits, the active list d_active with its uint32 length
         at d_n_active (read on the device), and the list of the rays that scattered to d_next_active with its length to d_n_next —
         e.g. the data_ptr() of torch tensors; asynchronous on `stream`, counters until collect()."""
-        rq = _abi.BounceRequest(flags, _abi.RT_TRACE_RAY_AS_GIVEN if as_given else _abi.RT_TRACE_RAY_NEW,
-                                0 if seed is None else 1, 0, (seed or 0) & 0xFFFFFFFFFFFFFFFF)
-        vp = lambda ptr: C.c_void_p(ptr) if ptr else None
-        _abi.check(self._lib.rt_scene_bounce_device(self._h, C.byref(rq), vp(d_rays), n, vp(d_rng_state), vp(d_active), vp(d_n_active),
-                                                    vp(d_bounce), vp(d_hits), vp(d_next_active), vp(d_n_next), vp(stream)),
-                   "rt_scene_bounce_device")
+        rq = _bounce_request(flags, as_given, seed)
+        _abi.check(self._lib.rt_scene_bounce_device(self._h, C.byref(rq), _addr(d_rays), n, _addr(d_rng_state), _addr(d_active),
+                                                    _addr(d_n_active), _addr(d_bounce), _addr(d_hits), _addr(d_next_active),
+                                                    _addr(d_n_next), _addr(stream)), "rt_scene_bounce_device")
 
     @property
     def n_lights(self) -> int:
@@ -384,8 +431,7 @@ class Scene:
         the mixture of the light table with RT_FLAG_LIGHTS_BY_POWER, 1 / M without.  Host only."""
         m = self.n_lights
         wi, p = np.zeros(m, np.uint32), np.zeros(m, np.float32)
-        _abi.check(self._lib.rt_scene_light_table(self._h, flags, wi.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                  p.ctypes.data_as(C.POINTER(C.c_float)), m), "rt_scene_light_table")
+        _abi.check(self._lib.rt_scene_light_table(self._h, flags, _arg(wi), _arg(p), m), "rt_scene_light_table")
         return wi, p
 
     def set_light_sampling(self, sampling: int):
@@ -427,18 +473,12 @@ class Scene:
         n = len(h)
         if rng_state is None:
             raise ValueError("rng_state: need (N, 4) uint64 states")
-        state = np.array(rng_state, np.uint64, order="C")
-        if state.shape != (n, 4):
-            raise ValueError(f"rng_state: need an (N, 4) uint64 array, got {state.shape}")
-        act = None if active is None else np.ascontiguousarray(active, np.uint32).reshape(-1)
-        rq = _abi.DirectRequest(flags, 0, t_min, t_max)
+        state = _states(rng_state, n)
+        rq = _direct_request(flags, t_min, t_max)
         out = np.zeros(n, _abi.DIRECT_DTYPE)
         st = TileStats()
-        # (an empty list is still a list: ctypes gets a non-NULL pointer to an array of one)
-        act_arg = None if act is None else (act if len(act) else np.zeros(1, np.uint32)).ctypes.data_as(C.POINTER(C.c_uint32))
-        _abi.check(self._lib.rt_scene_direct(self._h, C.byref(rq), h.ctypes.data_as(C.POINTER(_abi.Hit)), n,
-                                             state.ctypes.data_as(C.POINTER(C.c_uint64)), act_arg, 0 if act is None else len(act),
-                                             out.ctypes.data_as(C.POINTER(_abi.Direct)), C.byref(st)), "rt_scene_direct")
+        _abi.check(self._lib.rt_scene_direct(self._h, C.byref(rq), _arg(h), n, _arg(state), *_active(active), _arg(out), C.byref(st)),
+                   "rt_scene_direct")
         return {"direct": out, "states": state, "stats": st}
 
     def direct_device(self, d_hits: int, n: int, d_rng_state: int, d_out: int, *, d_active: int = 0, d_n_active: int = 0,
@@ -446,10 +486,9 @@ class Scene:
         """Direct lighting on device buffers (rt_scene_direct_device): n rt_hit at d_hits, 4 n uint64 states at d_rng_state (updated in
         place), n rt_direct to d_out; optionally the active list d_active with its uint32 length at d_n_active (read on the device:
         the d_next_active / d_n_next of a bounce step as they stand); asynchronous on `stream`, counters until collect()."""
-        rq = _abi.DirectRequest(flags, 0, t_min, t_max)
-        vp = lambda ptr: C.c_void_p(ptr) if ptr else None
-        _abi.check(self._lib.rt_scene_direct_device(self._h, C.byref(rq), vp(d_hits), n, vp(d_rng_state), vp(d_active), vp(d_n_active),
-                                                    vp(d_out), vp(stream)), "rt_scene_direct_device")
+        rq = _direct_request(flags, t_min, t_max)
+        _abi.check(self._lib.rt_scene_direct_device(self._h, C.byref(rq), _addr(d_hits), n, _addr(d_rng_state), _addr(d_active),
+                                                    _addr(d_n_active), _addr(d_out), _addr(stream)), "rt_scene_direct_device")
 
     def trace_nee(self, origins, directions, t_min=0.001, t_max=1000.0, *, spp: int = 1, max_bounces: int = 10, seed: int = 0,
                   rng_state=None, as_given: bool = False, mode: int = _abi.RT_NEE_MIS, flags: int = 0):
@@ -461,21 +500,13 @@ class Scene:
         rng_state is given."""
         rays = _pack_rays(origins, directions, t_min, t_max)
         n = len(rays)
-        state = None
-        if rng_state is not None:
-            state = np.array(rng_state, np.uint64, order="C")
-            if state.shape != (n, 4):
-                raise ValueError(f"rng_state: need an (N, 4) uint64 array, got {state.shape}")
-        rq = _abi.NeeRequest(spp, max_bounces, seed & 0xFFFFFFFFFFFFFFFF, flags,
-                             _abi.RT_TRACE_RAY_AS_GIVEN if as_given else _abi.RT_TRACE_RAY_NEW, mode, 0)
+        state = _states(rng_state, n)
+        rq = _nee_request(spp, max_bounces, seed, flags, as_given, mode)
         rgb = np.empty((n, 3), np.float32)
         segs, shadow = np.empty(n, np.uint32), np.empty(n, np.uint32)
-        u32p = C.POINTER(C.c_uint32)
         st = TileStats()
-        _abi.check(self._lib.rt_scene_trace_nee(self._h, C.byref(rq), rays.ctypes.data_as(C.POINTER(_abi.Ray)), n,
-                                                state.ctypes.data_as(C.POINTER(C.c_uint64)) if state is not None else None,
-                                                rgb.ctypes.data_as(C.POINTER(C.c_float)), segs.ctypes.data_as(u32p),
-                                                shadow.ctypes.data_as(u32p), C.byref(st)), "rt_scene_trace_nee")
+        _abi.check(self._lib.rt_scene_trace_nee(self._h, C.byref(rq), _arg(rays), n, _arg(state), _arg(rgb), _arg(segs), _arg(shadow),
+                                                C.byref(st)), "rt_scene_trace_nee")
         if state is not None:
             return rgb, segs, shadow, st, state
         return rgb, segs, shadow, st
@@ -486,11 +517,10 @@ class Scene:
         """Next-event estimation on device buffers (rt_scene_trace_nee_device): n rt_ray at d_rays, 3 n float32 sums to d_rgb,
         optionally n uint32 path segments to d_segments, n uint32 shadow rays to d_shadow and 4 n uint64 states at d_rng_state (read
         and written back) — e.g. the data_ptr() of torch tensors; asynchronous on `stream`, counters until collect()."""
-        rq = _abi.NeeRequest(spp, max_bounces, seed & 0xFFFFFFFFFFFFFFFF, flags,
-                             _abi.RT_TRACE_RAY_AS_GIVEN if as_given else _abi.RT_TRACE_RAY_NEW, mode, 0)
-        vp = lambda ptr: C.c_void_p(ptr) if ptr else None
-        _abi.check(self._lib.rt_scene_trace_nee_device(self._h, C.byref(rq), vp(d_rays), n, vp(d_rng_state), vp(d_rgb), vp(d_segments),
-                                                       vp(d_shadow), vp(stream)), "rt_scene_trace_nee_device")
+        rq = _nee_request(spp, max_bounces, seed, flags, as_given, mode)
+        _abi.check(self._lib.rt_scene_trace_nee_device(self._h, C.byref(rq), _addr(d_rays), n, _addr(d_rng_state), _addr(d_rgb),
+                                                       _addr(d_segments), _addr(d_shadow), _addr(stream)),
+                   "rt_scene_trace_nee_device")
 
     def render_aov(self, req: TileRequest, begin: int = 0, end: Optional[int] = None, *,
                    planes: Sequence[str] = _abi.AOV_PLANES, out: Optional[dict] = None):
@@ -505,9 +535,9 @@ class Scene:
         bad = [n for n in names if n not in _abi.AOV_PLANES]
         if bad or not names:
             raise ValueError(f"planes: a non-empty subset of {_abi.AOV_PLANES}, got {names}")
-        hs = req.height // max(req.divisions, 1)                          # (a bad request is refused by the library)
-        shapes = {"albedo": ((hs, req.width, 3), np.float32), "normal": ((hs, req.width, 3), np.float32),
-                  "depth": ((hs, req.width), np.float32), "hits": ((hs, req.width), np.uint32), "index": ((hs, req.width), np.uint32)}
+        hs, w = _strip_shape(req)
+        shapes = {"albedo": ((hs, w, 3), np.float32), "normal": ((hs, w, 3), np.float32),
+                  "depth": ((hs, w), np.float32), "hits": ((hs, w), np.uint32), "index": ((hs, w), np.uint32)}
         if out is None:
             if begin != 0:
                 raise ValueError("out: a call that starts after sample 0 continues the sums: pass the planes of the last call")
@@ -517,10 +547,9 @@ class Scene:
             shape, dt = shapes[n]
             if a is None or a.dtype != dt or a.shape != shape or not a.flags.c_contiguous or not a.flags.writeable:
                 raise ValueError(f"out[{n!r}]: need a writeable contiguous {np.dtype(dt).name} array of shape {shape}")
-        pl = _abi.AovPlanes(*[out[n].ctypes.data if n in names else None for n in _abi.AOV_PLANES])
+        pl = _aov_planes([{n: out[n].ctypes.data for n in names}])
         st = TileStats()
-        _abi.check(self._lib.rt_scene_render_aov(self._h, C.byref(req), begin, end, C.byref(pl), C.byref(st)),
-                   "rt_scene_render_aov")
+        _abi.check(self._lib.rt_scene_render_aov(self._h, C.byref(req), begin, end, pl, C.byref(st)), "rt_scene_render_aov")
         return {n: out[n] for n in names}, st
 
     def render_aovs_device(self, reqs: Sequence[TileRequest], begin: int, end: int, d_planes: Sequence[dict], stream: int = 0):
@@ -530,9 +559,7 @@ class Scene:
         n = len(reqs)
         if len(d_planes) != n:
             raise ValueError("d_planes: one entry per request")
-        arr = (TileRequest * n)(*reqs)
-        pl = (_abi.AovPlanes * n)(*[_abi.AovPlanes(*[d.get(k) or None for k in _abi.AOV_PLANES]) for d in d_planes])
-        _abi.check(self._lib.rt_scene_render_aovs_device(self._h, arr, n, begin, end, pl, C.c_void_p(stream) if stream else None),
+        _abi.check(self._lib.rt_scene_render_aovs_device(self._h, _requests(reqs), n, begin, end, _aov_planes(d_planes), _addr(stream)),
                    "rt_scene_render_aovs_device")
 
     def denoise(self, reqs, accum, planes, color_samples: int, aov_samples: int = 1, dreq: Optional[DenoiseRequest] = None,
@@ -555,39 +582,27 @@ class Scene:
             raise ValueError(f"outputs: a non-empty subset of {DENOISE_OUTPUTS}, got {outs}")
         dq = DenoiseRequest.defaults() if dreq is None else DenoiseRequest.from_buffer_copy(dreq)
         dq.color_samples, dq.aov_samples = color_samples, aov_samples
-        hs = reqs[0].height // max(reqs[0].divisions, 1)
-        shape = (hs, reqs[0].width, 3)
+        shape = (*_strip_shape(reqs[0]), 3)
         acc = [np.ascontiguousarray(a, np.float32) for a in accum]
         if any(a.shape != shape for a in acc):
             raise ValueError(f"accum: need arrays of shape {shape}")
         want = {"albedo": np.float32, "normal": np.float32, "depth": np.float32, "hits": np.uint32}
-        keep = []
-        pl = (_abi.AovPlanes * n)()
-        for i, d in enumerate(planes):
-            ptrs = []
-            for k in _abi.AOV_PLANES:
-                a = (d or {}).get(k)
-                if a is None or k == "index":
-                    ptrs.append(None)
-                    continue
-                a = np.ascontiguousarray(a, want[k])
-                keep.append(a)
-                ptrs.append(a.ctypes.data)
-            pl[i] = _abi.AovPlanes(*ptrs)
+        # (contiguous copies where needed, kept alive until the call returns)
+        keep = [{k: np.ascontiguousarray(a, want[k]) for k, a in (d or {}).items() if k in want and a is not None} for d in planes]
         res = [{} for _ in range(n)]
         arrays = {}
         for o in DENOISE_OUTPUTS:
             if o in outs:
                 for r in res:
                     r[o] = np.empty(shape, np.uint8 if o == "rgb" else np.float32)
-                arrays[o] = (C.c_void_p * n)(*[r[o].ctypes.data for r in res])
+                arrays[o] = _addr_array([r[o].ctypes.data for r in res])
             else:
                 arrays[o] = None
-        arr = (TileRequest * n)(*reqs)
-        acc_p = (C.c_void_p * n)(*[a.ctypes.data for a in acc])
         st = TileStats()
-        _abi.check(self._lib.rt_scene_denoise(self._h, arr, n, C.byref(dq), acc_p, pl, arrays["rgb"], shape[0] * shape[1] * 3,
-                                              arrays["f32"], arrays["linear"], C.byref(st)), "rt_scene_denoise")
+        _abi.check(self._lib.rt_scene_denoise(self._h, _requests(reqs), n, C.byref(dq), _addr_array([a.ctypes.data for a in acc]),
+                                              _aov_planes([{k: a.ctypes.data for k, a in d.items()} for d in keep]), arrays["rgb"],
+                                              shape[0] * shape[1] * 3, arrays["f32"], arrays["linear"], C.byref(st)),
+                   "rt_scene_denoise")
         return (res[0] if single else res), st
 
     def denoise_device(self, reqs: Sequence[TileRequest], dreq: DenoiseRequest, d_accum: Sequence[int], d_planes: Sequence[dict],
@@ -602,22 +617,15 @@ class Scene:
         n = len(reqs)
         if len(d_accum) != n or len(d_planes) != n:
             raise ValueError("d_accum and d_planes: one entry per request")
-        arr = (TileRequest * n)(*reqs)
-        pl = (_abi.AovPlanes * n)(*[_abi.AovPlanes(*[d.get(k) or None for k in _abi.AOV_PLANES]) for d in d_planes])
-
-        def ptrs(a):
-            if a is None:
-                return None
-            if len(a) != n:
-                raise ValueError("output arrays: one device pointer per request")
-            return (C.c_void_p * n)(*[p or None for p in a])
-
+        if any(a is not None and len(a) != n for a in (d_rgb, d_f32, d_linear)):
+            raise ValueError("output arrays: one device pointer per request")
         if not out_len_each:
-            out_len_each = (reqs[0].height // max(reqs[0].divisions, 1)) * reqs[0].width * 3
-        _abi.check(self._lib.rt_scene_denoise_device(self._h, arr, n, C.byref(dreq), (C.c_void_p * n)(*[p or None for p in d_accum]),
-                                                     pl, ptrs(d_rgb), out_len_each, ptrs(d_f32), ptrs(d_linear),
-                                                     C.c_void_p(d_scratch) if d_scratch else None, scratch_bytes,
-                                                     C.c_void_p(stream) if stream else None), "rt_scene_denoise_device")
+            hs, w = _strip_shape(reqs[0])
+            out_len_each = hs * w * 3
+        _abi.check(self._lib.rt_scene_denoise_device(self._h, _requests(reqs), n, C.byref(dreq), _addr_array(d_accum),
+                                                     _aov_planes(d_planes), _addr_array(d_rgb), out_len_each, _addr_array(d_f32),
+                                                     _addr_array(d_linear), _addr(d_scratch), scratch_bytes, _addr(stream)),
+                   "rt_scene_denoise_device")
 
     def set_camera(self, cam: Optional[Camera]):
         """Place the camera of every later call that generates camera rays (rt_scene_set_camera): tiles, passes, feature buffers,
@@ -630,22 +638,21 @@ class Scene:
         Returns (rays, states, stats): a RAY_DTYPE array whose directions are to be traced as given, and the (n, 4) uint64
         xoshiro256++ states after the camera's draws (None unless want_states) — the arguments of trace(..., as_given=True)."""
         end = req.spp if end is None else end
-        n = (req.height // max(req.divisions, 1)) * req.width * max(end - begin, 0)     # (a bad request is refused by the library)
+        hs, w = _strip_shape(req)
+        n = hs * w * max(end - begin, 0)
         rays = np.empty(n, _abi.RAY_DTYPE)
         states = np.empty((n, 4), np.uint64) if want_states else None
         st = TileStats()
-        _abi.check(self._lib.rt_scene_camera_rays(self._h, C.byref(req), begin, end, rays.ctypes.data_as(C.POINTER(_abi.Ray)),
-                                                  states.ctypes.data_as(C.POINTER(C.c_uint64)) if want_states else None,
-                                                  C.byref(st)), "rt_scene_camera_rays")
+        _abi.check(self._lib.rt_scene_camera_rays(self._h, C.byref(req), begin, end, _arg(rays), _arg(states), C.byref(st)),
+                   "rt_scene_camera_rays")
         return rays, states, st
 
     def camera_rays_device(self, req: TileRequest, begin: int, end: int, d_rays: int, d_rng_state: int = 0, stream: int = 0):
         """The camera rays of a strip on device buffers (rt_scene_camera_rays_device): Hs W (end - begin) rt_ray to d_rays and,
         optionally, 4 uint64 per record to d_rng_state — e.g. the data_ptr() of torch tensors that trace_device / intersect_device
         then read; asynchronous on `stream`, counters until collect()."""
-        vp = lambda ptr: C.c_void_p(ptr) if ptr else None
-        _abi.check(self._lib.rt_scene_camera_rays_device(self._h, C.byref(req), begin, end, vp(d_rays), vp(d_rng_state), vp(stream)),
-                   "rt_scene_camera_rays_device")
+        _abi.check(self._lib.rt_scene_camera_rays_device(self._h, C.byref(req), begin, end, _addr(d_rays), _addr(d_rng_state),
+                                                         _addr(stream)), "rt_scene_camera_rays_device")
 
     def collect(self) -> TileStats:
         st = TileStats()
@@ -771,12 +778,8 @@ class FrameContext:
         self._lib = _abi.load()
         if not _is_initialised():
             init()
-        if devices is None:
-            dv, nd = None, 0
-        else:
-            dv, nd = (C.c_int * len(devices))(*devices), len(devices)
         h = C.c_void_p()
-        _abi.check(self._lib.rt_frame_ctx_create(dv, nd, C.byref(h)), "rt_frame_ctx_create")
+        _abi.check(self._lib.rt_frame_ctx_create(*_devices(devices), C.byref(h)), "rt_frame_ctx_create")
         self._h = h
         self._buf = None
         self._pinned = None                  # the array whose page-locked registration the context holds (kept alive here)
@@ -784,9 +787,7 @@ class FrameContext:
             self.set_world(world)
 
     def set_world(self, world: World):
-        _abi.check(self._lib.rt_frame_ctx_set_world(self._h, _abi.ptr(world.spheres), len(world.spheres),
-                                                    _abi.ptr(world.triangles), len(world.triangles),
-                                                    _abi.ptr(world.world_index)), "rt_frame_ctx_set_world")
+        _abi.check(self._lib.rt_frame_ctx_set_world(self._h, *_world_args(world)), "rt_frame_ctx_set_world")
 
     def set_camera(self, cam: Optional[Camera]):
         """The job's camera (rt_frame_ctx_set_camera): every later frame is rendered from it; None: the reference camera."""
@@ -811,8 +812,7 @@ class FrameContext:
             self.release_buffer()
         fs = FrameStats()
         try:
-            _abi.check(self._lib.rt_frame_ctx_render(self._h, C.byref(req), out.ctypes.data_as(C.c_void_p), out.size,
-                                                     C.byref(fs)), "rt_frame_ctx_render")
+            _abi.check(self._lib.rt_frame_ctx_render(self._h, C.byref(req), _arg(out), out.size, C.byref(fs)), "rt_frame_ctx_render")
         finally:
             self._pinned = out               # (registered or not: harmless to hold, and an error return may have left it registered)
         return out.reshape(-1)[:n].reshape(req.height, req.width, 3), fs
@@ -845,11 +845,6 @@ def render_frame_native(world: World, req: TileRequest, devices: Optional[Sequen
     n = req.width * req.height * 3
     out = np.empty(n, np.uint8)
     st = TileStats()
-    if devices is None:
-        dv, nd = None, 0
-    else:
-        dv, nd = (C.c_int * len(devices))(*devices), len(devices)
-    _abi.check(lib.rt_render_frame(dv, nd, C.byref(req), _abi.ptr(world.spheres), len(world.spheres),
-                                   _abi.ptr(world.triangles), len(world.triangles), _abi.ptr(world.world_index),
-                                   out.ctypes.data_as(C.c_void_p), n, C.byref(st)), "rt_render_frame")
+    _abi.check(lib.rt_render_frame(*_devices(devices), C.byref(req), *_world_args(world), _arg(out), n, C.byref(st)),
+               "rt_render_frame")
     return out.reshape(req.height, req.width, 3), st

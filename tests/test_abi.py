@@ -1,8 +1,8 @@
-"""The C-ABI library loads and exports every symbol include/rt_tile.h declares (no compute
-calls: this container has no GPU), argument checks that need no device, struct layouts."""
+"""The C-ABI library without compute calls (this container has no GPU): defaults, status texts, the argument checks that need no
+device, the C client, the guard at the boundary.  (What the header declares, the binding mirrors and the libraries export:
+tests/test_surface.py.)"""
 import ctypes as C
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -10,12 +10,11 @@ import pytest
 
 from ray_tracer_s8_amd import _abi
 
-ROOT = Path(__file__).resolve().parent.parent
-HEADER = (ROOT / "include" / "rt_tile.h").read_text()
+from _surface import HEADER, ROOT, check_exports, exported, parse
 
 
 def declared_functions():
-    return re.findall(r"RT_API\s+[\w\s\*]+?\b(rt_\w+)\s*\(", HEADER)
+    return list(parse()["functions"])
 
 
 def test_header_declares_expected_surface():
@@ -35,19 +34,12 @@ def test_library_exports_every_declared_symbol():
     assert lib.rt_abi_version() == 4 == _abi.RT_ABI_VERSION
 
 
-def _exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
-    return {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("rt_")}
-
-
 def test_product_library_exports_exactly_the_header():
     """`nm -D librt_s8.so`: the rt_* functions of rt_tile.h and nothing else — no rt_debug_* hook (those live in the test
     library lib/librt_s8_dbg.so, the same sources compiled with -DRT_DEBUG_HOOKS)."""
     from ray_tracer_s8_amd import build
-    _abi.load()
-    assert _exported(build.LIB_PATH) == set(declared_functions())
-    _abi.load_debug()
-    dbg = _exported(build.DEBUG_LIB_PATH)
+    check_exports(declared_functions(), exactly=True)
+    dbg = exported(build.DEBUG_LIB_PATH)
     assert set(declared_functions()) < dbg
     assert {n for n in dbg if n.startswith("rt_debug_")} == {"rt_debug_read_counters", "rt_debug_sqrt_selftest", "rt_debug_set",
                                                               "rt_debug_throw", "rt_debug_unit"}
@@ -197,7 +189,7 @@ def test_scene_size_limit_is_checked_before_anything_is_allocated():
     lib = _abi.load()
     sph = np.zeros(1, _abi.SPHERE_DTYPE)
     out = C.c_void_p()
-    too_many = 0x3ffffff + 1
+    too_many = _abi.RT_MAX_PRIMITIVES + 1
     rc = lib.rt_scene_create(0, sph.ctypes.data_as(C.c_void_p), C.c_uint32(too_many), None, C.c_uint32(0), None, C.byref(out))
     assert rc == -8 and not out.value
     rq = _abi.default_request(width=8, height=8, divisions=1, spp=1)

@@ -1,12 +1,7 @@
-"""Feature buffers of a strip, the part that needs no GPU: rt_tile.h declares rt_scene_render_aov / rt_scene_render_aovs_device
-with the argument lists the binding uses, both libraries export them (and the product library still exports exactly what the
-header declares), rt_aov_planes is 40 bytes with the documented offsets (as is the binding's AovPlanes), the ABI it was added to is
-unchanged (RT_ABI_VERSION 4), the argument checks refuse before any device work, and the helper that turns sums into means."""
+"""Feature buffers of a strip, the part that needs no GPU: rt_tile.h documents the contract, the argument checks refuse before any
+device work, and the helper that turns sums into means.  (The declarations of rt_scene_render_aov / rt_scene_render_aovs_device, the
+binding's argument lists, rt_aov_planes' layout, the exports and the ABI version: tests/test_surface.py.)"""
 import ctypes as C
-import re
-import shutil
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -14,51 +9,7 @@ import pytest
 import ray_tracer_s8_amd as rt
 from ray_tracer_s8_amd import _abi
 
-ROOT = Path(__file__).resolve().parent.parent
-HEADER = (ROOT / "include" / "rt_tile.h").read_text()
-
-AOV_ENTRY_POINTS = {
-    "rt_scene_render_aov": ["rt_scene*", "const rt_tile_request*", "uint32_t", "uint32_t", "const rt_aov_planes*", "rt_tile_stats*"],
-    "rt_scene_render_aovs_device": ["rt_scene*", "const rt_tile_request*", "uint32_t", "uint32_t", "uint32_t", "const rt_aov_planes*",
-                                    "void*"],
-}
-PLANE_FIELDS = [("float*", "albedo", 0), ("float*", "normal", 8), ("float*", "depth", 16), ("uint32_t*", "hits", 24),
-                ("uint32_t*", "index", 32)]
-
-
-def _declared_params(name):
-    m = re.search(r"RT_API\s+int\s+" + name + r"\s*\(([^)]*)\)\s*;", HEADER)
-    assert m, f"{name} is not declared in rt_tile.h"
-    types = []
-    for arg in m.group(1).split(","):
-        arg = " ".join(re.sub(r"/\*.*?\*/", "", arg).split())
-        t = re.sub(r"\s*\b\w+$", "", arg)
-        types.append(re.sub(r"\s*\*", "*", t))
-    return types
-
-
-def _exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
-    return {ln.split()[-1] for ln in out.splitlines() if ln.split()}
-
-
-def _header_struct_fields(name):
-    m = re.search(r"typedef\s+struct\s+" + name + r"\s*\{(.*?)\}\s*" + name + r"\s*;", HEADER, re.S)
-    assert m, f"{name} is not defined in rt_tile.h"
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = " ".join(decl.split())
-        if not decl:
-            continue
-        typ, name_ = decl.rsplit(" ", 1)
-        fields.append((typ.replace(" ", ""), name_))
-    return fields
-
-
-def test_header_declares_the_aov_entry_points():
-    for name, params in AOV_ENTRY_POINTS.items():
-        assert _declared_params(name) == params, name
+from _surface import HEADER, check_abi_version_unchanged, check_exports
 
 
 def test_header_documents_the_contract():
@@ -70,56 +21,16 @@ def test_header_documents_the_contract():
     assert "(4, additions only: feature buffers of a strip rt_scene_render_aov / rt_scene_render_aovs_device" in version_comment
 
 
-def test_binding_argtypes_match_the_header():
-    lib = _abi.load()
-    vp, u32 = C.c_void_p, C.c_uint32
-    assert lib.rt_scene_render_aov.argtypes == [vp, C.POINTER(_abi.TileRequest), u32, u32, C.POINTER(_abi.AovPlanes),
-                                                C.POINTER(_abi.TileStats)]
-    assert lib.rt_scene_render_aov.restype is C.c_int
-    assert lib.rt_scene_render_aovs_device.argtypes == [vp, C.POINTER(_abi.TileRequest), u32, u32, u32, C.POINTER(_abi.AovPlanes), vp]
-    assert lib.rt_scene_render_aovs_device.restype is C.c_int
-
-
 def test_libraries_export_the_aov_entry_points_and_the_product_exactly_the_header():
-    from ray_tracer_s8_amd import build
-    _abi.load()
-    _abi.load_debug()
-    for path in (build.LIB_PATH, build.DEBUG_LIB_PATH):
-        exported = _exported(path)
-        for name in AOV_ENTRY_POINTS:
-            assert name in exported, (path, name)
-    declared = set(re.findall(r"RT_API\s+[\w\s\*]*?\b(rt_\w+)\s*\(", HEADER))
-    product = {s for s in _exported(build.LIB_PATH) if s.startswith("rt_")}
-    assert product == declared, (product ^ declared)
-
-
-def test_aov_planes_layout():
-    assert _header_struct_fields("rt_aov_planes") == [(t, n) for t, n, _ in PLANE_FIELDS]
-    assert C.sizeof(_abi.AovPlanes) == 40
-    for _, n, off in PLANE_FIELDS:
-        f = getattr(_abi.AovPlanes, n)
-        assert f.offset == off and f.size == 8, n
-    assert tuple(n for n, _ in _abi.AovPlanes._fields_) == _abi.AOV_PLANES == tuple(n for _, n, _ in PLANE_FIELDS)
-
-
-def test_header_layout_compiles_as_c():
-    """sizeof and offsetof as a C compiler sees the header."""
-    gcc = shutil.which("gcc")
-    assert gcc
-    src = ("#include <stddef.h>\n#include \"rt_tile.h\"\n"
-           "_Static_assert(sizeof(rt_aov_planes) == 40, \"rt_aov_planes\");\n"
-           "_Static_assert(offsetof(rt_aov_planes, albedo) == 0 && offsetof(rt_aov_planes, normal) == 8, \"a\");\n"
-           "_Static_assert(offsetof(rt_aov_planes, depth) == 16 && offsetof(rt_aov_planes, hits) == 24, \"b\");\n"
-           "_Static_assert(offsetof(rt_aov_planes, index) == 32, \"c\");\n"
-           "_Static_assert(sizeof(rt_tile_request) == 64 && sizeof(rt_tile_stats) == 64, \"abi 4\");\n")
-    r = subprocess.run([gcc, "-std=c11", "-Wall", "-Werror", "-fsyntax-only", f"-I{ROOT / 'include'}", "-x", "c", "-"], input=src,
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    check_exports(["rt_scene_render_aov", "rt_scene_render_aovs_device"], exactly=True)
 
 
 def test_abi_version_unchanged():
-    assert re.search(r"#define\s+RT_ABI_VERSION\s+4u", HEADER)
-    assert _abi.RT_ABI_VERSION == 4 and _abi.load().rt_abi_version() == 4
+    check_abi_version_unchanged()
+
+
+def test_aov_plane_names_are_the_struct_fields():
+    assert tuple(n for n, _ in _abi.AovPlanes._fields_) == _abi.AOV_PLANES
 
 
 def test_aov_entry_points_check_arguments_without_a_device():

@@ -1,8 +1,8 @@
-"""Cone sampling of sphere lights, the part that needs no GPU: rt_tile.h declares RT_LIGHTS_AREA / RT_LIGHTS_CONE and
-rt_scene_set_light_sampling / rt_scene_light_sampling with the argument lists the binding uses, states the contract in both sections and
-the limit it lifts, both libraries export the two functions, _abi.py and the package mirror them, the ABI they were added to is
-unchanged (RT_ABI_VERSION 4, the RT_FLAG_* set as it was: the switch is a property of the scene, not a flag), and the calls refuse a
-NULL scene and a value above RT_LIGHTS_CONE before anything else."""
+"""Cone sampling of sphere lights, the part that needs no GPU: rt_tile.h states the contract in both sections and the limit it lifts,
+the package mirrors the binding, the RT_FLAG_* set is as it was (the switch is a property of the scene, not a flag), and the calls
+refuse a NULL scene and a value above RT_LIGHTS_CONE before anything else.  (RT_LIGHTS_AREA / RT_LIGHTS_CONE, the declarations of
+rt_scene_set_light_sampling / rt_scene_light_sampling, the binding's argument lists, the exports and the ABI version:
+tests/test_surface.py.)"""
 import ctypes as C
 import re
 
@@ -10,13 +10,10 @@ import pytest
 
 from ray_tracer_s8_amd import _abi
 
-from test_trace_surface import HEADER, _declared_params, _exported
+from _surface import HEADER, check_abi_version_unchanged, check_exports
 
 
 def test_header_declares_the_enum_and_the_entry_points():
-    assert re.search(r"enum\s*\{\s*RT_LIGHTS_AREA\s*=\s*0u\s*,\s*RT_LIGHTS_CONE\s*=\s*1u\s*\}", HEADER)
-    assert _declared_params("rt_scene_set_light_sampling") == ["rt_scene*", "uint32_t"]
-    assert _declared_params("rt_scene_light_sampling") == ["rt_scene*", "uint32_t*"]
     assert HEADER.index("RT_API int rt_scene_direct_device") < HEADER.index("RT_API int rt_scene_set_light_sampling") < \
         HEADER.index("RT_API int rt_scene_light_sampling") < HEADER.index("typedef struct rt_nee_request")
     assert "additions only: cone sampling of sphere lights" in HEADER
@@ -32,8 +29,7 @@ def test_flag_set_and_abi_version_are_unchanged():
     assert sorted(bits) == list(range(16))
     flags = {n: getattr(_abi, n) for n in dir(_abi) if n.startswith("RT_FLAG_") and n != "RT_FLAG_NONE"}
     assert sorted(flags.values()) == [1 << b for b in range(16)]
-    assert re.search(r"#define\s+RT_ABI_VERSION\s+4u", HEADER)
-    assert _abi.RT_ABI_VERSION == 4 and _abi.load().rt_abi_version() == 4
+    check_abi_version_unchanged()
 
 
 def test_binding_mirrors_the_header():
@@ -48,11 +44,7 @@ def test_binding_mirrors_the_header():
 
 
 def test_libraries_export_the_entry_points():
-    from ray_tracer_s8_amd import build
-    _abi.load()
-    _abi.load_debug()
-    for path in (build.LIB_PATH, build.DEBUG_LIB_PATH):
-        assert {"rt_scene_set_light_sampling", "rt_scene_light_sampling"} <= _exported(path), path
+    check_exports(["rt_scene_set_light_sampling", "rt_scene_light_sampling"])
 
 
 def test_calls_check_their_arguments_without_a_device():

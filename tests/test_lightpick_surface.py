@@ -1,7 +1,7 @@
-"""Light selection by power, the part that needs no GPU: rt_tile.h declares RT_FLAG_LIGHTS_BY_POWER (bit 15, beside no other flag) and
-rt_scene_light_table with the argument list the binding uses, both libraries export it, _abi.py mirrors both, the ABI they were added
-to is unchanged (RT_ABI_VERSION 4), the header no longer states the limit the flag lifts, and the call refuses a NULL scene before
-anything else.  (capacity < M needs a scene with emitters: tests/test_gpu_lightpick.py.)"""
+"""Light selection by power, the part that needs no GPU: rt_tile.h declares RT_FLAG_LIGHTS_BY_POWER (bit 15, beside no other flag),
+_abi.py mirrors it, the header no longer states the limit the flag lifts, and the call refuses a NULL scene before anything else.
+(The declaration of rt_scene_light_table, the binding's argument list, the exports and the ABI version: tests/test_surface.py.
+capacity < M needs a scene with emitters: tests/test_gpu_lightpick.py.)"""
 import ctypes as C
 import re
 
@@ -9,16 +9,13 @@ import numpy as np
 
 from ray_tracer_s8_amd import _abi
 
-from test_trace_surface import HEADER, _declared_params, _exported
-
-PARAMS = ["rt_scene*", "uint32_t", "uint32_t*", "float*", "uint32_t"]
+from _surface import HEADER, check_abi_version_unchanged, check_exports
 
 
 def test_header_declares_the_flag_and_the_entry_point():
     assert re.search(r"RT_FLAG_LIGHTS_BY_POWER\s*=\s*1u\s*<<\s*15\b", HEADER)
     bits = [int(b) for b in re.findall(r"RT_FLAG_\w+\s*=\s*1u\s*<<\s*(\d+)", HEADER)]
     assert sorted(bits) == list(range(16))                                 # every bit once: the new flag shares none
-    assert _declared_params("rt_scene_light_table") == PARAMS
     assert HEADER.index("RT_API int rt_scene_light_count") < HEADER.index("RT_API int rt_scene_light_table") < HEADER.index("RT_API int rt_scene_direct(")
     assert "additions only: light selection by power" in HEADER
     assert "not by power" not in HEADER                                    # the limit of both sections is gone
@@ -38,16 +35,11 @@ def test_binding_mirrors_the_header():
 
 
 def test_libraries_export_the_entry_point():
-    from ray_tracer_s8_amd import build
-    _abi.load()
-    _abi.load_debug()
-    for path in (build.LIB_PATH, build.DEBUG_LIB_PATH):
-        assert "rt_scene_light_table" in _exported(path), path
+    check_exports(["rt_scene_light_table"])
 
 
 def test_abi_version_unchanged():
-    assert re.search(r"#define\s+RT_ABI_VERSION\s+4u", HEADER)
-    assert _abi.RT_ABI_VERSION == 4 and _abi.load().rt_abi_version() == 4
+    check_abi_version_unchanged()
 
 
 def test_light_table_checks_its_scene_without_a_device():

@@ -1,8 +1,8 @@
-"""Light samples at glossy hits, the part that needs no GPU: rt_tile.h compiles as C and declares RT_GLOSSY_BOUNCE / RT_GLOSSY_MIS and
-rt_scene_set_glossy_sampling / rt_scene_glossy_sampling with the argument lists the binding uses, states the contract in the
-next-event-estimation section, both libraries export the two functions, _abi.py and the package mirror them, the ABI they were added
-to is unchanged (RT_ABI_VERSION 4, the RT_FLAG_* set and rt_nee_request as they were: the switch is a property of the scene), and the
-calls refuse a NULL scene and a value above RT_GLOSSY_MIS before anything else."""
+"""Light samples at glossy hits, the part that needs no GPU: a C99 client of the two calls compiles against rt_tile.h, the header states
+the contract in the next-event-estimation section, the package mirrors the binding, the RT_FLAG_* set and rt_nee_request's documented
+size are as they were (the switch is a property of the scene), and the calls refuse a NULL scene and a value above RT_GLOSSY_MIS
+before anything else.  (RT_GLOSSY_BOUNCE / RT_GLOSSY_MIS, the declarations of rt_scene_set_glossy_sampling /
+rt_scene_glossy_sampling, the binding's argument lists, the exports and the ABI version: tests/test_surface.py.)"""
 import ctypes as C
 import re
 import shutil
@@ -12,7 +12,7 @@ import pytest
 
 from ray_tracer_s8_amd import _abi
 
-from test_trace_surface import HEADER, ROOT, _declared_params, _exported
+from _surface import HEADER, ROOT, check_abi_version_unchanged, check_exports
 
 
 def test_header_compiles_as_c(tmp_path):
@@ -26,9 +26,6 @@ def test_header_compiles_as_c(tmp_path):
 
 
 def test_header_declares_the_enum_and_the_entry_points():
-    assert re.search(r"enum\s*\{\s*RT_GLOSSY_BOUNCE\s*=\s*0u\s*,\s*RT_GLOSSY_MIS\s*=\s*1u\s*\}", HEADER)
-    assert _declared_params("rt_scene_set_glossy_sampling") == ["rt_scene*", "uint32_t"]
-    assert _declared_params("rt_scene_glossy_sampling") == ["rt_scene*", "uint32_t*"]
     assert HEADER.index("RT_API int rt_scene_trace_nee_device") < HEADER.index("RT_API int rt_scene_set_glossy_sampling") < \
         HEADER.index("RT_API int rt_scene_glossy_sampling")
     assert "additions only: light samples at glossy hits" in HEADER
@@ -44,8 +41,7 @@ def test_header_declares_the_enum_and_the_entry_points():
 def test_flag_set_request_and_abi_version_are_unchanged():
     bits = [int(b) for b in re.findall(r"RT_FLAG_\w+\s*=\s*1u\s*<<\s*(\d+)", HEADER)]
     assert sorted(bits) == list(range(16))
-    assert re.search(r"#define\s+RT_ABI_VERSION\s+4u", HEADER)
-    assert _abi.RT_ABI_VERSION == 4 and _abi.load().rt_abi_version() == 4
+    check_abi_version_unchanged()
     assert C.sizeof(_abi.NeeRequest) == 32 and re.search(r"\}\s*rt_nee_request;\s*/\* 32 bytes \*/", HEADER)
     assert re.search(r"enum\s*\{\s*RT_NEE_LIGHT_ONLY\s*=\s*0u\s*,\s*RT_NEE_MIS\s*=\s*1u\s*\}", HEADER)
 
@@ -63,11 +59,7 @@ def test_binding_mirrors_the_header():
 
 
 def test_libraries_export_the_entry_points():
-    from ray_tracer_s8_amd import build
-    _abi.load()
-    _abi.load_debug()
-    for path in (build.LIB_PATH, build.DEBUG_LIB_PATH):
-        assert {"rt_scene_set_glossy_sampling", "rt_scene_glossy_sampling"} <= _exported(path), path
+    check_exports(["rt_scene_set_glossy_sampling", "rt_scene_glossy_sampling"])
 
 
 def test_calls_check_their_arguments_without_a_device():

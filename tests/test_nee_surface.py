@@ -1,92 +1,35 @@
-"""The next-event-estimation integrator for caller rays, the part that needs no GPU: rt_tile.h declares rt_scene_trace_nee /
-rt_scene_trace_nee_device with the argument lists the binding uses, both libraries export them, rt_nee_request is 32 bytes with the
-documented offsets (as is the binding's twin), RT_NEE_LIGHT_ONLY = 0 and RT_NEE_MIS = 1, the ABI they were added to is unchanged
-(RT_ABI_VERSION 4), every argument check of the contract refuses before any device work, and Scene.trace_nee checks its arguments
-before it calls.  (The limit of 2^23 emitters is the plan's: tests/test_nee_host.py.)"""
+"""The next-event-estimation integrator for caller rays, the part that needs no GPU: where rt_tile.h puts its section, the package's
+names, every argument check of the contract refuses before any device work, and Scene.trace_nee checks its arguments before it
+calls.  (The declarations of rt_scene_trace_nee / rt_scene_trace_nee_device, the binding's argument lists, rt_nee_request's layout,
+RT_NEE_LIGHT_ONLY = 0 and RT_NEE_MIS = 1, the exports and the ABI version: tests/test_surface.py.  The limit of 2^23 emitters is the
+plan's: tests/test_nee_host.py.)"""
 import ctypes as C
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from ray_tracer_s8_amd import _abi
 
-from test_trace_surface import HEADER, ROOT, _declared_params, _exported, _header_struct_fields
-
-ENTRY_POINTS = {
-    "rt_scene_trace_nee": ["rt_scene*", "const rt_nee_request*", "const rt_ray*", "uint32_t", "uint64_t*", "float*", "uint32_t*",
-                           "uint32_t*", "rt_tile_stats*"],
-    "rt_scene_trace_nee_device": ["rt_scene*", "const rt_nee_request*", "const void*", "uint32_t", "void*", "void*", "void*", "void*",
-                                  "void*"],
-}
-REQUEST_FIELDS = [("uint32_t", "spp", 0, 4), ("uint32_t", "max_bounces", 4, 4), ("uint64_t", "seed", 8, 8), ("uint32_t", "flags", 16, 4),
-                  ("uint32_t", "ray_form", 20, 4), ("uint32_t", "mode", 24, 4), ("uint32_t", "reserved", 28, 4)]
+from _surface import HEADER, check_abi_version_unchanged, check_exports
 
 
 def test_header_declares_the_nee_entry_points():
-    for name, params in ENTRY_POINTS.items():
-        assert _declared_params(name) == params, name
-    assert re.search(r"RT_NEE_LIGHT_ONLY\s*=\s*0u\s*,\s*RT_NEE_MIS\s*=\s*1u", HEADER)
     assert HEADER.index("RT_API int rt_scene_direct_device") < HEADER.index("typedef struct rt_nee_request") < HEADER.index("typedef struct rt_aov_planes")
     assert "additions only: next-event estimation" in HEADER
 
 
-def test_binding_argtypes_match_the_header():
-    lib = _abi.load()
-    vp, u32, u32p = C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)
-    assert lib.rt_scene_trace_nee.argtypes == [vp, C.POINTER(_abi.NeeRequest), C.POINTER(_abi.Ray), u32, C.POINTER(C.c_uint64),
-                                               C.POINTER(C.c_float), u32p, u32p, C.POINTER(_abi.TileStats)]
-    assert lib.rt_scene_trace_nee_device.argtypes == [vp, C.POINTER(_abi.NeeRequest), vp, u32] + [vp] * 5
-    assert all(getattr(lib, n).restype is C.c_int for n in ENTRY_POINTS)
-
-
 def test_libraries_export_the_nee_entry_points():
-    from ray_tracer_s8_amd import build
-    _abi.load()
-    _abi.load_debug()
-    for path in (build.LIB_PATH, build.DEBUG_LIB_PATH):
-        exported = _exported(path)
-        for name in ENTRY_POINTS:
-            assert name in exported, (path, name)
-    declared = set(re.findall(r"RT_API\s+[\w\s\*]*?\b(rt_\w+)\s*\(", HEADER))
-    assert {s for s in _exported(build.LIB_PATH) if s.startswith("rt_")} == declared
-
-
-def test_struct_layout_and_enum():
-    assert _header_struct_fields("rt_nee_request") == [(t, n) for t, n, _, _ in REQUEST_FIELDS]
-    assert C.sizeof(_abi.NeeRequest) == 32
-    assert [n for n, _ in _abi.NeeRequest._fields_] == [n for _, n, _, _ in REQUEST_FIELDS]
-    for _, n, off, size in REQUEST_FIELDS:
-        f = getattr(_abi.NeeRequest, n)
-        assert f.offset == off and f.size == size, n
-    assert (_abi.RT_NEE_LIGHT_ONLY, _abi.RT_NEE_MIS) == (0, 1)
-    import ray_tracer_s8_amd as rt
-    assert rt.NeeRequest is _abi.NeeRequest and (rt.RT_NEE_LIGHT_ONLY, rt.RT_NEE_MIS) == (0, 1)
-    assert hasattr(rt.Scene, "trace_nee") and hasattr(rt.Scene, "trace_nee_device")
-
-
-def test_header_layout_compiles_as_c():
-    """sizeof and offsetof as a C compiler sees the header."""
-    gcc = shutil.which("gcc")
-    assert gcc
-    src = ("#include <stddef.h>\n#include \"rt_tile.h\"\n"
-           "_Static_assert(sizeof(rt_nee_request) == 32 && offsetof(rt_nee_request, max_bounces) == 4, \"rt_nee_request\");\n"
-           "_Static_assert(offsetof(rt_nee_request, seed) == 8 && offsetof(rt_nee_request, flags) == 16, \"rt_nee_request\");\n"
-           "_Static_assert(offsetof(rt_nee_request, ray_form) == 20 && offsetof(rt_nee_request, mode) == 24, \"rt_nee_request\");\n"
-           "_Static_assert(offsetof(rt_nee_request, reserved) == 28, \"rt_nee_request\");\n"
-           "_Static_assert(RT_NEE_LIGHT_ONLY == 0 && RT_NEE_MIS == 1, \"mode\");\n"
-           "_Static_assert(sizeof(rt_trace_request) == 24 && sizeof(rt_direct_request) == 16 && sizeof(rt_direct) == 32, \"abi 4\");\n"
-           "_Static_assert(sizeof(rt_ray) == 32 && sizeof(rt_hit) == 32 && sizeof(rt_tile_stats) == 64 && sizeof(rt_bounce) == 16, \"abi 4\");\n")
-    r = subprocess.run([gcc, "-std=c11", "-Wall", "-Werror", "-fsyntax-only", f"-I{ROOT / 'include'}", "-x", "c", "-"], input=src,
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    check_exports(["rt_scene_trace_nee", "rt_scene_trace_nee_device"], exactly=True)
 
 
 def test_abi_version_unchanged():
-    assert re.search(r"#define\s+RT_ABI_VERSION\s+4u", HEADER)
-    assert _abi.RT_ABI_VERSION == 4 and _abi.load().rt_abi_version() == 4
+    check_abi_version_unchanged()
+
+
+def test_package_exports_the_nee_names():
+    import ray_tracer_s8_amd as rt
+    assert rt.NeeRequest is _abi.NeeRequest and (rt.RT_NEE_LIGHT_ONLY, rt.RT_NEE_MIS) == (0, 1)
+    assert hasattr(rt.Scene, "trace_nee") and hasattr(rt.Scene, "trace_nee_device")
 
 
 def arg_error_calls(lib, scene):
@@ -163,6 +106,8 @@ def test_python_argument_handling():
             sc.trace_nee(o.reshape(3, 5), d.reshape(3, 5))
         with pytest.raises(ValueError):
             sc.trace_nee(o, d, rng_state=states[:-1])
+        with pytest.raises(ValueError):
+            sc.trace_nee(o, d, rng_state=states[:, :3])
         with pytest.raises(AssertionError):                                # well-formed arguments do reach the library
             sc.trace_nee(o, d, rng_state=states, mode=_abi.RT_NEE_LIGHT_ONLY)
     finally:
