@@ -26,6 +26,7 @@
 
 #include "rt_assign.h"
 #include "rt_bvh.h"
+#include "rt_frame_plan.h"
 #include "rt_kernel.hip.h"
 #include "rt_plan.h"
 #include "rt_query.hip.h"
@@ -332,13 +333,6 @@ void scene_refs(const rt_scene* sc, bool full_chain, rtk::SceneRefs& r) {
     r.geom_r = sc->d_geom_r;
     r.tri = sc->d_tri;
     r.counters = sc->d_counters;
-}
-
-bool same_frame(const rt_tile_request& a, const rt_tile_request& b) {
-    return a.width == b.width && a.height == b.height && a.divisions == b.divisions && a.spp == b.spp &&
-           a.max_bounces == b.max_bounces && a.aperture == b.aperture && a.focus_distance == b.focus_distance &&
-           a.fov == b.fov && a.focal_length == b.focal_length && a.t_min == b.t_min && a.t_max == b.t_max &&
-           a.flags == b.flags;
 }
 
 // Enqueue a batch of strips of one frame (<= MAX_BATCH) as ONE launch of persistent waves.
@@ -743,8 +737,7 @@ RT_API void rt_tile_request_defaults(rt_tile_request* rq) {
 }
 
 RT_API size_t rt_tile_bytes(const rt_tile_request* rq) {
-    if (!rq || rq->divisions == 0) return 0;
-    return (size_t)(rq->height / rq->divisions) * rq->width * 3;   // main.rs:53-59
+    return rq ? rtframe::strip_bytes(*rq) : 0;
 }
 
 static int rt_init_impl(int* n_devices) {
@@ -974,7 +967,7 @@ static int check_batch(const rt_tile_request* rqs, uint32_t n) {
     for (uint32_t i = 0; i < n; i++) {
         int rc = check_request(&rqs[i]);
         if (rc) return rc;
-        if (!same_frame(rqs[0], rqs[i]))
+        if (!rtframe::same_frame(rqs[0], rqs[i]))
             return fail(RT_ERR_BAD_ARG, "batched requests must agree on every field but division_no and seed");
     }
     return RT_OK;
@@ -1058,12 +1051,14 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
     if ((rc = hf.device()) || (rc = sc->d_out.reserve(need * n, "strips")) || (want_f32 && (rc = sc->d_outf.reserve(need * n * sizeof(float), "strips f32"))) ||
         (pass && (rc = sc->d_acc.reserve(need * n * sizeof(float), "running sums"))))
         return rc;
+    // Launch groups [first, count): the last quarter of the strips as its own launch when the downloads are worth hiding, so that the
+    // D2H copies of the strips before it (copy stream) run under it and only the last group's copies are exposed (d2h_ms = that part).
+    const std::vector<std::pair<uint32_t, uint32_t>> groups = rtframe::launch_groups(n, need);
     // per-strip costs: one block of COST_COPIES x MAX_BATCH counters per launch group of the call
-    constexpr size_t COST_BLOCK = (size_t)rtk::COST_COPIES * rtk::MAX_BATCH;
-    const size_t cost_blocks = strip_cost_out ? (n + rtk::MAX_BATCH - 1) / rtk::MAX_BATCH + 1 : 0;
+    constexpr size_t COST_BLOCK = rtframe::COST_BLOCK;
     unsigned long long* d_cost = nullptr;
     if (strip_cost_out) {
-        const size_t cost_b = cost_blocks * COST_BLOCK * sizeof(unsigned long long);
+        const size_t cost_b = groups.size() * COST_BLOCK * sizeof(unsigned long long);
         if ((rc = sc->d_cost.reserve(cost_b, "strip costs"))) return rc;
         d_cost = (unsigned long long*)sc->d_cost.d;
         HIPCHK(hipMemsetAsync(d_cost, 0, cost_b, st));
@@ -1078,19 +1073,6 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
         drgb[i] = sc->d_out.d + need * i;
         df32[i] = (want_f32 && out_f32[i]) ? sc->d_outf.d + need * i * sizeof(float) : nullptr;
         if (pass) dacc[i] = sc->d_acc.d + need * i * sizeof(float);
-    }
-    // Launch groups: the last quarter of the strips goes out as its own launch, so that the D2H copies of the strips
-    // before it (copy stream) run under it and only the last group's copies are exposed (d2h_ms = that exposed part).
-    std::vector<std::pair<uint32_t, uint32_t>> groups;    // [first, count)
-    {
-        // ... when the downloads are worth hiding: a second launch costs its own tail (half a millisecond at c3, one at c4), a
-        // frame's strips come down at about 50 GB/s, so below 64 MiB per call one launch and an exposed download are faster
-        // (c3, 24.9 MB: 9.3 instead of 9.6 ms per frame; c4's 99.5 MB keeps the split)
-        const uint32_t tail = (n >= 4 && (uint64_t)need * n > (64ull << 20)) ? std::max<uint32_t>(1, n / 4) : 0;
-        for (uint32_t i0 = 0; i0 < n - tail; i0 += rtk::MAX_BATCH)
-            groups.emplace_back(i0, std::min<uint32_t>(rtk::MAX_BATCH, n - tail - i0));
-        for (uint32_t i0 = n - tail; i0 < n; i0 += rtk::MAX_BATCH)
-            groups.emplace_back(i0, std::min<uint32_t>(rtk::MAX_BATCH, n - i0));
     }
     hipStream_t cs = sc->ctx->copy_stream;
     std::vector<EvPair> gev;
@@ -1143,13 +1125,7 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
     }
     HIPCHK(hipEventRecord(gev.back().b, cs));
     HIPCHK(hipEventSynchronize(gev.back().b));
-    if (strip_cost_out)
-        for (size_t g = 0; g < groups.size(); g++)
-            for (uint32_t i = 0; i < groups[g].second; i++) {
-                unsigned long long sum = 0;
-                for (uint32_t c = 0; c < rtk::COST_COPIES; c++) sum += cost_raw[g * COST_BLOCK + (size_t)c * rtk::MAX_BATCH + i];
-                strip_cost_out[groups[g].first + i] = sum;
-            }
+    if (strip_cost_out) rtframe::fold_strip_costs(cost_raw.data(), groups, strip_cost_out);
     float d2h = 0.f;
     HIPCHK(hipEventElapsedTime(&d2h, gev.back().a, gev.back().b));   // last launch done -> last byte on the host
     ev_return.ok = true;
@@ -2057,78 +2033,58 @@ struct rt_frame_ctx {
     const HostScene* hs = nullptr;
     bool have_world = false;
     float scene_ms_pending = 0.f;       // duration of the last set_world, charged to the next frame's stats
-    // CMD_RENDER
-    rt_tile_request rq;
-    uint8_t* out = nullptr;
-    size_t strip = 0;
-    bool use_queue = false;
-    std::atomic<uint32_t> next_strip{0};
-    // strip assignment (rt_assign.h): owner[k] = entry of strip k for THIS frame; strip_cost = ray segments per strip measured on the
-    // job's last frame (valid while the world and the frame's geometry stay what they were)
-    std::vector<uint32_t> owner;
-    uint32_t assignment = 0;
-    std::vector<double> strip_cost;
-    rt_tile_request cost_rq;            // the frame the costs were measured on
-    rtplan::Pose cost_pose;             //   ... and the camera it was seen from (cost_has_pose false: the reference camera)
-    bool cost_has_pose = false;
-    // the job's camera (rt_frame_ctx_set_camera): handed to every entry's scene at the start of a frame
+    // ---- the job's state, kept from frame to frame
+    // its camera (rt_frame_ctx_set_camera): handed to every entry's scene at the start of a frame
     rtplan::Pose pose;
     bool has_pose = false;
-    bool cost_valid = false;
-    std::vector<unsigned long long> cost_now;   // filled by the dispatchers during a frame (each writes its own strips' entries)
+    rtframe::CostMemory costs;          // ray segments per strip of the job's last frame: the next frame is assigned by them
     // the caller's frame buffer, page-locked once
     void* pinned_ptr = nullptr;
     size_t pinned_len = 0;
+    // ---- CMD_RENDER: the frame in flight (written by rt_frame_ctx_render before the hand-over, read by the dispatchers)
+    rtframe::FramePlan plan;            // the kernels' request, the strip size, owner[k] = entry of strip k (rt_frame_plan.h)
+    uint8_t* out = nullptr;
+    std::atomic<uint32_t> next_strip{0};        // strip queue: the next strip to pull
+    std::vector<unsigned long long> cost_now;   // filled by the dispatchers (each writes its own strips' entries)
 };
 
 namespace {
 
-int frame_dev_render(rt_frame_ctx* fc, int w) {
+// Entry w's strips of the frame in flight (plan.owner: snake / longest-first by measured cost / k % n, rt_frame_plan.h) as one
+// batch: one launch per <= MAX_BATCH strips, the last quarter as its own launch so that the downloads of the others run under it
+// (controller main.rs:47-75 fires one request per division; Docker DNS round-robins them over the slaves).  Stitch by division_no:
+// strip k lands at byte offset k * strip (controller main.rs:109-115).
+int frame_dev_render_owned(rt_frame_ctx* fc, int w) {
     FrameDev& d = fc->fd[w];
-    const int nd = (int)fc->fd.size();
-    const rt_tile_request& rq0 = fc->rq;
-    const size_t strip = fc->strip;
+    const rtframe::FramePlan& plan = fc->plan;
+    std::vector<rt_tile_request> rqs;
+    std::vector<uint8_t*> outs;
+    for (uint32_t k = 0; k < plan.rq.divisions; k++) {
+        if (plan.owner[k] != (uint32_t)w) continue;
+        rt_tile_request rq = plan.rq;
+        rq.division_no = k;
+        rqs.push_back(rq);
+        outs.push_back(fc->out + (size_t)k * plan.strip_bytes);
+    }
+    if (rqs.empty()) return RT_OK;
+    std::vector<unsigned long long> cost(rqs.size(), 0ull);
+    int r = rt_scene_render_tiles_impl(d.scene, rqs.data(), (uint32_t)rqs.size(), outs.data(), plan.strip_bytes, nullptr, &d.st, cost.data());
+    if (r) return r;
+    for (size_t i = 0; i < rqs.size(); i++) fc->cost_now[rqs[i].division_no] = cost[i];      // (disjoint entries per dispatcher)
+    return RT_OK;
+}
+
+// Dynamic assignment: pull one strip at a time, the bottom of the frame first (its strips cost the most: longest-first keeps the
+// devices' finish times within one cheap strip of each other).  Two strips in flight per entry, each on its own stream with its
+// own device buffer: the launch tail and the download of one run under the other.  Streams and buffers belong to the context:
+// made on the first queue-mode frame, grown when a frame has larger strips.
+int frame_dev_render_queue(rt_frame_ctx* fc, int w) {
+    FrameDev& d = fc->fd[w];
+    const rt_tile_request& rq0 = fc->plan.rq;
+    const size_t strip = fc->plan.strip_bytes;
     uint8_t* out_rgb = fc->out;
-    std::memset(&d.st, 0, sizeof d.st);
     rt_scene* sc = d.scene;
-    if (!sc) return fail(RT_ERR_BAD_ARG, "rt_frame_ctx_render before rt_frame_ctx_set_world");
-    {
-        std::lock_guard<std::mutex> lk(sc->mu);          // the job's camera: this entry's launches of the frame read it
-        sc->pose = fc->pose;
-        sc->has_pose = fc->has_pose;
-    }
-    if (!fc->use_queue) {
-        // strip k -> entry k % nd (controller main.rs:47-75 fires one request per division; Docker DNS round-robins them
-        // over the slaves): all strips of this device go out as one batch (one launch per <= MAX_BATCH strips, the last
-        // quarter as its own launch so that the downloads of the others run under it); stitch by division_no: strip k
-        // lands at byte offset k * strip (controller main.rs:109-115)
-        // (which strips: fc->owner, made by rt_frame_ctx_render — snake / longest-first by measured cost / k % nd, rt_assign.h)
-        std::vector<rt_tile_request> rqs;
-        std::vector<uint8_t*> outs;
-        std::vector<uint32_t> mine;
-        for (uint32_t k = 0; k < rq0.divisions; k++) {
-            if (fc->owner[k] != (uint32_t)w) continue;
-            rt_tile_request rq = rq0;
-            rq.division_no = k;
-            rqs.push_back(rq);
-            outs.push_back(out_rgb + (size_t)k * strip);
-            mine.push_back(k);
-        }
-        (void)nd;
-        if (rqs.empty()) return RT_OK;
-        std::vector<unsigned long long> cost(rqs.size(), 0ull);
-        int r = rt_scene_render_tiles_impl(sc, rqs.data(), (uint32_t)rqs.size(), outs.data(), strip, nullptr, &d.st, cost.data());
-        if (r) return r;
-        for (size_t i = 0; i < mine.size(); i++) fc->cost_now[mine[i]] = cost[i];      // (disjoint entries per dispatcher)
-        return RT_OK;
-    }
-    // ---- dynamic assignment: pull one strip at a time, the bottom of the frame first (its strips cost the most:
-    // longest-first keeps the devices' finish times within one cheap strip of each other).  Two strips in flight per
-    // entry, each on its own stream with its own device buffer: the launch tail and the download of one run under
-    // the other.  Streams and buffers belong to the context: made on the first queue-mode frame, grown when a frame
-    // has larger strips.
-    DeviceCtx* ctx = sc->ctx;
-    HIPCHK(hipSetDevice(ctx->dev));
+    HIPCHK(hipSetDevice(sc->ctx->dev));
     for (int i = 0; i < 2; i++)
         if (!d.qs[i]) HIPCHK(hipStreamCreateWithFlags(&d.qs[i], hipStreamNonBlocking));
     for (int i = 0; i < 2; i++) {
@@ -2166,6 +2122,19 @@ int frame_dev_render(rt_frame_ctx* fc, int w) {
             busy[i] = false;
         }
     return rt_scene_collect_impl(sc, &d.st);
+}
+
+int frame_dev_render(rt_frame_ctx* fc, int w) {
+    FrameDev& d = fc->fd[w];
+    std::memset(&d.st, 0, sizeof d.st);
+    rt_scene* sc = d.scene;
+    if (!sc) return fail(RT_ERR_BAD_ARG, "rt_frame_ctx_render before rt_frame_ctx_set_world");
+    {
+        std::lock_guard<std::mutex> lk(sc->mu);          // the job's camera: this entry's launches of the frame read it
+        sc->pose = fc->pose;
+        sc->has_pose = fc->has_pose;
+    }
+    return fc->plan.mode == rtassign::QUEUE ? frame_dev_render_queue(fc, w) : frame_dev_render_owned(fc, w);
 }
 
 void frame_dev_release(FrameDev& d) {
@@ -2268,8 +2237,6 @@ int rt_frame_ctx_create_impl(const int* devices, int n_devices, rt_frame_ctx** o
         if (d < 0 || d >= (int)g_ctx.size()) return fail(RT_ERR_BAD_DEVICE, "bad device ordinal");
     rt_frame_ctx* fc = new rt_frame_ctx;
     fc->fd.resize(devs.size());
-    std::memset(&fc->rq, 0, sizeof fc->rq);
-    std::memset(&fc->cost_rq, 0, sizeof fc->cost_rq);
     size_t started = 0;
     try {
         for (; started < devs.size(); started++) {
@@ -2315,7 +2282,7 @@ int rt_frame_ctx_set_world_impl(rt_frame_ctx* fc, const rt_sphere* sp, uint32_t 
     rtscene::build_host_scene(sp, ns, tr, nt, world_index, dbg(DBG_REORDER) != 0, hs);
     fc->hs = &hs;
     fc->have_world = false;
-    fc->cost_valid = false;            // another world: the strips' costs are to be measured again
+    fc->costs.forget();                // another world: the strips' costs are to be measured again
     rc = frame_run(fc, rt_frame_ctx::CMD_UPLOAD);
     fc->hs = nullptr;
     if (rc) return rc;
@@ -2336,21 +2303,29 @@ int rt_frame_ctx_set_camera_impl(rt_frame_ctx* fc, const rt_camera* cam) {
     return RT_OK;
 }
 
-int rt_frame_ctx_render_impl(rt_frame_ctx* fc, const rt_tile_request* rq_in, uint8_t* out_rgb, size_t out_len,
-                             rt_frame_stats* stats) {
-    if (!fc) return fail(RT_ERR_BAD_ARG, "ctx is NULL");
+// The frame calls' arguments, in the one order both rt_render_frame and rt_frame_ctx_render report them: the request, the buffer,
+// `world` (the one-shot call's world and rt_init, before any thread or upload; nothing for a context), the tiling, the length.
+template <class WorldCheck>
+int check_frame_args(const rt_tile_request* rq_in, const uint8_t* out_rgb, size_t out_len, WorldCheck&& world) {
     if (!rq_in) return fail(RT_ERR_BAD_ARG, "request is NULL");
     rt_tile_request rq0 = *rq_in;
     rq0.division_no = 0;
     int rc = check_request(&rq0);
     if (rc) return rc;
     if (!out_rgb) return fail(RT_ERR_BAD_ARG, "out_rgb is NULL");
+    if ((rc = world())) return rc;
     // the controller's ImageBuffer::from_vec(width, height, ..).unwrap() (controller main.rs:117-119)
     // panics unless the strips tile the frame exactly
     if (rq0.height % rq0.divisions != 0) return fail(RT_ERR_FRAME_SIZE, "height % divisions != 0");
-    const size_t strip = rt_tile_bytes(&rq0);
-    const size_t frame_bytes = strip * rq0.divisions;
-    if (out_len < frame_bytes) return fail(RT_ERR_BUFFER_TOO_SMALL, "out_len < H*W*3");
+    if (out_len < rtframe::strip_bytes(rq0) * rq0.divisions) return fail(RT_ERR_BUFFER_TOO_SMALL, "out_len < H*W*3");
+    return RT_OK;
+}
+
+int rt_frame_ctx_render_impl(rt_frame_ctx* fc, const rt_tile_request* rq_in, uint8_t* out_rgb, size_t out_len,
+                             rt_frame_stats* stats) {
+    if (!fc) return fail(RT_ERR_BAD_ARG, "ctx is NULL");
+    int rc = check_frame_args(rq_in, out_rgb, out_len, [] { return RT_OK; });
+    if (rc) return rc;
     std::lock_guard<std::mutex> call(fc->call_mu);
     if (!fc->have_world) return fail(RT_ERR_BAD_ARG, "rt_frame_ctx_render before rt_frame_ctx_set_world");
     const auto t0 = std::chrono::steady_clock::now();
@@ -2358,97 +2333,30 @@ int rt_frame_ctx_render_impl(rt_frame_ctx* fc, const rt_tile_request* rq_in, uin
     // until another buffer comes (or release / destroy).  Best effort: a buffer the caller registered itself (or that
     // cannot be registered) is used as it is.
     float pin_ms = 0.f;
-    const bool want_pin = !(rq0.flags & RT_FLAG_FRAME_NO_PIN);
-    if (!want_pin || fc->pinned_ptr != (void*)out_rgb || fc->pinned_len < frame_bytes) {
-        if (fc->pinned_ptr && !(want_pin && fc->pinned_ptr == (void*)out_rgb && fc->pinned_len >= frame_bytes)) frame_unpin(fc);
-        if (want_pin) {
-            (void)hipSetDevice(fc->fd[0].dev);                 // (not device 0 by accident: the context may exclude it)
-            if (hipHostRegister(out_rgb, frame_bytes, hipHostRegisterPortable) == hipSuccess) {
-                fc->pinned_ptr = out_rgb;
-                fc->pinned_len = frame_bytes;
-            } else {
-                (void)hipGetLastError();
-            }
-            pin_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const size_t frame_bytes = rtframe::strip_bytes(*rq_in) * rq_in->divisions;
+    const rtframe::PinStep pin = rtframe::pin_step(!(rq_in->flags & RT_FLAG_FRAME_NO_PIN), fc->pinned_ptr, fc->pinned_len, out_rgb, frame_bytes);
+    if (pin.release) frame_unpin(fc);
+    if (pin.acquire) {
+        (void)hipSetDevice(fc->fd[0].dev);                 // (not device 0 by accident: the context may exclude it)
+        if (hipHostRegister(out_rgb, frame_bytes, hipHostRegisterPortable) == hipSuccess) {
+            fc->pinned_ptr = out_rgb;
+            fc->pinned_len = frame_bytes;
+        } else {
+            (void)hipGetLastError();
         }
+        pin_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
-    rq0.flags &= ~(uint32_t)(RT_FLAG_FRAME_QUEUE | RT_FLAG_FRAME_NO_PIN | RT_FLAG_FRAME_STATIC);   // frame-level: not the kernels' business
-    fc->use_queue = (rq_in->flags & RT_FLAG_FRAME_QUEUE) != 0;
-    // The balanced assignments cut the frame into their OWN strips: at least six per entry, so that longest-first has something to
-    // even out with (c5's 16 strips are two per entry at 8 devices: 3 % off the mean at best).  `divisions` is the reference's wire
-    // format, not a property of the image: every sample's stream is keyed by its pixel's place in the FRAME (rt_tile.h `seed`), so
-    // any cut into whole rows gives the same bytes.  The strip queue and RT_FLAG_FRAME_STATIC keep the request's strips.
-    size_t istrip = strip;
-    if (!fc->use_queue && !(rq_in->flags & RT_FLAG_FRAME_STATIC) && fc->fd.size() > 1) {
-        const uint32_t want = std::max<uint32_t>(rq0.divisions, 6u * (uint32_t)fc->fd.size());
-        for (uint32_t dv = want; dv <= std::min<uint32_t>(rq0.height, 4u * want); dv++)
-            if (rq0.height % dv == 0) {
-                rq0.divisions = dv;
-                istrip = rt_tile_bytes(&rq0);
-                break;
-            }
-    }
-    fc->rq = rq0;
+    // the frame's strips and which entry renders which (rt_frame_plan.h)
+    fc->plan = rtframe::plan_frame(*rq_in, (uint32_t)fc->fd.size(), fc->costs, fc->pose, fc->has_pose);
     fc->out = out_rgb;
-    fc->strip = istrip;
     fc->next_strip.store(0);
-    // which entry renders which strip (rt_assign.h).  The measured costs hold for the same world and the same frame geometry
-    // (size, strips, samples, depth, camera — its knobs and its pose —, t window): the seed changes the paths, not where the
-    // expensive rows are.
-    {
-        rt_tile_request a = rq0, b = fc->cost_rq;
-        a.seed = b.seed = 0;
-        a.division_no = b.division_no = 0;
-        a.flags = b.flags = 0;
-        const bool same_pose = fc->has_pose == fc->cost_has_pose && (!fc->has_pose || std::memcmp(&fc->pose, &fc->cost_pose, sizeof fc->pose) == 0);
-        const bool usable = fc->cost_valid && same_frame(a, b) && same_pose && fc->strip_cost.size() == rq0.divisions;
-        const rtassign::Mode mode = fc->use_queue ? rtassign::QUEUE
-                                    : (rq_in->flags & RT_FLAG_FRAME_STATIC) ? rtassign::STATIC_MOD
-                                    : usable ? rtassign::BY_COST : rtassign::SNAKE;
-        fc->assignment = (uint32_t)mode;
-        rtassign::assign(rq0.divisions, (uint32_t)fc->fd.size(), usable ? fc->strip_cost.data() : nullptr,
-                         mode == rtassign::QUEUE ? rtassign::STATIC_MOD : mode, fc->owner);
-        fc->cost_now.assign(rq0.divisions, 0ull);
-    }
+    fc->cost_now.assign(fc->plan.rq.divisions, 0ull);
     rc = frame_run(fc, rt_frame_ctx::CMD_RENDER);
     if (rc) return rc;
-    if (!fc->use_queue) {
-        // the strips' costs as this frame measured them: the next frame of the job is assigned by them
-        fc->strip_cost.assign(fc->cost_now.begin(), fc->cost_now.end());
-        fc->cost_rq = rq0;
-        fc->cost_pose = fc->pose;
-        fc->cost_has_pose = fc->has_pose;
-        // (nothing counted — RT_STRIP_COST=0, or a frame without a ray — is no measurement: the next frame is a snake frame again)
-        unsigned long long cost_sum = 0ull;
-        for (unsigned long long c : fc->cost_now) cost_sum += c;
-        fc->cost_valid = dbg(DBG_STRIP_COST) != 0 && cost_sum > 0ull;
-    }
-    rt_frame_stats fs;
-    std::memset(&fs, 0, sizeof fs);
-    rt_tile_stats& tot = fs.totals;
-    float last = -1.f;
-    for (const FrameDev& d : fc->fd) {
-        tot.ray_segments += d.st.ray_segments;
-        tot.primary_rays += d.st.primary_rays;
-        tot.broad_candidates += d.st.broad_candidates;
-        tot.exact_fallbacks += d.st.exact_fallbacks;
-        tot.node_steps += d.st.node_steps;
-        tot.kernel_ms = std::max(tot.kernel_ms, d.st.kernel_ms);   // devices run concurrently
-        tot.h2d_ms = std::max(tot.h2d_ms, d.st.h2d_ms);
-        tot.d2h_ms = std::max(tot.d2h_ms, d.st.d2h_ms);
-        tot.n_launches += d.st.n_launches;
-        if (d.st.n_launches) {
-            tot.engine = d.st.engine;
-            tot.broad_form = d.st.broad_form;
-        }
-        if (d.busy_ms > last) {                                     // the entry that finished last
-            last = d.busy_ms;
-            // strip-queue mode keeps two launches in flight per entry, so their event times overlap and do not add up
-            // to a duration: there kernel_ms is the dispatcher's wall time and nothing is booked as exposed download
-            fs.kernel_ms = fc->use_queue ? d.busy_ms : d.st.kernel_ms;
-            fs.d2h_exposed_ms = fc->use_queue ? 0.f : d.st.d2h_ms;
-        }
-    }
+    rtframe::remember_frame(fc->costs, fc->plan, fc->pose, fc->has_pose, fc->cost_now, dbg(DBG_STRIP_COST) != 0);
+    std::vector<rtframe::EntryResult> res;
+    for (const FrameDev& d : fc->fd) res.push_back({d.st, d.busy_ms});
+    rt_frame_stats fs = rtframe::fold_frame_stats(res.data(), res.size(), fc->plan.mode == rtassign::QUEUE);
     fs.wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     fs.pin_ms = pin_ms;
     fs.scene_ms = fc->scene_ms_pending;
@@ -2456,17 +2364,7 @@ int rt_frame_ctx_render_impl(rt_frame_ctx* fc, const rt_tile_request* rq_in, uin
     fs.host_ms = fs.wall_ms - fs.pin_ms - fs.kernel_ms - fs.d2h_exposed_ms;
     fs.n_devices = (uint32_t)fc->fd.size();
     fs.pinned = fc->pinned_ptr == (void*)out_rgb ? 1u : 0u;
-    fs.assignment = fc->assignment;
-    {
-        unsigned long long mx = 0, tot = 0;
-        for (size_t e = 0; e < fc->fd.size(); e++) {
-            const unsigned long long sg = fc->fd[e].st.ray_segments;
-            if (e < RT_FRAME_STATS_ENTRIES) fs.entry_segments[e] = sg;
-            mx = std::max(mx, sg);
-            tot += sg;
-        }
-        fs.balance_max_over_mean = tot ? (float)((double)mx * (double)fc->fd.size() / (double)tot) : 0.f;
-    }
+    fs.assignment = (uint32_t)fc->plan.mode;
     if (stats) *stats = fs;
     return RT_OK;
 }
@@ -2482,17 +2380,12 @@ int rt_render_frame_impl(const int* devices, int n_devices, const rt_tile_reques
                          uint32_t ns, const rt_triangle* tr, uint32_t nt, const uint32_t* world_index, uint8_t* out_rgb,
                          size_t out_len, rt_tile_stats* stats) {
     // argument errors before any thread or upload
-    if (!rq_in) return fail(RT_ERR_BAD_ARG, "request is NULL");
-    rt_tile_request rq0 = *rq_in;
-    rq0.division_no = 0;
-    int rc = check_request(&rq0);
+    int rc = check_frame_args(rq_in, out_rgb, out_len, [&] {
+        int rw = check_world(sp, ns, tr, nt, world_index);
+        if (rw) return rw;
+        return g_init ? RT_OK : fail(RT_ERR_NOT_INITIALIZED, "call rt_init() first");
+    });
     if (rc) return rc;
-    if (!out_rgb) return fail(RT_ERR_BAD_ARG, "out_rgb is NULL");
-    rc = check_world(sp, ns, tr, nt, world_index);
-    if (rc) return rc;
-    if (!g_init) return fail(RT_ERR_NOT_INITIALIZED, "call rt_init() first");
-    if (rq0.height % rq0.divisions != 0) return fail(RT_ERR_FRAME_SIZE, "height % divisions != 0");
-    if (out_len < rt_tile_bytes(&rq0) * rq0.divisions) return fail(RT_ERR_BUFFER_TOO_SMALL, "out_len < H*W*3");
     rt_frame_ctx* fc = nullptr;
     rc = rt_frame_ctx_create_impl(devices, n_devices, &fc);
     if (rc) return rc;

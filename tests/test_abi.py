@@ -234,6 +234,10 @@ def test_frame_context_lifecycle_and_error_paths():
     assert lib.rt_frame_ctx_render(None, C.byref(rq), _abi.ptr(buf), buf.size, C.byref(st)) == _abi.RT_ERR_BAD_ARG
     assert lib.rt_frame_ctx_release_buffer(None) == _abi.RT_ERR_BAD_ARG
     lib.rt_frame_ctx_destroy(None)
+    # rt_render_frame reports the frame's arguments in rt_frame_ctx_render's words, before any thread, upload or question about rt_init
+    frame = lambda r, o, n, devs=None, nd=0: lib.rt_render_frame(devs, nd, r, _abi.ptr(sph), 1, None, 0, None, o, n, None)
+    assert frame(None, _abi.ptr(buf), buf.size) == _abi.RT_ERR_BAD_ARG and lib.rt_last_error() == b"request is NULL"
+    assert frame(C.byref(rq), None, buf.size) == _abi.RT_ERR_BAD_ARG and lib.rt_last_error() == b"out_rgb is NULL"
     n = C.c_int(0)
     if lib.rt_init(C.byref(n)) != _abi.RT_OK:                    # CPU container: no context can exist
         fc = C.c_void_p()
@@ -249,10 +253,15 @@ def test_frame_context_lifecycle_and_error_paths():
     assert lib.rt_frame_ctx_set_world(fc, None, 1, None, 0, None) == _abi.RT_ERR_BAD_ARG        # count without a pointer
     assert lib.rt_frame_ctx_set_world(fc, _abi.ptr(sph), 1, None, 0, None) == _abi.RT_OK
     assert lib.rt_frame_ctx_render(fc, None, _abi.ptr(buf), buf.size, None) == _abi.RT_ERR_BAD_ARG
+    assert lib.rt_last_error() == b"request is NULL"
     assert lib.rt_frame_ctx_render(fc, C.byref(rq), None, buf.size, None) == _abi.RT_ERR_BAD_ARG
-    assert lib.rt_frame_ctx_render(fc, C.byref(rq), _abi.ptr(buf), 10, None) == _abi.RT_ERR_BUFFER_TOO_SMALL
+    assert lib.rt_last_error() == b"out_rgb is NULL"
     odd = rq.copy(); odd.divisions = 3
-    assert lib.rt_frame_ctx_render(fc, C.byref(odd), _abi.ptr(buf), buf.size, None) == _abi.RT_ERR_FRAME_SIZE
+    for render in (lambda r, n: lib.rt_frame_ctx_render(fc, C.byref(r), _abi.ptr(buf), n, None), lambda r, n: frame(C.byref(r), _abi.ptr(buf), n)):
+        assert render(rq, 10) == _abi.RT_ERR_BUFFER_TOO_SMALL and lib.rt_last_error() == b"out_len < H*W*3"
+        assert render(odd, buf.size) == _abi.RT_ERR_FRAME_SIZE and lib.rt_last_error() == b"height % divisions != 0"
+        assert render(odd, 10) == _abi.RT_ERR_FRAME_SIZE                 # the tiling before the length
+    assert frame(C.byref(rq), _abi.ptr(buf), buf.size, bad_dev, 1) == _abi.RT_ERR_BAD_DEVICE
     assert lib.rt_frame_ctx_render(fc, C.byref(rq), _abi.ptr(buf), buf.size, C.byref(st)) == _abi.RT_OK
     assert st.n_devices == 2 and st.totals.primary_rays == 64 and st.wall_ms > 0
     assert lib.rt_frame_ctx_release_buffer(fc) == _abi.RT_OK

@@ -510,7 +510,8 @@ def test_frame_context_balances_entries_by_measured_strip_cost(ndev, oracle):
     want, _, info = oracle.render(one, sph, backend=1)
     with rt.FrameContext(devices=[0] * 8, world=rt.World(sph)) as fc:
         seen = {}
-        for name, fl in (("static", _abi.RT_FLAG_FRAME_STATIC), ("first", 0), ("second", 0), ("third", 0), ("static2", _abi.RT_FLAG_FRAME_STATIC)):
+        for name, fl in (("static", _abi.RT_FLAG_FRAME_STATIC), ("first", 0), ("second", 0), ("third", 0), ("queue", _abi.RT_FLAG_FRAME_QUEUE),
+                         ("fourth", 0), ("static2", _abi.RT_FLAG_FRAME_STATIC)):
             r = rq.copy()
             r.flags = fl
             img, fs = fc.render(r)
@@ -523,7 +524,9 @@ def test_frame_context_balances_entries_by_measured_strip_cost(ndev, oracle):
         # per entry, so the first default frame is a snake frame and measures those)
         assert seen["static"][0] == 0 and seen["static2"][0] == 0
         assert seen["first"][0] == 1 and seen["second"][0] == 2 and seen["third"][0] == 2
-        # (tiny strips here — 8 rows, 5 tiles — and four of them per entry: bench.py reports the balance of c4 / c5 at full size)
+        # a strip-queue frame measures nothing per strip and leaves the measured costs as they were
+        assert seen["queue"][0] == 3 and seen["fourth"][0] == 2
+        # (tiny strips here — the context's own cut, 64 strips of 4 rows, 5 tiles each — and eight of them per entry: bench.py reports the balance of c4 / c5 at full size)
         assert seen["second"][1] < seen["static"][1] and seen["second"][1] < 1.05, seen
         # another world: costs are forgotten, the next frame is a snake frame again
         sph2 = scenes.cornell16()
