@@ -4,6 +4,7 @@
 // take a RenderInfo, produce the strip's RGB8 bytes) and, in rt_render_frame, to the
 // controller's dispatch + assembly (ray-tracer-controller/src/main.rs:47-75, 109-115).
 // No torch types, no CPU fallback: without a HIP device every entry point fails loudly.
+// Device memory, events and streams are held by the owners of rt_device.h: nothing here frees or destroys one by hand.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
@@ -17,6 +18,7 @@
 #include <atomic>
 #include <climits>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <stdexcept>
@@ -26,6 +28,7 @@
 
 #include "rt_assign.h"
 #include "rt_bvh.h"
+#include "rt_device.h"
 #include "rt_frame_plan.h"
 #include "rt_kernel.hip.h"
 #include "rt_plan.h"
@@ -86,33 +89,23 @@ int guarded(F&& body) noexcept {
                                         std::to_string(__LINE__) + ")");                              \
     } while (0)
 
-// A device staging buffer that grows on demand and never shrinks.  Its owner has the device current and no work in flight on the
-// old area when it grows.
-struct DevBuf {
-    char* d = nullptr;
-    size_t cap = 0;   // bytes
-    int reserve(size_t bytes, const char* what) {
-        if (cap >= bytes) return RT_OK;
-        release();
-        if (hipMalloc(&d, bytes) != hipSuccess) {
-            d = nullptr;
-            (void)hipGetLastError();   // (the failure is reported here: it must not stick to the next HIP call)
-            return fail(RT_ERR_OOM, std::string("hipMalloc(") + what + ") failed");
-        }
-        cap = bytes;
-        return RT_OK;
-    }
-    void release() {
-        (void)hipFree(d);
-        d = nullptr;
-        cap = 0;
-    }
-};
+using rtdev::DevArray;
+using rtdev::Event;
+using rtdev::EventPool;
+using rtdev::GrowBuf;
+using rtdev::Stream;
+
+// A staging buffer grown to at least `bytes`.  Its owner has the device current and no work in flight on the old area.
+int reserve(GrowBuf& buf, size_t bytes, const char* what) {
+    if (buf.grow(bytes) == hipSuccess) return RT_OK;
+    (void)hipGetLastError();   // (the failure is reported here: it must not stick to the next HIP call)
+    return fail(RT_ERR_OOM, std::string("hipMalloc(") + what + ") failed");
+}
 
 struct DeviceCtx {
     int dev = -1;
-    hipStream_t stream = nullptr;
-    hipStream_t copy_stream = nullptr;   // D2H of finished strips while the next launch of the batch runs
+    Stream stream;
+    Stream copy_stream;   // D2H of finished strips while the next launch of the batch runs
     int n_cu = 0;
     std::mutex mu;   // serialises synchronous calls on one device
 };
@@ -180,13 +173,15 @@ rtplan::Knobs plan_knobs() {
 
 }  // namespace
 
+// Its device resources are owners of rt_device.h, released by the (implicit) destructor: ctx->dev MUST be current on the thread that
+// deletes a scene, a frame context's dispatcher included.  Only rt_scene_destroy_impl deletes one, and it sets the device first.
 struct rt_scene {
     DeviceCtx* ctx = nullptr;
     rtplan::SceneShape shape;       // what the engine rules read (rt_plan.h)
     uint32_t n_lights = 0;          // direct lighting: the emitters of the scene (rt_scene_light_count)
-    uint32_t* d_lights = nullptr;   //   their primitive numbers in ascending world position (rtscene::emitter_list)
-    float* d_light_c = nullptr;     // RT_FLAG_LIGHTS_BY_POWER (rtscene::light_table): the running sums of the powers, per emitter
-    float* d_light_ip = nullptr;    //   1 / p of an emitter, by primitive number
+    DevArray<uint32_t> d_lights;    //   their primitive numbers in ascending world position (rtscene::emitter_list)
+    DevArray<float> d_light_c;      // RT_FLAG_LIGHTS_BY_POWER (rtscene::light_table): the running sums of the powers, per emitter
+    DevArray<float> d_light_ip;     //   1 / p of an emitter, by primitive number
     float light_total = 0.f;        //   the last running sum
     std::vector<uint32_t> light_world;   // rt_scene_light_table: the world position and the mixture probability of every emitter
     std::vector<float> light_p;
@@ -196,52 +191,48 @@ struct rt_scene {
                                                 //   or NEE call is enqueued, where it picks the kernel instance
     uint32_t glossy_sampling = RT_GLOSSY_BOUNCE;   // whether RT_NEE_MIS takes light samples at glossy hits (rt_scene_set_glossy_sampling);
                                                    //   read when an NEE call is enqueued, where it picks the kernel instance
-    float4* d_geom = nullptr;
-    float4* d_geom_pk = nullptr;
-    float4* d_geom_px = nullptr;   // expanded-form broad phase records
-    float4* d_mat = nullptr;
-    float* d_emis = nullptr;
-    float* d_tri = nullptr;
-    float4* d_tri_box = nullptr;
-    float4* d_bvh = nullptr;       // rtbvh::FlatNode[]
-    float4* d_trav = nullptr;      // rtbvh::TravNode[]
-    uint32_t* d_stack_ovf = nullptr;   // quantised-node kernel: stack entries beyond the LDS part, [entry][thread]
-    size_t stack_ovf_words = 0;
-    hipEvent_t ovf_done = nullptr;     // end of the last launch that used d_stack_ovf: the area is one per scene, so such
-                                       // launches are chained even when the caller spreads them over several streams
-    uint4* d_travq = nullptr;      // rtbvh::QNode[] (quantised twin)
-    float4* d_geom_r = nullptr;    // (cx,cy,cz,radius)
-    uint32_t* d_big = nullptr;     // culled walk: spheres root-tested at query start (too large for its slack)
+    DevArray<float4> d_geom;
+    DevArray<float4> d_geom_pk;
+    DevArray<float4> d_geom_px;    // expanded-form broad phase records
+    DevArray<float4> d_mat;
+    DevArray<float> d_emis;
+    DevArray<float> d_tri;
+    DevArray<float4> d_tri_box;
+    DevArray<float4> d_bvh;        // rtbvh::FlatNode[]
+    DevArray<float4> d_trav;       // rtbvh::TravNode[]
+    GrowBuf stack_ovf;             // quantised-node kernel: stack entries (uint32_t) beyond the LDS part, [entry][thread].  Its `done` is
+                                   // the end of the last launch that used it: the area is one per scene, so such launches are
+                                   // chained even when the caller spreads them over several streams
+    DevArray<uint4> d_travq;       // rtbvh::QNode[] (quantised twin)
+    DevArray<float4> d_geom_r;     // (cx,cy,cz,radius)
+    DevArray<uint32_t> d_big;      // culled walk: spheres root-tested at query start (too large for its slack)
     uint32_t n_big = 0;
     float tri_k = 0.f, tri_diag = 0.f, tri_es = 0.f, tri_e = 0.f;   // culled walk over the exact nodes: maxima over the triangles not in `big`
     rtbvh::QGrid grid;
-    uint32_t* d_leaf_of = nullptr;
-    uint32_t* d_world_rank = nullptr;   // world_index of every primitive when the caller gave one (rt_tile.h "the world's order")
+    DevArray<uint32_t> d_leaf_of;
+    DevArray<uint32_t> d_world_rank;    // world_index of every primitive when the caller gave one (rt_tile.h "the world's order")
     bool has_order = false;
     float bvh_build_ms = 0.f;
-    unsigned long long* d_counters = nullptr;   // [0..2] stats, [4 + slot] tile queues
+    DevArray<unsigned long long> d_counters;    // [0..2] stats, [4 + slot] tile queues
     // Sample-unit rings (rt_kernel.hip.h "Sample units"): scratch of one launch, [waves][slots][16 B].  Launches on ONE stream
     // follow each other, so a ring belongs to the stream that used it last; a launch on another stream that has to share it
-    // (more streams than rings) waits for that launch's end first.
+    // (more streams than rings) waits for that launch's end (the area's `done`) first.
     struct Ring {
-        float* d = nullptr;
-        size_t bytes = 0;
+        GrowBuf buf;
         hipStream_t last = nullptr;
-        hipEvent_t done = nullptr;          // end of the last launch that used it
         uint64_t stamp = 0;
     };
     Ring rings[4];
     uint64_t ring_clock = 0;
     // staging of the tile host form (grown on demand): the strips' bytes, their f32 twins, the running sums of
     // rt_scene_render_tile_pass and the per-strip ray segments of the batched call (frame context)
-    DevBuf d_out, d_outf, d_acc, d_cost;
+    GrowBuf d_out, d_outf, d_acc, d_cost;
     // ... and ONE buffer for the arrays of the eight other host forms (rt_scene_intersect, _trace, _bounce, _direct, _trace_nee,
     // _render_aov, _camera_rays, _denoise; Staging).  They can share it: every such call holds ctx->mu and sc->mu from start to end,
     // begins by collecting everything pending, and waits for its own downloads before it returns, so no two of them are ever in
-    // flight; and DevBuf::reserve frees (hipFree) only when it grows, which is before the call has enqueued anything.
-    DevBuf d_stage;
-    // HIP-event bookkeeping of launches not yet collected
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, free_ev;
+    // flight; and GrowBuf::grow frees only when it grows, which is before the call has enqueued anything.
+    GrowBuf d_stage;
+    EventPool events;   // the pairs of events that time the launches; its pending list is the launches not yet collected
     uint64_t primary_rays = 0;
     float h2d_ms = 0.f;
     uint32_t last_engine = 0, last_form = 0;
@@ -263,22 +254,6 @@ int check_request(const rt_tile_request* rq) {
     return RT_OK;
 }
 
-struct EvPair {
-    hipEvent_t a, b;
-};
-
-int get_events(rt_scene* sc, EvPair& ev) {
-    if (!sc->free_ev.empty()) {
-        ev.a = sc->free_ev.back().first;
-        ev.b = sc->free_ev.back().second;
-        sc->free_ev.pop_back();
-        return RT_OK;
-    }
-    HIPCHK(hipEventCreate(&ev.a));
-    HIPCHK(hipEventCreate(&ev.b));
-    return RT_OK;
-}
-
 constexpr uint32_t QUEUE_SLOTS = 16384;          // uncollected launches per scene (one 8-byte queue head each)
 #ifdef RT_PROFILE_TIME
 constexpr uint32_t COUNTER_WORDS = 4 + QUEUE_SLOTS + 16 * 8192;      // (+ one block per wave: the phase clock, tools/phase_time.py)
@@ -287,7 +262,7 @@ constexpr uint32_t COUNTER_WORDS = 4 + QUEUE_SLOTS;
 #endif
 
 int check_slot(const rt_scene* sc) {
-    if (sc->pending.size() >= QUEUE_SLOTS) return fail(RT_ERR_LIMIT, "too many uncollected launches: call rt_scene_collect()");
+    if (sc->events.pending().size() >= QUEUE_SLOTS) return fail(RT_ERR_LIMIT, "too many uncollected launches: call rt_scene_collect()");
     return RT_OK;
 }
 
@@ -295,14 +270,15 @@ int check_slot(const rt_scene* sc) {
 // here.  Caller holds sc->mu and has the device current.
 template <class P>
 int enqueue(rt_scene* sc, hipStream_t stream, void (*kern)(const P), uint32_t blocks, uint32_t block, size_t lds, const P& p) {
-    EvPair ev;
-    int rc;
-    if ((rc = check_slot(sc)) || (rc = get_events(sc, ev))) return rc;
-    HIPCHK(hipEventRecord(ev.a, stream));
+    EventPool::Lease ev;
+    int rc = check_slot(sc);
+    if (rc) return rc;
+    HIPCHK(sc->events.lease(ev));
+    HIPCHK(hipEventRecord(ev.a(), stream));
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(block), lds, stream, p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev.b, stream));
-    sc->pending.push_back({ev.a, ev.b});
+    HIPCHK(hipEventRecord(ev.b(), stream));
+    ev.to_pending();
     return RT_OK;
 }
 
@@ -326,13 +302,13 @@ void scene_refs(const rt_scene* sc, bool full_chain, rtk::SceneRefs& r) {
     r.n_tri = sc->shape.n_tri;
     r.root_ref = sc->shape.root_ref;
     r.full_chain = full_chain ? 1u : 0u;
-    r.trav = sc->d_trav;
-    r.bvh_nodes = sc->d_bvh;
-    r.leaf_of = sc->d_leaf_of;
-    r.world_rank = sc->has_order ? sc->d_world_rank : nullptr;
-    r.geom_r = sc->d_geom_r;
-    r.tri = sc->d_tri;
-    r.counters = sc->d_counters;
+    r.trav = sc->d_trav.get();
+    r.bvh_nodes = sc->d_bvh.get();
+    r.leaf_of = sc->d_leaf_of.get();
+    r.world_rank = sc->has_order ? sc->d_world_rank.get() : nullptr;
+    r.geom_r = sc->d_geom_r.get();
+    r.tri = sc->d_tri.get();
+    r.counters = sc->d_counters.get();
 }
 
 // Enqueue a batch of strips of one frame (<= MAX_BATCH) as ONE launch of persistent waves.
@@ -347,16 +323,7 @@ struct Pass {
 };
 // The scene's stack-overflow area of the capped-stack kernels, grown to at least `words`.
 int acquire_stack_ovf(rt_scene* sc, size_t words) {
-    if (words > sc->stack_ovf_words) {
-        if (sc->d_stack_ovf) {
-            if (sc->ovf_done) HIPCHK(hipEventSynchronize(sc->ovf_done));   // a launch in flight may still use the old area
-            (void)hipFree(sc->d_stack_ovf);
-            sc->d_stack_ovf = nullptr;
-            sc->stack_ovf_words = 0;
-        }
-        HIPCHK(hipMalloc(&sc->d_stack_ovf, words * sizeof(uint32_t)));
-        sc->stack_ovf_words = words;
-    }
+    HIPCHK(sc->stack_ovf.grow(words * sizeof(uint32_t)));
     return RT_OK;
 }
 
@@ -365,27 +332,18 @@ int acquire_stack_ovf(rt_scene* sc, size_t words) {
 int acquire_ring(rt_scene* sc, hipStream_t stream, size_t bytes, rt_scene::Ring*& rg) {
     rg = nullptr;
     for (auto& r : sc->rings)
-        if (r.d && r.last == stream) { rg = &r; break; }
+        if (r.buf.data() && r.last == stream) { rg = &r; break; }
     if (!rg)
         for (auto& r : sc->rings)
-            if (!r.d) { rg = &r; break; }
+            if (!r.buf.data()) { rg = &r; break; }
     if (!rg) {
         rg = &sc->rings[0];
         for (auto& r : sc->rings)
             if (r.stamp < rg->stamp) rg = &r;
     }
-    if (rg->bytes < bytes) {
-        if (rg->d) {
-            if (rg->done) HIPCHK(hipEventSynchronize(rg->done));     // a launch in flight may still use the old area
-            (void)hipFree(rg->d);
-            rg->d = nullptr;
-            rg->bytes = 0;
-        }
-        HIPCHK(hipMalloc(&rg->d, bytes));
-        rg->bytes = bytes;
-    }
-    if (!rg->done) HIPCHK(hipEventCreateWithFlags(&rg->done, hipEventDisableTiming));
-    else if (rg->last != stream) HIPCHK(hipStreamWaitEvent(stream, rg->done, 0));
+    HIPCHK(rg->buf.grow(bytes));
+    if (!rg->buf.done) HIPCHK(rg->buf.done.create(hipEventDisableTiming));
+    else if (rg->last != stream) HIPCHK(hipStreamWaitEvent(stream, rg->buf.done.get(), 0));
     rg->last = stream;
     rg->stamp = ++sc->ring_clock;
     return RT_OK;
@@ -400,25 +358,25 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
     const rtplan::SampleRange smp = pass ? rtplan::SampleRange{pass->begin, pass->end, true} : rtplan::SampleRange{0u, rqs[0].spp, false};
     rtplan::Plan pl = rtplan::plan_launch(sh, rqs[0], n, smp, kn, p, sc->has_pose ? &sc->pose : nullptr);
     if (pl.status != RT_OK) return fail(pl.status, pl.error);
-    p.geom_pk = sc->d_geom_pk;
-    p.geom_px = sc->d_geom_px;
-    p.geom = sc->d_geom;
-    p.mat = sc->d_mat;
-    p.emis = sc->d_emis;
-    p.tri = sc->d_tri;
-    p.tri_box = sc->d_tri_box;
-    p.bvh_nodes = sc->d_bvh;
-    p.trav = sc->d_trav;
-    p.travq = sc->d_travq;
-    p.geom_r = sc->d_geom_r;
+    p.geom_pk = sc->d_geom_pk.get();
+    p.geom_px = sc->d_geom_px.get();
+    p.geom = sc->d_geom.get();
+    p.mat = sc->d_mat.get();
+    p.emis = sc->d_emis.get();
+    p.tri = sc->d_tri.get();
+    p.tri_box = sc->d_tri_box.get();
+    p.bvh_nodes = sc->d_bvh.get();
+    p.trav = sc->d_trav.get();
+    p.travq = sc->d_travq.get();
+    p.geom_r = sc->d_geom_r.get();
     for (int i = 0; i < 3; i++) {
         p.q_base[i] = sc->grid.base[i];
         p.q_step[i] = sc->grid.step[i];
         p.q_rstep[i] = 1.0f / sc->grid.step[i];
     }
-    p.leaf_of = sc->d_leaf_of;
-    p.world_rank = sc->has_order ? sc->d_world_rank : nullptr;
-    p.big = sc->d_big;
+    p.leaf_of = sc->d_leaf_of.get();
+    p.world_rank = sc->has_order ? sc->d_world_rank.get() : nullptr;
+    p.big = sc->d_big.get();
     p.n_big = sc->n_big;
     p.r_slack = sh.r_slack;
     p.tri_k = sc->tri_k;
@@ -434,8 +392,8 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
     }
     int rc = check_slot(sc);               // (here already: the slot is the launch's queue head)
     if (rc) return rc;
-    p.counters = sc->d_counters;
-    p.queue = sc->d_counters + 4 + sc->pending.size();
+    p.counters = sc->d_counters.get();
+    p.queue = sc->d_counters.get() + 4 + sc->events.pending().size();
     p.strip_cost = dbg(DBG_STRIP_COST) ? d_strip_cost : nullptr;
 
     // persistent grid: as many workgroups as the chip holds at this LDS/VGPR budget
@@ -450,24 +408,24 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
     p.stack_ovf = nullptr;
     if (pl.capped) {
         if ((rc = acquire_stack_ovf(sc, pl.ovf_words))) return rc;
-        p.stack_ovf = sc->d_stack_ovf;
+        p.stack_ovf = (uint32_t*)sc->stack_ovf.data();
     }
     if (dbg(DBG_VERBOSE))
         fprintf(stderr, "[rt] sample-unit ring %zu B: %u units per pixel, %u slots of %u records per wave\n", pl.ring_bytes, p.upp, p.n_slots,
                 p.slot_stride);
     rt_scene::Ring* rg = nullptr;
     if ((rc = acquire_ring(sc, stream, pl.ring_bytes, rg))) return rc;
-    p.ring = rg->d;
+    p.ring = (float*)rg->buf.data();
     if (p.stack_ovf) {
-        if (sc->ovf_done) HIPCHK(hipStreamWaitEvent(stream, sc->ovf_done, 0));
-        else HIPCHK(hipEventCreateWithFlags(&sc->ovf_done, hipEventDisableTiming));
+        if (sc->stack_ovf.done) HIPCHK(hipStreamWaitEvent(stream, sc->stack_ovf.done.get(), 0));
+        else HIPCHK(sc->stack_ovf.done.create(hipEventDisableTiming));
     }
     HIPCHK(hipMemsetAsync(p.queue, 0, sizeof(unsigned long long), stream));
     sc->last_engine = (uint32_t)pl.engine;
     sc->last_form = pl.expanded ? 1u : 0u;
     if ((rc = enqueue(sc, stream, kern, pl.blocks, pl.block, pl.lds, p))) return rc;
-    HIPCHK(hipEventRecord(rg->done, stream));
-    if (p.stack_ovf) HIPCHK(hipEventRecord(sc->ovf_done, stream));
+    HIPCHK(hipEventRecord(rg->buf.done.get(), stream));
+    if (p.stack_ovf) HIPCHK(hipEventRecord(sc->stack_ovf.done.get(), stream));
     sc->primary_rays += (uint64_t)p.Hs * p.W * p.upp * n;
     return RT_OK;
 }
@@ -475,18 +433,17 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
 int collect_locked(rt_scene* sc, rt_tile_stats* st) {
     float ms = 0.f;
     uint32_t n = 0;
-    for (auto& pr : sc->pending) {
-        HIPCHK(hipEventSynchronize(pr.second));
+    for (const EventPool::Pair& pr : sc->events.pending()) {
+        HIPCHK(hipEventSynchronize(pr.b));
         float t = 0.f;
-        HIPCHK(hipEventElapsedTime(&t, pr.first, pr.second));
+        HIPCHK(hipEventElapsedTime(&t, pr.a, pr.b));
         ms += t;
         n++;
-        sc->free_ev.push_back(pr);
     }
-    sc->pending.clear();
+    sc->events.collected();
     unsigned long long c[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpy(c, sc->d_counters, sizeof c, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemset(sc->d_counters, 0, sizeof c));
+    HIPCHK(hipMemcpy(c, sc->d_counters.get(), sizeof c, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemset(sc->d_counters.get(), 0, sizeof c));
     if (st) {
         st->ray_segments = c[0];
         st->broad_candidates = c[1];
@@ -508,46 +465,46 @@ int collect_locked(rt_scene* sc, rt_tile_stats* st) {
 // The skeleton of a synchronous host-buffer call on the scene's stream: uploads, the call's launches, downloads, each phase
 // timed; the stats are the call's own.  Made under sc->ctx->mu and sc->mu with the device current.  The entry point checks its
 // arguments and reserves its staging, then: begin(), upload, uploads_done(), launch_*, kernels_done(), download, finish().
-// However it returns, the events go back to the scene, the scene's upload time stays for the next tile call, and an error return
+// However it returns, the leased events go back to the scene's pool, the scene's upload time stays for the next tile call, and an error return
 // waits for the stream: what is already enqueued writes into caller memory.
 struct StagedCall {
     rt_scene* const sc;
     const hipStream_t st;
     const float scene_h2d_ms;
-    EvPair up{nullptr, nullptr}, down{nullptr, nullptr};
+    EventPool::Lease up, down;
     bool finished = false;
-    explicit StagedCall(rt_scene* s) : sc(s), st(s->ctx->stream), scene_h2d_ms(s->h2d_ms) {}
+    explicit StagedCall(rt_scene* s) : sc(s), st(s->ctx->stream.get()), scene_h2d_ms(s->h2d_ms) {}
     StagedCall(const StagedCall&) = delete;
     ~StagedCall() {
         if (!finished) (void)hipStreamSynchronize(st);
-        if (up.b) sc->free_ev.push_back({up.a, up.b});
-        if (down.b) sc->free_ev.push_back({down.a, down.b});
         sc->h2d_ms = scene_h2d_ms;
     }
     // settles anything enqueued earlier; the upload phase begins
     int begin() {
-        int rc;
-        if ((rc = collect_locked(sc, nullptr)) || (rc = get_events(sc, up)) || (rc = get_events(sc, down))) return rc;
-        HIPCHK(hipEventRecord(up.a, st));
+        int rc = collect_locked(sc, nullptr);
+        if (rc) return rc;
+        HIPCHK(sc->events.lease(up));
+        HIPCHK(sc->events.lease(down));
+        HIPCHK(hipEventRecord(up.a(), st));
         return RT_OK;
     }
     int uploads_done() {
-        HIPCHK(hipEventRecord(up.b, st));
+        HIPCHK(hipEventRecord(up.b(), st));
         return RT_OK;
     }
     int kernels_done() {
-        HIPCHK(hipEventRecord(down.a, st));
+        HIPCHK(hipEventRecord(down.a(), st));
         return RT_OK;
     }
     // waits for the downloads; *stats (optional): the call's launches, with its upload and download times
     int finish(rt_tile_stats* stats) {
-        HIPCHK(hipEventRecord(down.b, st));
-        HIPCHK(hipEventSynchronize(down.b));
+        HIPCHK(hipEventRecord(down.b(), st));
+        HIPCHK(hipEventSynchronize(down.b()));
         finished = true;
         rt_tile_stats s;
         float h2d = 0.f, d2h = 0.f;
-        HIPCHK(hipEventElapsedTime(&h2d, up.a, up.b));
-        HIPCHK(hipEventElapsedTime(&d2h, down.a, down.b));
+        HIPCHK(hipEventElapsedTime(&h2d, up.a(), up.b()));
+        HIPCHK(hipEventElapsedTime(&d2h, down.a(), down.b()));
         int rc = collect_locked(sc, &s);
         if (rc) return rc;
         s.h2d_ms = h2d;
@@ -573,15 +530,15 @@ __attribute__((format(printf, 1, 2))) std::string vtext(const char* fmt, ...) {
 // The scene's materials, and its emitter list, into a parameter block that has the fields.
 template <class P>
 void material_refs(const rt_scene* sc, P& p) {
-    p.mat = sc->d_mat;
-    p.emis = sc->d_emis;
+    p.mat = sc->d_mat.get();
+    p.emis = sc->d_emis.get();
 }
 template <class P>
 void light_refs(const rt_scene* sc, P& p) {
-    p.lights = sc->d_lights;
+    p.lights = sc->d_lights.get();
     p.n_lights = sc->n_lights;
-    p.table.light_c = sc->d_light_c;
-    p.table.light_ip = sc->d_light_ip;
+    p.table.light_c = sc->d_light_c.get();
+    p.table.light_ip = sc->d_light_ip.get();
     p.table.light_total = sc->light_total;
 }
 
@@ -641,7 +598,7 @@ template <class L>
 int device_form(rt_scene* sc, void* hip_stream, L&& launch) {
     std::lock_guard<std::mutex> lk(sc->mu);
     HIPCHK(hipSetDevice(sc->ctx->dev));
-    return launch(hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream);
+    return launch(hip_stream ? (hipStream_t)hip_stream : sc->ctx->stream.get());
 }
 
 // The prologue of a host form: the device's lock and the scene's for the length of the call, and the device made current.
@@ -661,12 +618,12 @@ struct HostForm {
 struct Staging {
     enum : unsigned { UP = rtplan::STAGE_UP, DOWN = rtplan::STAGE_DOWN, DEVICE = rtplan::STAGE_DEVICE };
     using Entry = rtplan::StageEntry;     // {host, bytes, copy}
-    DevBuf& buf;
+    GrowBuf& buf;
     std::vector<Entry> e;
     const size_t total;
     Staging(rt_scene* sc, std::vector<Entry> entries) : buf(sc->d_stage), e(std::move(entries)), total(rtplan::stage_layout(e.data(), e.size())) {}
-    int reserve(const char* what) { return buf.reserve(total, what); }
-    char* dev(size_t k) const { return e[k].present() ? buf.d + e[k].off : nullptr; }    // (after reserve)
+    int reserve(const char* what) { return ::reserve(buf, total, what); }
+    char* dev(size_t k) const { return e[k].present() ? buf.data() + e[k].off : nullptr; }    // (after reserve)
     // the upload phase of `call`, and its download phase up to finish()
     int upload(StagedCall& call) const {
         for (int k = 0; k < (int)e.size(); k++)
@@ -776,11 +733,11 @@ static int ensure_ctx(DeviceCtx* c) {
         for (int alt = 0; alt < 2; alt++)     // the expanded broad phase (ISECT 0, 1) / the node-visit counting twin (ISECT 2 ... 9)
             HIPCHK(hipFuncSetAttribute((const void*)(isect < 2 ? rtk::kernel_linear(isect, alt != 0) : rtk::kernel_traverse(isect, alt != 0)),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)rtplan::LDS_LIMIT));
-    hipStream_t st = nullptr, cs = nullptr;
-    HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-    c->copy_stream = cs;
-    c->stream = st;
+    Stream st, cs;                        // (both or neither: the context counts as made by its `stream`)
+    HIPCHK(st.create(hipStreamNonBlocking));
+    HIPCHK(cs.create(hipStreamNonBlocking));
+    c->copy_stream = std::move(cs);
+    c->stream = std::move(st);
     return RT_OK;
 }
 
@@ -789,9 +746,7 @@ static int rt_shutdown_impl(void) {
     if (g_live_scenes.load() > 0)
         return fail(RT_ERR_BAD_ARG, "rt_shutdown() refused: destroy every rt_scene first (their device contexts stay valid)");
     for (DeviceCtx* c : g_ctx) {
-        (void)hipSetDevice(c->dev);
-        if (c->stream) (void)hipStreamDestroy(c->stream);
-        if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
+        (void)hipSetDevice(c->dev);      // (its streams go with it)
         delete c;
     }
     g_ctx.clear();
@@ -824,62 +779,19 @@ static int upload_scene(int device, const HostScene& hs, rt_scene** out) {
         if (rc0) return rc0;
     }
     HIPCHK(hipSetDevice(ctx->dev));
-    rt_scene* sc = new (std::nothrow) rt_scene;
+    struct Destroy {
+        void operator()(rt_scene* s) const { rt_scene_destroy_impl(s); }
+    };
+    std::unique_ptr<rt_scene, Destroy> sc(new (std::nothrow) rt_scene);      // an error return or an exception below releases everything made so far
     if (!sc) return fail(RT_ERR_OOM, "host allocation failed");
-    g_live_scenes.fetch_add(1);            // (rt_scene_destroy_impl, also on the error paths below, takes it back)
-    struct SceneGuard {                    // an error return or an exception below releases everything made so far
-        rt_scene* sc;
-        ~SceneGuard() {
-            if (sc) rt_scene_destroy_impl(sc);
-        }
-    } guard{sc};
+    g_live_scenes.fetch_add(1);            // (rt_scene_destroy_impl takes it back)
     const rtbvh::FlatBVH& bvh = hs.bvh;
     sc->ctx = ctx;
     sc->shape = hs.shape;
     sc->bvh_build_ms = hs.bvh_build_ms;
     sc->grid = bvh.grid;
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess) return fail(RT_ERR_HIP, "hipEventCreate failed");
-    if (hipEventCreate(&e1) != hipSuccess) {
-        (void)hipEventDestroy(e0);
-        return fail(RT_ERR_HIP, "hipEventCreate failed");
-    }
-#define SC_CHK(expr)                                                                      \
-    do {                                                                                  \
-        hipError_t _e = (expr);                                                           \
-        if (_e != hipSuccess) {                                                           \
-            (void)hipEventDestroy(e0);                                                    \
-            (void)hipEventDestroy(e1);                                                    \
-            return fail(_e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP,              \
-                        std::string(#expr) + ": " + hipGetErrorString(_e));               \
-        }                                                                                 \
-    } while (0)
-#define SC_UP(dst, vec)                                                                                       \
-    do {                                                                                                      \
-        SC_CHK(hipMalloc(&sc->dst, (vec).size() * sizeof((vec)[0])));                                         \
-        SC_CHK(hipMemcpyAsync(sc->dst, (vec).data(), (vec).size() * sizeof((vec)[0]), hipMemcpyHostToDevice,  \
-                              ctx->stream));                                                                  \
-    } while (0)
-    SC_CHK(hipEventRecord(e0, ctx->stream));
-    SC_UP(d_geom, hs.geom);
-    SC_UP(d_geom_pk, hs.geom_pk);
-    SC_UP(d_geom_px, hs.geom_px);
-    SC_UP(d_mat, hs.mat);
-    SC_UP(d_emis, hs.emis);
-    SC_UP(d_tri, hs.tri);
-    SC_UP(d_tri_box, hs.tri_box);
-    SC_UP(d_bvh, bvh.nodes);
-    SC_UP(d_leaf_of, bvh.leaf_of);
-    SC_UP(d_world_rank, hs.world_rank);
     sc->has_order = hs.has_order;
-    SC_UP(d_trav, bvh.trav);
-    SC_UP(d_travq, bvh.travq);
-    SC_UP(d_geom_r, hs.geom_r);
-    SC_UP(d_big, hs.big);
-    SC_UP(d_lights, hs.lights);
     sc->n_lights = hs.n_lights;
-    SC_UP(d_light_c, hs.light_c);
-    SC_UP(d_light_ip, hs.light_ip_prim);
     sc->light_total = hs.light_total;
     sc->light_p.assign(hs.light_p.begin(), hs.light_p.begin() + hs.n_lights);
     sc->light_world.resize(hs.n_lights);
@@ -889,21 +801,47 @@ static int upload_scene(int device, const HostScene& hs, rt_scene** out) {
     sc->tri_diag = hs.tri_diag;
     sc->tri_es = hs.tri_es;
     sc->tri_e = hs.tri_e;
-    SC_CHK(hipMalloc(&sc->d_counters, COUNTER_WORDS * sizeof(unsigned long long)));
-    SC_CHK(hipMemsetAsync(sc->d_counters, 0, COUNTER_WORDS * sizeof(unsigned long long), ctx->stream));
-    SC_CHK(hipEventRecord(e1, ctx->stream));
-    SC_CHK(hipEventSynchronize(e1));
-    SC_CHK(hipEventElapsedTime(&sc->h2d_ms, e0, e1));
-#undef SC_UP
-#undef SC_CHK
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    const hipStream_t st = ctx->stream.get();
+    Event e0, e1;
+    if (e0.create() != hipSuccess || e1.create() != hipSuccess) return fail(RT_ERR_HIP, "hipEventCreate failed");
+    // The steps of the upload, in order; after the first that fails the rest are skipped.  Out of memory is its own status, and the
+    // text names the array or the call.
+    int rc = RT_OK;
+    auto step = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string("scene upload, ") + what + ": " + hipGetErrorString(e));
+    };
+    auto up = [&](auto& dst, const auto& vec, const char* what) {
+        if (!rc) step(dst.upload(vec, st), what);
+    };
+    step(hipEventRecord(e0.get(), st), "hipEventRecord");
+    up(sc->d_geom, hs.geom, "geom");
+    up(sc->d_geom_pk, hs.geom_pk, "geom_pk");
+    up(sc->d_geom_px, hs.geom_px, "geom_px");
+    up(sc->d_mat, hs.mat, "mat");
+    up(sc->d_emis, hs.emis, "emis");
+    up(sc->d_tri, hs.tri, "tri");
+    up(sc->d_tri_box, hs.tri_box, "tri_box");
+    up(sc->d_bvh, bvh.nodes, "bvh nodes");
+    up(sc->d_leaf_of, bvh.leaf_of, "leaf_of");
+    up(sc->d_world_rank, hs.world_rank, "world_rank");
+    up(sc->d_trav, bvh.trav, "trav");
+    up(sc->d_travq, bvh.travq, "travq");
+    up(sc->d_geom_r, hs.geom_r, "geom_r");
+    up(sc->d_big, hs.big, "big");
+    up(sc->d_lights, hs.lights, "lights");
+    up(sc->d_light_c, hs.light_c, "light_c");
+    up(sc->d_light_ip, hs.light_ip_prim, "light_ip");
+    if (!rc) step(sc->d_counters.alloc(COUNTER_WORDS), "counters");
+    if (!rc) step(hipMemsetAsync(sc->d_counters.get(), 0, COUNTER_WORDS * sizeof(unsigned long long), st), "hipMemsetAsync(counters)");
+    if (!rc) step(hipEventRecord(e1.get(), st), "hipEventRecord");
+    if (!rc) step(hipEventSynchronize(e1.get()), "hipEventSynchronize");
+    if (!rc) step(hipEventElapsedTime(&sc->h2d_ms, e0.get(), e1.get()), "hipEventElapsedTime");
+    if (rc) return rc;
     if (dbg(DBG_VERBOSE))
         fprintf(stderr, "[rt] scene: %u prims  culled walk: %u big spheres, slack radius %g, box density %.3f -> %s  bvh build %.2f ms (host)  uploads %.2f ms  upload total %.2f ms\n",
                 hs.shape.n_sph + hs.shape.n_tri, hs.n_big, hs.shape.r_slack, hs.shape.cull_density, hs.shape.cull_pays ? "default" : "off", sc->bvh_build_ms, sc->h2d_ms,
                 std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_create0).count());
-    guard.sc = nullptr;
-    *out = sc;
+    *out = sc.release();
     return RT_OK;
 }
 
@@ -920,43 +858,12 @@ static int rt_scene_create_impl(int device, const rt_sphere* sp, uint32_t ns, co
     return upload_scene(device, hs, out);
 }
 
+// The scene's device is made current BEFORE `delete`: the members free their device memory and destroy their events in their
+// destructors, on whichever thread this runs (a caller's, or a frame context's dispatcher).
 static int rt_scene_destroy_impl(rt_scene* sc) {
     if (!sc) return RT_OK;
     if (sc->ctx) (void)hipSetDevice(sc->ctx->dev);
-    for (auto& pr : sc->pending) {
-        (void)hipEventSynchronize(pr.second);
-        (void)hipEventDestroy(pr.first);
-        (void)hipEventDestroy(pr.second);
-    }
-    for (auto& pr : sc->free_ev) {
-        (void)hipEventDestroy(pr.first);
-        (void)hipEventDestroy(pr.second);
-    }
-    (void)hipFree(sc->d_geom);
-    (void)hipFree(sc->d_geom_pk);
-    (void)hipFree(sc->d_geom_px);
-    (void)hipFree(sc->d_mat);
-    (void)hipFree(sc->d_emis);
-    (void)hipFree(sc->d_tri);
-    (void)hipFree(sc->d_tri_box);
-    (void)hipFree(sc->d_bvh);
-    (void)hipFree(sc->d_trav);
-    (void)hipFree(sc->d_travq);
-    (void)hipFree(sc->d_stack_ovf);
-    if (sc->ovf_done) (void)hipEventDestroy(sc->ovf_done);
-    for (auto& r : sc->rings) {
-        (void)hipFree(r.d);
-        if (r.done) (void)hipEventDestroy(r.done);
-    }
-    (void)hipFree(sc->d_geom_r);
-    (void)hipFree(sc->d_big);
-    (void)hipFree(sc->d_lights);
-    (void)hipFree(sc->d_light_c);
-    (void)hipFree(sc->d_light_ip);
-    (void)hipFree(sc->d_leaf_of);
-    (void)hipFree(sc->d_world_rank);
-    (void)hipFree(sc->d_counters);
-    for (DevBuf* b : {&sc->d_out, &sc->d_outf, &sc->d_acc, &sc->d_cost, &sc->d_stage}) b->release();
+    for (const EventPool::Pair& pr : sc->events.pending()) (void)hipEventSynchronize(pr.b);
     delete sc;
     g_live_scenes.fetch_sub(1);
     return RT_OK;
@@ -1047,9 +954,9 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
     if (out_f32)
         for (uint32_t i = 0; i < n; i++) want_f32 |= out_f32[i] != nullptr;
     HostForm hf(sc);
-    hipStream_t st = sc->ctx->stream;
-    if ((rc = hf.device()) || (rc = sc->d_out.reserve(need * n, "strips")) || (want_f32 && (rc = sc->d_outf.reserve(need * n * sizeof(float), "strips f32"))) ||
-        (pass && (rc = sc->d_acc.reserve(need * n * sizeof(float), "running sums"))))
+    hipStream_t st = sc->ctx->stream.get();
+    if ((rc = hf.device()) || (rc = reserve(sc->d_out, need * n, "strips")) || (want_f32 && (rc = reserve(sc->d_outf, need * n * sizeof(float), "strips f32"))) ||
+        (pass && (rc = reserve(sc->d_acc, need * n * sizeof(float), "running sums"))))
         return rc;
     // Launch groups [first, count): the last quarter of the strips as its own launch when the downloads are worth hiding, so that the
     // D2H copies of the strips before it (copy stream) run under it and only the last group's copies are exposed (d2h_ms = that part).
@@ -1059,8 +966,8 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
     unsigned long long* d_cost = nullptr;
     if (strip_cost_out) {
         const size_t cost_b = groups.size() * COST_BLOCK * sizeof(unsigned long long);
-        if ((rc = sc->d_cost.reserve(cost_b, "strip costs"))) return rc;
-        d_cost = (unsigned long long*)sc->d_cost.d;
+        if ((rc = reserve(sc->d_cost, cost_b, "strip costs"))) return rc;
+        d_cost = (unsigned long long*)sc->d_cost.data();
         HIPCHK(hipMemsetAsync(d_cost, 0, cost_b, st));
     }
     // settle anything enqueued earlier so the stats of this call are its own
@@ -1070,34 +977,24 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
     sc->h2d_ms = prev.h2d_ms;
     std::vector<void*> drgb(n), df32(n), dacc(pass ? n : 0);
     for (uint32_t i = 0; i < n; i++) {
-        drgb[i] = sc->d_out.d + need * i;
-        df32[i] = (want_f32 && out_f32[i]) ? sc->d_outf.d + need * i * sizeof(float) : nullptr;
-        if (pass) dacc[i] = sc->d_acc.d + need * i * sizeof(float);
+        drgb[i] = sc->d_out.data() + need * i;
+        df32[i] = (want_f32 && out_f32[i]) ? sc->d_outf.data() + need * i * sizeof(float) : nullptr;
+        if (pass) dacc[i] = sc->d_acc.data() + need * i * sizeof(float);
     }
-    hipStream_t cs = sc->ctx->copy_stream;
-    std::vector<EvPair> gev;
-    gev.reserve(groups.size());
-    // whatever happens below, the events go back to the scene's free list, and an error return waits for the work
-    // already enqueued (it writes into caller memory)
-    struct EvReturn {
-        rt_scene* sc;
-        std::vector<EvPair>& v;
+    hipStream_t cs = sc->ctx->copy_stream.get();
+    std::vector<EventPool::Lease> gev(groups.size());      // (back to the scene's pool however the call returns, after the wait below)
+    // an error return waits for the work already enqueued: it writes into caller memory
+    struct WaitOnError {
         hipStream_t a, b;
         bool ok = false;
-        ~EvReturn() {
+        ~WaitOnError() {
             if (!ok) {
                 (void)hipStreamSynchronize(a);
                 (void)hipStreamSynchronize(b);
             }
-            for (auto& e : v) sc->free_ev.push_back({e.a, e.b});
         }
-    } ev_return{sc, gev, st, cs};
-    for (size_t g = 0; g < groups.size(); g++) {
-        EvPair e;
-        rc = get_events(sc, e);
-        if (rc) return rc;
-        gev.push_back(e);
-    }
+    } wait{st, cs};
+    for (EventPool::Lease& e : gev) HIPCHK(sc->events.lease(e));
     if (pass && pass->begin > 0)            // (a pass from sample 0 reads no sum: the caller's buffer may be uninitialised)
         for (uint32_t i = 0; i < n; i++)
             HIPCHK(hipMemcpyAsync(dacc[i], pass->d_acc[i], need * sizeof(float), hipMemcpyHostToDevice, st));
@@ -1108,10 +1005,10 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
         rc = launch_batch(sc, rqs + i0, m, drgb.data() + i0, want_f32 ? df32.data() + i0 : nullptr, st,
                           d_cost ? d_cost + g * COST_BLOCK : nullptr, pass ? &part : nullptr);
         if (rc) return rc;
-        HIPCHK(hipEventRecord(gev[g].a, st));
+        HIPCHK(hipEventRecord(gev[g].a(), st));
     }
     for (size_t g = 0; g < groups.size(); g++) {
-        HIPCHK(hipStreamWaitEvent(cs, gev[g].a, 0));
+        HIPCHK(hipStreamWaitEvent(cs, gev[g].a(), 0));
         for (uint32_t i = groups[g].first; i < groups[g].first + groups[g].second; i++) {
             HIPCHK(hipMemcpyAsync(out_rgb[i], drgb[i], need, hipMemcpyDeviceToHost, cs));
             if (df32[i]) HIPCHK(hipMemcpyAsync(out_f32[i], df32[i], need * sizeof(float), hipMemcpyDeviceToHost, cs));
@@ -1123,12 +1020,12 @@ static int rt_scene_render_tiles_impl(rt_scene* sc, const rt_tile_request* rqs, 
         cost_raw.resize(groups.size() * COST_BLOCK);
         HIPCHK(hipMemcpyAsync(cost_raw.data(), d_cost, cost_raw.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
     }
-    HIPCHK(hipEventRecord(gev.back().b, cs));
-    HIPCHK(hipEventSynchronize(gev.back().b));
+    HIPCHK(hipEventRecord(gev.back().b(), cs));
+    HIPCHK(hipEventSynchronize(gev.back().b()));
     if (strip_cost_out) rtframe::fold_strip_costs(cost_raw.data(), groups, strip_cost_out);
     float d2h = 0.f;
-    HIPCHK(hipEventElapsedTime(&d2h, gev.back().a, gev.back().b));   // last launch done -> last byte on the host
-    ev_return.ok = true;
+    HIPCHK(hipEventElapsedTime(&d2h, gev.back().a(), gev.back().b()));   // last launch done -> last byte on the host
+    wait.ok = true;
     rt_tile_stats s;
     rc = collect_locked(sc, &s);
     if (rc) return rc;
@@ -1573,7 +1470,7 @@ static int launch_aov(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, uint
     p.s_end = end;
     p.planes = mask;
     scene_refs(sc, qp.full_chain, p);
-    p.mat = sc->d_mat;
+    p.mat = sc->d_mat.get();
     for (uint32_t i0 = 0; i0 < n; i0 += rtk::MAX_BATCH) {
         const uint32_t m = std::min<uint32_t>(rtk::MAX_BATCH, n - i0);
         p.n_strips = m;
@@ -1910,7 +1807,7 @@ extern "C" __attribute__((visibility("default"))) int rt_debug_read_counters(rt_
         if (!sc || !out || first > COUNTER_WORDS || n > COUNTER_WORDS - first) return fail(RT_ERR_BAD_ARG, "counter range");
         std::lock_guard<std::mutex> lk(sc->mu);
         HIPCHK(hipSetDevice(sc->ctx->dev));
-        HIPCHK(hipMemcpy(out, sc->d_counters + first, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out, sc->d_counters.get() + first, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         return RT_OK;
     });
 }
@@ -1921,15 +1818,14 @@ extern "C" __attribute__((visibility("default"))) int rt_debug_sqrt_selftest(int
     return guarded([&]() -> int {
         if (!mismatches || n > (1ull << 32) - from) return fail(RT_ERR_BAD_ARG, "sqrt self-test range");
         HIPCHK(hipSetDevice(device));
-        unsigned long long* d_bad = nullptr;
-        HIPCHK(hipMalloc(&d_bad, sizeof(unsigned long long)));
-        hipError_t e = hipMemset(d_bad, 0, sizeof(unsigned long long));
+        DevArray<unsigned long long> d_bad;
+        HIPCHK(d_bad.alloc(1));
+        hipError_t e = hipMemset(d_bad.get(), 0, sizeof(unsigned long long));
         if (e == hipSuccess) {
-            rtk::sqrt_selftest_launch(from, n, d_bad, 0);
+            rtk::sqrt_selftest_launch(from, n, d_bad.get(), 0);
             e = hipGetLastError();
         }
-        if (e == hipSuccess) e = hipMemcpy(mismatches, d_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost);
-        (void)hipFree(d_bad);
+        if (e == hipSuccess) e = hipMemcpy(mismatches, d_bad.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost);
         if (e != hipSuccess) return fail(RT_ERR_HIP, hipGetErrorString(e));
         return RT_OK;
     });
@@ -1945,19 +1841,17 @@ extern "C" __attribute__((visibility("default"))) int rt_debug_unit(int device, 
         if (!in || !out || n > (1ull << 24)) return fail(RT_ERR_BAD_ARG, "unit records");
         const size_t bi = (size_t)n * rtk::unit_record_in(family) * 4, bo = (size_t)n * rtk::unit_record_out(family) * 4;
         HIPCHK(hipSetDevice(device));
-        uint32_t *d_in = nullptr, *d_out = nullptr;
-        hipError_t e = hipMalloc(&d_in, bi);
-        if (e == hipSuccess) e = hipMalloc(&d_out, bo);
-        if (e == hipSuccess) e = hipMemcpy(d_in, in, bi, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemset(d_out, 0, bo);
+        DevArray<uint32_t> d_in, d_out;
+        hipError_t e = d_in.alloc(bi / 4);
+        if (e == hipSuccess) e = d_out.alloc(bo / 4);
+        if (e == hipSuccess) e = hipMemcpy(d_in.get(), in, bi, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(d_out.get(), 0, bo);
         if (e == hipSuccess) {
-            rtk::unit_launch(unit, family, n, d_in, d_out, 0);
+            rtk::unit_launch(unit, family, n, d_in.get(), d_out.get(), 0);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemcpy(out, d_out, bo, hipMemcpyDeviceToHost);
-        (void)hipFree(d_in);
-        (void)hipFree(d_out);
+        if (e == hipSuccess) e = hipMemcpy(out, d_out.get(), bo, hipMemcpyDeviceToHost);
         if (e != hipSuccess) return fail(RT_ERR_HIP, hipGetErrorString(e));
         return RT_OK;
     });
@@ -2012,8 +1906,8 @@ struct FrameDev {
     rt_scene* scene = nullptr;          // the job's world on this device (owned by the dispatcher thread)
     std::thread th;
     // strip-queue mode: two strips in flight, each on its own stream with its own device buffer (made on first use)
-    hipStream_t qs[2] = {nullptr, nullptr};
-    DevBuf qd[2];
+    Stream qs[2];
+    GrowBuf qd[2];
     // result of the last command
     int rc = RT_OK;
     std::string err;
@@ -2086,9 +1980,9 @@ int frame_dev_render_queue(rt_frame_ctx* fc, int w) {
     rt_scene* sc = d.scene;
     HIPCHK(hipSetDevice(sc->ctx->dev));
     for (int i = 0; i < 2; i++)
-        if (!d.qs[i]) HIPCHK(hipStreamCreateWithFlags(&d.qs[i], hipStreamNonBlocking));
+        if (!d.qs[i]) HIPCHK(d.qs[i].create(hipStreamNonBlocking));
     for (int i = 0; i < 2; i++) {
-        int rc = d.qd[i].reserve(strip, "strip");
+        int rc = reserve(d.qd[i], strip, "strip");
         if (rc) return rc;
     }
     bool busy[2] = {false, false};
@@ -2097,28 +1991,28 @@ int frame_dev_render_queue(rt_frame_ctx* fc, int w) {
         bool* busy;
         ~Settle() {
             for (int i = 0; i < 2; i++)
-                if (busy[i]) (void)hipStreamSynchronize(d.qs[i]);
+                if (busy[i]) (void)hipStreamSynchronize(d.qs[i].get());
         }
     } settle{d, busy};
     for (uint32_t turn = 0;; turn++) {
         const int sl = (int)(turn & 1u);
         if (busy[sl]) {
-            HIPCHK(hipStreamSynchronize(d.qs[sl]));
+            HIPCHK(hipStreamSynchronize(d.qs[sl].get()));
             busy[sl] = false;
         }
         const uint32_t i = fc->next_strip.fetch_add(1);
         if (i >= rq0.divisions) break;
         rt_tile_request rq = rq0;
         rq.division_no = rq0.divisions - 1u - i;
-        void* d1[1] = {d.qd[sl].d};
-        int r = rt_scene_render_tiles_device_impl(sc, &rq, 1, d1, strip, nullptr, d.qs[sl]);
+        void* d1[1] = {d.qd[sl].data()};
+        int r = rt_scene_render_tiles_device_impl(sc, &rq, 1, d1, strip, nullptr, d.qs[sl].get());
         if (r) return r;
-        HIPCHK(hipMemcpyAsync(out_rgb + (size_t)rq.division_no * strip, d.qd[sl].d, strip, hipMemcpyDeviceToHost, d.qs[sl]));
+        HIPCHK(hipMemcpyAsync(out_rgb + (size_t)rq.division_no * strip, d.qd[sl].data(), strip, hipMemcpyDeviceToHost, d.qs[sl].get()));
         busy[sl] = true;
     }
     for (int i = 0; i < 2; i++)
         if (busy[i]) {
-            HIPCHK(hipStreamSynchronize(d.qs[i]));
+            HIPCHK(hipStreamSynchronize(d.qs[i].get()));
             busy[i] = false;
         }
     return rt_scene_collect_impl(sc, &d.st);
@@ -2137,20 +2031,15 @@ int frame_dev_render(rt_frame_ctx* fc, int w) {
     return fc->plan.mode == rtassign::QUEUE ? frame_dev_render_queue(fc, w) : frame_dev_render_owned(fc, w);
 }
 
+// On the dispatcher thread, with the entry's device current: the context itself is deleted on the caller's thread, with nothing left to free.
 void frame_dev_release(FrameDev& d) {
-    if (d.scene) {
-        rt_scene_destroy_impl(d.scene);       // (sets the scene's device current)
-        d.scene = nullptr;
-    } else {
-        (void)hipSetDevice(d.dev);
-    }
+    rt_scene_destroy_impl(d.scene);
+    d.scene = nullptr;
+    (void)hipSetDevice(d.dev);
     for (int i = 0; i < 2; i++) {
-        if (d.qs[i]) {
-            (void)hipStreamSynchronize(d.qs[i]);
-            (void)hipStreamDestroy(d.qs[i]);
-            d.qs[i] = nullptr;
-        }
-        d.qd[i].release();
+        if (d.qs[i]) (void)hipStreamSynchronize(d.qs[i].get());
+        d.qs[i].reset();
+        d.qd[i].reset();
     }
 }
 
