@@ -71,6 +71,23 @@ DEBUG_FLAGS = ["-DRT_DEBUG_HOOKS"]
 DEBUG_LIB_PATH = LIB_DIR / f"librt_s8_{DEBUG_VARIANT}.so"
 
 
+# The FILM library: the moments fold and the variance-guided resolve of film.py, a second, private library that
+# only ray_tracer_s8_amd/_film_lib.py loads.  Its sources lie beside csrc/, not under it (_deps() globs csrc/ for the libraries
+# above), it exports only rtf_* names, and it takes no RT_EXTRA_HIPCC_FLAGS: experiments are the product library's.
+FILM_CSRC = PKG / "film_csrc"
+FILM_UNIT = "rt_film.hip"
+FILM_FLAGS = ["-fno-slp-vectorize"]
+FILM_LIB_PATH = LIB_DIR / "librt_film.so"
+FILM_FLAGS_PATH = FILM_LIB_PATH.with_suffix(".flags")
+
+
+def _film_deps() -> list[Path]:
+    """What the film library is compiled from: film_csrc/, the three csrc/ headers it includes (and the C header rt_plan.h reads),
+    this recipe."""
+    return sorted(f for f in FILM_CSRC.rglob("*") if f.is_file()) + [CSRC / "rt_denoise_math.h", CSRC / "rt_consts.h", CSRC / "rt_plan.h",
+                                                                    ROOT / "include" / "rt_tile.h", Path(__file__)]
+
+
 def _extra_flags() -> list[str]:
     return os.environ.get("RT_EXTRA_HIPCC_FLAGS", "").split()          # experiments only (e.g. -DRT_MAXC=12)
 
@@ -134,7 +151,10 @@ def _compile(lib_path: Path, flags_path: Path, obj_dir: Path, extra: list[str], 
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """Compile librt_s8.so (or the RT_LIB_VARIANT named) if missing or stale.  Raises on failure (no fallback)."""
+    """Compile librt_s8.so (or the RT_LIB_VARIANT named) if missing or stale, and with no variant named the film library next to
+    it.  Raises on failure (no fallback)."""
+    if not VARIANT:
+        build_film(force, verbose)
     if not force and not needs_build():
         return LIB_PATH
     return _compile(LIB_PATH, FLAGS_PATH, LIB_DIR / (f"obj_{VARIANT}" if VARIANT else "obj"), _extra_flags(), verbose)
@@ -150,7 +170,45 @@ def build_debug(force: bool = False, verbose: bool = False) -> Path:
     return _compile(DEBUG_LIB_PATH, fp, LIB_DIR / f"obj_{DEBUG_VARIANT}", DEBUG_FLAGS, verbose)
 
 
+def film_flags_record() -> str:
+    """The compile line of the film library's one translation unit (its own record, lib/librt_film.flags)."""
+    return f"{FILM_UNIT}: {' '.join([f for f in HIPCC_FLAGS if f != '-shared'] + FILM_FLAGS)}\n"
+
+
+def film_needs_build() -> bool:
+    if not FILM_LIB_PATH.exists() or not FILM_FLAGS_PATH.exists() or FILM_FLAGS_PATH.read_text() != film_flags_record():
+        return True
+    t = FILM_LIB_PATH.stat().st_mtime
+    return any(d.stat().st_mtime > t for d in _film_deps())
+
+
+def build_film(force: bool = False, verbose: bool = False) -> Path:
+    """Compile lib/librt_film.so (film_csrc/) if missing or stale: the product's flags, linked like the product
+    library, with a flags record and a staleness check of its own.  Raises on failure (no fallback)."""
+    if not force and not film_needs_build():
+        return FILM_LIB_PATH
+    LIB_DIR.mkdir(parents=True, exist_ok=True)
+    hipcc = os.environ.get("HIPCC", "hipcc")
+    if FILM_FLAGS_PATH.exists():
+        FILM_FLAGS_PATH.unlink()
+    obj_dir = LIB_DIR / "obj_film"
+    obj_dir.mkdir(exist_ok=True)
+    obj = obj_dir / (Path(FILM_UNIT).stem + ".o")
+    common = [f for f in HIPCC_FLAGS if f != "-shared"] + FILM_FLAGS
+    cmds = [[hipcc, *common, f"-I{ROOT / 'include'}", f"-I{CSRC}", f"-I{FILM_CSRC}", "-c", str(FILM_CSRC / FILM_UNIT), "-o", str(obj)],
+            [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(FILM_LIB_PATH), str(obj)]]
+    for cmd in cmds:
+        if verbose:
+            print(" ".join(cmd))
+        proc = subprocess.run(cmd, capture_output=True, text=True)
+        if proc.returncode != 0:
+            raise RuntimeError(f"hipcc failed ({proc.returncode}): {' '.join(cmd)}\n{proc.stdout}\n{proc.stderr}")
+    FILM_FLAGS_PATH.write_text(film_flags_record())
+    return FILM_LIB_PATH
+
+
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
     if not VARIANT:
         print(build_debug(force=True, verbose=True))
+        print(build_film(force=True, verbose=True))

@@ -10,13 +10,18 @@ Normative: after passes covering [0, e), accum[p] is the f32 sum in the order s 
 chosen integrator returns for the camera ray of (p, s) traced from the camera's state of (p, s) — bit for bit however the samples were
 cut into passes or sub-ranges.  With integrator="path" that sum is the tile path's progressive accum.
 
+With moments=True the film also keeps, per pixel, the sums S1 and S2 of the samples' y = (c0 + c1) + c2 and of y y, folded by a HIP
+kernel of the film library (lib/librt_film.so, film_csrc/) that replaces the torch fold, and resolve_guided() runs that
+library's variance-guided a-trous over accum and the moments.
+
 This module imports without torch; torch is imported when a Film is constructed, and must have been imported before the library
 bound a HIP runtime (_abi.check_single_hip_runtime)."""
 from __future__ import annotations
 
+import math
 from typing import NamedTuple, Optional, Sequence
 
-from . import _abi
+from . import _abi, _film_lib
 from ._abi import DenoiseRequest, TileRequest, TileStats
 from .interface import DENOISE_OUTPUTS, denoise_scratch_bytes
 
@@ -26,6 +31,15 @@ FEATURE_PLANES = ("albedo", "normal", "depth", "hits")
 # The library holds at most 16 384 uncollected launches per scene (rt_scene_collect): the film collects into its running sum before
 # its own could pass half of that, which leaves the other half to whatever else the caller enqueues on the scene.
 COLLECT_AT = 8192
+# resolve_guided: what it writes, the planes it reads, and its defaults.  sigma_l: the least mean squared error of the
+# grid 1 ... 128 at 8 samples on c2 and c3 (SVGF's 4 leaves most of the noise in: a variance estimated from 8 samples and not
+# accumulated over frames is itself noisy); var_eps, a standard deviation of y, is small against that of a visibly noisy pixel, keeps
+# a step of 1/255 in converged regions and barely moves the error anywhere on the grid (4.23 "Measured").
+GUIDED_OUTPUTS = ("rgb", "linear", "f32", "variance")
+GUIDED_PLANES = ("normal", "depth", "hits")
+GUIDED_MAX_ITERATIONS = _film_lib.MAX_ITERATIONS
+SIGMA_L = 16.0
+VAR_EPS = 2.0 ** -8
 
 # every field of a request but division_no: what the strips of one frame agree on
 _FRAME_FIELDS = tuple(n for n, _ in TileRequest._fields_ if n != "division_no")
@@ -96,6 +110,35 @@ def fold(accum, records) -> None:
         accum.add_(records[:, j])
 
 
+def check_guided(moments: bool, samples: int, planes: Sequence[str] = (), outputs: Sequence[str] = ("rgb",), iterations: int = 5,
+                 sigma_l: float = SIGMA_L, var_eps: float = VAR_EPS, k_normal: float = 1.0, k_depth: float = 4.0) -> tuple:
+    """The checks of resolve_guided's arguments, all of them ValueError and none of them a GPU call.  moments: whether the film was
+    made with moments=True; planes: the names of the planes given (index is ignored).  Returns (planes, outputs) as tuples, the
+    planes in GUIDED_PLANES' order.  Pure: no torch, no GPU."""
+    if not moments:
+        raise ValueError("resolve_guided and variance need a film made with moments=True")
+    if samples < 2:
+        raise ValueError(f"the film holds {samples} samples: a variance needs at least 2")
+    outs = tuple(outputs)
+    if not outs or any(o not in GUIDED_OUTPUTS for o in outs) or len(set(outs)) != len(outs):
+        raise ValueError(f"outputs: a non-empty subset of {GUIDED_OUTPUTS}, got {outs}")
+    names = tuple(n for n in planes if n != "index")
+    if "albedo" in names:
+        raise ValueError("planes: the guided filter does not demodulate by the albedo, leave it out")
+    if any(n not in GUIDED_PLANES for n in names):
+        raise ValueError(f"planes: a subset of {GUIDED_PLANES}, got {names}")
+    if "depth" in names and "hits" not in names:
+        raise ValueError("planes: the depth plane needs the hits plane")
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or not 0 <= iterations <= GUIDED_MAX_ITERATIONS:
+        raise ValueError(f"iterations: an int in 0 ... {GUIDED_MAX_ITERATIONS}, got {iterations!r}")
+    for name, v in (("sigma_l", sigma_l), ("var_eps", var_eps), ("k_normal", k_normal), ("k_depth", k_depth)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"{name}: a finite number >= 0, got {v!r}")
+    if not var_eps > 0:
+        raise ValueError("var_eps must be > 0")
+    return tuple(n for n in GUIDED_PLANES if n in names), outs
+
+
 def _add_stats(total: TileStats, st: TileStats) -> None:
     for f in _SUMMED_STATS:
         setattr(total, f, getattr(total, f) + getattr(st, f))
@@ -130,10 +173,11 @@ class Film:
     RtError its accum is undefined until reset()."""
 
     def __init__(self, scene, reqs, *, integrator: str = "nee", mode: int = _abi.RT_NEE_MIS, flags: int = 0,
-                 max_records: int = 1 << 22, stream=None, _collect_at: int = COLLECT_AT):
+                 max_records: int = 1 << 22, stream=None, moments: bool = False, _collect_at: int = COLLECT_AT):
         plan = check_job(reqs, integrator, mode, max_records)
         import torch
         _abi.check_single_hip_runtime()           # torch imported after the library bound its runtime: say so, before any HIP call
+        self._film_lib = _film_lib.load() if moments else None        # (after the check: it binds to the same HIP runtime)
         self._torch = torch
         self.scene = scene
         self.integrator, self.mode, self.flags, self.max_records = integrator, mode, flags, max_records
@@ -161,6 +205,9 @@ class Film:
             self._rays = torch.empty((n, 8), dtype=torch.float32, device=self.device)
             self._states = torch.empty((n, 4), dtype=torch.int64, device=self.device)
             self._rgb = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+            self.moments = torch.zeros((self.rows, self.width, 2), dtype=torch.float32, device=self.device) if moments else None
+        self._guided_scratch = None
+        self._guided_out: dict = {}
 
     # ---- the film's own state
 
@@ -195,10 +242,13 @@ class Film:
         self.stream.synchronize()
 
     def reset(self):
-        """Back to no samples: accum is zeroed on the film's stream.  The feature buffers do not depend on it and stay."""
+        """Back to no samples: accum (and moments) are zeroed on the film's stream.  The feature buffers do not depend on it and
+        stay."""
         self._check_open()
         with self._torch.cuda.stream(self.stream):
             self.accum.zero_()
+            if self.moments is not None:
+                self.moments.zero_()
         self.samples = 0
 
     def close(self):
@@ -207,7 +257,8 @@ class Film:
             return
         self.sync()
         self.accum = self._rays = self._states = self._rgb = self._scratch = None
-        self.planes, self._out = {}, {}
+        self.moments = self._guided_scratch = None
+        self.planes, self._out, self._guided_out = {}, {}, {}
 
     def __enter__(self):
         return self
@@ -226,6 +277,13 @@ class Film:
 
     _fold = staticmethod(fold)                    # (tools/film_bench.py times a pass without it by shadowing this on the instance)
 
+    def _fold_moments(self, acc, mom, records):
+        """accum and moments of a strip += its records (P, n, 3), in record order: one launch of the film library's fold kernel on the
+        film's stream."""
+        P, n = records.shape[0], records.shape[1]
+        _film_lib.check("rtf_fold_moments", self._film_lib.rtf_fold_moments(records.data_ptr(), P, n, acc.data_ptr(), mom.data_ptr(),
+                                                                            self.stream.cuda_stream))
+
     def render_pass(self, begin: int, end: int):
         """Add samples [begin, end) of the spp-sample job to accum; begin must be `samples`, and begin < end <= spp.  Per strip and
         per sub-range of sample_chunks: the camera's rays and states, the trace from those states with spp = 1, and the fold."""
@@ -240,12 +298,16 @@ class Film:
         with self._torch.cuda.stream(self.stream):
             for i, rq in enumerate(self.reqs):
                 acc = self._strip(self.accum, i).view(pixels, 3)
+                mom = self._strip(self.moments, i).view(pixels, 2) if self.moments is not None else None
                 for b, e in chunks:
                     n = pixels * (e - b)
                     self._reserve(2)
                     self.scene.camera_rays_device(rq, b, e, self._rays.data_ptr(), self._states.data_ptr(), stream=handle)
                     self._trace(n, rq.max_bounces, handle)
-                    self._fold(acc, self._rgb[:n].view(pixels, e - b, 3))
+                    if mom is None:
+                        self._fold(acc, self._rgb[:n].view(pixels, e - b, 3))
+                    else:
+                        self._fold_moments(acc, mom, self._rgb[:n].view(pixels, e - b, 3))
         self.samples = end
 
     def render_progressive(self, pass_spp: int):
@@ -338,3 +400,55 @@ class Film:
     def preview(self, outputs: Sequence[str] = ("rgb",)) -> dict:
         """resolve with no iterations and no planes: sqrt(accum / samples), what the tile path's pass shows."""
         return self.resolve(DenoiseRequest.defaults(iterations=0), None, outputs)
+
+    # ---- the variance-guided resolve (DESIGN.md 4.23)
+
+    def _guided(self, guide: dict, outs: tuple, iterations: int, sigma_l: float, var_eps: float, k_normal: float, k_depth: float,
+                lds_max_step: int) -> dict:
+        """One rtf_resolve call on the film's stream into the film's own output tensors.  These launches are the film library's, not
+        the scene's: they count neither against _reserve nor in collect()."""
+        torch = self._torch
+        with torch.cuda.stream(self.stream):
+            if self._guided_scratch is None:
+                self._guided_scratch = torch.empty(_film_lib.resolve_scratch_bytes(self.width, self.rows), dtype=torch.uint8,
+                                                   device=self.device)
+            for o in outs:
+                if o not in self._guided_out:
+                    shape = (self.rows, self.width) if o == "variance" else (self.rows, self.width, 3)
+                    self._guided_out[o] = torch.empty(shape, dtype=torch.uint8 if o == "rgb" else torch.float32, device=self.device)
+            ptr = lambda d, k: d[k].data_ptr() if k in d else None
+            out = {o: self._guided_out[o] for o in outs}
+            a = _film_lib.ResolveArgs(W=self.width, R=self.rows, samples=self.samples, iterations=iterations, lds_max_step=lds_max_step,
+                                      sigma_l=sigma_l, var_eps=var_eps, k_normal=k_normal, k_depth=k_depth,
+                                      accum=self.accum.data_ptr(), moments=self.moments.data_ptr(), normal=ptr(guide, "normal"),
+                                      depth=ptr(guide, "depth"), hits=ptr(guide, "hits"), scratch=self._guided_scratch.data_ptr(),
+                                      scratch_bytes=self._guided_scratch.numel(), out_rgb=ptr(out, "rgb"), out_f32=ptr(out, "f32"),
+                                      out_linear=ptr(out, "linear"), out_variance=ptr(out, "variance"))
+            _film_lib.check("rtf_resolve", self._film_lib.rtf_resolve(a, self.stream.cuda_stream))
+        return out
+
+    def variance(self):
+        """v0 of every pixel, the variance of the mean of y over the samples folded so far, as an (R, W) float32 tensor (the film's
+        own: the next variance() or resolve_guided(outputs=("variance", ...)) writes it again).  Needs moments=True and samples >= 2."""
+        self._check_open()
+        check_guided(self.moments is not None, self.samples, (), ("variance",), 0)
+        return self._guided({}, ("variance",), 0, SIGMA_L, VAR_EPS, 0.0, 0.0, _film_lib.LDS_PLAN)["variance"]
+
+    def resolve_guided(self, planes: Optional[dict] = None, outputs: Sequence[str] = ("rgb",), iterations: int = 5,
+                       sigma_l: float = SIGMA_L, var_eps: float = VAR_EPS, k_normal: Optional[float] = None,
+                       k_depth: Optional[float] = None, _lds_max_step: int = _film_lib.LDS_PLAN) -> dict:
+        """The variance-guided a-trous over all strips as one image (rtf_resolve): the colour edge-stop of each pixel
+        is scaled by its prefiltered variance of the mean, which the iterations carry along.  planes: a part of what features()
+        returned out of normal, depth (needs hits) and hits, or None; index is ignored and albedo refused (no demodulation here).
+        outputs: a non-empty subset of ("rgb", "linear", "f32", "variance").  k_normal, k_depth: None for DenoiseRequest.defaults()'s.
+        Returns {output: tensor} in resolve()'s layout, variance as (R, W) float32.  Needs moments=True and samples >= 2."""
+        self._check_open()
+        given = {n: t for n, t in (planes or {}).items() if t is not None}
+        if k_normal is None or k_depth is None:
+            dq = DenoiseRequest.defaults()
+            k_normal = dq.k_normal if k_normal is None else k_normal
+            k_depth = dq.k_depth if k_depth is None else k_depth
+        names, outs = check_guided(self.moments is not None, self.samples, tuple(given), outputs, iterations, sigma_l, var_eps,
+                                   k_normal, k_depth)
+        guide = self._check_planes({n: given[n] for n in names})
+        return self._guided(guide, outs, iterations, float(sigma_l), float(var_eps), float(k_normal), float(k_depth), _lds_max_step)

@@ -1,0 +1,219 @@
+"""The film library off the GPU: the product's per-pixel lines (film_csrc/rt_film_math.h, through the g++ harness
+tests/host/film_host.cpp) equal the numpy restatement of film_csrc/rt_film.h (tests/_film_np.py) bit for bit, for the moments fold on
+adversarial records and for the guided resolve on seeded synthetic images under every plane subset; and properties of the contract
+hold on the restatement.  Without the feature every test here fails: there is no film_csrc."""
+import ctypes as C
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import _film_np as fnp
+
+ROOT = Path(__file__).resolve().parents[1]
+CSRC = ROOT / "ray_tracer_s8_amd" / "csrc"
+FILM_CSRC = ROOT / "ray_tracer_s8_amd" / "film_csrc"
+SRC = ROOT / "tests" / "host" / "film_host.cpp"
+OUT = ROOT / "tests" / "host" / "_build" / "libfilm_host.so"
+DEPS = [SRC, FILM_CSRC / "rt_film_math.h", CSRC / "rt_denoise_math.h", CSRC / "rt_consts.h"]
+f32 = np.float32
+OUTPUTS = ("linear", "f32", "rgb", "variance")
+# the plane subsets a call may have: normal or not, times nothing / hits / depth and hits
+SUBSETS = [(n, d) for n in (False, True) for d in ("", "hits", "depth")]
+ITERATIONS = (0, 1, 3, 5, 8)
+
+
+@pytest.fixture(scope="module")
+def lib():
+    OUT.parent.mkdir(exist_ok=True)
+    if not OUT.exists() or OUT.stat().st_mtime < max(d.stat().st_mtime for d in DEPS):
+        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", f"-I{CSRC}", f"-I{FILM_CSRC}",
+                        "-o", str(OUT), str(SRC)], check=True)
+    l = C.CDLL(str(OUT))
+    vp = C.c_void_p
+    l.film_fold_host.argtypes = [vp, C.c_uint64, C.c_uint32, vp, vp]
+    l.film_fold_host.restype = None
+    l.film_resolve_host.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32] + [vp] * 10
+    l.film_resolve_host.restype = None
+    return l
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data
+
+
+def host_fold(lib, acc, mom, rec):
+    acc, mom, rec = acc.copy(), mom.copy(), np.ascontiguousarray(rec, f32)
+    lib.film_fold_host(rec.ctypes.data, rec.shape[0], rec.shape[1], acc.ctypes.data, mom.ctypes.data)
+    return acc, mom
+
+
+def host_resolve(lib, C_, M, e, *, N=None, D=None, hits=None, iterations=5, sigma_l=16.0, var_eps=2.0 ** -8, k_normal=1.0, k_depth=4.0):
+    R, W = C_.shape[:2]
+    fp = np.array([e, sigma_l, var_eps, k_normal, k_depth], f32)
+    lin, ff = np.empty((R, W, 3), f32), np.empty((R, W, 3), f32)
+    rgb, var = np.empty((R, W, 3), np.uint8), np.empty((R, W), f32)
+    args = [np.ascontiguousarray(a) if a is not None else None for a in (C_, M, N, D, hits)]
+    lib.film_resolve_host(W, R, iterations, fp.ctypes.data, *[_p(a) for a in args], lin.ctypes.data, ff.ctypes.data, rgb.ctypes.data,
+                          var.ctypes.data)
+    return dict(linear=lin, f32=ff, rgb=rgb, variance=var)
+
+
+def _eq(a, b, what):
+    if a.dtype == np.uint8:
+        bad = np.argwhere(a != b)
+    else:
+        bad = np.argwhere(a.view(np.uint32) != b.view(np.uint32))
+    assert len(bad) == 0, (what, len(bad), bad[:4], a[tuple(bad[0])], b[tuple(bad[0])])
+
+
+def planes_of(s, normal, depth):
+    return dict(N=s["N"] if normal else None, D=s["D"] if depth == "depth" else None, hits=s["hits"] if depth else None)
+
+
+# ---- the fold ---------------------------------------------------------------------------------------------------------------------
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32).tobytes()
+
+
+def test_fold_of_adversarial_records_equals_the_numpy_loop(lib):
+    P, K = 257, 7
+    v = fnp.adversarial_records(P, K)
+    assert (np.abs(v[(v != 0) & (np.abs(v) < 1.2e-38)]) > 0).any() and np.signbit(v[v == 0]).any()
+    acc0, mom0 = np.zeros((P, 3), f32), np.zeros((P, 2), f32)
+    want_acc, want_mom = fnp.fold(acc0, mom0, v)
+    # the restatement is the plain loop, written out once more for the moments
+    s1, s2 = np.zeros(P, f32), np.zeros(P, f32)
+    with np.errstate(all="ignore"):
+        for j in range(K):
+            y = ((v[:, j, 0] + v[:, j, 1]) + v[:, j, 2]).astype(f32)
+            s1, s2 = (s1 + y).astype(f32), (s2 + y * y).astype(f32)
+    assert _bits(want_mom[:, 0]) == _bits(s1) and _bits(want_mom[:, 1]) == _bits(s2)
+    assert np.isinf(want_mom[2]).all() and not np.isnan(want_mom).any() and not np.isnan(want_acc).any()
+    assert _bits(want_acc[0]) == _bits(np.zeros(3, f32)) and _bits(want_mom[0]) == _bits(np.zeros(2, f32))       # +0 + -0 stays +0
+    got_acc, got_mom = host_fold(lib, acc0, mom0, v)
+    assert _bits(got_acc) == _bits(want_acc)
+    assert _bits(got_mom) == _bits(want_mom), np.argwhere(got_mom.view(np.uint32) != want_mom.view(np.uint32))[:5]
+    # ... and it is the ORDER that is pinned: the reversed fold differs, in accum and in both moments
+    rev_acc, rev_mom = host_fold(lib, acc0, mom0, v[:, ::-1])
+    assert _bits(rev_acc) != _bits(want_acc)
+    assert _bits(rev_mom[:, 0]) != _bits(want_mom[:, 0]) and _bits(rev_mom[:, 1]) != _bits(want_mom[:, 1])
+    # cut into sub-ranges, the running sums carried: the same bytes
+    acc, mom = acc0, mom0
+    for b, e in ((0, 1), (1, 4), (4, 7)):
+        acc, mom = host_fold(lib, acc, mom, v[:, b:e])
+    assert _bits(acc) == _bits(want_acc) and _bits(mom) == _bits(want_mom)
+
+
+@pytest.mark.parametrize("P,K", [(1, 1), (63, 1), (1, 7), (63, 7)])
+def test_fold_sizes(lib, P, K):
+    v = fnp.adversarial_records(P, K)
+    acc0, mom0 = np.zeros((P, 3), f32), np.zeros((P, 2), f32)
+    want = fnp.fold(acc0, mom0, v)
+    got = host_fold(lib, acc0, mom0, v)
+    assert _bits(got[0]) == _bits(want[0]) and _bits(got[1]) == _bits(want[1])
+
+
+# ---- the guided resolve -----------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def images():
+    return {(R, W): fnp.synthetic(np.random.default_rng(R * 1000 + W), R, W) for R, W in [(1, 1), (2, 3), (9, 70), (70, 130)]}
+
+
+def test_the_synthetic_images_hit_the_clamp_and_have_fireflies(images):
+    s = images[(70, 130)]
+    e = f32(8)
+    m, a = s["M"][..., 0] / e, s["M"][..., 1] / e
+    d = a - m * m
+    assert (d < 0).sum() > 20 and (d > 0).sum() > 1000, ((d < 0).sum(), (d > 0).sum())
+    v0 = fnp.entry_variance(s["M"], 8)
+    assert (v0 == 0).sum() >= (d < 0).sum() and np.isfinite(v0).all() and v0.max() > 10 * np.median(v0[v0 > 0])
+    assert (s["hits"] == 0).any() and (s["hits"] == 4).any() and ((s["hits"] > 0) & (s["hits"] < 4)).any()
+    assert (np.all(s["N"] == 0, axis=-1) & (s["hits"] > 0)).any()
+
+
+@pytest.mark.parametrize("R,W", [(1, 1), (2, 3), (9, 70), (70, 130)])
+@pytest.mark.parametrize("normal,depth", SUBSETS)
+def test_host_lines_equal_the_restatement(lib, images, R, W, normal, depth):
+    s = images[(R, W)]
+    kw = planes_of(s, normal, depth)
+    for it in ITERATIONS:
+        for sl, ve, kn, kd in [(16.0, 2.0 ** -8, 1.0, 4.0)] + ([(0.0, 1e-3, 0.0, 0.0), (4.0, 1.0, 2.0, 8.0)] if it == 3 else []):
+            want = fnp.resolve(s["C"], s["M"], 8, iterations=it, sigma_l=f32(sl), var_eps=f32(ve), k_normal=f32(kn), k_depth=f32(kd), **kw)
+            got = host_resolve(lib, s["C"], s["M"], 8, iterations=it, sigma_l=sl, var_eps=ve, k_normal=kn, k_depth=kd, **kw)
+            for o in OUTPUTS:
+                _eq(got[o], want[o], (R, W, normal, depth, it, sl, o))
+
+
+# ---- properties of the contract, on the restatement -------------------------------------------------------------------------------
+def test_no_iteration_is_the_preview(images):
+    s = images[(9, 70)]
+    out = fnp.resolve(s["C"], s["M"], 8, iterations=0, N=s["N"], D=s["D"], hits=s["hits"])
+    prev = np.sqrt(s["C"] / f32(8))
+    assert _bits(out["f32"]) == _bits(prev) and _bits(out["linear"]) == _bits(s["C"] / f32(8))
+    assert np.array_equal(out["rgb"], fnp.dn.as_u8(prev * f32(255.999)))
+    assert _bits(out["variance"]) == _bits(fnp.entry_variance(s["M"], 8))
+
+
+def test_a_constant_image_with_zero_variance_stays_constant():
+    R, W, e = 9, 21, 4
+    c = np.array([0.75, 0.5, 0.125], f32)
+    Cc = np.broadcast_to(c * f32(e), (R, W, 3)).astype(f32)
+    y = (c[0] + c[1]) + c[2]
+    M = np.broadcast_to(np.array([y * f32(e), (y * y) * f32(e)], f32), (R, W, 2)).astype(f32)
+    for it in (1, 5, 8):
+        out = fnp.resolve(Cc, M, e, iterations=it)
+        assert _bits(out["linear"]) == _bits(np.broadcast_to(c, (R, W, 3)).astype(f32)) and not out["variance"].any()
+
+
+def test_pixels_further_apart_than_var_eps_with_no_variance_do_not_mix():
+    """Two values of y that differ by more than var_eps, v = 0 everywhere: a_p = 1 / var_eps, so every tap of the other value has
+    x > 1 and weight +0, and every tap of the pixel's own value has x = 0 and its full B3 weight: outputs equal inputs exactly."""
+    rng = np.random.default_rng(21)
+    R, W, e = 12, 37, 2
+    ve = f32(2.0 ** -6)
+    pick = rng.random((R, W)) < 0.5
+    c = np.where(pick[..., None], np.array([0.25, 0.5, 0.125], f32), np.array([0.25, 0.5, 0.125 + 2.0 ** -5], f32)).astype(f32)
+    y = fnp.lum(c)
+    assert np.abs(y[pick][0] - y[~pick][0]) > ve
+    Cc = (c * f32(e)).astype(f32)
+    M = np.stack([y * f32(e), (y * y) * f32(e)], -1).astype(f32)
+    assert not fnp.entry_variance(M, e).any()
+    for it in (1, 5):
+        out = fnp.resolve(Cc, M, e, iterations=it, var_eps=ve)
+        assert _bits(out["linear"]) == _bits(c) and not out["variance"].any()
+
+
+def test_sky_and_geometry_do_not_mix(images):
+    s = images[(70, 130)]
+    kw = dict(N=s["N"], D=s["D"], hits=s["hits"], iterations=5)
+    base = fnp.resolve(s["C"], s["M"], 8, **kw)
+    geo = s["hits"] > 0
+    for side in (geo, ~geo):
+        C2, M2 = s["C"].copy(), s["M"].copy()
+        C2[side] = C2[side] * f32(3) + f32(1)
+        M2[side] = M2[side] * f32(5) + f32(2)
+        out = fnp.resolve(C2, M2, 8, **kw)
+        for o in ("linear", "variance"):
+            assert _bits(out[o][~side]) == _bits(base[o][~side]), o
+
+
+def test_the_variance_never_grows_past_the_largest_of_its_taps(images):
+    """v_{i+1} = sum w^2 v_q / (sum w)^2 <= max v_q, because sum w^2 <= (sum w)^2 for w >= 0: up to the roundings of the sums, which
+    the factor 1 + 2^-18 covers (some 60 f32 operations of relative error 2^-24 each)."""
+    s = images[(9, 70)]
+    trace = []
+    fnp.resolve(s["C"], s["M"], 8, N=s["N"], D=s["D"], hits=s["hits"], iterations=5, trace=trace)
+    side = s["hits"] > 0
+    for i, ((_, v), (_, v1)) in enumerate(zip(trace, trace[1:])):
+        step = 1 << i
+        vmax = np.zeros_like(v)
+        for dy in range(-2, 3):
+            for dx in range(-2, 3):
+                vq = fnp.dn._shift(v, step * dy, step * dx, f32(0))
+                same = fnp.dn._shift(side, step * dy, step * dx, False) == side
+                inside = fnp.dn._shift(np.ones_like(side), step * dy, step * dx, False)
+                vmax = np.where(same & inside, np.maximum(vmax, vq), vmax)
+        assert (v1 <= vmax * f32(1 + 2.0 ** -18)).all(), i
+    assert trace[-1][1].max() < trace[0][1].max()
