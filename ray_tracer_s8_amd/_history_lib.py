@@ -1,0 +1,73 @@
+"""The binding of lib/librt_history.so, the film-history library (history_csrc/rt_history.h): a ctypes table and a
+lazy load().
+
+Private to film_history.py: the library holds the reprojection and blend of rt.FilmHistory, is no part of the tile ABI
+(include/rt_tile.h, _abi.py) or of the film library, and exports only rth_* names.  Every function returns an int status, which `check`
+turns into an RthError.  This module imports without torch; the library is loaded by FilmHistory after a Film exists, so that it binds
+to the HIP runtime torch and librt_s8.so use."""
+from __future__ import annotations
+
+import ctypes as C
+
+from . import build as _build
+from ._abi import Camera, TileRequest
+
+RTH_VERSION = 1
+RTH_OK = 0
+STATUS = {1: "RTH_ERR_BAD_ARG", 2: "RTH_ERR_LIMIT", 3: "RTH_ERR_HIP", 4: "RTH_ERR_INTERNAL"}
+
+
+class RthError(RuntimeError):
+    def __init__(self, what: str, status: int):
+        super().__init__(f"{what}: {STATUS.get(status, status)}")
+        self.status = status
+
+
+class State(C.Structure):
+    _fields_ = [("accum", C.c_void_p), ("moments", C.c_void_p), ("length", C.c_void_p), ("depth", C.c_void_p), ("index", C.c_void_p),
+                ("normal", C.c_void_p)]
+
+
+class AccumulateArgs(C.Structure):
+    _fields_ = [("W", C.c_uint32), ("R", C.c_uint32), ("have_prev", C.c_uint32), ("reserved", C.c_uint32),
+                ("alpha", C.c_float), ("n_max", C.c_float), ("k_depth", C.c_float), ("k_normal", C.c_float),
+                ("request", C.POINTER(TileRequest)), ("camera", C.POINTER(Camera)),
+                ("prev_request", C.POINTER(TileRequest)), ("prev_camera", C.POINTER(Camera)),
+                ("accum", C.c_void_p), ("moments", C.c_void_p), ("depth", C.c_void_p), ("hits", C.c_void_p), ("index", C.c_void_p),
+                ("normal", C.c_void_p), ("prev", State), ("next", State)]
+
+
+assert C.sizeof(State) == 48 and C.sizeof(AccumulateArgs) == 208
+
+# name: argument types (every function returns int)
+SIGNATURES = {
+    "rth_version": [C.POINTER(C.c_uint32)],
+    "rth_accumulate": [C.POINTER(AccumulateArgs), C.c_void_p],
+}
+
+_lib = None
+
+
+def check(what: str, status: int) -> None:
+    if status != RTH_OK:
+        raise RthError(what, status)
+
+
+def load(build_if_missing: bool = True) -> C.CDLL:
+    """Load librt_history.so (building it with hipcc if it is missing).  Raises if it cannot: there is no fall-back."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    path = _build.HISTORY_LIB_PATH
+    if build_if_missing and not path.exists():
+        path = _build.build_history()
+    lib = C.CDLL(str(path))
+    for name, argtypes in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = argtypes, C.c_int
+    v = C.c_uint32(0)
+    check("rth_version", lib.rth_version(C.byref(v)))
+    if v.value != RTH_VERSION:
+        raise RuntimeError(f"{path} is version {v.value}, this binding is version {RTH_VERSION}: rebuild it (build.build_history)")
+    _lib = lib
+    return lib

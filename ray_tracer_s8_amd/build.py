@@ -88,6 +88,23 @@ def _film_deps() -> list[Path]:
                                                                     ROOT / "include" / "rt_tile.h", Path(__file__)]
 
 
+# The HISTORY library: the temporal accumulation of film_history.py, a third, private library that only
+# ray_tracer_s8_amd/_history_lib.py loads.  Built like the film library: sources beside csrc/, rth_* exports only, the product's flags
+# plus -fno-slp-vectorize, no RT_EXTRA_HIPCC_FLAGS, a record and a staleness check of its own.
+HISTORY_CSRC = PKG / "history_csrc"
+HISTORY_UNIT = "rt_history.hip"
+HISTORY_FLAGS = ["-fno-slp-vectorize"]
+HISTORY_LIB_PATH = LIB_DIR / "librt_history.so"
+HISTORY_FLAGS_PATH = HISTORY_LIB_PATH.with_suffix(".flags")
+
+
+def _history_deps() -> list[Path]:
+    """What the history library is compiled from: history_csrc/, the two csrc/ headers it includes (and the C header they read), this
+    recipe."""
+    return sorted(f for f in HISTORY_CSRC.rglob("*") if f.is_file()) + [CSRC / "rt_consts.h", CSRC / "rt_plan.h",
+                                                                       ROOT / "include" / "rt_tile.h", Path(__file__)]
+
+
 def _extra_flags() -> list[str]:
     return os.environ.get("RT_EXTRA_HIPCC_FLAGS", "").split()          # experiments only (e.g. -DRT_MAXC=12)
 
@@ -151,10 +168,11 @@ def _compile(lib_path: Path, flags_path: Path, obj_dir: Path, extra: list[str], 
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """Compile librt_s8.so (or the RT_LIB_VARIANT named) if missing or stale, and with no variant named the film library next to
-    it.  Raises on failure (no fallback)."""
+    """Compile librt_s8.so (or the RT_LIB_VARIANT named) if missing or stale, and with no variant named the film library and the
+    history library next to it.  Raises on failure (no fallback)."""
     if not VARIANT:
         build_film(force, verbose)
+        build_history(force, verbose)
     if not force and not needs_build():
         return LIB_PATH
     return _compile(LIB_PATH, FLAGS_PATH, LIB_DIR / (f"obj_{VARIANT}" if VARIANT else "obj"), _extra_flags(), verbose)
@@ -207,8 +225,48 @@ def build_film(force: bool = False, verbose: bool = False) -> Path:
     return FILM_LIB_PATH
 
 
+def history_flags_record() -> str:
+    """The compile line of the history library's one translation unit (its own record, lib/librt_history.flags)."""
+    return f"{HISTORY_UNIT}: {' '.join([f for f in HIPCC_FLAGS if f != '-shared'] + HISTORY_FLAGS)}\n"
+
+
+def history_needs_build() -> bool:
+    if (not HISTORY_LIB_PATH.exists() or not HISTORY_FLAGS_PATH.exists()
+            or HISTORY_FLAGS_PATH.read_text() != history_flags_record()):
+        return True
+    t = HISTORY_LIB_PATH.stat().st_mtime
+    return any(d.stat().st_mtime > t for d in _history_deps())
+
+
+def build_history(force: bool = False, verbose: bool = False) -> Path:
+    """Compile lib/librt_history.so (history_csrc/) if missing or stale, as build_film compiles the film library.
+    Raises on failure (no fallback)."""
+    if not force and not history_needs_build():
+        return HISTORY_LIB_PATH
+    LIB_DIR.mkdir(parents=True, exist_ok=True)
+    hipcc = os.environ.get("HIPCC", "hipcc")
+    if HISTORY_FLAGS_PATH.exists():
+        HISTORY_FLAGS_PATH.unlink()
+    obj_dir = LIB_DIR / "obj_history"
+    obj_dir.mkdir(exist_ok=True)
+    obj = obj_dir / (Path(HISTORY_UNIT).stem + ".o")
+    common = [f for f in HIPCC_FLAGS if f != "-shared"] + HISTORY_FLAGS
+    cmds = [[hipcc, *common, f"-I{ROOT / 'include'}", f"-I{CSRC}", f"-I{HISTORY_CSRC}", "-c", str(HISTORY_CSRC / HISTORY_UNIT),
+             "-o", str(obj)],
+            [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(HISTORY_LIB_PATH), str(obj)]]
+    for cmd in cmds:
+        if verbose:
+            print(" ".join(cmd))
+        proc = subprocess.run(cmd, capture_output=True, text=True)
+        if proc.returncode != 0:
+            raise RuntimeError(f"hipcc failed ({proc.returncode}): {' '.join(cmd)}\n{proc.stdout}\n{proc.stderr}")
+    HISTORY_FLAGS_PATH.write_text(history_flags_record())
+    return HISTORY_LIB_PATH
+
+
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
     if not VARIANT:
         print(build_debug(force=True, verbose=True))
         print(build_film(force=True, verbose=True))
+        print(build_history(force=True, verbose=True))

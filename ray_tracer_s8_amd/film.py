@@ -241,10 +241,17 @@ class Film:
         """Wait until everything the film enqueued has run."""
         self.stream.synchronize()
 
-    def reset(self):
+    def reset(self, seed: Optional[int] = None):
         """Back to no samples: accum (and moments) are zeroed on the film's stream.  The feature buffers do not depend on it and
-        stay."""
+        stay.  seed: also the job's seed from here on, set on the film's own copies of the requests (never the caller's), for the
+        passes and the features that follow.  A sample's stream depends on (seed, pixel, sample) only: without a new seed a frame
+        rendered again under the same camera has the same bytes, and a history of identical frames (rt.FilmHistory) gains nothing."""
         self._check_open()
+        if seed is not None:
+            if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+                raise ValueError(f"seed: an int in 0 ... 2^64 - 1, got {seed!r}")
+            for rq in self.reqs:
+                rq.seed = seed
         with self._torch.cuda.stream(self.stream):
             self.accum.zero_()
             if self.moments is not None:
@@ -366,12 +373,15 @@ class Film:
             raise ValueError("planes: call features() first, it sets their sample count")
         return guide
 
-    def resolve(self, dreq: Optional[DenoiseRequest] = None, planes: Optional[dict] = None, outputs: Sequence[str] = ("rgb",)) -> dict:
+    def resolve(self, dreq: Optional[DenoiseRequest] = None, planes: Optional[dict] = None, outputs: Sequence[str] = ("rgb",),
+                _state: Optional[tuple] = None) -> dict:
         """The denoiser over all strips as one image (rt_scene_denoise_device) with color_samples = samples.  dreq: None for the
         library's defaults; its sample counts are set here.  planes: the dict features() returned (its sample count is the film's
         aov_samples), a part of it, or None for the plain colour a-trous.  outputs: a non-empty subset of ("rgb", "linear", "f32").
-        Returns {output: (R, W, 3) tensor}, uint8 for rgb and float32 otherwise."""
+        Returns {output: (R, W, 3) tensor}, uint8 for rgb and float32 otherwise.  _state: (accum, moments) tensors of the film's
+        shape to resolve in the place of the film's own (film_history.py)."""
         self._check_open()
+        accum = self.accum if _state is None else _state[0]
         torch = self._torch
         outs = tuple(outputs)
         if not outs or any(o not in DENOISE_OUTPUTS for o in outs):
@@ -392,7 +402,7 @@ class Film:
             ptrs = {k: self._strip_ptrs(t) for k, t in guide.items()}
             arrays = {o: self._strip_ptrs(self._out[o]) if o in outs else None for o in DENOISE_OUTPUTS}
             self._reserve(2 * n + _abi.RT_DENOISE_MAX_ITERATIONS)
-            self.scene.denoise_device(self.reqs, dq, self._strip_ptrs(self.accum), [{k: p[i] for k, p in ptrs.items()} for i in range(n)],
+            self.scene.denoise_device(self.reqs, dq, self._strip_ptrs(accum), [{k: p[i] for k, p in ptrs.items()} for i in range(n)],
                                       self._scratch.data_ptr(), self._scratch.numel(), d_rgb=arrays["rgb"], d_f32=arrays["f32"],
                                       d_linear=arrays["linear"], stream=self.stream.cuda_stream)
         return {o: self._out[o] for o in outs}
@@ -404,10 +414,12 @@ class Film:
     # ---- the variance-guided resolve
 
     def _guided(self, guide: dict, outs: tuple, iterations: int, sigma_l: float, var_eps: float, k_normal: float, k_depth: float,
-                lds_max_step: int) -> dict:
+                lds_max_step: int, _state: Optional[tuple] = None) -> dict:
         """One rtf_resolve call on the film's stream into the film's own output tensors.  These launches are the film library's, not
-        the scene's: they count neither against _reserve nor in collect()."""
+        the scene's: they count neither against _reserve nor in collect().  _state: (accum, moments) tensors of the film's shape to
+        resolve in the place of the film's own (film_history.py)."""
         torch = self._torch
+        accum, moments = (self.accum, self.moments) if _state is None else _state
         with torch.cuda.stream(self.stream):
             if self._guided_scratch is None:
                 self._guided_scratch = torch.empty(_film_lib.resolve_scratch_bytes(self.width, self.rows), dtype=torch.uint8,
@@ -420,7 +432,7 @@ class Film:
             out = {o: self._guided_out[o] for o in outs}
             a = _film_lib.ResolveArgs(W=self.width, R=self.rows, samples=self.samples, iterations=iterations, lds_max_step=lds_max_step,
                                       sigma_l=sigma_l, var_eps=var_eps, k_normal=k_normal, k_depth=k_depth,
-                                      accum=self.accum.data_ptr(), moments=self.moments.data_ptr(), normal=ptr(guide, "normal"),
+                                      accum=accum.data_ptr(), moments=moments.data_ptr(), normal=ptr(guide, "normal"),
                                       depth=ptr(guide, "depth"), hits=ptr(guide, "hits"), scratch=self._guided_scratch.data_ptr(),
                                       scratch_bytes=self._guided_scratch.numel(), out_rgb=ptr(out, "rgb"), out_f32=ptr(out, "f32"),
                                       out_linear=ptr(out, "linear"), out_variance=ptr(out, "variance"))
@@ -436,12 +448,14 @@ class Film:
 
     def resolve_guided(self, planes: Optional[dict] = None, outputs: Sequence[str] = ("rgb",), iterations: int = 5,
                        sigma_l: float = SIGMA_L, var_eps: float = VAR_EPS, k_normal: Optional[float] = None,
-                       k_depth: Optional[float] = None, _lds_max_step: int = _film_lib.LDS_PLAN) -> dict:
+                       k_depth: Optional[float] = None, _lds_max_step: int = _film_lib.LDS_PLAN,
+                       _state: Optional[tuple] = None) -> dict:
         """The variance-guided a-trous over all strips as one image (rtf_resolve): the colour edge-stop of each pixel
         is scaled by its prefiltered variance of the mean, which the iterations carry along.  planes: a part of what features()
         returned out of normal, depth (needs hits) and hits, or None; index is ignored and albedo refused (no demodulation here).
         outputs: a non-empty subset of ("rgb", "linear", "f32", "variance").  k_normal, k_depth: None for DenoiseRequest.defaults()'s.
-        Returns {output: tensor} in resolve()'s layout, variance as (R, W) float32.  Needs moments=True and samples >= 2."""
+        Returns {output: tensor} in resolve()'s layout, variance as (R, W) float32.  Needs moments=True and samples >= 2.  _state: as
+        resolve()'s."""
         self._check_open()
         given = {n: t for n, t in (planes or {}).items() if t is not None}
         if k_normal is None or k_depth is None:
@@ -451,4 +465,5 @@ class Film:
         names, outs = check_guided(self.moments is not None, self.samples, tuple(given), outputs, iterations, sigma_l, var_eps,
                                    k_normal, k_depth)
         guide = self._check_planes({n: given[n] for n in names})
-        return self._guided(guide, outs, iterations, float(sigma_l), float(var_eps), float(k_normal), float(k_depth), _lds_max_step)
+        return self._guided(guide, outs, iterations, float(sigma_l), float(var_eps), float(k_normal), float(k_depth), _lds_max_step,
+                            _state)

@@ -1,0 +1,99 @@
+// rt_history.hip — the host side of librt_history.so (rt_history.h): argument checks, the two cameras, the launch.
+// No global state, no allocation; every function catches everything inside its body.
+#include <cmath>
+#include <cstring>
+
+#include "rt_history.h"
+#include "rt_history.hip.h"
+#include "rt_plan.h"
+
+#define RTH_EXPORT extern "C" __attribute__((visibility("default")))
+
+namespace {
+
+template <class F>
+int guarded(const F& body) {
+    try {
+        return body();
+    } catch (...) {
+        return RTH_ERR_INTERNAL;
+    }
+}
+
+bool finite_nonneg(float v) { return std::isfinite(v) && v >= 0.0f; }
+
+bool request_ok(const rt_tile_request* rq, uint32_t W, uint32_t R) {
+    if (!rq || rq->width != W || rq->height == 0 || rq->divisions == 0 || rq->division_no >= rq->divisions) return false;
+    const uint32_t Hs = rq->height / rq->divisions;
+    if (Hs == 0 || R % Hs != 0) return false;
+    return (uint64_t)rq->division_no * Hs + R <= rq->height;
+}
+
+bool planes_ok(const rth_state& s, bool normals) {
+    return s.accum && s.moments && s.length && s.depth && s.index && (!normals || s.normal) && ((uintptr_t)s.moments & 7u) == 0;
+}
+
+}  // namespace
+
+RTH_EXPORT int rth_version(uint32_t* version) {
+    return guarded([&] {
+        if (!version) return RTH_ERR_BAD_ARG;
+        *version = RTH_VERSION;
+        return RTH_OK;
+    });
+}
+
+RTH_EXPORT int rth_accumulate(const rth_accumulate_args* a, void* stream) {
+    return guarded([&] {
+        if (!a || a->W == 0 || a->R == 0 || a->reserved != 0) return RTH_ERR_BAD_ARG;
+        if (a->W >= (1u << 24) || a->R >= (1u << 24)) return RTH_ERR_LIMIT;                   // (float)W, (float)R and the taps exact
+        if (!request_ok(a->request, a->W, a->R)) return RTH_ERR_BAD_ARG;
+        if (a->request->height >= (1u << 24)) return RTH_ERR_LIMIT;
+        if (!(a->alpha > 0.0f && a->alpha <= 1.0f) || !(a->n_max >= 1.0f) || !std::isfinite(a->n_max)) return RTH_ERR_BAD_ARG;
+        if (!finite_nonneg(a->k_depth) || !finite_nonneg(a->k_normal)) return RTH_ERR_BAD_ARG;
+        if (!a->accum || !a->moments || !a->depth || !a->hits || !a->index || ((uintptr_t)a->moments & 7u) != 0) return RTH_ERR_BAD_ARG;
+        const bool normals = a->normal != nullptr;
+        if (!planes_ok(a->next, normals)) return RTH_ERR_BAD_ARG;
+        const rt_tile_request& rq = *a->request;
+
+        rthk::Params p;
+        std::memset(&p, 0, sizeof p);
+        rthm::Frame& f = p.f;
+        f.W = a->W;
+        f.R = a->R;
+        f.normals = normals ? 1u : 0u;
+        f.alpha = a->alpha;
+        f.n_max = a->n_max;
+        f.kd = a->k_depth;
+        f.kn2 = a->k_normal * a->k_normal;
+        if (a->have_prev) {
+            if (!planes_ok(a->prev, normals) || !request_ok(a->prev_request, a->W, a->R)) return RTH_ERR_BAD_ARG;
+            if (a->prev.accum == a->next.accum || a->prev.moments == a->next.moments || a->prev.length == a->next.length ||
+                a->prev.depth == a->next.depth || a->prev.index == a->next.index || (normals && a->prev.normal == a->next.normal))
+                return RTH_ERR_BAD_ARG;                           // a frame never reads what it writes
+            const rt_tile_request& pq = *a->prev_request;
+            if (pq.height != rq.height || pq.divisions != rq.divisions || pq.division_no != rq.division_no) return RTH_ERR_BAD_ARG;
+        }
+        if (!rthm::set_cameras(f, rq, a->camera, a->have_prev ? a->prev_request : nullptr, a->prev_camera)) return RTH_ERR_BAD_ARG;
+        p.accum = a->accum;
+        p.moments = a->moments;
+        p.depth = a->depth;
+        p.hits = a->hits;
+        p.index = a->index;
+        p.normal = a->normal;
+        const rth_state* src[2] = {&a->prev, &a->next};
+        rthk::State* dst[2] = {&p.prev, &p.next};
+        for (int k = f.have_prev ? 0 : 1; k < 2; k++) {
+            dst[k]->accum = src[k]->accum;
+            dst[k]->moments = src[k]->moments;
+            dst[k]->length = src[k]->length;
+            dst[k]->depth = src[k]->depth;
+            dst[k]->index = src[k]->index;
+            dst[k]->normal = src[k]->normal;
+        }
+        const dim3 grid((a->W + rthk::TILE_X - 1) / rthk::TILE_X, (a->R + rthk::TILE_Y - 1) / rthk::TILE_Y);
+        if (grid.y > 65535u) return RTH_ERR_LIMIT;
+        hipLaunchKernelGGL(rthk::rth_accumulate_kernel, grid, dim3(rthk::BLOCK), 0, (hipStream_t)stream, p);
+        return hipGetLastError() == hipSuccess ? RTH_OK : RTH_ERR_HIP;
+    });
+}

@@ -1,0 +1,271 @@
+"""The film history off the GPU: the product's per-pixel lines and camera setup (history_csrc/rt_history_math.h,
+through the g++ harness tests/host/history_host.cpp) equal the numpy restatement of history_csrc/rt_history.h (tests/_history_np.py)
+bit for bit on seeded synthetic frames, under identical, translated, rotated and placed cameras, whole films and bands, with and
+without normals, and every branch of the per-pixel code is taken at least once; properties of the contract hold on the restatement;
+the harness as a stand-alone program runs clean under the address and undefined-behaviour sanitizers.  Without the feature every test
+here fails: there is no history_csrc."""
+import ctypes as C
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import _history_np as hnp
+from ray_tracer_s8_amd import _abi
+
+ROOT = Path(__file__).resolve().parents[1]
+CSRC = ROOT / "ray_tracer_s8_amd" / "csrc"
+HISTORY_CSRC = ROOT / "ray_tracer_s8_amd" / "history_csrc"
+SRC = ROOT / "tests" / "host" / "history_host.cpp"
+BUILD = ROOT / "tests" / "host" / "_build"
+OUT = BUILD / "libhistory_host.so"
+DEPS = [SRC, HISTORY_CSRC / "rt_history_math.h", CSRC / "rt_plan.h", CSRC / "rt_consts.h", ROOT / "include" / "rt_tile.h"]
+GXX = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", f"-I{ROOT / 'include'}", f"-I{CSRC}", f"-I{HISTORY_CSRC}"]
+f32 = np.float32
+BRANCHES = ("NO_HITS", "FIRST", "CUR_NONE", "BEHIND", "OUTSIDE", "TAP_OUT", "TAP_EMPTY", "TAP_NONE", "TAP_INDEX", "TAP_DEPTH",
+            "TAP_NORMAL", "TAP_OK", "NO_TAP", "BLEND", "N_MAX", "N_BELOW", "ALPHA", "RCP_N")
+# (W, H, divisions): the frames; the film is the whole frame or, where there are three strips or more, strips 1 and 2
+SIZES = [(1, 1, 1), (3, 2, 1), (70, 9, 3), (130, 70, 5)]
+
+# the cameras of consecutive frames, as (origin, target, up) or None for the reference camera
+LOOK = lambda o, t=None, up=(0.0, 1.0, 0.0): (tuple(o), tuple(t) if t is not None else (o[0], o[1], o[2] - 1.0), up)
+PATHS = {
+    "identical": [None, None, None, None],
+    "translated": [None, LOOK((0.3, 0.1, 0.0)), LOOK((0.5, -0.2, 0.1)), LOOK((0.5, -0.2, 0.1))],
+    "rotated": [LOOK((0, 0, 0)), LOOK((0, 0, 0), (0.2, 0.05, -1.0)), LOOK((0, 0, 0), (0.3, -0.1, -1.0), (0.1, 1.0, 0.0)), None],
+    "placed against reference": [LOOK((0.4, 0.2, 0.5), (0.0, 0.0, -5.0)), None, LOOK((-0.4, 0.1, 0.3), (0.2, 0.0, -5.0)), None],
+    "behind": [LOOK((0.0, 0.0, -9.0)), None, LOOK((0.0, 0.0, -9.0)), LOOK((0.1, 0.0, 0.0))],
+    "off to the left and up": [None, LOOK((4.0, -2.5, 0.0)), LOOK((4.4, -2.7, 0.0)), None],
+    "off to the right and down": [None, LOOK((-4.0, 2.5, 0.0)), LOOK((-4.4, 2.7, 0.0)), None],
+    "half a pixel": [None, LOOK((0.02, 0.013, 0.0)), LOOK((0.04, 0.03, 0.0)), LOOK((0.06, 0.04, 0.0))],
+}
+
+
+@pytest.fixture(scope="module")
+def lib():
+    BUILD.mkdir(exist_ok=True)
+    if not OUT.exists() or OUT.stat().st_mtime < max(d.stat().st_mtime for d in DEPS):
+        subprocess.run([*GXX, "-fPIC", "-shared", "-o", str(OUT), str(SRC)], check=True)
+    l = C.CDLL(str(OUT))
+    vp = C.c_void_p
+    l.history_frame_host.argtypes = [C.c_uint32, C.c_uint32, vp, C.POINTER(_abi.TileRequest), C.POINTER(_abi.Camera),
+                                     C.POINTER(_abi.TileRequest), C.POINTER(_abi.Camera)] + [vp] * 6 + [C.POINTER(vp), C.POINTER(vp), vp]
+    l.history_frame_host.restype = C.c_int
+    assert l.history_branch_count() == len(BRANCHES)
+    return l
+
+
+def _camera(pose):
+    return None if pose is None else _abi.Camera.look_at(*pose)
+
+
+def _new_state(R, W):
+    return dict(accum=np.zeros((R, W, 3), f32), moments=np.zeros((R, W, 2), f32), length=np.zeros((R, W), f32),
+                depth=np.zeros((R, W), f32), index=np.zeros((R, W), np.uint32), normal=np.zeros((R, W, 3), f32))
+
+
+def host_frame(lib, rq, pose, prev_rq, prev_pose, frame, prev, consts, counts):
+    """One frame through the harness: the next state as a dict of new arrays."""
+    R, W = frame["depth"].shape
+    normals = consts[3] is not None
+    nxt = _new_state(R, W)
+    fp = np.array([consts[0], consts[1], consts[2], consts[3] if normals else 0.0], f32)
+    pack = lambda s: (C.c_void_p * 6)(*[s[n].ctypes.data if s[n] is not None else None for n in hnp.STATE])
+    arr = [np.ascontiguousarray(frame[n]) for n in ("C", "M", "depth", "hits", "index")]
+    nrm = np.ascontiguousarray(frame["normal"]) if normals else None
+    cam, pcam = _camera(pose), _camera(prev_pose)
+    rc = lib.history_frame_host(W, R, fp.ctypes.data, C.byref(rq), C.byref(cam) if cam else None,
+                                C.byref(prev_rq) if prev is not None else None, C.byref(pcam) if pcam else None,
+                                *[a.ctypes.data for a in arr], nrm.ctypes.data if normals else None,
+                                pack(prev if prev is not None else nxt), pack(nxt), counts.ctypes.data)
+    assert rc == 0
+    if not normals:
+        nxt["normal"] = None
+    return nxt
+
+
+def _eq(got, want, what):
+    for n in hnp.STATE:
+        if want[n] is None:
+            continue
+        bad = np.argwhere(got[n].view(np.uint32) != want[n].view(np.uint32))
+        assert len(bad) == 0, (what, n, len(bad), bad[:4].tolist(), got[n][tuple(bad[0])], want[n][tuple(bad[0])])
+
+
+def sequence(rq_of, R, poses, consts, seed):
+    """The frames of a path: [(rq, pose, frame)], seeded."""
+    rng = np.random.default_rng(seed)
+    rq = rq_of()
+    return [(rq, pose, hnp.synthetic_frame(rng, rq, pose, R, consts[2], consts[3])) for pose in poses]
+
+
+def film_of(W, H, div, band):
+    first, n = (1, 2) if band else (0, div)
+    hs = H // div
+    return (lambda: _abi.default_request(width=W, height=H, divisions=div, division_no=first, spp=4)), hs * n
+
+
+def restate(frames, consts):
+    states, prev, last = [], None, None
+    for rq, pose, frame in frames:
+        cam = hnp.cameras(rq, pose, last[0] if last else None, last[1] if last else None)
+        prev = hnp.accumulate(cam, frame, prev, consts[0], consts[1], consts[2], consts[3])
+        states.append(prev)
+        last = (rq, pose)
+    return states
+
+
+def test_host_lines_equal_the_restatement_and_every_branch_is_taken(lib):
+    counts = np.zeros(len(BRANCHES), np.uint64)
+    for W, H, div in SIZES:
+        for band in ((False, True) if div >= 3 else (False,)):
+            rq_of, R = film_of(W, H, div, band)
+            for k, (name, poses) in enumerate(PATHS.items()):
+                # alpha above 1/N from the third frame on with n_max 3, below it throughout with n_max 8; with and without normals
+                for consts in ((0.4, 3.0, 0.05, 0.9), (0.05, 8.0, 0.1, None)):
+                    frames = sequence(rq_of, R, poses, consts, 1000 * W + 10 * k + band)
+                    want = restate(frames, consts)
+                    prev, last = None, None
+                    for i, (rq, pose, frame) in enumerate(frames):
+                        prev = host_frame(lib, rq, pose, last[0] if last else None, last[1] if last else None, frame, prev, consts, counts)
+                        _eq(prev, want[i], (W, H, band, name, consts, i))
+                        last = (rq, pose)
+    # a state whose length is 0 in places (no frame of the library's writes one: the caller's zeroed planes): those taps are skipped
+    rq_of, R = film_of(70, 9, 3, False)
+    consts = (0.2, 8.0, 0.1, 0.9)
+    frames = sequence(rq_of, R, PATHS["half a pixel"], consts, 31)
+    prev = restate(frames[:1], consts)[0]
+    prev["length"][np.random.default_rng(32).random((R, 70)) < 0.2] = 0
+    (rq0, pose0, _), (rq1, pose1, frame) = frames[:2]
+    want = hnp.accumulate(hnp.cameras(rq1, pose1, rq0, pose0), frame, prev, *consts)
+    _eq(host_frame(lib, rq1, pose1, rq0, pose0, frame, prev, consts, counts), want, "zeroed lengths")
+    never = [b for b, c in zip(BRANCHES, counts) if c == 0]
+    assert not never, (never, dict(zip(BRANCHES, counts.tolist())))
+
+
+def test_band_footprints_straddle_the_first_and_the_last_row(lib):
+    """A band of a taller frame under a vertical drift: some footprints have taps on both sides of the band's first row, some of its
+    last, and the rows outside the band are not read (they do not exist)."""
+    rq_of, R = film_of(130, 70, 5, True)
+    consts = (0.2, 8.0, 0.1, None)
+    poses = [None, LOOK((0.0, 0.35, 0.0)), LOOK((0.0, -0.3, 0.0))]
+    frames = sequence(rq_of, R, poses, consts, 77)
+    for a, b in ((0, 1), (1, 2)):
+        cam = hnp.cameras(frames[b][0], frames[b][1], frames[a][0], frames[a][1])
+        fr = frames[b][2]
+        z = np.where(fr["hits"] != 0, fr["depth"] / np.maximum(fr["hits"], 1).astype(f32), f32(0)).astype(f32)
+        fx, fy, zp, front = hnp.reproject(cam, 130, R, z)
+        assert ((fy > -1) & (fy < 0)).any() or ((fy > R - 1) & (fy < R)).any(), (a, b)
+    counts = np.zeros(len(BRANCHES), np.uint64)
+    want = restate(frames, consts)
+    prev, last = None, None
+    for i, (rq, pose, frame) in enumerate(frames):
+        prev = host_frame(lib, rq, pose, last[0] if last else None, last[1] if last else None, frame, prev, consts, counts)
+        _eq(prev, want[i], i)
+        last = (rq, pose)
+    assert counts[BRANCHES.index("TAP_OUT")] > 0 and counts[BRANCHES.index("BLEND")] > 0
+
+
+# ---- properties of the contract, on the restatement -------------------------------------------------------------------------------
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32).tobytes()
+
+
+def _counts(length, n):
+    """Every length is n up to the roundings of its bilinear mean.  A pixel reprojects onto itself only up to the roundings of its
+    ray and projection, so its history is itself at a weight just below 1 and a neighbour of the same length at the rest: Sn / Sw
+    of four equal lengths is four products, three sums twice and a division, some 11 roundings of 2^-24 each, 2^-20 to be safe."""
+    return bool((np.abs(length - f32(n)) <= n * 2.0 ** -20).all())
+
+
+def _still(n, consts, W=70, H=9, vary=True):
+    """n frames under the reference camera with the same planes (and, with vary, colours of their own)."""
+    rq = _abi.default_request(width=W, height=H, divisions=1, division_no=0, spp=4)
+    rng = np.random.default_rng(5)
+    base = hnp.synthetic_frame(rng, rq, None, H, consts[2], consts[3])
+    frames = []
+    for i in range(n):
+        fr = dict(base)
+        if vary and i:
+            other = hnp.synthetic_frame(np.random.default_rng(100 + i), rq, None, H, consts[2], consts[3])
+            fr["C"], fr["M"] = other["C"], other["M"]
+        frames.append((rq, None, fr))
+    return frames
+
+
+def test_a_first_frame_returns_the_current_bytes():
+    consts = (0.2, 8.0, 0.1, 0.9)
+    (rq, pose, fr), = _still(1, consts)
+    st = hnp.accumulate(hnp.cameras(rq, pose), fr, None, *consts)
+    assert _bits(st["accum"]) == _bits(fr["C"]) and _bits(st["moments"]) == _bits(fr["M"]) and (st["length"] == 1).all()
+    assert _bits(st["normal"]) == _bits(fr["normal"]) and np.array_equal(st["index"], fr["index"])
+    assert not st["depth"][fr["hits"] == 0].any() and (st["depth"][fr["hits"] > 0] > 0).all()
+
+
+def test_alpha_one_returns_the_current_bytes_on_every_frame():
+    consts = (1.0, 8.0, 0.1, None)
+    frames = _still(4, consts)
+    for (rq, pose, fr), st in zip(frames, restate(frames, consts)):
+        assert _bits(st["accum"]) == _bits(fr["C"]) and _bits(st["moments"]) == _bits(fr["M"])
+
+
+def test_under_a_still_camera_the_length_counts_up_to_n_max_and_stays():
+    consts = (0.01, 5.0, 0.1, 0.9)
+    frames = _still(8, consts)
+    # (a hit pixel whose index is RT_HIT_NONE, or whose normal sum has no length, never passes the tests it is put to)
+    keeps = (frames[0][2]["hits"] > 0) & (frames[0][2]["index"] != hnp.NONE) & frames[0][2]["normal"].any(-1)
+    assert keeps.sum() > 300 and (~keeps).sum() > 20
+    for i, st in enumerate(restate(frames, consts)):
+        assert _counts(st["length"][keeps], min(i + 1, 5)), i
+        assert (st["length"][~keeps] == 1).all(), i
+
+
+def test_a_pixel_whose_index_changed_restarts_at_one():
+    consts = (0.2, 8.0, 0.1, None)
+    frames = _still(4, consts, vary=False)
+    changed = np.zeros((9, 70), bool)
+    changed[3:6, 10:30] = True
+    fr = dict(frames[2][2])
+    fr["index"] = np.where(changed, fr["index"] + np.uint32(1000), fr["index"]).astype(np.uint32)
+    frames[2] = (frames[2][0], None, fr)
+    st = restate(frames, consts)
+    keeps = (frames[0][2]["hits"] > 0) & (frames[0][2]["index"] != hnp.NONE)
+    assert _counts(st[1]["length"][keeps], 2)
+    assert (st[2]["length"][changed] == 1).all() and _counts(st[2]["length"][keeps & ~changed], 3)
+    assert _bits(st[2]["accum"][changed]) == _bits(fr["C"][changed])
+    # ... and once more in the frame after: its stored index is the changed one
+    assert (st[3]["length"][changed] == 1).all() and _counts(st[3]["length"][keeps & ~changed], 4)
+
+
+def test_a_parallel_quad_reprojects_by_the_analytic_disparity():
+    """A wall at z = -D seen from the reference camera and from one moved by b along x: every point of the wall moves by
+    b f' u_den / (vw D) pixels, whatever its position.  Within one pixel (the distances are those of the centre rays, in f32)."""
+    W, H, D, b = 160, 90, 5.0, 1.0
+    rq = _abi.default_request(width=W, height=H, divisions=1, division_no=0, spp=4)
+    cam = hnp.cameras(rq, LOOK((b, 0.0, 0.0)), rq, None)
+    c = cam["cur"]
+    xs = (np.arange(W) + 0.5) / float(c["u_den"])
+    ys = (H - np.arange(H) - 1 + 0.5) / float(c["v_den"])
+    d = (c["llc"].astype(np.float64) + xs[None, :, None] * c["hor"].astype(np.float64) + ys[:, None, None] * c["ver"].astype(np.float64)
+         - c["org"].astype(np.float64))
+    d /= np.linalg.norm(d, axis=-1, keepdims=True)
+    z = (-D / d[..., 2]).astype(f32)
+    fx, fy, zp, front = hnp.reproject(cam, W, H, z)
+    p = cam["prev"]
+    disparity = b * float(p["f"]) * float(p["u_den"]) / (float(p["vw"]) * D)
+    assert 5 < disparity < 40 and front.all()
+    assert np.abs(fx - (np.arange(W)[None, :] + disparity)).max() < 1.0
+    assert np.abs(fy - np.arange(H)[:, None]).max() < 1.0
+    # the camera moved to the right, so the wall's image moved to the left: history comes from the pixels to the right
+    assert (fx > np.arange(W)[None, :]).all()
+
+
+# ---- the harness as a stand-alone program under the sanitizers ---------------------------------------------------------------------
+def test_the_stand_alone_harness_runs_clean_under_asan_and_ubsan(tmp_path):
+    exe = tmp_path / "history_host"
+    r = subprocess.run([*GXX, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DHISTORY_HOST_MAIN",
+                        "-o", str(exe), str(SRC)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "pixels blended" in r.stdout, r.stdout + r.stderr

@@ -1,0 +1,223 @@
+"""The film history without a GPU (ray_tracer_s8_amd/film_history.py, _history_lib.py, build.py):
+1. check_history refuses, with ValueError, everything FilmHistory refuses, and accepts the rest;
+2. film_history.py and _history_lib.py import without torch and without loading the history library;
+3. librt_history.so exports exactly _history_lib.SIGNATURES, all rth_*, and the private header declares exactly those; librt_s8.so,
+   librt_s8_dbg.so and librt_film.so export what they exported;
+4. the product's and the film library's build records and staleness checks are unaffected by the history library being missing,
+   present or stale, and the history library keeps a record of its own;
+5. rth_accumulate refuses bad arguments with a status, before any launch;
+6. Film.reset(seed=...) sets the seed of the film's own requests, not the caller's.
+Without the feature every test here fails: there is no film_history, no _history_lib and no build_history."""
+import contextlib
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+import types
+from pathlib import Path
+
+import pytest
+
+import ray_tracer_s8_amd as rt
+from ray_tracer_s8_amd import _abi, build
+
+import _surface
+
+ROOT = Path(__file__).resolve().parent.parent
+
+
+def test_check_history_accepts():
+    from ray_tracer_s8_amd import film_history as fh
+    assert fh.check_history(True) == (fh.ALPHA, float(fh.N_MAX), fh.K_DEPTH, None)
+    assert fh.check_history(True, 1, 1, 0, 0) == (1.0, 1.0, 0.0, 0.0)
+    assert fh.check_history(True, 0.05, 64, 0.5, 0.95) == (0.05, 64.0, 0.5, 0.95)
+    assert 0 < fh.ALPHA <= 1 and fh.N_MAX >= 1 and fh.K_DEPTH >= 0
+    assert rt.FilmHistory is fh.FilmHistory and "FilmHistory" in rt.__all__
+
+
+def test_check_history_refuses():
+    from ray_tracer_s8_amd import film_history as fh
+    inf, nan = float("inf"), float("nan")
+    bad = {
+        "no moments": dict(moments=False),
+        "alpha 0": dict(alpha=0.0),
+        "alpha < 0": dict(alpha=-0.1),
+        "alpha > 1": dict(alpha=1.5),
+        "alpha nan": dict(alpha=nan),
+        "alpha inf": dict(alpha=inf),
+        "alpha a string": dict(alpha="0.2"),
+        "alpha True": dict(alpha=True),
+        "n_max 0": dict(n_max=0),
+        "n_max 0.5": dict(n_max=0.5),
+        "n_max inf": dict(n_max=inf),
+        "n_max nan": dict(n_max=nan),
+        "n_max None": dict(n_max=None),
+        "k_depth < 0": dict(k_depth=-1.0),
+        "k_depth nan": dict(k_depth=nan),
+        "k_depth inf": dict(k_depth=inf),
+        "k_normal < 0": dict(k_normal=-0.5),
+        "k_normal nan": dict(k_normal=nan),
+        "k_normal inf": dict(k_normal=inf),
+        "k_normal a string": dict(k_normal="0.9"),
+    }
+    for what, kw in bad.items():
+        args = dict(moments=True)
+        args.update(kw)
+        with pytest.raises(ValueError):
+            fh.check_history(**args)
+            pytest.fail(what)
+
+
+def test_film_history_runs_its_checks_before_anything_else():
+    """No film, a film without moments, bad constants: ValueError before torch or the library is touched."""
+    plain = types.SimpleNamespace(moments=None)
+    for film, kw in ((None, {}), (plain, {}), (types.SimpleNamespace(moments=object()), dict(alpha=0.0)),
+                     (types.SimpleNamespace(moments=object()), dict(n_max=0))):
+        with pytest.raises(ValueError):
+            rt.FilmHistory(film, **kw)
+
+
+_IMPORT_CHILD = r"""
+import sys
+import ray_tracer_s8_amd as rt
+import ray_tracer_s8_amd.film_history as fh
+import ray_tracer_s8_amd._history_lib as hl
+assert "torch" not in sys.modules
+assert hl._lib is None                                  # importing loads nothing
+assert callable(fh.check_history) and callable(fh.FilmHistory.accumulate) and callable(fh.FilmHistory.resolve_guided)
+assert sorted(hl.SIGNATURES) == ["rth_accumulate", "rth_version"]
+fh.check_history(True)
+assert "torch" not in sys.modules and hl._lib is None
+print("ok")
+"""
+
+
+def test_film_history_and_its_binding_import_without_torch():
+    r = subprocess.run([sys.executable, "-c", _IMPORT_CHILD], capture_output=True, text=True, cwd=ROOT, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
+
+
+def test_abi_module_holds_nothing_of_the_history_library():
+    names = [n for n in dir(_abi) if "rth" in n.lower() or "history" in n.lower()]
+    assert names == [], names
+
+
+def test_the_other_builds_are_unaffected_by_the_history_library(tmp_path, monkeypatch):
+    """needs_build(), flags_record(), film_needs_build() and film_flags_record() do not read the history library, its record or its
+    sources; the history library has a record and a staleness check of its own."""
+    assert build.HISTORY_LIB_PATH == build.LIB_DIR / "librt_history.so"
+    assert build.HISTORY_LIB_PATH not in (build.LIB_PATH, build.FILM_LIB_PATH, build.DEBUG_LIB_PATH)
+    assert not any(build.HISTORY_CSRC in d.parents for d in build._deps() + build._film_deps())
+    assert build.HISTORY_CSRC.parent == build.CSRC.parent and build.HISTORY_CSRC not in (build.CSRC, build.FILM_CSRC)
+    assert any(build.HISTORY_CSRC in d.parents for d in build._history_deps())
+    build.build_film()
+    state = lambda: (build.flags_record(), build.needs_build(), build.film_flags_record(), build.film_needs_build())
+    before = state()
+    assert "rt_history" not in before[0] + before[2] and len(before[0].splitlines()) == len(build.UNITS)
+    missing = tmp_path / "librt_history.so"
+    monkeypatch.setattr(build, "HISTORY_LIB_PATH", missing)
+    monkeypatch.setattr(build, "HISTORY_FLAGS_PATH", missing.with_suffix(".flags"))
+    assert build.history_needs_build() and state() == before
+    # present, with a record of other flags: stale for build_history, nothing to the others
+    missing.write_bytes(b"")
+    missing.with_suffix(".flags").write_text("rt_history.hip: -O0\n")
+    assert build.history_needs_build() and state() == before
+    # present with the right record, but older than its sources: stale again
+    missing.with_suffix(".flags").write_text(build.history_flags_record())
+    os.utime(missing, (1, 1))
+    assert build.history_needs_build() and state() == before
+    os.utime(missing, None)
+    assert not build.history_needs_build() and state() == before
+
+
+def test_the_history_library_is_compiled_with_the_products_flags():
+    path = build.build_history()
+    assert path == build.HISTORY_LIB_PATH and path.exists() and not build.history_needs_build()
+    line = build.HISTORY_FLAGS_PATH.read_text()
+    assert line == build.history_flags_record() and line.startswith("rt_history.hip: ")
+    flags = line.split(": ", 1)[1].split()
+    assert flags == [f for f in build.HIPCC_FLAGS if f != "-shared"] + ["-fno-slp-vectorize"]
+    assert "-ffp-contract=off" in flags and "--offload-arch=gfx950" in flags
+    assert not any("correctly-rounded" in f or "fast-math" in f for f in flags)          # correctly rounded div / sqrt: the default
+
+
+def _all_exported(path):
+    out = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
+    return {ln.split()[-1] for ln in out.splitlines() if ln.split()}
+
+
+def test_exports():
+    from ray_tracer_s8_amd import _film_lib, _history_lib
+    _abi.load()
+    _abi.load_debug()
+    declared = set(_surface.parse()["functions"])
+    assert len(declared) == 51 and _surface.exported(build.LIB_PATH) == declared
+    for path in (build.LIB_PATH, build.DEBUG_LIB_PATH, build.build_film()):
+        assert not [s for s in _all_exported(path) if "rth_" in s], path
+    film = {s for s in _all_exported(build.FILM_LIB_PATH) if not s.startswith("_")}
+    assert film == set(_film_lib.SIGNATURES) == {"rtf_version", "rtf_fold_moments", "rtf_resolve_scratch_bytes", "rtf_resolve"}
+    history = {s for s in _all_exported(build.build_history()) if not s.startswith("_")}
+    assert history == set(_history_lib.SIGNATURES) and all(s.startswith("rth_") for s in history), history
+    assert not _surface.exported(build.HISTORY_LIB_PATH)
+    # the private header declares exactly the functions the binding names
+    text = (build.HISTORY_CSRC / "rt_history.h").read_text()
+    assert set(re.findall(r"^int (rth_\w+)\(", text, re.M)) == set(_history_lib.SIGNATURES)
+    assert not (ROOT / "include" / "rt_history.h").exists()
+
+
+def test_the_binding_loads_the_library_and_refusals_are_statuses():
+    """Loading binds no device: rth_version is host arithmetic, and rth_accumulate refuses before any launch."""
+    from ray_tracer_s8_amd import _history_lib as hl
+    lib = hl.load()
+    assert lib.rth_version(None) == 1
+    assert lib.rth_accumulate(None, None) == 1
+    rq = _abi.default_request(width=8, height=6, divisions=3, division_no=1, spp=4)
+    one = C.c_void_p(8)                                   # (a non-null, 8-byte aligned address that is never read: every call is refused)
+    planes = dict(accum=one, moments=one, depth=one, hits=one, index=one)
+    state = hl.State(accum=one, moments=one, length=one, depth=one, index=one)
+    good = dict(W=8, R=4, alpha=0.2, n_max=8.0, k_depth=0.1, request=C.pointer(rq), next=state, **planes)
+    bad = [dict(W=0), dict(R=0), dict(R=3), dict(R=6), dict(W=7), dict(alpha=0.0), dict(alpha=1.5), dict(alpha=float("nan")),
+           dict(n_max=0.5), dict(n_max=float("inf")), dict(k_depth=-1.0), dict(k_normal=float("nan")), dict(reserved=1),
+           dict(request=None), dict(accum=None), dict(hits=None), dict(moments=C.c_void_p(4)), dict(next=hl.State()),
+           dict(normal=one),                                                      # with normals, the state needs a normal plane
+           dict(have_prev=1),                                                     # no previous state or request
+           dict(have_prev=1, prev=state, prev_request=C.pointer(rq)),             # reads what it writes
+           dict(W=1 << 24, R=2)]
+    for kw in bad:
+        a = hl.AccumulateArgs(**{**good, **kw})
+        assert lib.rth_accumulate(a, None) in (1, 2), kw
+    cam = _abi.Camera.look_at((0, 0, 0), (0, 0, 0))                               # a pose make_pose refuses
+    a = hl.AccumulateArgs(**good)
+    a.camera = C.pointer(cam)
+    assert lib.rth_accumulate(a, None) == 1
+    with pytest.raises(hl.RthError):
+        hl.check("rth_accumulate", 1)
+
+
+def test_film_reset_with_a_seed_sets_the_films_requests_and_not_the_callers():
+    """On a film put together without a device: reset() reads accum, moments, the stream and torch.cuda.stream only."""
+    from ray_tracer_s8_amd import film as film_mod
+
+    class Plane:
+        zeroed = 0
+
+        def zero_(self):
+            self.zeroed += 1
+
+    mine = [_abi.default_request(width=8, height=6, divisions=3, division_no=k, spp=4, seed=7) for k in range(3)]
+    plan = film_mod.check_job(mine)
+    film = film_mod.Film.__new__(film_mod.Film)
+    film.accum, film.moments, film.stream, film.samples, film.reqs = Plane(), Plane(), None, 3, plan.reqs
+    film._torch = types.SimpleNamespace(cuda=types.SimpleNamespace(stream=lambda s: contextlib.nullcontext()))
+    film.reset()
+    assert [r.seed for r in film.reqs] == [7, 7, 7] and film.samples == 0 and film.accum.zeroed == 1 and film.moments.zeroed == 1
+    film.samples = 2
+    film.reset(seed=0xDEADBEEF12345678)
+    assert [r.seed for r in film.reqs] == [0xDEADBEEF12345678] * 3 and film.samples == 0 and film.accum.zeroed == 2
+    assert [r.seed for r in mine] == [7, 7, 7]
+    assert [r.division_no for r in film.reqs] == [0, 1, 2]
+    for seed in (-1, 1 << 64, 1.5, "7", True):
+        with pytest.raises(ValueError):
+            film.reset(seed=seed)
+        assert [r.seed for r in film.reqs] == [0xDEADBEEF12345678] * 3 and film.accum.zeroed == 2
