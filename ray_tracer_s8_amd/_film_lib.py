@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from . import build as _build
+from . import _private_lib, build as _build
 
 RTF_VERSION = 1
 RTF_OK = 0
@@ -17,10 +17,8 @@ MAX_ITERATIONS = 8
 LDS_PLAN = 0xFFFFFFFF                 # lds_max_step: the plan's own choice
 
 
-class RtfError(RuntimeError):
-    def __init__(self, what: str, status: int):
-        super().__init__(f"{what}: {STATUS.get(status, status)}")
-        self.status = status
+class RtfError(_private_lib.StatusError):
+    STATUS = STATUS
 
 
 class ResolveArgs(C.Structure):
@@ -51,21 +49,9 @@ def check(what: str, status: int) -> None:
 def load(build_if_missing: bool = True) -> C.CDLL:
     """Load librt_film.so (building it with hipcc if it is missing).  Raises if it cannot: there is no fall-back."""
     global _lib
-    if _lib is not None:
-        return _lib
-    path = _build.FILM_LIB_PATH
-    if build_if_missing and not path.exists():
-        path = _build.build_film()
-    lib = C.CDLL(str(path))
-    for name, argtypes in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = argtypes, C.c_int
-    v = C.c_uint32(0)
-    check("rtf_version", lib.rtf_version(C.byref(v)))
-    if v.value != RTF_VERSION:
-        raise RuntimeError(f"{path} is version {v.value}, this binding is version {RTF_VERSION}: rebuild it (build.build_film)")
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = _private_lib.load(_build.FILM, SIGNATURES, RTF_VERSION, RtfError, "build.build_film", build_if_missing)
+    return _lib
 
 
 def resolve_scratch_bytes(width: int, rows: int) -> int:

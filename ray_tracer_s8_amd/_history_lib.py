@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from . import build as _build
+from . import _private_lib, build as _build
 from ._abi import Camera, TileRequest
 
 RTH_VERSION = 1
@@ -17,10 +17,8 @@ RTH_OK = 0
 STATUS = {1: "RTH_ERR_BAD_ARG", 2: "RTH_ERR_LIMIT", 3: "RTH_ERR_HIP", 4: "RTH_ERR_INTERNAL"}
 
 
-class RthError(RuntimeError):
-    def __init__(self, what: str, status: int):
-        super().__init__(f"{what}: {STATUS.get(status, status)}")
-        self.status = status
+class RthError(_private_lib.StatusError):
+    STATUS = STATUS
 
 
 class State(C.Structure):
@@ -56,18 +54,6 @@ def check(what: str, status: int) -> None:
 def load(build_if_missing: bool = True) -> C.CDLL:
     """Load librt_history.so (building it with hipcc if it is missing).  Raises if it cannot: there is no fall-back."""
     global _lib
-    if _lib is not None:
-        return _lib
-    path = _build.HISTORY_LIB_PATH
-    if build_if_missing and not path.exists():
-        path = _build.build_history()
-    lib = C.CDLL(str(path))
-    for name, argtypes in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = argtypes, C.c_int
-    v = C.c_uint32(0)
-    check("rth_version", lib.rth_version(C.byref(v)))
-    if v.value != RTH_VERSION:
-        raise RuntimeError(f"{path} is version {v.value}, this binding is version {RTH_VERSION}: rebuild it (build.build_history)")
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = _private_lib.load(_build.HISTORY, SIGNATURES, RTH_VERSION, RthError, "build.build_history", build_if_missing)
+    return _lib

@@ -1,13 +1,15 @@
-"""Build recipe for the HIP C-ABI library (gfx950 only).
+"""Build recipe for the HIP libraries (gfx950 only): each library is a `Library` value, and the recipe (record, staleness, compile
+and link, build if stale) is written once over it.
 
 `hipcc --offload-arch=gfx950` cross-compiles without a GPU, so this runs in the CPU
-container too.  The .so is built in-tree (ray_tracer_s8_amd/lib/) so it travels to the
-GPU box with the repo snapshot; it is git-ignored, not gpurun-ignored.
+container too.  The .so files are built in-tree (ray_tracer_s8_amd/lib/) so they travel to the
+GPU box with a snapshot of the working tree; git ignores them.
 """
 from __future__ import annotations
 
 import os
 import subprocess
+from dataclasses import dataclass, replace
 from pathlib import Path
 
 PKG = Path(__file__).resolve().parent
@@ -18,6 +20,7 @@ LIB_DIR = PKG / "lib"
 # directory — the product library lib/librt_s8.so is never rebuilt in place by an A/B run (round-2 advisor)
 VARIANT = os.environ.get("RT_LIB_VARIANT", "")
 LIB_PATH = LIB_DIR / (f"librt_s8_{VARIANT}.so" if VARIANT else "librt_s8.so")
+DEBUG_LIB_PATH = LIB_DIR / "librt_s8_dbg.so"
 
 # -ffp-contract=off: the kernel must perform the reference's IEEE binary32 operations one
 # by one (Rust never contracts a*b+c); FMA appears only where written as __builtin_fmaf.
@@ -54,219 +57,165 @@ UNITS = [
 ]
 
 
-def _deps() -> list[Path]:
-    """Everything a library is compiled from: every file under csrc/, subdirectories included (a new header cannot be forgotten; a
-    stray file there costs a rebuild, never a stale library), the C header, this recipe."""
-    return sorted(f for f in CSRC.rglob("*") if f.is_file()) + [ROOT / "include" / "rt_tile.h", Path(__file__)]
+@dataclass(frozen=True)
+class Library:
+    """One shared library as data.  Every function of the recipe below reads its argument only, so a test hands them a copy
+    (dataclasses.replace(lib, path=...)) instead of patching this module."""
+    path: Path                     # the .so; its record, the exact compile lines it was built with, is path.with_suffix(".flags")
+    obj_dir: Path
+    src_dir: Path
+    units: tuple                   # (file under src_dir, the flags that unit adds after the include directories)
+    extra: tuple = ()              # flags of every unit, ahead of the include directories
+    include_dirs: tuple = ()
+    deps: tuple = ()               # what staleness looks at: files, and directories taken with every file under them
+    as_built: bool = False         # used as it was built: only a missing file or record makes it stale
+
+    @property
+    def record_path(self) -> Path:
+        return self.path.with_suffix(".flags")
 
 
-FLAGS_PATH = LIB_PATH.with_suffix(".flags")      # the exact compile lines of the library next to it
+INCLUDE = ROOT / "include"
+# The product and the test library are compiled from everything under csrc/, subdirectories included (a new header cannot be
+# forgotten; a stray file there costs a rebuild, never a stale library), the C header and this recipe.
+_CSRC_DEPS = (CSRC, INCLUDE / "rt_tile.h", Path(__file__))
+
+# The PRODUCT with the default flags: it exports exactly include/rt_tile.h (tests/test_surface.py).  _product() is the product as
+# asked for now, RT_EXTRA_HIPCC_FLAGS included.
+PRODUCT = Library(LIB_PATH, LIB_DIR / (f"obj_{VARIANT}" if VARIANT else "obj"), CSRC, tuple(UNITS), include_dirs=(INCLUDE, CSRC),
+                  deps=_CSRC_DEPS)
 
 # The TEST library: the product sources plus -DRT_DEBUG_HOOKS, which compiles the rt_debug_* entry points (launch-path knobs,
 # counter read-back, a throwing body, the sqrt self-test, the unit kernels of rt_unit.hip.h and rt_unit_sampling.hip.h) that tests
 # and tools use.
-# The product library exports exactly include/rt_tile.h (tests/test_surface.py checks both).
-DEBUG_VARIANT = "dbg"
 DEBUG_FLAGS = ["-DRT_DEBUG_HOOKS"]
-DEBUG_LIB_PATH = LIB_DIR / f"librt_s8_{DEBUG_VARIANT}.so"
+DEBUG = replace(PRODUCT, path=DEBUG_LIB_PATH, obj_dir=LIB_DIR / "obj_dbg", extra=tuple(DEBUG_FLAGS))
 
 
-# The FILM library: the moments fold and the variance-guided resolve of film.py (DESIGN.md 4.23), a second, private library that
-# only ray_tracer_s8_amd/_film_lib.py loads.  Its sources lie beside csrc/, not under it (_deps() globs csrc/ for the libraries
-# above), it exports only rtf_* names, and it takes no RT_EXTRA_HIPCC_FLAGS: experiments are the product library's.
-FILM_CSRC = PKG / "film_csrc"
-FILM_UNIT = "rt_film.hip"
-FILM_FLAGS = ["-fno-slp-vectorize"]
-FILM_LIB_PATH = LIB_DIR / "librt_film.so"
-FILM_FLAGS_PATH = FILM_LIB_PATH.with_suffix(".flags")
+def _private(name: str, headers: tuple) -> Library:
+    """A private library: lib/librt_<name>.so from the one unit <name>_csrc/rt_<name>.hip, loaded by a binding module of its own
+    (_private_lib.py) and no part of the tile ABI.  Its sources lie beside csrc/, not under it, so they are no dependency of any
+    other library; its own dependencies are its directory, the csrc/ headers it includes (named here), the C header and this
+    recipe.  The product's flags plus -fno-slp-vectorize, and never RT_EXTRA_HIPCC_FLAGS: experiments are the product library's."""
+    src = PKG / f"{name}_csrc"
+    return Library(LIB_DIR / f"librt_{name}.so", LIB_DIR / f"obj_{name}", src, ((f"rt_{name}.hip", ()),), extra=("-fno-slp-vectorize",),
+                   include_dirs=(INCLUDE, CSRC, src),
+                   deps=(src, *(CSRC / h for h in headers), INCLUDE / "rt_tile.h", Path(__file__)))
 
 
-def _film_deps() -> list[Path]:
-    """What the film library is compiled from: film_csrc/, the three csrc/ headers it includes (and the C header rt_plan.h reads),
-    this recipe."""
-    return sorted(f for f in FILM_CSRC.rglob("*") if f.is_file()) + [CSRC / "rt_denoise_math.h", CSRC / "rt_consts.h", CSRC / "rt_plan.h",
-                                                                    ROOT / "include" / "rt_tile.h", Path(__file__)]
+# The FILM library: the moments fold and the variance-guided resolve of film.py (DESIGN.md 4.23); rtf_* exports, _film_lib.py.
+FILM = _private("film", ("rt_denoise_math.h", "rt_consts.h", "rt_plan.h"))
+# The HISTORY library: the temporal accumulation of film_history.py (DESIGN.md 4.24); rth_* exports, _history_lib.py.
+HISTORY = _private("history", ("rt_consts.h", "rt_plan.h"))
+# (the names the export tests know the private libraries and their headers by)
+FILM_LIB_PATH, FILM_CSRC = FILM.path, FILM.src_dir
+HISTORY_LIB_PATH, HISTORY_CSRC = HISTORY.path, HISTORY.src_dir
+
+LIBRARIES = (PRODUCT, DEBUG, FILM, HISTORY)
 
 
-# The HISTORY library: the temporal accumulation of film_history.py (DESIGN.md 4.24), a third, private library that only
-# ray_tracer_s8_amd/_history_lib.py loads.  Built like the film library: sources beside csrc/, rth_* exports only, the product's flags
-# plus -fno-slp-vectorize, no RT_EXTRA_HIPCC_FLAGS, a record and a staleness check of its own.
-HISTORY_CSRC = PKG / "history_csrc"
-HISTORY_UNIT = "rt_history.hip"
-HISTORY_FLAGS = ["-fno-slp-vectorize"]
-HISTORY_LIB_PATH = LIB_DIR / "librt_history.so"
-HISTORY_FLAGS_PATH = HISTORY_LIB_PATH.with_suffix(".flags")
+def _product(extra: list[str] | None = None) -> Library:
+    """The product as asked for NOW: RT_EXTRA_HIPCC_FLAGS (experiments only, e.g. -DRT_MAXC=12) is read at every call.  A prebuilt
+    experiment variant (RT_LIB_VARIANT set, RT_EXTRA_HIPCC_FLAGS not) is used as it was built: its flags are in its record."""
+    env = os.environ.get("RT_EXTRA_HIPCC_FLAGS")
+    return replace(PRODUCT, extra=tuple((env or "").split() if extra is None else extra), as_built=bool(VARIANT) and env is None)
 
 
-def _history_deps() -> list[Path]:
-    """What the history library is compiled from: history_csrc/, the two csrc/ headers it includes (and the C header they read), this
-    recipe."""
-    return sorted(f for f in HISTORY_CSRC.rglob("*") if f.is_file()) + [CSRC / "rt_consts.h", CSRC / "rt_plan.h",
-                                                                       ROOT / "include" / "rt_tile.h", Path(__file__)]
-
-
-def _extra_flags() -> list[str]:
-    return os.environ.get("RT_EXTRA_HIPCC_FLAGS", "").split()          # experiments only (e.g. -DRT_MAXC=12)
-
-
-def flags_record(extra: list[str] | None = None) -> str:
+def record(lib: Library) -> str:
     """What the library was (or would be) compiled with: one line per translation unit.  A library whose record differs
     from the flags asked for NOW is stale whatever its mtime — an A/B script that died before restoring the default
     build (tools/ab*.sh, phase_time.py: -DRT_PROFILE_TIME, experimental -D knobs) would otherwise leave a variant that
     looks fresh, travels to the GPU box and gets benchmarked."""
-    extra = _extra_flags() if extra is None else extra
-    common = [f for f in HIPCC_FLAGS if f != "-shared"] + extra
-    return "".join(f"{unit}: {' '.join(common + flags)}\n" for unit, flags in UNITS)
+    common = [f for f in HIPCC_FLAGS if f != "-shared"] + list(lib.extra)
+    return "".join(f"{unit}: {' '.join(common + list(flags))}\n" for unit, flags in lib.units)
 
 
-def built_with_default_flags() -> bool:
-    """True iff the library on disk was compiled with exactly HIPCC_FLAGS (no RT_EXTRA_HIPCC_FLAGS)."""
-    return LIB_PATH.exists() and FLAGS_PATH.exists() and FLAGS_PATH.read_text() == flags_record([])
+def dep_files(lib: Library) -> list[Path]:
+    """lib.deps as files, the directories read now: a file added to one is a dependency from then on."""
+    return [f for d in lib.deps for f in (sorted(p for p in d.rglob("*") if p.is_file()) if d.is_dir() else [d])]
 
 
-def needs_build() -> bool:
-    if not LIB_PATH.exists() or not FLAGS_PATH.exists():
+def stale(lib: Library) -> bool:
+    """Missing, built with other flags than record(lib), or older than one of its dependencies."""
+    if not lib.path.exists() or not lib.record_path.exists():
         return True
-    if VARIANT and "RT_EXTRA_HIPCC_FLAGS" not in os.environ:
-        return False          # a prebuilt experiment variant is used as it was built (its flags are in its record)
-    if FLAGS_PATH.read_text() != flags_record():
+    if lib.as_built:
+        return False
+    if lib.record_path.read_text() != record(lib):
         return True
-    t = LIB_PATH.stat().st_mtime
-    return any(d.stat().st_mtime > t for d in _deps())
+    t = lib.path.stat().st_mtime
+    return any(d.stat().st_mtime > t for d in dep_files(lib))
 
 
-def _compile(lib_path: Path, flags_path: Path, obj_dir: Path, extra: list[str], verbose: bool) -> Path:
-    LIB_DIR.mkdir(parents=True, exist_ok=True)
+def compile_and_link(lib: Library, verbose: bool = False) -> Path:
+    """Compile the units side by side (they are independent), then link.  Raises on failure (no fallback)."""
     hipcc = os.environ.get("HIPCC", "hipcc")
-    if flags_path.exists():
-        flags_path.unlink()                       # no record while the objects are in flux
-    obj_dir.mkdir(exist_ok=True)
-    common = [f for f in HIPCC_FLAGS if f != "-shared"] + extra + [f"-I{ROOT / 'include'}", f"-I{CSRC}"]
-    cmds, objs = [], []
-    for unit, flags in UNITS:
-        obj = obj_dir / (Path(unit).stem + ".o")
-        objs.append(str(obj))
-        cmds.append([hipcc, *common, *flags, "-c", str(CSRC / unit), "-o", str(obj)])
-    cmds.append([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(lib_path), *objs])
-    # the compiles are independent: run them side by side, then link
+    lib.path.parent.mkdir(parents=True, exist_ok=True)
+    lib.record_path.unlink(missing_ok=True)           # no record while the objects are in flux
+    lib.obj_dir.mkdir(parents=True, exist_ok=True)
+    common = [f for f in HIPCC_FLAGS if f != "-shared"] + list(lib.extra) + [f"-I{d}" for d in lib.include_dirs]
+    objs = [str(lib.obj_dir / (Path(unit).stem + ".o")) for unit, _ in lib.units]
+    cmds = [[hipcc, *common, *flags, "-c", str(lib.src_dir / unit), "-o", obj] for (unit, flags), obj in zip(lib.units, objs)]
+    link = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(lib.path), *objs]
     procs = []
-    for cmd in cmds[:-1]:
+    for cmd in cmds:
         if verbose:
             print(" ".join(cmd))
         procs.append(subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-    for cmd, pr in zip(cmds[:-1], procs):
+    for cmd, pr in zip(cmds, procs):
         so, se = pr.communicate()
         if pr.returncode != 0:
             raise RuntimeError(f"hipcc failed ({pr.returncode}): {' '.join(cmd)}\n{so}\n{se}")
     if verbose:
-        print(" ".join(cmds[-1]))
-    proc = subprocess.run(cmds[-1], capture_output=True, text=True)
+        print(" ".join(link))
+    proc = subprocess.run(link, capture_output=True, text=True)
     if proc.returncode != 0:
         raise RuntimeError(f"hipcc link failed ({proc.returncode}):\n{proc.stdout}\n{proc.stderr}")
-    flags_path.write_text(flags_record(extra))
-    return lib_path
+    lib.record_path.write_text(record(lib))
+    return lib.path
+
+
+def ensure(lib: Library, force: bool = False, verbose: bool = False) -> Path:
+    """Build the library if it is missing or stale, or if forced."""
+    return compile_and_link(lib, verbose) if force or stale(lib) else lib.path
+
+
+def flags_record(extra: list[str] | None = None) -> str:
+    """The product's record with `extra` in the place of RT_EXTRA_HIPCC_FLAGS."""
+    return record(_product(extra))
+
+
+def built_with_default_flags() -> bool:
+    """True iff the library on disk was compiled with exactly HIPCC_FLAGS (no RT_EXTRA_HIPCC_FLAGS)."""
+    return LIB_PATH.exists() and PRODUCT.record_path.exists() and PRODUCT.record_path.read_text() == record(PRODUCT)
+
+
+def needs_build() -> bool:
+    return stale(_product())
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
     """Compile librt_s8.so (or the RT_LIB_VARIANT named) if missing or stale, and with no variant named the film library and the
-    history library next to it.  Raises on failure (no fallback)."""
-    if not VARIANT:
-        build_film(force, verbose)
-        build_history(force, verbose)
-    if not force and not needs_build():
-        return LIB_PATH
-    return _compile(LIB_PATH, FLAGS_PATH, LIB_DIR / (f"obj_{VARIANT}" if VARIANT else "obj"), _extra_flags(), verbose)
+    history library first."""
+    for lib in () if VARIANT else (FILM, HISTORY):
+        ensure(lib, force, verbose)
+    return ensure(_product(), force, verbose)
 
 
 def build_debug(force: bool = False, verbose: bool = False) -> Path:
-    """Compile the test library lib/librt_s8_dbg.so (product sources + -DRT_DEBUG_HOOKS) if missing or stale."""
-    fp = DEBUG_LIB_PATH.with_suffix(".flags")
-    stale = (not DEBUG_LIB_PATH.exists() or not fp.exists() or fp.read_text() != flags_record(DEBUG_FLAGS)
-             or any(d.stat().st_mtime > DEBUG_LIB_PATH.stat().st_mtime for d in _deps()))
-    if not force and not stale:
-        return DEBUG_LIB_PATH
-    return _compile(DEBUG_LIB_PATH, fp, LIB_DIR / f"obj_{DEBUG_VARIANT}", DEBUG_FLAGS, verbose)
-
-
-def film_flags_record() -> str:
-    """The compile line of the film library's one translation unit (its own record, lib/librt_film.flags)."""
-    return f"{FILM_UNIT}: {' '.join([f for f in HIPCC_FLAGS if f != '-shared'] + FILM_FLAGS)}\n"
-
-
-def film_needs_build() -> bool:
-    if not FILM_LIB_PATH.exists() or not FILM_FLAGS_PATH.exists() or FILM_FLAGS_PATH.read_text() != film_flags_record():
-        return True
-    t = FILM_LIB_PATH.stat().st_mtime
-    return any(d.stat().st_mtime > t for d in _film_deps())
+    return ensure(DEBUG, force, verbose)
 
 
 def build_film(force: bool = False, verbose: bool = False) -> Path:
-    """Compile lib/librt_film.so (film_csrc/) if missing or stale: the product's flags, linked like the product
-    library, with a flags record and a staleness check of its own.  Raises on failure (no fallback)."""
-    if not force and not film_needs_build():
-        return FILM_LIB_PATH
-    LIB_DIR.mkdir(parents=True, exist_ok=True)
-    hipcc = os.environ.get("HIPCC", "hipcc")
-    if FILM_FLAGS_PATH.exists():
-        FILM_FLAGS_PATH.unlink()
-    obj_dir = LIB_DIR / "obj_film"
-    obj_dir.mkdir(exist_ok=True)
-    obj = obj_dir / (Path(FILM_UNIT).stem + ".o")
-    common = [f for f in HIPCC_FLAGS if f != "-shared"] + FILM_FLAGS
-    cmds = [[hipcc, *common, f"-I{ROOT / 'include'}", f"-I{CSRC}", f"-I{FILM_CSRC}", "-c", str(FILM_CSRC / FILM_UNIT), "-o", str(obj)],
-            [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(FILM_LIB_PATH), str(obj)]]
-    for cmd in cmds:
-        if verbose:
-            print(" ".join(cmd))
-        proc = subprocess.run(cmd, capture_output=True, text=True)
-        if proc.returncode != 0:
-            raise RuntimeError(f"hipcc failed ({proc.returncode}): {' '.join(cmd)}\n{proc.stdout}\n{proc.stderr}")
-    FILM_FLAGS_PATH.write_text(film_flags_record())
-    return FILM_LIB_PATH
-
-
-def history_flags_record() -> str:
-    """The compile line of the history library's one translation unit (its own record, lib/librt_history.flags)."""
-    return f"{HISTORY_UNIT}: {' '.join([f for f in HIPCC_FLAGS if f != '-shared'] + HISTORY_FLAGS)}\n"
-
-
-def history_needs_build() -> bool:
-    if (not HISTORY_LIB_PATH.exists() or not HISTORY_FLAGS_PATH.exists()
-            or HISTORY_FLAGS_PATH.read_text() != history_flags_record()):
-        return True
-    t = HISTORY_LIB_PATH.stat().st_mtime
-    return any(d.stat().st_mtime > t for d in _history_deps())
+    return ensure(FILM, force, verbose)
 
 
 def build_history(force: bool = False, verbose: bool = False) -> Path:
-    """Compile lib/librt_history.so (history_csrc/) if missing or stale, as build_film compiles the film library.
-    Raises on failure (no fallback)."""
-    if not force and not history_needs_build():
-        return HISTORY_LIB_PATH
-    LIB_DIR.mkdir(parents=True, exist_ok=True)
-    hipcc = os.environ.get("HIPCC", "hipcc")
-    if HISTORY_FLAGS_PATH.exists():
-        HISTORY_FLAGS_PATH.unlink()
-    obj_dir = LIB_DIR / "obj_history"
-    obj_dir.mkdir(exist_ok=True)
-    obj = obj_dir / (Path(HISTORY_UNIT).stem + ".o")
-    common = [f for f in HIPCC_FLAGS if f != "-shared"] + HISTORY_FLAGS
-    cmds = [[hipcc, *common, f"-I{ROOT / 'include'}", f"-I{CSRC}", f"-I{HISTORY_CSRC}", "-c", str(HISTORY_CSRC / HISTORY_UNIT),
-             "-o", str(obj)],
-            [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(HISTORY_LIB_PATH), str(obj)]]
-    for cmd in cmds:
-        if verbose:
-            print(" ".join(cmd))
-        proc = subprocess.run(cmd, capture_output=True, text=True)
-        if proc.returncode != 0:
-            raise RuntimeError(f"hipcc failed ({proc.returncode}): {' '.join(cmd)}\n{proc.stdout}\n{proc.stderr}")
-    HISTORY_FLAGS_PATH.write_text(history_flags_record())
-    return HISTORY_LIB_PATH
+    return ensure(HISTORY, force, verbose)
 
 
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
     if not VARIANT:
-        print(build_debug(force=True, verbose=True))
-        print(build_film(force=True, verbose=True))
-        print(build_history(force=True, verbose=True))
+        for lib in (DEBUG, FILM, HISTORY):
+            print(ensure(lib, force=True, verbose=True))

@@ -330,6 +330,18 @@ class Film:
     def _strip_ptrs(self, frame):
         return [self._strip(frame, i).data_ptr() for i in range(len(self.reqs))]
 
+    def _plane_spec(self, name: str) -> tuple:
+        """(shape, dtype) of a feature plane: albedo and normal (R, W, 3), the rest (R, W); hits and index int32, the rest float32."""
+        shape = (self.rows, self.width, 3) if name in ("albedo", "normal") else (self.rows, self.width)
+        return shape, self._torch.int32 if name in ("hits", "index") else self._torch.float32
+
+    def _check_plane(self, name: str, t) -> None:
+        """A caller's tensor against _plane_spec: contiguous, on the film's device, of that shape and dtype."""
+        shape, dtype = self._plane_spec(name)
+        if tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+            raise ValueError(f"planes[{name!r}]: need a contiguous {dtype} tensor of shape {shape} on {self.device}, as features() "
+                             "returns it")
+
     def features(self, aov_samples: int = 1, planes: Sequence[str] = FEATURE_PLANES) -> dict:
         """The feature buffers of the frame over samples [0, aov_samples) (rt_scene_render_aovs_device), as frame-shaped tensors laid
         out like accum: albedo and normal (R, W, 3) float32, depth (R, W) float32, hits and index (R, W) int32 holding the uint32
@@ -344,8 +356,7 @@ class Film:
         with torch.cuda.stream(self.stream):
             out = {}
             for n in names:
-                shape = (self.rows, self.width, 3) if n in ("albedo", "normal") else (self.rows, self.width)
-                dtype = torch.int32 if n in ("hits", "index") else torch.float32
+                shape, dtype = self._plane_spec(n)
                 t = self.planes.get(n)
                 out[n] = t.zero_() if t is not None else torch.zeros(shape, dtype=dtype, device=self.device)
             ptrs = {n: self._strip_ptrs(t) for n, t in out.items()}
@@ -356,18 +367,13 @@ class Film:
         return dict(out)
 
     def _check_planes(self, planes: Optional[dict]) -> dict:
-        torch = self._torch
         guide = {}
         for n, t in (planes or {}).items():
             if n == "index" or t is None:
                 continue
             if n not in FEATURE_PLANES:
                 raise ValueError(f"planes: unknown plane {n!r}")
-            shape = (self.rows, self.width, 3) if n in ("albedo", "normal") else (self.rows, self.width)
-            dtype = torch.int32 if n == "hits" else torch.float32
-            if tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"planes[{n!r}]: need a contiguous {dtype} tensor of shape {shape} on {self.device}, as features() "
-                                 "returns it")
+            self._check_plane(n, t)
             guide[n] = t
         if guide and not self.aov_samples:
             raise ValueError("planes: call features() first, it sets their sample count")

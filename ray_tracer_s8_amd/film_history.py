@@ -139,19 +139,13 @@ class FilmHistory:
     # ---- a frame
 
     def _check_planes(self, planes) -> dict:
-        film, torch = self.film, self.film._torch
         names = REQUIRED_PLANES + (("normal",) if self.k_normal is not None else ())
         given = planes or {}
         missing = [n for n in names if given.get(n) is None]
         if missing:
             raise ValueError(f"planes: need {names} as film.features() returns them, {missing} missing")
         for n in names:
-            t = given[n]
-            shape = (film.rows, film.width, 3) if n == "normal" else (film.rows, film.width)
-            dtype = torch.int32 if n in ("hits", "index") else torch.float32
-            if tuple(t.shape) != shape or t.dtype != dtype or t.device != film.device or not t.is_contiguous():
-                raise ValueError(f"planes[{n!r}]: need a contiguous {dtype} tensor of shape {shape} on {film.device}, as features() "
-                                 "returns it")
+            self.film._check_plane(n, given[n])
         return {n: given[n] for n in names}
 
     def accumulate(self, camera: Optional[Camera], planes: dict) -> dict:

@@ -97,10 +97,15 @@ def write_json(path=FIXTURE):
     Path(path).write_text(json.dumps(surface(), indent=1) + "\n")
 
 
-def exported(path):
-    """The rt_* symbols a shared library defines (`nm -D`)."""
+def all_exported(path):
+    """Every symbol a shared library defines (`nm -D`)."""
     out = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
-    return {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("rt_")}
+    return {ln.split()[-1] for ln in out.splitlines() if ln.split()}
+
+
+def exported(path):
+    """The rt_* symbols a shared library defines."""
+    return {s for s in all_exported(path) if s.startswith("rt_")}
 
 
 def check_abi_version_unchanged():

@@ -2,12 +2,10 @@
 1. check_guided refuses, with ValueError, everything resolve_guided and variance refuse, and accepts the rest;
 2. film.py and _film_lib.py import without torch and without loading the film library;
 3. Film(None, reqs, moments=True) runs check_job first;
-4. the product library's build record and staleness check are unaffected by the film library's presence or staleness, and the film
-   library keeps a record of its own;
-5. librt_s8.so still exports exactly the header, no rtf_ symbol is in either librt_s8*.so, and librt_film.so exports the four rtf_
+4. librt_s8.so still exports exactly the header, no rtf_ symbol is in any other library, and librt_film.so exports the four rtf_
    functions of film_csrc/rt_film.h; the binding's table names exactly those.
+The film library's record and staleness are tests/test_build_recipe.py's.
 Without the feature every test here fails: there is no check_guided, no _film_lib and no build_film."""
-import os
 import re
 import subprocess
 import sys
@@ -110,60 +108,15 @@ def test_abi_module_holds_nothing_of_the_film_library():
     assert names == [], names
 
 
-def test_the_product_build_is_unaffected_by_the_film_library(tmp_path, monkeypatch):
-    """needs_build() and flags_record() read LIB_PATH, its record and _deps() only: the film library missing, present or stale does not
-    change them, and the film library's sources are no dependency of the product library."""
-    assert build.FILM_LIB_PATH == build.LIB_DIR / "librt_film.so" and build.FILM_LIB_PATH != build.LIB_PATH
-    assert not any(build.FILM_CSRC in d.parents for d in build._deps())
-    assert build.CSRC not in build.FILM_CSRC.parents and build.FILM_CSRC.parent == build.CSRC.parent
-    if "RT_LIB_VARIANT" not in os.environ:
-        assert build.LIB_PATH.name == "librt_s8.so"
-    record, need = build.flags_record(), build.needs_build()
-    assert "rt_film" not in record and len(record.splitlines()) == len(build.UNITS)
-    missing = tmp_path / "librt_film.so"
-    monkeypatch.setattr(build, "FILM_LIB_PATH", missing)
-    monkeypatch.setattr(build, "FILM_FLAGS_PATH", missing.with_suffix(".flags"))
-    assert build.film_needs_build()
-    assert build.flags_record() == record and build.needs_build() == need
-    # present, with a record of other flags: stale for build_film, nothing to the product
-    missing.write_bytes(b"")
-    missing.with_suffix(".flags").write_text("rt_film.hip: -O0\n")
-    assert build.film_needs_build()
-    assert build.flags_record() == record and build.needs_build() == need
-    # present with the right record, but older than its sources: stale again
-    missing.with_suffix(".flags").write_text(build.film_flags_record())
-    os.utime(missing, (1, 1))
-    assert build.film_needs_build()
-    assert build.flags_record() == record and build.needs_build() == need
-    os.utime(missing, None)
-    assert not build.film_needs_build()
-
-
-def test_the_film_library_is_compiled_with_the_products_flags():
-    path = build.build_film()
-    assert path == build.FILM_LIB_PATH and path.exists() and not build.film_needs_build()
-    line = build.FILM_FLAGS_PATH.read_text()
-    assert line == build.film_flags_record() and line.startswith("rt_film.hip: ")
-    flags = line.split(": ", 1)[1].split()
-    assert flags == [f for f in build.HIPCC_FLAGS if f != "-shared"] + ["-fno-slp-vectorize"]
-    assert "-ffp-contract=off" in flags and "--offload-arch=gfx950" in flags
-    assert not any("correctly-rounded" in f or "fast-math" in f for f in flags)          # correctly rounded div / sqrt: the default
-
-
-def _all_exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
-    return {ln.split()[-1] for ln in out.splitlines() if ln.split()}
-
-
 def test_exports():
     from ray_tracer_s8_amd import _film_lib
     _abi.load()
     _abi.load_debug()
     declared = set(_surface.parse()["functions"])
     assert len(declared) == 51 and _surface.exported(build.LIB_PATH) == declared
-    for path in (build.LIB_PATH, build.DEBUG_LIB_PATH):
-        assert not [s for s in _all_exported(path) if "rtf_" in s], path
-    film = {s for s in _all_exported(build.build_film()) if not s.startswith("_")}
+    for path in (build.LIB_PATH, build.DEBUG_LIB_PATH, build.build_history()):
+        assert not [s for s in _surface.all_exported(path) if "rtf_" in s], path
+    film = {s for s in _surface.all_exported(build.build_film()) if not s.startswith("_")}
     assert film == set(_film_lib.SIGNATURES), film
     assert not _surface.exported(build.FILM_LIB_PATH)
     # the private header declares exactly the functions the binding names

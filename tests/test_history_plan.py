@@ -3,14 +3,12 @@
 2. film_history.py and _history_lib.py import without torch and without loading the history library;
 3. librt_history.so exports exactly _history_lib.SIGNATURES, all rth_*, and the private header declares exactly those; librt_s8.so,
    librt_s8_dbg.so and librt_film.so export what they exported;
-4. the product's and the film library's build records and staleness checks are unaffected by the history library being missing,
-   present or stale, and the history library keeps a record of its own;
-5. rth_accumulate refuses bad arguments with a status, before any launch;
-6. Film.reset(seed=...) sets the seed of the film's own requests, not the caller's.
+4. rth_accumulate refuses bad arguments with a status, before any launch;
+5. Film.reset(seed=...) sets the seed of the film's own requests, not the caller's.
+The history library's record and staleness are tests/test_build_recipe.py's.
 Without the feature every test here fails: there is no film_history, no _history_lib and no build_history."""
 import contextlib
 import ctypes as C
-import os
 import re
 import subprocess
 import sys
@@ -103,50 +101,6 @@ def test_abi_module_holds_nothing_of_the_history_library():
     assert names == [], names
 
 
-def test_the_other_builds_are_unaffected_by_the_history_library(tmp_path, monkeypatch):
-    """needs_build(), flags_record(), film_needs_build() and film_flags_record() do not read the history library, its record or its
-    sources; the history library has a record and a staleness check of its own."""
-    assert build.HISTORY_LIB_PATH == build.LIB_DIR / "librt_history.so"
-    assert build.HISTORY_LIB_PATH not in (build.LIB_PATH, build.FILM_LIB_PATH, build.DEBUG_LIB_PATH)
-    assert not any(build.HISTORY_CSRC in d.parents for d in build._deps() + build._film_deps())
-    assert build.HISTORY_CSRC.parent == build.CSRC.parent and build.HISTORY_CSRC not in (build.CSRC, build.FILM_CSRC)
-    assert any(build.HISTORY_CSRC in d.parents for d in build._history_deps())
-    build.build_film()
-    state = lambda: (build.flags_record(), build.needs_build(), build.film_flags_record(), build.film_needs_build())
-    before = state()
-    assert "rt_history" not in before[0] + before[2] and len(before[0].splitlines()) == len(build.UNITS)
-    missing = tmp_path / "librt_history.so"
-    monkeypatch.setattr(build, "HISTORY_LIB_PATH", missing)
-    monkeypatch.setattr(build, "HISTORY_FLAGS_PATH", missing.with_suffix(".flags"))
-    assert build.history_needs_build() and state() == before
-    # present, with a record of other flags: stale for build_history, nothing to the others
-    missing.write_bytes(b"")
-    missing.with_suffix(".flags").write_text("rt_history.hip: -O0\n")
-    assert build.history_needs_build() and state() == before
-    # present with the right record, but older than its sources: stale again
-    missing.with_suffix(".flags").write_text(build.history_flags_record())
-    os.utime(missing, (1, 1))
-    assert build.history_needs_build() and state() == before
-    os.utime(missing, None)
-    assert not build.history_needs_build() and state() == before
-
-
-def test_the_history_library_is_compiled_with_the_products_flags():
-    path = build.build_history()
-    assert path == build.HISTORY_LIB_PATH and path.exists() and not build.history_needs_build()
-    line = build.HISTORY_FLAGS_PATH.read_text()
-    assert line == build.history_flags_record() and line.startswith("rt_history.hip: ")
-    flags = line.split(": ", 1)[1].split()
-    assert flags == [f for f in build.HIPCC_FLAGS if f != "-shared"] + ["-fno-slp-vectorize"]
-    assert "-ffp-contract=off" in flags and "--offload-arch=gfx950" in flags
-    assert not any("correctly-rounded" in f or "fast-math" in f for f in flags)          # correctly rounded div / sqrt: the default
-
-
-def _all_exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
-    return {ln.split()[-1] for ln in out.splitlines() if ln.split()}
-
-
 def test_exports():
     from ray_tracer_s8_amd import _film_lib, _history_lib
     _abi.load()
@@ -154,10 +108,10 @@ def test_exports():
     declared = set(_surface.parse()["functions"])
     assert len(declared) == 51 and _surface.exported(build.LIB_PATH) == declared
     for path in (build.LIB_PATH, build.DEBUG_LIB_PATH, build.build_film()):
-        assert not [s for s in _all_exported(path) if "rth_" in s], path
-    film = {s for s in _all_exported(build.FILM_LIB_PATH) if not s.startswith("_")}
+        assert not [s for s in _surface.all_exported(path) if "rth_" in s], path
+    film = {s for s in _surface.all_exported(build.FILM_LIB_PATH) if not s.startswith("_")}
     assert film == set(_film_lib.SIGNATURES) == {"rtf_version", "rtf_fold_moments", "rtf_resolve_scratch_bytes", "rtf_resolve"}
-    history = {s for s in _all_exported(build.build_history()) if not s.startswith("_")}
+    history = {s for s in _surface.all_exported(build.build_history()) if not s.startswith("_")}
     assert history == set(_history_lib.SIGNATURES) and all(s.startswith("rth_") for s in history), history
     assert not _surface.exported(build.HISTORY_LIB_PATH)
     # the private header declares exactly the functions the binding names
