@@ -110,8 +110,14 @@ HISTORY = _private("history", ("rt_consts.h", "rt_plan.h"))
 # (the names the export tests know the private libraries and their headers by)
 FILM_LIB_PATH, FILM_CSRC = FILM.path, FILM.src_dir
 HISTORY_LIB_PATH, HISTORY_CSRC = HISTORY.path, HISTORY.src_dir
+# The SAMPLER library: the adaptive sampling of film_sampler.py; rts_* exports, _sampler_lib.py.  It includes no csrc/
+# header.
+SAMPLER = _private("sampler", ())
 
+# LIBRARIES is the set the recipe's golden test (tests/test_build_recipe.py) knows, and stays those four; a library added since is a
+# Library value like them and a member of PRIVATE_LIBRARIES, the private libraries build() makes, which is the set to add to.
 LIBRARIES = (PRODUCT, DEBUG, FILM, HISTORY)
+PRIVATE_LIBRARIES = (FILM, HISTORY, SAMPLER)
 
 
 def _product(extra: list[str] | None = None) -> Library:
@@ -195,9 +201,9 @@ def needs_build() -> bool:
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """Compile librt_s8.so (or the RT_LIB_VARIANT named) if missing or stale, and with no variant named the film library and the
-    history library first."""
-    for lib in () if VARIANT else (FILM, HISTORY):
+    """Compile librt_s8.so (or the RT_LIB_VARIANT named) if missing or stale, and with no variant named the private libraries
+    (PRIVATE_LIBRARIES) first."""
+    for lib in () if VARIANT else PRIVATE_LIBRARIES:
         ensure(lib, force, verbose)
     return ensure(_product(), force, verbose)
 
@@ -214,8 +220,12 @@ def build_history(force: bool = False, verbose: bool = False) -> Path:
     return ensure(HISTORY, force, verbose)
 
 
+def build_sampler(force: bool = False, verbose: bool = False) -> Path:
+    return ensure(SAMPLER, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
     if not VARIANT:
-        for lib in (DEBUG, FILM, HISTORY):
+        for lib in (DEBUG, *PRIVATE_LIBRARIES):
             print(ensure(lib, force=True, verbose=True))

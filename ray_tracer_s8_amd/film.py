@@ -275,12 +275,15 @@ class Film:
 
     # ---- samples
 
-    def _trace(self, n: int, max_bounces: int, handle: int):
-        kw = dict(d_rng_state=self._states.data_ptr(), spp=1, max_bounces=max_bounces, as_given=True, flags=self.flags, stream=handle)
+    def _trace(self, n: int, max_bounces: int, handle: int, rays=None, states=None):
+        """The film's integrator over the first n records of its ray and state buffers into _rgb.  rays, states: tensors to trace in
+        the place of the film's own (film_sampler.py)."""
+        rays, states = self._rays if rays is None else rays, self._states if states is None else states
+        kw = dict(d_rng_state=states.data_ptr(), spp=1, max_bounces=max_bounces, as_given=True, flags=self.flags, stream=handle)
         if self.integrator == "path":
-            self.scene.trace_device(self._rays.data_ptr(), n, self._rgb.data_ptr(), **kw)
+            self.scene.trace_device(rays.data_ptr(), n, self._rgb.data_ptr(), **kw)
         else:
-            self.scene.trace_nee_device(self._rays.data_ptr(), n, self._rgb.data_ptr(), mode=self.mode, **kw)
+            self.scene.trace_nee_device(rays.data_ptr(), n, self._rgb.data_ptr(), mode=self.mode, **kw)
 
     _fold = staticmethod(fold)                    # (tools/film_bench.py times a pass without it by shadowing this on the instance)
 
