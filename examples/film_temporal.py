@@ -7,6 +7,10 @@ Every frame gets a seed of its own (film.reset(seed=...)).  A sample's stream de
 camera that stands still would render the same bytes again and a history of identical frames would gain nothing.
 
     python examples/film_temporal.py [--frames 8] [--width 480 --height 270 --divisions 5] [--spp 8] [--out film_temporal]
+                                     [--clip G [--clip-radius 1] [--alpha A]]
+
+--clip G clips the reprojected history of every pixel to mean +- G standard deviations of the frame's colours around it before the
+blend, which lets a longer memory (--alpha below the default) keep less of what the frame no longer shows.
 
 Writes OUT_single.npy and OUT_history.npy: the last frame resolved from its own samples alone and from the history, (height, width, 3)
 uint8 RGB, top row first (numpy.load reads them)."""
@@ -39,6 +43,9 @@ def main():
     ap.add_argument("--divisions", type=int, default=5)
     ap.add_argument("--spp", type=int, default=8)
     ap.add_argument("--out", default="film_temporal")
+    ap.add_argument("--clip", type=float, default=None, metavar="G", help="clip the history to the frame's colour box of G deviations")
+    ap.add_argument("--clip-radius", type=int, default=1, choices=(1, 2), help="the radius of the box's window, with --clip")
+    ap.add_argument("--alpha", type=float, default=None, help="the history's alpha (default: FilmHistory's)")
     a = ap.parse_args()
     sph, rq = scenes.config("c2")
     strips = [rt.default_request(width=a.width, height=a.height, divisions=a.divisions, division_no=k, spp=a.spp,
@@ -46,7 +53,11 @@ def main():
     with rt.Scene(0, rt.World(sph)) as scene:
         scene.set_light_sampling(rt.RT_LIGHTS_CONE)
         scene.set_glossy_sampling(rt.RT_GLOSSY_MIS)
-        with rt.Film(scene, strips, integrator="nee", mode=rt.RT_NEE_MIS, moments=True) as film, rt.FilmHistory(film) as history:
+        options = {} if a.alpha is None else {"alpha": a.alpha}
+        if a.clip is not None:
+            options.update(clip=a.clip, clip_radius=a.clip_radius)
+        with rt.Film(scene, strips, integrator="nee", mode=rt.RT_NEE_MIS, moments=True) as film, \
+                rt.FilmHistory(film, **options) as history:
             for i in range(a.frames):
                 camera = orbit_camera(i, a.orbit)
                 scene.set_camera(camera)
@@ -60,10 +71,11 @@ def main():
             resolved = history.resolve_guided(guide)["rgb"]
             film.sync()                                      # the film's stream: .cpu() below copies on torch's current one
             length = history.length.cpu().numpy()
+            clipped = "" if a.clip is None else f", {100.0 * (history.clip_amount.cpu().numpy() > 0).mean():.1f} % clipped in the last frame"
             np.save(f"{a.out}_single.npy", single.cpu().numpy())
             np.save(f"{a.out}_history.npy", resolved.cpu().numpy())
             print(f"{a.out}_single.npy, {a.out}_history.npy: frame {a.frames - 1} of {a.frames} at {a.spp} samples each, "
-                  f"mean history length {length.mean():.2f}, {100.0 * (length > 1).mean():.1f} % of the pixels with history")
+                  f"mean history length {length.mean():.2f}, {100.0 * (length > 1).mean():.1f} % of the pixels with history{clipped}")
 
 
 if __name__ == "__main__":

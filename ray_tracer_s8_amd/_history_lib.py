@@ -12,8 +12,9 @@ import ctypes as C
 from . import _private_lib, build as _build
 from ._abi import Camera, TileRequest
 
-RTH_VERSION = 1
+RTH_VERSION = 2
 RTH_OK = 0
+CLIP_FORM_STAGED, CLIP_FORM_DIRECT = 1, 2            # clip_form, for tests and tools; 0 is the library's choice
 STATUS = {1: "RTH_ERR_BAD_ARG", 2: "RTH_ERR_LIMIT", 3: "RTH_ERR_HIP", 4: "RTH_ERR_INTERNAL"}
 
 
@@ -32,10 +33,12 @@ class AccumulateArgs(C.Structure):
                 ("request", C.POINTER(TileRequest)), ("camera", C.POINTER(Camera)),
                 ("prev_request", C.POINTER(TileRequest)), ("prev_camera", C.POINTER(Camera)),
                 ("accum", C.c_void_p), ("moments", C.c_void_p), ("depth", C.c_void_p), ("hits", C.c_void_p), ("index", C.c_void_p),
-                ("normal", C.c_void_p), ("prev", State), ("next", State)]
+                ("normal", C.c_void_p), ("prev", State), ("next", State),
+                ("clip_gamma", C.c_float), ("clip_radius", C.c_uint32), ("samples", C.c_uint32), ("clip_form", C.c_uint32),
+                ("clip_amount", C.c_void_p)]
 
 
-assert C.sizeof(State) == 48 and C.sizeof(AccumulateArgs) == 208
+assert C.sizeof(State) == 48 and C.sizeof(AccumulateArgs) == 232
 
 # name: argument types (every function returns int)
 SIGNATURES = {

@@ -13,7 +13,8 @@ its depth and the two camera poses, and blended with the current frame's (DESIGN
 The arithmetic is normative in history_csrc/rt_history.h and runs in one HIP kernel of a private library (lib/librt_history.so,
 _history_lib.py).  What the history holds are sums at the film's sample count, like the film's own accum and moments, so the film's
 resolves run on them unchanged; every frame of a history therefore has the same film.samples.  The world is static: only the
-camera moves.
+camera moves.  FilmHistory(film, clip=g) also clips the reprojected colours to the current frame's colour box before the blend
+(DESIGN.md 4.26); it is off by default.
 
 This module imports without torch; the library is loaded when a FilmHistory is constructed."""
 from __future__ import annotations
@@ -54,6 +55,19 @@ def check_history(moments: bool, alpha: float = ALPHA, n_max: float = N_MAX, k_d
     return float(alpha), float(n_max), float(k_depth), None if k_normal is None else float(k_normal)
 
 
+def check_clip(clip: Optional[float] = None, clip_radius: int = 1) -> tuple:
+    """The checks of FilmHistory's clip arguments: ValueError, and no GPU call.  Returns (gamma, radius): (0.0, 0) for clip=None, the
+    history without the clip; otherwise clip is a finite number > 0, the half-width of the colour box in standard deviations of the
+    window, and clip_radius 1 or 2, the window's radius in pixels.  Pure: no torch, no GPU."""
+    if clip is None:
+        return 0.0, 0
+    if isinstance(clip, bool) or not isinstance(clip, (int, float)) or not math.isfinite(clip) or not clip > 0:
+        raise ValueError(f"clip: None or a finite number > 0, got {clip!r}")
+    if isinstance(clip_radius, bool) or not isinstance(clip_radius, int) or clip_radius not in (1, 2):
+        raise ValueError(f"clip_radius: 1 or 2, got {clip_radius!r}")
+    return float(clip), int(clip_radius)
+
+
 class FilmHistory:
     """The history of one film: two sets of state planes on the film's device, alternated frame by frame, and the calls that fill and
     resolve them.
@@ -64,12 +78,21 @@ class FilmHistory:
     tap starts again from the current frame alone, with length 1.  k_normal: the least cosine between the two frames' normals, or
     None to leave the normals out.
 
+    clip: None, or g > 0 to clip the reprojected colour of every pixel, before the blend, to mean +- g standard deviations of the
+    current frame's colours in the (2 clip_radius + 1)^2 window around it (rt_history.h step 5a): history the frame
+    does not support (a highlight that moved, a surface uncovered) is pulled to what it does support, at the price of a bias
+    towards the frame's own noise where the box is narrow.  The history then keeps one more (R, W) plane, clip_amount: by how much
+    each pixel's history was moved, summed over the channels, in the frame accumulated last.
+
     Everything is enqueued on film.stream; the tensors returned are the history's own and are written again two frames later.  The
     resolves write the film's output tensors.  Not thread-safe."""
 
-    def __init__(self, film, alpha: float = ALPHA, n_max: float = N_MAX, k_depth: float = K_DEPTH, k_normal: Optional[float] = None):
+    def __init__(self, film, alpha: float = ALPHA, n_max: float = N_MAX, k_depth: float = K_DEPTH, k_normal: Optional[float] = None,
+                 clip: Optional[float] = None, clip_radius: int = 1):
         self.alpha, self.n_max, self.k_depth, self.k_normal = check_history(getattr(film, "moments", None) is not None, alpha, n_max,
                                                                             k_depth, k_normal)
+        self.clip, self.clip_radius = check_clip(clip, clip_radius)
+        self._clip_form = 0                       # the library's choice; tests and tools set a _history_lib.CLIP_FORM_*
         film._check_open()
         self._lib = _history_lib.load()
         self.film = film
@@ -81,6 +104,7 @@ class FilmHistory:
             shapes["normal"] = ((R, W, 3), torch.float32)
         with torch.cuda.stream(film.stream):
             self._sets = [{n: torch.zeros(s, dtype=d, device=film.device) for n, (s, d) in shapes.items()} for _ in range(2)]
+            self._clip_amount = torch.zeros((R, W), dtype=torch.float32, device=film.device) if self.clip else None
         self._cur: Optional[int] = None           # the set the last frame wrote
         self._request = self._camera = None       # the last frame's first strip and camera
         self._samples = 0
@@ -114,6 +138,15 @@ class FilmHistory:
         self._state()
         return self._sets[self._cur]["length"]
 
+    @property
+    def clip_amount(self):
+        """Of a history with clip: by how much the last frame's clip moved each pixel's history (the sum over the channels of the
+        absolute change of the colour sums; 0 where nothing was clipped or there was no history), as an (R, W) float32 tensor."""
+        self._state()
+        if self._clip_amount is None:
+            raise ValueError("the history was made without clip")
+        return self._clip_amount
+
     def reset(self):
         """Forget the history: the next frame is a first frame.  Nothing is enqueued."""
         self._check_open()
@@ -127,7 +160,7 @@ class FilmHistory:
             return
         if self.film.accum is not None:
             self.film.sync()
-        self._sets = None
+        self._sets = self._clip_amount = None
         self._cur = self._request = self._camera = None
 
     def __enter__(self):
@@ -152,7 +185,8 @@ class FilmHistory:
         """One frame into the history (rth_accumulate): the film's accum and moments as they stand, under `camera`, the rt.Camera the
         frame's passes and features were enqueued under (None: the reference camera; the film cannot know it, so the caller states
         it), with the feature buffers `planes` of the same frame: depth, hits and index, and normal when the history has a k_normal.
-        Returns {"accum", "moments", "length"}: (R, W, 3), (R, W, 2) and (R, W) float32 tensors of the history's.  A refused call
+        Returns {"accum", "moments", "length"}: (R, W, 3), (R, W, 2) and (R, W) float32 tensors of the history's, and with clip also
+        "clip": the (R, W) clip_amount.  A refused call
         (ValueError, or _history_lib.RthError for a pose the library refuses) leaves the history as it was."""
         self._check_open()
         film = self.film
@@ -174,6 +208,10 @@ class FilmHistory:
                                         accum=film.accum.data_ptr(), moments=film.moments.data_ptr(), depth=given["depth"].data_ptr(),
                                         hits=given["hits"].data_ptr(), index=given["index"].data_ptr(), normal=ptr(given, "normal"),
                                         next=state(self._sets[nxt]))
+        a.samples = film.samples
+        if self.clip:
+            a.clip_gamma, a.clip_radius, a.clip_form = self.clip, self.clip_radius, self._clip_form
+            a.clip_amount = self._clip_amount.data_ptr()
         a.request = C.pointer(request)
         if cam is not None:
             a.camera = C.pointer(cam)
@@ -186,7 +224,10 @@ class FilmHistory:
             _history_lib.check("rth_accumulate", self._lib.rth_accumulate(a, film.stream.cuda_stream))
         self._cur, self._request, self._camera, self._samples = nxt, request, cam, film.samples
         self.frames += 1
-        return {n: self._sets[nxt][n] for n in OUTPUTS}
+        out = {n: self._sets[nxt][n] for n in OUTPUTS}
+        if self.clip:
+            out["clip"] = self._clip_amount
+        return out
 
     # ---- the film's resolves, on the history's sums
 

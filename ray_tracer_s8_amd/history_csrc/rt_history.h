@@ -1,6 +1,7 @@
 /* rt_history.h — the private C declarations of librt_history.so, the film-history library: temporal accumulation
  * for ray_tracer_s8_amd/film_history.py.  The last frame's colour sums, moments and history length are reprojected into the current
- * frame by the current frame's depth and the two camera poses, and blended with the current frame's.  Private: this header is not
+ * frame by the current frame's depth and the two camera poses, optionally clipped to the current frame's colour box (step 5a), and
+ * blended with the current frame's.  Private: this header is not
  * installed under include/, the library is loaded by ray_tracer_s8_amd/_history_lib.py only, and nothing here is part of the tile ABI
  * (include/rt_tile.h) or of the film library (film_csrc/rt_film.h).
  *
@@ -44,6 +45,27 @@
  *      address is formed for a tap that is not inside.
  *      From +0, in tap order: Sw += w;  Sc += w C_q per channel;  S1w += w S1_q;  S2w += w S2_q;  Sn += w N_q.
  *      No admitted tap, or Sw not > 0: no history.  Otherwise Ch = Sc / Sw, S1h = S1w / Sw, S2h = S2w / Sw, Nh = Sn / Sw.
+ *   5a. Clip, only in a call with clip_gamma > 0: g = clip_gamma, rho = clip_radius in {1, 2}, e_f = (float)samples.
+ *      The history that reached the blend is rectified to the colour statistics of the current frame around the pixel.
+ *      Window.  For dy = -rho ... rho outer and dx = -rho ... rho inner, q = (x + dx, r + dy).  A tap outside the film is skipped and
+ *      no address is formed for it; the centre is always inside.  From +0, in tap order: n += 1 (an integer), and per channel k
+ *      A_k += C_q[k];  B_k += C_q[k] C_q[k].  C is the current frame's accum.
+ *      Box.  n_f = (float)n;  mu_k = A_k / n_f;  d_k = B_k / n_f - mu_k mu_k;  d_k = d_k > 0 ? d_k : +0;  s_k = g sqrt(d_k);
+ *        lo_k = mu_k - s_k;  hi_k = mu_k + s_k.
+ *      Clip.  Ch'_k = Ch_k < lo_k ? lo_k : (Ch_k > hi_k ? hi_k : Ch_k).  A NaN bound never clips.
+ *      Moments.  If neither comparison was taken for any channel, Ch, S1h and S2h go on unchanged, bit for bit, and amount = +0.
+ *      Otherwise y = (Ch_0 + Ch_1) + Ch_2 and y' = (Ch'_0 + Ch'_1) + Ch'_2;
+ *        S1h' = S1h + (y' - y), then S1h' = S1h' > 0 ? S1h' : +0;
+ *        S2h' = S2h + (S1h' S1h' - S1h S1h) / e_f, then S2h' = S2h' > 0 ? S2h' : +0;
+ *        amount = (|Ch_0 - Ch'_0| + |Ch_1 - Ch'_1|) + |Ch_2 - Ch'_2|.
+ *      Step 6 then blends Ch', S1h' and S2h'; Nh is not touched.  A pixel with "no history" has amount = +0.
+ *      What the shift keeps.  v = S2h - S1h^2 / e is the history's own spread (e times the resolve's variance of the mean, before its
+ *      normalisation); the clip moves the history's mean and leaves v, so the guided resolve's variance stays that of the history.
+ *      To the roundings: with u = 2^-24, a = S1h'^2, b = S1h^2 and no clamp of S2h' taken, the products round to a (1 + d1) and
+ *      b (1 + d2), their difference once more, the quotient by e_f once more and the sum with S2h once more, every |d| <= u.  The
+ *      first three leave (a - b) / e off by at most (u (a + b) + 2 u |a - b|) / e <= 3 u (a + b) / e to first order, and the last
+ *      rounding adds at most u S2h' / (1 - u).  So  |(S2h' - S1h'^2 / e) - v| <= 2^-23 S2h' + 2^-22 (S1h^2 + S1h'^2) / e,  where the
+ *      factors 2 and 4/3 over the first-order terms take every higher-order term.  (tests/test_history_clip_host.py holds it to that.)
  *   6. Blend.  N = Nh + 1, and N = n_max if N > n_max.  a = 1 / N, and a = alpha if alpha > a.  b = 1 - a.  Each of the five values
  *      C[0..2], S1, S2 becomes b h + a c (two products, one sum).
  *   "No history": the five outputs are the current values bit for bit and N = 1.
@@ -69,7 +91,12 @@
 extern "C" {
 #endif
 
-#define RTH_VERSION 1u
+#define RTH_VERSION 2u
+
+/* The two forms of a clipping call's kernel, which give the same bytes: the window staged in LDS by the workgroup, or read by
+ * every lane from memory.  clip_form = 0 takes the faster one as measured: direct at radius 1, staged at radius 2. */
+#define RTH_CLIP_FORM_STAGED 1u
+#define RTH_CLIP_FORM_DIRECT 2u
 
 #define RTH_OK 0
 #define RTH_ERR_BAD_ARG 1        /* a null pointer, a zero size, a value out of range, a pose make_pose refuses, frames that differ */
@@ -106,6 +133,11 @@ typedef struct rth_accumulate_args {
     const float* normal;          /* [R*W*3] or NULL: a call with normals has it and both states' normal planes */
     rth_state prev;               /* read */
     rth_state next;               /* written; no plane of it may be one of prev's or an input */
+    float clip_gamma;             /* 0: no clip, and none of the fields below is read; otherwise finite and > 0 (step 5a) */
+    uint32_t clip_radius;         /* 1 or 2 */
+    uint32_t samples;             /* e, the film's sample count: >= 1 */
+    uint32_t clip_form;           /* 0: the library's choice; RTH_CLIP_FORM_*: private, for tests and tools; another value is refused */
+    float* clip_amount;           /* [R*W] the amount of every pixel, or NULL; 4-byte aligned, none of the call's other planes */
 } rth_accumulate_args;
 
 int rth_version(uint32_t* version);

@@ -1,0 +1,175 @@
+// Test harness (CPU only, built by tests/test_history_clip_host.py with g++ -ffp-contract=off): one frame of the film-history library
+// with its clip (history_csrc/rt_history.h step 5a) run with the product's own per-pixel lines and camera setup
+// (history_csrc/rt_history_math.h, csrc/rt_plan.h) over plain arrays, counting how often each branch of accumulate_pixel and of the
+// clip is taken.  With -DHISTORY_CLIP_HOST_MAIN it is a stand-alone program (its own main) that runs a few frames, for a sanitizer
+// build.
+#include <cstdint>
+#include <cstdio>
+#include <vector>
+
+#include "rt_history_math.h"
+
+namespace {
+
+struct Planes {
+    float* accum;
+    float* moments;
+    float* length;
+    float* depth;
+    uint32_t* index;
+    float* normal;
+};
+
+struct PrevState {
+    const Planes& s;
+    void guard(size_t i, float& N, uint32_t& index, float& z) const {
+        N = s.length[i];
+        index = s.index[i];
+        z = s.depth[i];
+    }
+    void normal(size_t i, float n[3]) const {
+        for (int k = 0; k < 3; k++) n[k] = s.normal[3 * i + k];
+    }
+    void values(size_t i, float C[3], float M[2]) const {
+        for (int k = 0; k < 3; k++) C[k] = s.accum[3 * i + k];
+        M[0] = s.moments[2 * i];
+        M[1] = s.moments[2 * i + 1];
+    }
+};
+
+// the current frame's accum, record i = y W + x
+struct CurWindow {
+    const float* C;
+    void colour(size_t i, bool inside, float c[3]) const {
+        for (int k = 0; k < 3; k++) c[k] = inside ? C[3 * i + k] : 0.0f;
+    }
+};
+
+struct Counter {
+    uint64_t* c;
+    void operator()(int b) const { c[b]++; }
+};
+
+template <int RADIUS>
+void frame(const rthm::Frame& f, const rthm::Clip& clip, const float* C, const float* M, const float* depth, const uint32_t* hits,
+           const uint32_t* index, const float* normal, const Planes& pv, const Planes& nx, float* amount, uint64_t* counts,
+           uint64_t* clip_counts) {
+    const float zero[3] = {0.0f, 0.0f, 0.0f};
+    for (uint32_t r = 0; r < f.R; r++)
+        for (uint32_t x = 0; x < f.W; x++) {
+            const size_t i = (size_t)r * f.W + x;
+            float oN, oZ;
+            rthm::accumulate_pixel_clip<RADIUS>(f, clip, x, r, C + 3 * i, M + 2 * i, depth[i], hits[i], index[i],
+                                                normal ? normal + 3 * i : zero, PrevState{pv}, CurWindow{C}, i, (size_t)f.W,
+                                                Counter{counts}, Counter{clip_counts}, nx.accum + 3 * i, nx.moments + 2 * i, oN, oZ,
+                                                amount[i]);
+            nx.length[i] = oN;
+            nx.depth[i] = oZ;
+            nx.index[i] = index[i];
+            if (normal)
+                for (int k = 0; k < 3; k++) nx.normal[3 * i + k] = normal[3 * i + k];
+        }
+}
+
+}  // namespace
+
+extern "C" {
+
+int history_clip_branch_count() { return rthm::CB_COUNT; }
+int history_clip_base_branch_count() { return rthm::BR_COUNT; }
+
+// One frame of a clipping call.  fp: alpha, n_max, k_depth, k_normal, clip_gamma, (float)samples.  radius: 1 or 2.  rq, cam: the
+// frame's first strip and camera (cam NULL: the reference camera); prq: NULL for a first frame.  normal NULL: a call without normals.
+// prev, next: six plane pointers each in rth_state's order.  amount: [R*W].  counts: BR_COUNT counters, clip_counts: CB_COUNT, both
+// added to.  Returns 0, 1 for a pose make_pose refuses, 2 for another radius.
+int history_clip_frame_host(uint32_t W, uint32_t R, const float* fp, uint32_t radius, const rt_tile_request* rq, const rt_camera* cam,
+                            const rt_tile_request* prq, const rt_camera* pcam, const float* C, const float* M, const float* depth,
+                            const uint32_t* hits, const uint32_t* index, const float* normal, void* const* prev, void* const* next,
+                            float* amount, uint64_t* counts, uint64_t* clip_counts) {
+    rthm::Frame f = {};
+    f.W = W;
+    f.R = R;
+    f.normals = normal ? 1u : 0u;
+    f.alpha = fp[0];
+    f.n_max = fp[1];
+    f.kd = fp[2];
+    f.kn2 = fp[3] * fp[3];
+    const rthm::Clip clip = {fp[4], fp[5]};
+    if (!rthm::set_cameras(f, *rq, cam, prq, pcam)) return 1;
+    Planes pv = {}, nx;
+    if (prq) pv = {(float*)prev[0], (float*)prev[1], (float*)prev[2], (float*)prev[3], (uint32_t*)prev[4], (float*)prev[5]};
+    nx = {(float*)next[0], (float*)next[1], (float*)next[2], (float*)next[3], (uint32_t*)next[4], (float*)next[5]};
+    if (radius == 1u)
+        frame<1>(f, clip, C, M, depth, hits, index, normal, pv, nx, amount, counts, clip_counts);
+    else if (radius == 2u)
+        frame<2>(f, clip, C, M, depth, hits, index, normal, pv, nx, amount, counts, clip_counts);
+    else
+        return 2;
+    return 0;
+}
+}
+
+#ifdef HISTORY_CLIP_HOST_MAIN
+// Four frames of a 37 x 11 band (strips 1 and 2 of 3 of a 37 x 33 frame) under a camera that drifts and turns, with normals and a
+// window of radius 2, the state alternated between two sets: every branch that reads a plane runs under the sanitizer, and the
+// window's halo lies outside the band on every side.
+int main() {
+    const uint32_t W = 37, H = 33, R = 22;
+    rt_tile_request rq = {};
+    rq.width = W;
+    rq.height = H;
+    rq.divisions = 3;
+    rq.division_no = 1;
+    rq.fov = 1.0f;
+    rq.focal_length = 1.0f;
+    const size_t np = (size_t)W * R;
+    std::vector<float> C(np * 3), M(np * 2), D(np), N(np * 3), amount(np);
+    std::vector<uint32_t> hits(np), idx(np);
+    struct Set {
+        std::vector<float> a, m, l, d, n;
+        std::vector<uint32_t> i;
+    } sets[2];
+    for (auto& s : sets) {
+        s.a.resize(np * 3);
+        s.m.resize(np * 2);
+        s.l.resize(np);
+        s.d.resize(np);
+        s.n.resize(np * 3);
+        s.i.resize(np);
+    }
+    std::vector<uint64_t> counts(rthm::BR_COUNT), clip_counts(rthm::CB_COUNT);
+    const float fp[6] = {0.3f, 3.0f, 0.2f, 0.5f, 1.0f, 2.0f};
+    rt_camera cams[4] = {};
+    uint32_t lcg = 12345u;
+    auto rnd = [&] { return (float)((lcg = lcg * 1664525u + 1013904223u) >> 8) / 16777216.0f; };
+    for (int k = 0; k < 4; k++) {
+        cams[k].origin[0] = 0.4f * k - 0.5f;
+        cams[k].origin[1] = 0.1f * k;
+        cams[k].target[0] = 0.3f * k - 0.4f;
+        cams[k].target[2] = -1.0f;
+        cams[k].up[1] = 1.0f;
+        for (size_t i = 0; i < np; i++) {
+            hits[i] = rnd() < 0.1f ? 0u : 2u;
+            idx[i] = rnd() < 0.05f ? 0xffffffffu : (uint32_t)(i % W) / 8u;
+            D[i] = hits[i] * (4.0f + rnd());
+            for (int c = 0; c < 3; c++) {
+                C[3 * i + c] = rnd();
+                N[3 * i + c] = c == 2 ? (float)hits[i] : 0.2f * rnd();
+            }
+            M[2 * i] = rnd();
+            M[2 * i + 1] = rnd();
+        }
+        Set &pv = sets[(k + 1) & 1], &nx = sets[k & 1];
+        void* prev[6] = {pv.a.data(), pv.m.data(), pv.l.data(), pv.d.data(), pv.i.data(), pv.n.data()};
+        void* next[6] = {nx.a.data(), nx.m.data(), nx.l.data(), nx.d.data(), nx.i.data(), nx.n.data()};
+        if (history_clip_frame_host(W, R, fp, 2u, &rq, &cams[k], k ? &rq : nullptr, k ? &cams[k - 1] : nullptr, C.data(), M.data(),
+                                    D.data(), hits.data(), idx.data(), N.data(), prev, next, amount.data(), counts.data(),
+                                    clip_counts.data()))
+            return 1;
+    }
+    const uint64_t blended = counts[rthm::BR_BLEND], touched = clip_counts[rthm::CB_TOUCHED], out = clip_counts[rthm::CB_TAP_OUT];
+    std::printf("history_clip_host: %llu pixels blended, %llu clipped, %llu taps outside the band\n", (unsigned long long)blended,
+                (unsigned long long)touched, (unsigned long long)out);
+    return blended && touched && out ? 0 : 2;
+}
+#endif

@@ -1,0 +1,123 @@
+"""The film history's clip without a GPU (ray_tracer_s8_amd/film_history.py, _history_lib.py; rt_history.h step 5a):
+1. check_clip accepts None and a finite gamma > 0 with a radius of 1 or 2, and refuses the rest with ValueError; FilmHistory runs
+   it before it touches torch or the library; check_history is what it was;
+2. the modules import without torch and without loading the library;
+3. the binding still names two functions, the private header declares exactly those, the version is 2 on both sides and the
+   argument record has the header's size;
+4. rth_accumulate refuses every bad clip argument with status 1, before any launch (that a call without the clip reads none of
+   the clip's fields is tests/test_gpu_film_history_clip.py's, where such a call can be let through).
+Without the feature every test here fails: there is no check_clip and the argument record has no clip fields."""
+import ctypes as C
+import inspect
+import re
+import subprocess
+import sys
+import types
+from pathlib import Path
+
+import pytest
+
+import ray_tracer_s8_amd as rt
+from ray_tracer_s8_amd import _abi, build
+
+ROOT = Path(__file__).resolve().parent.parent
+
+
+def test_check_clip_accepts():
+    from ray_tracer_s8_amd import film_history as fh
+    assert fh.check_clip() == (0.0, 0) and fh.check_clip(None) == (0.0, 0) and fh.check_clip(None, 7) == (0.0, 0)
+    assert fh.check_clip(1.0) == (1.0, 1) and fh.check_clip(2, 2) == (2.0, 2) and fh.check_clip(1e30, 1) == (1e30, 1)
+    got = fh.check_clip(0.5, 2)
+    assert isinstance(got[0], float) and isinstance(got[1], int)
+
+
+def test_check_clip_refuses():
+    from ray_tracer_s8_amd import film_history as fh
+    inf, nan = float("inf"), float("nan")
+    bad = [dict(clip=0), dict(clip=0.0), dict(clip=-1.0), dict(clip=nan), dict(clip=inf), dict(clip=-inf), dict(clip="1"),
+           dict(clip=True), dict(clip=1.0, clip_radius=0), dict(clip=1.0, clip_radius=3), dict(clip=1.0, clip_radius=-1),
+           dict(clip=1.0, clip_radius=1.0), dict(clip=1.0, clip_radius=None), dict(clip=1.0, clip_radius=True),
+           dict(clip=1.0, clip_radius="2")]
+    for kw in bad:
+        with pytest.raises(ValueError):
+            fh.check_clip(**kw)
+            pytest.fail(str(kw))
+
+
+def test_check_history_is_what_it_was_and_film_history_checks_the_clip_first():
+    from ray_tracer_s8_amd import film_history as fh
+    assert list(inspect.signature(fh.check_history).parameters) == ["moments", "alpha", "n_max", "k_depth", "k_normal"]
+    assert fh.check_history(True, 0.05, 64, 0.5, 0.95) == (0.05, 64.0, 0.5, 0.95)
+    params = inspect.signature(fh.FilmHistory.__init__).parameters
+    assert list(params) == ["self", "film", "alpha", "n_max", "k_depth", "k_normal", "clip", "clip_radius"]
+    assert params["clip"].default is None and params["clip_radius"].default == 1
+    assert (params["alpha"].default, params["n_max"].default, params["k_depth"].default) == (fh.ALPHA, fh.N_MAX, fh.K_DEPTH)
+    film = types.SimpleNamespace(moments=object())            # (anything past the checks would fail on it with AttributeError)
+    for kw in (dict(clip=0.0), dict(clip=float("nan")), dict(clip=1.0, clip_radius=3), dict(clip=-2.0, clip_radius=2)):
+        with pytest.raises(ValueError):
+            rt.FilmHistory(film, **kw)
+
+
+_IMPORT_CHILD = r"""
+import sys
+import ray_tracer_s8_amd as rt
+import ray_tracer_s8_amd.film_history as fh
+import ray_tracer_s8_amd._history_lib as hl
+assert "torch" not in sys.modules and hl._lib is None
+assert fh.check_clip(1.5, 2) == (1.5, 2) and fh.check_clip(None) == (0.0, 0)
+assert sorted(hl.SIGNATURES) == ["rth_accumulate", "rth_version"]
+assert hl.RTH_VERSION == 2
+assert "torch" not in sys.modules and hl._lib is None
+print("ok")
+"""
+
+
+def test_the_modules_import_without_torch():
+    r = subprocess.run([sys.executable, "-c", _IMPORT_CHILD], capture_output=True, text=True, cwd=ROOT, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
+
+
+def test_the_header_declares_the_two_functions_and_the_binding_has_its_record():
+    from ray_tracer_s8_amd import _history_lib as hl
+    assert sorted(hl.SIGNATURES) == ["rth_accumulate", "rth_version"]
+    text = (build.HISTORY_CSRC / "rt_history.h").read_text()
+    assert sorted(re.findall(r"^int (rth_\w+)\(", text, re.M)) == sorted(hl.SIGNATURES)
+    assert re.search(r"^#define RTH_VERSION 2u$", text, re.M) and hl.RTH_VERSION == 2
+    # the record: the header's fields in the header's order, the clip's appended after `next`, `reserved` where it was
+    body = text[text.index("typedef struct rth_accumulate_args {"):text.index("} rth_accumulate_args;")]
+    declared = re.findall(r"(\w+)(?:, (\w+))?(?:, (\w+))?;", re.sub(r"/\*.*?\*/", "", body))
+    names = [n for group in declared for n in group if n]
+    assert names == [n for n, _ in hl.AccumulateArgs._fields_], names
+    assert names[-6:] == ["next", "clip_gamma", "clip_radius", "samples", "clip_form", "clip_amount"] and names[3] == "reserved"
+    assert C.sizeof(hl.AccumulateArgs) == 232 and hl.AccumulateArgs.clip_gamma.offset == 208 and hl.AccumulateArgs.clip_amount.offset == 224
+    version = C.c_uint32(0)
+    assert hl.load().rth_version(C.byref(version)) == 0 and version.value == 2
+
+
+def test_bad_clip_arguments_are_refused_with_status_1():
+    """Before any launch: every address here is one that is never read."""
+    from ray_tracer_s8_amd import _history_lib as hl
+    lib = hl.load()
+    rq = _abi.default_request(width=8, height=6, divisions=3, division_no=1, spp=4)
+    addr = lambda k: C.c_void_p(8 * k)                       # distinct non-null, 8-byte aligned addresses
+    planes = dict(accum=addr(1), moments=addr(2), depth=addr(3), hits=addr(4), index=addr(5))
+    nxt = hl.State(accum=addr(6), moments=addr(7), length=addr(8), depth=addr(9), index=addr(10))
+    prv = hl.State(accum=addr(11), moments=addr(12), length=addr(13), depth=addr(14), index=addr(15))
+    good = dict(W=8, R=4, alpha=0.2, n_max=8.0, k_depth=0.1, request=C.pointer(rq), next=nxt, clip_gamma=1.0, clip_radius=1, samples=4,
+                clip_amount=addr(20), **planes)
+    inf, nan = float("inf"), float("nan")
+    bad = [dict(clip_gamma=-1.0), dict(clip_gamma=nan), dict(clip_gamma=inf), dict(clip_gamma=-inf),
+           dict(clip_radius=0), dict(clip_radius=3), dict(clip_radius=0xFFFFFFFF), dict(samples=0),
+           dict(clip_amount=C.c_void_p(8 * 20 + 2)), dict(clip_amount=C.c_void_p(8 * 20 + 1)),
+           dict(clip_form=7)]                                                         # a form the library does not have
+    bad += [dict(clip_amount=addr(k)) for k in range(1, 11)]                          # an input or a plane of next
+    bad += [dict(clip_amount=addr(k), have_prev=1, prev=prv, prev_request=C.pointer(rq)) for k in range(11, 16)]    # a plane of prev
+    bad += [dict(clip_amount=addr(16), normal=addr(16), next=hl.State(accum=addr(6), moments=addr(7), length=addr(8), depth=addr(9),
+                                                                      index=addr(10), normal=addr(17)))]           # the normal input
+    for kw in bad:
+        a = hl.AccumulateArgs(**{**good, **kw})
+        assert lib.rth_accumulate(a, None) == 1, kw
+    # a negative, NaN or infinite gamma is refused whatever the other fields hold; the reserved word stays 0 in a clipping call
+    for g in (-1.0, nan, inf):
+        assert lib.rth_accumulate(hl.AccumulateArgs(**{**good, "clip_gamma": g, "clip_radius": 0, "samples": 0}), None) == 1
+    assert lib.rth_accumulate(hl.AccumulateArgs(**{**good, "reserved": 1}), None) == 1

@@ -13,7 +13,14 @@ c3), the config's own divisions, bounces and seed, along the orbit of examples/f
               n_max; and of the history's mean over a small grid of k_depth x k_normal.  The share of pixels with history and their
               mean length at the last pose go with each history.
 
+  --clip      the clip of the history to the frame's colour box beside all that, from the same run: in frame_ms,
+              accumulate() with the clip at gamma = 1 and a radius of 1 and of 2, in both forms of the kernel (the window staged in
+              LDS, and `_direct`), alternating with the calls without it, and whether the two forms' bytes are equal; in quality,
+              the history's mean and resolve_guided for gamma x radius x alpha at n_max = 32 (CLIP_GAMMAS, CLIP_RADII, CLIP_ALPHAS),
+              and the share of the pixels with history that the last pose's clip moved.
+
     python tools/film_history_bench.py [--configs c2 c3] [--width 1920 --height 1080 --spp 8] [--runs 7 --warmup 2] [--aperture 0]
+                                       [--clip]
 Prints one JSON line.  torch is imported first: the libraries then bind to torch's HIP runtime."""
 import argparse
 import json
@@ -27,13 +34,17 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 import ray_tracer_s8_amd as rt  # noqa: E402
-from ray_tracer_s8_amd import _abi, scenes  # noqa: E402
+from ray_tracer_s8_amd import _abi, _history_lib, scenes  # noqa: E402
 from ray_tracer_s8_amd import film_history as fh  # noqa: E402
 
 ALPHA_GRID = (0.05, 0.1, 0.2, 0.5)
 N_MAX_GRID = (8, 32)
 SIGMA_GRID = (4.0, 8.0, 16.0)
 GATE_GRID = ((0.02, None), (0.1, None), (0.5, None), (0.02, 0.9), (0.1, 0.9), (0.5, 0.9), (0.1, 0.99))     # (k_depth, k_normal)
+CLIP_GAMMAS = (0.5, 1.0, 1.5, 2.0, 3.0)
+CLIP_RADII = (1, 2)
+CLIP_ALPHAS = (0.05, 0.2, 0.5)
+CLIP_N_MAX = 32
 PLANES = ("normal", "depth", "hits", "index")
 GUIDE = ("normal", "depth", "hits")
 
@@ -77,6 +88,16 @@ def frame_times(sc, rq, a, variants=None):
     """variants: {name: FilmHistory-like factory(film)} timed next to the two of the product (tools of an experiment add theirs)."""
     with rt.Film(sc, _requests(rq, a.width, a.height, a.spp, rq.seed), integrator="nee", moments=True) as film:
         make = {"accumulate": lambda f: rt.FilmHistory(f), "accumulate_normals": lambda f: rt.FilmHistory(f, k_normal=0.9)}
+        if a.clip:
+            def clipped(radius, form):
+                def make_one(f):
+                    h = rt.FilmHistory(f, clip=1.0, clip_radius=radius)
+                    h._clip_form = form
+                    return h
+                return make_one
+            for r in CLIP_RADII:
+                make[f"accumulate_clip_radius_{r}"] = clipped(r, _history_lib.CLIP_FORM_STAGED)
+                make[f"accumulate_clip_radius_{r}_direct"] = clipped(r, _history_lib.CLIP_FORM_DIRECT)
         make.update(variants or {})
         hist = {k: m(film) for k, m in make.items()}
         t = {k: [] for k in ("pass", "features", "resolve_guided", *hist)}
@@ -99,7 +120,9 @@ def frame_times(sc, rq, a, variants=None):
         film.sync()
         twin = lambda k: hist["accumulate_normals" if k.endswith("_normals") else "accumulate"]
         equal = {k: bool(torch.equal(h.accum.view(torch.int32), twin(k).accum.view(torch.int32)))
-                 for k, h in hist.items() if k not in ("accumulate", "accumulate_normals")}
+                 for k, h in hist.items() if k in (variants or {})}
+        equal.update({k: bool(torch.equal(h.accum.view(torch.int32), hist[k[:-len("_direct")]].accum.view(torch.int32)))
+                      for k, h in hist.items() if k.endswith("_direct")})
         for h in hist.values():
             h.close()
     out = {"width": a.width, "height": a.height, "spp": a.spp, "calls_per_window": a.calls, "ms": {k: _spread(v) for k, v in t.items()}}
@@ -138,6 +161,8 @@ def quality(sc, rq, a):
             rt.Film(sc, _requests(rq, W, H, a.reference_spp, rq.seed ^ 0x5EED), integrator="nee") as big:
         grid = {(al, nm): rt.FilmHistory(film, alpha=al, n_max=nm) for al in ALPHA_GRID for nm in N_MAX_GRID}
         gates = {g: rt.FilmHistory(film, k_depth=g[0], k_normal=g[1]) for g in GATE_GRID}
+        clips = {(g, r, al): rt.FilmHistory(film, alpha=al, n_max=CLIP_N_MAX, clip=g, clip_radius=r)
+                 for g in CLIP_GAMMAS for r in CLIP_RADII for al in CLIP_ALPHAS} if a.clip else {}
         stats = {}
         for i in range(a.frames):
             camera, planes = _frame(sc, film, rq, i, a)
@@ -164,8 +189,20 @@ def quality(sc, rq, a):
             for g, h in gates.items():
                 h.accumulate(camera, planes)
                 row(f"history mean k_depth={g[0]:g} k_normal={g[1]}").add(err(h.accum, a.spp))
+            for (g, r, al), h in clips.items():
+                h.accumulate(camera, planes)
+                row(f"clip mean gamma={g:g} radius={r} alpha={al:g} n_max={CLIP_N_MAX}").add(err(h.accum, a.spp))
+                for s in SIGMA_GRID:
+                    row(f"clip resolve_guided sigma_l={s:g} gamma={g:g} radius={r} alpha={al:g} n_max={CLIP_N_MAX}").add(
+                        err(h.resolve_guided(guide, ("linear",), sigma_l=s)["linear"]))
             film.collect()
         film.sync()
+        clipped = {}
+        for (g, r, al), h in clips.items():
+            has = h.length > 1
+            clipped[f"gamma={g:g} radius={r} alpha={al:g}"] = float(((h.clip_amount > 0) & has).double().sum().item()
+                                                                    / max(int(has.sum().item()), 1))
+            h.close()
         for name, h in [(f"alpha={al:g} n_max={nm}", h) for (al, nm), h in grid.items()] + \
                        [(f"k_depth={g[0]:g} k_normal={g[1]}", h) for g, h in gates.items()]:
             n = h.length.to(torch.float64)
@@ -173,6 +210,7 @@ def quality(sc, rq, a):
             h.close()
     return {"width": W, "height": H, "spp": a.spp, "frames": a.frames, "orbit": a.orbit, "reference_spp": a.reference_spp,
             "errors": {k: v.result() for k, v in rows.items()}, "history_at_the_last_pose": stats,
+            **({"clipped_of_the_pixels_with_history_at_the_last_pose": clipped} if a.clip else {}),
             "defaults": {"alpha": fh.ALPHA, "n_max": fh.N_MAX, "k_depth": fh.K_DEPTH}}
 
 
@@ -200,6 +238,7 @@ def parser():
     ap.add_argument("--orbit", type=int, default=96, help="viewpoints of the whole circle")
     ap.add_argument("--reference-spp", type=int, default=1024)
     ap.add_argument("--aperture", type=float, default=None, help="0: pinhole rays (default: the reference's 0.1, focused at 1)")
+    ap.add_argument("--clip", action="store_true", help="also time and grade the clip of the history (DESIGN.md 4.26)")
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--calls", type=int, default=10, help="accumulate / resolve calls per timed window")
