@@ -113,11 +113,15 @@ HISTORY_LIB_PATH, HISTORY_CSRC = HISTORY.path, HISTORY.src_dir
 # The SAMPLER library: the adaptive sampling of film_sampler.py; rts_* exports, _sampler_lib.py.  It includes no csrc/
 # header.
 SAMPLER = _private("sampler", ())
+# The UPSAMPLE library: the joint-bilateral upsampling of film_upsampler.py; rtu_* exports, _upsample_lib.py.
+UPSAMPLE = _private("upsample", ("rt_denoise_math.h", "rt_consts.h"))
 
-# LIBRARIES is the set the recipe's golden test (tests/test_build_recipe.py) knows, and stays those four; a library added since is a
-# Library value like them and a member of PRIVATE_LIBRARIES, the private libraries build() makes, which is the set to add to.
+# LIBRARIES is the set the recipe's golden test (tests/test_build_recipe.py) knows, and stays those four; PRIVATE_LIBRARIES is the set
+# tests/test_sampler_plan.py knows, and stays those three.  A library added since is a Library value like them and a member of
+# FILM_LIBRARIES, the private libraries build() makes, which is the set to add to.
 LIBRARIES = (PRODUCT, DEBUG, FILM, HISTORY)
 PRIVATE_LIBRARIES = (FILM, HISTORY, SAMPLER)
+FILM_LIBRARIES = (*PRIVATE_LIBRARIES, UPSAMPLE)
 
 
 def _product(extra: list[str] | None = None) -> Library:
@@ -202,8 +206,8 @@ def needs_build() -> bool:
 
 def build(force: bool = False, verbose: bool = False) -> Path:
     """Compile librt_s8.so (or the RT_LIB_VARIANT named) if missing or stale, and with no variant named the private libraries
-    (PRIVATE_LIBRARIES) first."""
-    for lib in () if VARIANT else PRIVATE_LIBRARIES:
+    (FILM_LIBRARIES) first."""
+    for lib in () if VARIANT else FILM_LIBRARIES:
         ensure(lib, force, verbose)
     return ensure(_product(), force, verbose)
 
@@ -224,8 +228,12 @@ def build_sampler(force: bool = False, verbose: bool = False) -> Path:
     return ensure(SAMPLER, force, verbose)
 
 
+def build_upsample(force: bool = False, verbose: bool = False) -> Path:
+    return ensure(UPSAMPLE, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
     if not VARIANT:
-        for lib in (DEBUG, *PRIVATE_LIBRARIES):
+        for lib in (DEBUG, *FILM_LIBRARIES):
             print(ensure(lib, force=True, verbose=True))

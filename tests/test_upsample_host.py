@@ -1,0 +1,213 @@
+"""The film upsampler off the GPU: the product's per-pixel lines (upsample_csrc/rt_upsample_math.h, through the g++
+harness tests/host/upsample_host.cpp) equal the numpy restatement of upsample_csrc/rt_upsample.h (tests/_upsample_np.py) bit for bit:
+scales 2, 3 and 4, every plane set a call may have (albedo among them), strip offsets above zero, a 1 x 1 low film; every admission
+test rejects somewhere and both classes occur, in the harness's counters and in the restatement's alike, each class on at least 5 % of
+the pixels of the shared synthetic pairs; the properties rt_upsample.h states hold on the restatement; the harness as a stand-alone
+program runs clean under the address and undefined-behaviour sanitizers.  Without the feature every test here fails: there is no
+upsample_csrc."""
+import ctypes as C
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import _upsample_np as unp
+
+ROOT = Path(__file__).resolve().parents[1]
+CSRC = ROOT / "ray_tracer_s8_amd" / "csrc"
+UPSAMPLE_CSRC = ROOT / "ray_tracer_s8_amd" / "upsample_csrc"
+SRC = ROOT / "tests" / "host" / "upsample_host.cpp"
+BUILD = ROOT / "tests" / "host" / "_build"
+OUT = BUILD / "libupsample_host.so"
+DEPS = [SRC, UPSAMPLE_CSRC / "rt_upsample_math.h", CSRC / "rt_denoise_math.h", CSRC / "rt_consts.h"]
+GXX = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", f"-I{UPSAMPLE_CSRC}", f"-I{CSRC}"]
+f32 = np.float32
+BRANCHES = ("index", "hits", "depth", "normal", "admitted", "class0", "class1")        # rtum::Branch, in its order
+SUBSETS = unp.plane_subsets()
+
+
+@pytest.fixture(scope="module")
+def lib():
+    BUILD.mkdir(exist_ok=True)
+    if not OUT.exists() or OUT.stat().st_mtime < max(d.stat().st_mtime for d in DEPS):
+        subprocess.run([*GXX, "-fPIC", "-shared", "-o", str(OUT), str(SRC)], check=True)
+    l = C.CDLL(str(OUT))
+    l.upsample_host.argtypes = [C.c_void_p] * 10
+    assert l.upsample_branch_count() == len(BRANCHES)
+    return l
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32) if a.dtype == np.float32 else a
+
+
+def same(got, want, what):
+    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
+    bad = np.argwhere(bits(got) != bits(want))
+    assert len(bad) == 0, (what, len(bad), bad[:4].tolist(), got[tuple(bad[0])], want[tuple(bad[0])])
+
+
+def host(lib, L, lo, hi, geom, kl, kh, k_depth=unp.K_DEPTH, k_normal=unp.K_NORMAL, eps=unp.EPS):
+    """upsample_host on the restatement's arguments: its four outputs and its counters by name."""
+    Rl, Wl = L.shape[:2]
+    Rh, Wh = geom["Rh"], geom["Wh"]
+    dims = np.array([Wl, Rl, geom["Hl"], geom["y0l"], Wh, Rh, geom["Hh"], geom["y0h"], kl, kh], np.uint32)
+    fp = np.array([k_depth, k_normal, eps], f32)
+    keep = [np.ascontiguousarray(L, f32)]
+    ptrs = []
+    for side in (lo, hi):
+        p = (C.c_void_p * 5)()
+        for k, n in enumerate(unp.PLANES):
+            if n in side:
+                keep.append(np.ascontiguousarray(side[n]))
+                p[k] = keep[-1].ctypes.data
+        ptrs.append(p)
+    lin, f, rgb = np.full((Rh, Wh, 3), 7, f32), np.full((Rh, Wh, 3), 7, f32), np.full((Rh, Wh, 3), 7, np.uint8)
+    cls = np.full((Rh, Wh), 7, np.uint8)
+    counts = np.zeros(len(BRANCHES), np.uint64)
+    assert lib.upsample_host(dims.ctypes.data, fp.ctypes.data, keep[0].ctypes.data, C.addressof(ptrs[0]), C.addressof(ptrs[1]),
+                             lin.ctypes.data, f.ctypes.data, rgb.ctypes.data, cls.ctypes.data, counts.ctypes.data) == 0
+    return dict(linear=lin, f32=f, rgb=rgb, cls=cls, counts=dict(zip(BRANCHES, (int(c) for c in counts))))
+
+
+def compare(lib, L, lo, hi, geom, kl, kh, what, **kw):
+    got = host(lib, L, lo, hi, geom, kl, kh, **kw)
+    want = unp.upsample(L, lo, hi, geom, kl=kl, kh=kh, **{**dict(k_depth=unp.K_DEPTH, k_normal=unp.K_NORMAL, eps=unp.EPS), **kw})
+    for o in ("linear", "f32", "rgb", "cls"):
+        same(got[o], want[o], (what, o))
+    assert got["counts"] == want["counts"], (what, got["counts"], want["counts"])
+    return want
+
+
+@pytest.mark.parametrize("s", unp.SCALES)
+@pytest.mark.parametrize("Wl,Rl,above,below", unp.SIZES)
+def test_the_products_lines_equal_the_restatement_on_every_plane_set(lib, Wl, Rl, above, below, s):
+    L, lo, hi, geom, kl, kh, _ = unp.pair(unp.seed_of(Wl, Rl, s), Wl, Rl, s, above, below)
+    assert (geom["y0l"] > 0) == (above > 0) and geom["y0h"] == s * geom["y0l"]
+    total = dict.fromkeys(BRANCHES, 0)
+    for names in SUBSETS:
+        want = compare(lib, L, unp.take(lo, names), unp.take(hi, names), geom, kl, kh, (names, s))
+        n = geom["Rh"] * geom["Wh"]
+        assert want["counts"]["class0"] + want["counts"]["class1"] == n
+        assert np.isfinite(want["linear"]).all()
+        if not set(names) & set(unp.TESTS):
+            # no plane that tests a tap: every pixel is class 0
+            assert want["counts"]["class1"] == 0 and want["counts"]["admitted"] == 4 * n
+        for b in BRANCHES:
+            total[b] += want["counts"][b]
+    if Wl * Rl >= 15:
+        assert all(total.values()), total                          # every branch, on this pair alone
+
+
+@pytest.mark.parametrize("s", unp.SCALES)
+def test_every_branch_and_each_class_on_five_percent_of_the_pixels(lib, s):
+    """On the shared pairs, with every plane: each admission test rejects and each class holds at least 5 % of the pixels.  With one
+    testing plane alone (and what it needs), the same of the classes: the restatement alone is held to it, then the harness."""
+    for Wl, Rl, above, below in unp.SIZES[1:]:
+        L, lo, hi, geom, kl, kh, _ = unp.pair(unp.seed_of(Wl, Rl, s), Wl, Rl, s, above, below)
+        n = geom["Rh"] * geom["Wh"]
+        small = Wl * Rl <= 15                                      # (the 60 to 240 pixels of the 5 x 3 pair: held to the full set only)
+        for names in (unp.PLANES,) if small else (unp.PLANES, ("index",), ("depth", "hits"), ("normal",)):
+            want = unp.upsample(L, unp.take(lo, names), unp.take(hi, names), geom, unp.K_DEPTH, unp.K_NORMAL, unp.EPS, kl, kh)
+            c = want["counts"]
+            assert c["class0"] >= 0.05 * n and c["class1"] >= 0.05 * n, (names, s, Wl, Rl, c, n)
+            if names == unp.PLANES and not small:
+                assert all(c[b] > 0 for b in BRANCHES), c
+            got = host(lib, L, unp.take(lo, names), unp.take(hi, names), geom, kl, kh)
+            assert got["counts"] == c
+
+
+def test_a_one_by_one_low_film_and_a_band_in_the_middle_of_its_frame(lib):
+    rng = np.random.default_rng(3)
+    for s in unp.SCALES:
+        # one pixel: every tap is that pixel, whatever the weights
+        L, lo, hi, geom, kl, kh, _ = unp.pair(11 + s, 1, 1, s)
+        want = compare(lib, L, {}, {}, geom, kl, kh, ("1x1", s))
+        for k in range(3):
+            assert np.abs(want["linear"][..., k] / L[0, 0, k] - 1).max() <= 2.0 ** -20 if L[0, 0, k] else (want["linear"][..., k] == 0).all()
+        # a one-pixel film that is strip 1 of 3 of a one-column frame
+        L, lo, hi, geom, kl, kh, _ = unp.pair(17 + s, 1, 1, s, 1, 1)
+        assert geom["y0l"] == 1 and geom["Hl"] == 3 and geom["y0h"] == s
+        for names in ((), unp.PLANES):
+            compare(lib, L, unp.take(lo, names), unp.take(hi, names), geom, kl, kh, ("1x1 of 3", s, names))
+        # other constants: k_depth 0 admits only equal distances, k_normal 0 every facing pair, a large eps
+        L, lo, hi, geom, kl, kh, _ = unp.pair(23 + s, 9, 4, s, 1, 0, kl=3, kh=2)
+        for kw in (dict(k_depth=f32(0)), dict(k_normal=f32(0)), dict(eps=f32(1.5)), dict(k_depth=f32(10), k_normal=f32(1))):
+            compare(lib, L, lo, hi, geom, kl, kh, (s, kw), **kw)
+
+
+def test_no_planes_is_the_plain_bilinear_image(lib):
+    """With no planes every pixel is class 0 and the value is the bilinear one: the restatement against a second, direct writing."""
+    for s in unp.SCALES:
+        L, lo, hi, geom, kl, kh, _ = unp.pair(31 + s, 12, 6, s, 1, 1)
+        want = unp.upsample(L, {}, {}, geom)
+        assert (want["cls"] == 0).all() and want["counts"]["admitted"] == 4 * want["cls"].size
+        Rl, Wl = L.shape[:2]
+        uh, vh = unp.frame_dens(geom["Wh"], geom["Hh"])
+        ul, vl = unp.frame_dens(Wl, geom["Hl"])
+        ref = np.zeros_like(want["linear"])
+        for r in range(geom["Rh"]):
+            for x in range(geom["Wh"]):
+                fx = f32(f32(f32(x) + f32(0.5)) / uh) * ul - f32(0.5)
+                cv = f32(f32(f32(geom["Hh"] - (geom["y0h"] + r) - 1) + f32(0.5)) / vh) * vl - f32(0.5)
+                fy = f32(f32(geom["Hl"] - 1) - cv) - f32(geom["y0l"])
+                x0, y0 = int(np.floor(fx)), int(np.floor(fy))
+                ax, ay = f32(fx - f32(x0)), f32(fy - f32(y0))
+                sw, sv = f32(0), np.zeros(3, f32)
+                for dy in (0, 1):
+                    for dx in (0, 1):
+                        b = f32((ax if dx else f32(1) - ax) * (ay if dy else f32(1) - ay))
+                        q = L[min(max(y0 + dy, 0), Rl - 1), min(max(x0 + dx, 0), Wl - 1)]
+                        sw = f32(sw + b)
+                        sv = (sv + b * q).astype(f32)
+                ref[r, x] = sv / sw
+        same(want["linear"], ref, ("bilinear", s))
+        same(host(lib, L, {}, {}, geom, kl, kh)["linear"], ref, ("bilinear, the product's lines", s))
+
+
+def test_a_colour_constant_over_each_region_comes_back_at_every_class_0_pixel():
+    """rt_upsample.h "What class 0 keeps".  Every admitted tap of a class-0 pixel has the pixel's index, so every V_q is one value
+    c > 0, and every weight is >= 0: nothing cancels.  Each of Sv and Sw takes at most four product roundings and three sum
+    roundings (Sw's products are the weights themselves, which Sv shares, and the first sum, from +0, is exact: the count is
+    generous), then V one quotient: 15 roundings, each at most u = 2^-24 relative, so V is within 15 u < 2^-20 of c to first order,
+    and the remaining u takes every higher-order term (they are of order 15^2 u^2 / 2 < 2^-40).  With albedo, L = Al / kl makes
+    V_q = x / (x + eps) with x the region's albedo, again one value, and the exit multiplies by Ah / kh + eps: one more rounding,
+    still within 2^-20 because Sw's four products were counted and do not occur."""
+    for s in unp.SCALES:
+        for Wl, Rl, above, below in unp.SIZES[1:]:
+            L, lo, hi, geom, kl, kh, reg = unp.pair(unp.seed_of(Wl, Rl, s), Wl, Rl, s, above, below)
+            names = ("normal", "depth", "hits", "index")
+            colours = np.random.default_rng(s).uniform(0.05, 3.0, (unp.REGIONS + 1, 3)).astype(f32)
+            Lc = colours[reg]
+            # the low side's thin pixels do not exist (thin = 0 there), so index -> region is one to one on it
+            want = unp.upsample(Lc, unp.take(lo, names), unp.take(hi, names), geom, unp.K_DEPTH, unp.K_NORMAL, unp.EPS, kl, kh)
+            ih = hi["index"]
+            region_h = np.where(ih == unp.NONE, 0, ih.astype(np.int64) - 10)
+            at = want["cls"] == 0
+            assert at.sum() >= 0.05 * at.size
+            assert (region_h[at] >= 0).all() and (region_h[at] < unp.REGIONS).all()     # a thin pixel is never class 0: no tap has its index
+            c = colours[region_h[at]].astype(np.float64)
+            rel = np.abs(want["linear"][at].astype(np.float64) - c) / c
+            assert rel.max() <= 2.0 ** -20, (s, Wl, Rl, rel.max())
+            # with albedo: L = Al / kl
+            names = unp.PLANES
+            La = (lo["albedo"] / f32(kl)).astype(f32)
+            want = unp.upsample(La, unp.take(lo, names), unp.take(hi, names), geom, unp.K_DEPTH, unp.K_NORMAL, unp.EPS, kl, kh)
+            at = want["cls"] == 0
+            x = La.reshape(-1, 3)[[np.flatnonzero(reg.reshape(-1) == k)[0] if (reg == k).any() else 0 for k in range(unp.REGIONS)]]
+            const = (x / (x + unp.EPS)).astype(f32)                 # the region's constant, as the taps form it
+            d = (hi["albedo"] / f32(kh) + unp.EPS).astype(f32)
+            expect = const[region_h[at]].astype(np.float64) * d[at].astype(np.float64)
+            rel = np.abs(want["linear"][at].astype(np.float64) - expect) / expect
+            assert at.sum() >= 0.05 * at.size and rel.max() <= 2.0 ** -20, (s, Wl, Rl, rel.max())
+
+
+def test_the_stand_alone_harness_runs_clean_under_asan_and_ubsan(tmp_path):
+    exe = tmp_path / "upsample_host"
+    r = subprocess.run([*GXX, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DUPSAMPLE_HOST_MAIN",
+                        "-o", str(exe), str(SRC)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "pixels upsampled" in r.stdout, r.stdout + r.stderr

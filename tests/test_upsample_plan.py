@@ -1,0 +1,271 @@
+"""The film upsampler without a GPU (ray_tracer_s8_amd/film_upsampler.py, _upsample_lib.py, build.py):
+1. check_upsample refuses, with ValueError, everything FilmUpsampler and upsample() refuse, and returns the plan of the rest;
+2. film_upsampler.py and _upsample_lib.py import without torch and without loading the library;
+3. librt_upsample.so exports exactly _upsample_lib.SIGNATURES, all rtu_*, and the private header declares exactly those; no rtu_ name is
+   in any other library or source directory, there is no include/rt_upsample.h, and _abi holds nothing of the library;
+4. the library is a build.Library value: a member of FILM_LIBRARIES, which build() makes, and of neither LIBRARIES nor
+   PRIVATE_LIBRARIES, which keep their values; its record is the golden one, the product's flags plus -fno-slp-vectorize whatever
+   RT_EXTRA_HIPCC_FLAGS says; its sources are a dependency of no other library, and of csrc/ it depends on the two headers it includes;
+5. every refusal of the library's call comes back as a status, with no device bound.
+Without the feature every test here fails: there is no film_upsampler, no _upsample_lib and no build.UPSAMPLE."""
+import ctypes as C
+import re
+import subprocess
+import sys
+import types
+from pathlib import Path
+
+import pytest
+
+import ray_tracer_s8_amd as rt
+from ray_tracer_s8_amd import _abi, build
+
+import _surface
+
+ROOT = Path(__file__).resolve().parent.parent
+GOLDEN = Path(__file__).resolve().parent / "golden" / "build_records"
+NAMES = ("rtu_version", "rtu_upsample")
+
+
+def strips(width, height, divisions, numbers, spp=4, **kw):
+    return [_abi.default_request(width=width, height=height, divisions=divisions, division_no=k, spp=spp, **kw) for k in numbers]
+
+
+def test_check_upsample_returns_the_plan():
+    from ray_tracer_s8_amd import film_upsampler as fu
+    lo = strips(24, 42, 3, (1, 2))
+    for s in (2, 3, 4):
+        hi = strips(24 * s, 42 * s, 6, (2, 3, 4, 5), spp=1)
+        p = fu.check_upsample(lo, hi, ("hits", "albedo", "index"), ("index", "albedo", "hits"), ("class", "rgb"))
+        assert (p.scale, p.width, p.rows, p.height, p.y0_lo, p.y0_hi) == (s, 24 * s, 28 * s, 42 * s, 14, 14 * s)
+        assert p.planes == ("albedo", "hits", "index") and len(p.reqs_hi) == 4 and p.reqs_hi[0] is not hi[0]
+        assert (p.k_depth, p.k_normal) == (fu.K_DEPTH, fu.K_NORMAL) and p.eps > 0
+    hi = strips(48, 84, 6, (2, 3, 4, 5))
+    assert fu.check_upsample(lo, hi).planes == ()
+    assert fu.check_upsample(lo, hi, fu.PLANES, fu.PLANES).planes == fu.PLANES
+    assert fu.check_upsample(lo, hi, fu.PLANES, fu.PLANES, albedo=False).planes == ("normal", "depth", "hits", "index")
+    assert fu.check_upsample(lo, hi, fu.PLANES, fu.PLANES, use_index=False).planes == ("albedo", "normal", "depth", "hits")
+    # a plane that is left out may be given on one side only
+    assert fu.check_upsample(lo, hi, ("albedo", "hits"), ("hits",), albedo=False).planes == ("hits",)
+    assert fu.check_upsample(lo, hi, ("hits",), ("hits", "index"), use_index=False).planes == ("hits",)
+    # other divisions of the full frame, as long as the rows are the film's; one request for one strip
+    assert fu.check_upsample(lo, strips(48, 84, 3, (1, 2))).rows == 56
+    assert fu.check_upsample(lo[0], strips(48, 84, 3, (1,))[0]).y0_hi == 28
+    p = fu.check_upsample(lo, hi, k_depth=0, k_normal=1, eps=1e-9)
+    assert (p.k_depth, p.k_normal, p.eps) == (0.0, 1.0, 1e-9)
+    assert fu.OUTPUTS == ("rgb", "linear", "f32", "class") and fu.PLANES == _abi.AOV_PLANES
+    assert rt.FilmUpsampler is fu.FilmUpsampler and "FilmUpsampler" in rt.__all__
+
+
+def test_check_upsample_refuses():
+    from ray_tracer_s8_amd import film_upsampler as fu
+    lo = strips(24, 42, 3, (1, 2))
+    hi = strips(48, 84, 6, (2, 3, 4, 5))
+    inf, nan = float("inf"), float("nan")
+    bad = {
+        "no strips": dict(reqs_hi=[]),
+        "not a request": dict(reqs_hi=[object()]),
+        "scale 1": dict(reqs_hi=strips(24, 42, 3, (1, 2))),
+        "scale 5": dict(reqs_hi=strips(120, 210, 3, (1, 2))),
+        "scale 1.5": dict(reqs_hi=strips(36, 63, 3, (1, 2))),
+        "scales differ": dict(reqs_hi=strips(48, 126, 3, (1, 2))),
+        "a half scale in height": dict(reqs_hi=strips(48, 105, 3, (1, 2))),
+        "other rows": dict(reqs_hi=strips(48, 84, 6, (2, 3, 4))),
+        "rows shifted": dict(reqs_hi=strips(48, 84, 6, (1, 2, 3, 4))),
+        "strips not consecutive": dict(reqs_hi=strips(48, 84, 6, (2, 3, 5))),
+        "fov": dict(reqs_hi=strips(48, 84, 6, (2, 3, 4, 5), fov=0.5)),
+        "focal_length": dict(reqs_hi=strips(48, 84, 6, (2, 3, 4, 5), focal_length=2.0)),
+        "aperture": dict(reqs_hi=strips(48, 84, 6, (2, 3, 4, 5), aperture=0.25)),
+        "focus_distance": dict(reqs_hi=strips(48, 84, 6, (2, 3, 4, 5), focus_distance=3.0)),
+        "depth without hits": dict(planes_lo=("depth",), planes_hi=("depth",)),
+        "a plane on the low side only": dict(planes_lo=("hits", "normal"), planes_hi=("hits",)),
+        "a plane on the high side only": dict(planes_lo=(), planes_hi=("index",)),
+        "albedo on one side": dict(planes_lo=("albedo",), planes_hi=()),
+        "an unknown plane": dict(planes_lo=("colour",), planes_hi=("colour",)),
+        "a plane twice": dict(planes_lo=("hits", "hits"), planes_hi=("hits",)),
+        "no outputs": dict(outputs=()),
+        "an unknown output": dict(outputs=("rgb", "variance")),
+        "an output twice": dict(outputs=("rgb", "rgb")),
+        "k_depth < 0": dict(k_depth=-0.1),
+        "k_depth inf": dict(k_depth=inf),
+        "k_depth nan": dict(k_depth=nan),
+        "k_depth None": dict(k_depth=None),
+        "k_depth True": dict(k_depth=True),
+        "k_normal < 0": dict(k_normal=-1.0),
+        "k_normal nan": dict(k_normal=nan),
+        "k_normal a string": dict(k_normal="0.9"),
+        "eps 0": dict(eps=0.0),
+        "eps < 0": dict(eps=-1e-3),
+        "eps inf": dict(eps=inf),
+        "eps nan": dict(eps=nan),
+        "use_index 1": dict(use_index=1),
+        "albedo None": dict(albedo=None),
+    }
+    for what, kw in bad.items():
+        args = dict(reqs_lo=lo, reqs_hi=hi)
+        args.update(kw)
+        with pytest.raises(ValueError):
+            fu.check_upsample(**args)
+            pytest.fail(what)
+    with pytest.raises(ValueError):
+        fu.check_upsample([], hi)
+
+
+def test_film_upsampler_runs_its_checks_before_anything_else():
+    """No film, strips that do not fit, bad constants: ValueError before torch or the library is touched."""
+    from ray_tracer_s8_amd import _upsample_lib
+    film = types.SimpleNamespace(reqs=tuple(strips(24, 42, 3, (1, 2))))
+    hi = strips(48, 84, 6, (2, 3, 4, 5))
+    loaded = _upsample_lib._lib
+    for f, h, kw in ((None, hi, {}), (film, strips(24, 42, 3, (1, 2)), {}), (film, hi, dict(k_depth=-1.0)), (film, hi, dict(eps=0.0)),
+                     (film, hi, dict(k_normal=float("nan"))), (film, [], {})):
+        with pytest.raises(ValueError):
+            rt.FilmUpsampler(f, h, **kw)
+    assert _upsample_lib._lib is loaded
+
+
+_IMPORT_CHILD = r"""
+import sys
+import ray_tracer_s8_amd as rt
+import ray_tracer_s8_amd.film_upsampler as fu
+import ray_tracer_s8_amd._upsample_lib as ul
+assert "torch" not in sys.modules
+assert ul._lib is None                                  # importing loads nothing
+assert callable(fu.check_upsample) and callable(fu.FilmUpsampler.features) and callable(fu.FilmUpsampler.upsample)
+assert callable(fu.FilmUpsampler.resolve) and callable(fu.FilmUpsampler.close)
+assert sorted(ul.SIGNATURES) == sorted(%r)
+lo = [rt.default_request(width=8, height=6, divisions=2, division_no=k, spp=2) for k in range(2)]
+hi = [rt.default_request(width=24, height=18, divisions=1, division_no=0, spp=1)]
+assert fu.check_upsample(lo, hi, ("hits",), ("hits",)).scale == 3
+assert "torch" not in sys.modules and ul._lib is None
+print("ok")
+""" % (NAMES,)
+
+
+def test_film_upsampler_and_its_binding_import_without_torch():
+    r = subprocess.run([sys.executable, "-c", _IMPORT_CHILD], capture_output=True, text=True, cwd=ROOT, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
+
+
+def test_abi_module_holds_nothing_of_the_upsample_library():
+    names = [n for n in dir(_abi) if "rtu_" in n.lower() or "upsampl" in n.lower()]
+    assert names == [], names
+    assert _abi.RT_ABI_VERSION == 4
+
+
+def test_exports():
+    from ray_tracer_s8_amd import _upsample_lib
+    _abi.load()
+    _abi.load_debug()
+    declared = set(_surface.parse()["functions"])
+    assert len(declared) == 51 and _surface.exported(build.LIB_PATH) == declared
+    for path in (build.LIB_PATH, build.DEBUG_LIB_PATH, build.build_film(), build.build_history(), build.build_sampler()):
+        assert not [s for s in _surface.all_exported(path) if "rtu_" in s], path
+    mine = {s for s in _surface.all_exported(build.build_upsample()) if not s.startswith("_")}
+    assert mine == set(_upsample_lib.SIGNATURES) == set(NAMES) and all(s.startswith("rtu_") for s in mine), mine
+    assert not _surface.exported(build.UPSAMPLE.path)                 # nothing of the tile ABI
+    # the private header declares exactly the functions the binding names, and the version the binding expects
+    text = (build.UPSAMPLE.src_dir / "rt_upsample.h").read_text()
+    assert set(re.findall(r"^int (rtu_\w+)\(", text, re.M)) == set(_upsample_lib.SIGNATURES)
+    assert re.search(r"^#define RTU_VERSION (\d+)u$", text, re.M).group(1) == str(_upsample_lib.RTU_VERSION) == "1"
+    status = dict((int(v), n) for n, v in re.findall(r"^#define (RTU_ERR_\w+) (\d+)", text, re.M))
+    assert status == _upsample_lib.STATUS and sorted(status) == [1, 2, 3, 4]
+    assert not (ROOT / "include" / "rt_upsample.h").exists()
+    # and no other source of the package speaks of an rtu_ name
+    for d in (build.CSRC, build.FILM_CSRC, build.HISTORY_CSRC, build.SAMPLER.src_dir, ROOT / "include"):
+        for f in d.rglob("*"):
+            if f.is_file():
+                assert "rtu_" not in f.read_text().lower(), f
+
+
+def test_the_upsampler_is_a_library_of_the_film_set(monkeypatch):
+    lib = build.UPSAMPLE
+    assert isinstance(lib, build.Library)
+    # the tuples the earlier tests pin keep their values; the new one holds them and this library
+    assert build.LIBRARIES == (build.PRODUCT, build.DEBUG, build.FILM, build.HISTORY)
+    assert build.PRIVATE_LIBRARIES == (build.FILM, build.HISTORY, build.SAMPLER)
+    assert build.FILM_LIBRARIES == (build.FILM, build.HISTORY, build.SAMPLER, build.UPSAMPLE)
+    assert lib not in build.LIBRARIES and lib not in build.PRIVATE_LIBRARIES
+    assert lib.path == build.LIB_DIR / "librt_upsample.so" and lib.obj_dir == build.LIB_DIR / "obj_upsample"
+    others = (*build.LIBRARIES, build.SAMPLER)
+    assert lib.path not in [o.path for o in others] and lib.obj_dir not in [o.obj_dir for o in others]
+    assert lib.units == (("rt_upsample.hip", ()),) and (lib.src_dir / "rt_upsample.hip").is_file()
+    for name in ("rt_upsample.h", "rt_upsample_math.h", "rt_upsample.hip.h"):
+        assert (lib.src_dir / name).is_file()
+    # beside csrc/: its own directory, the csrc/ headers it includes and no other, the C header, the recipe
+    assert lib.src_dir == build.PKG / "upsample_csrc" and build.CSRC not in lib.src_dir.parents
+    deps = build.dep_files(lib)
+    assert any(lib.src_dir in d.parents for d in deps) and Path(build.__file__) in deps
+    assert sorted(d.name for d in deps if d.parent == build.CSRC) == ["rt_consts.h", "rt_denoise_math.h"]
+    included = set()
+    for f in lib.src_dir.iterdir():
+        included |= set(re.findall(r'^#include "(\w+\.h)"', f.read_text(), re.M))
+    assert {n for n in included if (build.CSRC / n).exists()} == {"rt_consts.h", "rt_denoise_math.h"}
+    for other in others:
+        assert not any(lib.src_dir in d.parents for d in build.dep_files(other)), other.path
+        assert not any(other.src_dir in d.parents for d in deps if other.src_dir != build.CSRC), other.path
+        assert "rt_upsample" not in build.record(other)
+    # the record: the golden one, the product's flags plus -fno-slp-vectorize, never the experiments' flags
+    golden = (GOLDEN / "upsample.flags").read_text()
+    before = [build.record(o) for o in others if o is not build.PRODUCT]
+    assert build.record(lib) == golden and golden.startswith("rt_upsample.hip: ")
+    flags = golden.split(": ", 1)[1].split()
+    assert flags == [f for f in build.HIPCC_FLAGS if f != "-shared"] + ["-fno-slp-vectorize"]
+    assert "-ffp-contract=off" in flags and not any("correctly-rounded" in f or "fast-math" in f for f in flags)
+    monkeypatch.setenv("RT_EXTRA_HIPCC_FLAGS", "-DRT_PROFILE_TIME")
+    assert "-DRT_PROFILE_TIME" in build.flags_record() and build.record(lib) == golden
+    assert [build.record(o) for o in others if o is not build.PRODUCT] == before
+    monkeypatch.delenv("RT_EXTRA_HIPCC_FLAGS")
+    path = build.build_upsample()
+    assert path == lib.path and path.exists() and not build.stale(lib) and lib.record_path.read_text() == golden
+
+
+def test_build_makes_the_film_set(monkeypatch):
+    """build() goes over FILM_LIBRARIES: it asks for each of them, then for the product."""
+    asked = []
+    monkeypatch.setattr(build, "ensure", lambda lib, force=False, verbose=False: asked.append(lib.path) or lib.path)
+    build.build()
+    assert asked == [*(l.path for l in build.FILM_LIBRARIES), build.LIB_PATH]
+
+
+def test_the_binding_loads_the_library_and_refusals_are_statuses():
+    """Loading binds no device: rtu_version is host arithmetic, and rtu_upsample refuses before any launch."""
+    from ray_tracer_s8_amd import _upsample_lib as ul
+    lib = ul.load()
+    inf, nan = float("inf"), float("nan")
+    assert lib.rtu_version(None) == 1
+    v = C.c_uint32(0)
+    assert lib.rtu_version(C.byref(v)) == 0 and v.value == ul.RTU_VERSION
+    assert lib.rtu_upsample(None, None) == 1
+    MB = 1 << 20
+    at = lambda k: C.c_void_p(k * MB)                                 # (addresses never read: every call here is refused)
+    full = lambda k: dict(albedo=at(k), normal=at(k + 1), depth=at(k + 2), hits=at(k + 3), index=at(k + 4), samples=1)
+
+    def call(lo=None, hi=None, **kw):
+        good = dict(Wl=8, Rl=4, Hl=12, y0l=4, Wh=16, Rh=8, Hh=24, y0h=8, scale=2, k_depth=0.1, k_normal=0.9, eps=0.01, linear=at(1),
+                    out_linear=at(20), out_f32=at(21), out_rgb=at(22), out_class=at(23))
+        good.update(kw)
+        return lib.rtu_upsample(ul.UpsampleArgs(lo=ul.Planes(**{**full(2), **(lo or {})}), hi=ul.Planes(**{**full(10), **(hi or {})}),
+                                                **good), None)
+
+    bad = [dict(Wl=0), dict(Rl=0), dict(Hl=0), dict(Wh=0), dict(Rh=0), dict(Hh=0), dict(scale=1), dict(scale=5), dict(scale=3),
+           dict(Wh=17), dict(Hh=25), dict(y0l=9), dict(y0h=17), dict(Rh=17), dict(form=1), dict(reserved=1), dict(linear=None),
+           dict(linear=C.c_void_p(MB + 2)), dict(out_linear=None, out_f32=None, out_rgb=None, out_class=None),
+           dict(out_f32=C.c_void_p(21 * MB + 1)), dict(k_depth=-1.0), dict(k_depth=nan), dict(k_depth=inf), dict(k_normal=-0.5),
+           dict(k_normal=nan), dict(eps=0.0), dict(eps=-1.0), dict(eps=inf), dict(eps=nan),
+           # an output that is an input, an output that is another output, an output that ends inside an input
+           dict(out_linear=at(1)), dict(out_rgb=at(2)), dict(out_f32=at(12)), dict(out_class=at(14)), dict(out_f32=at(20)),
+           dict(out_class=at(22)), dict(out_linear=C.c_void_p(MB - 16)), dict(out_class=C.c_void_p(5 * MB + 8 * 4 * 4 - 1))]
+    for kw in bad:
+        assert call(**kw) == 1, kw
+    sides = [(dict(albedo=None), None), (None, dict(normal=None)), (dict(hits=None), dict(hits=None)), (dict(index=None), None),
+             (dict(samples=0), None), (None, dict(samples=0)), (dict(reserved=1), None), (None, dict(reserved=1)),
+             (dict(depth=C.c_void_p(4 * MB + 2)), None)]
+    for lo, hi in sides:
+        assert call(lo, hi) == 1, (lo, hi)
+    # a frame beyond what the kernel indexes: more than 2^31 - 1 output pixels, a side of 2^24 or more
+    assert call(Wl=1 << 15, Rl=1 << 14, Hl=1 << 14, y0l=0, Wh=1 << 16, Rh=1 << 15, Hh=1 << 15, y0h=0) == 2
+    assert call(Wl=1 << 23, Wh=1 << 24) == 2 and call(Hl=1 << 23, Hh=1 << 24) == 2
+    with pytest.raises(ul.RtuError):
+        ul.check("rtu_upsample", 2)
+    assert isinstance(ul.RtuError("x", 1), RuntimeError) and "RTU_ERR_BAD_ARG" in str(ul.RtuError("x", 1))
