@@ -35,8 +35,15 @@
  *     r_{i+1} = Sc / Sw;  v_{i+1} = Sv / (Sw*Sw).
  *   Outputs (each optional, at least one): linear, f32 and rgb as rtdn::output_pixel without albedo; variance: v_I as an (R, W) f32
  *     plane.
- * With I = 0, f32 and rgb are the film's preview, bit for bit.  Inputs are finite and non-negative, as the film writes them;
- * otherwise the result is unspecified, but nothing faults or reads outside a buffer.  There is no albedo demodulation. */
+ * With I = 0, f32 and rgb are the film's preview, bit for bit.  There is no albedo demodulation.
+ *
+ * Subnormal, infinite and NaN inputs.  The film writes finite, non-negative sums, but no value of a plane is refused, and nothing
+ * faults or reads outside a buffer whatever the planes hold: no address depends on a plane's value.  The arithmetic above proceeds
+ * as IEEE 754 defines it for every operand, with subnormal operands and results kept (nothing is flushed to zero), signed zeros
+ * and infinities as the operations make them, and each `x > 0 ? x : +0` as written: false for a NaN and for -0, so both give +0.
+ * Where the text yields a NaN the output is a NaN, of unspecified payload and sign; `as u8` of a NaN is 0.  Every other output
+ * value, the signs of zeros included, is the one the text defines (tests/test_gpu_film_extremes.py holds the
+ * kernels to it). */
 #ifndef RT_FILM_H
 #define RT_FILM_H
 

@@ -79,7 +79,17 @@
  * resolve derives from blended moments is SVGF's: the variance of the integrated signal at e samples per frame, NOT divided by the
  * history length.  It steers the edge-stop; it is not the variance of the blended mean.
  *
- * Inputs are finite as the film writes them; otherwise the result is unspecified, but nothing faults or reads outside a buffer. */
+ * Subnormal, infinite and NaN inputs.  The film writes finite sums, but no value of a plane or of the previous state is refused, and
+ * nothing faults or reads outside a buffer whatever they hold: the one index that depends on a plane's value is the reprojected
+ * position (fx, fy), which step 4 tests against the film's bounds before it is converted to an integer (a NaN or an infinity fails
+ * that test: "no history"), and every tap is tested against the bounds again.  The arithmetic above proceeds as IEEE 754 defines it
+ * for every operand, with subnormal operands and results kept (nothing is flushed to zero), signed zeros and infinities as the
+ * operations make them, and every comparison as written: each is false for a NaN, so `!(x <= lim)` rejects a tap whose distance is
+ * a NaN, `N > n_max` and `alpha > a` keep a NaN, the clip leaves a channel alone whose bound or value is a NaN, and
+ * `d > 0 ? d : +0` gives +0 for a NaN and for -0.  (float)hits is the correctly rounded conversion, above 2^24 too.  Where the text
+ * yields a NaN the output is a NaN, of unspecified payload and sign, and it stays in the state for the frames that read it.  Every
+ * other output value, the signs of zeros included, is the one the text defines (DESIGN.md 4.28:
+ * tests/test_gpu_film_extremes.py holds the kernels to it, both forms of the clip among them). */
 #ifndef RT_HISTORY_H
 #define RT_HISTORY_H
 

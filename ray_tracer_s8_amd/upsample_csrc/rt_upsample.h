@@ -55,7 +55,14 @@
  * roundings, so V is within 15 u < 2^-20 of c, relatively, to first order, the slack to 2^-20 taking every higher-order term.
  * (tests/test_upsample_host.py holds the restatement to that.)
  *
- * Inputs are finite as the film writes them; otherwise the result is unspecified, but nothing faults or reads outside a buffer. */
+ * Subnormal, infinite and NaN inputs.  The film writes finite sums, but no value of a plane is refused, and nothing faults or reads
+ * outside a buffer whatever the planes hold: every tap address comes from the two frames' sizes alone and is clamped into the low
+ * film.  The arithmetic above proceeds as IEEE 754 defines it for every operand, with subnormal operands and results kept (nothing
+ * is flushed to zero), signed zeros and infinities as the operations make them, and every comparison as written: each is false for
+ * a NaN, so a tap whose depth or normal test meets a NaN is rejected, and `!(Sw > 0)` sends a pixel whose weights sum to a NaN to
+ * class 1.  (float)hits is the correctly rounded conversion, above 2^24 too; eps + A / k = 0 divides by zero as IEEE does.  Where
+ * the text yields a NaN the output is a NaN, of unspecified payload and sign; `as u8` of a NaN is 0.  Every other output value, the
+ * signs of zeros included, is the one the text defines (tests/test_gpu_film_extremes.py holds the kernel to it). */
 #ifndef RT_UPSAMPLE_H
 #define RT_UPSAMPLE_H
 

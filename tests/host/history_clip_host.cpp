@@ -159,6 +159,24 @@ int main() {
             M[2 * i] = rnd();
             M[2 * i + 1] = rnd();
         }
+        // a few subnormal, huge and non-finite inputs at pixels of their own (the classes of tests/_extreme_planes.py), and the integer
+        // planes' extremes: whatever a plane holds, no line reads or writes outside its buffer
+        const float special[] = {1e-45f, -1e-45f, 5.9e-39f, 1.1754942e-38f, -0.0f, 1e-30f, 1.9e19f, 3e38f, -3.4028235e38f,
+                                 __builtin_inff(), -__builtin_inff(), __builtin_nanf(""), -__builtin_nanf(""), -1.5f};
+        for (size_t j = 0; j < sizeof special / sizeof *special; j++) {
+            const size_t i = (53 * j + 11 * (size_t)k + 5) % np;
+            const float v = special[j];
+            switch ((j + (size_t)k) % 4) {
+                case 0: C[3 * i + j % 3] = v; break;
+                case 1: M[2 * i + j % 2] = v; break;
+                case 2: D[i] = v; break;
+                default: N[3 * i + j % 3] = v; break;
+            }
+        }
+        hits[(29 * (size_t)k + 3) % np] = 0xffffffffu;
+        hits[(29 * (size_t)k + 47) % np] = (1u << 24) + 1u;
+        hits[(29 * (size_t)k + 91) % np] = 0u;                    // (under a depth and a normal that are not zero)
+        idx[(29 * (size_t)k + 135) % np] = 0xffffffffu;
         Set &pv = sets[(k + 1) & 1], &nx = sets[k & 1];
         void* prev[6] = {pv.a.data(), pv.m.data(), pv.l.data(), pv.d.data(), pv.i.data(), pv.n.data()};
         void* next[6] = {nx.a.data(), nx.m.data(), nx.l.data(), nx.d.data(), nx.i.data(), nx.n.data()};

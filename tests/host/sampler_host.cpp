@@ -92,6 +92,18 @@ int main() {
         mom[2 * i] = y * (float)e0;
         mom[2 * i + 1] = (y * y + s * s) * (float)e0;
     }
+    // a few subnormal, huge and non-finite sums at pixels of their own (the classes of tests/_extreme_planes.py), and below some
+    // such samples: whatever the planes hold, no line reads or writes outside its buffer
+    const float special[] = {1e-45f, -1e-45f, 5.9e-39f, 1.1754942e-38f, -0.0f, 1e-30f, 1.9e19f, 3e38f, -3.4028235e38f,
+                             __builtin_inff(), -__builtin_inff(), __builtin_nanf(""), -__builtin_nanf(""), -1.5f};
+    const size_t n_special = sizeof special / sizeof *special;
+    for (size_t j = 0; j < n_special; j++) {
+        const size_t i = (31 * j + 7) % n;
+        if (j % 3 == 2)
+            acc[3 * i + j % 3] = special[j];
+        else
+            mom[2 * i + j % 3] = special[j];
+    }
     uint64_t total = 0;
     for (uint32_t dilate = 0; dilate < 2; dilate++) {
         if (sampler_select_host(W, R, Hs, dilate, 0.05f, 0.015625f, mom.data(), cnt.data(), err.data(), active.data(), sc.data())) return 1;
@@ -102,6 +114,7 @@ int main() {
             sampler_gather_host(na, k, P, active.data() + (size_t)s * P, rays.data(), out.data());
             std::vector<float> rgb((size_t)na * k * 3);
             for (float& v : rgb) v = rnd();
+            for (size_t j = 0; j < n_special && !rgb.empty(); j++) rgb[(13 * j + s) % rgb.size()] = special[j];
             sampler_fold_host(na, k, P, active.data() + (size_t)s * P, rgb.data(), acc.data() + 3 * (size_t)s * P,
                               mom.data() + 2 * (size_t)s * P, cnt.data() + (size_t)s * P);
             total += na;

@@ -145,8 +145,29 @@ int main() {
             }
         }
     };
+    // a few subnormal, huge and non-finite values at pixels of their own (the classes of tests/_extreme_planes.py) and the integer
+    // planes' extremes, on a side's planes: whatever a plane holds, no line reads or writes outside its buffer
+    const float special[] = {1e-45f, -1e-45f, 5.9e-39f, 1.1754942e-38f, -0.0f, 1e-30f, 1.9e19f, 3e38f, -3.4028235e38f,
+                             __builtin_inff(), -__builtin_inff(), __builtin_nanf(""), -__builtin_nanf(""), -1.5f};
+    auto salt = [&](size_t n, float k, float* A, float* N, float* D, uint32_t* h, uint32_t* ix) {
+        for (size_t j = 0; j < sizeof special / sizeof *special; j++) {
+            const size_t i = (17 * j + 5) % n;
+            switch (j % 3) {
+                case 0: A[3 * i + j % 3] = special[j]; break;
+                case 1: N[3 * i + j % 3] = special[j]; break;
+                default: D[i] = special[j]; break;
+            }
+        }
+        A[3 * (n / 2)] = -0.01f * k;                              // d = A / k + eps = 0 at the side's k
+        h[3 % n] = 0xffffffffu;
+        h[7 % n] = (1u << 24) + 1u;
+        h[11 % n] = 0u;                                           // (under a depth and a normal that are not zero)
+        ix[13 % n] = 0xffffffffu;
+    };
     fill(nl, Wl, 4, 2, Al.data(), Nl.data(), Dl.data(), hl.data(), il.data());
+    salt(nl, 2.0f, Al.data(), Nl.data(), Dl.data(), hl.data(), il.data());
     for (float& v : L) v = 2.0f * rnd();
+    for (size_t j = 0; j < sizeof special / sizeof *special; j++) L[(7 * j + 2) % L.size()] = special[j];
     std::vector<uint64_t> counts(rtum::BR_COUNT);
     const float fp[3] = {0.1f, 0.9f, 0.01f};
     for (uint32_t s = 2; s <= 4; s++) {
@@ -156,6 +177,7 @@ int main() {
         std::vector<uint32_t> hh(nh), ih(nh);
         std::vector<uint8_t> rgb(nh * 3), cls(nh);
         fill(nh, Wh, 4 * s, 1, Ah.data(), Nh.data(), Dh.data(), hh.data(), ih.data());
+        salt(nh, 1.0f, Ah.data(), Nh.data(), Dh.data(), hh.data(), ih.data());
         const uint32_t dims[10] = {Wl, Rl, Hl, y0l, Wh, Rh, s * Hl, s * y0l, 2, 1};
         for (uint32_t planes = 0; planes <= rtum::P_ALL; planes++) {
             if (!rtum::planes_ok(planes)) continue;

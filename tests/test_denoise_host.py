@@ -22,8 +22,8 @@ MAX_ITER = 8
 TILE_ABI_MAX_PIXELS = 0x7FFFFFFF
 
 
-@pytest.fixture(scope="module")
-def lib():
+def load_lib():
+    """The harness as a library, built if it is missing or older than its sources (tests/test_extreme_planes_host.py loads it too)."""
     OUT.parent.mkdir(exist_ok=True)
     if not OUT.exists() or OUT.stat().st_mtime < max(d.stat().st_mtime for d in DEPS):
         subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", f"-I{CSRC}", f"-I{ROOT / 'include'}",
@@ -35,6 +35,11 @@ def lib():
     l.dn_lds_max_step_default.restype = C.c_uint32
     l.dn_lds_cu.restype = C.c_uint64
     return l
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return load_lib()
 
 
 def _p(a):

@@ -24,8 +24,8 @@ SUBSETS = [(n, d) for n in (False, True) for d in ("", "hits", "depth")]
 ITERATIONS = (0, 1, 3, 5, 8)
 
 
-@pytest.fixture(scope="module")
-def lib():
+def load_lib():
+    """The harness as a library, built if it is missing or older than its sources (tests/test_extreme_planes_host.py loads it too)."""
     OUT.parent.mkdir(exist_ok=True)
     if not OUT.exists() or OUT.stat().st_mtime < max(d.stat().st_mtime for d in DEPS):
         subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", f"-I{CSRC}", f"-I{FILM_CSRC}",
@@ -37,6 +37,11 @@ def lib():
     l.film_resolve_host.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32] + [vp] * 10
     l.film_resolve_host.restype = None
     return l
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return load_lib()
 
 
 def _p(a):

@@ -28,8 +28,8 @@ GAMMAS = (0.5, 1.0, 3.0)
 RADII = (1, 2)
 
 
-@pytest.fixture(scope="module")
-def lib():
+def load_lib():
+    """The harness as a library, built if it is missing or older than its sources (tests/test_extreme_planes_host.py loads it too)."""
     BUILD.mkdir(exist_ok=True)
     deps = [SRC] + DEPS[1:]
     if not OUT.exists() or OUT.stat().st_mtime < max(d.stat().st_mtime for d in deps):
@@ -42,6 +42,11 @@ def lib():
     l.history_clip_frame_host.restype = C.c_int
     assert l.history_clip_branch_count() == len(CLIP_BRANCHES) and l.history_clip_base_branch_count() == len(BRANCHES)
     return l
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return load_lib()
 
 
 def host_frame(lib, rq, pose, prev_rq, prev_pose, frame, prev, consts, gamma, radius, counts, clip_counts):

@@ -42,8 +42,8 @@ PATHS = {
 }
 
 
-@pytest.fixture(scope="module")
-def lib():
+def load_lib():
+    """The harness as a library, built if it is missing or older than its sources (tests/test_extreme_planes_host.py loads it too)."""
     BUILD.mkdir(exist_ok=True)
     if not OUT.exists() or OUT.stat().st_mtime < max(d.stat().st_mtime for d in DEPS):
         subprocess.run([*GXX, "-fPIC", "-shared", "-o", str(OUT), str(SRC)], check=True)
@@ -54,6 +54,11 @@ def lib():
     l.history_frame_host.restype = C.c_int
     assert l.history_branch_count() == len(BRANCHES)
     return l
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return load_lib()
 
 
 def _camera(pose):

@@ -27,8 +27,8 @@ BRANCHES = ("index", "hits", "depth", "normal", "admitted", "class0", "class1") 
 SUBSETS = unp.plane_subsets()
 
 
-@pytest.fixture(scope="module")
-def lib():
+def load_lib():
+    """The harness as a library, built if it is missing or older than its sources (tests/test_extreme_planes_host.py loads it too)."""
     BUILD.mkdir(exist_ok=True)
     if not OUT.exists() or OUT.stat().st_mtime < max(d.stat().st_mtime for d in DEPS):
         subprocess.run([*GXX, "-fPIC", "-shared", "-o", str(OUT), str(SRC)], check=True)
@@ -36,6 +36,11 @@ def lib():
     l.upsample_host.argtypes = [C.c_void_p] * 10
     assert l.upsample_branch_count() == len(BRANCHES)
     return l
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return load_lib()
 
 
 def bits(a):
