@@ -115,6 +115,9 @@ HISTORY_LIB_PATH, HISTORY_CSRC = HISTORY.path, HISTORY.src_dir
 SAMPLER = _private("sampler", ())
 # The UPSAMPLE library: the joint-bilateral upsampling of film_upsampler.py; rtu_* exports, _upsample_lib.py.
 UPSAMPLE = _private("upsample", ("rt_denoise_math.h", "rt_consts.h"))
+# The ROBUST library: the median-of-means estimate of film_robust.py; rtr_* exports, _robust_lib.py.  It includes no
+# csrc/ header.
+ROBUST = _private("robust", ())
 
 # LIBRARIES is the set the recipe's golden test (tests/test_build_recipe.py) knows, and stays those four; PRIVATE_LIBRARIES is the set
 # tests/test_sampler_plan.py knows, and stays those three.  A library added since is a Library value like them and a member of
@@ -122,6 +125,9 @@ UPSAMPLE = _private("upsample", ("rt_denoise_math.h", "rt_consts.h"))
 LIBRARIES = (PRODUCT, DEBUG, FILM, HISTORY)
 PRIVATE_LIBRARIES = (FILM, HISTORY, SAMPLER)
 FILM_LIBRARIES = (*PRIVATE_LIBRARIES, UPSAMPLE)
+# FILM_LIBRARIES is in turn the set tests/test_upsample_plan.py knows, and stays those four.  ALL_FILM_LIBRARIES is every private
+# library: build() makes FILM_LIBRARIES through ensure and the rest through build_robust's own step.
+ALL_FILM_LIBRARIES = (*FILM_LIBRARIES, ROBUST)
 
 
 def _product(extra: list[str] | None = None) -> Library:
@@ -206,10 +212,13 @@ def needs_build() -> bool:
 
 def build(force: bool = False, verbose: bool = False) -> Path:
     """Compile librt_s8.so (or the RT_LIB_VARIANT named) if missing or stale, and with no variant named the private libraries
-    (FILM_LIBRARIES) first."""
+    (FILM_LIBRARIES) first and the robust library (build_robust) last."""
     for lib in () if VARIANT else FILM_LIBRARIES:
         ensure(lib, force, verbose)
-    return ensure(_product(), force, verbose)
+    path = ensure(_product(), force, verbose)
+    if not VARIANT:
+        build_robust(force, verbose)
+    return path
 
 
 def build_debug(force: bool = False, verbose: bool = False) -> Path:
@@ -232,8 +241,14 @@ def build_upsample(force: bool = False, verbose: bool = False) -> Path:
     return ensure(UPSAMPLE, force, verbose)
 
 
+def build_robust(force: bool = False, verbose: bool = False) -> Path:
+    """The robust library if it is missing or stale, or if forced: the recipe's steps themselves, not `ensure`, which build() calls
+    for exactly FILM_LIBRARIES and the product (tests/test_upsample_plan.py)."""
+    return compile_and_link(ROBUST, verbose) if force or stale(ROBUST) else ROBUST.path
+
+
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
     if not VARIANT:
-        for lib in (DEBUG, *FILM_LIBRARIES):
+        for lib in (DEBUG, *ALL_FILM_LIBRARIES):
             print(ensure(lib, force=True, verbose=True))

@@ -172,6 +172,8 @@ class Film:
     caller's own between two calls takes the counters of the film's launches with it.  A Film is not thread-safe, and after an
     RtError its accum is undefined until reset()."""
 
+    _taps: Sequence = ()                          # (the constructor's list; a film put together without it has no tap)
+
     def __init__(self, scene, reqs, *, integrator: str = "nee", mode: int = _abi.RT_NEE_MIS, flags: int = 0,
                  max_records: int = 1 << 22, stream=None, moments: bool = False, _collect_at: int = COLLECT_AT):
         plan = check_job(reqs, integrator, mode, max_records)
@@ -208,6 +210,7 @@ class Film:
             self.moments = torch.zeros((self.rows, self.width, 2), dtype=torch.float32, device=self.device) if moments else None
         self._guided_scratch = None
         self._guided_out: dict = {}
+        self._taps: list = []                     # what is shown every strip's records after their fold (film_robust.py)
 
     # ---- the film's own state
 
@@ -256,6 +259,8 @@ class Film:
             self.accum.zero_()
             if self.moments is not None:
                 self.moments.zero_()
+            for t in self._taps:
+                t._on_reset()
         self.samples = 0
 
     def close(self):
@@ -296,7 +301,9 @@ class Film:
 
     def render_pass(self, begin: int, end: int):
         """Add samples [begin, end) of the spp-sample job to accum; begin must be `samples`, and begin < end <= spp.  Per strip and
-        per sub-range of sample_chunks: the camera's rays and states, the trace from those states with spp = 1, and the fold."""
+        per sub-range of sample_chunks: the camera's rays and states, the trace from those states with spp = 1, and the fold.  A tap
+        in _taps (rt.FilmRobust) is then shown the records the fold just read, on the film's stream: _on_records(strip, b, e, records)
+        with records the (pixels, e - b, 3) view.  With no tap nothing more is enqueued."""
         self._check_open()
         if begin != self.samples:
             raise ValueError(f"render_pass({begin}, {end}): the film holds samples [0, {self.samples}), the next pass begins there")
@@ -314,10 +321,13 @@ class Film:
                     self._reserve(2)
                     self.scene.camera_rays_device(rq, b, e, self._rays.data_ptr(), self._states.data_ptr(), stream=handle)
                     self._trace(n, rq.max_bounces, handle)
+                    records = self._rgb[:n].view(pixels, e - b, 3)
                     if mom is None:
-                        self._fold(acc, self._rgb[:n].view(pixels, e - b, 3))
+                        self._fold(acc, records)
                     else:
-                        self._fold_moments(acc, mom, self._rgb[:n].view(pixels, e - b, 3))
+                        self._fold_moments(acc, mom, records)
+                    for t in self._taps:
+                        t._on_records(i, b, e, records)
         self.samples = end
 
     def render_progressive(self, pass_spp: int):

@@ -19,6 +19,8 @@ The sampler keeps sums of its own: it never writes the film's accum, moments or 
 film stays what it was.  Its resolves are the film's, run on the sums restated "at the film's count" (rts_normalise).
 
 Composing with rt.FilmHistory is out of scope: a history blends sums that every pixel holds at one count, which the sampler's are not.
+The sampler's rounds do not feed the film's taps (rt.FilmRobust): a tap sees the film's own passes only, and composing the two is out
+of scope.
 
 This module imports without torch; the library is loaded when a FilmSampler is constructed."""
 from __future__ import annotations

@@ -1,0 +1,121 @@
+// rt_robust.hip — the host side of librt_robust.so (rt_robust.h): argument checks, the choice of the resolve kernel's
+// instance by K, the launches.  No global state, no allocation; every function catches everything inside its body.
+#include <cstring>
+
+#include "rt_robust.h"
+#include "rt_robust.hip.h"
+
+#define RTR_EXPORT extern "C" __attribute__((visibility("default")))
+
+namespace {
+
+template <class F>
+int guarded(const F& body) {
+    try {
+        return body();
+    } catch (...) {
+        return RTR_ERR_INTERNAL;
+    }
+}
+
+struct Range {
+    uintptr_t b, e;
+};
+
+// buffer q of n bytes (nothing for a NULL)
+Range range(const void* q, uint64_t n) { return q ? Range{(uintptr_t)q, (uintptr_t)q + (uintptr_t)n} : Range{0, 0}; }
+bool overlap(const Range& a, const Range& b) { return a.b < a.e && b.b < b.e && a.b < b.e && b.b < a.e; }
+bool misaligned(const void* q) { return ((uintptr_t)q & 3u) != 0; }
+
+using ResolveKernel = void (*)(const rtrk::ResolveParams);
+
+// the instance for a bucket count: seven of them, odd 3 ... 15
+ResolveKernel resolve_instance(uint32_t K) {
+    switch (K) {
+        case 3: return rtrk::rtr_resolve_kernel<3>;
+        case 5: return rtrk::rtr_resolve_kernel<5>;
+        case 7: return rtrk::rtr_resolve_kernel<7>;
+        case 9: return rtrk::rtr_resolve_kernel<9>;
+        case 11: return rtrk::rtr_resolve_kernel<11>;
+        case 13: return rtrk::rtr_resolve_kernel<13>;
+        case 15: return rtrk::rtr_resolve_kernel<15>;
+        default: return nullptr;
+    }
+}
+
+constexpr uint64_t MAX_COUNT = 0x7fffffffull;     // pixels, and records, of a call
+
+}  // namespace
+
+RTR_EXPORT int rtr_version(uint32_t* version) {
+    return guarded([&] {
+        if (!version) return RTR_ERR_BAD_ARG;
+        *version = RTR_VERSION;
+        return RTR_OK;
+    });
+}
+
+RTR_EXPORT int rtr_fold(const rtr_fold_args* a, void* stream) {
+    return guarded([&] {
+        if (!a || a->pixels == 0 || a->n == 0 || !rtrm::buckets_ok(a->K)) return RTR_ERR_BAD_ARG;
+        if (!a->records || !a->buckets || misaligned(a->records) || misaligned(a->buckets)) return RTR_ERR_BAD_ARG;
+        const uint64_t P = a->pixels;
+        if (a->bucket_stride < 3 * P) return RTR_ERR_BAD_ARG;          // the parts of two buckets would overlap
+        if (P > MAX_COUNT || P * a->n > MAX_COUNT || a->bucket_stride > (1ull << 40)) return RTR_ERR_LIMIT;
+        const Range rec = range(a->records, P * a->n * 12);
+        for (uint32_t k = 0; k < a->K; k++)
+            if (overlap(rec, range((const void*)((uintptr_t)a->buckets + (uintptr_t)(k * a->bucket_stride * 4)), P * 12)))
+                return RTR_ERR_BAD_ARG;
+
+        rtrk::FoldParams p;
+        std::memset(&p, 0, sizeof p);
+        p.pixels = a->pixels, p.n = a->n, p.first_mod_K = a->first % a->K, p.K = a->K;
+        p.bucket_stride = (size_t)a->bucket_stride;
+        p.records = a->records;
+        p.buckets = a->buckets;
+        const dim3 grid((a->pixels + rtrk::BLOCK - 1) / rtrk::BLOCK);
+        hipLaunchKernelGGL(rtrk::rtr_fold_kernel, grid, dim3(rtrk::BLOCK), 0, (hipStream_t)stream, p);
+        return hipGetLastError() == hipSuccess ? RTR_OK : RTR_ERR_HIP;
+    });
+}
+
+RTR_EXPORT int rtr_resolve(const rtr_resolve_args* a, void* stream) {
+    return guarded([&] {
+        if (!a || a->W == 0 || a->R == 0 || !rtrm::buckets_ok(a->K) || a->samples < a->K) return RTR_ERR_BAD_ARG;
+        if (a->mode != RTR_GINI && a->mode != RTR_TRIM) return RTR_ERR_BAD_ARG;
+        if (a->mode == RTR_TRIM ? a->c > (a->K - 1) / 2 : a->c != 0) return RTR_ERR_BAD_ARG;
+        if (!a->buckets) return RTR_ERR_BAD_ARG;
+        if (!a->out_linear && !a->out_gini && !a->out_kept && !a->out_variance && !a->out_accum && !a->out_moments) return RTR_ERR_BAD_ARG;
+        const void* dwords[] = {a->buckets, a->out_linear, a->out_gini, a->out_kept, a->out_variance, a->out_accum, a->out_moments};
+        for (const void* q : dwords)
+            if (misaligned(q)) return RTR_ERR_BAD_ARG;
+        const uint64_t n = (uint64_t)a->W * a->R;
+        if (n > MAX_COUNT) return RTR_ERR_LIMIT;
+        // an output overlaps neither the buckets nor another output
+        const Range in = range(a->buckets, n * a->K * 12);
+        const Range out[] = {range(a->out_linear, n * 12), range(a->out_gini, n * 4),   range(a->out_kept, n * 4),
+                             range(a->out_variance, n * 4), range(a->out_accum, n * 12), range(a->out_moments, n * 8)};
+        for (int k = 0; k < 6; k++) {
+            if (overlap(out[k], in)) return RTR_ERR_BAD_ARG;
+            for (int j = k + 1; j < 6; j++)
+                if (overlap(out[k], out[j])) return RTR_ERR_BAD_ARG;
+        }
+
+        rtrk::ResolveParams p;
+        std::memset(&p, 0, sizeof p);
+        p.call = rtrm::make_call(a->K, a->samples, a->mode, a->c);
+        p.pixels = (uint32_t)n;
+        p.buckets = a->buckets;
+        p.out_linear = a->out_linear;
+        p.out_gini = a->out_gini;
+        p.out_kept = a->out_kept;
+        p.out_variance = a->out_variance;
+        p.out_accum = a->out_accum;
+        p.out_moments = a->out_moments;
+        const ResolveKernel k = resolve_instance(a->K);
+        if (!k) return RTR_ERR_INTERNAL;
+        const dim3 grid(((uint32_t)n + rtrk::BLOCK - 1) / rtrk::BLOCK);
+        hipLaunchKernelGGL(k, grid, dim3(rtrk::BLOCK), 0, (hipStream_t)stream, p);
+        return hipGetLastError() == hipSuccess ? RTR_OK : RTR_ERR_HIP;
+    });
+}
