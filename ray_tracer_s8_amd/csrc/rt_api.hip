@@ -130,13 +130,22 @@ enum DebugKnob {
     DBG_TAIL_TILES,        // RT_TAIL_TILES      tiles at the end of a launch's queue handed out in quarters; -1: host rule (default -1)
     DBG_STRIP_COST,        // RT_STRIP_COST      0: the kernels do not count per-strip ray segments for the frame context (A/B)   (default 1)
     DBG_DENOISE_LDS_STEP,  // RT_DENOISE_LDS_STEP denoiser: largest step staged in LDS (0: none); -1: rtplan::DN_LDS_MAX_STEP    (default -1)
+    DBG_LTREE_GENERAL,     // RT_LTREE_GENERAL   1: the LDS-tree engines take their general kernel for sphere-only worlds too (A/B, tests)  (default 0)
+    DBG_PLAIN_FRAME,       // RT_PLAIN_FRAME     0: plain frames commit through the general path of the LDS-tree kernels (A/B, tests)       (default 1)
     DBG_N
 };
 std::atomic<int> g_dbg[DBG_N];
 const struct { const char* env; int def; } g_dbg_spec[DBG_N] = {
     {"RT_LDS_TREE", 1}, {"RT_CULL_WALK", -1}, {"RT_NO_STAGE", 0}, {"RT_SLOTS", 0}, {"RT_FORCE_CAPPED", 0},
     {"RT_STACK_LDS", 0}, {"RT_COMPACT", 1}, {"RT_REFILL_EIGHTHS", 0}, {"RT_COMMIT_SLOTS", 0}, {"RT_VERBOSE", 0}, {"RT_REORDER", 1}, {"RT_TAIL_TILES", -1}, {"RT_STRIP_COST", 1},
-    {"RT_DENOISE_LDS_STEP", -1}};
+    {"RT_DENOISE_LDS_STEP", -1}, {"RT_LTREE_GENERAL", 0}, {"RT_PLAIN_FRAME", 1}};
+#ifdef RT_DEBUG_HOOKS
+// An OUTPUT of the launch path, not a knob: which variant of an LDS-tree kernel the last tile launch of the process took — bit 0 the
+// sphere-only instantiation, bit 1 the plain-frame commit.  Test library only (the product stores nothing); never read from the
+// environment; tests exchange it through rt_debug_set under the name RT_LAST_VARIANT (tests/test_abi.py pins the set of
+// rt_debug_* exports, so it has no entry point of its own and, for want of a scene argument there, is one word per process).
+std::atomic<int> g_last_variant{0};
+#endif
 std::once_flag g_dbg_once;
 void dbg_load_env() {
     std::call_once(g_dbg_once, [] {
@@ -168,6 +177,8 @@ rtplan::Knobs plan_knobs() {
     k.compact = dbg(DBG_COMPACT);
     k.refill_eighths = dbg(DBG_REFILL_EIGHTHS);
     k.tail_tiles = dbg(DBG_TAIL_TILES);
+    k.ltree_general = dbg(DBG_LTREE_GENERAL);
+    k.plain_frame = dbg(DBG_PLAIN_FRAME);
     return k;
 }
 
@@ -395,9 +406,12 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
     p.counters = sc->d_counters.get();
     p.queue = sc->d_counters.get() + 4 + sc->events.pending().size();
     p.strip_cost = dbg(DBG_STRIP_COST) ? d_strip_cost : nullptr;
+    bool any_f32 = false;
+    for (uint32_t i = 0; i < n; i++) any_f32 = any_f32 || p.strips[i].f32 != nullptr;
+    p.plain = rtplan::plain_frame(pl, any_f32, p.strip_cost != nullptr) ? 1u : 0u;
 
     // persistent grid: as many workgroups as the chip holds at this LDS/VGPR budget
-    const rtk::KernelFn kern = pl.isect < 2 ? rtk::kernel_linear(pl.isect, pl.expanded) : rtk::kernel_traverse(pl.isect, pl.count_steps);
+    const rtk::KernelFn kern = pl.isect < 2 ? rtk::kernel_linear(pl.isect, pl.expanded) : rtk::kernel_traverse(pl.isect, pl.count_steps, pl.tris);
     int per_cu = 0;
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, pl.block, pl.lds));
     if (per_cu < 1) per_cu = 1;
@@ -423,6 +437,9 @@ int launch_batch(rt_scene* sc, const rt_tile_request* rqs, uint32_t n, void* con
     HIPCHK(hipMemsetAsync(p.queue, 0, sizeof(unsigned long long), stream));
     sc->last_engine = (uint32_t)pl.engine;
     sc->last_form = pl.expanded ? 1u : 0u;
+#ifdef RT_DEBUG_HOOKS
+    g_last_variant.store((pl.tris ? 0 : 1) | (p.plain ? 2 : 0), std::memory_order_relaxed);
+#endif
     if ((rc = enqueue(sc, stream, kern, pl.blocks, pl.block, pl.lds, p))) return rc;
     HIPCHK(hipEventRecord(rg->buf.done.get(), stream));
     if (p.stack_ovf) HIPCHK(hipEventRecord(sc->stack_ovf.done.get(), stream));
@@ -733,6 +750,10 @@ static int ensure_ctx(DeviceCtx* c) {
         for (int alt = 0; alt < 2; alt++)     // the expanded broad phase (ISECT 0, 1) / the node-visit counting twin (ISECT 2 ... 9)
             HIPCHK(hipFuncSetAttribute((const void*)(isect < 2 ? rtk::kernel_linear(isect, alt != 0) : rtk::kernel_traverse(isect, alt != 0)),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)rtplan::LDS_LIMIT));
+    for (int isect : {5, 6})                  // ... and the sphere-only instantiations of the LDS-tree kernels
+        for (int alt = 0; alt < 2; alt++)
+            HIPCHK(hipFuncSetAttribute((const void*)rtk::kernel_traverse(isect, alt != 0, false), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)rtplan::LDS_LIMIT));
     Stream st, cs;                        // (both or neither: the context counts as made by its `stream`)
     HIPCHK(st.create(hipStreamNonBlocking));
     HIPCHK(cs.create(hipStreamNonBlocking));
@@ -1861,6 +1882,7 @@ extern "C" __attribute__((visibility("default"))) int rt_debug_unit(int device, 
 extern "C" __attribute__((visibility("default"))) int rt_debug_set(const char* name, int value) {
     dbg_load_env();
     if (!name) return INT32_MIN;
+    if (!strcmp(name, "RT_LAST_VARIANT")) return g_last_variant.exchange(value);      // (the launch path's output, see there)
     for (int k = 0; k < DBG_N; k++)
         if (!strcmp(name, g_dbg_spec[k].env)) return g_dbg[k].exchange(value);
     return INT32_MIN;

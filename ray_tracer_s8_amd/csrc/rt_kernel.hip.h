@@ -193,6 +193,9 @@ struct KParams {
     unsigned long long* counters;// [0] segments [1] candidates [2] fallbacks
     unsigned long long* queue;   // tile queue head of this launch (zeroed on the stream before it)
     StripDesc strips[MAX_BATCH];
+    uint32_t plain;              // 1: a plain frame (rtplan::plain_frame): s_begin 0, no acc_out, grp 1, spp_rcp != 0, path32 0, no strip has an
+                                 //   f32 plane, no strip_cost — the LDS-tree kernels then commit through the copy without those tests
+                                 //   (the last field: every other one keeps its place in the kernel argument)
 };
 
 // ------------------------------------------------------------------ vector helpers
@@ -650,7 +653,9 @@ __device__ __forceinline__ float cull_bound_tri(float best, V3 o, float k, float
 // through LDS in chunks; 2 = per-lane traversal of the reference BVH (exact 64-byte nodes); 3 = the same walk over
 // 32-byte nodes whose boxes are rounded outwards onto a 16-bit grid, every reached leaf being validated with the
 // reference's exact own-leaf AABB test.
-template <int ISECT, bool EXPANDED, int BS = BLOCK, bool STATS = false>
+// TRIS = false (LDS-tree kernels, chosen by the host for a world without triangles: rtplan::Plan::tris): every primitive is a sphere, so
+// the root tests, the hit arm and the culling bound carry no sphere / triangle choice and no triangle code.
+template <int ISECT, bool EXPANDED, int BS = BLOCK, bool STATS = false, bool TRIS = true>
 __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE : ISECT == 9 ? RT_MINWAVES_TRAV : ISECT >= 7 ? RT_MINWAVES_CULL : ISECT >= 3 ? RT_MINWAVES_QTRAV : ISECT == 2 ? RT_MINWAVES_TRAV : RT_MINWAVES) void rt_tile_kernel(const KParams p) {
     constexpr int BLOCK = BS;                        // threads per workgroup = stride of the per-lane LDS arrays
     constexpr bool STREAMED = (ISECT == 1);
@@ -669,6 +674,11 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
     // the branch-free node step (see there) pays where a step is bound by the wave's instruction stream = nodes in LDS;
     // the L2-gather engines are bound by the gathers and keep the step that skips them at leaves (c3 -14 %, c5 -11 %)
     constexpr bool BFSTEP = LTREE;
+    static_assert(TRIS || LTREE, "the sphere-only instantiation exists for the LDS-tree kernels");
+    constexpr bool PLAIN_OK = LTREE;                 // the plain-frame copy of the commit is compiled in (KParams::plain)
+    // path stack entries are u32: never in the LDS-tree kernels, sphere-only or general — plan_launch admits the LDS tree only up to
+    // rtplan::LT_MAX_PRIMS primitives, and rt_plan.h asserts that this lies within PATH16_MAX_PRIMS, where KParams::path32 is 0
+    auto path32 = [&]() -> bool { return !LTREE && p.path32 != 0u; };
     // leaf-list slots per lane: the exact-node kernel's are fixed (7 KiB lets six of its workgroups share a CU's LDS on
     // c3-class trees; a run-time count cost it 1 %), the quantised kernels' are chosen by the host's LDS plan
     const uint32_t ML = QNODES ? p.maxl : (uint32_t)MAXL_EXACT;   // (LTREE: MAXL_LTREE, see its step)
@@ -809,7 +819,7 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
     // the exact-node variant also holds triangles: cull_bound_tri; a scene of both takes the larger)
     auto far_bound = [&](float best) -> float {
         float b = cull_bound(best, o, p.r_slack);
-        if ((ISECT == 9 || ISECT == 6) && p.n_tri) b = __builtin_fmaxf(b, cull_bound_tri(best, o, p.tri_k, p.tri_diag, p.tri_es, p.tri_e));
+        if (TRIS && (ISECT == 9 || ISECT == 6) && p.n_tri) b = __builtin_fmaxf(b, cull_bound_tri(best, o, p.tri_k, p.tri_diag, p.tri_es, p.tri_e));
         return b;
     };
     V3 td = mk(0, 0, 0);                     // linear engines: 2 * d of the current segment
@@ -878,141 +888,150 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                 // the colours were stored by other lanes of this wave in earlier rounds: every store has completed before the loads
                 // are issued (ring_load: same CU, same write-through L1)
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                const uint32_t n_lanes = p.n_slots * p.grp;               // lane L <-> pixel L % grp of slot L / grp
-                for (uint32_t l0 = 0; l0 < n_lanes; l0 += 64u) {
-                    const uint32_t L = l0 + (uint32_t)lane;
-                    const uint32_t slot = p.grp == 1u ? L : __umulhi(L, p.grp_magic), g = L - slot * p.grp;      // (grp > 1: below 8 spp only)
-                    const bool mine = slot < p.n_slots && ((complete >> (slot & 31u)) & 1u) != 0u;
-                    if (__ballot(mine) == 0ull) continue;
-                    uint32_t stg = STAGE_TILES, cstrip = 0;
-                    bool fin = false;
-                    uint32_t pin = 0;
-                    if (mine) {
-                        const float* sb = ring + __umul24(slot, p.slot_stride) * 3u;
-                        // (header and the first samples are asked for together: one trip to L2, not two; a lane beyond the slot's
-                        // pixels — the short last slot of a tile — sums records nobody wrote and stores nothing)
-                        const uint32_t hx = ring_load(reinterpret_cast<const uint32_t*>(sb) + 0);
-                        const uint32_t hrow = ring_load(reinterpret_cast<const uint32_t*>(sb) + 1);
-                        const uint32_t hmeta = ring_load(reinterpret_cast<const uint32_t*>(sb) + 2);
-                        const float* r = sb + 3u + g * p.upp * 3u;
-                        float sum_r = 0.f, sum_g = 0.f, sum_b = 0.f;
-                        cstrip = hmeta & 0xffu;
-                        if (p.s_begin != 0u && g < ((hmeta >> 8) & 0xffu)) {
-                            // a progressive pass continues the pixel's running sum over samples 0 .. s_begin - 1 (rt_tile.h
-                            // rt_scene_render_tile_pass): the same sequential f32 sum as one pass, resumed where the last pass stopped
-                            const float* a = p.strips[cstrip].acc + ((size_t)hrow * p.W + hx + g) * 3;
-                            sum_r = a[0];
-                            sum_g = a[1];
-                            sum_b = a[2];
-                        }
-                        {
-                            // pix_color += (main.rs:75), s = 0 .. spp - 1; the loads of four samples in flight together
-                            uint32_t i = 0;
-                            // (batches of RT_COMMIT_BATCH, then of four, then single samples: at the reference's 100 samples per pixel a
-                            // pixel's sum is 13 + 1 trips instead of 25)
-                            auto batch = [&](auto cb_tag) {
-                                constexpr int CB = decltype(cb_tag)::value;
+                // PLAIN (LDS-tree kernels, KParams::plain): the launch is a plain frame — one pixel per slot, a power-of-two sample count,
+                // no running sum in or out, no f32 plane, no per-strip cost — and the copy of the commit chosen here once carries none
+                // of those launch-uniform tests.  The same operations on the same operands in the same order either way.  Only the commit
+                // has such a copy: the acquisition's and the kernel's last p.strip_cost tests (once per tile, once per wave) stay as they are.
+                auto commit_complete = [&](auto plain_tag) {
+                    constexpr bool PLAIN = decltype(plain_tag)::value;
+                    const uint32_t n_lanes = PLAIN ? p.n_slots : p.n_slots * p.grp;               // lane L <-> pixel L % grp of slot L / grp
+                    for (uint32_t l0 = 0; l0 < n_lanes; l0 += 64u) {
+                        const uint32_t L = l0 + (uint32_t)lane;
+                        const uint32_t slot = (PLAIN || p.grp == 1u) ? L : __umulhi(L, p.grp_magic), g = PLAIN ? 0u : L - slot * p.grp;      // (grp > 1: below 8 spp only)
+                        const bool mine = slot < p.n_slots && ((complete >> (slot & 31u)) & 1u) != 0u;
+                        if (__ballot(mine) == 0ull) continue;
+                        uint32_t stg = STAGE_TILES, cstrip = 0;
+                        bool fin = false;
+                        uint32_t pin = 0;
+                        if (mine) {
+                            const float* sb = ring + __umul24(slot, p.slot_stride) * 3u;
+                            // (header and the first samples are asked for together: one trip to L2, not two; a lane beyond the slot's
+                            // pixels — the short last slot of a tile — sums records nobody wrote and stores nothing)
+                            const uint32_t hx = ring_load(reinterpret_cast<const uint32_t*>(sb) + 0);
+                            const uint32_t hrow = ring_load(reinterpret_cast<const uint32_t*>(sb) + 1);
+                            const uint32_t hmeta = ring_load(reinterpret_cast<const uint32_t*>(sb) + 2);
+                            const float* r = sb + 3u + g * p.upp * 3u;
+                            float sum_r = 0.f, sum_g = 0.f, sum_b = 0.f;
+                            cstrip = hmeta & 0xffu;
+                            if (!PLAIN && p.s_begin != 0u && g < ((hmeta >> 8) & 0xffu)) {
+                                // a progressive pass continues the pixel's running sum over samples 0 .. s_begin - 1 (rt_tile.h
+                                // rt_scene_render_tile_pass): the same sequential f32 sum as one pass, resumed where the last pass stopped
+                                const float* a = p.strips[cstrip].acc + ((size_t)hrow * p.W + hx + g) * 3;
+                                sum_r = a[0];
+                                sum_g = a[1];
+                                sum_b = a[2];
+                            }
+                            {
+                                // pix_color += (main.rs:75), s = 0 .. spp - 1; the loads of four samples in flight together
+                                uint32_t i = 0;
+                                // (batches of RT_COMMIT_BATCH, then of four, then single samples: at the reference's 100 samples per pixel a
+                                // pixel's sum is 13 + 1 trips instead of 25)
+                                auto batch = [&](auto cb_tag) {
+                                    constexpr int CB = decltype(cb_tag)::value;
 #pragma clang loop unroll(disable)
-                                for (; i + (uint32_t)CB <= p.upp; i += (uint32_t)CB) {
-                                    LCOUNT(12);
-                                    float c[3 * CB];
+                                    for (; i + (uint32_t)CB <= p.upp; i += (uint32_t)CB) {
+                                        LCOUNT(12);
+                                        float c[3 * CB];
 #pragma unroll
-                                    for (int e = 0; e < 3 * CB; e++) c[e] = ring_load(r + e);
+                                        for (int e = 0; e < 3 * CB; e++) c[e] = ring_load(r + e);
 #pragma unroll
-                                    for (int e = 0; e < CB; e++) {
-                                        sum_r = sum_r + c[3 * e + 0];
-                                        sum_g = sum_g + c[3 * e + 1];
-                                        sum_b = sum_b + c[3 * e + 2];
+                                        for (int e = 0; e < CB; e++) {
+                                            sum_r = sum_r + c[3 * e + 0];
+                                            sum_g = sum_g + c[3 * e + 1];
+                                            sum_b = sum_b + c[3 * e + 2];
+                                        }
+                                        r += 3 * CB;
                                     }
-                                    r += 3 * CB;
-                                }
-                            };
-                            if (RT_COMMIT_BATCH > 4 && !QNODES) batch(std::integral_constant<int, RT_COMMIT_BATCH>{});      // (the 96-register quantised kernels would spill)
-                            batch(std::integral_constant<int, 4>{});
+                                };
+                                if (RT_COMMIT_BATCH > 4 && !QNODES) batch(std::integral_constant<int, RT_COMMIT_BATCH>{});      // (the 96-register quantised kernels would spill)
+                                batch(std::integral_constant<int, 4>{});
 #pragma clang loop unroll(disable)
-                            for (; i < p.upp; i++) {
-                                LCOUNT(12);
-                                const float cr = ring_load(r + 0);
-                                const float cg = ring_load(r + 1);
-                                const float cb = ring_load(r + 2);
-                                sum_r = sum_r + cr;
-                                sum_g = sum_g + cg;
-                                sum_b = sum_b + cb;
-                                r += 3;
-                            }
-                        }
-                        if (g < ((hmeta >> 8) & 0xffu)) {                    // (the last slot of a ragged tile holds fewer pixels)
-                            // ---- mean, gamma, quantise, store (main.rs:78-81)
-                            // pix_color / sample_count (main.rs:78-80).  When the sample count is a power of two the quotient IS the
-                            // product with its exact reciprocal (one rounding of the same real value either way, subnormal results
-                            // included), and a multiply is a tenth of an IEEE division's instructions: wave-uniform choice.
-                            float cr_, cg_, cb_;
-                            if (p.spp_rcp != 0.0f) {
-                                cr_ = __builtin_sqrtf(sum_r * p.spp_rcp);
-                                cg_ = __builtin_sqrtf(sum_g * p.spp_rcp);
-                                cb_ = __builtin_sqrtf(sum_b * p.spp_rcp);
-                            } else {
-                                cr_ = __builtin_sqrtf(sum_r / p.spp_f);
-                                cg_ = __builtin_sqrtf(sum_g / p.spp_f);
-                                cb_ = __builtin_sqrtf(sum_b / p.spp_f);
-                            }
-                            const uint32_t sidx = hmeta & 0xffu;
-                            stg = (hmeta >> 16) & 0xffu;
-                            const size_t oidx = ((size_t)hrow * p.W + hx + g) * 3;          // row within the strip
-                            if (p.acc_out) {                                                    // (progressive pass: the sum over 0 .. s_begin + upp - 1)
-                                float* a = p.strips[sidx].acc;
-                                a[oidx + 0] = sum_r;
-                                a[oidx + 1] = sum_g;
-                                a[oidx + 2] = sum_b;
-                            }
-                            if (!CAN_STAGE || stg == STAGE_TILES) {
-                                uint8_t* orgb = p.strips[sidx].rgb;
-                                orgb[oidx + 0] = f32_as_u8(cr_ * 255.999f);
-                                orgb[oidx + 1] = f32_as_u8(cg_ * 255.999f);
-                                orgb[oidx + 2] = f32_as_u8(cb_ * 255.999f);
-                            } else {
-                                uint8_t* sd = stage_base + stg * STAGE_TILE_BYTES + ((hx + g) & 63u) * 3u;
-                                sd[0] = f32_as_u8(cr_ * 255.999f);
-                                sd[1] = f32_as_u8(cg_ * 255.999f);
-                                sd[2] = f32_as_u8(cb_ * 255.999f);
-                                fin = true;
-                            }
-                            float* of = p.strips[sidx].f32;
-                            if (of) {
-                                of[oidx + 0] = cr_;
-                                of[oidx + 1] = cg_;
-                                of[oidx + 2] = cb_;
-                            }
-                            (void)pin;
-                        }
-                    }
-                    if (p.strip_cost && mine && g == 0u) {
-                        // the slot's ray segments -> per-strip cost: into the wave's running sum for its strip (LDS: the strip the wave
-                        // issues from, or the one before), else — a straggler from further back — straight to the launch's array
-                        const uint32_t sg = wq.cnt[slot & (SLOTS_MAX - 1u)] >> SLOT_UNIT_BITS;
-                        if (cstrip == wq.cost_strip[0]) (void)__hip_atomic_fetch_add(&wq.cost_acc[0], sg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                        else if (cstrip == wq.cost_strip[1]) (void)__hip_atomic_fetch_add(&wq.cost_acc[1], sg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                        else if (sg) atomicAdd(&p.strip_cost[(blockIdx.x % COST_COPIES) * MAX_BATCH + cstrip], (unsigned long long)sg);
-                    }
-                    if (CAN_STAGE && __ballot(fin)) {
-                        // staged tiles that are complete now: LDS -> three whole lines of the strip
-                        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // the byte stores of this wave's other lanes
-#pragma unroll
-                        for (uint32_t k = 0; k < STAGE_TILES; k++) {
-                            const unsigned long long mk = __ballot(fin && stg == k);
-                            if (mk == 0ull) continue;
-                            const int left = (int)uni((uint32_t)wst.left[k]) - (int)__builtin_popcountll(mk);
-                            if (left == 0) {
-                                if (lane < (int)(STAGE_TILE_BYTES / 4)) {
-                                    uint32_t* d32 = reinterpret_cast<uint32_t*>(((uintptr_t)uni(wst.dst_hi[k]) << 32) | uni(wst.dst_lo[k]));
-                                    d32[lane] = reinterpret_cast<const uint32_t*>(stage_base + k * STAGE_TILE_BYTES)[lane];
+                                for (; i < p.upp; i++) {
+                                    LCOUNT(12);
+                                    const float cr = ring_load(r + 0);
+                                    const float cg = ring_load(r + 1);
+                                    const float cb = ring_load(r + 2);
+                                    sum_r = sum_r + cr;
+                                    sum_g = sum_g + cg;
+                                    sum_b = sum_b + cb;
+                                    r += 3;
                                 }
                             }
-                            if (lane == 0) wst.left[k] = left == 0 ? -1 : left;
+                            if (g < ((hmeta >> 8) & 0xffu)) {                    // (the last slot of a ragged tile holds fewer pixels)
+                                // ---- mean, gamma, quantise, store (main.rs:78-81)
+                                // pix_color / sample_count (main.rs:78-80).  When the sample count is a power of two the quotient IS the
+                                // product with its exact reciprocal (one rounding of the same real value either way, subnormal results
+                                // included), and a multiply is a tenth of an IEEE division's instructions: wave-uniform choice.
+                                float cr_, cg_, cb_;
+                                if (PLAIN || p.spp_rcp != 0.0f) {
+                                    cr_ = __builtin_sqrtf(sum_r * p.spp_rcp);
+                                    cg_ = __builtin_sqrtf(sum_g * p.spp_rcp);
+                                    cb_ = __builtin_sqrtf(sum_b * p.spp_rcp);
+                                } else {
+                                    cr_ = __builtin_sqrtf(sum_r / p.spp_f);
+                                    cg_ = __builtin_sqrtf(sum_g / p.spp_f);
+                                    cb_ = __builtin_sqrtf(sum_b / p.spp_f);
+                                }
+                                const uint32_t sidx = hmeta & 0xffu;
+                                stg = (hmeta >> 16) & 0xffu;
+                                const size_t oidx = ((size_t)hrow * p.W + hx + g) * 3;          // row within the strip
+                                if (!PLAIN && p.acc_out) {                                          // (progressive pass: the sum over 0 .. s_begin + upp - 1)
+                                    float* a = p.strips[sidx].acc;
+                                    a[oidx + 0] = sum_r;
+                                    a[oidx + 1] = sum_g;
+                                    a[oidx + 2] = sum_b;
+                                }
+                                if (!CAN_STAGE || stg == STAGE_TILES) {
+                                    uint8_t* orgb = p.strips[sidx].rgb;
+                                    orgb[oidx + 0] = f32_as_u8(cr_ * 255.999f);
+                                    orgb[oidx + 1] = f32_as_u8(cg_ * 255.999f);
+                                    orgb[oidx + 2] = f32_as_u8(cb_ * 255.999f);
+                                } else {
+                                    uint8_t* sd = stage_base + stg * STAGE_TILE_BYTES + ((hx + g) & 63u) * 3u;
+                                    sd[0] = f32_as_u8(cr_ * 255.999f);
+                                    sd[1] = f32_as_u8(cg_ * 255.999f);
+                                    sd[2] = f32_as_u8(cb_ * 255.999f);
+                                    fin = true;
+                                }
+                                float* of = PLAIN ? nullptr : p.strips[sidx].f32;
+                                if (of) {
+                                    of[oidx + 0] = cr_;
+                                    of[oidx + 1] = cg_;
+                                    of[oidx + 2] = cb_;
+                                }
+                                (void)pin;
+                            }
                         }
-                        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // reads done before a slot is written again
+                        if (!PLAIN && p.strip_cost && mine && g == 0u) {
+                            // the slot's ray segments -> per-strip cost: into the wave's running sum for its strip (LDS: the strip the wave
+                            // issues from, or the one before), else — a straggler from further back — straight to the launch's array
+                            const uint32_t sg = wq.cnt[slot & (SLOTS_MAX - 1u)] >> SLOT_UNIT_BITS;
+                            if (cstrip == wq.cost_strip[0]) (void)__hip_atomic_fetch_add(&wq.cost_acc[0], sg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                            else if (cstrip == wq.cost_strip[1]) (void)__hip_atomic_fetch_add(&wq.cost_acc[1], sg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                            else if (sg) atomicAdd(&p.strip_cost[(blockIdx.x % COST_COPIES) * MAX_BATCH + cstrip], (unsigned long long)sg);
+                        }
+                        if (CAN_STAGE && __ballot(fin)) {
+                            // staged tiles that are complete now: LDS -> three whole lines of the strip
+                            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // the byte stores of this wave's other lanes
+#pragma unroll
+                            for (uint32_t k = 0; k < STAGE_TILES; k++) {
+                                const unsigned long long mk = __ballot(fin && stg == k);
+                                if (mk == 0ull) continue;
+                                const int left = (int)uni((uint32_t)wst.left[k]) - (int)__builtin_popcountll(mk);
+                                if (left == 0) {
+                                    if (lane < (int)(STAGE_TILE_BYTES / 4)) {
+                                        uint32_t* d32 = reinterpret_cast<uint32_t*>(((uintptr_t)uni(wst.dst_hi[k]) << 32) | uni(wst.dst_lo[k]));
+                                        d32[lane] = reinterpret_cast<const uint32_t*>(stage_base + k * STAGE_TILE_BYTES)[lane];
+                                    }
+                                }
+                                if (lane == 0) wst.left[k] = left == 0 ? -1 : left;
+                            }
+                            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // reads done before a slot is written again
+                        }
                     }
-                }
+                };
+                if (PLAIN_OK && p.plain != 0u) commit_complete(std::true_type{});
+                else commit_complete(std::false_type{});
                 // the committed slots are free again
                 if (slot_done) wq.cnt[cold<QNODES>(lane)] = SLOT_FREE;
                 freem = uni(freem | complete);
@@ -1297,7 +1316,7 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                     const uint32_t prim = p.big[j];
                     float t;
                     bool hit;
-                    if (prim < p.n_sph) {
+                    if (!TRIS || prim < p.n_sph) {
                         const float4 g = RT_SPHERE_REC(p, prim);
                         hit = exact_sphere(o, 2.0f * d, mk(g.x, g.y, g.z), g.w, p.t_min, p.t_max, t);
                     } else {
@@ -1332,7 +1351,7 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                     // Sphere::aabb = c -+ r).  The filter is a pure predicate of (ray, primitive), so it is applied
                     // lazily: only to a hit that would replace the running closest one.  (A lane without a finite
                     // inverse direction walked the exact nodes: nothing to validate.)
-                    if (prim < p.n_sph) {
+                    if (!TRIS || prim < p.n_sph) {
                         const float4 g = RT_SPHERE_REC(p, prim);
                         if (exact_sphere(o, 2.0f * d, mk(g.x, g.y, g.z), g.w, p.t_min, p.t_max, t)) {   // (2f32 * ray.direction), sphere.rs:44
                             if (QNODES)
@@ -2009,7 +2028,7 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                 m = at32(p.mat, (uint32_t)h.idx);
                 if (!(em > 0.0f)) {
                     hp = o + h.t * d;                                                  // Ray::at (ray.rs:147-149), as in consider
-                    if ((uint32_t)h.idx < p.n_sph) {
+                    if (!TRIS || (uint32_t)h.idx < p.n_sph) {
                         float4 g = TRAVERSE ? RT_SPHERE_REC(p, (uint32_t)h.idx) : at32(p.geom, (uint32_t)h.idx);      // (asked for together with the material instead: no gain, measured in round 3)
                         nv = hp - mk(g.x, g.y, g.z);                                   // sphere.rs:49-51
                     } else {
@@ -2029,7 +2048,7 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                 } else {
                     const V3 n = nn;
                     // push the hit on the path stack: albedo product is applied back-to-front
-                    if (p.path32)
+                    if (path32())
                         reinterpret_cast<uint32_t*>(lpath)[k * BLOCK + cold<QNODES>(tid)] = (uint32_t)h.idx;
                     else
                         reinterpret_cast<uint16_t*>(lpath)[k * BLOCK + cold<QNODES>(tid16)] = (uint16_t)h.idx;
@@ -2075,7 +2094,7 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                 // pair costs one trip to L2, not two; the products are taken in the same order (c5 +0.4 %, round 3)
                 {
                     auto path_idx = [&](uint32_t i) -> uint32_t {
-                        return p.path32 ? reinterpret_cast<uint32_t*>(lpath)[i * BLOCK + cold<QNODES>(tid)]
+                        return path32() ? reinterpret_cast<uint32_t*>(lpath)[i * BLOCK + cold<QNODES>(tid)]
                                         : (uint32_t) reinterpret_cast<uint16_t*>(lpath)[i * BLOCK + cold<QNODES>(tid16)];
                     };
                     uint32_t i = k;
@@ -2128,7 +2147,8 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
 // (which engine runs which ISECT: the engine table of rt_plan.h).  nullptr for an ISECT the unit does not hold.
 using KernelFn = void (*)(const KParams);
 KernelFn kernel_linear(int isect, bool expanded);        // ISECT 0, 1; expanded: the expanded-form broad phase
-KernelFn kernel_traverse(int isect, bool stats);         // ISECT 2 ... 9; stats: the twin that also counts node visits (RT_FLAG_COUNT_STEPS)
+KernelFn kernel_traverse(int isect, bool stats, bool tris = true);   // ISECT 2 ... 9; stats: the twin that also counts node visits (RT_FLAG_COUNT_STEPS);
+                                                         //   tris = false: the sphere-only instantiation of ISECT 5 and 6 (every other ISECT has none: its general one)
 void sqrt_selftest_launch(uint32_t from, unsigned long long n, unsigned long long* d_bad, hipStream_t st);   // rt_kernels_trav.hip
 
 }  // namespace rtk

@@ -8,10 +8,10 @@
 
 namespace rtk {
 template <bool STATS>
-KernelFn traverse_kernel(int isect) {           // (the order of the cases is the kernels' order in the code object)
+KernelFn traverse_kernel(int isect, bool tris) {           // (the order of the cases is the kernels' order in the code object)
     switch (isect) {
-        case 5: return rt_tile_kernel<5, false, LTREE_BLOCK, STATS>;
-        case 6: return rt_tile_kernel<6, false, LTREE_BLOCK, STATS>;
+        case 5: return tris ? rt_tile_kernel<5, false, LTREE_BLOCK, STATS, true> : rt_tile_kernel<5, false, LTREE_BLOCK, STATS, false>;
+        case 6: return tris ? rt_tile_kernel<6, false, LTREE_BLOCK, STATS, true> : rt_tile_kernel<6, false, LTREE_BLOCK, STATS, false>;
         case 7: return rt_tile_kernel<7, false, BLOCK, STATS>;
         case 8: return rt_tile_kernel<8, false, BLOCK, STATS>;
         case 9: return rt_tile_kernel<9, false, BLOCK, STATS>;
@@ -21,7 +21,7 @@ KernelFn traverse_kernel(int isect) {           // (the order of the cases is th
         default: return nullptr;
     }
 }
-KernelFn kernel_traverse(int isect, bool stats) { return stats ? traverse_kernel<true>(isect) : traverse_kernel<false>(isect); }
+KernelFn kernel_traverse(int isect, bool stats, bool tris) { return stats ? traverse_kernel<true>(isect, tris) : traverse_kernel<false>(isect, tris); }
 
 // Self-test of sqrt_rn as the traversal kernels use it (tests/test_gpu_parity.py, rt_debug_sqrt_selftest): every f32 bit pattern in
 // [from, from + n) through sqrt_rn and through the compiler's IEEE sequence; counts the patterns whose results differ in any bit

@@ -62,6 +62,8 @@ struct Knobs {
     int compact = 1;          // 0: per-lane root tests in the exact-node L2 kernel
     int refill_eighths = 0;   // refill threshold of the walks; 0: host rule
     int tail_tiles = -1;      // tiles at the end of the queue handed out in parts; -1: host rule
+    int ltree_general = 0;    // 1: the LDS-tree engines take their general kernel (spheres and triangles) whatever the world holds
+    int plain_frame = 1;      // 0: no launch counts as a plain frame (the LDS-tree kernels commit through their general path)
 };
 
 // The engines (rt_tile_stats.engine) and the kernels that run them: template argument ISECT of rtk::rt_tile_kernel, that of the
@@ -96,6 +98,9 @@ struct Plan {
     int block = rtk::BLOCK;      //   its workgroup size
     bool expanded = false;       //   linear engines: the expanded-form broad phase (rt_tile_stats.broad_form)
     bool count_steps = false;    //   traversal engines: the twin that counts node visits
+    bool tris = true;            //   LDS-tree engines (4, 7): false picks the sphere-only instantiation — the world has no triangle
+                                 //   (LT_SPHERE_ONLY_MAX_TRIS) and Knobs::ltree_general is 0; every other engine has one kernel: true
+    bool plain_shape = false;    // the plan's part of a plain frame (plain_frame below)
     size_t lds = 0;              // dynamic LDS bytes
     uint32_t maxl_l2 = 0;        // leaf slots of an L2 walk (the RT_VERBOSE line's; the LDS tree's own are p.maxl)
     uint32_t ovf_entries = 0;    // capped stack: entries per thread in the HBM overflow area
@@ -104,6 +109,18 @@ struct Plan {
     size_t ring_bytes = 0;       // sample-unit ring: [waves][n_slots][slot_stride] 12-byte records
     size_t ovf_words = 0;        // stack overflow area
 };
+
+constexpr uint32_t LT_MAX_PRIMS = 0x7fffu;        // the LDS-tree engines' 16-bit references hold 15 bits of primitive number
+constexpr uint32_t PATH16_MAX_PRIMS = 65536u;     // up to here a path stack entry is 16 bits (KParams::path32 == 0)
+constexpr uint32_t LT_SPHERE_ONLY_MAX_TRIS = 0;   // the LDS-tree engines take their sphere-only kernel up to this many triangles: none —
+                                                  // it rests on the world's contents, not on a measurement: that kernel has no triangle code
+
+// A plain frame: every launch-uniform choice of the commit falls the flagship's way — all samples in one pass and no running sum
+// in or out, one pixel per slot (8 samples per pixel and more), a power-of-two sample count (the mean is a product), 16-bit path
+// entries — and no strip asks for an f32 plane or a per-strip cost.  The LDS-tree kernels then commit through a copy of the commit
+// that carries none of those tests (rtk::KParams::plain); any other launch, and every other engine, takes the general path.
+// any_f32 / strip_cost: what the launch's strips and its caller ask for (rt_api.hip launch_batch).
+inline bool plain_frame(const Plan& pl, bool any_f32, bool strip_cost) { return pl.plain_shape && !any_f32 && !strip_cost; }
 
 // An explicit request flag wins over the process-level knob (RT_CULL_WALK), the knob over the host rule.
 inline bool cull_wanted(uint32_t flags, int knob, bool rule) {
@@ -278,7 +295,8 @@ Plan plan_launch(const SceneShape& sh, const rt_tile_request& rq, uint32_t n_str
     // L2-gather kernel (A/B runs, tests).
     bool ltree_fits = false;
     const size_t lt_lane = ((size_t)MAXL_LTREE + (size_t)(rq.max_bounces + 1) + (size_t)(sh.bvh_depth + 2)) * sizeof(uint16_t);
-    if (traverse && kn.lds_tree != 0 && !(fl & RT_FLAG_NO_LDS_TREE) && sh.n_internal > 0 && n_prims <= 0x7fffu &&
+    static_assert(LT_MAX_PRIMS <= PATH16_MAX_PRIMS, "the LDS-tree kernels compile the 32-bit path entries out (rt_kernel.hip.h path32())");
+    if (traverse && kn.lds_tree != 0 && !(fl & RT_FLAG_NO_LDS_TREE) && sh.n_internal > 0 && n_prims <= LT_MAX_PRIMS &&
         ((size_t)sh.n_internal + 2) * LNODE_DW < 0x8000u) {
         const size_t fixed = (((size_t)sh.n_internal + 2) * LNODE_DW + n_prims) * 4 + 16 + lt_lane * LTREE_BLOCK;   // + node DONE and the NaN field
         ltree_fits = fixed <= LDS_LIMIT;
@@ -317,7 +335,7 @@ Plan plan_launch(const SceneShape& sh, const rt_tile_request& rq, uint32_t n_str
     const int bs = ENGINES[pl.engine].block;
     p.chunk = traverse ? 0 : (streamed ? STREAM_CHUNK : sh.n_sph_pad);
     p.n_chunks = p.chunk ? (sh.n_sph_pad + p.chunk - 1) / p.chunk : 0;
-    p.path32 = (sh.n_sph + sh.n_tri) > 65536u ? 1u : 0u;
+    p.path32 = (sh.n_sph + sh.n_tri) > PATH16_MAX_PRIMS ? 1u : 0u;
     size_t geom_bytes = traverse ? 0 : (size_t)(p.chunk ? p.chunk : 1) * 4 * sizeof(float);   // float4 records
     p.lds_cand_off = (uint32_t)geom_bytes;
     size_t path_bytes = (size_t)p.depth * BLOCK * (p.path32 ? 4 : 2);
@@ -402,6 +420,7 @@ Plan plan_launch(const SceneShape& sh, const rt_tile_request& rq, uint32_t n_str
     pl.block = bs;
     pl.expanded = expanded;
     pl.count_steps = traverse && (fl & RT_FLAG_COUNT_STEPS);
+    pl.tris = !(ltree && sh.n_tri <= LT_SPHERE_ONLY_MAX_TRIS && kn.ltree_general == 0);
     pl.maxl_l2 = maxl;
     pl.ovf_entries = pl.capped ? stack_capped - stack_lds : 0u;
     fill_camera(rq, pose, p);
@@ -453,6 +472,7 @@ Plan plan_launch(const SceneShape& sh, const rt_tile_request& rq, uint32_t n_str
     p.tiles_total = (uint32_t)n_tiles;
     p.n_tiles = (uint32_t)n_tiles;             // (queue entries: the split into whole tiles and parts follows the grid, plan_queue)
     p.tiles_big = (uint32_t)n_tiles;
+    pl.plain_shape = ltree && kn.plain_frame != 0 && p.s_begin == 0u && p.acc_out == 0u && p.grp == 1u && p.spp_rcp != 0.0f && p.path32 == 0u;
     return pl;
 }
 
