@@ -118,6 +118,9 @@ UPSAMPLE = _private("upsample", ("rt_denoise_math.h", "rt_consts.h"))
 # The ROBUST library: the median-of-means estimate of film_robust.py; rtr_* exports, _robust_lib.py.  It includes no
 # csrc/ header.
 ROBUST = _private("robust", ())
+# The DISPLAY library: the metered exposure and the tone curves of film_display.py; rtd_* exports, _display_lib.py.
+# It includes no csrc/ header.
+DISPLAY = _private("display", ())
 
 # LIBRARIES is the set the recipe's golden test (tests/test_build_recipe.py) knows, and stays those four; PRIVATE_LIBRARIES is the set
 # tests/test_sampler_plan.py knows, and stays those three.  A library added since is a Library value like them and a member of
@@ -128,6 +131,10 @@ FILM_LIBRARIES = (*PRIVATE_LIBRARIES, UPSAMPLE)
 # FILM_LIBRARIES is in turn the set tests/test_upsample_plan.py knows, and stays those four.  ALL_FILM_LIBRARIES is every private
 # library: build() makes FILM_LIBRARIES through ensure and the rest through build_robust's own step.
 ALL_FILM_LIBRARIES = (*FILM_LIBRARIES, ROBUST)
+# ALL_FILM_LIBRARIES is the set tests/test_robust_plan.py knows, and stays those five, as build() stays the steps that test records.
+# EVERY_FILM_LIBRARY is every private library, and the set to add to: what build() does not make (DISPLAY) is built by the driver's
+# build() through build_display, and by its binding's load() where the file is missing.
+EVERY_FILM_LIBRARY = (*ALL_FILM_LIBRARIES, DISPLAY)
 
 
 def _product(extra: list[str] | None = None) -> Library:
@@ -247,8 +254,14 @@ def build_robust(force: bool = False, verbose: bool = False) -> Path:
     return compile_and_link(ROBUST, verbose) if force or stale(ROBUST) else ROBUST.path
 
 
+def build_display(force: bool = False, verbose: bool = False) -> Path:
+    """The display library if it is missing or stale, or if forced.  No step of build(): the tests of the libraries before it pin
+    what build() asks for."""
+    return ensure(DISPLAY, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
     if not VARIANT:
-        for lib in (DEBUG, *ALL_FILM_LIBRARIES):
+        for lib in (DEBUG, *EVERY_FILM_LIBRARY):
             print(ensure(lib, force=True, verbose=True))
