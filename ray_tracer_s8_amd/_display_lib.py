@@ -21,10 +21,6 @@ RECORD_FIELDS = ("scale", "white", "target", "bin_key", "bin_white", "counted", 
 STATUS = {1: "RTD_ERR_BAD_ARG", 2: "RTD_ERR_LIMIT", 3: "RTD_ERR_HIP", 4: "RTD_ERR_INTERNAL"}
 
 
-class RtdError(_private_lib.StatusError):
-    STATUS = STATUS
-
-
 class MeterArgs(C.Structure):
     _fields_ = [("W", C.c_uint32), ("R", C.c_uint32), ("form", C.c_uint32), ("reserved", C.c_uint32),
                 ("linear", C.c_void_p), ("hist", C.c_void_p)]
@@ -51,17 +47,5 @@ SIGNATURES = {
     "rtd_apply": [C.POINTER(ApplyArgs), C.c_void_p],
 }
 
-_lib = None
-
-
-def check(what: str, status: int) -> None:
-    if status != RTD_OK:
-        raise RtdError(what, status)
-
-
-def load(build_if_missing: bool = True) -> C.CDLL:
-    """Load librt_display.so (building it with hipcc if it is missing).  Raises if it cannot: there is no fall-back."""
-    global _lib
-    if _lib is None:
-        _lib = _private_lib.load(_build.DISPLAY, SIGNATURES, RTD_VERSION, RtdError, "build.build_display", build_if_missing)
-    return _lib
+BINDING = _private_lib.Binding(_build.PRIVATE["display"], "rtd", RTD_VERSION, STATUS, SIGNATURES)
+load, check, RtdError = BINDING.load, BINDING.check, BINDING.Error

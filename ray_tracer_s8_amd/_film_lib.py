@@ -17,10 +17,6 @@ MAX_ITERATIONS = 8
 LDS_PLAN = 0xFFFFFFFF                 # lds_max_step: the plan's own choice
 
 
-class RtfError(_private_lib.StatusError):
-    STATUS = STATUS
-
-
 class ResolveArgs(C.Structure):
     _fields_ = [("W", C.c_uint32), ("R", C.c_uint32), ("samples", C.c_uint32), ("iterations", C.c_uint32),
                 ("lds_max_step", C.c_uint32), ("reserved", C.c_uint32),
@@ -38,20 +34,8 @@ SIGNATURES = {
     "rtf_resolve": [C.POINTER(ResolveArgs), C.c_void_p],
 }
 
-_lib = None
-
-
-def check(what: str, status: int) -> None:
-    if status != RTF_OK:
-        raise RtfError(what, status)
-
-
-def load(build_if_missing: bool = True) -> C.CDLL:
-    """Load librt_film.so (building it with hipcc if it is missing).  Raises if it cannot: there is no fall-back."""
-    global _lib
-    if _lib is None:
-        _lib = _private_lib.load(_build.FILM, SIGNATURES, RTF_VERSION, RtfError, "build.build_film", build_if_missing)
-    return _lib
+BINDING = _private_lib.Binding(_build.PRIVATE["film"], "rtf", RTF_VERSION, STATUS, SIGNATURES)
+load, check, RtfError = BINDING.load, BINDING.check, BINDING.Error
 
 
 def resolve_scratch_bytes(width: int, rows: int) -> int:

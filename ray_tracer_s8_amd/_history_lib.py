@@ -18,10 +18,6 @@ CLIP_FORM_STAGED, CLIP_FORM_DIRECT = 1, 2            # clip_form, for tests and 
 STATUS = {1: "RTH_ERR_BAD_ARG", 2: "RTH_ERR_LIMIT", 3: "RTH_ERR_HIP", 4: "RTH_ERR_INTERNAL"}
 
 
-class RthError(_private_lib.StatusError):
-    STATUS = STATUS
-
-
 class State(C.Structure):
     _fields_ = [("accum", C.c_void_p), ("moments", C.c_void_p), ("length", C.c_void_p), ("depth", C.c_void_p), ("index", C.c_void_p),
                 ("normal", C.c_void_p)]
@@ -46,17 +42,5 @@ SIGNATURES = {
     "rth_accumulate": [C.POINTER(AccumulateArgs), C.c_void_p],
 }
 
-_lib = None
-
-
-def check(what: str, status: int) -> None:
-    if status != RTH_OK:
-        raise RthError(what, status)
-
-
-def load(build_if_missing: bool = True) -> C.CDLL:
-    """Load librt_history.so (building it with hipcc if it is missing).  Raises if it cannot: there is no fall-back."""
-    global _lib
-    if _lib is None:
-        _lib = _private_lib.load(_build.HISTORY, SIGNATURES, RTH_VERSION, RthError, "build.build_history", build_if_missing)
-    return _lib
+BINDING = _private_lib.Binding(_build.PRIVATE["history"], "rth", RTH_VERSION, STATUS, SIGNATURES)
+load, check, RthError = BINDING.load, BINDING.check, BINDING.Error

@@ -18,10 +18,6 @@ MODES = {"gini": 0, "trim": 1}                    # RTR_GINI, RTR_TRIM
 STATUS = {1: "RTR_ERR_BAD_ARG", 2: "RTR_ERR_LIMIT", 3: "RTR_ERR_HIP", 4: "RTR_ERR_INTERNAL"}
 
 
-class RtrError(_private_lib.StatusError):
-    STATUS = STATUS
-
-
 class FoldArgs(C.Structure):
     _fields_ = [("pixels", C.c_uint32), ("n", C.c_uint32), ("first", C.c_uint32), ("K", C.c_uint32), ("bucket_stride", C.c_uint64),
                 ("records", C.c_void_p), ("buckets", C.c_void_p)]
@@ -43,17 +39,5 @@ SIGNATURES = {
     "rtr_resolve": [C.POINTER(ResolveArgs), C.c_void_p],
 }
 
-_lib = None
-
-
-def check(what: str, status: int) -> None:
-    if status != RTR_OK:
-        raise RtrError(what, status)
-
-
-def load(build_if_missing: bool = True) -> C.CDLL:
-    """Load librt_robust.so (building it with hipcc if it is missing).  Raises if it cannot: there is no fall-back."""
-    global _lib
-    if _lib is None:
-        _lib = _private_lib.load(_build.ROBUST, SIGNATURES, RTR_VERSION, RtrError, "build.build_robust", build_if_missing)
-    return _lib
+BINDING = _private_lib.Binding(_build.PRIVATE["robust"], "rtr", RTR_VERSION, STATUS, SIGNATURES)
+load, check, RtrError = BINDING.load, BINDING.check, BINDING.Error

@@ -16,10 +16,6 @@ RTS_OK = 0
 STATUS = {1: "RTS_ERR_BAD_ARG", 2: "RTS_ERR_LIMIT", 3: "RTS_ERR_HIP", 4: "RTS_ERR_INTERNAL", 5: "RTS_ERR_SCRATCH"}
 
 
-class RtsError(_private_lib.StatusError):
-    STATUS = STATUS
-
-
 class SelectArgs(C.Structure):
     _fields_ = [("W", C.c_uint32), ("R", C.c_uint32), ("Hs", C.c_uint32), ("dilate", C.c_uint32), ("reserved", C.c_uint32),
                 ("threshold", C.c_float), ("eps", C.c_float), ("reserved2", C.c_uint32),
@@ -56,20 +52,8 @@ SIGNATURES = {
     "rts_normalise": [C.POINTER(NormaliseArgs), C.c_void_p],
 }
 
-_lib = None
-
-
-def check(what: str, status: int) -> None:
-    if status != RTS_OK:
-        raise RtsError(what, status)
-
-
-def load(build_if_missing: bool = True) -> C.CDLL:
-    """Load librt_sampler.so (building it with hipcc if it is missing).  Raises if it cannot: there is no fall-back."""
-    global _lib
-    if _lib is None:
-        _lib = _private_lib.load(_build.SAMPLER, SIGNATURES, RTS_VERSION, RtsError, "build.build_sampler", build_if_missing)
-    return _lib
+BINDING = _private_lib.Binding(_build.PRIVATE["sampler"], "rts", RTS_VERSION, STATUS, SIGNATURES)
+load, check, RtsError = BINDING.load, BINDING.check, BINDING.Error
 
 
 def scratch_bytes(W: int, R: int, Hs: int) -> int:

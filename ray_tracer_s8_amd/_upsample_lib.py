@@ -18,10 +18,6 @@ STATUS = {1: "RTU_ERR_BAD_ARG", 2: "RTU_ERR_LIMIT", 3: "RTU_ERR_HIP", 4: "RTU_ER
 PLANES = ("albedo", "normal", "depth", "hits", "index")           # the fields of rtu_planes, in its order
 
 
-class RtuError(_private_lib.StatusError):
-    STATUS = STATUS
-
-
 class Planes(C.Structure):
     _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("hits", C.c_void_p), ("index", C.c_void_p),
                 ("samples", C.c_uint32), ("reserved", C.c_uint32)]
@@ -44,17 +40,5 @@ SIGNATURES = {
     "rtu_upsample": [C.POINTER(UpsampleArgs), C.c_void_p],
 }
 
-_lib = None
-
-
-def check(what: str, status: int) -> None:
-    if status != RTU_OK:
-        raise RtuError(what, status)
-
-
-def load(build_if_missing: bool = True) -> C.CDLL:
-    """Load librt_upsample.so (building it with hipcc if it is missing).  Raises if it cannot: there is no fall-back."""
-    global _lib
-    if _lib is None:
-        _lib = _private_lib.load(_build.UPSAMPLE, SIGNATURES, RTU_VERSION, RtuError, "build.build_upsample", build_if_missing)
-    return _lib
+BINDING = _private_lib.Binding(_build.PRIVATE["upsample"], "rtu", RTU_VERSION, STATUS, SIGNATURES)
+load, check, RtuError = BINDING.load, BINDING.check, BINDING.Error

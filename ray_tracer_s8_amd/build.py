@@ -92,49 +92,34 @@ DEBUG_FLAGS = ["-DRT_DEBUG_HOOKS"]
 DEBUG = replace(PRODUCT, path=DEBUG_LIB_PATH, obj_dir=LIB_DIR / "obj_dbg", extra=tuple(DEBUG_FLAGS))
 
 
+# What the host files of the private libraries share (rt_private_host.h): beside csrc/, so a library that includes no csrc/ header
+# depends on nothing under csrc/.
+PRIVATE_CSRC = PKG / "private_csrc"
+
+
 def _private(name: str, headers: tuple) -> Library:
     """A private library: lib/librt_<name>.so from the one unit <name>_csrc/rt_<name>.hip, loaded by a binding module of its own
-    (_private_lib.py) and no part of the tile ABI.  Its sources lie beside csrc/, not under it, so they are no dependency of any
-    other library; its own dependencies are its directory, the csrc/ headers it includes (named here), the C header and this
-    recipe.  The product's flags plus -fno-slp-vectorize, and never RT_EXTRA_HIPCC_FLAGS: experiments are the product library's."""
+    (_private_lib.Binding) and no part of the tile ABI.  Its sources lie beside csrc/, not under it, so they are no dependency of
+    any other library; its own dependencies are its directory, private_csrc/, the csrc/ headers it includes (named here), the C
+    header and this recipe.  The product's flags plus -fno-slp-vectorize, and never RT_EXTRA_HIPCC_FLAGS: experiments are the
+    product library's."""
     src = PKG / f"{name}_csrc"
     return Library(LIB_DIR / f"librt_{name}.so", LIB_DIR / f"obj_{name}", src, ((f"rt_{name}.hip", ()),), extra=("-fno-slp-vectorize",),
-                   include_dirs=(INCLUDE, CSRC, src),
-                   deps=(src, *(CSRC / h for h in headers), INCLUDE / "rt_tile.h", Path(__file__)))
+                   include_dirs=(INCLUDE, CSRC, src, PRIVATE_CSRC),
+                   deps=(src, PRIVATE_CSRC, *(CSRC / h for h in headers), INCLUDE / "rt_tile.h", Path(__file__)))
 
 
-# The FILM library: the moments fold and the variance-guided resolve of film.py (DESIGN.md 4.23); rtf_* exports, _film_lib.py.
-FILM = _private("film", ("rt_denoise_math.h", "rt_consts.h", "rt_plan.h"))
-# The HISTORY library: the temporal accumulation of film_history.py (DESIGN.md 4.24); rth_* exports, _history_lib.py.
-HISTORY = _private("history", ("rt_consts.h", "rt_plan.h"))
-# (the names the export tests know the private libraries and their headers by)
-FILM_LIB_PATH, FILM_CSRC = FILM.path, FILM.src_dir
-HISTORY_LIB_PATH, HISTORY_CSRC = HISTORY.path, HISTORY.src_dir
-# The SAMPLER library: the adaptive sampling of film_sampler.py (DESIGN.md 4.25); rts_* exports, _sampler_lib.py.  It includes no csrc/
-# header.
-SAMPLER = _private("sampler", ())
-# The UPSAMPLE library: the joint-bilateral upsampling of film_upsampler.py (DESIGN.md 4.27); rtu_* exports, _upsample_lib.py.
-UPSAMPLE = _private("upsample", ("rt_denoise_math.h", "rt_consts.h"))
-# The ROBUST library: the median-of-means estimate of film_robust.py (DESIGN.md 4.29); rtr_* exports, _robust_lib.py.  It includes no
-# csrc/ header.
-ROBUST = _private("robust", ())
-# The DISPLAY library: the metered exposure and the tone curves of film_display.py (DESIGN.md 4.30); rtd_* exports, _display_lib.py.
-# It includes no csrc/ header.
-DISPLAY = _private("display", ())
-
-# LIBRARIES is the set the recipe's golden test (tests/test_build_recipe.py) knows, and stays those four; PRIVATE_LIBRARIES is the set
-# tests/test_sampler_plan.py knows, and stays those three.  A library added since is a Library value like them and a member of
-# FILM_LIBRARIES, the private libraries build() makes, which is the set to add to.
-LIBRARIES = (PRODUCT, DEBUG, FILM, HISTORY)
-PRIVATE_LIBRARIES = (FILM, HISTORY, SAMPLER)
-FILM_LIBRARIES = (*PRIVATE_LIBRARIES, UPSAMPLE)
-# FILM_LIBRARIES is in turn the set tests/test_upsample_plan.py knows, and stays those four.  ALL_FILM_LIBRARIES is every private
-# library: build() makes FILM_LIBRARIES through ensure and the rest through build_robust's own step.
-ALL_FILM_LIBRARIES = (*FILM_LIBRARIES, ROBUST)
-# ALL_FILM_LIBRARIES is the set tests/test_robust_plan.py knows, and stays those five, as build() stays the steps that test records.
-# EVERY_FILM_LIBRARY is every private library, and the set to add to: what build() does not make (DISPLAY) is built by the driver's
-# build() through build_display, and by its binding's load() where the file is missing.
-EVERY_FILM_LIBRARY = (*ALL_FILM_LIBRARIES, DISPLAY)
+# The PRIVATE libraries, in the order build() makes them: name -> Library, with the csrc/ headers each one includes.  A further
+# library is one entry here, its directory, its binding module and its golden record.
+PRIVATE = {
+    "film": _private("film", ("rt_denoise_math.h", "rt_consts.h", "rt_plan.h")),    # moments fold, guided resolve (DESIGN.md 4.23); rtf_*
+    "history": _private("history", ("rt_consts.h", "rt_plan.h")),                   # temporal accumulation (4.24); rth_*
+    "sampler": _private("sampler", ()),                                             # adaptive sampling (4.25); rts_*
+    "upsample": _private("upsample", ("rt_denoise_math.h", "rt_consts.h")),         # joint-bilateral upsampling (4.27); rtu_*
+    "robust": _private("robust", ()),                                               # median of means (4.29); rtr_*
+    "display": _private("display", ()),                                             # metered exposure, tone curves (4.30); rtd_*
+}
+FILM, HISTORY, SAMPLER, UPSAMPLE, ROBUST, DISPLAY = PRIVATE.values()
 
 
 def _product(extra: list[str] | None = None) -> Library:
@@ -218,50 +203,19 @@ def needs_build() -> bool:
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """Compile librt_s8.so (or the RT_LIB_VARIANT named) if missing or stale, and with no variant named the private libraries
-    (FILM_LIBRARIES) first and the robust library (build_robust) last."""
-    for lib in () if VARIANT else FILM_LIBRARIES:
+    """Compile librt_s8.so (or the RT_LIB_VARIANT named) if missing or stale, and with no variant named every private library
+    first."""
+    for lib in () if VARIANT else PRIVATE.values():
         ensure(lib, force, verbose)
-    path = ensure(_product(), force, verbose)
-    if not VARIANT:
-        build_robust(force, verbose)
-    return path
+    return ensure(_product(), force, verbose)
 
 
 def build_debug(force: bool = False, verbose: bool = False) -> Path:
     return ensure(DEBUG, force, verbose)
 
 
-def build_film(force: bool = False, verbose: bool = False) -> Path:
-    return ensure(FILM, force, verbose)
-
-
-def build_history(force: bool = False, verbose: bool = False) -> Path:
-    return ensure(HISTORY, force, verbose)
-
-
-def build_sampler(force: bool = False, verbose: bool = False) -> Path:
-    return ensure(SAMPLER, force, verbose)
-
-
-def build_upsample(force: bool = False, verbose: bool = False) -> Path:
-    return ensure(UPSAMPLE, force, verbose)
-
-
-def build_robust(force: bool = False, verbose: bool = False) -> Path:
-    """The robust library if it is missing or stale, or if forced: the recipe's steps themselves, not `ensure`, which build() calls
-    for exactly FILM_LIBRARIES and the product (tests/test_upsample_plan.py)."""
-    return compile_and_link(ROBUST, verbose) if force or stale(ROBUST) else ROBUST.path
-
-
-def build_display(force: bool = False, verbose: bool = False) -> Path:
-    """The display library if it is missing or stale, or if forced.  No step of build(): the tests of the libraries before it pin
-    what build() asks for."""
-    return ensure(DISPLAY, force, verbose)
-
-
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
     if not VARIANT:
-        for lib in (DEBUG, *EVERY_FILM_LIBRARY):
-            print(ensure(lib, force=True, verbose=True))
+        for lib in (DEBUG, *PRIVATE.values()):          # (the private ones were forced by build())
+            print(ensure(lib, force=lib is DEBUG, verbose=True))

@@ -4,8 +4,9 @@
 
 #include "rt_display.h"
 #include "rt_display.hip.h"
+#include "rt_private_host.h"
 
-#define RTD_EXPORT extern "C" __attribute__((visibility("default")))
+using namespace rtpriv;
 
 static_assert(RTD_HIST_WORDS == rtdm::HIST_WORDS && RTD_RECORD_WORDS == rtdm::RECORD_WORDS, "the header's sizes");
 static_assert(RTD_AUTO == rtdm::MODE_AUTO && RTD_MANUAL == rtdm::MODE_MANUAL, "the header's modes");
@@ -13,24 +14,6 @@ static_assert(RTD_NONE == rtdm::CURVE_NONE && RTD_REINHARD == rtdm::CURVE_REINHA
 static_assert(RTD_HIST_WAVE == rtdk::FORM_WAVE && RTD_HIST_MATCH == rtdk::FORM_MATCH, "the header's forms");
 
 namespace {
-
-template <class F>
-int guarded(const F& body) {
-    try {
-        return body();
-    } catch (...) {
-        return RTD_ERR_INTERNAL;
-    }
-}
-
-struct Range {
-    uintptr_t b, e;
-};
-
-// buffer q of n bytes (nothing for a NULL)
-Range range(const void* q, uint64_t n) { return q ? Range{(uintptr_t)q, (uintptr_t)q + (uintptr_t)n} : Range{0, 0}; }
-bool overlap(const Range& a, const Range& b) { return a.b < a.e && b.b < b.e && a.b < b.e && b.b < a.e; }
-bool misaligned(const void* q, uintptr_t to = 4) { return ((uintptr_t)q & (to - 1)) != 0; }
 
 using ApplyKernel = void (*)(const rtdk::ApplyParams);
 
@@ -49,16 +32,16 @@ constexpr uint64_t HIST_BYTES = 4 * RTD_HIST_WORDS, RECORD_BYTES = 4 * RTD_RECOR
 
 }  // namespace
 
-RTD_EXPORT int rtd_version(uint32_t* version) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rtd_version(uint32_t* version) {
+    return guarded<RTD_ERR_INTERNAL>([&] {
         if (!version) return RTD_ERR_BAD_ARG;
         *version = RTD_VERSION;
         return RTD_OK;
     });
 }
 
-RTD_EXPORT int rtd_meter(const rtd_meter_args* a, void* stream) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rtd_meter(const rtd_meter_args* a, void* stream) {
+    return guarded<RTD_ERR_INTERNAL>([&] {
         if (!a || a->W == 0 || a->R == 0 || a->reserved != 0) return RTD_ERR_BAD_ARG;
         if (a->form != RTD_HIST_WAVE && a->form != RTD_HIST_MATCH) return RTD_ERR_BAD_ARG;
         if (!a->linear || !a->hist || misaligned(a->linear) || misaligned(a->hist)) return RTD_ERR_BAD_ARG;
@@ -78,12 +61,12 @@ RTD_EXPORT int rtd_meter(const rtd_meter_args* a, void* stream) {
             hipLaunchKernelGGL(rtdk::rtd_meter_kernel<rtdk::FORM_WAVE>, grid, dim3(rtdk::METER_BLOCK), 0, (hipStream_t)stream, p);
         else
             hipLaunchKernelGGL(rtdk::rtd_meter_kernel<rtdk::FORM_MATCH>, grid, dim3(rtdk::METER_BLOCK), 0, (hipStream_t)stream, p);
-        return hipGetLastError() == hipSuccess ? RTD_OK : RTD_ERR_HIP;
+        return after_launch(RTD_OK, RTD_ERR_HIP);
     });
 }
 
-RTD_EXPORT int rtd_expose(const rtd_expose_args* a, void* stream) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rtd_expose(const rtd_expose_args* a, void* stream) {
+    return guarded<RTD_ERR_INTERNAL>([&] {
         if (!a || a->reserved != 0) return RTD_ERR_BAD_ARG;
         rtdk::ExposeParams p;
         std::memset(&p, 0, sizeof p);
@@ -99,12 +82,12 @@ RTD_EXPORT int rtd_expose(const rtd_expose_args* a, void* stream) {
         }
         p.record = a->record;
         hipLaunchKernelGGL(rtdk::rtd_expose_kernel, dim3(1), dim3(rtdk::BLOCK), 0, (hipStream_t)stream, p);
-        return hipGetLastError() == hipSuccess ? RTD_OK : RTD_ERR_HIP;
+        return after_launch(RTD_OK, RTD_ERR_HIP);
     });
 }
 
-RTD_EXPORT int rtd_apply(const rtd_apply_args* a, void* stream) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rtd_apply(const rtd_apply_args* a, void* stream) {
+    return guarded<RTD_ERR_INTERNAL>([&] {
         if (!a || a->W == 0 || a->R == 0 || a->dither > 1u) return RTD_ERR_BAD_ARG;
         const ApplyKernel k = apply_instance(a->curve, a->dither != 0u);
         if (!k) return RTD_ERR_BAD_ARG;
@@ -114,9 +97,7 @@ RTD_EXPORT int rtd_apply(const rtd_apply_args* a, void* stream) {
         if (n > MAX_PIXELS) return RTD_ERR_LIMIT;
         // no buffer overlaps another
         const Range all[] = {range(a->linear, n * 12), range(a->record, RECORD_BYTES), range(a->out_f32, n * 12), range(a->out_rgb, n * 3)};
-        for (int i = 0; i < 4; i++)
-            for (int j = i + 1; j < 4; j++)
-                if (overlap(all[i], all[j])) return RTD_ERR_BAD_ARG;
+        if (any_overlap(all)) return RTD_ERR_BAD_ARG;
 
         rtdk::ApplyParams p;
         std::memset(&p, 0, sizeof p);
@@ -129,6 +110,6 @@ RTD_EXPORT int rtd_apply(const rtd_apply_args* a, void* stream) {
         p.out_rgb = a->out_rgb;
         const dim3 grid((p.groups + rtdk::BLOCK - 1) / rtdk::BLOCK);
         hipLaunchKernelGGL(k, grid, dim3(rtdk::BLOCK), 0, (hipStream_t)stream, p);
-        return hipGetLastError() == hipSuccess ? RTD_OK : RTD_ERR_HIP;
+        return after_launch(RTD_OK, RTD_ERR_HIP);
     });
 }

@@ -5,22 +5,12 @@
 
 #include "rt_film.h"
 #include "rt_film.hip.h"
+#include "rt_private_host.h"
 #include "rt_plan.h"
 
-#define RTF_EXPORT extern "C" __attribute__((visibility("default")))
+using namespace rtpriv;
 
 namespace {
-
-int after_launch() { return hipGetLastError() == hipSuccess ? RTF_OK : RTF_ERR_HIP; }
-
-template <class F>
-int guarded(const F& body) {
-    try {
-        return body();
-    } catch (...) {
-        return RTF_ERR_INTERNAL;
-    }
-}
 
 bool finite_nonneg(float v) { return std::isfinite(v) && v >= 0.0f; }
 
@@ -45,26 +35,26 @@ int check_image(uint32_t W, uint32_t R) {
 
 }  // namespace
 
-RTF_EXPORT int rtf_version(uint32_t* version) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rtf_version(uint32_t* version) {
+    return guarded<RTF_ERR_INTERNAL>([&] {
         if (!version) return RTF_ERR_BAD_ARG;
         *version = RTF_VERSION;
         return RTF_OK;
     });
 }
 
-RTF_EXPORT int rtf_fold_moments(const float* records, uint64_t P, uint32_t n, float* accum, float* moments, void* stream) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rtf_fold_moments(const float* records, uint64_t P, uint32_t n, float* accum, float* moments, void* stream) {
+    return guarded<RTF_ERR_INTERNAL>([&] {
         if (!records || !accum || !moments || P == 0 || n == 0) return RTF_ERR_BAD_ARG;
         if (P > 0x7FFFFFFFull) return RTF_ERR_LIMIT;                              // a strip of the tile ABI's largest frame
         const uint32_t blocks = (uint32_t)((P + rtfk::BLOCK - 1) / rtfk::BLOCK);
         hipLaunchKernelGGL(rtfk::rtf_fold_kernel, dim3(blocks), dim3(rtfk::BLOCK), 0, (hipStream_t)stream, records, P, n, accum, moments);
-        return after_launch();
+        return after_launch(RTF_OK, RTF_ERR_HIP);
     });
 }
 
-RTF_EXPORT int rtf_resolve_scratch_bytes(uint32_t W, uint32_t R, uint64_t* bytes) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rtf_resolve_scratch_bytes(uint32_t W, uint32_t R, uint64_t* bytes) {
+    return guarded<RTF_ERR_INTERNAL>([&] {
         if (!bytes) return RTF_ERR_BAD_ARG;
         if (int rc = check_image(W, R)) return rc;
         *bytes = rtplan::plan_denoise(W, R, 0, false).scratch_bytes;
@@ -72,8 +62,8 @@ RTF_EXPORT int rtf_resolve_scratch_bytes(uint32_t W, uint32_t R, uint64_t* bytes
     });
 }
 
-RTF_EXPORT int rtf_resolve(const rtf_resolve_args* a, void* stream) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rtf_resolve(const rtf_resolve_args* a, void* stream) {
+    return guarded<RTF_ERR_INTERNAL>([&] {
         if (!a) return RTF_ERR_BAD_ARG;
         if (int rc = check_image(a->W, a->R)) return rc;
         if (a->samples < 2 || a->iterations > RTF_MAX_ITERATIONS || a->reserved != 0) return RTF_ERR_BAD_ARG;
@@ -82,7 +72,7 @@ RTF_EXPORT int rtf_resolve(const rtf_resolve_args* a, void* stream) {
         if (!a->accum || !a->moments || !a->scratch) return RTF_ERR_BAD_ARG;
         if (a->depth && !a->hits) return RTF_ERR_BAD_ARG;
         if (!a->out_rgb && !a->out_f32 && !a->out_linear && !a->out_variance) return RTF_ERR_BAD_ARG;
-        if (((uintptr_t)a->scratch & 15u) != 0) return RTF_ERR_BAD_ARG;
+        if (misaligned(a->scratch, 16)) return RTF_ERR_BAD_ARG;
         const uint32_t W = a->W, R = a->R;
         const uint32_t mask = (a->normal ? rtdn::P_NORMAL : 0u) | (a->depth ? rtdn::P_DEPTH : 0u) | (a->hits ? rtdn::P_HITS : 0u);
         const bool guided = mask != 0;
@@ -118,7 +108,7 @@ RTF_EXPORT int rtf_resolve(const rtf_resolve_args* a, void* stream) {
 
         p.dst = buf[0];
         hipLaunchKernelGGL(rtfk::rtf_entry_kernel, dim3(stride_blocks), dim3(rtfk::BLOCK), 0, st, p);
-        if (int rc = after_launch()) return rc;
+        if (int rc = after_launch(RTF_OK, RTF_ERR_HIP)) return rc;
         uint32_t cur = 0;
         for (uint32_t i = 0; i < a->iterations; i++) {
             p.s = pl.step[i];
@@ -129,13 +119,13 @@ RTF_EXPORT int rtf_resolve(const rtf_resolve_args* a, void* stream) {
                 hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rtplan::DN_LDS_CU) != hipSuccess)
                 return RTF_ERR_HIP;
             hipLaunchKernelGGL(kern, dim3(tiles), dim3(rtplan::DN_BLOCK), pl.lds[i], st, p);
-            if (int rc = after_launch()) return rc;
+            if (int rc = after_launch(RTF_OK, RTF_ERR_HIP)) return rc;
             cur ^= 1u;
         }
         if (a->iterations == 0) {
             p.src = buf[0];
             hipLaunchKernelGGL(rtfk::rtf_output_kernel, dim3(stride_blocks), dim3(rtfk::BLOCK), 0, st, p);
-            if (int rc = after_launch()) return rc;
+            if (int rc = after_launch(RTF_OK, RTF_ERR_HIP)) return rc;
         }
         return RTF_OK;
     });

@@ -5,20 +5,12 @@
 
 #include "rt_history.h"
 #include "rt_history.hip.h"
+#include "rt_private_host.h"
 #include "rt_plan.h"
 
-#define RTH_EXPORT extern "C" __attribute__((visibility("default")))
+using namespace rtpriv;
 
 namespace {
-
-template <class F>
-int guarded(const F& body) {
-    try {
-        return body();
-    } catch (...) {
-        return RTH_ERR_INTERNAL;
-    }
-}
 
 bool finite_nonneg(float v) { return std::isfinite(v) && v >= 0.0f; }
 
@@ -30,7 +22,7 @@ bool request_ok(const rt_tile_request* rq, uint32_t W, uint32_t R) {
 }
 
 bool planes_ok(const rth_state& s, bool normals) {
-    return s.accum && s.moments && s.length && s.depth && s.index && (!normals || s.normal) && ((uintptr_t)s.moments & 7u) == 0;
+    return s.accum && s.moments && s.length && s.depth && s.index && (!normals || s.normal) && !misaligned(s.moments, 8);
 }
 
 // whether q is one of the call's planes: an input, or a plane of next or (in a call that reads it) of prev
@@ -50,23 +42,23 @@ bool is_a_plane(const rth_accumulate_args& a, const void* q) {
 
 }  // namespace
 
-RTH_EXPORT int rth_version(uint32_t* version) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rth_version(uint32_t* version) {
+    return guarded<RTH_ERR_INTERNAL>([&] {
         if (!version) return RTH_ERR_BAD_ARG;
         *version = RTH_VERSION;
         return RTH_OK;
     });
 }
 
-RTH_EXPORT int rth_accumulate(const rth_accumulate_args* a, void* stream) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rth_accumulate(const rth_accumulate_args* a, void* stream) {
+    return guarded<RTH_ERR_INTERNAL>([&] {
         if (!a || a->W == 0 || a->R == 0 || a->reserved != 0) return RTH_ERR_BAD_ARG;
         if (a->W >= (1u << 24) || a->R >= (1u << 24)) return RTH_ERR_LIMIT;                   // (float)W, (float)R and the taps exact
         if (!request_ok(a->request, a->W, a->R)) return RTH_ERR_BAD_ARG;
         if (a->request->height >= (1u << 24)) return RTH_ERR_LIMIT;
         if (!(a->alpha > 0.0f && a->alpha <= 1.0f) || !(a->n_max >= 1.0f) || !std::isfinite(a->n_max)) return RTH_ERR_BAD_ARG;
         if (!finite_nonneg(a->k_depth) || !finite_nonneg(a->k_normal)) return RTH_ERR_BAD_ARG;
-        if (!a->accum || !a->moments || !a->depth || !a->hits || !a->index || ((uintptr_t)a->moments & 7u) != 0) return RTH_ERR_BAD_ARG;
+        if (!a->accum || !a->moments || !a->depth || !a->hits || !a->index || misaligned(a->moments, 8)) return RTH_ERR_BAD_ARG;
         const bool normals = a->normal != nullptr;
         if (!planes_ok(a->next, normals)) return RTH_ERR_BAD_ARG;
         const bool clip = a->clip_gamma != 0.0f;                  // (a NaN is not 0, and is refused below)
@@ -74,7 +66,7 @@ RTH_EXPORT int rth_accumulate(const rth_accumulate_args* a, void* stream) {
             if (!(a->clip_gamma > 0.0f) || !std::isfinite(a->clip_gamma)) return RTH_ERR_BAD_ARG;
             if ((a->clip_radius != 1u && a->clip_radius != 2u) || a->samples == 0 || a->clip_form > RTH_CLIP_FORM_DIRECT)
                 return RTH_ERR_BAD_ARG;
-            if (a->clip_amount && (((uintptr_t)a->clip_amount & 3u) != 0 || is_a_plane(*a, a->clip_amount))) return RTH_ERR_BAD_ARG;
+            if (a->clip_amount && (misaligned(a->clip_amount) || is_a_plane(*a, a->clip_amount))) return RTH_ERR_BAD_ARG;
         }
         const rt_tile_request& rq = *a->request;
 
@@ -135,6 +127,6 @@ RTH_EXPORT int rth_accumulate(const rth_accumulate_args* a, void* stream) {
             else
                 hipLaunchKernelGGL((rthk::rth_accumulate_kernel<2, true>), grid, block, 0, st, p);
         }
-        return hipGetLastError() == hipSuccess ? RTH_OK : RTH_ERR_HIP;
+        return after_launch(RTH_OK, RTH_ERR_HIP);
     });
 }

@@ -4,28 +4,11 @@
 
 #include "rt_robust.h"
 #include "rt_robust.hip.h"
+#include "rt_private_host.h"
 
-#define RTR_EXPORT extern "C" __attribute__((visibility("default")))
+using namespace rtpriv;
 
 namespace {
-
-template <class F>
-int guarded(const F& body) {
-    try {
-        return body();
-    } catch (...) {
-        return RTR_ERR_INTERNAL;
-    }
-}
-
-struct Range {
-    uintptr_t b, e;
-};
-
-// buffer q of n bytes (nothing for a NULL)
-Range range(const void* q, uint64_t n) { return q ? Range{(uintptr_t)q, (uintptr_t)q + (uintptr_t)n} : Range{0, 0}; }
-bool overlap(const Range& a, const Range& b) { return a.b < a.e && b.b < b.e && a.b < b.e && b.b < a.e; }
-bool misaligned(const void* q) { return ((uintptr_t)q & 3u) != 0; }
 
 using ResolveKernel = void (*)(const rtrk::ResolveParams);
 
@@ -47,16 +30,16 @@ constexpr uint64_t MAX_COUNT = 0x7fffffffull;     // pixels, and records, of a c
 
 }  // namespace
 
-RTR_EXPORT int rtr_version(uint32_t* version) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rtr_version(uint32_t* version) {
+    return guarded<RTR_ERR_INTERNAL>([&] {
         if (!version) return RTR_ERR_BAD_ARG;
         *version = RTR_VERSION;
         return RTR_OK;
     });
 }
 
-RTR_EXPORT int rtr_fold(const rtr_fold_args* a, void* stream) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rtr_fold(const rtr_fold_args* a, void* stream) {
+    return guarded<RTR_ERR_INTERNAL>([&] {
         if (!a || a->pixels == 0 || a->n == 0 || !rtrm::buckets_ok(a->K)) return RTR_ERR_BAD_ARG;
         if (!a->records || !a->buckets || misaligned(a->records) || misaligned(a->buckets)) return RTR_ERR_BAD_ARG;
         const uint64_t P = a->pixels;
@@ -75,12 +58,12 @@ RTR_EXPORT int rtr_fold(const rtr_fold_args* a, void* stream) {
         p.buckets = a->buckets;
         const dim3 grid((a->pixels + rtrk::BLOCK - 1) / rtrk::BLOCK);
         hipLaunchKernelGGL(rtrk::rtr_fold_kernel, grid, dim3(rtrk::BLOCK), 0, (hipStream_t)stream, p);
-        return hipGetLastError() == hipSuccess ? RTR_OK : RTR_ERR_HIP;
+        return after_launch(RTR_OK, RTR_ERR_HIP);
     });
 }
 
-RTR_EXPORT int rtr_resolve(const rtr_resolve_args* a, void* stream) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rtr_resolve(const rtr_resolve_args* a, void* stream) {
+    return guarded<RTR_ERR_INTERNAL>([&] {
         if (!a || a->W == 0 || a->R == 0 || !rtrm::buckets_ok(a->K) || a->samples < a->K) return RTR_ERR_BAD_ARG;
         if (a->mode != RTR_GINI && a->mode != RTR_TRIM) return RTR_ERR_BAD_ARG;
         if (a->mode == RTR_TRIM ? a->c > (a->K - 1) / 2 : a->c != 0) return RTR_ERR_BAD_ARG;
@@ -92,14 +75,10 @@ RTR_EXPORT int rtr_resolve(const rtr_resolve_args* a, void* stream) {
         const uint64_t n = (uint64_t)a->W * a->R;
         if (n > MAX_COUNT) return RTR_ERR_LIMIT;
         // an output overlaps neither the buckets nor another output
-        const Range in = range(a->buckets, n * a->K * 12);
-        const Range out[] = {range(a->out_linear, n * 12), range(a->out_gini, n * 4),   range(a->out_kept, n * 4),
-                             range(a->out_variance, n * 4), range(a->out_accum, n * 12), range(a->out_moments, n * 8)};
-        for (int k = 0; k < 6; k++) {
-            if (overlap(out[k], in)) return RTR_ERR_BAD_ARG;
-            for (int j = k + 1; j < 6; j++)
-                if (overlap(out[k], out[j])) return RTR_ERR_BAD_ARG;
-        }
+        const Range all[] = {range(a->buckets, n * a->K * 12), range(a->out_linear, n * 12), range(a->out_gini, n * 4),
+                             range(a->out_kept, n * 4),        range(a->out_variance, n * 4), range(a->out_accum, n * 12),
+                             range(a->out_moments, n * 8)};
+        if (any_overlap(all)) return RTR_ERR_BAD_ARG;
 
         rtrk::ResolveParams p;
         std::memset(&p, 0, sizeof p);
@@ -116,6 +95,6 @@ RTR_EXPORT int rtr_resolve(const rtr_resolve_args* a, void* stream) {
         if (!k) return RTR_ERR_INTERNAL;
         const dim3 grid(((uint32_t)n + rtrk::BLOCK - 1) / rtrk::BLOCK);
         hipLaunchKernelGGL(k, grid, dim3(rtrk::BLOCK), 0, (hipStream_t)stream, p);
-        return hipGetLastError() == hipSuccess ? RTR_OK : RTR_ERR_HIP;
+        return after_launch(RTR_OK, RTR_ERR_HIP);
     });
 }

@@ -5,29 +5,11 @@
 
 #include "rt_sampler.h"
 #include "rt_sampler.hip.h"
+#include "rt_private_host.h"
 
-#define RTS_EXPORT extern "C" __attribute__((visibility("default")))
+using namespace rtpriv;
 
 namespace {
-
-int after_launch() { return hipGetLastError() == hipSuccess ? RTS_OK : RTS_ERR_HIP; }
-
-template <class F>
-int guarded(const F& body) {
-    try {
-        return body();
-    } catch (...) {
-        return RTS_ERR_INTERNAL;
-    }
-}
-
-bool aligned(const void* p, uintptr_t a) { return p && ((uintptr_t)p & (a - 1u)) == 0; }
-
-// [a, a + na) and [b, b + nb) share a byte
-bool overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
 
 // the select's scratch: the noisy bytes, the active bytes, then (8-byte aligned) the workgroup offsets of every strip
 struct Layout {
@@ -57,23 +39,23 @@ int layout(uint32_t W, uint32_t R, uint32_t Hs, Layout& l) {
 // what gather and fold agree on
 int check_chunk(uint32_t n_active, uint32_t k, uint32_t pixels, uint32_t reserved, const uint32_t* active) {
     if (k == 0 || pixels == 0 || reserved != 0 || n_active > pixels) return RTS_ERR_BAD_ARG;
-    if (n_active != 0 && !aligned(active, 4)) return RTS_ERR_BAD_ARG;
+    if (n_active != 0 && (!active || misaligned(active))) return RTS_ERR_BAD_ARG;
     if ((uint64_t)pixels * k > (1ull << 30)) return RTS_ERR_LIMIT;                // half-records and floats in a grid of uint32 blocks
     return RTS_OK;
 }
 
 }  // namespace
 
-RTS_EXPORT int rts_version(uint32_t* version) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rts_version(uint32_t* version) {
+    return guarded<RTS_ERR_INTERNAL>([&] {
         if (!version) return RTS_ERR_BAD_ARG;
         *version = RTS_VERSION;
         return RTS_OK;
     });
 }
 
-RTS_EXPORT int rts_scratch_bytes(uint32_t W, uint32_t R, uint32_t Hs, uint64_t* bytes) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rts_scratch_bytes(uint32_t W, uint32_t R, uint32_t Hs, uint64_t* bytes) {
+    return guarded<RTS_ERR_INTERNAL>([&] {
         if (!bytes) return RTS_ERR_BAD_ARG;
         Layout l;
         if (int rc = layout(W, R, Hs, l)) return rc;
@@ -82,14 +64,15 @@ RTS_EXPORT int rts_scratch_bytes(uint32_t W, uint32_t R, uint32_t Hs, uint64_t* 
     });
 }
 
-RTS_EXPORT int rts_select(const rts_select_args* a, void* stream) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rts_select(const rts_select_args* a, void* stream) {
+    return guarded<RTS_ERR_INTERNAL>([&] {
         if (!a || a->reserved != 0 || a->reserved2 != 0 || a->dilate > 1u) return RTS_ERR_BAD_ARG;
         Layout l;
         if (int rc = layout(a->W, a->R, a->Hs, l)) return rc;
         if (!(a->threshold >= 0.0f) || !std::isfinite(a->eps) || !(a->eps > 0.0f)) return RTS_ERR_BAD_ARG;
-        if (!aligned(a->moments, 8) || !aligned(a->counts, 4) || !aligned(a->err, 4) || !aligned(a->active, 4) ||
-            !aligned(a->strip_counts, 4) || !aligned(a->scratch, 8))
+        if (!a->moments || !a->counts || !a->err || !a->active || !a->strip_counts || !a->scratch) return RTS_ERR_BAD_ARG;
+        if (misaligned(a->moments, 8) || misaligned(a->counts) || misaligned(a->err) || misaligned(a->active) ||
+            misaligned(a->strip_counts) || misaligned(a->scratch, 8))
             return RTS_ERR_BAD_ARG;
         if (a->scratch_bytes < l.bytes) return RTS_ERR_SCRATCH;
 
@@ -115,66 +98,68 @@ RTS_EXPORT int rts_select(const rts_select_args* a, void* stream) {
         const hipStream_t s = (hipStream_t)stream;
         const dim3 block(rtsk::BLOCK), per_strip(l.bps, l.strips);
         hipLaunchKernelGGL(rtsk::rts_metric_kernel, dim3((uint32_t)((pixels + rtsk::BLOCK - 1) / rtsk::BLOCK)), block, 0, s, p);
-        if (int rc = after_launch()) return rc;
+        if (int rc = after_launch(RTS_OK, RTS_ERR_HIP)) return rc;
         hipLaunchKernelGGL(rtsk::rts_count_kernel, per_strip, block, 0, s, p);
-        if (int rc = after_launch()) return rc;
+        if (int rc = after_launch(RTS_OK, RTS_ERR_HIP)) return rc;
         hipLaunchKernelGGL(rtsk::rts_scan_kernel, dim3(l.strips), block, 0, s, p);
-        if (int rc = after_launch()) return rc;
+        if (int rc = after_launch(RTS_OK, RTS_ERR_HIP)) return rc;
         hipLaunchKernelGGL(rtsk::rts_write_kernel, per_strip, block, 0, s, p);
-        return after_launch();
+        return after_launch(RTS_OK, RTS_ERR_HIP);
     });
 }
 
-RTS_EXPORT int rts_gather(const rts_gather_args* a, void* stream) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rts_gather(const rts_gather_args* a, void* stream) {
+    return guarded<RTS_ERR_INTERNAL>([&] {
         if (!a) return RTS_ERR_BAD_ARG;
         if (int rc = check_chunk(a->n_active, a->k, a->pixels, a->reserved, a->active)) return rc;
-        if (!aligned(a->rays, 16) || !aligned(a->states, 16) || !aligned(a->out_rays, 16) || !aligned(a->out_states, 16))
+        if (!a->rays || !a->states || !a->out_rays || !a->out_states) return RTS_ERR_BAD_ARG;
+        if (misaligned(a->rays, 16) || misaligned(a->states, 16) || misaligned(a->out_rays, 16) || misaligned(a->out_states, 16))
             return RTS_ERR_BAD_ARG;
-        const uint64_t in_bytes = (uint64_t)a->pixels * a->k * RTS_RECORD_BYTES, out_bytes = (uint64_t)a->n_active * a->k * RTS_RECORD_BYTES;
-        const void* in[2] = {a->rays, a->states};
-        const void* out[2] = {a->out_rays, a->out_states};
-        for (const void* i : in)
-            for (const void* o : out)
-                if (overlap(i, in_bytes, o, out_bytes ? out_bytes : 1)) return RTS_ERR_BAD_ARG;           // never in place
-        if (overlap(out[0], out_bytes ? out_bytes : 1, out[1], out_bytes ? out_bytes : 1)) return RTS_ERR_BAD_ARG;
+        // never in place; an output that takes nothing is still a place (one byte of it)
+        const uint64_t in_bytes = (uint64_t)a->pixels * a->k * RTS_RECORD_BYTES, taken = (uint64_t)a->n_active * a->k * RTS_RECORD_BYTES;
+        const uint64_t out_bytes = taken ? taken : 1;
+        const Range in[] = {range(a->rays, in_bytes), range(a->states, in_bytes)};
+        const Range out[] = {range(a->out_rays, out_bytes), range(a->out_states, out_bytes)};
+        if (any_overlap(in, out) || any_overlap(out)) return RTS_ERR_BAD_ARG;
         if (a->n_active == 0) return RTS_OK;
         rtsk::GatherParams p = {a->n_active, a->k, a->pixels, a->active, static_cast<const uint4*>(a->rays),
                                 static_cast<const uint4*>(a->states), static_cast<uint4*>(a->out_rays), static_cast<uint4*>(a->out_states)};
         const uint64_t halves = 2ull * a->n_active * a->k;
         hipLaunchKernelGGL(rtsk::rts_gather_kernel, dim3((uint32_t)((halves + rtsk::BLOCK - 1) / rtsk::BLOCK)), dim3(rtsk::BLOCK), 0,
                            (hipStream_t)stream, p);
-        return after_launch();
+        return after_launch(RTS_OK, RTS_ERR_HIP);
     });
 }
 
-RTS_EXPORT int rts_fold(const rts_fold_args* a, void* stream) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rts_fold(const rts_fold_args* a, void* stream) {
+    return guarded<RTS_ERR_INTERNAL>([&] {
         if (!a) return RTS_ERR_BAD_ARG;
         if (int rc = check_chunk(a->n_active, a->k, a->pixels, a->reserved, a->active)) return rc;
-        if (!aligned(a->rgb, 4) || !aligned(a->accum, 4) || !aligned(a->moments, 8) || !aligned(a->counts, 4)) return RTS_ERR_BAD_ARG;
+        if (!a->rgb || !a->accum || !a->moments || !a->counts) return RTS_ERR_BAD_ARG;
+        if (misaligned(a->rgb) || misaligned(a->accum) || misaligned(a->moments, 8) || misaligned(a->counts)) return RTS_ERR_BAD_ARG;
         if (a->n_active == 0) return RTS_OK;
         rtsk::FoldParams p = {a->n_active, a->k, a->pixels, a->active, a->rgb, a->accum, a->moments, a->counts};
         hipLaunchKernelGGL(rtsk::rts_fold_kernel, dim3((a->n_active + rtsk::BLOCK - 1u) / rtsk::BLOCK), dim3(rtsk::BLOCK), 0,
                            (hipStream_t)stream, p);
-        return after_launch();
+        return after_launch(RTS_OK, RTS_ERR_HIP);
     });
 }
 
-RTS_EXPORT int rts_normalise(const rts_normalise_args* a, void* stream) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rts_normalise(const rts_normalise_args* a, void* stream) {
+    return guarded<RTS_ERR_INTERNAL>([&] {
         if (!a || a->reserved != 0) return RTS_ERR_BAD_ARG;
         if (int rc = check_image(a->W, a->R)) return rc;
         if (a->e0 < 2u) return RTS_ERR_BAD_ARG;
         if (a->e0 > (1u << 24)) return RTS_ERR_LIMIT;                             // (float)e0 and e0 - 1 exact
-        if (!aligned(a->accum, 4) || !aligned(a->moments, 8) || !aligned(a->counts, 4) || !aligned(a->out_accum, 4) ||
-            !aligned(a->out_moments, 8))
+        if (!a->accum || !a->moments || !a->counts || !a->out_accum || !a->out_moments) return RTS_ERR_BAD_ARG;
+        if (misaligned(a->accum) || misaligned(a->moments, 8) || misaligned(a->counts) || misaligned(a->out_accum) ||
+            misaligned(a->out_moments, 8))
             return RTS_ERR_BAD_ARG;
         if (a->out_accum == a->accum || a->out_moments == a->moments) return RTS_ERR_BAD_ARG;
         const uint64_t pixels = (uint64_t)a->W * a->R;
         rtsk::NormaliseParams p = {pixels, (int32_t)a->e0, (float)a->e0, a->accum, a->moments, a->counts, a->out_accum, a->out_moments};
         hipLaunchKernelGGL(rtsk::rts_normalise_kernel, dim3((uint32_t)((pixels + rtsk::BLOCK - 1) / rtsk::BLOCK)), dim3(rtsk::BLOCK), 0,
                            (hipStream_t)stream, p);
-        return after_launch();
+        return after_launch(RTS_OK, RTS_ERR_HIP);
     });
 }

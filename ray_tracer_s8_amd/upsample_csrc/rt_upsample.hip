@@ -7,19 +7,11 @@
 
 #include "rt_upsample.h"
 #include "rt_upsample.hip.h"
+#include "rt_private_host.h"
 
-#define RTU_EXPORT extern "C" __attribute__((visibility("default")))
+using namespace rtpriv;
 
 namespace {
-
-template <class F>
-int guarded(const F& body) {
-    try {
-        return body();
-    } catch (...) {
-        return RTU_ERR_INTERNAL;
-    }
-}
 
 bool finite_nonneg(float v) { return std::isfinite(v) && v >= 0.0f; }
 
@@ -28,14 +20,6 @@ uint32_t planes_of(const rtu_planes& s) {
     return (s.albedo ? rtum::P_ALBEDO : 0u) | (s.normal ? rtum::P_NORMAL : 0u) | (s.depth ? rtum::P_DEPTH : 0u) |
            (s.hits ? rtum::P_HITS : 0u) | (s.index ? rtum::P_INDEX : 0u);
 }
-
-struct Range {
-    uintptr_t b, e;
-};
-
-// buffer q of n bytes (nothing for a NULL)
-Range range(const void* q, uint64_t n) { return q ? Range{(uintptr_t)q, (uintptr_t)q + (uintptr_t)n} : Range{0, 0}; }
-bool overlap(const Range& a, const Range& b) { return a.b < a.e && b.b < b.e && a.b < b.e && b.b < a.e; }
 
 using Kernel = void (*)(const rtuk::Params);
 
@@ -55,16 +39,16 @@ Kernel pick(uint32_t planes, std::integer_sequence<uint32_t, P...>) {
 
 }  // namespace
 
-RTU_EXPORT int rtu_version(uint32_t* version) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rtu_version(uint32_t* version) {
+    return guarded<RTU_ERR_INTERNAL>([&] {
         if (!version) return RTU_ERR_BAD_ARG;
         *version = RTU_VERSION;
         return RTU_OK;
     });
 }
 
-RTU_EXPORT int rtu_upsample(const rtu_upsample_args* a, void* stream) {
-    return guarded([&] {
+RT_PRIVATE_EXPORT int rtu_upsample(const rtu_upsample_args* a, void* stream) {
+    return guarded<RTU_ERR_INTERNAL>([&] {
         if (!a || a->reserved != 0 || a->lo.reserved != 0 || a->hi.reserved != 0 || a->form != 0) return RTU_ERR_BAD_ARG;
         if (a->Wl == 0 || a->Rl == 0 || a->Hl == 0 || a->Wh == 0 || a->Rh == 0 || a->Hh == 0) return RTU_ERR_BAD_ARG;
         if (a->scale < RTU_MIN_SCALE || a->scale > RTU_MAX_SCALE) return RTU_ERR_BAD_ARG;
@@ -85,7 +69,7 @@ RTU_EXPORT int rtu_upsample(const rtu_upsample_args* a, void* stream) {
         const void* dwords[] = {a->linear,   a->lo.albedo, a->lo.normal, a->lo.depth, a->lo.hits, a->lo.index, a->hi.albedo,
                                 a->hi.normal, a->hi.depth,  a->hi.hits,   a->hi.index, a->out_linear, a->out_f32};
         for (const void* q : dwords)
-            if (((uintptr_t)q & 3u) != 0) return RTU_ERR_BAD_ARG;
+            if (misaligned(q)) return RTU_ERR_BAD_ARG;
         // an output overlaps neither an input nor another output
         const Range in[] = {range(a->linear, nl * 12),      range(a->lo.albedo, nl * 12), range(a->lo.normal, nl * 12),
                             range(a->lo.depth, nl * 4),     range(a->lo.hits, nl * 4),    range(a->lo.index, nl * 4),
@@ -93,12 +77,7 @@ RTU_EXPORT int rtu_upsample(const rtu_upsample_args* a, void* stream) {
                             range(a->hi.hits, nh * 4),      range(a->hi.index, nh * 4)};
         const Range out[] = {range(a->out_linear, nh * 12), range(a->out_f32, nh * 12), range(a->out_rgb, nh * 3),
                              range(a->out_class, nh)};
-        for (int k = 0; k < 4; k++) {
-            for (const Range& r : in)
-                if (overlap(out[k], r)) return RTU_ERR_BAD_ARG;
-            for (int j = k + 1; j < 4; j++)
-                if (overlap(out[k], out[j])) return RTU_ERR_BAD_ARG;
-        }
+        if (any_overlap(out, in) || any_overlap(out)) return RTU_ERR_BAD_ARG;
 
         rtuk::Params p;
         std::memset(&p, 0, sizeof p);
@@ -125,6 +104,6 @@ RTU_EXPORT int rtu_upsample(const rtu_upsample_args* a, void* stream) {
         const Kernel k = pick(planes, std::make_integer_sequence<uint32_t, rtum::P_ALL + 1u>{});
         if (!k) return RTU_ERR_INTERNAL;
         hipLaunchKernelGGL(k, grid, dim3(rtuk::BLOCK), 0, (hipStream_t)stream, p);
-        return hipGetLastError() == hipSuccess ? RTU_OK : RTU_ERR_HIP;
+        return after_launch(RTU_OK, RTU_ERR_HIP);
     });
 }

@@ -2,13 +2,9 @@
 1. check_display, check_exposure, check_outputs and percentile_q16 refuse, with ValueError, everything FilmDisplay refuses; FilmDisplay
    is in rt.__all__;
 2. film_display.py and _display_lib.py import without torch and without loading the library;
-3. librt_display.so exports exactly _display_lib.SIGNATURES, all rtd_*, and nothing of the tile ABI; the private header declares
-   exactly those, with the version, the statuses, the modes, the curves and the forms the binding expects; no rtd_ name is in any other
-   library or source directory, and there is no include/rt_display.h;
-4. the library is a build.Library value beside csrc/ that depends on no csrc/ header: the last member of EVERY_FILM_LIBRARY and a member
-   of none of LIBRARIES, PRIVATE_LIBRARIES, FILM_LIBRARIES and ALL_FILM_LIBRARIES, which keep their values; its record is the golden
-   one, the product's flags plus -fno-slp-vectorize whatever RT_EXTRA_HIPCC_FLAGS says; the driver's build() makes it;
-5. every refusal of the library's calls comes back as a status, with no device bound and addresses that are never read.
+3. the binding has the version, the status table, the modes, the curves, the forms and the sizes of this library's header;
+4. every refusal of the library's calls comes back as a status, with no device bound and addresses that are never read.
+What holds of every private library (a library of its own, its record, its exports, who builds it) is tests/test_private_libraries.py's.
 Without the feature every test here fails: there is no film_display, no _display_lib and no build.DISPLAY."""
 import ctypes as C
 import math
@@ -21,12 +17,9 @@ from pathlib import Path
 import pytest
 
 import ray_tracer_s8_amd as rt
-from ray_tracer_s8_amd import _abi, build
-
-import _surface
+from ray_tracer_s8_amd import build
 
 ROOT = Path(__file__).resolve().parent.parent
-GOLDEN = Path(__file__).resolve().parent / "golden" / "build_records"
 NAMES = ("rtd_version", "rtd_meter", "rtd_expose", "rtd_apply")
 
 
@@ -90,7 +83,7 @@ def test_percentiles_exposures_and_outputs():
 def test_film_display_runs_its_checks_before_anything_else():
     """Bad arguments: ValueError before the film, torch or the library is touched."""
     from ray_tracer_s8_amd import _display_lib
-    loaded = _display_lib._lib
+    loaded = _display_lib.BINDING.loaded
     film = types.SimpleNamespace(rows=36, width=64)                     # (no _check_open, no _torch: touching either would raise)
     for kw in (dict(curve="aces"), dict(key=0), dict(rate=2.0), dict(shape=(0, 3)), dict(key_percentile=0.9, white_percentile=0.1),
                dict(dither="yes"), dict(scale_range=(2.0, 1.0))):
@@ -98,7 +91,7 @@ def test_film_display_runs_its_checks_before_anything_else():
             rt.FilmDisplay(film, **kw)
     with pytest.raises(ValueError):
         rt.FilmDisplay(types.SimpleNamespace())                        # no shape to take from the film
-    assert _display_lib._lib is loaded
+    assert _display_lib.BINDING.loaded is loaded
 
 
 _IMPORT_CHILD = r"""
@@ -107,13 +100,13 @@ import ray_tracer_s8_amd as rt
 import ray_tracer_s8_amd.film_display as fd
 import ray_tracer_s8_amd._display_lib as dl
 assert "torch" not in sys.modules
-assert dl._lib is None                                  # importing loads nothing
+assert not dl.BINDING.loaded                            # importing loads nothing
 assert callable(fd.check_display) and callable(fd.percentile_q16) and rt.FilmDisplay is fd.FilmDisplay
 assert all(callable(getattr(fd.FilmDisplay, n)) for n in ("meter", "apply", "display", "set_exposure", "auto", "exposure", "reset", "close"))
 assert isinstance(fd.FilmDisplay.histogram, property)
 assert sorted(dl.SIGNATURES) == sorted(%r)
 assert fd.check_display((9, 70), "reinhard").curve == "reinhard"
-assert "torch" not in sys.modules and dl._lib is None
+assert "torch" not in sys.modules and not dl.BINDING.loaded
 print("ok")
 """ % (NAMES,)
 
@@ -123,97 +116,15 @@ def test_film_display_and_its_binding_import_without_torch():
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
 
 
-def test_exports():
+def test_the_bindings_own_constants():
     from ray_tracer_s8_amd import _display_lib
-    _abi.load()
-    _abi.load_debug()
-    others = (build.LIB_PATH, build.DEBUG_LIB_PATH, build.build_film(), build.build_history(), build.build_sampler(), build.build_upsample(),
-              build.build_robust())
-    for path in others:
-        assert not [s for s in _surface.all_exported(path) if "rtd_" in s], path
-    mine = {s for s in _surface.all_exported(build.build_display()) if not s.startswith("_")}
-    assert mine == set(_display_lib.SIGNATURES) == set(NAMES) and all(s.startswith("rtd_") for s in mine), mine
-    assert not _surface.exported(build.DISPLAY.path)                  # nothing of the tile ABI
-    # the private header declares exactly the functions the binding names, the version and the constants the binding expects
+    assert _display_lib.RTD_VERSION == 1 and set(_display_lib.SIGNATURES) == set(NAMES)
+    assert _display_lib.STATUS == {1: "RTD_ERR_BAD_ARG", 2: "RTD_ERR_LIMIT", 3: "RTD_ERR_HIP", 4: "RTD_ERR_INTERNAL"}
     text = (build.DISPLAY.src_dir / "rt_display.h").read_text()
-    assert set(re.findall(r"^int (rtd_\w+)\(", text, re.M)) == set(_display_lib.SIGNATURES)
-    assert re.search(r"^#define RTD_VERSION (\d+)u$", text, re.M).group(1) == str(_display_lib.RTD_VERSION) == "1"
-    status = dict((int(v), n) for n, v in re.findall(r"^#define (RTD_ERR_\w+) (\d+)", text, re.M))
-    assert status == _display_lib.STATUS and sorted(status) == [1, 2, 3, 4]
-    assert status == {1: "RTD_ERR_BAD_ARG", 2: "RTD_ERR_LIMIT", 3: "RTD_ERR_HIP", 4: "RTD_ERR_INTERNAL"}
-    assert re.search(r"^#define RTD_OK 0$", text, re.M)
     named = lambda names: dict((n.lower(), int(v)) for n, v in re.findall(rf"^#define RTD_({names}) (\d+)u", text, re.M))
     assert named("AUTO|MANUAL") == _display_lib.MODES and named("NONE|REINHARD|FILMIC") == _display_lib.CURVES
     assert named("HIST_WAVE|HIST_MATCH") == {"hist_" + k: v for k, v in _display_lib.FORMS.items()}
     assert named("HIST_WORDS|RECORD_WORDS") == dict(hist_words=_display_lib.HIST_WORDS, record_words=_display_lib.RECORD_WORDS)
-    assert not (ROOT / "include" / "rt_display.h").exists()
-    # and no other source of the package speaks of an rtd_ name
-    for d in (build.CSRC, build.FILM_CSRC, build.HISTORY_CSRC, build.SAMPLER.src_dir, build.UPSAMPLE.src_dir, build.ROBUST.src_dir,
-              ROOT / "include"):
-        for f in d.rglob("*"):
-            if f.is_file():
-                assert "rtd_" not in f.read_text().lower(), f
-
-
-def test_the_display_library_is_a_library_of_its_own(monkeypatch):
-    lib = build.DISPLAY
-    assert isinstance(lib, build.Library)
-    assert build.LIBRARIES == (build.PRODUCT, build.DEBUG, build.FILM, build.HISTORY)
-    assert build.PRIVATE_LIBRARIES == (build.FILM, build.HISTORY, build.SAMPLER)
-    assert build.FILM_LIBRARIES == (build.FILM, build.HISTORY, build.SAMPLER, build.UPSAMPLE)
-    assert build.ALL_FILM_LIBRARIES == (*build.FILM_LIBRARIES, build.ROBUST)
-    for pinned in (build.LIBRARIES, build.PRIVATE_LIBRARIES, build.FILM_LIBRARIES, build.ALL_FILM_LIBRARIES):
-        assert lib not in pinned
-    assert build.EVERY_FILM_LIBRARY == (*build.ALL_FILM_LIBRARIES, lib)
-    assert lib.path == build.LIB_DIR / "librt_display.so" and lib.obj_dir == build.LIB_DIR / "obj_display"
-    others = (*build.LIBRARIES, build.SAMPLER, build.UPSAMPLE, build.ROBUST)
-    assert lib.path not in [o.path for o in others] and lib.obj_dir not in [o.obj_dir for o in others]
-    assert lib.units == (("rt_display.hip", ()),) and (lib.src_dir / "rt_display.hip").is_file()
-    for name in ("rt_display.h", "rt_display_math.h", "rt_display.hip.h"):
-        assert (lib.src_dir / name).is_file()
-    # beside csrc/: its own directory, no csrc/ header, the C header, the recipe
-    assert lib.src_dir == build.PKG / "display_csrc" and build.CSRC not in lib.src_dir.parents
-    deps = build.dep_files(lib)
-    assert any(lib.src_dir in d.parents for d in deps) and Path(build.__file__) in deps
-    assert not [d for d in deps if build.CSRC in d.parents]
-    included = set()
-    for f in lib.src_dir.iterdir():
-        included |= set(re.findall(r'^#include "([\w.]+)"', f.read_text(), re.M))
-    assert included == {"rt_display.h", "rt_display_math.h", "rt_display.hip.h"}
-    for other in others:
-        assert not any(lib.src_dir in d.parents for d in build.dep_files(other)), other.path
-        assert not any(other.src_dir in d.parents for d in deps if other.src_dir != build.CSRC), other.path
-        assert "rt_display" not in build.record(other)
-    # the record: the golden one, the product's flags plus -fno-slp-vectorize, never the experiments' flags
-    golden = (GOLDEN / "display.flags").read_text()
-    before = [build.record(o) for o in others if o is not build.PRODUCT]
-    assert build.record(lib) == golden and golden.startswith("rt_display.hip: ")
-    flags = golden.split(": ", 1)[1].split()
-    assert flags == [f for f in build.HIPCC_FLAGS if f != "-shared"] + ["-fno-slp-vectorize"]
-    assert "-ffp-contract=off" in flags and "-fno-unroll-loops" in flags
-    monkeypatch.setenv("RT_EXTRA_HIPCC_FLAGS", "-DRT_PROFILE_TIME")
-    assert "-DRT_PROFILE_TIME" in build.flags_record() and build.record(lib) == golden
-    assert [build.record(o) for o in others if o is not build.PRODUCT] == before
-    monkeypatch.delenv("RT_EXTRA_HIPCC_FLAGS")
-    path = build.build_display()
-    assert path == lib.path and path.exists() and not build.stale(lib) and lib.record_path.read_text() == golden
-
-
-def test_who_builds_the_display_library(monkeypatch):
-    """build() asks for what it asked for before (the tests of the libraries before this one pin that), build_display asks for the
-    display library alone, and the driver's build() calls it, forced, beside build_debug."""
-    asked = []
-    monkeypatch.setattr(build, "stale", lambda lib: asked.append(lib.path) or False)
-    monkeypatch.setattr(build, "compile_and_link", lambda lib, verbose=False: asked.append(("compile", lib.path)) or lib.path)
-    assert build.build() == build.LIB_PATH
-    assert asked == [*(l.path for l in build.FILM_LIBRARIES), build.LIB_PATH, build.ROBUST.path]
-    asked.clear()
-    assert build.build_display() == build.DISPLAY.path and asked == [build.DISPLAY.path]
-    asked.clear()
-    assert build.build_display(force=True) == build.DISPLAY.path and asked == [("compile", build.DISPLAY.path)]
-    entry = (ROOT / "__graft_entry__.py").read_text()
-    assert "hip_build.build_display(force=True)" in entry
-    assert entry.index("build_debug(force=True)") < entry.index("build_display(force=True)") < entry.index("orc.build(")
 
 
 def test_the_binding_loads_the_library_and_refusals_are_statuses():

@@ -2,11 +2,9 @@
 1. check_guided refuses, with ValueError, everything resolve_guided and variance refuse, and accepts the rest;
 2. film.py and _film_lib.py import without torch and without loading the film library;
 3. Film(None, reqs, moments=True) runs check_job first;
-4. librt_s8.so still exports exactly the header, no rtf_ symbol is in any other library, and librt_film.so exports the four rtf_
-   functions of film_csrc/rt_film.h; the binding's table names exactly those.
-The film library's record and staleness are tests/test_build_recipe.py's.
-Without the feature every test here fails: there is no check_guided, no _film_lib and no build_film."""
-import re
+4. the binding loads the library with no device bound, and its refusals are statuses.
+What holds of every private library (a library of its own, its record, its exports, who builds it) is tests/test_private_libraries.py's.
+Without the feature every test here fails: there is no check_guided, no _film_lib and no build.FILM."""
 import subprocess
 import sys
 from pathlib import Path
@@ -14,9 +12,7 @@ from pathlib import Path
 import pytest
 
 import ray_tracer_s8_amd as rt
-from ray_tracer_s8_amd import _abi, build
-
-import _surface
+from ray_tracer_s8_amd import _abi
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -82,11 +78,11 @@ import ray_tracer_s8_amd as rt
 import ray_tracer_s8_amd.film as film
 import ray_tracer_s8_amd._film_lib as fl
 assert "torch" not in sys.modules
-assert fl._lib is None                                  # importing loads nothing
+assert not fl.BINDING.loaded                            # importing loads nothing
 assert callable(film.check_guided) and callable(film.Film.resolve_guided) and callable(film.Film.variance)
 assert sorted(fl.SIGNATURES) == ["rtf_fold_moments", "rtf_resolve", "rtf_resolve_scratch_bytes", "rtf_version"]
 film.check_guided(True, 2)
-assert "torch" not in sys.modules and fl._lib is None
+assert "torch" not in sys.modules and not fl.BINDING.loaded
 print("ok")
 """
 
@@ -106,23 +102,6 @@ def test_film_with_moments_runs_check_job_first():
 def test_abi_module_holds_nothing_of_the_film_library():
     names = [n for n in dir(_abi) if "rtf" in n.lower() or "film" in n.lower()]
     assert names == [], names
-
-
-def test_exports():
-    from ray_tracer_s8_amd import _film_lib
-    _abi.load()
-    _abi.load_debug()
-    declared = set(_surface.parse()["functions"])
-    assert len(declared) == 51 and _surface.exported(build.LIB_PATH) == declared
-    for path in (build.LIB_PATH, build.DEBUG_LIB_PATH, build.build_history()):
-        assert not [s for s in _surface.all_exported(path) if "rtf_" in s], path
-    film = {s for s in _surface.all_exported(build.build_film()) if not s.startswith("_")}
-    assert film == set(_film_lib.SIGNATURES), film
-    assert not _surface.exported(build.FILM_LIB_PATH)
-    # the private header declares exactly the functions the binding names
-    text = (build.FILM_CSRC / "rt_film.h").read_text()
-    assert set(re.findall(r"^int (rtf_\w+)\(", text, re.M)) == set(_film_lib.SIGNATURES)
-    assert not (ROOT / "include" / "rt_film.h").exists()
 
 
 def test_the_binding_loads_the_library_and_reports_scratch_bytes():

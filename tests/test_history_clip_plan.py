@@ -63,11 +63,11 @@ import sys
 import ray_tracer_s8_amd as rt
 import ray_tracer_s8_amd.film_history as fh
 import ray_tracer_s8_amd._history_lib as hl
-assert "torch" not in sys.modules and hl._lib is None
+assert "torch" not in sys.modules and not hl.BINDING.loaded
 assert fh.check_clip(1.5, 2) == (1.5, 2) and fh.check_clip(None) == (0.0, 0)
 assert sorted(hl.SIGNATURES) == ["rth_accumulate", "rth_version"]
 assert hl.RTH_VERSION == 2
-assert "torch" not in sys.modules and hl._lib is None
+assert "torch" not in sys.modules and not hl.BINDING.loaded
 print("ok")
 """
 
@@ -80,7 +80,7 @@ def test_the_modules_import_without_torch():
 def test_the_header_declares_the_two_functions_and_the_binding_has_its_record():
     from ray_tracer_s8_amd import _history_lib as hl
     assert sorted(hl.SIGNATURES) == ["rth_accumulate", "rth_version"]
-    text = (build.HISTORY_CSRC / "rt_history.h").read_text()
+    text = (build.HISTORY.src_dir / "rt_history.h").read_text()
     assert sorted(re.findall(r"^int (rth_\w+)\(", text, re.M)) == sorted(hl.SIGNATURES)
     assert re.search(r"^#define RTH_VERSION 2u$", text, re.M) and hl.RTH_VERSION == 2
     # the record: the header's fields in the header's order, the clip's appended after `next`, `reserved` where it was

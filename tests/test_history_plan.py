@@ -1,15 +1,12 @@
 """The film history without a GPU (ray_tracer_s8_amd/film_history.py, _history_lib.py, build.py):
 1. check_history refuses, with ValueError, everything FilmHistory refuses, and accepts the rest;
 2. film_history.py and _history_lib.py import without torch and without loading the history library;
-3. librt_history.so exports exactly _history_lib.SIGNATURES, all rth_*, and the private header declares exactly those; librt_s8.so,
-   librt_s8_dbg.so and librt_film.so export what they exported;
-4. rth_accumulate refuses bad arguments with a status, before any launch;
-5. Film.reset(seed=...) sets the seed of the film's own requests, not the caller's.
-The history library's record and staleness are tests/test_build_recipe.py's.
-Without the feature every test here fails: there is no film_history, no _history_lib and no build_history."""
+3. rth_accumulate refuses bad arguments with a status, before any launch;
+4. Film.reset(seed=...) sets the seed of the film's own requests, not the caller's.
+What holds of every private library (a library of its own, its record, its exports, who builds it) is tests/test_private_libraries.py's.
+Without the feature every test here fails: there is no film_history, no _history_lib and no build.HISTORY."""
 import contextlib
 import ctypes as C
-import re
 import subprocess
 import sys
 import types
@@ -18,9 +15,7 @@ from pathlib import Path
 import pytest
 
 import ray_tracer_s8_amd as rt
-from ray_tracer_s8_amd import _abi, build
-
-import _surface
+from ray_tracer_s8_amd import _abi
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -82,11 +77,11 @@ import ray_tracer_s8_amd as rt
 import ray_tracer_s8_amd.film_history as fh
 import ray_tracer_s8_amd._history_lib as hl
 assert "torch" not in sys.modules
-assert hl._lib is None                                  # importing loads nothing
+assert not hl.BINDING.loaded                            # importing loads nothing
 assert callable(fh.check_history) and callable(fh.FilmHistory.accumulate) and callable(fh.FilmHistory.resolve_guided)
 assert sorted(hl.SIGNATURES) == ["rth_accumulate", "rth_version"]
 fh.check_history(True)
-assert "torch" not in sys.modules and hl._lib is None
+assert "torch" not in sys.modules and not hl.BINDING.loaded
 print("ok")
 """
 
@@ -99,25 +94,6 @@ def test_film_history_and_its_binding_import_without_torch():
 def test_abi_module_holds_nothing_of_the_history_library():
     names = [n for n in dir(_abi) if "rth" in n.lower() or "history" in n.lower()]
     assert names == [], names
-
-
-def test_exports():
-    from ray_tracer_s8_amd import _film_lib, _history_lib
-    _abi.load()
-    _abi.load_debug()
-    declared = set(_surface.parse()["functions"])
-    assert len(declared) == 51 and _surface.exported(build.LIB_PATH) == declared
-    for path in (build.LIB_PATH, build.DEBUG_LIB_PATH, build.build_film()):
-        assert not [s for s in _surface.all_exported(path) if "rth_" in s], path
-    film = {s for s in _surface.all_exported(build.FILM_LIB_PATH) if not s.startswith("_")}
-    assert film == set(_film_lib.SIGNATURES) == {"rtf_version", "rtf_fold_moments", "rtf_resolve_scratch_bytes", "rtf_resolve"}
-    history = {s for s in _surface.all_exported(build.build_history()) if not s.startswith("_")}
-    assert history == set(_history_lib.SIGNATURES) and all(s.startswith("rth_") for s in history), history
-    assert not _surface.exported(build.HISTORY_LIB_PATH)
-    # the private header declares exactly the functions the binding names
-    text = (build.HISTORY_CSRC / "rt_history.h").read_text()
-    assert set(re.findall(r"^int (rth_\w+)\(", text, re.M)) == set(_history_lib.SIGNATURES)
-    assert not (ROOT / "include" / "rt_history.h").exists()
 
 
 def test_the_binding_loads_the_library_and_refusals_are_statuses():

@@ -1,14 +1,11 @@
 """The robust film without a GPU (ray_tracer_s8_amd/film_robust.py, _robust_lib.py, build.py, film.py):
 1. check_robust and check_estimate refuse, with ValueError, everything FilmRobust refuses; FilmRobust is in rt.__all__;
 2. film_robust.py and _robust_lib.py import without torch and without loading the library;
-3. librt_robust.so exports exactly _robust_lib.SIGNATURES, all rtr_*, and the private header declares exactly those; no rtr_ name is in
-   any other library or source directory, and there is no include/rt_robust.h;
-4. the library is a build.Library value beside csrc/ that depends on no csrc/ header: a member of ALL_FILM_LIBRARIES and of none of
-   LIBRARIES, PRIVATE_LIBRARIES and FILM_LIBRARIES, which keep their values; its record is the golden one, the product's flags plus
-   -fno-slp-vectorize whatever RT_EXTRA_HIPCC_FLAGS says; build() asks for it through stale and compile_and_link, after the product;
-5. every refusal of the library's calls comes back as a status, with no device bound;
-6. the film's tap: a film with no tap makes the calls it made before and no other, and a tap is shown every strip's sub-range after
+3. the binding has the version, the status table and the modes of this library's header;
+4. every refusal of the library's calls comes back as a status, with no device bound;
+5. the film's tap: a film with no tap makes the calls it made before and no other, and a tap is shown every strip's sub-range after
    its fold, in order, and the reset after the film's own zeroing.
+What holds of every private library (a library of its own, its record, its exports, who builds it) is tests/test_private_libraries.py's.
 Without the feature every test here fails: there is no film_robust, no _robust_lib, no build.ROBUST and no Film._taps."""
 import ctypes as C
 import re
@@ -23,10 +20,7 @@ import pytest
 import ray_tracer_s8_amd as rt
 from ray_tracer_s8_amd import _abi, build
 
-import _surface
-
 ROOT = Path(__file__).resolve().parent.parent
-GOLDEN = Path(__file__).resolve().parent / "golden" / "build_records"
 NAMES = ("rtr_version", "rtr_fold", "rtr_resolve")
 
 
@@ -74,13 +68,13 @@ def test_check_estimate():
 def test_film_robust_runs_its_checks_before_anything_else():
     """Bad arguments, a film that holds samples: ValueError before torch or the library is touched."""
     from ray_tracer_s8_amd import _robust_lib
-    loaded = _robust_lib._lib
+    loaded = _robust_lib.BINDING.loaded
     fresh, used = types.SimpleNamespace(samples=0), types.SimpleNamespace(samples=3)
     for film, kw in ((fresh, dict(buckets=4)), (fresh, dict(mode="trim")), (fresh, dict(c=1)), (fresh, dict(mode="x")),
                      (used, {}), (None, {})):
         with pytest.raises(ValueError):
             rt.FilmRobust(film, **kw)
-    assert _robust_lib._lib is loaded
+    assert _robust_lib.BINDING.loaded is loaded
 
 
 _IMPORT_CHILD = r"""
@@ -89,12 +83,12 @@ import ray_tracer_s8_amd as rt
 import ray_tracer_s8_amd.film_robust as fr
 import ray_tracer_s8_amd._robust_lib as rl
 assert "torch" not in sys.modules
-assert rl._lib is None                                  # importing loads nothing
+assert not rl.BINDING.loaded                            # importing loads nothing
 assert callable(fr.check_robust) and callable(fr.FilmRobust.estimate) and callable(fr.FilmRobust.state)
 assert all(callable(getattr(fr.FilmRobust, n)) for n in ("preview", "resolve", "resolve_guided", "variance", "close"))
 assert sorted(rl.SIGNATURES) == sorted(%r)
 assert fr.check_robust(0, 5, "trim", 2) == (5, "trim", 2)
-assert "torch" not in sys.modules and rl._lib is None
+assert "torch" not in sys.modules and not rl.BINDING.loaded
 print("ok")
 """ % (NAMES,)
 
@@ -104,89 +98,14 @@ def test_film_robust_and_its_binding_import_without_torch():
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
 
 
-def test_exports():
+def test_the_bindings_own_constants():
     from ray_tracer_s8_amd import _robust_lib
-    _abi.load()
-    _abi.load_debug()
-    others = (build.LIB_PATH, build.DEBUG_LIB_PATH, build.build_film(), build.build_history(), build.build_sampler(), build.build_upsample())
-    for path in others:
-        assert not [s for s in _surface.all_exported(path) if "rtr_" in s], path
-    mine = {s for s in _surface.all_exported(build.build_robust()) if not s.startswith("_")}
-    assert mine == set(_robust_lib.SIGNATURES) == set(NAMES) and all(s.startswith("rtr_") for s in mine), mine
-    assert not _surface.exported(build.ROBUST.path)                   # nothing of the tile ABI
-    # the private header declares exactly the functions the binding names, the version and the statuses the binding expects
+    assert _robust_lib.RTR_VERSION == 1 and set(_robust_lib.SIGNATURES) == set(NAMES)
+    assert _robust_lib.STATUS == {1: "RTR_ERR_BAD_ARG", 2: "RTR_ERR_LIMIT", 3: "RTR_ERR_HIP", 4: "RTR_ERR_INTERNAL"}
     text = (build.ROBUST.src_dir / "rt_robust.h").read_text()
-    assert set(re.findall(r"^int (rtr_\w+)\(", text, re.M)) == set(_robust_lib.SIGNATURES)
-    assert re.search(r"^#define RTR_VERSION (\d+)u$", text, re.M).group(1) == str(_robust_lib.RTR_VERSION) == "1"
-    status = dict((int(v), n) for n, v in re.findall(r"^#define (RTR_ERR_\w+) (\d+)", text, re.M))
-    assert status == _robust_lib.STATUS and sorted(status) == [1, 2, 3, 4]
     modes = dict((n.lower(), int(v)) for n, v in re.findall(r"^#define RTR_(GINI|TRIM) (\d+)u", text, re.M))
     assert modes == _robust_lib.MODES
-    assert not (ROOT / "include" / "rt_robust.h").exists()
-    # and no other source of the package speaks of an rtr_ name
-    for d in (build.CSRC, build.FILM_CSRC, build.HISTORY_CSRC, build.SAMPLER.src_dir, build.UPSAMPLE.src_dir, ROOT / "include"):
-        for f in d.rglob("*"):
-            if f.is_file():
-                assert "rtr_" not in f.read_text().lower(), f
-
-
-def test_the_robust_library_is_a_library_of_its_own(monkeypatch):
-    lib = build.ROBUST
-    assert isinstance(lib, build.Library)
-    assert build.LIBRARIES == (build.PRODUCT, build.DEBUG, build.FILM, build.HISTORY)
-    assert build.PRIVATE_LIBRARIES == (build.FILM, build.HISTORY, build.SAMPLER)
-    assert build.FILM_LIBRARIES == (build.FILM, build.HISTORY, build.SAMPLER, build.UPSAMPLE)
-    assert lib not in build.LIBRARIES and lib not in build.PRIVATE_LIBRARIES and lib not in build.FILM_LIBRARIES
-    assert build.ALL_FILM_LIBRARIES == (*build.FILM_LIBRARIES, lib)
-    assert lib.path == build.LIB_DIR / "librt_robust.so" and lib.obj_dir == build.LIB_DIR / "obj_robust"
-    others = (*build.LIBRARIES, build.SAMPLER, build.UPSAMPLE)
-    assert lib.path not in [o.path for o in others] and lib.obj_dir not in [o.obj_dir for o in others]
-    assert lib.units == (("rt_robust.hip", ()),) and (lib.src_dir / "rt_robust.hip").is_file()
-    for name in ("rt_robust.h", "rt_robust_math.h", "rt_robust.hip.h"):
-        assert (lib.src_dir / name).is_file()
-    # beside csrc/: its own directory, no csrc/ header, the C header, the recipe
-    assert lib.src_dir == build.PKG / "robust_csrc" and build.CSRC not in lib.src_dir.parents
-    deps = build.dep_files(lib)
-    assert any(lib.src_dir in d.parents for d in deps) and Path(build.__file__) in deps
-    assert not [d for d in deps if build.CSRC in d.parents]
-    included = set()
-    for f in lib.src_dir.iterdir():
-        included |= set(re.findall(r'^#include "([\w.]+)"', f.read_text(), re.M))
-    assert included == {"rt_robust.h", "rt_robust_math.h", "rt_robust.hip.h"}
-    for other in others:
-        assert not any(lib.src_dir in d.parents for d in build.dep_files(other)), other.path
-        assert not any(other.src_dir in d.parents for d in deps if other.src_dir != build.CSRC), other.path
-        assert "rt_robust" not in build.record(other)
-    # the record: the golden one, the product's flags plus -fno-slp-vectorize, never the experiments' flags
-    golden = (GOLDEN / "robust.flags").read_text()
-    before = [build.record(o) for o in others if o is not build.PRODUCT]
-    assert build.record(lib) == golden and golden.startswith("rt_robust.hip: ")
-    flags = golden.split(": ", 1)[1].split()
-    assert flags == [f for f in build.HIPCC_FLAGS if f != "-shared"] + ["-fno-slp-vectorize"]
-    assert "-ffp-contract=off" in flags and "-fno-unroll-loops" in flags
-    monkeypatch.setenv("RT_EXTRA_HIPCC_FLAGS", "-DRT_PROFILE_TIME")
-    assert "-DRT_PROFILE_TIME" in build.flags_record() and build.record(lib) == golden
-    assert [build.record(o) for o in others if o is not build.PRODUCT] == before
-    monkeypatch.delenv("RT_EXTRA_HIPCC_FLAGS")
-    path = build.build_robust()
-    assert path == lib.path and path.exists() and not build.stale(lib) and lib.record_path.read_text() == golden
-
-
-def test_build_asks_for_the_robust_library_last(monkeypatch):
-    """build() with the recipe's steps replaced by recorders: FILM_LIBRARIES and the product as before, then ROBUST, compiled if it
-    is stale or the build forced, and left alone otherwise."""
-    for is_stale, force, compiled in ((True, False, True), (False, False, False), (False, True, True)):
-        asked = []
-        monkeypatch.setattr(build, "stale", lambda lib: asked.append(("stale", lib.path)) or is_stale)
-        monkeypatch.setattr(build, "compile_and_link", lambda lib, verbose=False: asked.append(("compile", lib.path)) or lib.path)
-        assert build.build(force=force) == build.LIB_PATH
-        paths = [*(l.path for l in build.FILM_LIBRARIES), build.LIB_PATH, build.ROBUST.path]
-        if force:
-            assert asked == [("compile", p) for p in paths]
-        else:
-            assert [p for w, p in asked if w == "stale"] == paths
-            assert [p for w, p in asked if w == "compile"] == (paths if compiled else [])
-        assert asked[-1] == ("compile" if compiled else "stale", build.ROBUST.path)
+    assert (_robust_lib.MIN_BUCKETS, _robust_lib.MAX_BUCKETS) == (3, 15)
 
 
 def test_the_binding_loads_the_library_and_refusals_are_statuses():

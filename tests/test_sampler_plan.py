@@ -1,14 +1,10 @@
 """The film sampler without a GPU (ray_tracer_s8_amd/film_sampler.py, _sampler_lib.py, build.py):
 1. check_sampler refuses, with ValueError, everything FilmSampler refuses, and accepts the rest;
 2. film_sampler.py and _sampler_lib.py import without torch and without loading the sampler library;
-3. librt_sampler.so exports exactly _sampler_lib.SIGNATURES, all rts_*, and the private header declares exactly those; no rts_ symbol is
-   in any other library, and there is no include/rt_sampler.h;
-4. the library is a fifth build.Library value: in PRIVATE_LIBRARIES and not in LIBRARIES, its record the golden one and the product's
-   flags plus -fno-slp-vectorize whatever RT_EXTRA_HIPCC_FLAGS says, its sources a dependency of no other library;
-5. every refusal of the library's calls comes back as a status, with no device bound.
+3. every refusal of the library's calls comes back as a status, with no device bound.
+What holds of every private library (a library of its own, its record, its exports, who builds it) is tests/test_private_libraries.py's.
 Without the feature every test here fails: there is no film_sampler, no _sampler_lib and no build.SAMPLER."""
 import ctypes as C
-import re
 import subprocess
 import sys
 import types
@@ -17,12 +13,9 @@ from pathlib import Path
 import pytest
 
 import ray_tracer_s8_amd as rt
-from ray_tracer_s8_amd import _abi, build
-
-import _surface
+from ray_tracer_s8_amd import _abi
 
 ROOT = Path(__file__).resolve().parent.parent
-GOLDEN = Path(__file__).resolve().parent / "golden" / "build_records"
 NAMES = ("rts_version", "rts_scratch_bytes", "rts_select", "rts_gather", "rts_fold", "rts_normalise")
 
 
@@ -83,12 +76,12 @@ import ray_tracer_s8_amd as rt
 import ray_tracer_s8_amd.film_sampler as fs
 import ray_tracer_s8_amd._sampler_lib as sl
 assert "torch" not in sys.modules
-assert sl._lib is None                                  # importing loads nothing
+assert not sl.BINDING.loaded                            # importing loads nothing
 assert callable(fs.check_sampler) and callable(fs.FilmSampler.begin) and callable(fs.FilmSampler.render_pass)
 assert callable(fs.FilmSampler.render) and callable(fs.FilmSampler.resolve_guided) and callable(fs.FilmSampler.variance)
 assert sorted(sl.SIGNATURES) == sorted(%r)
 fs.check_sampler(True)
-assert "torch" not in sys.modules and sl._lib is None
+assert "torch" not in sys.modules and not sl.BINDING.loaded
 print("ok")
 """ % (NAMES,)
 
@@ -101,60 +94,6 @@ def test_film_sampler_and_its_binding_import_without_torch():
 def test_abi_module_holds_nothing_of_the_sampler_library():
     names = [n for n in dir(_abi) if "rts_" in n.lower() or "sampler" in n.lower()]
     assert names == [], names
-
-
-def test_exports():
-    from ray_tracer_s8_amd import _sampler_lib
-    _abi.load()
-    _abi.load_debug()
-    declared = set(_surface.parse()["functions"])
-    assert len(declared) == 51 and _surface.exported(build.LIB_PATH) == declared
-    for path in (build.LIB_PATH, build.DEBUG_LIB_PATH, build.build_film(), build.build_history()):
-        assert not [s for s in _surface.all_exported(path) if "rts_" in s], path
-    sampler = {s for s in _surface.all_exported(build.build_sampler()) if not s.startswith("_")}
-    assert sampler == set(_sampler_lib.SIGNATURES) == set(NAMES) and all(s.startswith("rts_") for s in sampler), sampler
-    assert not _surface.exported(build.SAMPLER.path)                  # nothing of the tile ABI
-    # the private header declares exactly the functions the binding names
-    text = (build.SAMPLER.src_dir / "rt_sampler.h").read_text()
-    assert set(re.findall(r"^int (rts_\w+)\(", text, re.M)) == set(_sampler_lib.SIGNATURES)
-    assert not (ROOT / "include" / "rt_sampler.h").exists()
-    # and no other source of the package speaks of an rts_ name
-    for d in (build.CSRC, build.FILM_CSRC, build.HISTORY_CSRC, ROOT / "include"):
-        for f in d.rglob("*"):
-            if f.is_file():
-                assert "rts_" not in f.read_text(), f
-
-
-def test_the_sampler_is_a_fifth_library_beside_the_four(monkeypatch):
-    lib = build.SAMPLER
-    assert isinstance(lib, build.Library) and lib not in build.LIBRARIES and len(build.LIBRARIES) == 4
-    assert build.PRIVATE_LIBRARIES == (build.FILM, build.HISTORY, build.SAMPLER)
-    assert lib.path == build.LIB_DIR / "librt_sampler.so" and lib.obj_dir == build.LIB_DIR / "obj_sampler"
-    assert lib.path not in [o.path for o in build.LIBRARIES] and lib.obj_dir not in [o.obj_dir for o in build.LIBRARIES]
-    assert lib.units == (("rt_sampler.hip", ()),) and (lib.src_dir / "rt_sampler.hip").is_file()
-    for name in ("rt_sampler.h", "rt_sampler_math.h"):
-        assert (lib.src_dir / name).is_file()
-    # beside csrc/, a dependency of its own library and of no other; of csrc/ it takes nothing
-    assert lib.src_dir == build.PKG / "sampler_csrc" and build.CSRC not in lib.src_dir.parents
-    deps = build.dep_files(lib)
-    assert any(lib.src_dir in d.parents for d in deps) and Path(build.__file__) in deps
-    assert not [d for d in deps if d.parent == build.CSRC]
-    for other in build.LIBRARIES:
-        assert not any(lib.src_dir in d.parents for d in build.dep_files(other)), other.path
-        assert "rt_sampler" not in build.record(other)
-    # the record: the golden one, the product's flags plus -fno-slp-vectorize, never the experiments' flags
-    golden = (GOLDEN / "sampler.flags").read_text()
-    before = [build.record(o) for o in build.LIBRARIES if o is not build.PRODUCT]
-    assert build.record(lib) == golden and golden.startswith("rt_sampler.hip: ")
-    flags = golden.split(": ", 1)[1].split()
-    assert flags == [f for f in build.HIPCC_FLAGS if f != "-shared"] + ["-fno-slp-vectorize"]
-    assert "-ffp-contract=off" in flags and not any("correctly-rounded" in f or "fast-math" in f for f in flags)
-    monkeypatch.setenv("RT_EXTRA_HIPCC_FLAGS", "-DRT_PROFILE_TIME")
-    assert "-DRT_PROFILE_TIME" in build.flags_record() and build.record(lib) == golden
-    assert [build.record(o) for o in build.LIBRARIES if o is not build.PRODUCT] == before
-    monkeypatch.delenv("RT_EXTRA_HIPCC_FLAGS")
-    path = build.build_sampler()
-    assert path == lib.path and path.exists() and not build.stale(lib) and lib.record_path.read_text() == golden
 
 
 def test_the_binding_loads_the_library_and_refusals_are_statuses():

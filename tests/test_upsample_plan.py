@@ -1,15 +1,11 @@
 """The film upsampler without a GPU (ray_tracer_s8_amd/film_upsampler.py, _upsample_lib.py, build.py):
 1. check_upsample refuses, with ValueError, everything FilmUpsampler and upsample() refuse, and returns the plan of the rest;
 2. film_upsampler.py and _upsample_lib.py import without torch and without loading the library;
-3. librt_upsample.so exports exactly _upsample_lib.SIGNATURES, all rtu_*, and the private header declares exactly those; no rtu_ name is
-   in any other library or source directory, there is no include/rt_upsample.h, and _abi holds nothing of the library;
-4. the library is a build.Library value: a member of FILM_LIBRARIES, which build() makes, and of neither LIBRARIES nor
-   PRIVATE_LIBRARIES, which keep their values; its record is the golden one, the product's flags plus -fno-slp-vectorize whatever
-   RT_EXTRA_HIPCC_FLAGS says; its sources are a dependency of no other library, and of csrc/ it depends on the two headers it includes;
-5. every refusal of the library's call comes back as a status, with no device bound.
+3. _abi holds nothing of the library, and the binding has the version and the status table of this library;
+4. every refusal of the library's call comes back as a status, with no device bound.
+What holds of every private library (a library of its own, its record, its exports, who builds it) is tests/test_private_libraries.py's.
 Without the feature every test here fails: there is no film_upsampler, no _upsample_lib and no build.UPSAMPLE."""
 import ctypes as C
-import re
 import subprocess
 import sys
 import types
@@ -18,12 +14,9 @@ from pathlib import Path
 import pytest
 
 import ray_tracer_s8_amd as rt
-from ray_tracer_s8_amd import _abi, build
-
-import _surface
+from ray_tracer_s8_amd import _abi
 
 ROOT = Path(__file__).resolve().parent.parent
-GOLDEN = Path(__file__).resolve().parent / "golden" / "build_records"
 NAMES = ("rtu_version", "rtu_upsample")
 
 
@@ -116,12 +109,12 @@ def test_film_upsampler_runs_its_checks_before_anything_else():
     from ray_tracer_s8_amd import _upsample_lib
     film = types.SimpleNamespace(reqs=tuple(strips(24, 42, 3, (1, 2))))
     hi = strips(48, 84, 6, (2, 3, 4, 5))
-    loaded = _upsample_lib._lib
+    loaded = _upsample_lib.BINDING.loaded
     for f, h, kw in ((None, hi, {}), (film, strips(24, 42, 3, (1, 2)), {}), (film, hi, dict(k_depth=-1.0)), (film, hi, dict(eps=0.0)),
                      (film, hi, dict(k_normal=float("nan"))), (film, [], {})):
         with pytest.raises(ValueError):
             rt.FilmUpsampler(f, h, **kw)
-    assert _upsample_lib._lib is loaded
+    assert _upsample_lib.BINDING.loaded is loaded
 
 
 _IMPORT_CHILD = r"""
@@ -130,14 +123,14 @@ import ray_tracer_s8_amd as rt
 import ray_tracer_s8_amd.film_upsampler as fu
 import ray_tracer_s8_amd._upsample_lib as ul
 assert "torch" not in sys.modules
-assert ul._lib is None                                  # importing loads nothing
+assert not ul.BINDING.loaded                            # importing loads nothing
 assert callable(fu.check_upsample) and callable(fu.FilmUpsampler.features) and callable(fu.FilmUpsampler.upsample)
 assert callable(fu.FilmUpsampler.resolve) and callable(fu.FilmUpsampler.close)
 assert sorted(ul.SIGNATURES) == sorted(%r)
 lo = [rt.default_request(width=8, height=6, divisions=2, division_no=k, spp=2) for k in range(2)]
 hi = [rt.default_request(width=24, height=18, divisions=1, division_no=0, spp=1)]
 assert fu.check_upsample(lo, hi, ("hits",), ("hits",)).scale == 3
-assert "torch" not in sys.modules and ul._lib is None
+assert "torch" not in sys.modules and not ul.BINDING.loaded
 print("ok")
 """ % (NAMES,)
 
@@ -153,79 +146,11 @@ def test_abi_module_holds_nothing_of_the_upsample_library():
     assert _abi.RT_ABI_VERSION == 4
 
 
-def test_exports():
+def test_the_bindings_own_constants():
     from ray_tracer_s8_amd import _upsample_lib
-    _abi.load()
-    _abi.load_debug()
-    declared = set(_surface.parse()["functions"])
-    assert len(declared) == 51 and _surface.exported(build.LIB_PATH) == declared
-    for path in (build.LIB_PATH, build.DEBUG_LIB_PATH, build.build_film(), build.build_history(), build.build_sampler()):
-        assert not [s for s in _surface.all_exported(path) if "rtu_" in s], path
-    mine = {s for s in _surface.all_exported(build.build_upsample()) if not s.startswith("_")}
-    assert mine == set(_upsample_lib.SIGNATURES) == set(NAMES) and all(s.startswith("rtu_") for s in mine), mine
-    assert not _surface.exported(build.UPSAMPLE.path)                 # nothing of the tile ABI
-    # the private header declares exactly the functions the binding names, and the version the binding expects
-    text = (build.UPSAMPLE.src_dir / "rt_upsample.h").read_text()
-    assert set(re.findall(r"^int (rtu_\w+)\(", text, re.M)) == set(_upsample_lib.SIGNATURES)
-    assert re.search(r"^#define RTU_VERSION (\d+)u$", text, re.M).group(1) == str(_upsample_lib.RTU_VERSION) == "1"
-    status = dict((int(v), n) for n, v in re.findall(r"^#define (RTU_ERR_\w+) (\d+)", text, re.M))
-    assert status == _upsample_lib.STATUS and sorted(status) == [1, 2, 3, 4]
-    assert not (ROOT / "include" / "rt_upsample.h").exists()
-    # and no other source of the package speaks of an rtu_ name
-    for d in (build.CSRC, build.FILM_CSRC, build.HISTORY_CSRC, build.SAMPLER.src_dir, ROOT / "include"):
-        for f in d.rglob("*"):
-            if f.is_file():
-                assert "rtu_" not in f.read_text().lower(), f
-
-
-def test_the_upsampler_is_a_library_of_the_film_set(monkeypatch):
-    lib = build.UPSAMPLE
-    assert isinstance(lib, build.Library)
-    # the tuples the earlier tests pin keep their values; the new one holds them and this library
-    assert build.LIBRARIES == (build.PRODUCT, build.DEBUG, build.FILM, build.HISTORY)
-    assert build.PRIVATE_LIBRARIES == (build.FILM, build.HISTORY, build.SAMPLER)
-    assert build.FILM_LIBRARIES == (build.FILM, build.HISTORY, build.SAMPLER, build.UPSAMPLE)
-    assert lib not in build.LIBRARIES and lib not in build.PRIVATE_LIBRARIES
-    assert lib.path == build.LIB_DIR / "librt_upsample.so" and lib.obj_dir == build.LIB_DIR / "obj_upsample"
-    others = (*build.LIBRARIES, build.SAMPLER)
-    assert lib.path not in [o.path for o in others] and lib.obj_dir not in [o.obj_dir for o in others]
-    assert lib.units == (("rt_upsample.hip", ()),) and (lib.src_dir / "rt_upsample.hip").is_file()
-    for name in ("rt_upsample.h", "rt_upsample_math.h", "rt_upsample.hip.h"):
-        assert (lib.src_dir / name).is_file()
-    # beside csrc/: its own directory, the csrc/ headers it includes and no other, the C header, the recipe
-    assert lib.src_dir == build.PKG / "upsample_csrc" and build.CSRC not in lib.src_dir.parents
-    deps = build.dep_files(lib)
-    assert any(lib.src_dir in d.parents for d in deps) and Path(build.__file__) in deps
-    assert sorted(d.name for d in deps if d.parent == build.CSRC) == ["rt_consts.h", "rt_denoise_math.h"]
-    included = set()
-    for f in lib.src_dir.iterdir():
-        included |= set(re.findall(r'^#include "(\w+\.h)"', f.read_text(), re.M))
-    assert {n for n in included if (build.CSRC / n).exists()} == {"rt_consts.h", "rt_denoise_math.h"}
-    for other in others:
-        assert not any(lib.src_dir in d.parents for d in build.dep_files(other)), other.path
-        assert not any(other.src_dir in d.parents for d in deps if other.src_dir != build.CSRC), other.path
-        assert "rt_upsample" not in build.record(other)
-    # the record: the golden one, the product's flags plus -fno-slp-vectorize, never the experiments' flags
-    golden = (GOLDEN / "upsample.flags").read_text()
-    before = [build.record(o) for o in others if o is not build.PRODUCT]
-    assert build.record(lib) == golden and golden.startswith("rt_upsample.hip: ")
-    flags = golden.split(": ", 1)[1].split()
-    assert flags == [f for f in build.HIPCC_FLAGS if f != "-shared"] + ["-fno-slp-vectorize"]
-    assert "-ffp-contract=off" in flags and not any("correctly-rounded" in f or "fast-math" in f for f in flags)
-    monkeypatch.setenv("RT_EXTRA_HIPCC_FLAGS", "-DRT_PROFILE_TIME")
-    assert "-DRT_PROFILE_TIME" in build.flags_record() and build.record(lib) == golden
-    assert [build.record(o) for o in others if o is not build.PRODUCT] == before
-    monkeypatch.delenv("RT_EXTRA_HIPCC_FLAGS")
-    path = build.build_upsample()
-    assert path == lib.path and path.exists() and not build.stale(lib) and lib.record_path.read_text() == golden
-
-
-def test_build_makes_the_film_set(monkeypatch):
-    """build() goes over FILM_LIBRARIES: it asks for each of them, then for the product."""
-    asked = []
-    monkeypatch.setattr(build, "ensure", lambda lib, force=False, verbose=False: asked.append(lib.path) or lib.path)
-    build.build()
-    assert asked == [*(l.path for l in build.FILM_LIBRARIES), build.LIB_PATH]
+    assert _upsample_lib.RTU_VERSION == 1 and set(_upsample_lib.SIGNATURES) == set(NAMES)
+    assert _upsample_lib.STATUS == {1: "RTU_ERR_BAD_ARG", 2: "RTU_ERR_LIMIT", 3: "RTU_ERR_HIP", 4: "RTU_ERR_INTERNAL"}
+    assert (_upsample_lib.MIN_SCALE, _upsample_lib.MAX_SCALE) == (2, 4)
 
 
 def test_the_binding_loads_the_library_and_refusals_are_statuses():
