@@ -12,12 +12,14 @@ cut into passes or sub-ranges.  With integrator="path" that sum is the tile path
 
 With moments=True the film also keeps, per pixel, the sums S1 and S2 of the samples' y = (c0 + c1) + c2 and of y y, folded by a HIP
 kernel of the film library (lib/librt_film.so, film_csrc/) that replaces the torch fold, and resolve_guided() runs that
-library's variance-guided a-trous over accum and the moments.
+library's variance-guided a-trous over accum and the moments.  resolve_regression() runs that library's other kind of resolve, a local
+regression of the colour on the feature planes, with or without moments.
 
 This module imports without torch; torch is imported when a Film is constructed, and must have been imported before the library
 bound a HIP runtime (_abi.check_single_hip_runtime)."""
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import NamedTuple, Optional, Sequence
 
@@ -40,6 +42,16 @@ GUIDED_PLANES = ("normal", "depth", "hits")
 GUIDED_MAX_ITERATIONS = _film_lib.MAX_ITERATIONS
 SIGMA_L = 16.0
 VAR_EPS = 2.0 ** -8
+# resolve_regression: what it writes, the floats of a node's record, and the ridge of the fit, lambda n added to the
+# diagonal of every feature but the constant.  RIDGE: measured on the grid 1e-5 ... 1e-1 on c2 and c3 (4.31 "Measured").  The grid has
+# no single best: at 8 and at 32 samples the error is flat from 1e-5 to 1e-3, and which end is ahead, by under 2 %, changes with the
+# scene and the planes; 1e-4 is the middle of that stretch and within 2 % of the least error of each of those rows.  At 2 samples on c2
+# the other end, 1e-1, is better by a quarter.  In f32 a ridge of 1e-7 and below loses the pivots of collinear features (a flat wall's
+# normal) to rounding, so the default keeps three decades above that.
+REGRESSION_OUTPUTS = ("rgb", "linear", "f32")
+REGRESSION_RECORD = _film_lib.REGRESS_RECORD
+REGRESSION_PITCH = 16
+RIDGE = 1e-4
 
 # every field of a request but division_no: what the strips of one frame agree on
 _FRAME_FIELDS = tuple(n for n, _ in TileRequest._fields_ if n != "division_no")
@@ -139,6 +151,37 @@ def check_guided(moments: bool, samples: int, planes: Sequence[str] = (), output
     return tuple(n for n in GUIDED_PLANES if n in names), outs
 
 
+def check_regression(samples: int, planes: Sequence[str] = (), outputs: Sequence[str] = ("rgb",), ridge: float = RIDGE,
+                     albedo_eps: Optional[float] = None) -> tuple:
+    """The checks of resolve_regression's arguments, all of them ValueError and none of them a GPU call.  planes: the names of the
+    planes given (index is ignored).  Returns (planes, outputs) as tuples, the planes in FEATURE_PLANES' order.  Pure: no torch, no
+    GPU."""
+    if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
+        raise ValueError(f"the film holds {samples!r} samples: a fit needs at least 1")
+    outs = tuple(outputs)
+    if not outs or any(o not in REGRESSION_OUTPUTS for o in outs) or len(set(outs)) != len(outs):
+        raise ValueError(f"outputs: a non-empty subset of {REGRESSION_OUTPUTS}, got {outs}")
+    names = tuple(n for n in planes if n != "index")
+    if any(n not in FEATURE_PLANES for n in names):
+        raise ValueError(f"planes: a subset of {FEATURE_PLANES}, got {names}")
+    if "depth" in names and "hits" not in names:
+        raise ValueError("planes: the depth plane needs the hits plane")
+    for name, v in (("ridge", ridge),) + ((("albedo_eps", albedo_eps),) if albedo_eps is not None else ()):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{name}: a finite number > 0, got {v!r}")
+        as_f32 = ctypes.c_float(v).value
+        if not (as_f32 > 0 and math.isfinite(as_f32)):
+            raise ValueError(f"{name}: finite and > 0 as a float32, got {v!r}")
+    return tuple(n for n in FEATURE_PLANES if n in names), outs
+
+
+def regression_nodes(width: int, rows: int) -> tuple:
+    """(NY, NX) of the regression resolve's nodes on a width x rows image: one every 16 pixels, and one past each edge.  Pure."""
+    if width < 1 or rows < 1:
+        raise ValueError("width and rows must be at least 1")
+    return (rows - 1) // REGRESSION_PITCH + 2, (width - 1) // REGRESSION_PITCH + 2
+
+
 def _add_stats(total: TileStats, st: TileStats) -> None:
     for f in _SUMMED_STATS:
         setattr(total, f, getattr(total, f) + getattr(st, f))
@@ -210,6 +253,8 @@ class Film:
             self.moments = torch.zeros((self.rows, self.width, 2), dtype=torch.float32, device=self.device) if moments else None
         self._guided_scratch = None
         self._guided_out: dict = {}
+        self.regression_model = None
+        self._regression_out: dict = {}
         self._taps: list = []                     # what is shown every strip's records after their fold (film_robust.py)
 
     # ---- the film's own state
@@ -269,8 +314,8 @@ class Film:
             return
         self.sync()
         self.accum = self._rays = self._states = self._rgb = self._scratch = None
-        self.moments = self._guided_scratch = None
-        self.planes, self._out, self._guided_out = {}, {}, {}
+        self.moments = self._guided_scratch = self.regression_model = None
+        self.planes, self._out, self._guided_out, self._regression_out = {}, {}, {}, {}
 
     def __enter__(self):
         return self
@@ -486,3 +531,46 @@ class Film:
         guide = self._check_planes({n: given[n] for n in names})
         return self._guided(guide, outs, iterations, float(sigma_l), float(var_eps), float(k_normal), float(k_depth), _lds_max_step,
                             _state)
+
+    # ---- the regression resolve
+
+    def resolve_regression(self, planes: Optional[dict] = None, outputs: Sequence[str] = ("rgb",), ridge: float = RIDGE,
+                           albedo_eps: Optional[float] = None, _state: Optional[tuple] = None) -> dict:
+        """The local feature regression over all strips as one image (rtf_resolve, kind 1): around a node every 16
+        pixels the colour is fitted, over a 32 x 32 window, as a linear function of eight features of the planes (1, the unit normal,
+        the window's normalised depth and its square, the position in the window), by ridge-regularised least squares, and a pixel
+        takes the bilinear blend of its four nodes' fits.  planes: what features() returned or a part of it out of albedo (the colour
+        is then fitted demodulated), normal, depth (needs hits) and hits, or None; index is ignored.  outputs: a non-empty subset of
+        ("rgb", "linear", "f32").  albedo_eps: None for DenoiseRequest.defaults()'s.  Returns {output: tensor} in resolve()'s layout:
+        the film's own tensors, written again by the next call, as regression_model is, the (NY, NX, 32) float32 records of the fit.
+        Needs samples >= 1; works without moments (the film library is loaded here if the film did not load it).  _state: as
+        resolve()'s (its moments are not read)."""
+        self._check_open()
+        torch = self._torch
+        given = {n: t for n, t in (planes or {}).items() if t is not None}
+        names, outs = check_regression(self.samples, tuple(given), outputs, ridge, albedo_eps)
+        guide = self._check_planes({n: given[n] for n in names})
+        if albedo_eps is None:
+            albedo_eps = DenoiseRequest.defaults().albedo_eps
+        accum = self.accum if _state is None else _state[0]
+        if self._film_lib is None:
+            self._film_lib = _film_lib.load()
+        NY, NX = regression_nodes(self.width, self.rows)
+        with torch.cuda.stream(self.stream):
+            if self.regression_model is None:
+                self.regression_model = torch.zeros((NY, NX, REGRESSION_RECORD), dtype=torch.float32, device=self.device)
+            for o in outs:
+                if o not in self._regression_out:
+                    self._regression_out[o] = torch.empty((self.rows, self.width, 3), dtype=torch.uint8 if o == "rgb" else torch.float32,
+                                                          device=self.device)
+            ptr = lambda d, k: d[k].data_ptr() if k in d else None
+            out = {o: self._regression_out[o] for o in outs}
+            model = self.regression_model
+            a = _film_lib.ResolveArgs(W=self.width, R=self.rows, samples=self.samples, kind=_film_lib.RESOLVE_REGRESS,
+                                      accum=accum.data_ptr(), normal=ptr(guide, "normal"), depth=ptr(guide, "depth"),
+                                      hits=ptr(guide, "hits"), out_rgb=ptr(out, "rgb"), out_f32=ptr(out, "f32"),
+                                      out_linear=ptr(out, "linear"), albedo=ptr(guide, "albedo"),
+                                      aov_samples=self.aov_samples if guide else 0, albedo_eps=float(albedo_eps), ridge=float(ridge),
+                                      model=model.data_ptr(), model_bytes=model.numel() * 4)
+            _film_lib.check("rtf_resolve", self._film_lib.rtf_resolve(a, self.stream.cuda_stream))
+        return out

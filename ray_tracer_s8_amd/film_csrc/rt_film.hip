@@ -33,6 +33,53 @@ int check_image(uint32_t W, uint32_t R) {
     return RTF_OK;
 }
 
+// the appended fields of rtf_resolve_args, which kind 0 leaves at 0
+bool regress_fields_unset(const rtf_resolve_args* a) {
+    return !a->albedo && a->aov_samples == 0 && a->albedo_eps == 0.0f && a->ridge == 0.0f && a->reserved == 0 && !a->model &&
+           a->model_bytes == 0;
+}
+
+// kind RTF_RESOLVE_REGRESS: the fit, a workgroup per node, then the apply, a lane per pixel
+int resolve_regress(const rtf_resolve_args* a, void* stream) {
+    if (a->samples < 1 || a->iterations != 0 || a->out_variance || a->reserved != 0) return RTF_ERR_BAD_ARG;
+    if (!a->out_rgb && !a->out_f32 && !a->out_linear) return RTF_ERR_BAD_ARG;
+    if (!a->accum || !a->model || misaligned(a->model, 16)) return RTF_ERR_BAD_ARG;
+    if (!std::isfinite(a->ridge) || !(a->ridge > 0.0f)) return RTF_ERR_BAD_ARG;
+    if (a->depth && !a->hits) return RTF_ERR_BAD_ARG;
+    if (a->albedo && (!std::isfinite(a->albedo_eps) || !(a->albedo_eps > 0.0f))) return RTF_ERR_BAD_ARG;
+    if ((a->albedo || a->normal || a->depth || a->hits) && a->aov_samples < 1) return RTF_ERR_BAD_ARG;
+    const uint32_t NX = rtfm::rg_nodes(a->W), NY = rtfm::rg_nodes(a->R);
+    const uint64_t nodes = (uint64_t)NX * NY;
+    if (nodes > 0x7FFFFFFFull) return RTF_ERR_LIMIT;
+    if (a->model_bytes < nodes * rtfm::RG_RECORD * sizeof(float)) return RTF_ERR_SCRATCH;
+    hipStream_t st = (hipStream_t)stream;
+
+    rtfk::RegressParams p;
+    std::memset(&p, 0, sizeof p);
+    p.W = a->W;
+    p.R = a->R;
+    p.NX = NX;
+    p.NY = NY;
+    p.ridge = a->ridge;
+    p.pl.accum = a->accum;
+    p.pl.albedo = a->albedo;
+    p.pl.normal = a->normal;
+    p.pl.depth = a->depth;
+    p.pl.hits = a->hits;
+    p.pl.e_f = (float)a->samples;
+    p.pl.k_f = (float)a->aov_samples;
+    p.pl.albedo_eps = a->albedo_eps;
+    p.model = a->model;
+    p.rgb = a->out_rgb;
+    p.f32 = a->out_f32;
+    p.lin = a->out_linear;
+    hipLaunchKernelGGL(rtfk::rtf_regress_fit_kernel, dim3((uint32_t)nodes), dim3(rtfk::RG_BLOCK), 0, st, p);
+    if (int rc = after_launch(RTF_OK, RTF_ERR_HIP)) return rc;
+    const uint64_t npix = (uint64_t)a->W * a->R;
+    hipLaunchKernelGGL(rtfk::rtf_regress_apply_kernel, dim3((uint32_t)((npix + rtfk::BLOCK - 1) / rtfk::BLOCK)), dim3(rtfk::BLOCK), 0, st, p);
+    return after_launch(RTF_OK, RTF_ERR_HIP);
+}
+
 }  // namespace
 
 RT_PRIVATE_EXPORT int rtf_version(uint32_t* version) {
@@ -66,7 +113,9 @@ RT_PRIVATE_EXPORT int rtf_resolve(const rtf_resolve_args* a, void* stream) {
     return guarded<RTF_ERR_INTERNAL>([&] {
         if (!a) return RTF_ERR_BAD_ARG;
         if (int rc = check_image(a->W, a->R)) return rc;
-        if (a->samples < 2 || a->iterations > RTF_MAX_ITERATIONS || a->reserved != 0) return RTF_ERR_BAD_ARG;
+        if (a->kind == RTF_RESOLVE_REGRESS) return resolve_regress(a, stream);
+        if (a->kind != RTF_RESOLVE_ATROUS || !regress_fields_unset(a)) return RTF_ERR_BAD_ARG;
+        if (a->samples < 2 || a->iterations > RTF_MAX_ITERATIONS) return RTF_ERR_BAD_ARG;
         if (!finite_nonneg(a->sigma_l) || !finite_nonneg(a->k_normal) || !finite_nonneg(a->k_depth)) return RTF_ERR_BAD_ARG;
         if (!std::isfinite(a->var_eps) || !(a->var_eps > 0.0f)) return RTF_ERR_BAD_ARG;
         if (!a->accum || !a->moments || !a->scratch) return RTF_ERR_BAD_ARG;

@@ -8,7 +8,12 @@
 //   - step<LDS, FINAL>: one iteration on the pattern of csrc/rt_denoise.hip.h, 64 x 4 tiles, the (64 + 4s) x (4 + 4s) window of
 //     records (and guides) staged in LDS or each tap a float4 load; the prefilter's distance-1 taps lie inside the window for every
 //     s >= 1.  FINAL writes the outputs itself;
-//   - output: iterations == 0 — r0, v0 to the outputs.
+//   - output: iterations == 0 — r0, v0 to the outputs;
+//   - regress fit: a workgroup of 1024 lanes per node, a lane per pixel of its 32 x 32 window (lane l = 32 wy + wx, so a wave is two
+//     window rows and the group k of rt_film.h's window sum).  The count, zlo and zhi first, then the 60 window sums: each the xor
+//     butterfly of a wave, the sixteen wave totals through LDS, added in order by one lane.  The sums, the Cholesky factor and the
+//     record stay in LDS; lane 0 factors, lanes 0 ... 2 solve a channel each, 32 lanes store the record;
+//   - regress apply: a lane per pixel; it reads its four nodes' records, which the cache holds (128 B a node).
 // The film's planes are whole-frame contiguous: one pointer per plane.  Taps outside P are skipped before any load, so no lane reads
 // outside the image; out-of-image lanes of a tile only help stage.
 #pragma once
@@ -166,6 +171,113 @@ __global__ __launch_bounds__(256) void rtf_output_kernel(const ResolveParams p) 
         const float r[4] = {c.x, c.y, c.z, c.w};
         rtf_write(p, g, r);
     }
+}
+
+// ---- the regression resolve ---------------------------------------------------------------------------------------
+struct RegressParams {
+    uint32_t W, R, NX, NY;
+    float ridge;
+    rtfm::RgPlanes pl;
+    float* model;                // [NY*NX*32]
+    uint8_t* rgb;                // outputs or nullptr
+    float* f32;
+    float* lin;
+};
+
+constexpr uint32_t RG_BLOCK = 1024, RG_WAVES = 16;
+
+// the adjacent-pair tree over a wave's 64 values, in every lane: level 0 adds lanes 2m and 2m + 1, f32 addition commutes
+__device__ __forceinline__ float rtf_wave_tree(float v) {
+    RT_DN_UNROLL
+    for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(1024) void rtf_regress_fit_kernel(const RegressParams p) {
+    __shared__ float part[rtfm::RG_NS][RG_WAVES];
+    __shared__ float S[rtfm::RG_NS];
+    __shared__ float L[rtfm::RG_M * rtfm::RG_M];
+    __shared__ __attribute__((aligned(16))) float rec[rtfm::RG_RECORD];
+    __shared__ float wlo[RG_WAVES], whi[RG_WAVES];
+    __shared__ uint32_t wn[RG_WAVES];
+    __shared__ uint32_t fit_ok;
+    const uint32_t node = blockIdx.x;
+    const int j = (int)(node / p.NX), i = (int)(node - (uint32_t)j * p.NX);
+    const uint32_t l = threadIdx.x, wave = l >> 6, lane = l & 63u;
+    const int x = rtfm::RG_T * i - rtfm::RG_T + (int)(l & 31u), y = rtfm::RG_T * j - rtfm::RG_T + (int)(l >> 5);
+    const bool inside = x >= 0 && x < (int)p.W && y >= 0 && y < (int)p.R;
+    rtfm::RgPixel px;
+    px.r[0] = px.r[1] = px.r[2] = 0.0f;
+    px.g = {0.0f, 0.0f, 0.0f, -1.0f};
+    px.z = 0.0f;
+    px.valid = false;
+    if (inside) px = rtfm::rg_entry(p.pl, (size_t)y * p.W + (size_t)x);
+    const bool valid = inside && px.valid;
+    // the window's count, zlo and zhi: z is never a NaN and never -0, so min and max by comparison are those of the text
+    float lo = valid ? px.z : __builtin_inff(), hi = valid ? px.z : 0.0f;
+    RT_DN_UNROLL
+    for (int m = 1; m < 64; m <<= 1) {
+        const float ol = __shfl_xor(lo, m, 64), oh = __shfl_xor(hi, m, 64);
+        lo = ol < lo ? ol : lo;
+        hi = oh > hi ? oh : hi;
+    }
+    const uint32_t cnt = (uint32_t)__popcll(__ballot(valid));
+    if (lane == 0) {
+        wlo[wave] = lo;
+        whi[wave] = hi;
+        wn[wave] = cnt;
+    }
+    __syncthreads();
+    uint32_t n = 0;
+    float zlo = __builtin_inff(), zhi = 0.0f;
+    for (uint32_t k = 0; k < RG_WAVES; k++) {
+        n += wn[k];
+        zlo = wlo[k] < zlo ? wlo[k] : zlo;
+        zhi = whi[k] > zhi ? whi[k] : zhi;
+    }
+    if (n == 0u || !p.pl.depth) zlo = zhi = 0.0f;
+    const float s = zhi - zlo;
+    float phi[rtfm::RG_M];
+    rtfm::rg_features(px, x, y, i, j, zlo, s, phi);
+    // the window sums: A_ab, a <= b, then B_ac
+    RT_DN_UNROLL
+    for (int a = 0; a < rtfm::RG_M; a++) {
+        RT_DN_UNROLL
+        for (int b = a; b < rtfm::RG_M; b++) {
+            const float t = rtf_wave_tree(valid ? phi[a] * phi[b] : 0.0f);
+            if (lane == 0) part[rtfm::rg_ai(a, b)][wave] = t;
+        }
+        RT_DN_UNROLL
+        for (int c = 0; c < 3; c++) {
+            const float t = rtf_wave_tree(valid ? phi[a] * px.r[c] : 0.0f);
+            if (lane == 0) part[rtfm::RG_NA + 3 * a + c][wave] = t;
+        }
+    }
+    __syncthreads();
+    if (l < (uint32_t)rtfm::RG_NS) {
+        float t = 0.0f;
+        for (uint32_t k = 0; k < RG_WAVES; k++) t = t + part[l][k];
+        S[l] = t;
+    }
+    __syncthreads();
+    if (l == 0) fit_ok = rtfm::rg_cholesky(S, n, p.ridge, L) ? 1u : 0u;
+    __syncthreads();
+    const bool ok = fit_ok != 0u;
+    if (l < 3u) rtfm::rg_solve(S, n, ok, L, (int)l, rec);
+    if (l == 3u) rtfm::rg_record_tail(n, zlo, s, ok, rec);
+    __syncthreads();
+    if (l < (uint32_t)rtfm::RG_RECORD) p.model[(size_t)node * rtfm::RG_RECORD + l] = rec[l];
+}
+
+__global__ __launch_bounds__(256) void rtf_regress_apply_kernel(const RegressParams p) {
+    const uint64_t g = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (g >= (uint64_t)p.R * p.W) return;
+    const int y = (int)(g / p.W), x = (int)(g - (uint64_t)y * p.W);
+    const rtfm::RgPixel px = rtfm::rg_entry(p.pl, (size_t)g);
+    float r[3] = {px.r[0], px.r[1], px.r[2]};
+    if (px.valid) rtfm::rg_apply(px, x, y, p.model, p.NX, r);
+    rtdn::output_pixel(r, p.pl.albedo ? px.d : nullptr, p.lin ? p.lin + g * 3 : nullptr, p.f32 ? p.f32 + g * 3 : nullptr,
+                       p.rgb ? p.rgb + g * 3 : nullptr);
 }
 
 }  // namespace rtfk
