@@ -1,5 +1,5 @@
 """What the bindings of the private libraries (_film_lib.py, _history_lib.py, _sampler_lib.py, _upsample_lib.py, _robust_lib.py,
-_display_lib.py) share: one Binding each, which owns the status error, the check and the lazy load.
+_display_lib.py, and _jpeg_lib.py, whose library build.JPEG is held beside build.PRIVATE) share: one Binding each, which owns the status error, the check and the lazy load.
 
 A private library is a member of build.PRIVATE beside the product, no part of the tile ABI (include/rt_tile.h, _abi.py): every
 function of it returns an int status, and one of them, <prefix>_version(uint32_t*), reports the version its binding must match.  This
@@ -55,6 +55,6 @@ class Binding:
             if v.value != self.version:
                 key = self.library.src_dir.name.removesuffix("_csrc")
                 raise RuntimeError(f"{path} is version {v.value}, this binding is version {self.version}: rebuild it "
-                                   f'(build.ensure(build.PRIVATE["{key}"]))')
+                                   f"(build.ensure(build.{key.upper()}, force=True))")
             self._lib = lib
         return self._lib

@@ -121,6 +121,10 @@ PRIVATE = {
 }
 FILM, HISTORY, SAMPLER, UPSAMPLE, ROBUST, DISPLAY = PRIVATE.values()
 
+# The JPEG library (baseline JPEG encoding of a device frame, 4.32; rtj_*): a private library by the same recipe, held beside PRIVATE:
+# build() leaves it to its binding (_jpeg_lib.py builds a missing one on load), the driver's build() and `python -m` make it.
+JPEG = _private("jpeg", ())
+
 
 def _product(extra: list[str] | None = None) -> Library:
     """The product as asked for NOW: RT_EXTRA_HIPCC_FLAGS (experiments only, e.g. -DRT_MAXC=12) is read at every call.  A prebuilt
@@ -217,5 +221,5 @@ def build_debug(force: bool = False, verbose: bool = False) -> Path:
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
     if not VARIANT:
-        for lib in (DEBUG, *PRIVATE.values()):          # (the private ones were forced by build())
-            print(ensure(lib, force=lib is DEBUG, verbose=True))
+        for lib in (DEBUG, JPEG, *PRIVATE.values()):    # (the private ones were forced by build())
+            print(ensure(lib, force=lib is DEBUG or lib is JPEG, verbose=True))
