@@ -82,6 +82,19 @@ namespace rtk {
 #ifndef RT_LT_EAGER             // culled LDS-tree kernel: lanes with candidates but no hit yet that make a partial root-test round
 #define RT_LT_EAGER 12
 #endif
+// Round 6: per-round work of the LDS-tree kernels that a plain frame does not need; 0 restores the parent's code (A/B)
+#ifndef RT_R6_STEP1             // the first step of a block stays inside its variant (slow / fast) instead of being shared by both
+#define RT_R6_STEP1 1
+#endif
+#ifndef RT_R6_ADDR              // stack top, list end and list head live as LDS addresses across the whole closest-hit loop
+#define RT_R6_ADDR 1
+#endif
+#ifndef RT_R6_DELTA             // the stack pointer's step is the sum of two selects, each on the mask its compare wrote
+#define RT_R6_DELTA 1
+#endif
+#ifndef RT_R6_HEAD              // the head of a block of steps: what does not change during a round is formed once per round
+#define RT_R6_HEAD 1
+#endif
 
 // ---- Sample units (round 4).  The unit of work a lane takes is ONE SAMPLE of a pixel.  A wave keeps up to
 // n_slots PIXEL SLOTS; a slot holds a group of `grp` neighbouring pixels of a tile (one pixel from 8 samples per pixel up) = grp x spp
@@ -831,11 +844,29 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
     float t_far = __builtin_inff();          // CULL: no primitive entered beyond this distance can beat the running hit
     uint32_t* lc32 = reinterpret_cast<uint32_t*>(lds_raw + p.lds_cand_off);     // TRAVERSE: leaf candidates (u32)
     uint32_t* lstack = reinterpret_cast<uint32_t*>(lds_raw + p.lds_stack_off);   // TRAVERSE: per-lane stack
-    uint32_t sgx = 0, sgy = 0, sgz = 0;      // LTREE: (direction.axis < 0) of the current query, ray.rs:139-141
+    uint32_t sgx = 0, sgy = 0, sgz = 0;      // LTREE: (direction.axis < 0) of the current query, ray.rs:139-141 (ADDR: times 4)
     uint16_t* lc16 = reinterpret_cast<uint16_t*>(lds_raw + p.lds_cand_off);     // LTREE: both 16-bit
     uint16_t* lstack16 = reinterpret_cast<uint16_t*>(lds_raw + p.lds_stack_off);
 
     if (BFSTEP) lstack16[tid16] = (uint16_t)(lt_r0(p.n_internal) + p.n_internal * (uint32_t)LNODE_DW);  // stack slot 0: popping an empty stack yields DONE
+    // LTREE: the lane's stack and leaf-list columns as LDS byte addresses (the branch-free step reads and writes through a register plus
+    // an immediate offset).  top_a: the lane's top stack slot; cnt_m: one slot below the lane's next list slot; head_m: one slot below
+    // its first entry not root-tested yet.  Round 6 (RT_R6_ADDR): these three ARE the walk's state from the query's start to its last
+    // root test — the block of steps, the fullness test, the partial rounds and the flushes all work on addresses, and the indexes
+    // t_sp / t_cnt / t_head (formed before every block and taken back after it: a shift, three adds and two v_lshl_add, then two subs,
+    // an add and two shifts) are not carried by these kernels at all.
+    constexpr bool ADDR = BFSTEP && (RT_R6_ADDR != 0);
+    // (addresses are compared as unsigned numbers, so list0_m must not wrap below zero: the dynamic area lies behind the static one,
+    // and wave_q alone is a slot long — whatever lds_cand_off is, two spheres' tree included)
+    static_assert(!ADDR || sizeof(WaveQ) * (BS / 64) >= (size_t)BLOCK * 2u, "list0_m = lds0 + ... - SLOT must not wrap");
+    constexpr uint32_t SLOT = (uint32_t)BLOCK * 2u;      // bytes between two slots of a lane's column
+    typedef __attribute__((address_space(3))) unsigned char lds_byte;
+    typedef __attribute__((address_space(3))) uint16_t lds_u16;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_byte*)lds_raw;               // LDS address of the dynamic area
+    const uint32_t stack0_a = lds0 + p.lds_stack_off + (uint32_t)tid16 * 2u;     // slot 0 (DONE) of this lane
+    const uint32_t list0_m = lds0 + p.lds_cand_off + (uint32_t)tid16 * 2u - SLOT; // one slot below list slot 0
+    uint32_t top_a = 0, cnt_m = list0_m, head_m = list0_m;
+    auto lds16 = [&](uint32_t a) -> lds_u16& { return *(lds_u16*)(uintptr_t)a; };
 
     auto drain_counters = [&]() {
         const unsigned long long ws = wave_sum(n_seg), wc = wave_sum(n_cand), wf = wave_sum(n_fall);
@@ -1304,9 +1335,9 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                 // advisor: an origin at infinity, (-inf - o) * inv = NaN, would otherwise pop below slot 0)
                 aux.finite = aux.finite && __builtin_fabsf(o.x) < __builtin_inff() && __builtin_fabsf(o.y) < __builtin_inff() &&
                              __builtin_fabsf(o.z) < __builtin_inff();
-                sgx = aux.sx ? 1u : 0u;
-                sgy = aux.sy ? 1u : 0u;
-                sgz = aux.sz ? 1u : 0u;
+                sgx = aux.sx ? (ADDR ? 4u : 1u) : 0u;        // (ADDR: in bytes, as the step adds them: no shift per block of steps)
+                sgy = aux.sy ? (ADDR ? 4u : 1u) : 0u;
+                sgz = aux.sz ? (ADDR ? 4u : 1u) : 0u;
             }
             if (CULL) {
                 // spheres too large for the culling slack (a ground sphere) are root-tested here, under the same candidate
@@ -1329,8 +1360,13 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
             }
             if (TRAVERSE) {
                 t_ref = p.root_ref;
+                if (ADDR) {
+                    top_a = stack0_a;                        // (stack pointer 1, list empty: see below)
+                    cnt_m = list0_m;
+                } else {
                 t_sp = BFSTEP ? 1u : 0u;                     // slot 0 of the branch-free step's stack holds the DONE sentinel
                 t_cnt = 0;
+                }
                 in_trav = (p.n_sph + p.n_tri) > 0;
             }
         }
@@ -1341,9 +1377,10 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
             // exact root tests on them, first minimum wins (shapes/mod.rs:158-191).
             // Steps run until at most half of the wave's live lanes are still walking; the finished lanes are then
             // shaded / refilled while the stragglers keep their stack (LDS) and resume in the next round.
-            auto root_test = [&](uint32_t i) {
+            auto root_test = [&](uint32_t i) {                     // (ADDR: i is the entry's address in the form of cnt_m / head_m)
                     LCOUNT(6);
-                    const uint32_t prim = LTREE ? (uint32_t)lc16[i * BLOCK + tid16] & 0x7fffu
+                    const uint32_t prim = ADDR ? (uint32_t)lds16(i + SLOT) & 0x7fffu
+                                          : LTREE ? (uint32_t)lc16[i * BLOCK + tid16] & 0x7fffu
                                           : p.list16 ? (uint32_t)lc16[i * BLOCK + tid16] : lc32[i * BLOCK + tid];
                     float t;
                     // The quantised walk only over-approximates BVH::traverse, so a leaf it delivers counts iff
@@ -1379,6 +1416,14 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                     }
             };
             auto flush = [&]() {
+                if (ADDR) {                                      // (the same rounds over the same entries, counted by address)
+                    n_cand += (cnt_m - head_m) / SLOT;
+#pragma clang loop unroll(disable)
+                    for (uint32_t a = head_m; a < cnt_m; a += SLOT) root_test(a);
+                    cnt_m = head_m = list0_m;
+                    if (CULL && h.idx >= 0) t_far = far_bound(h.dist);
+                    return;
+                }
                 if (BFSTEP) n_cand += t_cnt - t_head;            // (the other steps count at the append)
                 // (Tried in round 3 and dropped on the LDS-tree kernel, tools/experiments/: striking the sure misses from the leaf
                 // lists first with the linear engines' conservative broad-phase test, r03_leaf_prefilter.patch, c3 14 560 -> 14 290;
@@ -1396,9 +1441,15 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
             // LTREE: one root test for every lane with a pending candidate, its oldest (list order kept: first minimum wins)
             auto flush_one = [&]() {
                 n_cand++;
+                if (ADDR) {
+                    root_test(head_m);
+                    head_m += SLOT;
+                    if (head_m == cnt_m) head_m = cnt_m = list0_m;
+                } else {
                 root_test(t_head);
                 t_head++;
                 if (t_head == t_cnt) t_head = t_cnt = 0;
+                }
                 if (CULL && h.idx >= 0) t_far = far_bound(h.dist);
             };
 
@@ -1544,14 +1595,7 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
             // Inside a block the stack pointer and the list length are carried as LDS byte addresses (top_a: the lane's top
             // stack slot; cnt_m: one slot below the lane's next list slot), so that the three accesses of a step are a
             // register plus an immediate offset: no index arithmetic in the step.
-            constexpr uint32_t SLOT = (uint32_t)BLOCK * 2u;      // bytes between two slots of a lane's column
-            typedef __attribute__((address_space(3))) unsigned char lds_byte;
-            typedef __attribute__((address_space(3))) uint16_t lds_u16;
-            const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_byte*)lds_raw;               // LDS address of the dynamic area
-            const uint32_t stack0_a = lds0 + p.lds_stack_off + (uint32_t)tid16 * 2u;     // slot 0 (DONE) of this lane
-            const uint32_t list0_m = lds0 + p.lds_cand_off + (uint32_t)tid16 * 2u - SLOT; // one slot below list slot 0
-            uint32_t top_a = 0, cnt_m = 0;
-            auto lds16 = [&](uint32_t a) -> lds_u16& { return *(lds_u16*)(uintptr_t)a; };
+            // (SLOT, stack0_a, list0_m, top_a, cnt_m, head_m, lds16: with the per-lane state above the loop)
             auto step = [&](auto slow_tag) {
                 constexpr bool SLOW = decltype(slow_tag)::value;
                 // the leaf flag (bit 15) moved to the weight of one list slot: two fast-class instructions (shift right, and) where
@@ -1567,9 +1611,12 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                 lds16(cnt_m + SLOT) = (uint16_t)t_ref;                           // (the flush masks the leaf flag off)
                 // Ray::intersects_aabb (ray.rs:174-194) on both child boxes; (near, far) planes fetched by sign
                 const float* __restrict__ nd = lnodes + ni;
-                const float* __restrict__ fx = nd + sgx;
-                const float* __restrict__ fy = nd + 6 + sgy;
-                const float* __restrict__ fz = nd + 12 + sgz;
+                auto plane = [&](const float* q, uint32_t sg) -> const float* {
+                    return ADDR ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(q) + sg) : q + sg;
+                };
+                const float* __restrict__ fx = plane(nd, sgx);
+                const float* __restrict__ fy = plane(nd + 6, sgy);
+                const float* __restrict__ fz = plane(nd + 12, sgz);
                 const float p0 = fx[0], p1 = fx[1], p2 = fx[3], p3 = fx[4], p4 = fy[0], p5 = fy[1], p6 = fy[3], p7 = fy[4];
                 const float p8 = fz[0], p9 = fz[1], p10 = fz[3], p11 = fz[4];
                 const uint32_t refs = __float_as_uint(nd[18]);
@@ -1612,26 +1659,45 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                 lds16(top_a + SLOT) = (uint16_t)cr;                // right subtree after the whole left subtree (CULL: the farther one)
                 const bool any = hl || hr;
                 t_ref = any ? (hl ? cl : cr) : top;
+#if RT_R6_DELTA
+                // round 6: -SLOT unless the left box is entered, +SLOT if the right one is — two selects, each on the mask its compare
+                // wrote, and a fast-class add (kept apart from the next one by the asm below: together they were a v_add3); the
+                // parent's form needed the scalar or and and of the two masks in every step
+                uint32_t delta = (hl ? 0u : 0u - SLOT) + (hr ? SLOT : 0u);
+#else
                 uint32_t delta = any ? 0u : 0u - SLOT;             // (two selects and a fast-class add; the sum of two selects was a v_add3)
                 delta = (hl && hr) ? SLOT : delta;
+#endif
                 asm volatile("" : "+v"(delta));
                 top_a += delta;
                 if (SLOW) top_a = max(top_a, stack0_a);          // (DONE may pop here: see above)
                 cnt_m += leaf_slot;
                 RT_HOOK_LT_STEP_END;
             };
+            // Round 6 (RT_R6_HEAD): the head of a block.  Neither the live lanes, nor the refill threshold, nor the lanes without a finite
+            // inverse direction change while the wave walks, so they are formed once per round and not once per block; and a lane walks
+            // iff its reference is not DONE (set here for the lanes that do not walk, kept by the block), so the walking lanes are one
+            // compare into a scalar pair — the ballot of the bool carried across the loop was a select and a compare, twice a block.
+            constexpr bool HEAD = RT_R6_HEAD != 0;
+            if (HEAD && !in_trav) t_ref = DONE;
+            const uint32_t live_r = (uint32_t)__builtin_popcountll(__ballot(active));
+            const uint32_t refill_r = live_r * p.refill_eighths;
+            const unsigned long long nonfinite_r = __ballot(!aux.finite);
             for (;;) {
-                const uint32_t walking = (uint32_t)__builtin_popcountll(__ballot(in_trav));
-                const uint32_t live = (uint32_t)__builtin_popcountll(__ballot(active));     // (lanes without a unit idle in the loop)
-                if (walking == 0 || (walking * 8 <= live * p.refill_eighths && walking < live)) break;
-                if (in_trav && t_cnt > p.maxl - (uint32_t)STEPS) flush();          // room for a block of appends
+                const unsigned long long walk_m = HEAD ? __ballot(t_ref != DONE) : __ballot(in_trav);
+                uint32_t walking = (uint32_t)__builtin_popcountll(walk_m);
+                if (HEAD) asm("" : "+s"(walking));      // (a 32-bit scalar: left to itself the compiler compared the counts as 64-bit VECTORS)
+                const uint32_t live = HEAD ? live_r : (uint32_t)__builtin_popcountll(__ballot(active));     // (lanes without a unit idle in the loop)
+                if (walking == 0 || (walking * 8 <= (HEAD ? refill_r : live * p.refill_eighths) && walking < live)) break;
+                // room for a block of appends (ADDR: the list's length against the bound, both in bytes)
+                if (in_trav && (ADDR ? cnt_m - list0_m > (p.maxl - (uint32_t)STEPS) * SLOT : t_cnt > p.maxl - (uint32_t)STEPS)) flush();
                 // Partial rounds of root tests.  The flush after the walk runs as many rounds as the LONGEST list among the
                 // finished lanes, most of them at a handful of lanes (round 3 census: 4.0 rounds at 17.4 lanes per loop round,
                 // 18 % of the kernel's time for 1.34 candidates per query).  Here, between two blocks of steps, one candidate per
                 // lane — its oldest: list order is kept, the first minimum still wins — is tested as soon as RT_LT_PARTIAL lanes have
                 // one pending: 3.4 rounds at 21 lanes.
                 if (RT_LT_PARTIAL < 64) {
-                    const bool pend = t_cnt > t_head;
+                    const bool pend = ADDR ? cnt_m > head_m : t_cnt > t_head;
                     // (culled walk: a lane that has candidates but no hit yet cannot skip anything: such lanes are tested as soon as
                     // there are RT_LT_EAGER of them)
                     if ((int)__builtin_popcountll(__ballot(pend)) >= RT_LT_PARTIAL ||
@@ -1639,19 +1705,31 @@ __global__ __launch_bounds__(BS, (ISECT == 5 || ISECT == 6) ? RT_MINWAVES_LTREE 
                         if (pend) flush_one();
                     }
                 }
-                const bool slow = __ballot(in_trav && !aux.finite) != 0;         // wave-uniform
+                const bool slow = HEAD ? (walk_m & nonfinite_r) != 0ull : __ballot(in_trav && !aux.finite) != 0;         // wave-uniform
                 if (in_trav) {
+                    if (!ADDR) {
                     top_a = stack0_a + (t_sp - 1u) * SLOT;
                     cnt_m = list0_m + t_cnt * SLOT;
+                    }
+                    // (the two arms open with different barriers: shared, the loads and the slab arithmetic of step 1 were hoisted above the
+                    // branch, and the fast block's fmaxf then met operands it no longer knew to be canonical: six v_max_f32 x, x, x)
                     if (slow) {
+#if RT_R6_STEP1
+                        asm volatile("; slow block" ::: "memory");
+#endif
 #pragma unroll
                         for (int rep = 0; rep < STEPS; rep++) step(std::true_type{});
                     } else {
+#if RT_R6_STEP1
+                        asm volatile("; fast block" ::: "memory");
+#endif
 #pragma unroll
                         for (int rep = 0; rep < STEPS; rep++) step(std::false_type{});
                     }
+                    if (!ADDR) {
                     t_sp = (top_a + SLOT - stack0_a) / SLOT;       // (0 for a lane that finished: its pop of DONE went below slot 0)
                     t_cnt = (cnt_m - list0_m) / SLOT;
+                    }
                     in_trav = t_ref != DONE;
                 }
             }

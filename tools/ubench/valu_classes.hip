@@ -67,6 +67,9 @@ constexpr int ITER = 2048;
 #define I_SUBU(n) "v_sub_u32 %" #n ", %" #n ", %8\n"
 #define I_MADF(n) "v_mad_f32 %" #n ", %" #n ", %8, %9\n"
 #define I_MAD64(n) "v_mad_u64_u32 v[40:41], s[20:21], %" #n ", %8, v[40:41]\n"
+#define I_CNDSDWA(n) "v_cndmask_b32_sdwa %" #n ", %" #n ", %8, vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1\n"
+#define I_PAIRSDWA(n) "v_cmp_lt_f32 vcc, %" #n ", %8\n s_nop 1\n v_cndmask_b32_sdwa %" #n ", %" #n ", %9, vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1\n"
+#define I_MOVCND(n) "s_mov_b64 vcc, s[20:21]\n v_cndmask_b32_sdwa %" #n ", %" #n ", %8, vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0\n"
 
 template <int MODE>
 __global__ __launch_bounds__(256) void k(float* out, float a, float b) {
@@ -126,6 +129,9 @@ __global__ __launch_bounds__(256) void k(float* out, float a, float b) {
         if (MODE == 50) R8(I_PERM);
         if (MODE == 51) R8(I_MAXI16);
         if (MODE == 52) R8(I_SUBU);
+        if (MODE == 53) R8(I_CNDSDWA);
+        if (MODE == 54) R8(I_MOVCND);
+        if (MODE == 55) R8(I_PAIRSDWA);
     }
     out[blockIdx.x * blockDim.x + threadIdx.x] = x0 + x1 + x2 + x3 + x4 + x5 + x6 + x7;
 }
@@ -209,5 +215,11 @@ int main() {
     run<46>("v_pk_mul_f32 (dep chain)", d_out);
     run<47>("v_cmp_lt_u32 vcc", d_out);
     run<48>("v_subrev_f32", d_out);
+    // round 6: the select that takes one 16-bit half of its second source (the LDS-tree step's child reference): alone (vcc written by
+    // a scalar instruction before the loop, like the plain v_cndmask_b32 case above), behind the s_mov_b64 that brings its mask to vcc
+    // (two instructions per count) and behind the compare that writes vcc (three per count, to set against the plain pair above)
+    run<53>("v_cndmask_b32_sdwa word", d_out);
+    run<54>("s_mov vcc + cndmask_sdwa (x2 instr)", d_out);
+    run<55>("cmp+nop+cndmask_sdwa vcc (x3 instr)", d_out);
     return 0;
 }
