@@ -14,10 +14,12 @@ from .film_upsampler import FilmUpsampler
 from .film_robust import FilmRobust
 from .film_display import FilmDisplay
 from .frame_encoder import FrameEncoder
+from .film_bloom import FilmBloom
 
 __all__ = [
     "NeeRequest", "RT_NEE_LIGHT_ONLY", "RT_NEE_MIS", "RT_LIGHTS_AREA", "RT_LIGHTS_CONE", "RT_GLOSSY_BOUNCE", "RT_GLOSSY_MIS", "DIRECT_DTYPE", "DirectRequest", "BOUNCE_DTYPE", "BounceRequest", "RT_BOUNCE_SCATTERED", "RT_BOUNCE_EMITTED", "RT_BOUNCE_MISSED",
     "HIT_DTYPE", "RAY_DTYPE", "RT_HIT_NONE", "RT_FLAG_EXACT_SCAN", "RT_FLAG_NO_BVH_CULL", "RT_FLAG_NONE", "SPHERE_DTYPE", "TRIANGLE_DTYPE", "RtError", "TileRequest", "TileStats",
     "TraceRequest", "AovPlanes", "Camera", "aov_means", "DenoiseRequest", "denoise_scratch_bytes", "default_request", "Controller", "FrameContext", "ImageSlice", "RenderInfo", "RenderMeta", "RenderSettings", "Scene", "Slave",
     "World", "init", "render_frame_native", "Film", "FilmHistory", "FilmSampler", "FilmUpsampler", "FilmRobust", "FilmDisplay", "FrameEncoder",
+    "FilmBloom",
 ]

@@ -1,5 +1,5 @@
 """What the bindings of the private libraries (_film_lib.py, _history_lib.py, _sampler_lib.py, _upsample_lib.py, _robust_lib.py,
-_display_lib.py, and _jpeg_lib.py, whose library build.JPEG is held beside build.PRIVATE) share: one Binding each, which owns the status error, the check and the lazy load.
+_display_lib.py, and _jpeg_lib.py and _bloom_lib.py, whose libraries build.JPEG and build.BLOOM are held beside build.PRIVATE) share: one Binding each, which owns the status error, the check and the lazy load.
 
 A private library is a member of build.PRIVATE beside the product, no part of the tile ABI (include/rt_tile.h, _abi.py): every
 function of it returns an int status, and one of them, <prefix>_version(uint32_t*), reports the version its binding must match.  This

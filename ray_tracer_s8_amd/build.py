@@ -125,6 +125,10 @@ FILM, HISTORY, SAMPLER, UPSAMPLE, ROBUST, DISPLAY = PRIVATE.values()
 # build() leaves it to its binding (_jpeg_lib.py builds a missing one on load), the driver's build() and `python -m` make it.
 JPEG = _private("jpeg", ())
 
+# The bloom library (pyramid bloom of a linear frame, 4.33; rtb_*): held beside PRIVATE in the same way, and built by the same three
+# (_bloom_lib.py on load, the driver's build(), `python -m`).
+BLOOM = _private("bloom", ())
+
 
 def _product(extra: list[str] | None = None) -> Library:
     """The product as asked for NOW: RT_EXTRA_HIPCC_FLAGS (experiments only, e.g. -DRT_MAXC=12) is read at every call.  A prebuilt
@@ -221,5 +225,5 @@ def build_debug(force: bool = False, verbose: bool = False) -> Path:
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
     if not VARIANT:
-        for lib in (DEBUG, JPEG, *PRIVATE.values()):    # (the private ones were forced by build())
-            print(ensure(lib, force=lib is DEBUG or lib is JPEG, verbose=True))
+        for lib in (DEBUG, JPEG, BLOOM, *PRIVATE.values()):    # (the private ones were forced by build())
+            print(ensure(lib, force=lib in (DEBUG, JPEG, BLOOM), verbose=True))
