@@ -29,12 +29,15 @@ inline size_t strip_bytes(const rt_tile_request& rq) {
     return rq.divisions ? (size_t)(rq.height / rq.divisions) * rq.width * 3 : 0;
 }
 
-// Two requests of the same frame: every field but division_no and seed (rt_scene_render_tiles' batches, the cost memory's key).
+// Two requests of the same frame: every field but division_no and seed (rt_scene_render_tiles' batches, the cost memory's key).  A
+// knob that is NaN in both agrees — a request is of its own frame, so a single strip with a NaN knob is rendered (to NaN rays, as
+// the reference's camera gives them) and not refused as a batch that disagrees.
+inline bool same_knob(float a, float b) { return a == b || (a != a && b != b); }
 inline bool same_frame(const rt_tile_request& a, const rt_tile_request& b) {
     return a.width == b.width && a.height == b.height && a.divisions == b.divisions && a.spp == b.spp &&
-           a.max_bounces == b.max_bounces && a.aperture == b.aperture && a.focus_distance == b.focus_distance &&
-           a.fov == b.fov && a.focal_length == b.focal_length && a.t_min == b.t_min && a.t_max == b.t_max &&
-           a.flags == b.flags;
+           a.max_bounces == b.max_bounces && same_knob(a.aperture, b.aperture) && same_knob(a.focus_distance, b.focus_distance) &&
+           same_knob(a.fov, b.fov) && same_knob(a.focal_length, b.focal_length) && same_knob(a.t_min, b.t_min) &&
+           same_knob(a.t_max, b.t_max) && a.flags == b.flags;
 }
 
 // The strips a frame is cut into (rt_tile.h "Strip assignment").  The balanced assignments cut the frame into their OWN strips: at

@@ -1,5 +1,6 @@
 """The placed camera restated in numpy (include/rt_tile.h "placed camera"): the basis and the camera vectors of a pose in np.float32,
-one ufunc per rounding, and Camera::get_ray for a pose drawing from the oracle's RNG.  Test infrastructure: the product's own
+one ufunc per rounding, and Camera::get_ray for a pose drawing from the oracle's RNG (get_ray; ray_dots gives the two squared lengths
+the same steps normalise; rays_of / strip_rays the records of a strip).  Test infrastructure: the product's own
 arithmetic is csrc/rt_plan.h (host) and the kernels' camera arm (device)."""
 import ctypes
 import ctypes.util
@@ -26,8 +27,13 @@ def _cross(a, b):
                      f32(a[0] * b[1]) - f32(a[1] * b[0])], f32)
 
 
+def _dot3(a):
+    """glam's dot3 of a vector with itself: (x x + y y) + z z, every product and sum rounded."""
+    return f32(f32(f32(a[0] * a[0]) + f32(a[1] * a[1])) + f32(a[2] * a[2]))
+
+
 def _length(a):
-    return np.sqrt(f32(f32(f32(a[0] * a[0]) + f32(a[1] * a[1])) + f32(a[2] * a[2])))
+    return np.sqrt(_dot3(a))
 
 
 def basis(origin, target, up):
@@ -91,10 +97,9 @@ def _normalize_or_zero(a):
     return np.zeros(3, f32)
 
 
-def get_ray(oracle, cv, rq, x, y_cam, state):
-    """Camera::get_ray (camera.rs:109-129) of the camera vectors cv for pixel column x, camera row y_cam, drawing from `state`
-    (advanced in place): the UnitDisc pair, then the u and the v jitter.  Returns (o, d): the lens point and the direction handed to
-    ray_color."""
+def _ray_steps(oracle, cv, x, y_cam, state):
+    """Camera::get_ray (camera.rs:109-129) step by step; returns (o, d, dot1, dot2), dot1 and dot2 the two squared lengths the steps
+    normalise: of llc + u hor + v ver - org and of focal_point - o."""
     x1, x2 = (f32(t) for t in oracle.draw(state, 2))
     with np.errstate(all="ignore"):
         offset = ((x1 * cv["lens_u"]).astype(f32) + (x2 * cv["lens_v"]).astype(f32)).astype(f32)
@@ -106,27 +111,54 @@ def get_ray(oracle, cv, rq, x, y_cam, state):
         d1 = _normalize(_normalize_or_zero(t))
         focal_point = (cv["org"] + (cv["focus_distance"] * d1).astype(f32)).astype(f32)
         o = (cv["org"] + offset).astype(f32)
-        d = _normalize(_normalize_or_zero((focal_point - o).astype(f32)))
-    return o, d
+        pre = (focal_point - o).astype(f32)
+        d = _normalize(_normalize_or_zero(pre))
+        return o, d, _dot3(t), _dot3(pre)
 
 
-def strip_rays(oracle, rq, pose=None, begin=0, end=None):
-    """The camera rays of samples [begin, end) of every pixel of the request's strip under `pose` ((origin, target, up) or None), in
-    the record order of rt_scene_camera_rays: (rays as a RAY_DTYPE array, states (n, 4) uint64 after get_ray's draws)."""
+def get_ray(oracle, cv, rq, x, y_cam, state):
+    """Camera::get_ray (camera.rs:109-129) of the camera vectors cv for pixel column x, camera row y_cam, drawing from `state`
+    (advanced in place): the UnitDisc pair, then the u and the v jitter.  Returns (o, d): the lens point and the direction handed to
+    ray_color."""
+    return _ray_steps(oracle, cv, x, y_cam, state)[:2]
+
+
+def ray_dots(oracle, cv, rq, x, y_cam, state):
+    """The two squared lengths get_ray normalises for the same arguments (the operands of the device's two square roots before the
+    last): (dot1 of llc + u hor + v ver - org, dot2 of focal_point - o), float32 each.  `state` is advanced as by get_ray."""
+    return _ray_steps(oracle, cv, x, y_cam, state)[2:]
+
+
+def sample_state(oracle, rq, x, yg, s):
+    """The stream of sample s of pixel (x, global row yg) of the request's job: SmallRng::seed_from_u64(seed + 4 PHI ((yg W + x) S + s))."""
+    return oracle.seed_from_u64(oracle.sample_seed(rq.seed, yg * rq.width + x, rq.spp, s))
+
+
+def strip_records(rq, begin=0, end=None):
+    """(x, global row, sample) of every record of samples [begin, end) of the request's strip, in the record order of
+    rt_scene_camera_rays: pixel-major, sample-minor."""
     end = rq.spp if end is None else end
     hs = rq.height // rq.divisions
+    return [(x, hs * rq.division_no + yl, s) for yl in range(hs) for x in range(rq.width) for s in range(begin, end)]
+
+
+def rays_of(oracle, rq, pose, records, dots=False):
+    """The camera rays of `records` ((x, global row, sample) each) of the request under `pose` ((origin, target, up) or None): (rays as
+    a RAY_DTYPE array, states (n, 4) uint64 after get_ray's draws) and, with dots, an (n, 2) float32 array of ray_dots."""
     cv = camera_vectors(rq, *(pose if pose is not None else (None, None, None)))
-    n = hs * rq.width * (end - begin)
+    n = len(records)
     rays = np.zeros(n, oracle.RAY_DTYPE)
     states = np.zeros((n, 4), np.uint64)
-    i = 0
-    for yl in range(hs):
-        yg = hs * rq.division_no + yl
-        for x in range(rq.width):
-            for s in range(begin, end):
-                st = oracle.seed_from_u64(oracle.sample_seed(rq.seed, yg * rq.width + x, rq.spp, s))
-                o, d = get_ray(oracle, cv, rq, x, rq.height - 1 - yg, st)
-                rays[i] = (o[0], o[1], o[2], rq.t_min, d[0], d[1], d[2], rq.t_max)
-                states[i] = st
-                i += 1
-    return rays, states
+    dd = np.zeros((n, 2), f32)
+    for i, (x, yg, s) in enumerate(records):
+        st = sample_state(oracle, rq, x, yg, s)
+        o, d, dd[i, 0], dd[i, 1] = _ray_steps(oracle, cv, x, rq.height - 1 - yg, st)
+        rays[i] = (o[0], o[1], o[2], rq.t_min, d[0], d[1], d[2], rq.t_max)
+        states[i] = st
+    return (rays, states, dd) if dots else (rays, states)
+
+
+def strip_rays(oracle, rq, pose=None, begin=0, end=None, dots=False):
+    """The camera rays of samples [begin, end) of every pixel of the request's strip under `pose` ((origin, target, up) or None), in
+    the record order of rt_scene_camera_rays: (rays as a RAY_DTYPE array, states (n, 4) uint64 after get_ray's draws[, dots])."""
+    return rays_of(oracle, rq, pose, strip_records(rq, begin, end), dots)

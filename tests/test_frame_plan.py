@@ -157,6 +157,19 @@ def test_cost_memory_key(lib):
     assert m.usable(rq, None) and not m.usable(rq, ps)
 
 
+def test_a_request_with_a_nan_knob_is_of_its_own_frame(lib):
+    """same_frame is also what admits a batch of strips: a knob that is NaN in both requests agrees (a single strip with a NaN fov or
+    aperture is a frame of NaN rays, not a batch that disagrees with itself), and still differs from every number."""
+    nan = float("nan")
+    for knob in ("aperture", "focus_distance", "fov", "focal_length", "t_min", "t_max"):
+        m, rq, ps = Mem(lib), request(**{knob: nan}), pose()
+        m.remember(rq, ps, range(1, 13))
+        assert m.usable(rq, ps) and m.usable(request(**{knob: nan, "seed": 8}), ps), knob
+        assert not m.usable(request(), ps) and not m.usable(request(**{knob: 0.0}), ps), knob
+        other = "fov" if knob != "fov" else "aperture"
+        assert not m.usable(request(**{knob: nan, other: 0.75}), ps), knob
+
+
 def test_cost_memory_takes_only_a_measurement(lib):
     m, rq, ps = Mem(lib), request(), pose()
     m.remember(rq, ps, range(1, 13), counting_on=False)                # counting off
